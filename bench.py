@@ -8,7 +8,7 @@ dual scalar are reduced -- the work of `find_arb!(r, v)` + the scatter loops of 
 region.  At N > 1 every rank sweeps its own shard and the launch that folds a rank's partial rows also
 all-reduces the n_tokens+1 doubles {Ψ, acc} over xGMI (fall-back: one small RCCL all-reduce per step).
 
-    python bench.py [--gpus N --steps K --warmup W --workload config3 --scaling weak|strong]
+    python bench.py [--gpus N --steps K --warmup W --workload config3 --scaling weak|strong] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload scaling          # the reference's own benchmark grid (benchmark/scaling.jl), route! per point
 
@@ -391,6 +391,33 @@ def at_scale_leg(args, local_rank, m=8_000_000, n=256):
             "seconds": time.perf_counter() - t0}
 
 
+DUMP_BYTES = 64 * 10 ** 6     # files included: 4 KiB of it are kept for the .npy headers
+
+
+def dump_outputs(out_dir, sb):
+    """--dump-outputs: what the timed path computed in its LAST step, as a caller of that path receives it -- the step's
+    output vector (netflows Ψ and the dual value) and, for the materialising sweep, the trades Δ / Λ of this rank's pools
+    ([m, 2] each, segment order) -- one float64 DIR/<name>.npy per array.  Where the whole set exceeds DUMP_BYTES the trades
+    are a fixed sample of rows (seed 0, ascending, the row indices in trade_rows.npy).  The inputs are seeded
+    (workloads.py), so two builds run with the same arguments can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    last = sb.ring[(sb.ring_pos - 1) % len(sb.ring)] if sb.ring else sb.be     # --cold-only: the copy the last step swept
+    out = sb.out_t.cpu().numpy()
+    arrays = {"netflows": out[:sb.n].copy(), "dual_value": out[sb.n:].copy()}
+    if sb.materialize:
+        D, L = last.trades()
+        room = DUMP_BYTES - 4096 - sum(a.nbytes for a in arrays.values())
+        per_row = D.itemsize * (D.shape[1] + L.shape[1])
+        if D.shape[0] * per_row > room:
+            k = room // (per_row + 8)
+            rows = np.sort(np.random.default_rng(0).choice(D.shape[0], size=k, replace=False))
+            D, L = D[rows], L[rows]
+            arrays["trade_rows"] = rows.astype(np.float64)
+        arrays["trades_delta"], arrays["trades_lambda"] = D, L
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def synth_mod():
     from cfmmrouter_amd import synth
     return synth
@@ -483,7 +510,14 @@ def main():
                          "one host-pointer cfmm_find_arb over all N shards (PCIe-inclusive)")
     ap.add_argument("--devices", default="", help="--single-process: comma-separated HIP ordinals (default 0..N-1; an "
                                                   "ordinal may repeat to put several shards on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (netflows, dual value, trades; rank 0's "
+                         "shard at N > 1) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.workload == "scaling" or args.single_process):
+        ap.error("--dump-outputs writes the outputs of the timed find_arb! step: not with --workload scaling or --single-process")
     if args.rccl:
         args.collective = "rccl_library"
 
@@ -540,6 +574,8 @@ def main():
     # pass 1 -- THE timed region: K steps between barrier + synchronize (ShardBench.timed_pass), nothing else on the stream
     # or the host; the MAX over ranks is reported
     elapsed, _ = sb.timed_pass(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sb)
     elapsed = sb.max_over_ranks(elapsed)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * sb.m_rank * args.steps / elapsed

@@ -4,7 +4,8 @@
  *   world = N > 1:       forks N processes BEFORE any HIP call, rank r on GPU r; rank 0 draws the 128-byte id and writes it into
  *                        one pipe per peer -- what a launcher (MPI_Bcast, a Julia Distributed remotecall) does with it; every
  *                        rank holds 1/N of the market and must return the psi of the WHOLE market (needs N GPUs: the driver's
- *                        node, not the 1-GPU box; tests/test_c_abi_gpu.py runs it wherever it sees several GPUs).
+ *                        node, not the 1-GPU box; tests/test_c_abi_gpu.py runs it wherever it sees several GPUs);
+ *   world = 1 fork:      the launcher path of world = N with one forked rank (a node with one GPU).
  * Market: 40 000 ProductTwoCoin pools over 16 tokens from a fixed LCG; checked against the unsharded sweep of the same pools. */
 #include <math.h>
 #include <stdio.h>
@@ -95,7 +96,8 @@ int main(int argc, char** argv)
         Ai[2 * i + 1] = b;
     }
     for (int j = 0; j < N; ++j) v[j] = exp(0.3 * sin(1.7 * j));
-    if (world <= 1) {
+    const int forked = world > 1 || (argc > 2 && strcmp(argv[2], "fork") == 0);
+    if (!forked) {
         double psi_ref[N], acc_ref;
         unsigned char id[CFMM_RCCL_ID_BYTES];
         cfmm_ctx* ctx = NULL;
@@ -108,7 +110,7 @@ int main(int argc, char** argv)
      * "broadcast" a real launcher does with MPI_Bcast / a Distributed.jl remotecall */
     int pipes[64][2];
     pid_t kids[64];
-    if (world > 64) return 2;
+    if (world < 1 || world > 64) return 2;
     for (int r = 1; r < world; ++r)
         if (pipe(pipes[r]) != 0) return 2;
     for (int r = 0; r < world; ++r) {
@@ -130,7 +132,9 @@ int main(int argc, char** argv)
                 _exit(1);
             }
             (void)rank;
-            _exit(run_rank(r, world, id, psi_ref, acc_ref));
+            const int rc_rank = run_rank(r, world, id, psi_ref, acc_ref);
+            fflush(stdout);                                                         /* _exit does not flush stdio */
+            _exit(rc_rank);
         }
     }
     int rc = 0;

@@ -22,7 +22,7 @@ rank, world = dist.get_rank(), dist.get_world_size()
 if "--selftest-fail" in sys.argv:     # ONE rank reports a disagreement in the start-up check: all ranks must fall back
     os.environ["CFMM_AMD_PEER_SELFTEST_FAIL"] = "1"
 n = 512
-CONFIG4 = "--config4" in sys.argv      # BASELINE config 4 at its stated size: 4M ProductTwoCoin pools, 512 tokens, world = 8 shards
+CONFIG4 = "--config4" in sys.argv      # BASELINE config 4 at its stated size: 4M ProductTwoCoin pools, 512 tokens, one shard per rank
 if CONFIG4:
     from benchlib.workloads import build_market, objective_for
     market = build_market("config4", 0, 1, "weak")

@@ -29,13 +29,14 @@ def test_plain_c_client(tmp_path):
     assert "two token indices must differ" in out
 
 
-def test_plain_c_client_compiles():
+def test_plain_c_client_compiles(tmp_path):
     """CPU: the header is valid C11 and the client links against the library."""
     libdir = os.path.join(ROOT, "cfmmrouter.jl_amd")
+    exe = str(tmp_path / "abi_smoke_cpu")
     subprocess.run(["gcc", "-O1", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"),
-                    os.path.join(ROOT, "tests", "c", "abi_smoke.c"), "-o", "/tmp/abi_smoke_cpu", "-L", libdir,
+                    os.path.join(ROOT, "tests", "c", "abi_smoke.c"), "-o", exe, "-L", libdir,
                     "-lcfmm_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-lm"], check=True)
-    r = subprocess.run(["/tmp/abi_smoke_cpu"], capture_output=True, text=True, timeout=120)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     import torch
     if not torch.cuda.is_available():
         assert r.returncode == 2 and "no CPU fallback" in r.stderr      # fails loudly without a device
@@ -54,7 +55,7 @@ def _build_c(name, tmp_path):
 def test_rccl_all_reduce_from_a_plain_c_host(tmp_path):
     """north_star's collective -- "RCCL all-reduce of psi and grad g over xGMI per outer iteration" -- at the C ABI, from a
     process with no Python and no torch in it: cfmm_rccl_unique_id + cfmm_rccl_init_rank (world 1 on the 1-GPU box: the
-    communicator path end to end; tests/c/abi_rccl.c N forks N ranks on an N-GPU node), the global psi through
+    communicator path end to end; tests/c/abi_rccl.c N forks N ranks on an N-GPU node, up to 4), the global psi through
     ncclAllReduce on the context's stream, route! on the sharded context, cfmm_set_rccl_comm(NULL)."""
     exe = _build_c("abi_rccl", tmp_path)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -65,29 +66,29 @@ def test_rccl_all_reduce_from_a_plain_c_host(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.xfail(strict=False, reason="first contact with a multi-GPU node: this path has never crossed a physical xGMI link; a "
-                                        "failure is reported (XFAIL), a pass too (XPASS), neither stops the suite")
-def test_rccl_all_reduce_across_physical_gpus_if_there_are_several(tmp_path):
+def test_rccl_all_reduce_across_physical_gpus_if_there_are_several(tmp_path, request):
     """The same plain-C client with one rank per GPU (processes forked before any HIP call, the 128-byte id handed over through pipes): every
-    rank holds 1 / N of the market and must return the psi of the WHOLE market -- north_star's collective over xGMI.  Needs
-    N >= 2 GPUs: skipped on the 1-GPU box, runs wherever the suite meets a multi-GPU node."""
+    rank holds 1 / N of the market and must return the psi of the WHOLE market -- north_star's collective over xGMI.  At most 4
+    ranks: with this process they hold the node's GPUs, and a shared node takes at most six such processes.  A node with one GPU
+    runs the same launcher path with one forked rank (`abi_rccl 1 fork`): RCCL does not put two ranks on one device."""
     import torch
-    n_gpus = torch.cuda.device_count()
-    if n_gpus < 2:
-        pytest.skip("one GPU visible: the multi-rank RCCL run needs at least two")
-    world = min(n_gpus, 8)
+    world = max(1, min(torch.cuda.device_count(), 4))
+    if world > 1:
+        request.applymarker(pytest.mark.xfail(strict=False, reason="first contact with a multi-GPU node: this path has never crossed a "
+                                                               "physical xGMI link; a failure is reported (XFAIL), a pass too (XPASS), "
+                                                               "neither stops the suite"))
     exe = _build_c("abi_rccl", tmp_path)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([exe, str(world)], capture_output=True, text=True, timeout=600, env=env)
+    r = subprocess.run([exe, str(world)] + (["fork"] if world == 1 else []), capture_output=True, text=True, timeout=600, env=env)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0 and "RCCL_ABI_OK" in r.stdout
     assert r.stdout.count("rel err vs unsharded") == world
 
 
-def test_rccl_client_compiles():
+def test_rccl_client_compiles(tmp_path):
     """CPU: the RCCL client is valid C against the header and links against the library (no RCCL needed to link: it is
     resolved at first use)."""
-    exe = _build_c("abi_rccl", __import__("pathlib").Path("/tmp"))
+    exe = _build_c("abi_rccl", tmp_path)
     r = subprocess.run([exe, "1"], capture_output=True, text=True, timeout=120)
     import torch
     if not torch.cuda.is_available():

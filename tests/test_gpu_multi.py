@@ -3,6 +3,7 @@ src/router.jl:39) on the 1-GPU box: the device list repeats ordinal 0, so N shar
 stores, N streams and N host worker threads run on one MI355X -- everything but the physical
 placement is what an 8-GPU node executes."""
 import os
+import socket
 import subprocess
 import sys
 
@@ -16,6 +17,12 @@ from oracle import cfmm_oracle as orc
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
 
 
 @pytest.mark.parametrize("nd", [1, 2, 8])
@@ -179,15 +186,18 @@ def test_multi_context_rejects_device_pointer_calls():
         be.close()
 
 
-@pytest.mark.parametrize("world", [2, 4, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_peer_gather_protocol_with_several_ranks_on_one_gpu(world):
     """The sharded fold + all-reduce launch (cfmm_set_peers, reduce_gather) at world > 1 on ONE GPU
-    (tests/peer_ranks_worker.py): every "rank" is a context with its own stream and shard; ranks wait for
-    each other's granules exactly as over xGMI.  Run in a subprocess with one hardware queue per rank
-    (GPU_MAX_HW_QUEUES): ranks that shared a queue would serialise behind each other's waiting launch --
-    an artefact of emulating several GPUs on one, not of the protocol."""
-    env = dict(os.environ, GPU_MAX_HW_QUEUES=str(2 * world), CFMM_AMD_PEER_TIMEOUT_S="10")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "peer_ranks_worker.py"), str(world)],
-                       capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    (tests/peer_ranks_worker.py): every rank is a process with its own context, stream and shard; ranks wait for
+    each other's granules exactly as over xGMI.  One rank per process: every rank's stream needs a hardware queue
+    of its own (ranks that shared a queue would serialise behind each other's waiting launch -- an artefact of
+    emulating several GPUs on one, not of the protocol), and a process gets at most two queues on a shared GPU.
+    At most four ranks: with this process they are the five processes holding the GPU."""
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
+           "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "tests", "peer_ranks_worker.py")]
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", CFMM_AMD_PEER_TIMEOUT_S="10")
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     print(r.stdout[-2000:], r.stderr[-2000:])
-    assert r.returncode == 0 and f"PEER_RANKS_OK world={world}" in r.stdout
+    assert r.returncode == 0
+    assert all(f"PEER_RANKS_OK world={world} rank={k}" in r.stdout for k in range(world))

@@ -591,8 +591,6 @@ def test_route_parity_by_convergence(name, solver):
     pgtol -> 1e-9 do not do that: L-BFGS-B's line search compares dual VALUES, whose rounding noise (~1e-15 relative, a
     sum over 10^6 pools) hides the remaining decrease, and the run ends in ABNORMAL_TERMINATION_IN_LNSRCH at the same
     residual.  At default tolerances only a sanity bound is asserted."""
-    if solver == "scipy" and name not in ("config5_300k", "config4shard"):
-        pytest.skip("the SciPy-driven loop is exercised on two shapes; the library's own solver on all")
     n = 512 if name == "config4shard" else 256
     if name.startswith("config5"):
         market = [synth.bounded_product_pools(300_000 if name.endswith("300k") else 1_000_000, n, seed=1234, consistent=True)]
