@@ -22,7 +22,7 @@ ERR_HIP = -2
 ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 
-KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3 = 0, 1, 2
+KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED = 0, 1, 2, 3
 
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -107,6 +107,9 @@ def lib():
     L.cfmm_pools_add_product.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p]
     L.cfmm_pools_add_geomean.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _f64p, _i32p]
     L.cfmm_pools_add_univ3.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p, _i64p, _f64p, _f64p]
+    L.cfmm_pools_add_weighted.argtypes = [_ctx, C.c_int64, C.c_int32, _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_trades_len.argtypes = [_ctx]
+    L.cfmm_trades_len.restype = C.c_int64
     L.cfmm_pools_clear.argtypes = [_ctx]
     L.cfmm_pools_count.argtypes = [_ctx]
     L.cfmm_pools_count.restype = C.c_int64
@@ -260,6 +263,18 @@ class Context:
         self._check(self._L.cfmm_pools_add_univ3(self._h, m, ptr(current_price), ptr(gamma), ptr(Ai0),
                                                  ptr(tick_off), ptr(lower_ticks), ptr(liquidity)))
 
+    def add_weighted(self, R, w, gamma, Ai0):
+        """m weighted pools of n coins each: R, w, Ai0 [m, n] (cfmm_pools_add_weighted)."""
+        gamma = f64(gamma)
+        m = gamma.size
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        n = R.shape[1] if R.ndim == 2 else (R.size // m if m else 0)
+        R, w = f64(R), f64(w)
+        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
+        if R.size != n * m or w.size != n * m or Ai0.size != n * m:
+            raise ArgumentError("R, w and Ai must have shape [m, n_coins]")
+        self._check(self._L.cfmm_pools_add_weighted(self._h, m, int(n), ptr(R), ptr(w), ptr(gamma), ptr(Ai0)))
+
     def clear(self):
         self._check(self._L.cfmm_pools_clear(self._h))
 
@@ -283,10 +298,24 @@ class Context:
         self._check(self._L.cfmm_eval(self._h, ptr(v), ptr(psi), C.byref(acc)))
         return psi, acc.value
 
+    @property
+    def trades_len(self) -> int:
+        """Doubles per trade array: Σ over pools of their coin counts (cfmm_trades_len)."""
+        return int(self._L.cfmm_trades_len(self._h))
+
     def trades(self, out=None):
         """r.Δs / r.Λs of the latest materialising sweep as [m, 2] arrays (cfmm_get_trades).  `out` = (Δ, Λ): fill
-        caller-owned C-contiguous float64 arrays instead of allocating (what a binding that owns r.Δs / r.Λs does)."""
+        caller-owned C-contiguous float64 arrays instead of allocating (what a binding that owns r.Δs / r.Λs does).
+        A market with weighted pools of more than two coins has ragged trades: two flat arrays of trades_len doubles
+        (segment order, each pool's coins in Ai order)."""
         m = self.pool_count
+        tl = self.trades_len
+        if tl != 2 * m:
+            if out is not None:
+                raise ArgumentError("out arrays are not supported for ragged trades")
+            D, Lm = np.empty(tl), np.empty(tl)
+            self._check(self._L.cfmm_get_trades(self._h, ptr(D), ptr(Lm)))
+            return D, Lm
         if out is None:
             D, Lm = np.empty((m, 2)), np.empty((m, 2))
         else:
@@ -297,8 +326,8 @@ class Context:
         self._check(self._L.cfmm_get_trades(self._h, ptr(D), ptr(Lm)))
         return D, Lm
 
-    def trades_range(self, seg, first, count):
-        D, Lm = np.empty((count, 2)), np.empty((count, 2))
+    def trades_range(self, seg, first, count, n_coins=2):
+        D, Lm = np.empty((count, n_coins)), np.empty((count, n_coins))
         self._check(self._L.cfmm_get_trades_range(self._h, int(seg), int(first), int(count), ptr(D), ptr(Lm)))
         return D, Lm
 
@@ -339,8 +368,8 @@ class Context:
         """update_reserves!(r) on the device (cfmm_update_reserves): consumes the latest materialised trades."""
         self._check(self._L.cfmm_update_reserves(self._h))
 
-    def reserves(self, seg: int, m: int):
-        R = np.empty((int(m), 2))
+    def reserves(self, seg: int, m: int, n_coins: int = 2):
+        R = np.empty((int(m), int(n_coins)))
         self._check(self._L.cfmm_get_reserves(self._h, int(seg), ptr(R)))
         return R
 

@@ -6,6 +6,8 @@ tests written against the reference read the same here:
     ProductTwoCoin(R, γ, idx)                src/cfmms.jl:101-111
     GeometricMeanTwoCoin(R, w, γ, idx)       src/cfmms.jl:152-165
     UniV3(current_price, lower_ticks, liquidity, γ, Ai)   src/cfmms.jl:226-245
+    GeometricMean(R, w, γ, Ai), Product(R, γ, Ai)        src/cfmms.jl:57-64 (2..8 coins; the reference declares
+                                                         them without a find_arb!, the device solves them exactly)
 
 Token indices are 1-BASED, exactly as in the reference (`Ai[j]` is the global id of the pool's
 j-th coin); they are converted to 0-based int32 once, when a Router packs the pools for the
@@ -20,7 +22,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, ArgumentError
+from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
+
+MAX_COINS = 8   # sweep.h kMaxCoins
 
 
 class CFMM:
@@ -79,13 +83,74 @@ class GeometricMeanTwoCoin(CFMM):
         return PoolBatch(KIND_GEOMEAN, R=R, w=w, γ=γ, Ai=idx)
 
 
+def _n_coin_check_cast(R, γ, Ai, w=None):
+    R = np.array(R, dtype=np.float64).reshape(-1)
+    Ai = np.array(Ai).reshape(-1)
+    n = R.size
+    if Ai.size != n:
+        raise ArgumentError("length of Ai must equal length of R")
+    if not 2 <= n <= MAX_COINS:
+        raise ArgumentError(f"weighted pools have 2..{MAX_COINS} coins, got {n}")
+    if np.any(Ai < 0):
+        raise ArgumentError("Ai must be non-negative")
+    if np.unique(Ai).size != n:
+        raise ArgumentError("the token indices of a pool must be distinct")
+    if not np.all(np.isfinite(R)) or np.any(R <= 0):
+        raise ArgumentError("reserves must be finite and > 0")
+    γ = float(γ)
+    if not (0.0 < γ <= 1.0):
+        raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
+    if w is None:
+        w = np.full(n, 1.0 / n)
+    else:
+        w = np.array(w, dtype=np.float64).reshape(-1)
+        if w.size != n:
+            raise ArgumentError("length of w must equal length of R")
+        if not np.all(np.isfinite(w)) or np.any(w <= 0):
+            raise ArgumentError("weights must be finite and > 0")
+    return R, γ, Ai.astype(np.int64), w
+
+
+class GeometricMean(CFMM):
+    """GeometricMean(R, w, γ, Ai): φ(R) = Π R_i^{w_i}, 2..8 coins -- src/cfmms.jl:60-63.  Argument order of
+    GeometricMeanTwoCoin; the device normalises w to sum to 1 (same level sets, same trades)."""
+
+    kind = KIND_WEIGHTED
+
+    def __init__(self, R, w, γ, Ai):
+        self.R, self.γ, self.Ai, self.w = _n_coin_check_cast(R, γ, Ai, w)
+
+    gamma = property(lambda self: self.γ)
+
+    @staticmethod
+    def batch(R, w, γ, Ai):
+        return PoolBatch(KIND_WEIGHTED, R=R, w=w, γ=γ, Ai=Ai)
+
+
+class Product(GeometricMean):
+    """Product(R, γ, Ai): φ(R) = Π R_i, 2..8 coins -- src/cfmms.jl:56-58.  The equal-weight GeometricMean: Π R_i has the
+    level sets of Π R_i^{1/n}, so the trades are the same."""
+
+    def __init__(self, R, γ, Ai):
+        self.R, self.γ, self.Ai, self.w = _n_coin_check_cast(R, γ, Ai)
+
+    @staticmethod
+    def batch(R, γ, Ai):
+        R = np.asarray(R, dtype=np.float64)
+        return PoolBatch(KIND_WEIGHTED, R=R, w=np.full(R.shape, 1.0 / R.shape[-1]), γ=γ, Ai=Ai)
+
+
 def ϕ(cfmm, R=None):
     """ϕ(c::CFMM; R=nothing): the trading function -- src/cfmms.jl:36-42, :113-116 (ProductTwoCoin:
     R₁R₂), :167-171 (GeometricMeanTwoCoin: R₁^w₁ R₂^w₂).  The reference defines no method for UniV3.
     Host-side definition (O(1) per pool, used by the optimality tests, not by the sweep)."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean)):
         raise ArgumentError("ϕ has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, Product):
+        return float(np.prod(R))
+    if isinstance(cfmm, GeometricMean):
+        return float(np.prod(R ** cfmm.w))
     if isinstance(cfmm, ProductTwoCoin):
         return R[0] * R[1]
     if isinstance(cfmm, GeometricMeanTwoCoin):
@@ -96,9 +161,16 @@ def ϕ(cfmm, R=None):
 def ϕ_grad_(out, cfmm, R=None):
     """∇ϕ!(x, c::CFMM; R=nothing): gradient of the trading function, stored in `out` --
     src/cfmms.jl:44-50, :117-122, :172-178."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean)):
         raise ArgumentError("∇ϕ! has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, Product):
+        p = np.prod(R)
+        out[:] = p / R
+        return None
+    if isinstance(cfmm, GeometricMean):
+        out[:] = cfmm.w * np.prod(R ** cfmm.w) / R
+        return None
     if isinstance(cfmm, ProductTwoCoin):
         out[0], out[1] = R[1], R[0]
         return None
@@ -153,12 +225,16 @@ def BoundedProduct(current_price, p_lower, p_upper, liquidity, γ, Ai):
 class PoolBatch:
     """m pools of one family, structure-of-arrays (the HBM layout, on the host).
 
-    Ai is 1-based [m, 2] like the reference's per-pool `Ai`."""
+    Ai is 1-based [m, 2] like the reference's per-pool `Ai` ([m, n_coins] for KIND_WEIGHTED: R, w and Ai of one batch have
+    one coin count; pools with different coin counts go in different batches)."""
 
     def __init__(self, kind, **a):
         self.kind = kind
         self.γ = np.ascontiguousarray(a["γ"], dtype=np.float64).reshape(-1)
         m = self.γ.size
+        if kind == KIND_WEIGHTED:
+            self._init_weighted(m, a)
+            return
         self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, 2)
         if kind in (KIND_PRODUCT, KIND_GEOMEAN):
             self.R = np.ascontiguousarray(a["R"], dtype=np.float64).reshape(m, 2)
@@ -169,6 +245,28 @@ class PoolBatch:
             self.tick_off = np.ascontiguousarray(a["tick_off"], dtype=np.int64).reshape(m + 1)
             self.lower_ticks = np.ascontiguousarray(a["lower_ticks"], dtype=np.float64).reshape(-1)
             self.liquidity = np.ascontiguousarray(a["liquidity"], dtype=np.float64).reshape(-1)
+
+    def _init_weighted(self, m, a):
+        R = np.asarray(a["R"], dtype=np.float64)
+        n = R.shape[-1] if R.ndim == 2 else (R.size // m if m else 2)
+        if not 2 <= n <= MAX_COINS:
+            raise ArgumentError(f"weighted pools have 2..{MAX_COINS} coins, got {n}")
+        try:
+            self.R = np.ascontiguousarray(R).reshape(m, n)
+            self.w = np.ascontiguousarray(a["w"], dtype=np.float64).reshape(m, n)
+            self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, n)
+        except ValueError:
+            raise ArgumentError("R, w and Ai of a weighted batch must have shape [m, n_coins]") from None
+        if not np.all(np.isfinite(self.R)) or np.any(self.R <= 0):
+            raise ArgumentError("reserves must be finite and > 0")
+        if not np.all(np.isfinite(self.w)) or np.any(self.w <= 0):
+            raise ArgumentError("weights must be finite and > 0")
+        if np.any(~(self.γ > 0)) or np.any(self.γ > 1):
+            raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
+        if m and np.any(np.sort(self.Ai, axis=1)[:, 1:] == np.sort(self.Ai, axis=1)[:, :-1]):
+            raise ArgumentError("the token indices of a pool must be distinct")
+
+    n_coins = property(lambda self: self.Ai.shape[1])
 
     def __len__(self):
         return self.γ.size
@@ -183,6 +281,8 @@ class PoolBatch:
             return ProductTwoCoin(self.R[i], self.γ[i], self.Ai[i])
         if self.kind == KIND_GEOMEAN:
             return GeometricMeanTwoCoin(self.R[i], self.w[i], self.γ[i], self.Ai[i])
+        if self.kind == KIND_WEIGHTED:
+            return GeometricMean(self.R[i], self.w[i], self.γ[i], self.Ai[i])
         o, e = self.tick_off[i], self.tick_off[i + 1]
         return UniV3(self.current_price[i], self.lower_ticks[o:e], self.liquidity[o:e], self.γ[i], self.Ai[i])
 
@@ -190,7 +290,7 @@ class PoolBatch:
         """Pools [lo, hi) as a new batch (used to shard a market across GPUs)."""
         if self.kind == KIND_PRODUCT:
             return PoolBatch(self.kind, R=self.R[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
-        if self.kind == KIND_GEOMEAN:
+        if self.kind in (KIND_GEOMEAN, KIND_WEIGHTED):
             return PoolBatch(self.kind, R=self.R[lo:hi], w=self.w[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
         o, e = self.tick_off[lo], self.tick_off[hi]
         return PoolBatch(self.kind, current_price=self.current_price[lo:hi],
@@ -204,10 +304,12 @@ class PoolBatch:
         kind = batches[0].kind
         if any(b.kind != kind for b in batches):
             raise ArgumentError("concat needs batches of one pool family")
+        if kind == KIND_WEIGHTED and len({b.n_coins for b in batches}) > 1:
+            raise ArgumentError("concat needs weighted batches of one coin count")
         cat = lambda name: np.concatenate([getattr(b, name) for b in batches])
         if kind == KIND_PRODUCT:
             return PoolBatch(kind, R=cat("R"), γ=cat("γ"), Ai=cat("Ai"))
-        if kind == KIND_GEOMEAN:
+        if kind in (KIND_GEOMEAN, KIND_WEIGHTED):
             return PoolBatch(kind, R=cat("R"), w=cat("w"), γ=cat("γ"), Ai=cat("Ai"))
         off, base = [np.zeros(1, dtype=np.int64)], 0
         for b in batches:
@@ -221,6 +323,11 @@ class PoolBatch:
         if kind == KIND_PRODUCT:
             return PoolBatch(kind, R=[p.R for p in pools], γ=[p.γ for p in pools], Ai=[p.Ai for p in pools])
         if kind == KIND_GEOMEAN:
+            return PoolBatch(kind, R=[p.R for p in pools], w=[p.w for p in pools], γ=[p.γ for p in pools],
+                             Ai=[p.Ai for p in pools])
+        if kind == KIND_WEIGHTED:
+            if len({len(p.Ai) for p in pools}) > 1:
+                raise ArgumentError("one weighted batch holds pools of one coin count (group them by len(Ai))")
             return PoolBatch(kind, R=[p.R for p in pools], w=[p.w for p in pools], γ=[p.γ for p in pools],
                              Ai=[p.Ai for p in pools])
         off = np.zeros(len(pools) + 1, dtype=np.int64)
@@ -239,20 +346,21 @@ def zerotrade(c):
 def find_arb_(Δ, Λ, cfmm, v, device=0):
     """find_arb!(Δ, Λ, cfmm, v) -- src/cfmms.jl:35 and the methods at :130, :185, :339.
 
-    Solves one pool's arbitrage problem at local prices `v` (length 2) ON THE DEVICE and
+    Solves one pool's arbitrage problem at local prices `v` (length len(cfmm.Ai)) ON THE DEVICE and
     overwrites Δ and Λ.  Convenience for tests and examples; routers sweep all pools at once."""
     from ._lib import Context
 
-    v = np.asarray(v, dtype=np.float64).reshape(2)
-    ctx = Context(2, device)
+    n = len(cfmm.Ai)
+    v = np.asarray(v, dtype=np.float64).reshape(n)
+    ctx = Context(n, device)
     try:
         _upload(ctx, PoolBatch.from_pools(cfmm.kind, [_with_local_idx(cfmm)]))
         ctx.find_arb(v)
         D, Lm = ctx.trades()
     finally:
         ctx.close()
-    Δ[:] = D[0]
-    Λ[:] = Lm[0]
+    Δ[:] = np.ravel(D)[:n]
+    Λ[:] = np.ravel(Lm)[:n]
     return None
 
 
@@ -261,6 +369,8 @@ def _with_local_idx(c):
         return ProductTwoCoin(c.R, c.γ, [1, 2])
     if c.kind == KIND_GEOMEAN:
         return GeometricMeanTwoCoin(c.R, c.w, c.γ, [1, 2])
+    if c.kind == KIND_WEIGHTED:
+        return GeometricMean(c.R, c.w, c.γ, np.arange(1, len(c.Ai) + 1))
     return UniV3(c.current_price, c.lower_ticks, c.liquidity, c.γ, [1, 2])
 
 
@@ -273,6 +383,8 @@ def _upload(ctx, batch: PoolBatch):
         ctx.add_product(batch.R, batch.γ, Ai0)
     elif batch.kind == KIND_GEOMEAN:
         ctx.add_geomean(batch.R, batch.w, batch.γ, Ai0)
+    elif batch.kind == KIND_WEIGHTED:
+        ctx.add_weighted(batch.R, batch.w, batch.γ, Ai0)
     elif batch.kind == KIND_UNIV3:
         ctx.add_univ3(batch.current_price, batch.γ, Ai0, batch.tick_off, batch.lower_ticks, batch.liquidity)
     else:

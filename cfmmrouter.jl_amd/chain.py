@@ -12,6 +12,7 @@ One line per pool:
      "reserves": ["123..", "456.."], "fee_bps": 30}                                    Uniswap-v2 style pairs
     {"type": "weighted", "tokens": [...], "decimals": [...], "balances": [...],
      "weights": [0.8, 0.2], "fee": 0.001}                                              Balancer-style 2-token pools
+                                     (3..8 tokens: one GeometricMean batch per token count, weights normalised)
     {"type": "concentrated", "tokens": [token0, token1], "decimals": [d0, d1], "fee_pips": 3000,
      "sqrt_price_x96": "...", "liquidity": "...", "ticks": [[index, liquidity_net], ...]}   Uniswap-v3 style pools
 
@@ -36,7 +37,7 @@ from fractions import Fraction
 import numpy as np
 
 from ._lib import ArgumentError
-from .cfmms import GeometricMeanTwoCoin, ProductTwoCoin, UniV3
+from .cfmms import MAX_COINS, GeometricMean, GeometricMeanTwoCoin, ProductTwoCoin, UniV3
 
 Q96 = 1 << 96
 TICK_BASE = 1.0001
@@ -126,10 +127,13 @@ def load_snapshot(source):
             tokens.append(name)
         return index[name]
 
-    prod, geo, conc = [], [], []
+    prod, geo, conc, multi = [], [], [], {}
     for k, rec in enumerate(records):
         where = f"pool {k}"
         toks = rec.get("tokens")
+        if rec.get("type") == "weighted" and isinstance(toks, (list, tuple)) and 3 <= len(toks) <= MAX_COINS:
+            multi.setdefault(len(toks), []).append(_weighted_n(rec, toks, tid, where))
+            continue
         if not isinstance(toks, (list, tuple)) or len(toks) != 2 or toks[0] == toks[1]:
             raise ArgumentError(f"{where}: tokens must be two distinct identifiers")
         dec = rec.get("decimals", [18, 18])
@@ -164,4 +168,26 @@ def load_snapshot(source):
         np.cumsum([len(c[1]) for c in conc], out=off[1:])
         batches.append(UniV3.batch([c[0] for c in conc], off, np.concatenate([c[1] for c in conc]),
                                    np.concatenate([c[2] for c in conc]), [c[3] for c in conc], [c[4] for c in conc]))
+    for n in sorted(multi):   # 3..8-token weighted pools: one batch per coin count (GeometricMean, src/cfmms.jl:60-63)
+        pools = multi[n]
+        batches.append(GeometricMean.batch([p[0] for p in pools], [p[1] for p in pools], [p[2] for p in pools],
+                                           [p[3] for p in pools]))
     return tokens, batches
+
+
+def _weighted_n(rec, toks, tid, where):
+    """one weighted record with 3..8 tokens -> (R, w normalised, γ, Ai)"""
+    n = len(toks)
+    if len(set(toks)) != n:
+        raise ArgumentError(f"{where}: tokens must be distinct identifiers")
+    dec = rec.get("decimals", [18] * n)
+    if len(dec) != n:
+        raise ArgumentError(f"{where}: decimals must have {n} entries")
+    r, w = rec.get("balances"), [float(x) for x in rec.get("weights", ())]
+    if r is None or len(r) != n:
+        raise ArgumentError(f"{where}: balances must have {n} entries")
+    if len(w) != n or min(w) <= 0:
+        raise ArgumentError(f"{where}: {n} positive weights are needed")
+    g = _gamma(rec, where)
+    tot = sum(w)
+    return ([_amount(r[i], dec[i], where) for i in range(n)], [x / tot for x in w], g, [tid(t) for t in toks])

@@ -100,7 +100,7 @@ int multi_host_sweep(cfmm_ctx* c, const double* v, bool materialize)
 }
 
 // Run add(child, lo, hi) on every shard with a non-empty block [lo, hi) of the m pools; all or nothing.
-int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add)
+int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add, int n_coins)
 {
     if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
     if (m == 0) return CFMM_OK;
@@ -120,8 +120,10 @@ int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx
         }
         added.push_back(d);
     }
-    c->psegs.push_back({kind, m, c->m_total});
+    c->psegs.push_back({kind, m, c->m_total, n_coins, c->flat_total});
     c->m_total += m;
+    c->flat_total += m * n_coins;
+    c->any_weighted = c->any_weighted || kind == CFMM_KIND_WEIGHTED;
     c->have_out = c->have_trades = false;
     return CFMM_OK;
 }
@@ -145,6 +147,7 @@ int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t coun
     if (!c->have_trades) return fail(c, CFMM_ERR_STATE, "no materialised trades: call cfmm_find_arb first");
     if (seg < 0 || seg >= (int32_t)c->psegs.size()) return fail(c, CFMM_ERR_INVALID_ARG, "segment out of range");
     const int64_t m = c->psegs[(size_t)seg].m;
+    const int nc = c->psegs[(size_t)seg].n_coins;   // doubles per row (ragged layout: the segment's coin count)
     if (first < 0 || count < 0 || first + count > m) return fail(c, CFMM_ERR_INVALID_ARG, "row range out of bounds");
     const int nd = (int)c->shards.size();
     for (int d = 0; d < nd; ++d) {
@@ -154,8 +157,8 @@ int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t coun
         if (b <= a) continue;
         cfmm_ctx* child = c->shards[(size_t)d];
         const int rc = cfmm_get_trades_range(child, child_segment(c, seg, d), a - lo, b - a,
-                                             Delta ? Delta + 2 * (a - first) : nullptr,
-                                             Lambda ? Lambda + 2 * (a - first) : nullptr);
+                                             Delta ? Delta + nc * (a - first) : nullptr,
+                                             Lambda ? Lambda + nc * (a - first) : nullptr);
         if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s", d, child->err.c_str());
     }
     return CFMM_OK;

@@ -38,6 +38,13 @@ int fused_grid_cap(const cfmm_ctx* c, int block)
 // (and the fold kernel) small.  Large-market mode (global bins) uses 512-thread blocks throughout.
 void plan_segment(const cfmm_ctx* c, Segment& s)
 {
+    // weighted segments: their own launch of 512-thread blocks (sweep_weighted), never single-block direct
+    if (s.kind == CFMM_KIND_WEIGHTED) {
+        const int64_t tiles = std::max<int64_t>(1, (s.m + kMidBlock - 1) / kMidBlock);
+        s.block = kMidBlock;
+        s.grid = (int)std::min<int64_t>(tiles, c->opt_max_grid > 0 ? c->opt_max_grid : fat_grid_cap(c, kMidBlock));
+        return;
+    }
     // tiny single-family markets: ONE block, whose row is the result (SweepArgs::direct: no fold launch)
     if (c->opt_direct_small != 0 && c->segs.size() == 1 && s.m <= kDirectPools && !global_bins(c) && c->opt_block == 0 &&
         c->opt_max_grid == 0) {
@@ -194,55 +201,83 @@ namespace cfmm {
 int ensure_geometry(cfmm_ctx* c)
 {
     if (!c->geometry_dirty) return CFMM_OK;
-    int64_t rows = 0, trades = 0;
-    bool fusable = c->opt_fuse_segments != 0 && c->segs.size() >= 2 && c->opt_geomean_exact == 0;
+    int64_t rows = 0, trades = 0, pools = 0, flat = 0;
+    size_t n_two_coin = 0;
     bool any_big = false;
+    c->any_weighted = false;
     for (auto& s : c->segs) {
         plan_segment(c, s);
-        s.trade_off = trades;
-        trades += s.m;
-        any_big = any_big || s.block == kBigBlock;
+        const bool wt = s.kind == CFMM_KIND_WEIGHTED;
+        s.trade_off = trades;           // (weighted segments have no rows in the two-coin trade buffers)
+        s.flat_off = flat;
+        if (!wt) trades += s.m;
+        pools += s.m;
+        flat += s.m * (wt ? s.n_coins : 2);
+        if (!wt) ++n_two_coin;
+        c->any_weighted = c->any_weighted || wt;
+        any_big = any_big || (!wt && s.block == kBigBlock);
     }
     c->groups.clear();
-    if (fusable) {
-        // fused launches use 512-thread blocks (Product / GeoMean blocks interleave on every CU) unless asked otherwise
-        const int block = (any_big && c->opt_block == kBigBlock) ? kBigBlock : kMidBlock;
-        (void)any_big;
-        for (size_t first = 0; first < c->segs.size(); first += kMaxMulti) {
+    const bool fusable = c->opt_fuse_segments != 0 && n_two_coin >= 2 && c->opt_geomean_exact == 0;
+    // launch groups: every weighted segment alone (sweep_weighted); runs of consecutive two-coin segments fused by up to
+    // kMaxMulti (sweep_multi) or one launch each
+    for (size_t run = 0; run < c->segs.size();) {
+        if (c->segs[run].kind == CFMM_KIND_WEIGHTED) {
+            Segment& sg = c->segs[run];
             Group g;
-            g.first = (int)first;
-            g.nseg = (int)std::min<size_t>(kMaxMulti, c->segs.size() - first);
-            g.multi = g.nseg >= 2;
-            g.block = block;
-            int64_t tiles = 1;
-            for (int k = 0; k < g.nseg; ++k) {
-                Segment& sg = c->segs[first + k];
-                sg.block = block;
-                tiles = std::max<int64_t>(tiles, (sg.m + block - 1) / block);
-            }
-            const int64_t cap = std::max<int64_t>(
-                1, (c->opt_max_grid > 0 ? c->opt_max_grid : fused_grid_cap(c, block)) / g.nseg);
-            const int per_seg = (int)std::min<int64_t>(tiles, cap);
-            for (int k = 0; k < g.nseg; ++k) c->segs[first + k].grid = per_seg;
-            g.grid = per_seg * g.nseg;
-            plan_xcd_map(c, g);   // may re-divide the same number of blocks among the segments by cost
-            g.row_off = rows;
-            c->segs[first].row_off = rows;
-            rows += g.grid;
-            c->groups.push_back(g);
-        }
-    } else {
-        for (size_t i = 0; i < c->segs.size(); ++i) {
-            Segment& sg = c->segs[i];
-            Group g;
-            g.first = (int)i;
+            g.first = (int)run;
             g.block = sg.block;
             g.grid = sg.grid;
             g.row_off = rows;
             sg.row_off = rows;
             rows += sg.grid;
             c->groups.push_back(g);
+            ++run;
+            continue;
         }
+        size_t run_end = run;
+        while (run_end < c->segs.size() && c->segs[run_end].kind != CFMM_KIND_WEIGHTED) ++run_end;
+        if (fusable) {
+            // fused launches use 512-thread blocks (Product / GeoMean blocks interleave on every CU) unless asked otherwise
+            const int block = (any_big && c->opt_block == kBigBlock) ? kBigBlock : kMidBlock;
+            (void)any_big;
+            for (size_t first = run; first < run_end; first += kMaxMulti) {
+                Group g;
+                g.first = (int)first;
+                g.nseg = (int)std::min<size_t>(kMaxMulti, run_end - first);
+                g.multi = g.nseg >= 2;
+                g.block = block;
+                int64_t tiles = 1;
+                for (int k = 0; k < g.nseg; ++k) {
+                    Segment& sg = c->segs[first + k];
+                    sg.block = block;
+                    tiles = std::max<int64_t>(tiles, (sg.m + block - 1) / block);
+                }
+                const int64_t cap = std::max<int64_t>(
+                    1, (c->opt_max_grid > 0 ? c->opt_max_grid : fused_grid_cap(c, block)) / g.nseg);
+                const int per_seg = (int)std::min<int64_t>(tiles, cap);
+                for (int k = 0; k < g.nseg; ++k) c->segs[first + k].grid = per_seg;
+                g.grid = per_seg * g.nseg;
+                plan_xcd_map(c, g);   // may re-divide the same number of blocks among the segments by cost
+                g.row_off = rows;
+                c->segs[first].row_off = rows;
+                rows += g.grid;
+                c->groups.push_back(g);
+            }
+        } else {
+            for (size_t i = run; i < run_end; ++i) {
+                Segment& sg = c->segs[i];
+                Group g;
+                g.first = (int)i;
+                g.block = sg.block;
+                g.grid = sg.grid;
+                g.row_off = rows;
+                sg.row_off = rows;
+                rows += sg.grid;
+                c->groups.push_back(g);
+            }
+        }
+        run = run_end;
     }
     // fee tables of the launches: the packed records of a launch's segments index ONE table staged in LDS
     {
@@ -279,10 +314,14 @@ int ensure_geometry(cfmm_ctx* c)
         }
     }
     c->rows_total = rows;
-    c->m_total = trades;
+    c->m_total = pools;
+    c->trade_rows = trades;
+    c->flat_total = flat;
     c->touched_bytes = 0;
-    for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3)
-        c->touched_bytes += s.m * (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16 : (s.has_walk ? 104 : 56) + 16);
+    for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3);
+                                    // weighted: per coin R, q, w, token (28 B) + {γ, log γ} per pool, and 16 B per coin written
+        c->touched_bytes += s.m * (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
+                                            : s.kind == CFMM_KIND_WEIGHTED ? 44 * s.n_coins + 16 : (s.has_walk ? 104 : 56) + 16);
     if (rows > c->rows_cap) {
         (void)hipFree(c->d_partials);
         c->d_partials = nullptr;
@@ -291,7 +330,7 @@ int ensure_geometry(cfmm_ctx* c)
         HIP_TRY(c, hipMemset(c->d_partials, 0, (size_t)rows * row_width(c) * sizeof(double)));
         c->rows_cap = rows;
     }
-    if (trades > c->trade_cap) {
+    if (trades > c->trade_cap) {   // (two-coin rows only)
         (void)hipFree(c->d_delta); (void)hipFree(c->d_lambda); (void)hipFree(c->d_over);
         c->d_delta = c->d_lambda = c->d_over = nullptr;
         c->trade_cap = 0;
@@ -337,7 +376,8 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
     HIP_TRY(c, hipSetDevice(c->device));
     // a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
     // exchanges, and RCCL all-reduces d_out behind the fold)
-    const bool direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !gb && !sharded;
+    const bool direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !gb && !sharded &&
+                        c->segs[(size_t)c->groups[0].first].kind != CFMM_KIND_WEIGHTED;
     size_t group_index = 0;
     for (const Group& g : c->groups) {
         const size_t gi = group_index++;
@@ -350,9 +390,11 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
         a.gtab = c->d_gtab ? c->d_gtab + gi * kMaxFeeTable : nullptr;
         a.gtab_n = a.gtab ? g.gtab_n : 0;
         a.need_logv = 0;
-        if (!gb && c->opt_geomean_exact == 0)
-            for (int k = 0; k < g.nseg; ++k)
-                if (c->segs[(size_t)g.first + k].kind == CFMM_KIND_GEOMEAN) a.need_logv = 1;
+        if (!gb)
+            for (int k = 0; k < g.nseg; ++k) {
+                const int kind = c->segs[(size_t)g.first + k].kind;
+                if ((kind == CFMM_KIND_GEOMEAN && c->opt_geomean_exact == 0) || kind == CFMM_KIND_WEIGHTED) a.need_logv = 1;
+            }
         if (a.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, a.gtab_n, a.v_shift == 4 ? 1 : 0) > 160 * 1024)
             a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
         a.copies = bin_copies(c, g.block);
@@ -443,6 +485,11 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
             switch (s.kind) {
             case CFMM_KIND_PRODUCT: e = launch_sweep(product_of(s), a, cfg, materialize, c->stream); break;
             case CFMM_KIND_GEOMEAN: e = launch_sweep(geomean_of(s), a, cfg, materialize, c->stream); break;
+            case CFMM_KIND_WEIGHTED:
+                e = launch_sweep(WeightedPools{s.wR, s.wq, s.ww, s.wtok, s.glg, s.n_coins, materialize ? s.wD : nullptr,
+                                               materialize ? s.wL : nullptr},
+                                 a, cfg, materialize, c->stream);
+                break;
             default: e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream); break;
             }
         }

@@ -20,17 +20,17 @@ int expanded_trades(cfmm_ctx* c, const double2** dD, const double2** dL)
         *dL = c->d_lambda;
         return CFMM_OK;
     }
-    if (c->m_total > c->x_cap) {
+    if (c->trade_rows > c->x_cap) {
         (void)hipFree(c->d_xdelta); (void)hipFree(c->d_xlambda);
         c->d_xdelta = c->d_xlambda = nullptr;
         c->x_cap = 0;
         c->x_valid = false;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xdelta), (size_t)c->m_total * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xlambda), (size_t)c->m_total * sizeof(double2)));
-        c->x_cap = c->m_total;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xdelta), (size_t)c->trade_rows * sizeof(double2)));
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xlambda), (size_t)c->trade_rows * sizeof(double2)));
+        c->x_cap = c->trade_rows;
     }
     if (!c->x_valid && c->have_trades) {
-        hipError_t e = launch_expand_trades(c->d_delta, c->d_lambda, c->d_over, c->d_xdelta, c->d_xlambda, c->m_total, c->stream);
+        hipError_t e = launch_expand_trades(c->d_delta, c->d_lambda, c->d_over, c->d_xdelta, c->d_xlambda, c->trade_rows, c->stream);
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "expand launch failed: %s", hipGetErrorString(e));
         c->x_valid = true;
     }
@@ -120,6 +120,28 @@ int download_trades(cfmm_ctx* c, int64_t row0, int64_t count, double* Delta, dou
     return CFMM_OK;
 }
 
+// Rows [first, first + count) of a weighted segment's coin-major [n_coins][m] array, transposed into the caller's
+// [count][n_coins] rows (the reference's per-pool vectors, coins in Ai order).
+int download_coin_major(cfmm_ctx* c, const double* src, int64_t m, int nc, int64_t first, int64_t count, double* dst)
+{
+    if (!dst || count == 0) return CFMM_OK;
+    std::vector<double> col((size_t)count);
+    for (int k = 0; k < nc; ++k) {
+        HIP_TRY(c, hipMemcpy(col.data(), src + (size_t)k * (size_t)m + (size_t)first, (size_t)count * sizeof(double),
+                             hipMemcpyDeviceToHost));
+        for (int64_t i = 0; i < count; ++i) dst[(size_t)i * (size_t)nc + (size_t)k] = col[(size_t)i];
+    }
+    return CFMM_OK;
+}
+
+int download_segment(cfmm_ctx* c, const Segment& s, int64_t first, int64_t count, double* Delta, double* Lambda)
+{
+    if (s.kind != CFMM_KIND_WEIGHTED) return download_trades(c, s.trade_off + first, count, Delta, Lambda);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = download_coin_major(c, s.wD, s.m, s.n_coins, first, count, Delta);
+    return rc != CFMM_OK ? rc : download_coin_major(c, s.wL, s.m, s.n_coins, first, count, Lambda);
+}
+
 } // namespace
 
 namespace cfmm {
@@ -154,7 +176,7 @@ int cfmm_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t count
     if (first < 0 || count < 0 || first + count > s.m) return fail(c, CFMM_ERR_INVALID_ARG, "row range out of bounds");
     if (count == 0) return CFMM_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    return download_trades(c, s.trade_off + first, count, Delta, Lambda);
+    return download_segment(c, s, first, count, Delta, Lambda);
 }
 
 int cfmm_get_trades(cfmm_ctx* c, double* Delta, double* Lambda)
@@ -165,14 +187,29 @@ int cfmm_get_trades(cfmm_ctx* c, double* Delta, double* Lambda)
     if (!c->shards.empty()) {
         for (size_t k = 0; k < c->psegs.size(); ++k) {
             const auto& ps = c->psegs[k];
-            const int rc = multi_get_trades_range(c, (int32_t)k, 0, ps.m, Delta ? Delta + 2 * ps.trade_off : nullptr,
-                                                  Lambda ? Lambda + 2 * ps.trade_off : nullptr);
+            const int rc = multi_get_trades_range(c, (int32_t)k, 0, ps.m, Delta ? Delta + ps.flat_off : nullptr,
+                                                  Lambda ? Lambda + ps.flat_off : nullptr);
             if (rc != CFMM_OK) return rc;
         }
         return CFMM_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    return download_trades(c, 0, c->m_total, Delta, Lambda);
+    if (!c->any_weighted) return download_trades(c, 0, c->trade_rows, Delta, Lambda);
+    // ragged layout (cfmm_trades_len): segment after segment, n_coins doubles per pool
+    for (const Segment& s : c->segs) {
+        const int rc = download_segment(c, s, 0, s.m, Delta ? Delta + s.flat_off : nullptr, Lambda ? Lambda + s.flat_off : nullptr);
+        if (rc != CFMM_OK) return rc;
+    }
+    return CFMM_OK;
+}
+
+int64_t cfmm_trades_len(const cfmm_ctx* c)
+{
+    if (!c) return 0;
+    int64_t len = 0;
+    for (const Segment& s : c->segs) len += s.m * (s.kind == CFMM_KIND_WEIGHTED ? s.n_coins : 2);
+    for (const auto& ps : c->psegs) len += ps.m * ps.n_coins;
+    return len;
 }
 
 int cfmm_trades_dev(cfmm_ctx* c, const double** d_delta, const double** d_lambda)
@@ -181,6 +218,9 @@ int cfmm_trades_dev(cfmm_ctx* c, const double** d_delta, const double** d_lambda
     CFMM_SINGLE_ONLY(c, "cfmm_trades_dev");
     int rc = ensure_geometry(c);
     if (rc != CFMM_OK) return rc;
+    if (c->any_weighted)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "cfmm_trades_dev: the market has weighted pools, whose trades are ragged and kept "
+                                             "per segment (use cfmm_get_trades / cfmm_get_trades_range)");
     HIP_TRY(c, hipSetDevice(c->device));
     // device consumers get the reference's layout: the compact records of the latest materialising sweep are
     // expanded (asynchronously, on the context's stream) into {Δ₁, Δ₂} / {Λ₁, Λ₂} arrays -- call again after
@@ -263,6 +303,10 @@ int cfmm_update_reserves(cfmm_ctx* c)
     for (size_t k = 0; k < c->segs.size() && e == hipSuccess; ++k) {
         Segment& s = c->segs[k];
         if (s.kind == CFMM_KIND_UNIV3) continue;
+        if (s.kind == CFMM_KIND_WEIGHTED) {
+            e = launch_update_weighted(s.wR, s.wq, s.ww, s.glg, s.wD, s.wL, s.n_coins, s.m, c->stream);
+            continue;
+        }
         e = launch_update_two_coin(s.R, s.gamma, c->d_delta + s.trade_off, c->d_lambda + s.trade_off, c->d_over + s.trade_off,
                                    c->trades_compact, s.kind == CFMM_KIND_GEOMEAN ? s.lR : nullptr, s.eta, s.m, d_left + k, c->stream);
     }
@@ -306,7 +350,7 @@ int cfmm_get_reserves(cfmm_ctx* c, int32_t seg, double* R)
             int64_t lo, hi;
             shard_range(c->psegs[(size_t)seg].m, d, nd, lo, hi);
             if (hi == lo) continue;
-            const int rc = cfmm_get_reserves(c->shards[(size_t)d], child_segment(c, seg, d), R + 2 * lo);
+            const int rc = cfmm_get_reserves(c->shards[(size_t)d], child_segment(c, seg, d), R + c->psegs[(size_t)seg].n_coins * lo);
             if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s", d, c->shards[(size_t)d]->err.c_str());
         }
         return CFMM_OK;
@@ -316,6 +360,7 @@ int cfmm_get_reserves(cfmm_ctx* c, int32_t seg, double* R)
     if (s.kind == CFMM_KIND_UNIV3) return fail(c, CFMM_ERR_INVALID_ARG, "UniV3 segments have prices, not reserves: cfmm_get_prices");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (s.kind == CFMM_KIND_WEIGHTED) return download_coin_major(c, s.wR, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
     HIP_TRY(c, hipMemcpy(R, s.R, (size_t)s.m * sizeof(double2), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }

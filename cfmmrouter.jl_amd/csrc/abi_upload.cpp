@@ -164,6 +164,8 @@ void free_segment(Segment& s)
     (void)hipFree(s.cur_a); (void)hipFree(s.cur_b); (void)hipFree(s.cur_c); (void)hipFree(s.curR);
     (void)hipFree(s.pg); (void)hipFree(s.cp); (void)hipFree(s.walk); (void)hipFree(s.ticks); (void)hipFree(s.thr);
     (void)hipFree(s.head);
+    (void)hipFree(s.wR); (void)hipFree(s.wq); (void)hipFree(s.ww); (void)hipFree(s.wtok); (void)hipFree(s.glg);
+    (void)hipFree(s.wD); (void)hipFree(s.wL);
     s = Segment{};
 }
 
@@ -440,6 +442,80 @@ int cfmm_pools_add_univ3(cfmm_ctx* c, int64_t m, const double* current_price, co
     return add_segment_common(c, std::move(s), Ai);
 }
 
+int cfmm_pools_add_weighted(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* R, const double* w, const double* gamma,
+                            const int32_t* Ai)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
+    if (n_coins < 2 || n_coins > kMaxCoins)
+        return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: weighted pools have 2 .. %d coins", (int)n_coins, kMaxCoins);
+    if (c->n > kMaxLdsTokens)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "weighted pools need n_tokens <= %d (large-market mode sweeps two-coin pools only)",
+                    kMaxLdsTokens);
+    if (m > 0 && (!R || !w || !gamma || !Ai)) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
+    const int nc = n_coins;
+    for (int64_t i = 0; i < m; ++i) {
+        for (int k = 0; k < nc; ++k) {
+            const size_t j = (size_t)(i * nc + k);
+            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
+            if (!finite_pos(w[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: weights must be finite and > 0", (long long)i);
+            const int32_t a = Ai[j];
+            if (a < 0 || a >= c->n)
+                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: token index out of range [0, %d)", (long long)i, c->n);
+            for (int k2 = 0; k2 < k; ++k2)
+                if (Ai[(size_t)(i * nc + k2)] == a)
+                    return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the token indices must be distinct", (long long)i);
+        }
+        if (!finite_pos(gamma[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
+        if (gamma[i] > 1.0)
+            return fail(c, CFMM_ERR_INVALID_ARG,
+                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
+                        (long long)i);
+    }
+    if (!c->shards.empty())
+        return multi_add(c, CFMM_KIND_WEIGHTED, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
+            return cfmm_pools_add_weighted(child, hi - lo, n_coins, R + nc * lo, w + nc * lo, gamma + lo, Ai + nc * lo);
+        }, nc);
+    // coin-major columns (sweep.h WeightedPools), weights normalised to sum to 1, q = log(R / w)
+    const size_t cells = (size_t)m * (size_t)nc;
+    std::vector<double> cR(cells), cq(cells), cw(cells);
+    std::vector<int32_t> ct(cells);
+    std::vector<double2> glg((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        double ws = 0.0;
+        for (int k = 0; k < nc; ++k) ws += w[(size_t)(i * nc + k)];
+        for (int k = 0; k < nc; ++k) {
+            const size_t src = (size_t)(i * nc + k), dst = (size_t)k * (size_t)m + (size_t)i;
+            const double wn = w[src] / ws;
+            cR[dst] = R[src];
+            cw[dst] = wn;
+            cq[dst] = std::log(R[src] / wn);
+            ct[dst] = Ai[src];
+        }
+        glg[(size_t)i] = make_double2(gamma[i], std::log(gamma[i]));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    Segment s;
+    s.kind = CFMM_KIND_WEIGHTED;
+    s.m = m;
+    s.n_coins = nc;
+    s.fast_ok = 0;   // one arithmetic only (the compiler's)
+    int rc;
+    if ((rc = upload(c, &s.wR, cR.data(), cells)) || (rc = upload(c, &s.wq, cq.data(), cells)) ||
+        (rc = upload(c, &s.ww, cw.data(), cells)) || (rc = upload(c, &s.wtok, ct.data(), cells)) ||
+        (rc = upload(c, &s.glg, glg.data(), (size_t)m))) {
+        free_segment(s);
+        return rc;
+    }
+    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.wD), cells * sizeof(double)) != hipSuccess ||
+                      hipMalloc(reinterpret_cast<void**>(&s.wL), cells * sizeof(double)) != hipSuccess)) {
+        (void)hipGetLastError();
+        free_segment(s);
+        return fail(c, CFMM_ERR_HIP, "trade buffers of a weighted segment: allocation failed");
+    }
+    return add_segment_common(c, std::move(s), Ai);
+}
+
 int cfmm_pools_clear(cfmm_ctx* c)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
@@ -447,6 +523,8 @@ int cfmm_pools_clear(cfmm_ctx* c)
         for (cfmm_ctx* child : c->shards) cfmm_pools_clear(child);
         c->psegs.clear();
         c->m_total = 0;
+        c->flat_total = 0;
+        c->any_weighted = false;
         c->have_out = c->have_trades = false;
         return CFMM_OK;
     }
@@ -455,6 +533,8 @@ int cfmm_pools_clear(cfmm_ctx* c)
     for (auto& s : c->segs) free_segment(s);
     c->segs.clear();
     c->m_total = 0;
+    c->flat_total = 0;
+    c->any_weighted = false;
     c->rows_total = 0;
     c->geometry_dirty = true;
     c->have_out = c->have_trades = false;

@@ -33,7 +33,7 @@ namespace cfmm {
 struct Segment {
     int kind = 0;
     int64_t m = 0;
-    int64_t trade_off = 0; // first row of this segment in the trade buffers
+    int64_t trade_off = 0; // first row of this segment in the (two-coin) trade buffers
     int64_t n_ticks_total = 0;
     int fast_ok = 0; // every constant the sweep divides by / takes roots of lies in [2^-kFastExp, 2^kFastExp] (sweep.h)
     // device arrays (owned)
@@ -65,6 +65,17 @@ struct Segment {
     // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
     std::vector<double> h_cp, h_gamma, h_lt, h_liq;
     std::vector<int64_t> h_tick_off;
+    // Weighted (CFMM_KIND_WEIGHTED) only: coin-major [n_coins][m] columns (sweep.h WeightedPools) and the segment's own trade
+    // arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
+    int n_coins = 2;
+    int64_t flat_off = 0;      // first double of this segment in the ragged trade layout of cfmm_get_trades (Σ coins before it)
+    double* wR = nullptr;
+    double* wq = nullptr;
+    double* ww = nullptr;
+    int32_t* wtok = nullptr;
+    double2* glg = nullptr;    // [m] {γ, log γ}
+    double* wD = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
+    double* wL = nullptr;      // [n_coins][m] Λ
 };
 
 // A launch: either one segment (sweep_kernel) or up to kMaxMulti segments fused (sweep_multi).
@@ -118,6 +129,9 @@ struct cfmm_ctx {
     std::vector<cfmm::Segment> segs;
     std::vector<cfmm::Group> groups;
     int64_t m_total = 0;
+    int64_t trade_rows = 0;       // rows of the two-coin trade buffers (pools of the two-coin segments; weighted segments keep their own)
+    int64_t flat_total = 0;       // Σ over segments of m × coins: the length of each ragged trade array (cfmm_trades_len)
+    bool any_weighted = false;    // some segment is CFMM_KIND_WEIGHTED (its trades are ragged)
     int64_t touched_bytes = 0;    // what one materialising sweep moves by construction (packed layout; ensure_geometry): decides "stream_stores" = auto
     int64_t rows_total = 0;
 
@@ -223,7 +237,7 @@ struct cfmm_ctx {
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
     std::vector<cfmm_ctx*> shards;
-    struct ParentSeg { int kind; int64_t m; int64_t trade_off; };
+    struct ParentSeg { int kind; int64_t m; int64_t trade_off; int n_coins; int64_t flat_off; };   // flat_off: see Segment
     std::vector<ParentSeg> psegs;          // one per cfmm_pools_add_* call with m > 0
     std::unique_ptr<cfmm::Workers> workers;
     bool shards_distinct = true;           // no two shards share a device (pre-armed evaluations need that)
@@ -286,7 +300,7 @@ int armed_eval(cfmm_ctx* c, const double* v, bool* lost_out);      // single dev
 // abi_multi.cpp
 void shard_range(int64_t m, int d, int nd, int64_t& lo, int64_t& hi);
 int multi_host_sweep(cfmm_ctx* c, const double* v, bool materialize);
-int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add);
+int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add, int n_coins = 2);
 int child_segment(const cfmm_ctx* c, int pseg, int d);
 int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t count, double* Delta, double* Lambda);
 

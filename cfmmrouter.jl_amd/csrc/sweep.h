@@ -91,6 +91,22 @@ struct UniV3Pools {              // src/cfmms.jl:226-245 as find_arb_pos constan
     int gbase;
 };
 
+// N-coin weighted geometric-mean pools (GeometricMean / Product, src/cfmms.jl:57-64; sweep_weighted).  Per-coin columns
+// are COIN-MAJOR ([n_coins][m]: coin k of pool i at k·m + i), so the lanes of a wavefront (consecutive pools) load each
+// column as one coalesced stream.  Weights are normalised to sum to 1 at upload.
+constexpr int kMaxCoins = 8;
+struct WeightedPools {
+    const double* R;             // [n_coins][m] reserves
+    const double* q;             // [n_coins][m] log(R / w): the v-independent part of s^λ = log(R·v/w), prepared at upload and
+                                 //               by update_weighted
+    const double* w;             // [n_coins][m] normalised weights
+    const int32_t* tok;          // [n_coins][m] token indices, 0-based
+    const double2* glg;          // [m] {γ, log γ}
+    int n_coins;                 // 2 .. kMaxCoins, uniform over the segment
+    double* Delta;               // [n_coins][m] trades of a materialising sweep (null otherwise)
+    double* Lambda;
+};
+
 // How a fold launch hands {Ψ, acc} to the host (mapped pinned memory), if at all: gran != null -> the block's 8 columns
 // leave as 16 SELF-VALIDATING 8-byte granules {tag, 32 bits of the double} (two per column) written by one store
 // instruction = two full 64-byte lines; the host re-reads them until all carry the tag -- no drain of the output stores,
@@ -200,6 +216,14 @@ hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchC
                         hipStream_t s);
 hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
                         hipStream_t s);
+
+// Weighted segments are their own launch (kMidBlock threads, full-range arithmetic, never fused, never single-block direct):
+// a.Delta / a.Lambda / a.Over / a.gflow are unused (the trades go to p.Delta / p.Lambda).
+hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+                        hipStream_t s);
+// R <- (R + γΔ) − Λ per coin, in place, then q <- log(R / w)
+hipError_t launch_update_weighted(double* R, double* q, const double* w, const double2* glg, const double* Delta,
+                                  const double* Lambda, int n_coins, int64_t m, hipStream_t s);
 
 // block b writes partial row b (see sweep_multi for the block -> segment map); without xcd_map the grid must be a
 // multiple of ma.nseg.

@@ -6,6 +6,7 @@
 //   find_arb!(.., ::ProductTwoCoin)    src/cfmms.jl:125-140   -> ProductOps::solve
 //   find_arb!(.., ::GeometricMeanTwoCoin) src/cfmms.jl:180-196 -> GeoMeanLogOps::solve (default), GeoMeanOps::solve
 //   find_arb!(.., ::UniV3) + helpers   src/cfmms.jl:294-395   -> UniV3Ops::solve_dir
+//   GeometricMean / Product, N coins  src/cfmms.jl:57-64 (no find_arb! upstream) -> sweep_weighted / weighted_pool
 //   acc loop of fn                     src/router.jl:79-83    -> per-lane acc + wave shuffles
 //   scatter loop of g! / netflows!     src/router.jl:98-100, :111-119 -> LDS bins + reduce_partials
 //                                      (n_tokens > 8192: flow array + gather_chunks / token_fold)
@@ -1187,6 +1188,142 @@ __global__ __launch_bounds__(BLOCK) void sweep_multi(MultiArgs ma)
 }
 
 // ---------------------------------------------------------------------------------------------
+// N-coin weighted geometric-mean pools -- GeometricMean / Product, src/cfmms.jl:57-64 (no find_arb! there)
+// ---------------------------------------------------------------------------------------------
+// maximise Σ v_k(λ_k − δ_k) s.t. Π (R_k + γδ_k − λ_k)^{w_k} >= Π R_k^{w_k}, δ, λ >= 0 (the problem of the find_arb!
+// docstring, src/cfmms.jl:21-33).  With the multiplier μ = e^t the KKT conditions give, coin by coin,
+//     R_k'(t) = R_k · exp(min(0, t − s_k^λ) + max(0, t − s_k^δ)),   s_k^λ = log(R_k v_k / w_k),  s_k^δ = s_k^λ − log γ,
+// and t* is the root of the nondecreasing piecewise-linear G(t) = Σ w_k [min(0, t − s_k^λ) + max(0, t − s_k^δ)].
+// No trade iff max s^λ <= min s^δ (the fee band: every trade is exactly +0.0).  Otherwise G is evaluated at its 2N
+// breakpoints (no sort: N² clamp terms each), the root is bracketed by the largest breakpoint with G <= 0 and the smallest
+// with G >= 0, and G is linear in between: t* = lo − G(lo) / slope, the slope being the summed weight of the terms live
+// inside the bracket.  Trades: λ_k = −R_k·expm1(t* − s_k^λ) where t* < s_k^λ, δ_k = R_k·expm1(t* − s_k^δ) / γ where
+// t* > s_k^δ.  Per pool there is no logarithm: log v is staged per token (SweepLds::lv), q_k = log(R_k / w_k) and log γ
+// are prepared at upload.  N = 2 is the two-coin closed forms' problem (ProductTwoCoin at equal weights, GeometricMeanTwoCoin).
+// The coin count is a template argument of the per-pool code (registers sized for exactly N) and a segment-uniform
+// switch in the kernel.
+template <int N, bool MAT>
+__device__ __forceinline__ void weighted_pool(const WeightedPools& p, const SweepArgs& a, const SweepLds& L, int64_t i,
+                                              double& acc)
+{
+    const int64_t m = a.m;
+    double R[N], w[N], sl[N];   // (s^δ = s^λ − log γ and the prices are re-derived where needed: registers)
+    int tok[N];
+    const double2 gl = p.glg[i];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        R[k] = p.R[k * m + i];
+        w[k] = p.w[k * m + i];
+        sl[k] = p.q[k * m + i];
+        tok[k] = p.tok[k * m + i];
+    }
+    const char* base = reinterpret_cast<const char*>(L.vy);
+    double lmax = -__builtin_inf(), dmin = __builtin_inf(), wsum = 0.0;
+    bool nan_in = false;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        sl[k] += a.need_logv ? L.lv[tok[k]] : log(*reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift)));
+        nan_in = nan_in || sl[k] != sl[k];
+        lmax = __builtin_fmax(lmax, sl[k]);
+        dmin = __builtin_fmin(dmin, sl[k] - gl.y);
+        wsum += w[k];
+    }
+    if (!nan_in && lmax <= dmin) {   // inside the fee band: no trade
+        if (MAT) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                p.Delta[k * m + i] = 0.0;
+                p.Lambda[k * m + i] = 0.0;
+            }
+        }
+        return;
+    }
+    // bracket of the root of G among the 2N breakpoints
+    double lo = -__builtin_inf(), glo = 0.0, hi = __builtin_inf(), ghi = 0.0;
+#pragma unroll
+    for (int j = 0; j < 2 * N; ++j) {
+        const double b = j < N ? sl[j] : sl[j - N] - gl.y;
+        double G = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) G += w[k] * (__builtin_fmin(b - sl[k], 0.0) + __builtin_fmax(b - (sl[k] - gl.y), 0.0));
+        if (G <= 0.0 && b > lo) { lo = b; glo = G; }
+        if (G >= 0.0 && b < hi) { hi = b; ghi = G; }
+    }
+    double t;
+    if (lo == -__builtin_inf()) {
+        t = hi - ghi / wsum;            // below every breakpoint: every λ term live, slope Σw
+    } else if (hi == __builtin_inf()) {
+        t = lo - glo / wsum;            // above every breakpoint: every δ term live
+    } else if (glo == 0.0 || !(lo < hi)) {
+        t = glo == 0.0 ? lo : hi;       // a breakpoint is the root (or rounding crossed the bracket over)
+    } else {
+        const double mid = lo + 0.5 * (hi - lo);
+        double slope = 0.0;
+#pragma unroll
+        for (int k = 0; k < N; ++k) slope += (mid < sl[k] ? w[k] : 0.0) + (mid > sl[k] - gl.y ? w[k] : 0.0);
+        t = slope > 0.0 ? __builtin_fmin(__builtin_fmax(lo - glo / slope, lo), hi) : lo;
+    }
+    if (nan_in) t = __builtin_nan("");
+    const double rg = 1.0 / gl.x;
+    double sum_l = 0.0, sum_d = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const double lam = nan_in ? t : (t < sl[k] ? -(R[k] * expm1(t - sl[k])) : 0.0);
+        const double sd = sl[k] - gl.y;
+        const double del = nan_in ? t : (t > sd ? (R[k] * expm1(t - sd)) * rg : 0.0);
+        const double v = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
+        if (MAT) {
+            p.Delta[k * m + i] = del;
+            p.Lambda[k * m + i] = lam;
+        }
+        sum_l += lam * v;     // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
+        sum_d += del * v;
+        const double f = lam - del;   // src/router.jl:99  G[Ai] .+= Λ .- Δ
+        if (f != 0.0 || f != f) atomicAdd(&L.my_bins[tok[k]], f);
+    }
+    acc += sum_l - sum_d;
+}
+
+template <int N, bool MAT>
+__device__ __forceinline__ void weighted_tiles(const WeightedPools& p, const SweepArgs& a, const SweepLds& L, int64_t i,
+                                               int64_t step, int64_t left, double& acc)
+{
+    for (; left > 0; --left, i += step) weighted_pool<N, MAT>(p, a, L, i, acc);
+}
+
+// One launch per weighted segment; prologue (carve_lds, stage_prices: arm word, cancel, give-up report) and epilogue
+// (finish_row: the partial row reduce_partials / reduce_gather fold) are the other families' own.
+template <bool MAT>
+__global__ __launch_bounds__(kMidBlock) void sweep_weighted(WeightedPools p, SweepArgs a)
+{
+    constexpr int BLOCK = kMidBlock;
+    const SweepLds L = carve_lds<BLOCK, false>(a);
+    const int staged = stage_prices<BLOCK, false>(a, L);
+    const bool poison = (staged & kStageLive) == 0;
+    const bool live = !poison || (staged & kStageGaveUp) != 0;
+    if (staged & kStageGaveUp) report(a, kFlagGaveUp);
+    double acc = 0.0;
+    if (!poison) {
+        const int64_t stride = (int64_t)gridDim.x * BLOCK;
+        const int64_t i0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+        const int64_t left = i0 < a.m ? (a.m - i0 + stride - 1) / stride : 0;
+        const int64_t step = a.reverse ? -stride : stride;
+        const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
+        switch (p.n_coins) {
+        case 2: weighted_tiles<2, MAT>(p, a, L, i, step, left, acc); break;
+        case 3: weighted_tiles<3, MAT>(p, a, L, i, step, left, acc); break;
+        case 4: weighted_tiles<4, MAT>(p, a, L, i, step, left, acc); break;
+        case 5: weighted_tiles<5, MAT>(p, a, L, i, step, left, acc); break;
+        case 6: weighted_tiles<6, MAT>(p, a, L, i, step, left, acc); break;
+        case 7: weighted_tiles<7, MAT>(p, a, L, i, step, left, acc); break;
+        case 8: weighted_tiles<8, MAT>(p, a, L, i, step, left, acc); break;
+        default: break;
+        }
+    }
+    finish_row<BLOCK, false>(a, L, acc, (int)blockIdx.x, poison, live);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Row fold: out[j] = sum over rows of partials[row][j]  (src/router.jl:81-83, :98-100 summed over blocks)
 // ---------------------------------------------------------------------------------------------
 // One block owns kReduceCols adjacent columns (64 B = half a 128-byte line of every row; rows are 128-byte aligned,
@@ -1482,6 +1619,11 @@ hipError_t prepare_kernels(size_t max_lds_bytes)
 #undef CFMM_SETM4
 #undef CFMM_SETM
     hipError_t e;
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)max_lds_bytes)) != hipSuccess)
+        return e;
     if ((e = set_lds_attr<ProductOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<ProductOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<ProductOps, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
@@ -1623,6 +1765,40 @@ __global__ __launch_bounds__(256) void expand_trades(const double2* __restrict__
     read_trade(rec, ovA, ovB, 1, i, d, l);
     Delta[i] = d;
     Lambda[i] = l;
+}
+
+// update_reserves! for weighted segments: R <- (R + γΔ) − Λ per coin, q <- log(R / w) (the upload's expression)
+__global__ __launch_bounds__(256) void update_weighted(double* __restrict__ R, double* __restrict__ q, const double* __restrict__ w,
+                                                       const double2* __restrict__ glg, const double* __restrict__ Delta,
+                                                       const double* __restrict__ Lambda, int n_coins, long long m)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const double g = glg[i].x;
+    for (int k = 0; k < n_coins; ++k) {
+        const long long j = (long long)k * m + i;
+        const double rn = (R[j] + g * Delta[j]) - Lambda[j];
+        R[j] = rn;
+        q[j] = log(rn / w[j]);
+    }
+}
+
+hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+{
+    if (a.m <= 0) return hipSuccess;
+    dim3 g(c.grid), b(kMidBlock);
+    if (mat) launch_k(&sweep_weighted<true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    else launch_k(&sweep_weighted<false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_weighted(double* R, double* q, const double* w, const double2* glg, const double* Delta,
+                                  const double* Lambda, int n_coins, int64_t m, hipStream_t s)
+{
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(update_weighted, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, R, q, w, glg, Delta, Lambda,
+                       n_coins, (long long)m);
+    return hipGetLastError();
 }
 
 hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const double2* ovB, double2* Delta, double2* Lambda,

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, ArgumentError, CFMMDeviceError, Context
+from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
 from .cfmms import CFMM, PoolBatch, _upload
 
 
@@ -88,7 +88,12 @@ def _segments_of(cfmms):
         if idx:
             batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
             order.extend(idx)
-    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3)]
+    for n in range(2, 9):   # weighted pools: one batch (one device segment) per coin count
+        idx = [i for i, c in enumerate(cfmms) if c.kind == KIND_WEIGHTED and len(c.Ai) == n]
+        if idx:
+            batches.append(PoolBatch.from_pools(KIND_WEIGHTED, [cfmms[i] for i in idx]))
+            order.extend(idx)
+    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED)]
     for i in host:
         if not callable(getattr(cfmms[i], "find_arb_", None)) or not hasattr(cfmms[i], "Ai"):
             raise ArgumentError(f"cfmms[{i}] ({type(cfmms[i]).__name__}): a pool type without a device kernel needs its own "
@@ -215,17 +220,37 @@ class Router:
             self._backend = MixedBackend(self._backend, self._host)
         self._psi = np.zeros(self.n_tokens)
         self._acc = 0.0
-        self._Δs = np.zeros((self._m, 2))  # zerotrade per pool, :23-26
-        self._Λs = np.zeros((self._m, 2))
+        # weighted pools: r.Δs / r.Λs are per-pool vectors (the reference's ragged Vector{Vector}, src/router.jl:7-8)
+        self._ragged = any(b.kind == KIND_WEIGHTED for b in batches)
+        self._zero_trades()
         self._trades_stale = False
         self.n_sweeps = 0
         self.info = None
 
     # r.Δs / r.Λs: [m, 2] arrays in router order (rows are the reference's per-pool vectors); routers with host-evaluated
     # pools: a list of per-pool vectors in router order (the reference's Vector{Vector}), host pools' vectors included
+    def _zero_trades(self):
+        """zerotrade per pool, src/router.jl:23-26"""
+        if self._ragged:
+            self._Δs = [np.zeros(b.Ai.shape[1]) for b in self._batches for _ in range(len(b))]
+            self._Λs = [np.zeros(b.Ai.shape[1]) for b in self._batches for _ in range(len(b))]
+        else:
+            self._Δs = np.zeros((self._m, 2))
+            self._Λs = np.zeros((self._m, 2))
+
+    def _split(self, flat):
+        """the ragged flat trade layout of cfmm_get_trades (packed order) -> per-pool vectors"""
+        flat = np.ravel(flat)
+        sizes = np.concatenate([np.full(len(b), b.Ai.shape[1], dtype=np.int64) for b in self._batches if len(b)] or
+                               [np.zeros(0, dtype=np.int64)])
+        return np.split(flat, np.cumsum(sizes)[:-1]) if sizes.size else []
+
     def _fetch(self):
         if self._trades_stale:
-            if self._host is not None:        # packed order on the device; _rows() maps router index -> row
+            if self._ragged:                  # packed order on the device; _rows() maps router index -> pool vector
+                D, Lm = self._backend.trades()
+                self._Δs, self._Λs = self._split(D), self._split(Lm)
+            elif self._host is not None:        # packed order on the device; _rows() maps router index -> row        # packed order on the device; _rows() maps router index -> row
                 self._Δs, self._Λs = self._backend.trades()
             elif self._order is not None:
                 D, Lm = self._backend.trades()
@@ -238,7 +263,7 @@ class Router:
                     self._Δs, self._Λs = self._backend.trades()
             self._trades_stale = False
 
-    def _rows(self, dev, host):
+    def _rows(self, dev, host=()):
         out = [None] * (self._m + len(self._host_idx))
         for k, i in enumerate(self._order if self._order is not None else range(self._m)):
             out[int(i)] = dev[k]
@@ -249,11 +274,15 @@ class Router:
     @property
     def Δs(self):
         self._fetch()
+        if self._ragged:
+            return self._rows(self._Δs, self._host.Δs if self._host is not None else ())
         return self._Δs if self._host is None else self._rows(self._Δs, self._host.Δs)
 
     @property
     def Λs(self):
         self._fetch()
+        if self._ragged:
+            return self._rows(self._Λs, self._host.Λs if self._host is not None else ())
         return self._Λs if self._host is None else self._rows(self._Λs, self._host.Λs)
 
     Deltas = Δs
@@ -518,7 +547,7 @@ def netflows_(ψ, r: Router, exact=False):
         return None
     Δs, Λs = r.Δs, r.Λs
     ψ[:] = 0.0
-    if r._host is not None:                      # per-pool vectors of any length, router order
+    if r._host is not None or r._ragged:         # per-pool vectors of any length, router order
         for Δ, Λ, c in zip(Δs, Λs, r.cfmms):
             ai = np.asarray(c.Ai, dtype=np.int64).reshape(-1) - 1
             for k in range(ai.size):             # broadcast assignment, element after element
@@ -585,7 +614,7 @@ def update_reserves_(r: Router, sync_host=True):
             if b.kind == KIND_UNIV3:
                 b.current_price[:] = ctx.prices(seg, len(b))
             else:
-                b.R[:] = ctx.reserves(seg, len(b))
+                b.R[:] = ctx.reserves(seg, len(b), b.R.shape[1])
             seg += 1
         if isinstance(r.cfmms, list):                     # keep the per-pool objects in step
             it = iter(range(r._m)) if r._order is None else iter(r._order)
@@ -597,8 +626,7 @@ def update_reserves_(r: Router, sync_host=True):
                         pool.current_tick = int(np.count_nonzero(pool.lower_ticks >= pool.current_price))
                     else:
                         pool.R[:] = b.R[k]
-    r._Δs = np.zeros((r._m, 2))
-    r._Λs = np.zeros((r._m, 2))
+    r._zero_trades()
     r._psi = np.zeros(r.n_tokens)
     r._acc = 0.0
     r._trades_stale = False
@@ -608,6 +636,8 @@ def update_reserves_(r: Router, sync_host=True):
 def _update_reserves_host(r: Router):
     if any(b.kind == KIND_UNIV3 for b in r._batches):
         raise NotImplementedError("update_reserves! is not defined for UniV3 pools (nor in the reference)")
+    if r._ragged:
+        raise NotImplementedError("this backend cannot update weighted pools (the device context does: cfmm_update_reserves)")
     if not hasattr(getattr(r._backend, "inner", r._backend), "reload"):    # (MixedBackend forwards to its inner backend)
         raise NotImplementedError("this backend cannot reload pools")
     D, Lm = r._backend.trades()                       # packed (segment) order

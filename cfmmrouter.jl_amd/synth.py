@@ -10,12 +10,15 @@ generator this repo owns: SplitMix64 in counter mode, u(i) = mix(seed*GOLD + i*G
     Ai       = two distinct tokens, uniform (scaling.jl:22, sample(..., replace=false))
     c        = U[0,1)^n, floored at 2^-53   (scaling.jl:31; LinearNonnegative needs c > 0)
     w₁       = U(0,1), w₂ = 1 − w₁          (test/cfmms.jl:101)
+
+N-coin weighted pools (weighted_pools) have no distribution in the reference; they reuse the reserve and fee
+distributions, with weights 0.05 + U[0,1) normalised to sum to 1 and n_coins distinct uniform tokens.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3
+from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED
 from .cfmms import PoolBatch
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -188,3 +191,22 @@ def basket(n_tokens, seed=1234):
 def sweep_prices(n_tokens, seed=1234, spread=0.2):
     """A strictly positive price vector off the no-arbitrage manifold (for fixed-v sweeps)."""
     return np.exp(spread * (2.0 * uniform(seed, 60, n_tokens) - 1.0))
+
+
+def weighted_pools(m, n_tokens, n_coins, seed=1234, first=0):
+    """m weighted geometric-mean pools (KIND_WEIGHTED) of n_coins coins each: R = 1000·U² + 1e-3 per coin, weights
+    0.05 + U normalised, γ ∈ {0.997, 1.0}, n_coins distinct uniform 1-based tokens (sampled without replacement)."""
+    if not 2 <= n_coins <= min(8, n_tokens):
+        raise ValueError("need 2 <= n_coins <= min(8, n_tokens)")
+    R = np.stack([1000.0 * uniform(seed, 60 + k, m, first) ** 2 + 1e-3 for k in range(n_coins)], axis=1)
+    w = np.stack([0.05 + uniform(seed, 70 + k, m, first) for k in range(n_coins)], axis=1)
+    w /= w.sum(axis=1, keepdims=True)
+    γ = np.where(uniform(seed, 80, m, first) < 0.5, 0.997, 1.0)
+    Ai = np.empty((m, n_coins), dtype=np.int64)
+    for k in range(n_coins):   # the r-th token not chosen yet: r = floor(U·(n − k)), stepped past the chosen ones in order
+        r = np.minimum((uniform(seed, 90 + k, m, first) * (n_tokens - k)).astype(np.int64), n_tokens - k - 1)
+        chosen = np.sort(Ai[:, :k], axis=1)
+        for j in range(k):
+            r = r + (r >= chosen[:, j])
+        Ai[:, k] = r
+    return PoolBatch(KIND_WEIGHTED, R=R, w=w, γ=γ, Ai=Ai + 1)

@@ -41,6 +41,7 @@ extern "C" {
 #define CFMM_KIND_PRODUCT 0 /* ProductTwoCoin        src/cfmms.jl:101-140 */
 #define CFMM_KIND_GEOMEAN 1 /* GeometricMeanTwoCoin  src/cfmms.jl:152-196 */
 #define CFMM_KIND_UNIV3 2   /* UniV3/BoundedProduct  src/cfmms.jl:226-395 */
+#define CFMM_KIND_WEIGHTED 3 /* GeometricMean / Product with 2..8 coins  src/cfmms.jl:57-64 (no find_arb! there) */
 
 typedef struct cfmm_ctx cfmm_ctx;
 
@@ -166,6 +167,17 @@ int cfmm_pools_add_univ3(cfmm_ctx* ctx, int64_t m, const double* current_price, 
                          const int32_t* Ai, const int64_t* tick_off, const double* lower_ticks,
                          const double* liquidity);
 
+/* m x GeometricMean(R, w, gamma, Ai) with n_coins coins each -- src/cfmms.jl:57-64 (Product(R, gamma, Ai) = equal w:
+ * the same level sets, hence the same trades).  The reference declares these N-coin CFMMs but gives them no find_arb!;
+ * here the problem of its find_arb! docstring (src/cfmms.jl:21-33) is solved exactly per pool.
+ * R[m][n_coins] > 0, w[m][n_coins] > 0 (normalised to sum to 1 per pool), Ai[m][n_coins] distinct and in
+ * [0, n_tokens), 2 <= n_coins <= 8, and 0 < gamma <= 1: unlike the two-coin families, gamma > 1 is refused (a fee that pays
+ * for round trips makes the N-coin problem unbounded).  Every call is its own segment (batches with different coin counts
+ * go in separate calls) and its own launch: weighted segments are never fused with other families.  Trades are ragged:
+ * see cfmm_get_trades.  n_tokens > 8192 (large-market mode) returns CFMM_ERR_UNSUPPORTED. */
+int cfmm_pools_add_weighted(cfmm_ctx* ctx, int64_t m, int32_t n_coins, const double* R, const double* w,
+                            const double* gamma, const int32_t* Ai);
+
 int cfmm_pools_clear(cfmm_ctx* ctx);
 int64_t cfmm_pools_count(const cfmm_ctx* ctx); /* length(r.cfmms) */
 int32_t cfmm_n_tokens(const cfmm_ctx* ctx);    /* length(r.v) */
@@ -183,10 +195,13 @@ int cfmm_find_arb(cfmm_ctx* ctx, const double* v);
  * *acc_out = pool part of fn.  Either output pointer may be NULL. */
 int cfmm_eval(cfmm_ctx* ctx, const double* v, double* psi_out, double* acc_out);
 
-/* r.Δs / r.Λs after find_arb! -- src/router.jl:7-8,40.  [m_total][2] each, segment order.
- * Requires a preceding cfmm_find_arb (cfmm_eval does not produce trades). */
+/* r.Δs / r.Λs after find_arb! -- src/router.jl:7-8,40, flattened: cfmm_trades_len doubles each, segment order, each
+ * pool's coins in its Ai order (2 per two-coin pool, n_coins per weighted pool).  Without weighted pools that is exactly
+ * [m_total][2].  Requires a preceding cfmm_find_arb (cfmm_eval does not produce trades). */
 int cfmm_get_trades(cfmm_ctx* ctx, double* Delta, double* Lambda);
-/* Same, one segment: rows [first, first+count) of segment `seg`. */
+/* Length of each array cfmm_get_trades writes: the sum over pools of their coin counts. */
+int64_t cfmm_trades_len(const cfmm_ctx* ctx);
+/* Same, one segment: rows [first, first+count) of segment `seg` (count x n_coins doubles for a weighted segment). */
 int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t count, double* Delta,
                           double* Lambda);
 
@@ -196,6 +211,7 @@ int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t cou
  * src/cfmms.jl:26-31: the pool ends at R + γΔ − Λ), applied IN PLACE ON THE DEVICE from the trades of
  * the latest materialising sweep (cfmm_find_arb, cfmm_route; consumed by this call):
  *   ProductTwoCoin / GeometricMeanTwoCoin:  R <- (R + γΔ) − Λ            (one kernel, no host traffic)
+ *   weighted (CFMM_KIND_WEIGHTED):          R <- (R + γΔ) − Λ per coin    (one kernel, no host traffic)
  *   UniV3 / BoundedProduct: the state is the price.  A pool that traded moves to the internal price
  *     P = p/γ (price falling, src/cfmms.jl:361) or γ·p (price rising, :381), p = v₁/v₂, clamped to the
  *     first tick's upper price; its tick constants are re-derived as at upload (:294-313).  That is
@@ -203,7 +219,7 @@ int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t cou
  *     materialising sweep must have been a host-pointer call.
  * Afterwards a sweep at the same prices finds no arbitrage in any pool. */
 int cfmm_update_reserves(cfmm_ctx* ctx);
-/* Current reserves R[m][2] of a two-coin segment / current prices [m] of a UniV3 segment. */
+/* Current reserves R[m][2] of a two-coin segment (R[m][n_coins] of a weighted one) / current prices [m] of a UniV3 segment. */
 int cfmm_get_reserves(cfmm_ctx* ctx, int32_t seg, double* R);
 int cfmm_get_prices(cfmm_ctx* ctx, int32_t seg, double* current_price);
 
@@ -228,6 +244,7 @@ int cfmm_sweep_dev(cfmm_ctx* ctx, const double* d_v, double* d_out, int material
 /* Device addresses of the trade rows of the latest materialising sweep ([m_total][2] doubles each, the
  * reference's Delta / Lambda layout), valid until pools change.  With "compact_trades" (default) these
  * are expanded copies written on the context's stream by this call: call it again after a later sweep. */
+/* Markets with weighted pools: CFMM_ERR_UNSUPPORTED (their trades are ragged and stay per segment; cfmm_get_trades). */
 int cfmm_trades_dev(cfmm_ctx* ctx, const double** d_delta, const double** d_lambda);
 
 /* With option "time_kernels"=1 every sweep launch is bracketed by hipEvents on the launch

@@ -16,7 +16,7 @@
 module CFMMRouterAMD
 
 using CFMMRouter
-using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective
+using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, Product, GeometricMean
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
 
@@ -110,6 +110,18 @@ function build_router(objective::O, cfmms::Vector{C}, n_tokens, ctx::Ptr{Cvoid})
             ctx, length(idx), cp, γ, Ai, off, ticks, liq))
         append!(order, idx)
     end
+    # --- N-coin GeometricMean / Product pools (src/cfmms.jl:56-63): one weighted segment per coin count ---
+    for n in 2:8
+        idx = findall(c -> (c isa GeometricMean || c isa Product) && length(c.Ai) == n, cfmms)
+        isempty(idx) && continue
+        R = Float64[c.R[j] for j in 1:n, c in cfmms[idx]]            # n×m column-major == [m][n] row-major
+        w = Float64[c isa Product ? 1.0 : c.w[j] for j in 1:n, c in cfmms[idx]]   # Product: equal weights
+        γ = Float64[c.γ for c in cfmms[idx]]
+        Ai = Int32[c.Ai[j] - 1 for j in 1:n, c in cfmms[idx]]
+        GC.@preserve R w γ Ai check(ctx, ccall((:cfmm_pools_add_weighted, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ctx, length(idx), Int32(n), R, w, γ, Ai))
+        append!(order, idx)
+    end
     # The reference's plugin seam (src/cfmms.jl:35,56; src/router.jl:40): a Router takes ANY CFMM{T} subtype that has a
     # find_arb!(Δ, Λ, cfmm, v) method.  Pools of such a type are not uploaded: every evaluation calls the user's own method
     # on the host and adds its (Λ − Δ) and dual term to what the device returns (host_part! below).
@@ -138,16 +150,26 @@ function host_part!(r::AMDRouter, v)
     return nothing
 end
 
+# r.Δs / r.Λs from the device (cfmm_get_trades): flat, segment after segment, length(c.Ai) values per pool -- r.order lists
+# the pools in that segment order
+function fetch_trades!(r::AMDRouter)
+    len = ccall((:cfmm_trades_len, LIB), Int64, (Ptr{Cvoid},), r.ctx)
+    D = Vector{Float64}(undef, len); L = Vector{Float64}(undef, len)
+    GC.@preserve D L check(r.ctx, ccall((:cfmm_get_trades, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), r.ctx, D, L))
+    off = 0
+    for i in r.order
+        n = length(r.cfmms[i].Ai)
+        r.Δs[i] .= @view D[off+1:off+n]; r.Λs[i] .= @view L[off+1:off+n]
+        off += n
+    end
+    return nothing
+end
+
 # find_arb!(r::Router, v) -- src/router.jl:38-42: materialising device sweep, then r.Δs/r.Λs are filled
 function find_arb!(r::AMDRouter, v)
     vv = Vector{Float64}(v)
     GC.@preserve vv check(r.ctx, ccall((:cfmm_find_arb, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), r.ctx, vv))
-    m = length(r.order)
-    D = Matrix{Float64}(undef, 2, m); L = Matrix{Float64}(undef, 2, m)
-    GC.@preserve D L check(r.ctx, ccall((:cfmm_get_trades, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), r.ctx, D, L))
-    for (k, i) in enumerate(r.order)
-        r.Δs[i] .= @view D[:, k]; r.Λs[i] .= @view L[:, k]
-    end
+    fetch_trades!(r)
     check(r.ctx, ccall((:cfmm_netflows, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}), r.ctx, r.Ψ))
     check(r.ctx, ccall((:cfmm_dual_value, LIB), Cint, (Ptr{Cvoid}, Ref{Float64}), r.ctx, r.acc))
     host_part!(r, vv)
@@ -230,6 +252,16 @@ function update_reserves!(r::AMDRouter; sync::Bool=true)
             end
             seg += Int32(1); pos += length(idx)
         end
+        for n in 2:8     # weighted segments follow, one per coin count (build_router)
+            idx = [i for i in r.order[pos+1:end] if (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product) && length(r.cfmms[i].Ai) == n]
+            isempty(idx) && continue
+            R = Matrix{Float64}(undef, n, length(idx))
+            GC.@preserve R check(r.ctx, ccall((:cfmm_get_reserves, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, R))
+            for (k, i) in enumerate(idx)
+                r.cfmms[i].R .= @view R[:, k]
+            end
+            seg += Int32(1); pos += length(idx)
+        end
     end
     foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
     return nothing
@@ -269,12 +301,7 @@ function route_native!(r::AMDRouter; v=nothing, m=5, factr=1e1, pgtol=1e-5, maxf
         vout, r.Ψ, info))
     r.v .= vout
     # trades were materialised at v* by the same call
-    mm = length(r.order)
-    D = Matrix{Float64}(undef, 2, mm); L = Matrix{Float64}(undef, 2, mm)
-    GC.@preserve D L check(r.ctx, ccall((:cfmm_get_trades, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), r.ctx, D, L))
-    for (k, i) in enumerate(r.order)
-        r.Δs[i] .= @view D[:, k]; r.Λs[i] .= @view L[:, k]
-    end
+    fetch_trades!(r)
     return info[]
 end
 
@@ -305,12 +332,7 @@ function polish!(r::AMDRouter; max_iters=8, rel_step=1e-7)
         (Ptr{Cvoid}, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Float64, Ptr{Float64}, Ref{PolishInfo}),
         r.ctx, kind, vec, idx, vio, max_iters, rel_step, r.Ψ, info))
     r.v .= vio
-    mm = length(r.order)
-    D = Matrix{Float64}(undef, 2, mm); L = Matrix{Float64}(undef, 2, mm)
-    GC.@preserve D L check(r.ctx, ccall((:cfmm_get_trades, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), r.ctx, D, L))
-    for (k, i) in enumerate(r.order)
-        r.Δs[i] .= @view D[:, k]; r.Λs[i] .= @view L[:, k]
-    end
+    fetch_trades!(r)
     return info[]
 end
 
