@@ -5,8 +5,8 @@ src/router.jl:1-2).  Julia's `f!` is spelled `f_` here.  All pool arithmetic run
 through libcfmm_amd.so (include/cfmm_amd.h); there is no CPU fallback in this package.
 """
 from ._lib import ArgumentError, CFMMDeviceError, Context, build, lib
-from .cfmms import (CFMM, BoundedProduct, GeometricMean, GeometricMeanTwoCoin, PoolBatch, Product, ProductTwoCoin, UniV3,
-                    find_arb_ as _find_arb_pool,
+from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwoCoin, PoolBatch, Product, ProductTwoCoin,
+                    UniV3, find_arb_ as _find_arb_pool,
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
@@ -22,8 +22,8 @@ def find_arb_(*args, **kw):
 
 
 __all__ = [
-    "CFMM", "ProductTwoCoin", "GeometricMeanTwoCoin", "UniV3", "BoundedProduct", "GeometricMean", "Product", "PoolBatch",
-    "find_arb_",
+    "CFMM", "ProductTwoCoin", "GeometricMeanTwoCoin", "UniV3", "BoundedProduct", "GeometricMean", "Product", "Curve",
+    "PoolBatch", "find_arb_",
     "update_reserves_", "Objective", "LinearNonnegative", "BasketLiquidation", "Swap", "f", "grad_",
     "lower_limit", "upper_limit", "Router", "route_", "netflows_", "netflows", "ArgumentError",
     "CFMMDeviceError", "Context", "DeviceBackend", "build", "lib", "zerotrade", "ϕ", "ϕ_grad_", "phi", "grad_phi_",

@@ -22,7 +22,7 @@ ERR_HIP = -2
 ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 
-KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED = 0, 1, 2, 3
+KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE = 0, 1, 2, 3, 4
 
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -108,6 +108,7 @@ def lib():
     L.cfmm_pools_add_geomean.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _f64p, _i32p]
     L.cfmm_pools_add_univ3.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p, _i64p, _f64p, _f64p]
     L.cfmm_pools_add_weighted.argtypes = [_ctx, C.c_int64, C.c_int32, _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_pools_add_curve.argtypes = [_ctx, C.c_int64, C.c_int32, _f64p, _f64p, _i32p, _f64p, _f64p]
     L.cfmm_trades_len.argtypes = [_ctx]
     L.cfmm_trades_len.restype = C.c_int64
     L.cfmm_pools_clear.argtypes = [_ctx]
@@ -274,6 +275,18 @@ class Context:
         if R.size != n * m or w.size != n * m or Ai0.size != n * m:
             raise ArgumentError("R, w and Ai must have shape [m, n_coins]")
         self._check(self._L.cfmm_pools_add_weighted(self._h, m, int(n), ptr(R), ptr(w), ptr(gamma), ptr(Ai0)))
+
+    def add_curve(self, R, gamma, Ai0, alpha, beta):
+        """m Curve pools of n coins each: R, Ai0 [m, n]; gamma, alpha, beta [m] (cfmm_pools_add_curve)."""
+        gamma, alpha, beta = f64(gamma), f64(alpha), f64(beta)
+        m = gamma.size
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        n = R.shape[1] if R.ndim == 2 else (R.size // m if m else 0)
+        R = f64(R)
+        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
+        if R.size != n * m or Ai0.size != n * m or alpha.size != m or beta.size != m:
+            raise ArgumentError("R and Ai must have shape [m, n_coins], gamma, alpha and beta shape [m]")
+        self._check(self._L.cfmm_pools_add_curve(self._h, m, int(n), ptr(R), ptr(gamma), ptr(Ai0), ptr(alpha), ptr(beta)))
 
     def clear(self):
         self._check(self._L.cfmm_pools_clear(self._h))

@@ -8,6 +8,8 @@ tests written against the reference read the same here:
     UniV3(current_price, lower_ticks, liquidity, γ, Ai)   src/cfmms.jl:226-245
     GeometricMean(R, w, γ, Ai), Product(R, γ, Ai)        src/cfmms.jl:57-64 (2..8 coins; the reference declares
                                                          them without a find_arb!, the device solves them exactly)
+    Curve(R, γ, Ai, α, β)                    src/cfmms.jl:66-70 (2..8 coins, φ = α·ΣR − β·ΠR⁻¹: StableSwap at
+                                             fixed D; no find_arb! in the reference either)
 
 Token indices are 1-BASED, exactly as in the reference (`Ai[j]` is the global id of the pool's
 j-th coin); they are converted to 0-based int32 once, when a Router packs the pools for the
@@ -22,7 +24,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
 
 MAX_COINS = 8   # sweep.h kMaxCoins
 
@@ -83,14 +85,14 @@ class GeometricMeanTwoCoin(CFMM):
         return PoolBatch(KIND_GEOMEAN, R=R, w=w, γ=γ, Ai=idx)
 
 
-def _n_coin_check_cast(R, γ, Ai, w=None):
+def _n_coin_check_cast(R, γ, Ai, w=None, family="weighted"):
     R = np.array(R, dtype=np.float64).reshape(-1)
     Ai = np.array(Ai).reshape(-1)
     n = R.size
     if Ai.size != n:
         raise ArgumentError("length of Ai must equal length of R")
     if not 2 <= n <= MAX_COINS:
-        raise ArgumentError(f"weighted pools have 2..{MAX_COINS} coins, got {n}")
+        raise ArgumentError(f"{family} pools have 2..{MAX_COINS} coins, got {n}")
     if np.any(Ai < 0):
         raise ArgumentError("Ai must be non-negative")
     if np.unique(Ai).size != n:
@@ -140,13 +142,44 @@ class Product(GeometricMean):
         return PoolBatch(KIND_WEIGHTED, R=R, w=np.full(R.shape, 1.0 / R.shape[-1]), γ=γ, Ai=Ai)
 
 
+def _curve_check_cast(α, β):
+    α, β = float(α), float(β)
+    if not (np.isfinite(α) and α >= 0.0):
+        raise ArgumentError("α must be finite and >= 0")
+    if not (np.isfinite(β) and β > 0.0):
+        raise ArgumentError("β must be finite and > 0")
+    return α, β
+
+
+class Curve(CFMM):
+    """Curve(R, γ, Ai, α, β): φ(R) = α·Σ R_i − β·Π R_i⁻¹, 2..8 coins -- src/cfmms.jl:66-70 (the fields of Curve{T}, in
+    the order of its default constructor).  Curve's StableSwap invariant with D held fixed: α = A·nⁿ, β = D^{n+1}/nⁿ
+    (chain.stableswap_params).  α = 0 trades exactly like Product."""
+
+    kind = KIND_CURVE
+
+    def __init__(self, R, γ, Ai, α, β):
+        self.R, self.γ, self.Ai, _ = _n_coin_check_cast(R, γ, Ai, family="Curve")
+        self.α, self.β = _curve_check_cast(α, β)
+
+    gamma = property(lambda self: self.γ)
+    alpha = property(lambda self: self.α)
+    beta = property(lambda self: self.β)
+
+    @staticmethod
+    def batch(R, γ, Ai, α, β):
+        return PoolBatch(KIND_CURVE, R=R, γ=γ, Ai=Ai, α=α, β=β)
+
+
 def ϕ(cfmm, R=None):
     """ϕ(c::CFMM; R=nothing): the trading function -- src/cfmms.jl:36-42, :113-116 (ProductTwoCoin:
     R₁R₂), :167-171 (GeometricMeanTwoCoin: R₁^w₁ R₂^w₂).  The reference defines no method for UniV3.
     Host-side definition (O(1) per pool, used by the optimality tests, not by the sweep)."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve)):
         raise ArgumentError("ϕ has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, Curve):
+        return float(cfmm.α * np.sum(R) - cfmm.β / np.prod(R))
     if isinstance(cfmm, Product):
         return float(np.prod(R))
     if isinstance(cfmm, GeometricMean):
@@ -161,9 +194,12 @@ def ϕ(cfmm, R=None):
 def ϕ_grad_(out, cfmm, R=None):
     """∇ϕ!(x, c::CFMM; R=nothing): gradient of the trading function, stored in `out` --
     src/cfmms.jl:44-50, :117-122, :172-178."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve)):
         raise ArgumentError("∇ϕ! has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, Curve):
+        out[:] = cfmm.α + cfmm.β / np.prod(R) / R
+        return None
     if isinstance(cfmm, Product):
         p = np.prod(R)
         out[:] = p / R
@@ -225,14 +261,14 @@ def BoundedProduct(current_price, p_lower, p_upper, liquidity, γ, Ai):
 class PoolBatch:
     """m pools of one family, structure-of-arrays (the HBM layout, on the host).
 
-    Ai is 1-based [m, 2] like the reference's per-pool `Ai` ([m, n_coins] for KIND_WEIGHTED: R, w and Ai of one batch have
-    one coin count; pools with different coin counts go in different batches)."""
+    Ai is 1-based [m, 2] like the reference's per-pool `Ai` ([m, n_coins] for KIND_WEIGHTED and KIND_CURVE: R, w and Ai of
+    one batch have one coin count; pools with different coin counts go in different batches)."""
 
     def __init__(self, kind, **a):
         self.kind = kind
         self.γ = np.ascontiguousarray(a["γ"], dtype=np.float64).reshape(-1)
         m = self.γ.size
-        if kind == KIND_WEIGHTED:
+        if kind in (KIND_WEIGHTED, KIND_CURVE):
             self._init_weighted(m, a)
             return
         self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, 2)
@@ -247,19 +283,32 @@ class PoolBatch:
             self.liquidity = np.ascontiguousarray(a["liquidity"], dtype=np.float64).reshape(-1)
 
     def _init_weighted(self, m, a):
+        """KIND_WEIGHTED (R, w, Ai [m, n]) and KIND_CURVE (R, Ai [m, n]; α, β [m])"""
+        curve = self.kind == KIND_CURVE
+        fam = "Curve" if curve else "weighted"
         R = np.asarray(a["R"], dtype=np.float64)
         n = R.shape[-1] if R.ndim == 2 else (R.size // m if m else 2)
         if not 2 <= n <= MAX_COINS:
-            raise ArgumentError(f"weighted pools have 2..{MAX_COINS} coins, got {n}")
+            raise ArgumentError(f"{fam} pools have 2..{MAX_COINS} coins, got {n}")
         try:
             self.R = np.ascontiguousarray(R).reshape(m, n)
-            self.w = np.ascontiguousarray(a["w"], dtype=np.float64).reshape(m, n)
+            if curve:
+                self.α = np.ascontiguousarray(a["α"], dtype=np.float64).reshape(m)
+                self.β = np.ascontiguousarray(a["β"], dtype=np.float64).reshape(m)
+            else:
+                self.w = np.ascontiguousarray(a["w"], dtype=np.float64).reshape(m, n)
             self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, n)
         except ValueError:
-            raise ArgumentError("R, w and Ai of a weighted batch must have shape [m, n_coins]") from None
+            raise ArgumentError(f"R{'' if curve else ', w'} and Ai of a {fam} batch must have shape [m, n_coins]"
+                                + (", α and β shape [m]" if curve else "")) from None
         if not np.all(np.isfinite(self.R)) or np.any(self.R <= 0):
             raise ArgumentError("reserves must be finite and > 0")
-        if not np.all(np.isfinite(self.w)) or np.any(self.w <= 0):
+        if curve:
+            if not np.all(np.isfinite(self.α)) or np.any(self.α < 0):
+                raise ArgumentError("α must be finite and >= 0")
+            if not np.all(np.isfinite(self.β)) or np.any(self.β <= 0):
+                raise ArgumentError("β must be finite and > 0")
+        elif not np.all(np.isfinite(self.w)) or np.any(self.w <= 0):
             raise ArgumentError("weights must be finite and > 0")
         if np.any(~(self.γ > 0)) or np.any(self.γ > 1):
             raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
@@ -283,6 +332,8 @@ class PoolBatch:
             return GeometricMeanTwoCoin(self.R[i], self.w[i], self.γ[i], self.Ai[i])
         if self.kind == KIND_WEIGHTED:
             return GeometricMean(self.R[i], self.w[i], self.γ[i], self.Ai[i])
+        if self.kind == KIND_CURVE:
+            return Curve(self.R[i], self.γ[i], self.Ai[i], self.α[i], self.β[i])
         o, e = self.tick_off[i], self.tick_off[i + 1]
         return UniV3(self.current_price[i], self.lower_ticks[o:e], self.liquidity[o:e], self.γ[i], self.Ai[i])
 
@@ -292,6 +343,8 @@ class PoolBatch:
             return PoolBatch(self.kind, R=self.R[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
         if self.kind in (KIND_GEOMEAN, KIND_WEIGHTED):
             return PoolBatch(self.kind, R=self.R[lo:hi], w=self.w[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
+        if self.kind == KIND_CURVE:
+            return PoolBatch(self.kind, R=self.R[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi], α=self.α[lo:hi], β=self.β[lo:hi])
         o, e = self.tick_off[lo], self.tick_off[hi]
         return PoolBatch(self.kind, current_price=self.current_price[lo:hi],
                          tick_off=self.tick_off[lo:hi + 1] - o, lower_ticks=self.lower_ticks[o:e],
@@ -304,13 +357,15 @@ class PoolBatch:
         kind = batches[0].kind
         if any(b.kind != kind for b in batches):
             raise ArgumentError("concat needs batches of one pool family")
-        if kind == KIND_WEIGHTED and len({b.n_coins for b in batches}) > 1:
-            raise ArgumentError("concat needs weighted batches of one coin count")
+        if kind in (KIND_WEIGHTED, KIND_CURVE) and len({b.n_coins for b in batches}) > 1:
+            raise ArgumentError("concat needs weighted / Curve batches of one coin count")
         cat = lambda name: np.concatenate([getattr(b, name) for b in batches])
         if kind == KIND_PRODUCT:
             return PoolBatch(kind, R=cat("R"), γ=cat("γ"), Ai=cat("Ai"))
         if kind in (KIND_GEOMEAN, KIND_WEIGHTED):
             return PoolBatch(kind, R=cat("R"), w=cat("w"), γ=cat("γ"), Ai=cat("Ai"))
+        if kind == KIND_CURVE:
+            return PoolBatch(kind, R=cat("R"), γ=cat("γ"), Ai=cat("Ai"), α=cat("α"), β=cat("β"))
         off, base = [np.zeros(1, dtype=np.int64)], 0
         for b in batches:
             off.append(b.tick_off[1:] + base)
@@ -330,6 +385,11 @@ class PoolBatch:
                 raise ArgumentError("one weighted batch holds pools of one coin count (group them by len(Ai))")
             return PoolBatch(kind, R=[p.R for p in pools], w=[p.w for p in pools], γ=[p.γ for p in pools],
                              Ai=[p.Ai for p in pools])
+        if kind == KIND_CURVE:
+            if len({len(p.Ai) for p in pools}) > 1:
+                raise ArgumentError("one Curve batch holds pools of one coin count (group them by len(Ai))")
+            return PoolBatch(kind, R=[p.R for p in pools], γ=[p.γ for p in pools], Ai=[p.Ai for p in pools],
+                             α=[p.α for p in pools], β=[p.β for p in pools])
         off = np.zeros(len(pools) + 1, dtype=np.int64)
         np.cumsum([p.lower_ticks.size for p in pools], out=off[1:])
         return PoolBatch(kind, current_price=[p.current_price for p in pools], tick_off=off,
@@ -371,6 +431,8 @@ def _with_local_idx(c):
         return GeometricMeanTwoCoin(c.R, c.w, c.γ, [1, 2])
     if c.kind == KIND_WEIGHTED:
         return GeometricMean(c.R, c.w, c.γ, np.arange(1, len(c.Ai) + 1))
+    if c.kind == KIND_CURVE:
+        return Curve(c.R, c.γ, np.arange(1, len(c.Ai) + 1), c.α, c.β)
     return UniV3(c.current_price, c.lower_ticks, c.liquidity, c.γ, [1, 2])
 
 
@@ -385,6 +447,8 @@ def _upload(ctx, batch: PoolBatch):
         ctx.add_geomean(batch.R, batch.w, batch.γ, Ai0)
     elif batch.kind == KIND_WEIGHTED:
         ctx.add_weighted(batch.R, batch.w, batch.γ, Ai0)
+    elif batch.kind == KIND_CURVE:
+        ctx.add_curve(batch.R, batch.γ, Ai0, batch.α, batch.β)
     elif batch.kind == KIND_UNIV3:
         ctx.add_univ3(batch.current_price, batch.γ, Ai0, batch.tick_off, batch.lower_ticks, batch.liquidity)
     else:

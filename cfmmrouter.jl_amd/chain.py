@@ -13,10 +13,18 @@ One line per pool:
     {"type": "weighted", "tokens": [...], "decimals": [...], "balances": [...],
      "weights": [0.8, 0.2], "fee": 0.001}                                              Balancer-style 2-token pools
                                      (3..8 tokens: one GeometricMean batch per token count, weights normalised)
+    {"type": "curve", "tokens": [...], "decimals": [...], "balances": [...], "A": 200,
+     "fee": 0.0004}                                                                     StableSwap pools, 2..8 tokens
     {"type": "concentrated", "tokens": [token0, token1], "decimals": [d0, d1], "fee_pips": 3000,
      "sqrt_price_x96": "...", "liquidity": "...", "ticks": [[index, liquidity_net], ...]}   Uniswap-v3 style pools
 
 Fees: exactly one of "fee" (fraction), "fee_bps" (1e-4) or "fee_pips" (1e-6); γ = 1 − fee.
+
+StableSwap -> the reference's `Curve(R, γ, Ai, α, β)` (src/cfmms.jl:66-70), one batch per token count: D is the
+invariant of the balances (StableSwap's Newton iteration, float64), α = A·nⁿ and β = D^{n+1}/nⁿ, so that
+φ(R) = α·ΣR − β·ΠR⁻¹ is the invariant with D held fixed.  "A" is the amplification coefficient itself (contracts that
+store A·nⁿ⁻¹ or A·100 must be converted by the caller).  The fee is charged on the input like every family here
+(γ = 1 − fee), not on the output as the contracts do (which also grows D).
 
 Concentrated liquidity -> the reference's `UniV3(current_price, lower_ticks, liquidity, γ, Ai)` (src/cfmms.jl:226-245):
   * price = amount of token1 per token0 = (sqrtPriceX96 / 2^96)², in human units × 10^(d0 − d1); the reference's
@@ -37,7 +45,7 @@ from fractions import Fraction
 import numpy as np
 
 from ._lib import ArgumentError
-from .cfmms import MAX_COINS, GeometricMean, GeometricMeanTwoCoin, ProductTwoCoin, UniV3
+from .cfmms import MAX_COINS, Curve, GeometricMean, GeometricMeanTwoCoin, ProductTwoCoin, UniV3
 
 Q96 = 1 << 96
 TICK_BASE = 1.0001
@@ -127,10 +135,14 @@ def load_snapshot(source):
             tokens.append(name)
         return index[name]
 
-    prod, geo, conc, multi = [], [], [], {}
+    prod, geo, conc, multi, curve = [], [], [], {}, {}
     for k, rec in enumerate(records):
         where = f"pool {k}"
         toks = rec.get("tokens")
+        if rec.get("type") == "curve":
+            c = _curve(rec, toks, tid, where)
+            curve.setdefault(len(c[0]), []).append(c)
+            continue
         if rec.get("type") == "weighted" and isinstance(toks, (list, tuple)) and 3 <= len(toks) <= MAX_COINS:
             multi.setdefault(len(toks), []).append(_weighted_n(rec, toks, tid, where))
             continue
@@ -172,7 +184,59 @@ def load_snapshot(source):
         pools = multi[n]
         batches.append(GeometricMean.batch([p[0] for p in pools], [p[1] for p in pools], [p[2] for p in pools],
                                            [p[3] for p in pools]))
+    for n in sorted(curve):   # StableSwap pools: one Curve batch per coin count
+        pools = curve[n]
+        batches.append(Curve.batch(*[[p[j] for p in pools] for j in range(5)]))
     return tokens, batches
+
+
+def stableswap_D(x, A):
+    """StableSwap's invariant D of balances x [..., n] at amplification A [...]: the root of
+    A·nⁿ·Σx + D = A·D·nⁿ + D^{n+1}/(nⁿ·Πx), by the contracts' own Newton iteration in float64 (vectorised)."""
+    x = np.asarray(x, dtype=np.float64)
+    A = np.asarray(A, dtype=np.float64)
+    n = x.shape[-1]
+    S = x.sum(axis=-1)
+    Ann = A * n ** n
+    D = S.copy()
+    for _ in range(255):
+        DP = D.copy()
+        for k in range(n):
+            DP = DP * D / (n * x[..., k])
+        Dn = (Ann * S + DP * n) * D / ((Ann - 1.0) * D + (n + 1) * DP)
+        done = np.all(np.abs(Dn - D) <= 4 * np.finfo(float).eps * Dn)
+        D = Dn
+        if done:
+            break
+    return D
+
+
+def stableswap_params(x, A):
+    """(α, β) of Curve for a StableSwap pool with balances x [..., n] and amplification A: α = A·nⁿ, β = D^{n+1}/nⁿ."""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[-1]
+    D = stableswap_D(x, A)
+    return np.asarray(A, dtype=np.float64) * n ** n, D ** (n + 1) / n ** n
+
+
+def _curve(rec, toks, tid, where):
+    """one "curve" record with 2..8 tokens -> (R, γ, Ai, α, β)"""
+    if not isinstance(toks, (list, tuple)) or not 2 <= len(toks) <= MAX_COINS or len(set(toks)) != len(toks):
+        raise ArgumentError(f"{where}: tokens must be 2..{MAX_COINS} distinct identifiers")
+    n = len(toks)
+    dec = rec.get("decimals", [18] * n)
+    if len(dec) != n:
+        raise ArgumentError(f"{where}: decimals must have {n} entries")
+    r = rec.get("balances")
+    if r is None or len(r) != n:
+        raise ArgumentError(f"{where}: balances must have {n} entries")
+    A = rec.get("A")
+    if A is None or not np.isfinite(float(A)) or float(A) < 0:
+        raise ArgumentError(f"{where}: the amplification A must be a finite number >= 0")
+    g = _gamma(rec, where)
+    R = [_amount(r[i], dec[i], where) for i in range(n)]
+    al, be = stableswap_params(R, float(A))
+    return R, g, [tid(t) for t in toks], float(al), float(be)
 
 
 def _weighted_n(rec, toks, tid, where):

@@ -123,7 +123,7 @@ int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx
     c->psegs.push_back({kind, m, c->m_total, n_coins, c->flat_total});
     c->m_total += m;
     c->flat_total += m * n_coins;
-    c->any_weighted = c->any_weighted || kind == CFMM_KIND_WEIGHTED;
+    c->any_ragged = c->any_ragged || ragged_kind(kind);
     c->have_out = c->have_trades = false;
     return CFMM_OK;
 }

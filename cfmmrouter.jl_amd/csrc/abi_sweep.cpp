@@ -38,8 +38,8 @@ int fused_grid_cap(const cfmm_ctx* c, int block)
 // (and the fold kernel) small.  Large-market mode (global bins) uses 512-thread blocks throughout.
 void plan_segment(const cfmm_ctx* c, Segment& s)
 {
-    // weighted segments: their own launch of 512-thread blocks (sweep_weighted), never single-block direct
-    if (s.kind == CFMM_KIND_WEIGHTED) {
+    // weighted / Curve segments: their own launch of 512-thread blocks (sweep_weighted, sweep_curve), never single-block direct
+    if (ragged_kind(s.kind)) {
         const int64_t tiles = std::max<int64_t>(1, (s.m + kMidBlock - 1) / kMidBlock);
         s.block = kMidBlock;
         s.grid = (int)std::min<int64_t>(tiles, c->opt_max_grid > 0 ? c->opt_max_grid : fat_grid_cap(c, kMidBlock));
@@ -204,25 +204,25 @@ int ensure_geometry(cfmm_ctx* c)
     int64_t rows = 0, trades = 0, pools = 0, flat = 0;
     size_t n_two_coin = 0;
     bool any_big = false;
-    c->any_weighted = false;
+    c->any_ragged = false;
     for (auto& s : c->segs) {
         plan_segment(c, s);
-        const bool wt = s.kind == CFMM_KIND_WEIGHTED;
-        s.trade_off = trades;           // (weighted segments have no rows in the two-coin trade buffers)
+        const bool wt = ragged_kind(s.kind);
+        s.trade_off = trades;           // (weighted / Curve segments have no rows in the two-coin trade buffers)
         s.flat_off = flat;
         if (!wt) trades += s.m;
         pools += s.m;
         flat += s.m * (wt ? s.n_coins : 2);
         if (!wt) ++n_two_coin;
-        c->any_weighted = c->any_weighted || wt;
+        c->any_ragged = c->any_ragged || wt;
         any_big = any_big || (!wt && s.block == kBigBlock);
     }
     c->groups.clear();
     const bool fusable = c->opt_fuse_segments != 0 && n_two_coin >= 2 && c->opt_geomean_exact == 0;
-    // launch groups: every weighted segment alone (sweep_weighted); runs of consecutive two-coin segments fused by up to
-    // kMaxMulti (sweep_multi) or one launch each
+    // launch groups: every weighted / Curve segment alone (sweep_weighted, sweep_curve); runs of consecutive two-coin segments
+    // fused by up to kMaxMulti (sweep_multi) or one launch each
     for (size_t run = 0; run < c->segs.size();) {
-        if (c->segs[run].kind == CFMM_KIND_WEIGHTED) {
+        if (ragged_kind(c->segs[run].kind)) {
             Segment& sg = c->segs[run];
             Group g;
             g.first = (int)run;
@@ -236,7 +236,7 @@ int ensure_geometry(cfmm_ctx* c)
             continue;
         }
         size_t run_end = run;
-        while (run_end < c->segs.size() && c->segs[run_end].kind != CFMM_KIND_WEIGHTED) ++run_end;
+        while (run_end < c->segs.size() && !ragged_kind(c->segs[run_end].kind)) ++run_end;
         if (fusable) {
             // fused launches use 512-thread blocks (Product / GeoMean blocks interleave on every CU) unless asked otherwise
             const int block = (any_big && c->opt_block == kBigBlock) ? kBigBlock : kMidBlock;
@@ -319,9 +319,11 @@ int ensure_geometry(cfmm_ctx* c)
     c->flat_total = flat;
     c->touched_bytes = 0;
     for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3);
-                                    // weighted: per coin R, q, w, token (28 B) + {γ, log γ} per pool, and 16 B per coin written
+                                    // weighted: per coin R, q, w, token (28 B) + {γ, log γ} per pool, and 16 B per coin written;
+                                    // Curve: per coin R, log R, token (20 B) + {α, log β}, {γ, log γ}, and 16 B per coin written
         c->touched_bytes += s.m * (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
-                                            : s.kind == CFMM_KIND_WEIGHTED ? 44 * s.n_coins + 16 : (s.has_walk ? 104 : 56) + 16);
+                                            : s.kind == CFMM_KIND_WEIGHTED ? 44 * s.n_coins + 16
+                                            : s.kind == CFMM_KIND_CURVE ? 36 * s.n_coins + 32 : (s.has_walk ? 104 : 56) + 16);
     if (rows > c->rows_cap) {
         (void)hipFree(c->d_partials);
         c->d_partials = nullptr;
@@ -377,7 +379,7 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
     // a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
     // exchanges, and RCCL all-reduces d_out behind the fold)
     const bool direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !gb && !sharded &&
-                        c->segs[(size_t)c->groups[0].first].kind != CFMM_KIND_WEIGHTED;
+                        !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
     size_t group_index = 0;
     for (const Group& g : c->groups) {
         const size_t gi = group_index++;
@@ -488,6 +490,11 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
             case CFMM_KIND_WEIGHTED:
                 e = launch_sweep(WeightedPools{s.wR, s.wq, s.ww, s.wtok, s.glg, s.n_coins, materialize ? s.wD : nullptr,
                                                materialize ? s.wL : nullptr},
+                                 a, cfg, materialize, c->stream);
+                break;
+            case CFMM_KIND_CURVE:
+                e = launch_sweep(CurvePools{s.wR, s.wq, s.wtok, s.cab, s.glg, s.n_coins, materialize ? s.wD : nullptr,
+                                            materialize ? s.wL : nullptr},
                                  a, cfg, materialize, c->stream);
                 break;
             default: e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream); break;

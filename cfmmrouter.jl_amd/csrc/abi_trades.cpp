@@ -136,7 +136,7 @@ int download_coin_major(cfmm_ctx* c, const double* src, int64_t m, int nc, int64
 
 int download_segment(cfmm_ctx* c, const Segment& s, int64_t first, int64_t count, double* Delta, double* Lambda)
 {
-    if (s.kind != CFMM_KIND_WEIGHTED) return download_trades(c, s.trade_off + first, count, Delta, Lambda);
+    if (!ragged_kind(s.kind)) return download_trades(c, s.trade_off + first, count, Delta, Lambda);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     int rc = download_coin_major(c, s.wD, s.m, s.n_coins, first, count, Delta);
     return rc != CFMM_OK ? rc : download_coin_major(c, s.wL, s.m, s.n_coins, first, count, Lambda);
@@ -194,7 +194,7 @@ int cfmm_get_trades(cfmm_ctx* c, double* Delta, double* Lambda)
         return CFMM_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->any_weighted) return download_trades(c, 0, c->trade_rows, Delta, Lambda);
+    if (!c->any_ragged) return download_trades(c, 0, c->trade_rows, Delta, Lambda);
     // ragged layout (cfmm_trades_len): segment after segment, n_coins doubles per pool
     for (const Segment& s : c->segs) {
         const int rc = download_segment(c, s, 0, s.m, Delta ? Delta + s.flat_off : nullptr, Lambda ? Lambda + s.flat_off : nullptr);
@@ -207,7 +207,7 @@ int64_t cfmm_trades_len(const cfmm_ctx* c)
 {
     if (!c) return 0;
     int64_t len = 0;
-    for (const Segment& s : c->segs) len += s.m * (s.kind == CFMM_KIND_WEIGHTED ? s.n_coins : 2);
+    for (const Segment& s : c->segs) len += s.m * (ragged_kind(s.kind) ? s.n_coins : 2);
     for (const auto& ps : c->psegs) len += ps.m * ps.n_coins;
     return len;
 }
@@ -218,8 +218,8 @@ int cfmm_trades_dev(cfmm_ctx* c, const double** d_delta, const double** d_lambda
     CFMM_SINGLE_ONLY(c, "cfmm_trades_dev");
     int rc = ensure_geometry(c);
     if (rc != CFMM_OK) return rc;
-    if (c->any_weighted)
-        return fail(c, CFMM_ERR_UNSUPPORTED, "cfmm_trades_dev: the market has weighted pools, whose trades are ragged and kept "
+    if (c->any_ragged)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "cfmm_trades_dev: the market has weighted or Curve pools, whose trades are ragged and kept "
                                              "per segment (use cfmm_get_trades / cfmm_get_trades_range)");
     HIP_TRY(c, hipSetDevice(c->device));
     // device consumers get the reference's layout: the compact records of the latest materialising sweep are
@@ -307,6 +307,10 @@ int cfmm_update_reserves(cfmm_ctx* c)
             e = launch_update_weighted(s.wR, s.wq, s.ww, s.glg, s.wD, s.wL, s.n_coins, s.m, c->stream);
             continue;
         }
+        if (s.kind == CFMM_KIND_CURVE) {
+            e = launch_update_curve(s.wR, s.wq, s.glg, s.wD, s.wL, s.n_coins, s.m, c->stream);
+            continue;
+        }
         e = launch_update_two_coin(s.R, s.gamma, c->d_delta + s.trade_off, c->d_lambda + s.trade_off, c->d_over + s.trade_off,
                                    c->trades_compact, s.kind == CFMM_KIND_GEOMEAN ? s.lR : nullptr, s.eta, s.m, d_left + k, c->stream);
     }
@@ -360,7 +364,7 @@ int cfmm_get_reserves(cfmm_ctx* c, int32_t seg, double* R)
     if (s.kind == CFMM_KIND_UNIV3) return fail(c, CFMM_ERR_INVALID_ARG, "UniV3 segments have prices, not reserves: cfmm_get_prices");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (s.kind == CFMM_KIND_WEIGHTED) return download_coin_major(c, s.wR, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
+    if (ragged_kind(s.kind)) return download_coin_major(c, s.wR, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
     HIP_TRY(c, hipMemcpy(R, s.R, (size_t)s.m * sizeof(double2), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }

@@ -165,7 +165,7 @@ void free_segment(Segment& s)
     (void)hipFree(s.pg); (void)hipFree(s.cp); (void)hipFree(s.walk); (void)hipFree(s.ticks); (void)hipFree(s.thr);
     (void)hipFree(s.head);
     (void)hipFree(s.wR); (void)hipFree(s.wq); (void)hipFree(s.ww); (void)hipFree(s.wtok); (void)hipFree(s.glg);
-    (void)hipFree(s.wD); (void)hipFree(s.wL);
+    (void)hipFree(s.wD); (void)hipFree(s.wL); (void)hipFree(s.cab);
     s = Segment{};
 }
 
@@ -516,6 +516,79 @@ int cfmm_pools_add_weighted(cfmm_ctx* c, int64_t m, int32_t n_coins, const doubl
     return add_segment_common(c, std::move(s), Ai);
 }
 
+int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* R, const double* gamma, const int32_t* Ai,
+                         const double* alpha, const double* beta)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
+    if (n_coins < 2 || n_coins > kMaxCoins)
+        return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: Curve pools have 2 .. %d coins", (int)n_coins, kMaxCoins);
+    if (c->n > kMaxLdsTokens)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "Curve pools need n_tokens <= %d (large-market mode sweeps two-coin pools only)",
+                    kMaxLdsTokens);
+    if (m > 0 && (!R || !gamma || !Ai || !alpha || !beta)) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
+    const int nc = n_coins;
+    for (int64_t i = 0; i < m; ++i) {
+        for (int k = 0; k < nc; ++k) {
+            const size_t j = (size_t)(i * nc + k);
+            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
+            const int32_t a = Ai[j];
+            if (a < 0 || a >= c->n)
+                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: token index out of range [0, %d)", (long long)i, c->n);
+            for (int k2 = 0; k2 < k; ++k2)
+                if (Ai[(size_t)(i * nc + k2)] == a)
+                    return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the token indices must be distinct", (long long)i);
+        }
+        if (!std::isfinite(alpha[i]) || alpha[i] < 0.0)
+            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: alpha must be finite and >= 0", (long long)i);
+        if (!finite_pos(beta[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: beta must be finite and > 0", (long long)i);
+        if (!finite_pos(gamma[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
+        if (gamma[i] > 1.0)
+            return fail(c, CFMM_ERR_INVALID_ARG,
+                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
+                        (long long)i);
+    }
+    if (!c->shards.empty())
+        return multi_add(c, CFMM_KIND_CURVE, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
+            return cfmm_pools_add_curve(child, hi - lo, n_coins, R + nc * lo, gamma + lo, Ai + nc * lo, alpha + lo, beta + lo);
+        }, nc);
+    // coin-major columns (sweep.h CurvePools): R, log R, token; per pool {α, log β} and {γ, log γ}
+    const size_t cells = (size_t)m * (size_t)nc;
+    std::vector<double> cR(cells), cl(cells);
+    std::vector<int32_t> ct(cells);
+    std::vector<double2> ab((size_t)m), glg((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        for (int k = 0; k < nc; ++k) {
+            const size_t src = (size_t)(i * nc + k), dst = (size_t)k * (size_t)m + (size_t)i;
+            cR[dst] = R[src];
+            cl[dst] = std::log(R[src]);
+            ct[dst] = Ai[src];
+        }
+        ab[(size_t)i] = make_double2(alpha[i], std::log(beta[i]));
+        glg[(size_t)i] = make_double2(gamma[i], std::log(gamma[i]));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    Segment s;
+    s.kind = CFMM_KIND_CURVE;
+    s.m = m;
+    s.n_coins = nc;
+    s.fast_ok = 0;   // one arithmetic only (the compiler's)
+    int rc;
+    if ((rc = upload(c, &s.wR, cR.data(), cells)) || (rc = upload(c, &s.wq, cl.data(), cells)) ||
+        (rc = upload(c, &s.wtok, ct.data(), cells)) || (rc = upload(c, &s.cab, ab.data(), (size_t)m)) ||
+        (rc = upload(c, &s.glg, glg.data(), (size_t)m))) {
+        free_segment(s);
+        return rc;
+    }
+    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.wD), cells * sizeof(double)) != hipSuccess ||
+                      hipMalloc(reinterpret_cast<void**>(&s.wL), cells * sizeof(double)) != hipSuccess)) {
+        (void)hipGetLastError();
+        free_segment(s);
+        return fail(c, CFMM_ERR_HIP, "trade buffers of a Curve segment: allocation failed");
+    }
+    return add_segment_common(c, std::move(s), Ai);
+}
+
 int cfmm_pools_clear(cfmm_ctx* c)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
@@ -524,7 +597,7 @@ int cfmm_pools_clear(cfmm_ctx* c)
         c->psegs.clear();
         c->m_total = 0;
         c->flat_total = 0;
-        c->any_weighted = false;
+        c->any_ragged = false;
         c->have_out = c->have_trades = false;
         return CFMM_OK;
     }
@@ -534,7 +607,7 @@ int cfmm_pools_clear(cfmm_ctx* c)
     c->segs.clear();
     c->m_total = 0;
     c->flat_total = 0;
-    c->any_weighted = false;
+    c->any_ragged = false;
     c->rows_total = 0;
     c->geometry_dirty = true;
     c->have_out = c->have_trades = false;

@@ -65,8 +65,9 @@ struct Segment {
     // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
     std::vector<double> h_cp, h_gamma, h_lt, h_liq;
     std::vector<int64_t> h_tick_off;
-    // Weighted (CFMM_KIND_WEIGHTED) only: coin-major [n_coins][m] columns (sweep.h WeightedPools) and the segment's own trade
-    // arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
+    // Weighted (CFMM_KIND_WEIGHTED) and Curve (CFMM_KIND_CURVE) only: coin-major [n_coins][m] columns (sweep.h WeightedPools,
+    // CurvePools) and the segment's own trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is
+    // unused)
     int n_coins = 2;
     int64_t flat_off = 0;      // first double of this segment in the ragged trade layout of cfmm_get_trades (Σ coins before it)
     double* wR = nullptr;
@@ -76,7 +77,12 @@ struct Segment {
     double2* glg = nullptr;    // [m] {γ, log γ}
     double* wD = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
     double* wL = nullptr;      // [n_coins][m] Λ
+    // Curve (CFMM_KIND_CURVE) segments use the same layout: wR, wq = log R, wtok, glg, wD, wL (no ww), and
+    double2* cab = nullptr;    // [m] {α, log β}
 };
+
+// Segments whose trades are ragged (n_coins per pool, kept in the segment's own wD / wL): their own launch each.
+inline bool ragged_kind(int kind) { return kind == CFMM_KIND_WEIGHTED || kind == CFMM_KIND_CURVE; }
 
 // A launch: either one segment (sweep_kernel) or up to kMaxMulti segments fused (sweep_multi).
 struct Group {
@@ -131,7 +137,7 @@ struct cfmm_ctx {
     int64_t m_total = 0;
     int64_t trade_rows = 0;       // rows of the two-coin trade buffers (pools of the two-coin segments; weighted segments keep their own)
     int64_t flat_total = 0;       // Σ over segments of m × coins: the length of each ragged trade array (cfmm_trades_len)
-    bool any_weighted = false;    // some segment is CFMM_KIND_WEIGHTED (its trades are ragged)
+    bool any_ragged = false;      // some segment is ragged_kind (weighted, Curve): its trades are ragged
     int64_t touched_bytes = 0;    // what one materialising sweep moves by construction (packed layout; ensure_geometry): decides "stream_stores" = auto
     int64_t rows_total = 0;
 

@@ -107,6 +107,19 @@ struct WeightedPools {
     double* Lambda;
 };
 
+// Curve (StableSwap) pools, φ(R) = α·Σ R − β·Π R⁻¹ (Curve{T}, src/cfmms.jl:66-70; sweep_curve, curve_pool.h).  Coin-major
+// columns as WeightedPools.
+struct CurvePools {
+    const double* R;             // [n_coins][m] reserves
+    const double* lR;            // [n_coins][m] log R (upload, update_curve)
+    const int32_t* tok;          // [n_coins][m] token indices, 0-based
+    const double2* ab;           // [m] {α, log β}
+    const double2* glg;          // [m] {γ, log γ}
+    int n_coins;                 // 2 .. kMaxCoins, uniform over the segment
+    double* Delta;               // [n_coins][m] trades of a materialising sweep (null otherwise)
+    double* Lambda;
+};
+
 // How a fold launch hands {Ψ, acc} to the host (mapped pinned memory), if at all: gran != null -> the block's 8 columns
 // leave as 16 SELF-VALIDATING 8-byte granules {tag, 32 bits of the double} (two per column) written by one store
 // instruction = two full 64-byte lines; the host re-reads them until all carry the tag -- no drain of the output stores,
@@ -224,6 +237,13 @@ hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const Launch
 // R <- (R + γΔ) − Λ per coin, in place, then q <- log(R / w)
 hipError_t launch_update_weighted(double* R, double* q, const double* w, const double2* glg, const double* Delta,
                                   const double* Lambda, int n_coins, int64_t m, hipStream_t s);
+
+// Curve segments likewise (their own launch of kMidBlock threads, never fused, never direct; trades to p.Delta / p.Lambda).
+hipError_t launch_sweep(const CurvePools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+                        hipStream_t s);
+// R <- (R + γΔ) − Λ per coin, in place, then lR <- log R (α and β are the pool's parameters: unchanged)
+hipError_t launch_update_curve(double* R, double* lR, const double2* glg, const double* Delta, const double* Lambda,
+                               int n_coins, int64_t m, hipStream_t s);
 
 // block b writes partial row b (see sweep_multi for the block -> segment map); without xcd_map the grid must be a
 // multiple of ma.nseg.

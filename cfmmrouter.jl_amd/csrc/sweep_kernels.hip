@@ -7,6 +7,7 @@
 //   find_arb!(.., ::GeometricMeanTwoCoin) src/cfmms.jl:180-196 -> GeoMeanLogOps::solve (default), GeoMeanOps::solve
 //   find_arb!(.., ::UniV3) + helpers   src/cfmms.jl:294-395   -> UniV3Ops::solve_dir
 //   GeometricMean / Product, N coins  src/cfmms.jl:57-64 (no find_arb! upstream) -> sweep_weighted / weighted_pool
+//   Curve (StableSwap), N coins       src/cfmms.jl:66-70 (no find_arb! upstream) -> sweep_curve / curve_solve
 //   acc loop of fn                     src/router.jl:79-83    -> per-lane acc + wave shuffles
 //   scatter loop of g! / netflows!     src/router.jl:98-100, :111-119 -> LDS bins + reduce_partials
 //                                      (n_tokens > 8192: flow array + gather_chunks / token_fold)
@@ -31,6 +32,7 @@
 // library's pow).  HBM-bound by design: no MFMA (there is no contraction anywhere on this path).
 
 #include "sweep.h"
+#include "curve_pool.h"
 
 #include <hip/hip_ext.h>
 
@@ -1324,6 +1326,99 @@ __global__ __launch_bounds__(kMidBlock) void sweep_weighted(WeightedPools p, Swe
 }
 
 // ---------------------------------------------------------------------------------------------
+// Curve (StableSwap) pools -- Curve{T}, src/cfmms.jl:66-70 (no find_arb! there): φ(R) = α·Σ R − β·Π R⁻¹
+// ---------------------------------------------------------------------------------------------
+// One lane per pool; the solve (outer safeguarded Newton on E2, inner exact E1 root) is curve_pool.h's curve_solve, the
+// derivation there.  Prices come from the LDS row stage_prices fills (v itself: no log v row).  Trades: λ_k = −R_k·expm1(
+// log r_k − ρ_k) for a coin that leaves, δ_k = R_k·expm1(log r_k − ρ_k)/γ for one that enters; a coin that does not trade
+// has log r_k = ρ_k exactly, hence +0.0.  Ψ and acc as weighted_pool (LDS bins of the wavefront, per-lane dual).
+template <int N, bool MAT>
+__device__ __forceinline__ void curve_pool(const CurvePools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
+{
+    const int64_t m = a.m;
+    double R[N], rho[N], v[N], lr[N];
+    int tok[N];   // (v is re-read from LDS after the solve: fewer registers live across it)
+    const double2 ab = p.ab[i];
+    const double2 gl = p.glg[i];
+    const char* base = reinterpret_cast<const char*>(L.vy);
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        R[k] = p.R[k * m + i];
+        rho[k] = p.lR[k * m + i];
+        tok[k] = p.tok[k * m + i];
+    }
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
+    if (!curve_solve<N>(rho, R, v, ab.x, ab.y, gl.x, lr)) {   // inside the fee band: no trade
+        if (MAT) {
+#pragma unroll
+            for (int k = 0; k < N; ++k) {
+                p.Delta[k * m + i] = 0.0;
+                p.Lambda[k * m + i] = 0.0;
+            }
+        }
+        return;
+    }
+    const double rg = 1.0 / gl.x;
+    double sum_l = 0.0, sum_d = 0.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const bool nan_k = lr[k] != lr[k];
+        const double em = expm1(lr[k] - rho[k]);
+        const double lam = nan_k ? lr[k] : (lr[k] < rho[k] ? -(R[k] * em) : 0.0);
+        const double del = nan_k ? lr[k] : (lr[k] > rho[k] ? (R[k] * em) * rg : 0.0);
+        if (MAT) {
+            p.Delta[k * m + i] = del;
+            p.Lambda[k * m + i] = lam;
+        }
+        const double vk = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
+        sum_l += lam * vk;     // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
+        sum_d += del * vk;
+        const double f = lam - del;   // src/router.jl:99  G[Ai] .+= Λ .- Δ
+        if (f != 0.0 || f != f) atomicAdd(&L.my_bins[tok[k]], f);
+    }
+    acc += sum_l - sum_d;
+}
+
+template <int N, bool MAT>
+__device__ __forceinline__ void curve_tiles(const CurvePools& p, const SweepArgs& a, const SweepLds& L, int64_t i, int64_t step,
+                                            int64_t left, double& acc)
+{
+    for (; left > 0; --left, i += step) curve_pool<N, MAT>(p, a, L, i, acc);
+}
+
+// One launch per Curve segment; prologue and epilogue are sweep_weighted's (the other families' own).
+template <bool MAT>
+__global__ __launch_bounds__(kMidBlock) void sweep_curve(CurvePools p, SweepArgs a)
+{
+    constexpr int BLOCK = kMidBlock;
+    const SweepLds L = carve_lds<BLOCK, false>(a);
+    const int staged = stage_prices<BLOCK, false>(a, L);
+    const bool poison = (staged & kStageLive) == 0;
+    const bool live = !poison || (staged & kStageGaveUp) != 0;
+    if (staged & kStageGaveUp) report(a, kFlagGaveUp);
+    double acc = 0.0;
+    if (!poison) {
+        const int64_t stride = (int64_t)gridDim.x * BLOCK;
+        const int64_t i0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+        const int64_t left = i0 < a.m ? (a.m - i0 + stride - 1) / stride : 0;
+        const int64_t step = a.reverse ? -stride : stride;
+        const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
+        switch (p.n_coins) {
+        case 2: curve_tiles<2, MAT>(p, a, L, i, step, left, acc); break;
+        case 3: curve_tiles<3, MAT>(p, a, L, i, step, left, acc); break;
+        case 4: curve_tiles<4, MAT>(p, a, L, i, step, left, acc); break;
+        case 5: curve_tiles<5, MAT>(p, a, L, i, step, left, acc); break;
+        case 6: curve_tiles<6, MAT>(p, a, L, i, step, left, acc); break;
+        case 7: curve_tiles<7, MAT>(p, a, L, i, step, left, acc); break;
+        case 8: curve_tiles<8, MAT>(p, a, L, i, step, left, acc); break;
+        default: break;
+        }
+    }
+    finish_row<BLOCK, false>(a, L, acc, (int)blockIdx.x, poison, live);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Row fold: out[j] = sum over rows of partials[row][j]  (src/router.jl:81-83, :98-100 summed over blocks)
 // ---------------------------------------------------------------------------------------------
 // One block owns kReduceCols adjacent columns (64 B = half a 128-byte line of every row; rows are 128-byte aligned,
@@ -1622,6 +1717,10 @@ hipError_t prepare_kernels(size_t max_lds_bytes)
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)max_lds_bytes)) != hipSuccess ||
         (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_curve<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_curve<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)max_lds_bytes)) != hipSuccess)
         return e;
     if ((e = set_lds_attr<ProductOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
@@ -1781,6 +1880,40 @@ __global__ __launch_bounds__(256) void update_weighted(double* __restrict__ R, d
         R[j] = rn;
         q[j] = log(rn / w[j]);
     }
+}
+
+// update_reserves! for Curve segments: R <- (R + γΔ) − Λ per coin, lR <- log R; α, β stay (the pool's parameters)
+__global__ __launch_bounds__(256) void update_curve(double* __restrict__ R, double* __restrict__ lR, const double2* __restrict__ glg,
+                                                    const double* __restrict__ Delta, const double* __restrict__ Lambda, int n_coins,
+                                                    long long m)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    const double g = glg[i].x;
+    for (int k = 0; k < n_coins; ++k) {
+        const long long j = (long long)k * m + i;
+        const double rn = (R[j] + g * Delta[j]) - Lambda[j];
+        R[j] = rn;
+        lR[j] = log(rn);
+    }
+}
+
+hipError_t launch_sweep(const CurvePools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+{
+    if (a.m <= 0) return hipSuccess;
+    dim3 g(c.grid), b(kMidBlock);
+    if (mat) launch_k(&sweep_curve<true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    else launch_k(&sweep_curve<false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_curve(double* R, double* lR, const double2* glg, const double* Delta, const double* Lambda,
+                               int n_coins, int64_t m, hipStream_t s)
+{
+    if (m <= 0) return hipSuccess;
+    hipLaunchKernelGGL(update_curve, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, R, lR, glg, Delta, Lambda, n_coins,
+                       (long long)m);
+    return hipGetLastError();
 }
 
 hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
 from .cfmms import CFMM, PoolBatch, _upload
 
 
@@ -88,12 +88,13 @@ def _segments_of(cfmms):
         if idx:
             batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
             order.extend(idx)
-    for n in range(2, 9):   # weighted pools: one batch (one device segment) per coin count
-        idx = [i for i, c in enumerate(cfmms) if c.kind == KIND_WEIGHTED and len(c.Ai) == n]
-        if idx:
-            batches.append(PoolBatch.from_pools(KIND_WEIGHTED, [cfmms[i] for i in idx]))
-            order.extend(idx)
-    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED)]
+    for kind in (KIND_WEIGHTED, KIND_CURVE):
+        for n in range(2, 9):   # weighted / Curve pools: one batch (one device segment) per coin count
+            idx = [i for i, c in enumerate(cfmms) if c.kind == kind and len(c.Ai) == n]
+            if idx:
+                batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
+                order.extend(idx)
+    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE)]
     for i in host:
         if not callable(getattr(cfmms[i], "find_arb_", None)) or not hasattr(cfmms[i], "Ai"):
             raise ArgumentError(f"cfmms[{i}] ({type(cfmms[i]).__name__}): a pool type without a device kernel needs its own "
@@ -220,8 +221,8 @@ class Router:
             self._backend = MixedBackend(self._backend, self._host)
         self._psi = np.zeros(self.n_tokens)
         self._acc = 0.0
-        # weighted pools: r.Δs / r.Λs are per-pool vectors (the reference's ragged Vector{Vector}, src/router.jl:7-8)
-        self._ragged = any(b.kind == KIND_WEIGHTED for b in batches)
+        # weighted / Curve pools: r.Δs / r.Λs are per-pool vectors (the reference's ragged Vector{Vector}, src/router.jl:7-8)
+        self._ragged = any(b.kind in (KIND_WEIGHTED, KIND_CURVE) for b in batches)
         self._zero_trades()
         self._trades_stale = False
         self.n_sweeps = 0
@@ -637,7 +638,8 @@ def _update_reserves_host(r: Router):
     if any(b.kind == KIND_UNIV3 for b in r._batches):
         raise NotImplementedError("update_reserves! is not defined for UniV3 pools (nor in the reference)")
     if r._ragged:
-        raise NotImplementedError("this backend cannot update weighted pools (the device context does: cfmm_update_reserves)")
+        raise NotImplementedError("this backend cannot update weighted or Curve pools (the device context does: "
+                                  "cfmm_update_reserves)")
     if not hasattr(getattr(r._backend, "inner", r._backend), "reload"):    # (MixedBackend forwards to its inner backend)
         raise NotImplementedError("this backend cannot reload pools")
     D, Lm = r._backend.trades()                       # packed (segment) order

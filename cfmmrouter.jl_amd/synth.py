@@ -13,12 +13,13 @@ generator this repo owns: SplitMix64 in counter mode, u(i) = mix(seed*GOLD + i*G
 
 N-coin weighted pools (weighted_pools) have no distribution in the reference; they reuse the reserve and fee
 distributions, with weights 0.05 + U[0,1) normalised to sum to 1 and n_coins distinct uniform tokens.
+Curve pools (curve_pools) have none either; see that function for their regimes.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED
 from .cfmms import PoolBatch
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -210,3 +211,39 @@ def weighted_pools(m, n_tokens, n_coins, seed=1234, first=0):
             r = r + (r >= chosen[:, j])
         Ai[:, k] = r
     return PoolBatch(KIND_WEIGHTED, R=R, w=w, γ=γ, Ai=Ai + 1)
+
+
+def _distinct_tokens(m, n_tokens, n_coins, seed, stream, first):
+    Ai = np.empty((m, n_coins), dtype=np.int64)
+    for k in range(n_coins):   # the r-th token not chosen yet: r = floor(U·(n − k)), stepped past the chosen ones in order
+        r = np.minimum((uniform(seed, stream + k, m, first) * (n_tokens - k)).astype(np.int64), n_tokens - k - 1)
+        chosen = np.sort(Ai[:, :k], axis=1)
+        for j in range(k):
+            r = r + (r >= chosen[:, j])
+        Ai[:, k] = r
+    return Ai + 1
+
+
+def curve_pools(m, n_tokens, n_coins, seed=1234, first=0, regime="mixed"):
+    """m Curve (StableSwap) pools (KIND_CURVE) of n_coins coins each, α = A·nⁿ, β = D^{n+1}/nⁿ from the balances.
+    Regimes ("mixed": pool by pool, 60 / 20 / 20 %):
+      "stableswap"  A = 10^U[0, 3.7) (1 .. 5000), balances B·(1 + 0.2·(U − 1/2)) near-balanced, B = 10^U[3, 6)
+      "small_a"     A = 10^U[−2, 0) (0.01 .. 1), balances 1000·U² + 1e-3 (weighted_pools' reserves)
+      "alpha0"      A = 0 (trades as Product), the same balances
+    γ ∈ {0.9996, 0.997, 1.0}, n_coins distinct uniform 1-based tokens."""
+    from .chain import stableswap_params
+
+    if not 2 <= n_coins <= min(8, n_tokens):
+        raise ValueError("need 2 <= n_coins <= min(8, n_tokens)")
+    u = uniform(seed, 100, m, first)
+    pick = {"mixed": u, "stableswap": np.zeros(m), "small_a": np.full(m, 0.7), "alpha0": np.full(m, 0.9)}[regime]
+    B = 10.0 ** (3.0 + 3.0 * uniform(seed, 101, m, first))
+    near = np.stack([B * (1.0 + 0.2 * (uniform(seed, 110 + k, m, first) - 0.5)) for k in range(n_coins)], axis=1)
+    wide = np.stack([1000.0 * uniform(seed, 120 + k, m, first) ** 2 + 1e-3 for k in range(n_coins)], axis=1)
+    A = np.where(pick < 0.6, 10.0 ** (3.7 * uniform(seed, 102, m, first)),
+                 np.where(pick < 0.8, 10.0 ** (-2.0 + 2.0 * uniform(seed, 103, m, first)), 0.0))
+    R = np.where((pick < 0.6)[:, None], near, wide)
+    α, β = stableswap_params(R, A)
+    g = uniform(seed, 104, m, first)
+    γ = np.where(g < 1 / 3, 0.9996, np.where(g < 2 / 3, 0.997, 1.0))
+    return PoolBatch(KIND_CURVE, R=R, γ=γ, Ai=_distinct_tokens(m, n_tokens, n_coins, seed, 130, first), α=α, β=β)

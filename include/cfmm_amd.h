@@ -42,6 +42,7 @@ extern "C" {
 #define CFMM_KIND_GEOMEAN 1 /* GeometricMeanTwoCoin  src/cfmms.jl:152-196 */
 #define CFMM_KIND_UNIV3 2   /* UniV3/BoundedProduct  src/cfmms.jl:226-395 */
 #define CFMM_KIND_WEIGHTED 3 /* GeometricMean / Product with 2..8 coins  src/cfmms.jl:57-64 (no find_arb! there) */
+#define CFMM_KIND_CURVE 4    /* Curve (StableSwap) with 2..8 coins       src/cfmms.jl:66-70 (no find_arb! there) */
 
 typedef struct cfmm_ctx cfmm_ctx;
 
@@ -178,6 +179,20 @@ int cfmm_pools_add_univ3(cfmm_ctx* ctx, int64_t m, const double* current_price, 
 int cfmm_pools_add_weighted(cfmm_ctx* ctx, int64_t m, int32_t n_coins, const double* R, const double* w,
                             const double* gamma, const int32_t* Ai);
 
+/* m x Curve(R, gamma, Ai, alpha, beta) with n_coins coins each -- src/cfmms.jl:66-70.  Trading function
+ *     phi(R) = alpha * sum_k R_k - beta / prod_k R_k,   alpha >= 0, beta > 0:
+ * Curve's StableSwap invariant A n^n sum x + D = A D n^n + D^(n+1) / (n^n prod x) with D held fixed (a swap keeps D), i.e.
+ * alpha = A n^n and beta = D^(n+1) / n^n (phi(R) = A D n^n - D on the pool's own reserves).  alpha = 0 trades exactly like
+ * Product.  The reference declares Curve without a find_arb!; here the problem of its find_arb! docstring
+ * (src/cfmms.jl:21-33) is solved per pool.  The fee is the reference's
+ * input-side gamma, as for every family (not Curve's own output-side fee, which also grows D).
+ * R[m][n_coins] > 0, Ai[m][n_coins] distinct and in [0, n_tokens), alpha[m] >= 0, beta[m] > 0, all finite,
+ * 0 < gamma <= 1 (gamma > 1 is refused, as for weighted pools), 2 <= n_coins <= 8.  Every call is its own segment and its
+ * own launch; trades are ragged (cfmm_get_trades); n_tokens > 8192 returns CFMM_ERR_UNSUPPORTED.
+ * cfmm_update_reserves moves R and keeps alpha and beta (the pool's parameters). */
+int cfmm_pools_add_curve(cfmm_ctx* ctx, int64_t m, int32_t n_coins, const double* R, const double* gamma,
+                         const int32_t* Ai, const double* alpha, const double* beta);
+
 int cfmm_pools_clear(cfmm_ctx* ctx);
 int64_t cfmm_pools_count(const cfmm_ctx* ctx); /* length(r.cfmms) */
 int32_t cfmm_n_tokens(const cfmm_ctx* ctx);    /* length(r.v) */
@@ -196,7 +211,7 @@ int cfmm_find_arb(cfmm_ctx* ctx, const double* v);
 int cfmm_eval(cfmm_ctx* ctx, const double* v, double* psi_out, double* acc_out);
 
 /* r.Δs / r.Λs after find_arb! -- src/router.jl:7-8,40, flattened: cfmm_trades_len doubles each, segment order, each
- * pool's coins in its Ai order (2 per two-coin pool, n_coins per weighted pool).  Without weighted pools that is exactly
+ * pool's coins in its Ai order (2 per two-coin pool, n_coins per weighted or Curve pool).  Without weighted or Curve pools that is exactly
  * [m_total][2].  Requires a preceding cfmm_find_arb (cfmm_eval does not produce trades). */
 int cfmm_get_trades(cfmm_ctx* ctx, double* Delta, double* Lambda);
 /* Length of each array cfmm_get_trades writes: the sum over pools of their coin counts. */
@@ -212,6 +227,7 @@ int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t cou
  * the latest materialising sweep (cfmm_find_arb, cfmm_route; consumed by this call):
  *   ProductTwoCoin / GeometricMeanTwoCoin:  R <- (R + γΔ) − Λ            (one kernel, no host traffic)
  *   weighted (CFMM_KIND_WEIGHTED):          R <- (R + γΔ) − Λ per coin    (one kernel, no host traffic)
+ *   Curve (CFMM_KIND_CURVE):                R <- (R + γΔ) − Λ per coin    (one kernel; α, β unchanged)
  *   UniV3 / BoundedProduct: the state is the price.  A pool that traded moves to the internal price
  *     P = p/γ (price falling, src/cfmms.jl:361) or γ·p (price rising, :381), p = v₁/v₂, clamped to the
  *     first tick's upper price; its tick constants are re-derived as at upload (:294-313).  That is
@@ -219,7 +235,7 @@ int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t cou
  *     materialising sweep must have been a host-pointer call.
  * Afterwards a sweep at the same prices finds no arbitrage in any pool. */
 int cfmm_update_reserves(cfmm_ctx* ctx);
-/* Current reserves R[m][2] of a two-coin segment (R[m][n_coins] of a weighted one) / current prices [m] of a UniV3 segment. */
+/* Current reserves R[m][2] of a two-coin segment (R[m][n_coins] of a weighted or Curve one) / current prices [m] of a UniV3 segment. */
 int cfmm_get_reserves(cfmm_ctx* ctx, int32_t seg, double* R);
 int cfmm_get_prices(cfmm_ctx* ctx, int32_t seg, double* current_price);
 
@@ -244,7 +260,7 @@ int cfmm_sweep_dev(cfmm_ctx* ctx, const double* d_v, double* d_out, int material
 /* Device addresses of the trade rows of the latest materialising sweep ([m_total][2] doubles each, the
  * reference's Delta / Lambda layout), valid until pools change.  With "compact_trades" (default) these
  * are expanded copies written on the context's stream by this call: call it again after a later sweep. */
-/* Markets with weighted pools: CFMM_ERR_UNSUPPORTED (their trades are ragged and stay per segment; cfmm_get_trades). */
+/* Markets with weighted or Curve pools: CFMM_ERR_UNSUPPORTED (their trades are ragged and stay per segment; cfmm_get_trades). */
 int cfmm_trades_dev(cfmm_ctx* ctx, const double** d_delta, const double** d_lambda);
 
 /* With option "time_kernels"=1 every sweep launch is bracketed by hipEvents on the launch

@@ -16,7 +16,7 @@
 module CFMMRouterAMD
 
 using CFMMRouter
-using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, Product, GeometricMean
+using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, Product, GeometricMean, Curve
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
 
@@ -120,6 +120,20 @@ function build_router(objective::O, cfmms::Vector{C}, n_tokens, ctx::Ptr{Cvoid})
         Ai = Int32[c.Ai[j] - 1 for j in 1:n, c in cfmms[idx]]
         GC.@preserve R w γ Ai check(ctx, ccall((:cfmm_pools_add_weighted, LIB), Cint,
             (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ctx, length(idx), Int32(n), R, w, γ, Ai))
+        append!(order, idx)
+    end
+    # --- Curve pools (src/cfmms.jl:66-70; φ = α·ΣR − β·ΠR⁻¹, StableSwap at fixed D): one segment per coin count ---
+    for n in 2:8
+        idx = findall(c -> c isa Curve && length(c.Ai) == n, cfmms)
+        isempty(idx) && continue
+        R = Float64[c.R[j] for j in 1:n, c in cfmms[idx]]            # n×m column-major == [m][n] row-major
+        γ = Float64[c.γ for c in cfmms[idx]]
+        Ai = Int32[c.Ai[j] - 1 for j in 1:n, c in cfmms[idx]]
+        α = Float64[c.α for c in cfmms[idx]]
+        β = Float64[c.β for c in cfmms[idx]]
+        GC.@preserve R γ Ai α β check(ctx, ccall((:cfmm_pools_add_curve, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+            ctx, length(idx), Int32(n), R, γ, Ai, α, β))
         append!(order, idx)
     end
     # The reference's plugin seam (src/cfmms.jl:35,56; src/router.jl:40): a Router takes ANY CFMM{T} subtype that has a
@@ -252,8 +266,11 @@ function update_reserves!(r::AMDRouter; sync::Bool=true)
             end
             seg += Int32(1); pos += length(idx)
         end
-        for n in 2:8     # weighted segments follow, one per coin count (build_router)
-            idx = [i for i in r.order[pos+1:end] if (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product) && length(r.cfmms[i].Ai) == n]
+        # weighted segments follow, one per coin count, then Curve segments (build_router); Curve's α, β stay
+        for curve in (false, true), n in 2:8
+            idx = [i for i in r.order[pos+1:end] if (curve ? r.cfmms[i] isa Curve :
+                                                     (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product)) &&
+                                                    length(r.cfmms[i].Ai) == n]
             isempty(idx) && continue
             R = Matrix{Float64}(undef, n, length(idx))
             GC.@preserve R check(r.ctx, ccall((:cfmm_get_reserves, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, R))
