@@ -27,9 +27,10 @@
 // -ffp-contract=off and the expressions keep the reference's operation order; with IEEE
 // correctly-rounded / and sqrt the ProductTwoCoin and UniV3 trades are bit-identical to the
 // reference arithmetic (everything v-independent in the UniV3 forms is prepared at upload with the
-// same IEEE operations).  GeometricMeanTwoCoin is evaluated in log space by default (~1e-15 of
-// the reserve scale from the reference's pow forms; GeoMeanOps keeps those, with the device
-// library's pow).  HBM-bound by design: no MFMA (there is no contraction anywhere on this path).
+// same IEEE operations).  GeometricMeanTwoCoin is evaluated in log space by default (GeoMeanOps
+// keeps the reference's pow forms, with the device library's pow).  Against a 60-digit truth both, and the
+// N-coin weighted pools, are within a few u·κ·scale (u = 2^-53, κ the conditioning of the exponent; bounds and
+// measured ratios in tests/test_gpu_precise.py).  HBM-bound by design: no MFMA (there is no contraction anywhere on this path).
 
 #include "sweep.h"
 #include "curve_pool.h"
@@ -361,9 +362,11 @@ struct GeoMeanOps {
 // with Δ = log v2 − log v1.  Per trading pool that leaves 1 exp + 3 divisions (the exponent, Y and
 // the final /γ) instead of 4 pow + 6 divisions; pools inside the
 // no-arbitrage band cost four multiplies and two compares.  The exponent carries an absolute rounding
-// error of a few 1e-16·max(1, η·|l|)/(η+1), so trades agree with the reference-order forms to ~1e-15 of
-// the reserve scale (asserted at 1e-12 in tests/test_gpu_parity.py); unlike r2^η in the reference,
-// nothing here can overflow.
+// error of about u·(|log γ| + |log η| + |log v1| + |log v2| + |log r_a| + e·|log r_b|)/(e+1), u = 2^-53, so with
+// κ = 1 + that sum / (e+1) the trades are within K·u·(κ·X* + r_b)/γ (Δ) and K·u·(κ·Y* + r_a) (Λ) of the exact
+// ones: measured K <= 2.8 on every path (fast and full arithmetic, device-pointer sweeps, direct path), asserted at
+// K = 4..8 against a 60-digit truth in tests/test_gpu_precise.py.  Unlike r2^η in the reference, nothing here can
+// overflow.
 struct GeoMeanLogOps {
     static constexpr bool kNeedsLogPrices = true;
     static constexpr bool kPrefetch = true;
