@@ -8,19 +8,24 @@ dual scalar are reduced -- the work of `find_arb!(r, v)` + the scatter loops of 
 region.  At N > 1 every rank sweeps its own shard and the launch that folds a rank's partial rows also
 all-reduces the n_tokens+1 doubles {Ψ, acc} over xGMI (fall-back: one small RCCL all-reduce per step).
 
-    python bench.py [--gpus N --steps K --warmup W --workload config3 --scaling weak|strong] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W --workload config3 --scaling weak|strong] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload scaling          # the reference's own benchmark grid (benchmark/scaling.jl), route! per point
 
     --scaling weak   (default)  every GPU sweeps one config-sized shard (config3: 1M pools per GPU)
     --scaling strong            the workload's pool count is divided among the GPUs (config4: 4M / N per GPU)
 
+A plain run is the headline alone: it sets up, runs W warm-up steps, times K steps, writes --dump-outputs and prints the
+line (metric, value, ms_per_step, config, library_options).  Everything else below -- the kernel-event and HBM-resident
+passes, roofline and its rocprofv3 children, host boundary, route!, the CPU baseline and parity, the other configurations,
+at N > 1 the collective check, sharded route!, collectives and strong-scaling legs -- runs only with --full.
+
 Where what lives (benchlib/): workloads.py (markets, byte accounting), shard.py (ShardBench: one rank's backend, stream,
 peer buffers, the step and the timed passes; the sharded route! leg), legs.py (route! wall-clock, host-pointer boundary,
 roofline record, the single-process multi-device line), traffic.py (live PMC traffic), grid.py (the reference's grid).
 This file keeps main() -- the timed region is `pass 1` below -- and cpu_baseline_leg, the ONE place that touches oracle/.
 
-Extra keys on the line: roofline (dominant kernel, hipEvents attached to every sweep launch; `frac` is the HBM-resident
+Extra keys on the --full line: roofline (dominant kernel, hipEvents attached to every sweep launch; `frac` is the HBM-resident
 figure in the reference's bytes, `bus_frac` the fraction of the bus from the PMC bytes), route (route! wall-clock on the same
 market through the GPU path), cpu_baseline (the C restatement of the reference path on the host cores: sweep throughput on
 a bounded sample and route! wall-clock) and parity (the GPU legs' netflows against that restatement, at the reference's
@@ -436,8 +441,23 @@ def summary_string(rec):
                ("%.0e" % p["fortran_reorder_slack"]) if "fortran_reorder_slack" in p else "-"))[:120]
 
 
+def headline(args, sb, world, value, ms_per_step, share):
+    """The keys every line carries, plain or --full: the timed steps' figure and what was timed"""
+    return {
+        "metric": METRIC, "value": value, "unit": "pools/s",
+        "value_is": "find_arb! pool-evaluations per second (materialising sweep + Ψ/dual reduction); "
+                    "route! wall-clock is reported under `route` (--full)", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {sb.desc}", "pools_per_gpu": sb.m_rank, "pools_total": world * sb.m_rank,
+                   "n_tokens": sb.n, "variant": "materialising" if sb.materialize else "fused", "segments": sb.be.ctx.segments(),
+                   "sharding": sb.sharding_text(), "full": bool(args.full),
+                   **({"rehearsal": "ranks share a GPU over gloo: not a measurement"} if share else {})},
+    }
+
+
 def scaling_grid_main(args):
-    """--workload scaling: the reference's published benchmark (benchmark/scaling.jl:8-38) on the GPU path, the CPU
+    """--workload scaling: the reference's published benchmark (benchmark/scaling.jl:8-38) on the GPU path, with --full the CPU
     restatement timed per point beside it (1 and 8 threads, the better one reported: the reference's thread count is not
     stated, its machine had 8 cores), and BASELINE.md's read-off plot values where the plot has them."""
     if not torch.cuda.is_available():
@@ -461,7 +481,7 @@ def scaling_grid_main(args):
         return {"cpu_restatement_ms": 1e3 * best[0], "cpu_threads": best[1], "cpu_evaluations": int(ref["info"]["funcalls"]),
                 "netflow_rel_err": float(np.max(np.abs(psi_dev - ref["psi"])) / np.max(np.abs(ref["psi"])))}
 
-    rows = run_grid(0, None if args.no_cpu else cpu_route)
+    rows = run_grid(0, cpu_route if args.full and not args.no_cpu else None)
     big = rows[-3]     # m = 10 000, sqrt(m) tokens: the point BASELINE.md reads 0.19 s for
     line = {"metric": METRIC, "value": big["m"] * big["native_evaluations"] / (big["native_ms"] * 1e-3), "unit": "pools/s",
             "value_is": "pool-evaluations per second INSIDE route! at the largest grid point (m = 10 000, 100 tokens); the "
@@ -513,6 +533,11 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last of them computed (netflows, dual value, trades; rank 0's "
                          "shard at N > 1) as DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg: kernel-event and HBM-resident passes, roofline (with its "
+                         "rocprofv3 children), host boundary, route!, CPU baseline and parity, the other configurations, and at "
+                         "N > 1 the collective check, sharded route!, collectives and strong scaling (the --no-* options trim "
+                         "this set); without it a run prints the headline line only")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
@@ -527,7 +552,7 @@ def main():
     if args.workload == "scaling":
         return scaling_grid_main(args)
     if args.single_process:
-        return single_process_main(args, cpu_baseline_leg)
+        return single_process_main(args, cpu_baseline_leg, full=args.full)
     if args.gpus > 1 and world == 1 and "TORCHELASTIC_RUN_ID" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher -- one rank per GPU over RCCL, rendezvous on
         # 127.0.0.1 (the container hostname may not resolve).  Same command line, re-executed under torchrun.
@@ -579,6 +604,16 @@ def main():
     elapsed = sb.max_over_ranks(elapsed)
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * sb.m_rank * args.steps / elapsed
+    head = headline(args, sb, world, value, ms_per_step, share)
+    options = {"library_options": {k: be.ctx.get_option(k) for k in ("pack", "compact_trades", "alternate", "fast_math", "armed",
+                                                                      "stop_in_noise", "host_flag", "zero_copy")}}
+    if not args.full:             # a plain run: the headline and nothing else
+        sb.close()
+        if rank == 0:
+            print(json.dumps({**head, **options}))
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     # pass 2 -- the same K steps with kernel events (roofline), out of the timed region
     kt, elapsed2 = sb.kernel_pass(args.steps)
@@ -618,19 +653,9 @@ def main():
         except Exception:
             traffic = None
 
-    line = {
-        "metric": METRIC, "value": value, "unit": "pools/s",
-        "value_is": "find_arb! pool-evaluations per second (materialising sweep + Ψ/dual reduction); "
-                    "route! wall-clock is reported under `route`", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {sb.desc}", "pools_per_gpu": sb.m_rank, "pools_total": world * sb.m_rank,
-                   "n_tokens": n, "variant": "materialising" if materialize else "fused", "segments": be.ctx.segments(),
-                   "sharding": sb.sharding_text(), **({"rehearsal": "ranks share a GPU over gloo: not a measurement"} if share else {})},
-        "roofline": roofline_record(sb, args, ms_per_step, sweep_ms, reduce_ms, elapsed2, cold, traffic, traffic_src, traffic_detail),
-        "library_options": {k: be.ctx.get_option(k) for k in ("pack", "compact_trades", "alternate", "fast_math", "armed",
-                                                               "stop_in_noise", "host_flag", "zero_copy")},
-    }
+    line = {**head,
+            "roofline": roofline_record(sb, args, ms_per_step, sweep_ms, reduce_ms, elapsed2, cold, traffic, traffic_src, traffic_detail),
+            **options}
     if world == 1 and not use_dist and not args.no_cpu and not args.no_live_traffic and not args.cold_only and cold is not None:
         # the HBM-resident kernel span as rocprofv3 reports it (a --cold-only child of this command under --kernel-trace --stats):
         # `kernel_ms`, `frac` and `frac_bus` are quoted on THAT clock -- the one profiles/ holds -- with the hipEvent figure beside it

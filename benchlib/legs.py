@@ -78,10 +78,11 @@ def finish_route(route_gpu):
     return {k: val for k, val in (route_gpu or {}).items() if not k.startswith("_")}
 
 
-def single_process_main(args, cpu_baseline_leg):
+def single_process_main(args, cpu_baseline_leg, full=True):
     """N shards driven by ONE host thread / process through cfmm_ctx_create_multi (what a Julia or C caller
     uses): every step is a host-pointer cfmm_find_arb -- v staged on every device, N sweeps launched by N
-    worker threads, the shards' {Ψ, acc} summed on the host.  PCIe-inclusive by construction."""
+    worker threads, the shards' {Ψ, acc} summed on the host.  PCIe-inclusive by construction.  full = False: the timed steps
+    alone, no route! and no CPU legs."""
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X; there is no CPU fallback for the product path")
     devs = [int(d) for d in args.devices.split(",")] if args.devices else list(range(args.gpus))
@@ -101,6 +102,17 @@ def single_process_main(args, cpu_baseline_leg):
     for _ in range(args.steps):
         be.ctx.find_arb(v)
     elapsed = time.perf_counter() - t0
+    line = {"metric": METRIC, "value": m_total * args.steps / elapsed, "unit": "pools/s", "n_gpus": args.gpus,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "value_is": "host-pointer cfmm_find_arb calls per second x pools (PCIe-inclusive: v in, Ψ out every step)",
+            "config": {"workload": f"{args.workload}: {desc}", "pools_total": m_total, "n_tokens": n, "devices": devs,
+                       "sharding": f"single process, cfmm_ctx_create_multi over {args.gpus} shards, host-side rank-ordered sum",
+                       "full": bool(full)}}
+    if not full:             # a plain run: the headline and nothing else
+        be.close()
+        print(json.dumps(line))
+        return
     psi = np.concatenate([be.ctx.netflows(), [be.ctx.dual_value()]])
     obj = objective_for(args.workload, n)
     v0 = np.ones(n) if isinstance(obj, cr.LinearNonnegative) else None
@@ -120,13 +132,7 @@ def single_process_main(args, cpu_baseline_leg):
                          pre_armed=len(set(devs)) == len(devs))
             psi_route, v_route = cr.netflows(r).copy(), r.v.copy()
     be.ctx.set_option("armed", 1)
-    line = {"metric": METRIC, "value": m_total * args.steps / elapsed, "unit": "pools/s", "n_gpus": args.gpus,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "value_is": "host-pointer cfmm_find_arb calls per second x pools (PCIe-inclusive: v in, Ψ out every step)",
-            "config": {"workload": f"{args.workload}: {desc}", "pools_total": m_total, "n_tokens": n, "devices": devs,
-                       "sharding": f"single process, cfmm_ctx_create_multi over {args.gpus} shards, host-side rank-ordered sum"},
-            "route": route}
+    line["route"] = route
     if not args.no_cpu:
         def sweep_at(vv):
             return be.ctx.eval(vv)[0]

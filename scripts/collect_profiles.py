@@ -11,6 +11,9 @@ import subprocess
 rnd = sys.argv[1] if len(sys.argv) > 1 else "r06"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src, dst = os.path.join(root, "gpurun_out"), os.path.join(root, "profiles")
+if "--src" in sys.argv:          # where the session's scratch files go (scripts/gpu_round.sh asks here)
+    print(src)
+    sys.exit(0)
 os.makedirs(dst, exist_ok=True)
 # The artefacts must belong to the tree they are committed with: gpu_round.sh records `git rev-parse HEAD`... which a GPU
 # box cannot know (the snapshot carries no .git), so the SESSION's head is written here, next to the artefacts, by

@@ -6,6 +6,7 @@
 #          [AB="workload:spec;spec ..."] [GRID=1] bash scripts/gpu_round.sh
 mkdir -p gpurun_out
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$PWD
+O=$(python "$R/scripts/collect_profiles.py" --src)     # the scratch folder collect_profiles.py copies from
 if [ -n "$TESTS" ]; then
   timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 < /dev/null | grep -v "^RCCL version\|^HIP version\|^ROCm version\|^Hostname\|^Librccl path\|amdgpu.ids" > gpurun_out/pytest_gpu.log; tail -4 gpurun_out/pytest_gpu.log
   g++ -O2 -std=c++17 -I include -o /tmp/solver_bench.bin scripts/native/solver_bench.cpp -L cfmmrouter.jl_amd -lcfmm_amd -Wl,-rpath,$R/cfmmrouter.jl_amd -Wl,-rpath,/opt/rocm/lib && { for n in 64 256 512; do /tmp/solver_bench.bin $n 20000 40; done; } > gpurun_out/solver_bench.txt 2>&1; cat gpurun_out/solver_bench.txt
@@ -16,11 +17,11 @@ fi
 for w in $FULL; do
   steps=100; [ "$w" = "config3" ] && steps=20      # config3 exactly as the driver runs it (--steps 20 --warmup 5)
   warm=10; [ "$w" = "config3" ] && warm=5
-  timeout 500 python bench.py --steps $steps --warmup $warm --workload $w > gpurun_out/benchfull_$w.log 2>&1 < /dev/null
-  timeout 20 python scripts/show_bench.py gpurun_out/benchfull_$w.log $w < /dev/null
+  timeout 500 python bench.py --full --steps $steps --warmup $warm --workload $w > "$O/benchfull_$w.log" 2>&1 < /dev/null
+  timeout 20 python scripts/show_bench.py "$O/benchfull_$w.log" $w < /dev/null
 done
 if [ -n "$GRID" ]; then
-  timeout 900 python bench.py --workload scaling > gpurun_out/benchfull_scaling.log 2>&1 < /dev/null; tail -c 600 gpurun_out/benchfull_scaling.log
+  timeout 900 python bench.py --full --workload scaling > "$O/benchfull_scaling.log" 2>&1 < /dev/null; tail -c 600 "$O/benchfull_scaling.log"
 fi
 if [ -n "$AB" ]; then   # AB="product1m:;max_grid=512 config3:;max_grid=768"  (specs separated by ';', '' = defaults), warm then HBM-resident
   for item in $AB; do

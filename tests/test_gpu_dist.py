@@ -7,7 +7,9 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -48,7 +50,7 @@ def test_sharded_paths_world1_rccl_and_peer():
 def test_bench_under_torchrun_world1(extra):
     """bench.py exactly as the driver launches it for N > 1, at N = 1: RCCL init, the collective in the
     timed step, the self-check against a plain all-reduce, the sharded route! leg."""
-    r = _torchrun([os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3",
+    r = _torchrun([os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "20", "--warmup", "3",
                    "--workload", "config4shard"] + extra)
     print(r.stdout[-2000:], r.stderr[-3000:])
     assert r.returncode == 0
@@ -72,9 +74,9 @@ def test_bench_under_torchrun_world1(extra):
 
 
 def test_bench_single_process_multi_device_and_cold_only():
-    """bench.py --single-process (cfmm_ctx_create_multi, here 3 shards on the one GPU) and --cold-only."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "3", "--single-process", "--devices",
-                        "0,0,0", "--steps", "10", "--warmup", "2", "--workload", "config4shard"],
+    """bench.py --full --single-process (cfmm_ctx_create_multi, here 3 shards on the one GPU) and --cold-only."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "3", "--single-process",
+                        "--devices", "0,0,0", "--steps", "10", "--warmup", "2", "--workload", "config4shard"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     print(r.stdout[-1500:], r.stderr[-2000:])
     assert r.returncode == 0
@@ -82,8 +84,8 @@ def test_bench_single_process_multi_device_and_cold_only():
     assert line["n_gpus"] == 3 and line["config"]["pools_total"] == 1_500_000
     assert "cfmm_ctx_create_multi" in line["config"]["sharding"] and line["route"]["evaluations"] >= 5
     json.dump(line, open(os.path.join(ROOT, "gpurun_out", "bench_single_process_3shards.json"), "w"), indent=1)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "6", "--cold-only",
-                        "--no-cpu", "--workload", "product1m"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "6",
+                        "--cold-only", "--no-cpu", "--workload", "product1m"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     print(r.stdout[-1500:], r.stderr[-2000:])
     assert r.returncode == 0
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -91,11 +93,38 @@ def test_bench_single_process_multi_device_and_cold_only():
     assert 0.2 < line["roofline"]["frac"] < 1.0
 
 
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """The driver's command without --full: set-up, warm-up, the timed steps, --dump-outputs and the headline line -- none of
+    the legs --full adds, and at most 30 s of the run's wall-clock outside its warm-up and timed steps."""
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    wall = time.perf_counter() - t0
+    print(r.stdout[-1500:], r.stderr[-2000:])
+    assert r.returncode == 0
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["metric"].startswith("find_arb! pools/sec") and line["unit"] == "pools/s" and line["higher_is_better"]
+    assert line["dtype"] == "f64" and (line["steps"], line["warmup"], line["n_gpus"]) == (20, 5, 1)
+    assert line["config"]["workload"].startswith("config3") and not line["config"]["full"]
+    m = line["config"]["pools_total"]
+    assert m == 1_000_000 and line["value"] == pytest.approx(m / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    moved = {"roofline", "route", "cpu_baseline", "parity", "host_boundary", "configs", "value_hbm_resident",
+             "collective_check_rel_err", "collectives", "strong_scaling", "route_sharded", "plain_n1"}
+    assert not moved & set(line), moved & set(line)
+    psi, acc = np.load(tmp_path / "netflows.npy"), np.load(tmp_path / "dual_value.npy")
+    D, L = np.load(tmp_path / "trades_delta.npy"), np.load(tmp_path / "trades_lambda.npy")
+    assert psi.shape == (256,) and acc.shape == (1,) and D.shape == L.shape == (m, 2)
+    assert np.isfinite(psi).all() and np.isfinite(acc).all() and np.abs(psi).max() > 0
+    outside = wall - (line["steps"] + line["warmup"]) * line["ms_per_step"] * 1e-3
+    print(f"plain run: {wall:.1f} s wall, {outside:.1f} s outside the steps")
+    assert outside <= 30.0
+
+
 def test_bench_default_line_and_reference_grid():
-    """The driver's command (N = 1, config3) carries the round-4 fields -- parity by convergence, the fraction of the bus
-    from live PMC bytes (or the committed fall-back), an HBM-resident step without kernel events -- and
-    `--workload scaling` reproduces the reference's own benchmark grid (benchmark/scaling.jl:8-38): 30 points."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"],
+    """The driver's command with --full (N = 1, config3) carries the round-4 fields -- parity by convergence, the fraction of
+    the bus from live PMC bytes (or the committed fall-back), an HBM-resident step without kernel events -- and
+    `--workload scaling --full` reproduces the reference's own benchmark grid (benchmark/scaling.jl:8-38): 30 points."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     print(r.stdout[-1500:], r.stderr[-2000:])
     assert r.returncode == 0
@@ -117,7 +146,7 @@ def test_bench_default_line_and_reference_grid():
     assert par["netflow_rel_err_at_fixed_v"] <= 1e-12 and par["route_native_netflow_rel_err"] <= 1e-6
     assert par["route_converged_netflow_rel_err"] <= 1e-8
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["value"] > 0
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "scaling"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "scaling"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     print(r.stdout[-800:], r.stderr[-2000:])
     assert r.returncode == 0
@@ -205,8 +234,8 @@ def test_bench_rehearsal_world2_on_one_gpu():
     the strong-scaling leg (config 4 divided among the ranks).  Timings of such a run mean nothing (`config.rehearsal`);
     what is asserted is that the line exists and that its parity figures are those of an N = 1 run."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2",
-           "--opt", "armed=0"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10",
+           "--warmup", "2", "--opt", "armed=0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, CFMM_BENCH_SHARE_GPU="1"))
     print(r.stdout[-2000:], r.stderr[-3000:])

@@ -371,6 +371,15 @@ def test_bench_self_spawns_one_rank_per_gpu(tmp_path):
         assert "[rank 0/2] bench.py needs an MI355X" in out or "[rank 1/2] bench.py needs an MI355X" in out
 
 
+def test_bench_offers_full():
+    """A plain bench run is the headline alone; every other leg is behind --full."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300,
+                       cwd=ROOT)
+    assert r.returncode == 0 and "--full" in r.stdout
+
+
 def test_univ3_ticks_visited_bookkeeping_matches_the_oracle_walk():
     """bench.py prices a multi-tick UniV3 sweep by the ticks the walk VISITS (32 B + 16 B per tick): the
     bookkeeping function must agree with what find_arb! (src/cfmms.jl:339-395, CPU restatement) does -- a pool counted
