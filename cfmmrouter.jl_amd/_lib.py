@@ -155,6 +155,20 @@ def f64(a, shape=None):
     return a if shape is None else a.reshape(shape)
 
 
+def _ncoin_arrays(R, gamma, Ai0, coins, pools, shape_error):
+    """The arrays of m N-coin pools (Context.add_weighted, add_curve): R, Ai0 and `coins` [m, n]; gamma and `pools` [m].
+    Returns m, n, R, gamma, Ai0 (int32), coins, pools, all contiguous."""
+    gamma = f64(gamma)
+    m = gamma.size
+    R = f64(R)
+    n = R.shape[1] if R.ndim == 2 else (R.size // m if m else 0)
+    Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
+    coins, pools = [f64(a) for a in coins], [f64(a) for a in pools]
+    if any(a.size != n * m for a in (R, Ai0, *coins)) or any(a.size != m for a in pools):
+        raise ArgumentError(shape_error)
+    return m, int(n), R, gamma, Ai0, coins, pools
+
+
 def ptr(a):
     if a is None:
         return None
@@ -266,27 +280,14 @@ class Context:
 
     def add_weighted(self, R, w, gamma, Ai0):
         """m weighted pools of n coins each: R, w, Ai0 [m, n] (cfmm_pools_add_weighted)."""
-        gamma = f64(gamma)
-        m = gamma.size
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        n = R.shape[1] if R.ndim == 2 else (R.size // m if m else 0)
-        R, w = f64(R), f64(w)
-        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
-        if R.size != n * m or w.size != n * m or Ai0.size != n * m:
-            raise ArgumentError("R, w and Ai must have shape [m, n_coins]")
-        self._check(self._L.cfmm_pools_add_weighted(self._h, m, int(n), ptr(R), ptr(w), ptr(gamma), ptr(Ai0)))
+        m, n, R, gamma, Ai0, (w,), _ = _ncoin_arrays(R, gamma, Ai0, [w], [], "R, w and Ai must have shape [m, n_coins]")
+        self._check(self._L.cfmm_pools_add_weighted(self._h, m, n, ptr(R), ptr(w), ptr(gamma), ptr(Ai0)))
 
     def add_curve(self, R, gamma, Ai0, alpha, beta):
         """m Curve pools of n coins each: R, Ai0 [m, n]; gamma, alpha, beta [m] (cfmm_pools_add_curve)."""
-        gamma, alpha, beta = f64(gamma), f64(alpha), f64(beta)
-        m = gamma.size
-        R = np.ascontiguousarray(R, dtype=np.float64)
-        n = R.shape[1] if R.ndim == 2 else (R.size // m if m else 0)
-        R = f64(R)
-        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
-        if R.size != n * m or Ai0.size != n * m or alpha.size != m or beta.size != m:
-            raise ArgumentError("R and Ai must have shape [m, n_coins], gamma, alpha and beta shape [m]")
-        self._check(self._L.cfmm_pools_add_curve(self._h, m, int(n), ptr(R), ptr(gamma), ptr(Ai0), ptr(alpha), ptr(beta)))
+        m, n, R, gamma, Ai0, _, (alpha, beta) = _ncoin_arrays(
+            R, gamma, Ai0, [], [alpha, beta], "R and Ai must have shape [m, n_coins], gamma, alpha and beta shape [m]")
+        self._check(self._L.cfmm_pools_add_curve(self._h, m, n, ptr(R), ptr(gamma), ptr(Ai0), ptr(alpha), ptr(beta)))
 
     def clear(self):
         self._check(self._L.cfmm_pools_clear(self._h))

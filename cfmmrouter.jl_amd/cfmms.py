@@ -258,6 +258,28 @@ def BoundedProduct(current_price, p_lower, p_upper, liquidity, γ, Ai):
     return UniV3(current_price, [p_upper, p_lower], [liquidity, 0.0], γ, Ai)
 
 
+# The per-pool fields of a batch of each kind, in the argument order of the kind's pool type (PoolBatch[i] builds one from
+# them).  "R", "w" and "Ai" are [m, n_coins], every other field [m]; a UniV3 batch also holds its pools' ticks as a CSR
+# (tick_off [m + 1], lower_ticks, liquidity).
+_FIELDS = {
+    KIND_PRODUCT: ("R", "γ", "Ai"),
+    KIND_GEOMEAN: ("R", "w", "γ", "Ai"),
+    KIND_WEIGHTED: ("R", "w", "γ", "Ai"),
+    KIND_CURVE: ("R", "γ", "Ai", "α", "β"),
+    KIND_UNIV3: ("current_price", "γ", "Ai"),
+}
+_COIN_FIELDS = ("R", "w", "Ai")
+_POOL_TYPE = {KIND_PRODUCT: ProductTwoCoin, KIND_GEOMEAN: GeometricMeanTwoCoin, KIND_WEIGHTED: GeometricMean, KIND_CURVE: Curve}
+_NCOIN_NAME = {KIND_WEIGHTED: "weighted", KIND_CURVE: "Curve"}
+# value checks of N-coin batches, in order: field, zero allowed, message
+_NCOIN_CHECKS = (("R", False, "reserves must be finite and > 0"), ("w", False, "weights must be finite and > 0"),
+                 ("α", True, "α must be finite and >= 0"), ("β", False, "β must be finite and > 0"))
+
+
+def _and(names):
+    return names[0] if len(names) == 1 else ", ".join(names[:-1]) + " and " + names[-1]
+
+
 class PoolBatch:
     """m pools of one family, structure-of-arrays (the HBM layout, on the host).
 
@@ -268,48 +290,41 @@ class PoolBatch:
         self.kind = kind
         self.γ = np.ascontiguousarray(a["γ"], dtype=np.float64).reshape(-1)
         m = self.γ.size
-        if kind in (KIND_WEIGHTED, KIND_CURVE):
-            self._init_weighted(m, a)
+        if kind in _NCOIN_NAME:
+            self._init_ncoin(m, a)
             return
-        self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, 2)
-        if kind in (KIND_PRODUCT, KIND_GEOMEAN):
-            self.R = np.ascontiguousarray(a["R"], dtype=np.float64).reshape(m, 2)
-        if kind == KIND_GEOMEAN:
-            self.w = np.ascontiguousarray(a["w"], dtype=np.float64).reshape(m, 2)
+        for f in _FIELDS[kind]:
+            if f != "γ":
+                self._set(f, a, m, 2)
         if kind == KIND_UNIV3:
-            self.current_price = np.ascontiguousarray(a["current_price"], dtype=np.float64).reshape(m)
             self.tick_off = np.ascontiguousarray(a["tick_off"], dtype=np.int64).reshape(m + 1)
             self.lower_ticks = np.ascontiguousarray(a["lower_ticks"], dtype=np.float64).reshape(-1)
             self.liquidity = np.ascontiguousarray(a["liquidity"], dtype=np.float64).reshape(-1)
 
-    def _init_weighted(self, m, a):
+    def _set(self, f, a, m, n):
+        """self.f <- a[f] as [m, n] (per-coin fields) or [m]"""
+        x = np.ascontiguousarray(a[f], dtype=np.int64 if f == "Ai" else np.float64)
+        setattr(self, f, x.reshape((m, n) if f in _COIN_FIELDS else m))
+
+    def _init_ncoin(self, m, a):
         """KIND_WEIGHTED (R, w, Ai [m, n]) and KIND_CURVE (R, Ai [m, n]; α, β [m])"""
-        curve = self.kind == KIND_CURVE
-        fam = "Curve" if curve else "weighted"
+        fam = _NCOIN_NAME[self.kind]
+        fields = [f for f in _FIELDS[self.kind] if f != "γ"]
         R = np.asarray(a["R"], dtype=np.float64)
         n = R.shape[-1] if R.ndim == 2 else (R.size // m if m else 2)
         if not 2 <= n <= MAX_COINS:
             raise ArgumentError(f"{fam} pools have 2..{MAX_COINS} coins, got {n}")
         try:
-            self.R = np.ascontiguousarray(R).reshape(m, n)
-            if curve:
-                self.α = np.ascontiguousarray(a["α"], dtype=np.float64).reshape(m)
-                self.β = np.ascontiguousarray(a["β"], dtype=np.float64).reshape(m)
-            else:
-                self.w = np.ascontiguousarray(a["w"], dtype=np.float64).reshape(m, n)
-            self.Ai = np.ascontiguousarray(a["Ai"], dtype=np.int64).reshape(m, n)
+            for f in fields:
+                self._set(f, a, m, n)
         except ValueError:
-            raise ArgumentError(f"R{'' if curve else ', w'} and Ai of a {fam} batch must have shape [m, n_coins]"
-                                + (", α and β shape [m]" if curve else "")) from None
-        if not np.all(np.isfinite(self.R)) or np.any(self.R <= 0):
-            raise ArgumentError("reserves must be finite and > 0")
-        if curve:
-            if not np.all(np.isfinite(self.α)) or np.any(self.α < 0):
-                raise ArgumentError("α must be finite and >= 0")
-            if not np.all(np.isfinite(self.β)) or np.any(self.β <= 0):
-                raise ArgumentError("β must be finite and > 0")
-        elif not np.all(np.isfinite(self.w)) or np.any(self.w <= 0):
-            raise ArgumentError("weights must be finite and > 0")
+            per_pool = [f for f in fields if f not in _COIN_FIELDS]
+            raise ArgumentError(f"{_and([f for f in fields if f in _COIN_FIELDS])} of a {fam} batch must have shape [m, n_coins]"
+                                + (f", {_and(per_pool)} shape [m]" if per_pool else "")) from None
+        for f, zero_ok, msg in _NCOIN_CHECKS:
+            x = getattr(self, f) if f in fields else None
+            if x is not None and (not np.all(np.isfinite(x)) or np.any(x < 0 if zero_ok else x <= 0)):
+                raise ArgumentError(msg)
         if np.any(~(self.γ > 0)) or np.any(self.γ > 1):
             raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
         if m and np.any(np.sort(self.Ai, axis=1)[:, 1:] == np.sort(self.Ai, axis=1)[:, :-1]):
@@ -326,29 +341,18 @@ class PoolBatch:
         i = int(i)
         if i < 0:
             i += len(self)
-        if self.kind == KIND_PRODUCT:
-            return ProductTwoCoin(self.R[i], self.γ[i], self.Ai[i])
-        if self.kind == KIND_GEOMEAN:
-            return GeometricMeanTwoCoin(self.R[i], self.w[i], self.γ[i], self.Ai[i])
-        if self.kind == KIND_WEIGHTED:
-            return GeometricMean(self.R[i], self.w[i], self.γ[i], self.Ai[i])
-        if self.kind == KIND_CURVE:
-            return Curve(self.R[i], self.γ[i], self.Ai[i], self.α[i], self.β[i])
-        o, e = self.tick_off[i], self.tick_off[i + 1]
-        return UniV3(self.current_price[i], self.lower_ticks[o:e], self.liquidity[o:e], self.γ[i], self.Ai[i])
+        if self.kind == KIND_UNIV3:
+            o, e = self.tick_off[i], self.tick_off[i + 1]
+            return UniV3(self.current_price[i], self.lower_ticks[o:e], self.liquidity[o:e], self.γ[i], self.Ai[i])
+        return _POOL_TYPE[self.kind](*(getattr(self, f)[i] for f in _FIELDS[self.kind]))
 
     def slice(self, lo, hi):
         """Pools [lo, hi) as a new batch (used to shard a market across GPUs)."""
-        if self.kind == KIND_PRODUCT:
-            return PoolBatch(self.kind, R=self.R[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
-        if self.kind in (KIND_GEOMEAN, KIND_WEIGHTED):
-            return PoolBatch(self.kind, R=self.R[lo:hi], w=self.w[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
-        if self.kind == KIND_CURVE:
-            return PoolBatch(self.kind, R=self.R[lo:hi], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi], α=self.α[lo:hi], β=self.β[lo:hi])
-        o, e = self.tick_off[lo], self.tick_off[hi]
-        return PoolBatch(self.kind, current_price=self.current_price[lo:hi],
-                         tick_off=self.tick_off[lo:hi + 1] - o, lower_ticks=self.lower_ticks[o:e],
-                         liquidity=self.liquidity[o:e], γ=self.γ[lo:hi], Ai=self.Ai[lo:hi])
+        part = {f: getattr(self, f)[lo:hi] for f in _FIELDS[self.kind]}
+        if self.kind == KIND_UNIV3:
+            o, e = self.tick_off[lo], self.tick_off[hi]
+            part.update(tick_off=self.tick_off[lo:hi + 1] - o, lower_ticks=self.lower_ticks[o:e], liquidity=self.liquidity[o:e])
+        return PoolBatch(self.kind, **part)
 
     @staticmethod
     def concat(batches):
@@ -357,45 +361,29 @@ class PoolBatch:
         kind = batches[0].kind
         if any(b.kind != kind for b in batches):
             raise ArgumentError("concat needs batches of one pool family")
-        if kind in (KIND_WEIGHTED, KIND_CURVE) and len({b.n_coins for b in batches}) > 1:
+        if kind in _NCOIN_NAME and len({b.n_coins for b in batches}) > 1:
             raise ArgumentError("concat needs weighted / Curve batches of one coin count")
         cat = lambda name: np.concatenate([getattr(b, name) for b in batches])
-        if kind == KIND_PRODUCT:
-            return PoolBatch(kind, R=cat("R"), γ=cat("γ"), Ai=cat("Ai"))
-        if kind in (KIND_GEOMEAN, KIND_WEIGHTED):
-            return PoolBatch(kind, R=cat("R"), w=cat("w"), γ=cat("γ"), Ai=cat("Ai"))
-        if kind == KIND_CURVE:
-            return PoolBatch(kind, R=cat("R"), γ=cat("γ"), Ai=cat("Ai"), α=cat("α"), β=cat("β"))
-        off, base = [np.zeros(1, dtype=np.int64)], 0
-        for b in batches:
-            off.append(b.tick_off[1:] + base)
-            base += int(b.tick_off[-1])
-        return PoolBatch(kind, current_price=cat("current_price"), tick_off=np.concatenate(off),
-                         lower_ticks=cat("lower_ticks"), liquidity=cat("liquidity"), γ=cat("γ"), Ai=cat("Ai"))
+        whole = {f: cat(f) for f in _FIELDS[kind]}
+        if kind == KIND_UNIV3:
+            off, base = [np.zeros(1, dtype=np.int64)], 0
+            for b in batches:
+                off.append(b.tick_off[1:] + base)
+                base += int(b.tick_off[-1])
+            whole.update(tick_off=np.concatenate(off), lower_ticks=cat("lower_ticks"), liquidity=cat("liquidity"))
+        return PoolBatch(kind, **whole)
 
     @staticmethod
     def from_pools(kind, pools):
-        if kind == KIND_PRODUCT:
-            return PoolBatch(kind, R=[p.R for p in pools], γ=[p.γ for p in pools], Ai=[p.Ai for p in pools])
-        if kind == KIND_GEOMEAN:
-            return PoolBatch(kind, R=[p.R for p in pools], w=[p.w for p in pools], γ=[p.γ for p in pools],
-                             Ai=[p.Ai for p in pools])
-        if kind == KIND_WEIGHTED:
-            if len({len(p.Ai) for p in pools}) > 1:
-                raise ArgumentError("one weighted batch holds pools of one coin count (group them by len(Ai))")
-            return PoolBatch(kind, R=[p.R for p in pools], w=[p.w for p in pools], γ=[p.γ for p in pools],
-                             Ai=[p.Ai for p in pools])
-        if kind == KIND_CURVE:
-            if len({len(p.Ai) for p in pools}) > 1:
-                raise ArgumentError("one Curve batch holds pools of one coin count (group them by len(Ai))")
-            return PoolBatch(kind, R=[p.R for p in pools], γ=[p.γ for p in pools], Ai=[p.Ai for p in pools],
-                             α=[p.α for p in pools], β=[p.β for p in pools])
-        off = np.zeros(len(pools) + 1, dtype=np.int64)
-        np.cumsum([p.lower_ticks.size for p in pools], out=off[1:])
-        return PoolBatch(kind, current_price=[p.current_price for p in pools], tick_off=off,
-                         lower_ticks=np.concatenate([p.lower_ticks for p in pools]) if pools else [],
-                         liquidity=np.concatenate([p.liquidity for p in pools]) if pools else [],
-                         γ=[p.γ for p in pools], Ai=[p.Ai for p in pools])
+        if kind in _NCOIN_NAME and len({len(p.Ai) for p in pools}) > 1:
+            raise ArgumentError(f"one {_NCOIN_NAME[kind]} batch holds pools of one coin count (group them by len(Ai))")
+        fields = {f: [getattr(p, f) for p in pools] for f in _FIELDS[kind]}
+        if kind == KIND_UNIV3:
+            off = np.zeros(len(pools) + 1, dtype=np.int64)
+            np.cumsum([p.lower_ticks.size for p in pools], out=off[1:])
+            fields.update(tick_off=off, lower_ticks=np.concatenate([p.lower_ticks for p in pools]) if pools else [],
+                          liquidity=np.concatenate([p.liquidity for p in pools]) if pools else [])
+        return PoolBatch(kind, **fields)
 
 
 def zerotrade(c):

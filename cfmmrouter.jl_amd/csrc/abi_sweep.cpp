@@ -38,7 +38,7 @@ int fused_grid_cap(const cfmm_ctx* c, int block)
 // (and the fold kernel) small.  Large-market mode (global bins) uses 512-thread blocks throughout.
 void plan_segment(const cfmm_ctx* c, Segment& s)
 {
-    // weighted / Curve segments: their own launch of 512-thread blocks (sweep_weighted, sweep_curve), never single-block direct
+    // N-coin segments (weighted, Curve): their own launch of 512-thread blocks (sweep_ncoin), never single-block direct
     if (ragged_kind(s.kind)) {
         const int64_t tiles = std::max<int64_t>(1, (s.m + kMidBlock - 1) / kMidBlock);
         s.block = kMidBlock;
@@ -219,7 +219,7 @@ int ensure_geometry(cfmm_ctx* c)
     }
     c->groups.clear();
     const bool fusable = c->opt_fuse_segments != 0 && n_two_coin >= 2 && c->opt_geomean_exact == 0;
-    // launch groups: every weighted / Curve segment alone (sweep_weighted, sweep_curve); runs of consecutive two-coin segments
+    // launch groups: every N-coin segment alone (sweep_ncoin); runs of consecutive two-coin segments
     // fused by up to kMaxMulti (sweep_multi) or one launch each
     for (size_t run = 0; run < c->segs.size();) {
         if (ragged_kind(c->segs[run].kind)) {
@@ -318,12 +318,10 @@ int ensure_geometry(cfmm_ctx* c)
     c->trade_rows = trades;
     c->flat_total = flat;
     c->touched_bytes = 0;
-    for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3);
-                                    // weighted: per coin R, q, w, token (28 B) + {γ, log γ} per pool, and 16 B per coin written;
-                                    // Curve: per coin R, log R, token (20 B) + {α, log β}, {γ, log γ}, and 16 B per coin written
-        c->touched_bytes += s.m * (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
-                                            : s.kind == CFMM_KIND_WEIGHTED ? 44 * s.n_coins + 16
-                                            : s.kind == CFMM_KIND_CURVE ? 36 * s.n_coins + 32 : (s.has_walk ? 104 : 56) + 16);
+    for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3)
+        c->touched_bytes += s.m * (ragged_kind(s.kind) ? ncoin_family(s.kind).bytes_per_pool(s.n_coins)
+                                   : (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
+                                               : (s.has_walk ? 104 : 56) + 16));
     if (rows > c->rows_cap) {
         (void)hipFree(c->d_partials);
         c->d_partials = nullptr;
@@ -395,7 +393,8 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
         if (!gb)
             for (int k = 0; k < g.nseg; ++k) {
                 const int kind = c->segs[(size_t)g.first + k].kind;
-                if ((kind == CFMM_KIND_GEOMEAN && c->opt_geomean_exact == 0) || kind == CFMM_KIND_WEIGHTED) a.need_logv = 1;
+                if ((kind == CFMM_KIND_GEOMEAN && c->opt_geomean_exact == 0) || (ragged_kind(kind) && ncoin_family(kind).need_logv))
+                    a.need_logv = 1;
             }
         if (a.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, a.gtab_n, a.v_shift == 4 ? 1 : 0) > 160 * 1024)
             a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
@@ -448,6 +447,10 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
             return UniV3Pools{s.pg, s.Ai, s.cur_a, s.cur_b, s.cur_c, s.curR, s.walk, s.ticks, s.thr,
                               c->opt_univ3_heads != 0 ? s.head : nullptr, s.has_walk, s.cp, s.pk, gbase_of(s)};
         };
+        auto ncoin_of = [&](const Segment& s) {
+            return NCoinPools{s.nc.R, s.nc.q, s.nc.tok, s.nc.glg, s.nc.par, s.n_coins, materialize ? s.nc.D : nullptr,
+                              materialize ? s.nc.L : nullptr};
+        };
         hipError_t e = hipSuccess;
         if (g.multi) {
             MultiArgs ma;
@@ -484,21 +487,10 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
             a.Over = materialize ? c->d_over + s.trade_off : nullptr;
             a.gflow = gb ? c->d_flow + s.trade_off : nullptr;
             LaunchCfg cfg{g.block, g.grid, lds, arith, ea, eb};
-            switch (s.kind) {
-            case CFMM_KIND_PRODUCT: e = launch_sweep(product_of(s), a, cfg, materialize, c->stream); break;
-            case CFMM_KIND_GEOMEAN: e = launch_sweep(geomean_of(s), a, cfg, materialize, c->stream); break;
-            case CFMM_KIND_WEIGHTED:
-                e = launch_sweep(WeightedPools{s.wR, s.wq, s.ww, s.wtok, s.glg, s.n_coins, materialize ? s.wD : nullptr,
-                                               materialize ? s.wL : nullptr},
-                                 a, cfg, materialize, c->stream);
-                break;
-            case CFMM_KIND_CURVE:
-                e = launch_sweep(CurvePools{s.wR, s.wq, s.wtok, s.cab, s.glg, s.n_coins, materialize ? s.wD : nullptr,
-                                            materialize ? s.wL : nullptr},
-                                 a, cfg, materialize, c->stream);
-                break;
-            default: e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream); break;
-            }
+            if (ragged_kind(s.kind)) e = launch_sweep_ncoin(s.kind, ncoin_of(s), a, cfg, materialize, c->stream);
+            else if (s.kind == CFMM_KIND_PRODUCT) e = launch_sweep(product_of(s), a, cfg, materialize, c->stream);
+            else if (s.kind == CFMM_KIND_GEOMEAN) e = launch_sweep(geomean_of(s), a, cfg, materialize, c->stream);
+            else e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream);
         }
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
         if (ea && eb) c->pending.push_back({ea, eb, 0});

@@ -138,8 +138,8 @@ int download_segment(cfmm_ctx* c, const Segment& s, int64_t first, int64_t count
 {
     if (!ragged_kind(s.kind)) return download_trades(c, s.trade_off + first, count, Delta, Lambda);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int rc = download_coin_major(c, s.wD, s.m, s.n_coins, first, count, Delta);
-    return rc != CFMM_OK ? rc : download_coin_major(c, s.wL, s.m, s.n_coins, first, count, Lambda);
+    int rc = download_coin_major(c, s.nc.D, s.m, s.n_coins, first, count, Delta);
+    return rc != CFMM_OK ? rc : download_coin_major(c, s.nc.L, s.m, s.n_coins, first, count, Lambda);
 }
 
 } // namespace
@@ -303,12 +303,8 @@ int cfmm_update_reserves(cfmm_ctx* c)
     for (size_t k = 0; k < c->segs.size() && e == hipSuccess; ++k) {
         Segment& s = c->segs[k];
         if (s.kind == CFMM_KIND_UNIV3) continue;
-        if (s.kind == CFMM_KIND_WEIGHTED) {
-            e = launch_update_weighted(s.wR, s.wq, s.ww, s.glg, s.wD, s.wL, s.n_coins, s.m, c->stream);
-            continue;
-        }
-        if (s.kind == CFMM_KIND_CURVE) {
-            e = launch_update_curve(s.wR, s.wq, s.glg, s.wD, s.wL, s.n_coins, s.m, c->stream);
+        if (ragged_kind(s.kind)) {
+            e = launch_update_ncoin(s.kind, s.nc.R, s.nc.q, s.nc.par, s.nc.glg, s.nc.D, s.nc.L, s.n_coins, s.m, c->stream);
             continue;
         }
         e = launch_update_two_coin(s.R, s.gamma, c->d_delta + s.trade_off, c->d_lambda + s.trade_off, c->d_over + s.trade_off,
@@ -364,7 +360,7 @@ int cfmm_get_reserves(cfmm_ctx* c, int32_t seg, double* R)
     if (s.kind == CFMM_KIND_UNIV3) return fail(c, CFMM_ERR_INVALID_ARG, "UniV3 segments have prices, not reserves: cfmm_get_prices");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (ragged_kind(s.kind)) return download_coin_major(c, s.wR, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
+    if (ragged_kind(s.kind)) return download_coin_major(c, s.nc.R, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
     HIP_TRY(c, hipMemcpy(R, s.R, (size_t)s.m * sizeof(double2), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }

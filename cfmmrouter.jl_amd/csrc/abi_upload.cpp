@@ -153,6 +153,91 @@ int add_segment_common(cfmm_ctx* c, Segment&& s, const int32_t* Ai)
     return CFMM_OK;
 }
 
+// The checks cfmm_pools_add_weighted and cfmm_pools_add_curve share, in this order: the arguments (arrays: no pool array is
+// null), then pool by pool each coin's reserve, the family's own check of that coin (coin_ok(i, j), j = i·n_coins + k),
+// its token index (range, distinct within the pool), then the family's own checks of the pool (pool_ok(i)) and its fee.
+// coin_ok / pool_ok return CFMM_OK or fail(...).
+template <class CoinOk, class PoolOk>
+int ncoin_check(cfmm_ctx* c, int kind, int64_t m, int32_t n_coins, const double* R, const double* gamma, const int32_t* Ai,
+                bool arrays, CoinOk coin_ok, PoolOk pool_ok)
+{
+    const char* fam = ncoin_family(kind).name;
+    if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
+    if (n_coins < 2 || n_coins > kMaxCoins)
+        return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: %s pools have 2 .. %d coins", (int)n_coins, fam, kMaxCoins);
+    if (c->n > kMaxLdsTokens)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "%s pools need n_tokens <= %d (large-market mode sweeps two-coin pools only)", fam,
+                    kMaxLdsTokens);
+    if (m > 0 && !arrays) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
+    const int nc = n_coins;
+    int rc;
+    for (int64_t i = 0; i < m; ++i) {
+        for (int k = 0; k < nc; ++k) {
+            const size_t j = (size_t)(i * nc + k);
+            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
+            if ((rc = coin_ok(i, j)) != CFMM_OK) return rc;
+            const int32_t a = Ai[j];
+            if (a < 0 || a >= c->n)
+                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: token index out of range [0, %d)", (long long)i, c->n);
+            for (int k2 = 0; k2 < k; ++k2)
+                if (Ai[(size_t)(i * nc + k2)] == a)
+                    return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the token indices must be distinct", (long long)i);
+        }
+        if ((rc = pool_ok(i)) != CFMM_OK) return rc;
+        if (!finite_pos(gamma[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
+        if (gamma[i] > 1.0)
+            return fail(c, CFMM_ERR_INVALID_ARG,
+                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
+                        (long long)i);
+    }
+    return CFMM_OK;
+}
+
+// The upload of m checked N-coin pools: coin-major columns (sweep.h NCoinPools) of R, tokens, the family's per-coin constant
+// q and its own column par, filled pool by pool by fill(i, q, par) (q[0 .. n_coins), par[0 .. par_per_pool)), {γ, log γ},
+// the segment's trade arrays, and the segment itself
+template <class Fill>
+int ncoin_add(cfmm_ctx* c, int kind, int64_t m, int nc, const double* R, const double* gamma, const int32_t* Ai, Fill fill)
+{
+    const NCoinFamily fam = ncoin_family(kind);
+    const size_t cells = (size_t)m * (size_t)nc, np = (size_t)fam.par_per_pool(nc);
+    std::vector<double> cR(cells), cq(cells), cpar((size_t)m * np);
+    std::vector<int32_t> ct(cells);
+    std::vector<double2> glg((size_t)m);
+    for (int64_t i = 0; i < m; ++i) {
+        double q[kMaxCoins], par[kMaxCoins];
+        fill(i, q, par);
+        for (int k = 0; k < nc; ++k) {
+            const size_t src = (size_t)(i * nc + k), dst = (size_t)k * (size_t)m + (size_t)i;
+            cR[dst] = R[src];
+            cq[dst] = q[k];
+            ct[dst] = Ai[src];
+        }
+        for (size_t k = 0; k < np; ++k) cpar[fam.par_coin_major ? k * (size_t)m + (size_t)i : (size_t)i * np + k] = par[k];
+        glg[(size_t)i] = make_double2(gamma[i], std::log(gamma[i]));
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    Segment s;
+    s.kind = kind;
+    s.m = m;
+    s.n_coins = nc;
+    s.fast_ok = 0;   // one arithmetic only (the compiler's)
+    int rc;
+    if ((rc = upload(c, &s.nc.R, cR.data(), cells)) || (rc = upload(c, &s.nc.q, cq.data(), cells)) ||
+        (rc = upload(c, &s.nc.tok, ct.data(), cells)) || (rc = upload(c, &s.nc.par, cpar.data(), cpar.size())) ||
+        (rc = upload(c, &s.nc.glg, glg.data(), (size_t)m))) {
+        free_segment(s);
+        return rc;
+    }
+    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.nc.D), cells * sizeof(double)) != hipSuccess ||
+                      hipMalloc(reinterpret_cast<void**>(&s.nc.L), cells * sizeof(double)) != hipSuccess)) {
+        (void)hipGetLastError();
+        free_segment(s);
+        return fail(c, CFMM_ERR_HIP, "trade buffers of a %s segment: allocation failed", fam.name);
+    }
+    return add_segment_common(c, std::move(s), Ai);
+}
+
 } // namespace
 
 namespace cfmm {
@@ -164,8 +249,8 @@ void free_segment(Segment& s)
     (void)hipFree(s.cur_a); (void)hipFree(s.cur_b); (void)hipFree(s.cur_c); (void)hipFree(s.curR);
     (void)hipFree(s.pg); (void)hipFree(s.cp); (void)hipFree(s.walk); (void)hipFree(s.ticks); (void)hipFree(s.thr);
     (void)hipFree(s.head);
-    (void)hipFree(s.wR); (void)hipFree(s.wq); (void)hipFree(s.ww); (void)hipFree(s.wtok); (void)hipFree(s.glg);
-    (void)hipFree(s.wD); (void)hipFree(s.wL); (void)hipFree(s.cab);
+    (void)hipFree(s.nc.R); (void)hipFree(s.nc.q); (void)hipFree(s.nc.tok); (void)hipFree(s.nc.glg); (void)hipFree(s.nc.par);
+    (void)hipFree(s.nc.D); (void)hipFree(s.nc.L);
     s = Segment{};
 }
 
@@ -446,147 +531,53 @@ int cfmm_pools_add_weighted(cfmm_ctx* c, int64_t m, int32_t n_coins, const doubl
                             const int32_t* Ai)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
-    if (n_coins < 2 || n_coins > kMaxCoins)
-        return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: weighted pools have 2 .. %d coins", (int)n_coins, kMaxCoins);
-    if (c->n > kMaxLdsTokens)
-        return fail(c, CFMM_ERR_UNSUPPORTED, "weighted pools need n_tokens <= %d (large-market mode sweeps two-coin pools only)",
-                    kMaxLdsTokens);
-    if (m > 0 && (!R || !w || !gamma || !Ai)) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
+    const auto weight_ok = [&](int64_t i, size_t j) {
+        return finite_pos(w[j]) ? CFMM_OK : fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: weights must be finite and > 0", (long long)i);
+    };
+    int rc = ncoin_check(c, CFMM_KIND_WEIGHTED, m, n_coins, R, gamma, Ai, R && w && gamma && Ai, weight_ok,
+                         [](int64_t) { return CFMM_OK; });
+    if (rc != CFMM_OK) return rc;
     const int nc = n_coins;
-    for (int64_t i = 0; i < m; ++i) {
-        for (int k = 0; k < nc; ++k) {
-            const size_t j = (size_t)(i * nc + k);
-            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
-            if (!finite_pos(w[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: weights must be finite and > 0", (long long)i);
-            const int32_t a = Ai[j];
-            if (a < 0 || a >= c->n)
-                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: token index out of range [0, %d)", (long long)i, c->n);
-            for (int k2 = 0; k2 < k; ++k2)
-                if (Ai[(size_t)(i * nc + k2)] == a)
-                    return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the token indices must be distinct", (long long)i);
-        }
-        if (!finite_pos(gamma[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
-        if (gamma[i] > 1.0)
-            return fail(c, CFMM_ERR_INVALID_ARG,
-                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
-                        (long long)i);
-    }
     if (!c->shards.empty())
         return multi_add(c, CFMM_KIND_WEIGHTED, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
             return cfmm_pools_add_weighted(child, hi - lo, n_coins, R + nc * lo, w + nc * lo, gamma + lo, Ai + nc * lo);
         }, nc);
-    // coin-major columns (sweep.h WeightedPools), weights normalised to sum to 1, q = log(R / w)
-    const size_t cells = (size_t)m * (size_t)nc;
-    std::vector<double> cR(cells), cq(cells), cw(cells);
-    std::vector<int32_t> ct(cells);
-    std::vector<double2> glg((size_t)m);
-    for (int64_t i = 0; i < m; ++i) {
+    // weights normalised to sum to 1, q = log(R / w)
+    return ncoin_add(c, CFMM_KIND_WEIGHTED, m, nc, R, gamma, Ai, [&](int64_t i, double* q, double* wn) {
         double ws = 0.0;
         for (int k = 0; k < nc; ++k) ws += w[(size_t)(i * nc + k)];
         for (int k = 0; k < nc; ++k) {
-            const size_t src = (size_t)(i * nc + k), dst = (size_t)k * (size_t)m + (size_t)i;
-            const double wn = w[src] / ws;
-            cR[dst] = R[src];
-            cw[dst] = wn;
-            cq[dst] = std::log(R[src] / wn);
-            ct[dst] = Ai[src];
+            const size_t src = (size_t)(i * nc + k);
+            wn[k] = w[src] / ws;
+            q[k] = std::log(R[src] / wn[k]);
         }
-        glg[(size_t)i] = make_double2(gamma[i], std::log(gamma[i]));
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    Segment s;
-    s.kind = CFMM_KIND_WEIGHTED;
-    s.m = m;
-    s.n_coins = nc;
-    s.fast_ok = 0;   // one arithmetic only (the compiler's)
-    int rc;
-    if ((rc = upload(c, &s.wR, cR.data(), cells)) || (rc = upload(c, &s.wq, cq.data(), cells)) ||
-        (rc = upload(c, &s.ww, cw.data(), cells)) || (rc = upload(c, &s.wtok, ct.data(), cells)) ||
-        (rc = upload(c, &s.glg, glg.data(), (size_t)m))) {
-        free_segment(s);
-        return rc;
-    }
-    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.wD), cells * sizeof(double)) != hipSuccess ||
-                      hipMalloc(reinterpret_cast<void**>(&s.wL), cells * sizeof(double)) != hipSuccess)) {
-        (void)hipGetLastError();
-        free_segment(s);
-        return fail(c, CFMM_ERR_HIP, "trade buffers of a weighted segment: allocation failed");
-    }
-    return add_segment_common(c, std::move(s), Ai);
+    });
 }
 
 int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* R, const double* gamma, const int32_t* Ai,
                          const double* alpha, const double* beta)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
-    if (n_coins < 2 || n_coins > kMaxCoins)
-        return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: Curve pools have 2 .. %d coins", (int)n_coins, kMaxCoins);
-    if (c->n > kMaxLdsTokens)
-        return fail(c, CFMM_ERR_UNSUPPORTED, "Curve pools need n_tokens <= %d (large-market mode sweeps two-coin pools only)",
-                    kMaxLdsTokens);
-    if (m > 0 && (!R || !gamma || !Ai || !alpha || !beta)) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
-    const int nc = n_coins;
-    for (int64_t i = 0; i < m; ++i) {
-        for (int k = 0; k < nc; ++k) {
-            const size_t j = (size_t)(i * nc + k);
-            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
-            const int32_t a = Ai[j];
-            if (a < 0 || a >= c->n)
-                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: token index out of range [0, %d)", (long long)i, c->n);
-            for (int k2 = 0; k2 < k; ++k2)
-                if (Ai[(size_t)(i * nc + k2)] == a)
-                    return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the token indices must be distinct", (long long)i);
-        }
+    const auto ab_ok = [&](int64_t i) {
         if (!std::isfinite(alpha[i]) || alpha[i] < 0.0)
             return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: alpha must be finite and >= 0", (long long)i);
         if (!finite_pos(beta[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: beta must be finite and > 0", (long long)i);
-        if (!finite_pos(gamma[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
-        if (gamma[i] > 1.0)
-            return fail(c, CFMM_ERR_INVALID_ARG,
-                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
-                        (long long)i);
-    }
+        return CFMM_OK;
+    };
+    int rc = ncoin_check(c, CFMM_KIND_CURVE, m, n_coins, R, gamma, Ai, R && gamma && Ai && alpha && beta,
+                         [](int64_t, size_t) { return CFMM_OK; }, ab_ok);
+    if (rc != CFMM_OK) return rc;
+    const int nc = n_coins;
     if (!c->shards.empty())
         return multi_add(c, CFMM_KIND_CURVE, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
             return cfmm_pools_add_curve(child, hi - lo, n_coins, R + nc * lo, gamma + lo, Ai + nc * lo, alpha + lo, beta + lo);
         }, nc);
-    // coin-major columns (sweep.h CurvePools): R, log R, token; per pool {α, log β} and {γ, log γ}
-    const size_t cells = (size_t)m * (size_t)nc;
-    std::vector<double> cR(cells), cl(cells);
-    std::vector<int32_t> ct(cells);
-    std::vector<double2> ab((size_t)m), glg((size_t)m);
-    for (int64_t i = 0; i < m; ++i) {
-        for (int k = 0; k < nc; ++k) {
-            const size_t src = (size_t)(i * nc + k), dst = (size_t)k * (size_t)m + (size_t)i;
-            cR[dst] = R[src];
-            cl[dst] = std::log(R[src]);
-            ct[dst] = Ai[src];
-        }
-        ab[(size_t)i] = make_double2(alpha[i], std::log(beta[i]));
-        glg[(size_t)i] = make_double2(gamma[i], std::log(gamma[i]));
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    Segment s;
-    s.kind = CFMM_KIND_CURVE;
-    s.m = m;
-    s.n_coins = nc;
-    s.fast_ok = 0;   // one arithmetic only (the compiler's)
-    int rc;
-    if ((rc = upload(c, &s.wR, cR.data(), cells)) || (rc = upload(c, &s.wq, cl.data(), cells)) ||
-        (rc = upload(c, &s.wtok, ct.data(), cells)) || (rc = upload(c, &s.cab, ab.data(), (size_t)m)) ||
-        (rc = upload(c, &s.glg, glg.data(), (size_t)m))) {
-        free_segment(s);
-        return rc;
-    }
-    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.wD), cells * sizeof(double)) != hipSuccess ||
-                      hipMalloc(reinterpret_cast<void**>(&s.wL), cells * sizeof(double)) != hipSuccess)) {
-        (void)hipGetLastError();
-        free_segment(s);
-        return fail(c, CFMM_ERR_HIP, "trade buffers of a Curve segment: allocation failed");
-    }
-    return add_segment_common(c, std::move(s), Ai);
+    // q = log R; per pool {α, log β}
+    return ncoin_add(c, CFMM_KIND_CURVE, m, nc, R, gamma, Ai, [&](int64_t i, double* q, double* ab) {
+        for (int k = 0; k < nc; ++k) q[k] = std::log(R[(size_t)(i * nc + k)]);
+        ab[0] = alpha[i];
+        ab[1] = std::log(beta[i]);
+    });
 }
 
 int cfmm_pools_clear(cfmm_ctx* c)

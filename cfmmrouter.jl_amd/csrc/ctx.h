@@ -65,24 +65,37 @@ struct Segment {
     // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
     std::vector<double> h_cp, h_gamma, h_lt, h_liq;
     std::vector<int64_t> h_tick_off;
-    // Weighted (CFMM_KIND_WEIGHTED) and Curve (CFMM_KIND_CURVE) only: coin-major [n_coins][m] columns (sweep.h WeightedPools,
-    // CurvePools) and the segment's own trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is
-    // unused)
+    // N-coin kinds (ragged_kind: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE) only: the coin-major columns and the segment's own
+    // trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
     int n_coins = 2;
     int64_t flat_off = 0;      // first double of this segment in the ragged trade layout of cfmm_get_trades (Σ coins before it)
-    double* wR = nullptr;
-    double* wq = nullptr;
-    double* ww = nullptr;
-    int32_t* wtok = nullptr;
-    double2* glg = nullptr;    // [m] {γ, log γ}
-    double* wD = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
-    double* wL = nullptr;      // [n_coins][m] Λ
-    // Curve (CFMM_KIND_CURVE) segments use the same layout: wR, wq = log R, wtok, glg, wD, wL (no ww), and
-    double2* cab = nullptr;    // [m] {α, log β}
+    struct {
+        double* R = nullptr;   // [n_coins][m] (sweep.h NCoinPools)
+        double* q = nullptr;   // [n_coins][m] the family's per-coin constant
+        int32_t* tok = nullptr;
+        double2* glg = nullptr;   // [m] {γ, log γ}
+        double* par = nullptr;    // the family's own column (NCoinFamily::par_per_pool doubles per pool)
+        double* D = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
+        double* L = nullptr;      // [n_coins][m] Λ
+    } nc;
 };
 
-// Segments whose trades are ragged (n_coins per pool, kept in the segment's own wD / wL): their own launch each.
+// Segments whose trades are ragged (n_coins per pool, kept in the segment's own nc.D / nc.L): their own launch each.
 inline bool ragged_kind(int kind) { return kind == CFMM_KIND_WEIGHTED || kind == CFMM_KIND_CURVE; }
+
+// What the host knows of an N-coin family (ragged_kind); the device side is sweep_kernels.hip's WeightedFamily / CurveFamily.
+struct NCoinFamily {
+    const char* name;          // in error texts
+    bool par_coin_major;       // the family's own column (NCoinPools::par): [n_coins][m] (weights) or [m] pairs ({α, log β})
+    bool need_logv;            // the sweep reads log v from LDS (SweepArgs::need_logv)
+    int64_t par_per_pool(int n_coins) const { return par_coin_major ? n_coins : 2; }
+    // bytes one materialising sweep moves per pool: per coin R, q, token (20 B) read and Δ, Λ (16 B) written, {γ, log γ}, par
+    int64_t bytes_per_pool(int n_coins) const { return 36 * n_coins + 16 + 8 * par_per_pool(n_coins); }
+};
+inline NCoinFamily ncoin_family(int kind)
+{
+    return kind == CFMM_KIND_CURVE ? NCoinFamily{"Curve", false, false} : NCoinFamily{"weighted", true, true};
+}
 
 // A launch: either one segment (sweep_kernel) or up to kMaxMulti segments fused (sweep_multi).
 struct Group {

@@ -91,30 +91,19 @@ struct UniV3Pools {              // src/cfmms.jl:226-245 as find_arb_pos constan
     int gbase;
 };
 
-// N-coin weighted geometric-mean pools (GeometricMean / Product, src/cfmms.jl:57-64; sweep_weighted).  Per-coin columns
-// are COIN-MAJOR ([n_coins][m]: coin k of pool i at k·m + i), so the lanes of a wavefront (consecutive pools) load each
-// column as one coalesced stream.  Weights are normalised to sum to 1 at upload.
+// N-coin pools, one launch per segment (sweep_ncoin): the weighted geometric-mean family (GeometricMean / Product,
+// src/cfmms.jl:57-64; WeightedFamily) and the Curve (StableSwap) family, φ(R) = α·Σ R − β·Π R⁻¹ (Curve{T},
+// src/cfmms.jl:66-70; CurveFamily, curve_pool.h).  Per-coin columns are COIN-MAJOR ([n_coins][m]: coin k of pool i at
+// k·m + i), so the lanes of a wavefront (consecutive pools) load each column as one coalesced stream.
 constexpr int kMaxCoins = 8;
-struct WeightedPools {
+struct NCoinPools {
     const double* R;             // [n_coins][m] reserves
-    const double* q;             // [n_coins][m] log(R / w): the v-independent part of s^λ = log(R·v/w), prepared at upload and
-                                 //               by update_weighted
-    const double* w;             // [n_coins][m] normalised weights
+    const double* q;             // [n_coins][m] the family's per-coin constant, prepared at upload and by update_ncoin:
+                                 //     weighted log(R / w) (the v-independent part of s^λ = log(R·v/w)), Curve log R
     const int32_t* tok;          // [n_coins][m] token indices, 0-based
     const double2* glg;          // [m] {γ, log γ}
-    int n_coins;                 // 2 .. kMaxCoins, uniform over the segment
-    double* Delta;               // [n_coins][m] trades of a materialising sweep (null otherwise)
-    double* Lambda;
-};
-
-// Curve (StableSwap) pools, φ(R) = α·Σ R − β·Π R⁻¹ (Curve{T}, src/cfmms.jl:66-70; sweep_curve, curve_pool.h).  Coin-major
-// columns as WeightedPools.
-struct CurvePools {
-    const double* R;             // [n_coins][m] reserves
-    const double* lR;            // [n_coins][m] log R (upload, update_curve)
-    const int32_t* tok;          // [n_coins][m] token indices, 0-based
-    const double2* ab;           // [m] {α, log β}
-    const double2* glg;          // [m] {γ, log γ}
+    const double* par;           // the family's own column: weighted [n_coins][m] weights (normalised to sum to 1 at
+                                 //     upload), Curve [m] {α, log β}
     int n_coins;                 // 2 .. kMaxCoins, uniform over the segment
     double* Delta;               // [n_coins][m] trades of a materialising sweep (null otherwise)
     double* Lambda;
@@ -230,20 +219,14 @@ hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchC
 hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
                         hipStream_t s);
 
-// Weighted segments are their own launch (kMidBlock threads, full-range arithmetic, never fused, never single-block direct):
-// a.Delta / a.Lambda / a.Over / a.gflow are unused (the trades go to p.Delta / p.Lambda).
-hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                        hipStream_t s);
-// R <- (R + γΔ) − Λ per coin, in place, then q <- log(R / w)
-hipError_t launch_update_weighted(double* R, double* q, const double* w, const double2* glg, const double* Delta,
-                                  const double* Lambda, int n_coins, int64_t m, hipStream_t s);
-
-// Curve segments likewise (their own launch of kMidBlock threads, never fused, never direct; trades to p.Delta / p.Lambda).
-hipError_t launch_sweep(const CurvePools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                        hipStream_t s);
-// R <- (R + γΔ) − Λ per coin, in place, then lR <- log R (α and β are the pool's parameters: unchanged)
-hipError_t launch_update_curve(double* R, double* lR, const double2* glg, const double* Delta, const double* Lambda,
-                               int n_coins, int64_t m, hipStream_t s);
+// N-coin segments (kind CFMM_KIND_WEIGHTED or CFMM_KIND_CURVE) are their own launch (kMidBlock threads, full-range
+// arithmetic, never fused, never single-block direct): a.Delta / a.Lambda / a.Over / a.gflow are unused (the trades go to
+// p.Delta / p.Lambda).
+hipError_t launch_sweep_ncoin(int kind, const NCoinPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+                              hipStream_t s);
+// R <- (R + γΔ) − Λ per coin, in place, then q <- the family's constant for the new R (par: unchanged)
+hipError_t launch_update_ncoin(int kind, double* R, double* q, const double* par, const double2* glg, const double* Delta,
+                               const double* Lambda, int n_coins, int64_t m, hipStream_t s);
 
 // block b writes partial row b (see sweep_multi for the block -> segment map); without xcd_map the grid must be a
 // multiple of ma.nseg.

@@ -6,8 +6,8 @@
 //   find_arb!(.., ::ProductTwoCoin)    src/cfmms.jl:125-140   -> ProductOps::solve
 //   find_arb!(.., ::GeometricMeanTwoCoin) src/cfmms.jl:180-196 -> GeoMeanLogOps::solve (default), GeoMeanOps::solve
 //   find_arb!(.., ::UniV3) + helpers   src/cfmms.jl:294-395   -> UniV3Ops::solve_dir
-//   GeometricMean / Product, N coins  src/cfmms.jl:57-64 (no find_arb! upstream) -> sweep_weighted / weighted_pool
-//   Curve (StableSwap), N coins       src/cfmms.jl:66-70 (no find_arb! upstream) -> sweep_curve / curve_solve
+//   GeometricMean / Product, N coins  src/cfmms.jl:57-64 (no find_arb! upstream) -> sweep_ncoin / weighted_pool
+//   Curve (StableSwap), N coins       src/cfmms.jl:66-70 (no find_arb! upstream) -> sweep_ncoin / curve_pool, curve_solve
 //   acc loop of fn                     src/router.jl:79-83    -> per-lane acc + wave shuffles
 //   scatter loop of g! / netflows!     src/router.jl:98-100, :111-119 -> LDS bins + reduce_partials
 //                                      (n_tokens > 8192: flow array + gather_chunks / token_fold)
@@ -32,6 +32,7 @@
 // N-coin weighted pools, are within a few u·κ·scale (u = 2^-53, κ the conditioning of the exponent; bounds and
 // measured ratios in tests/test_gpu_precise.py).  HBM-bound by design: no MFMA (there is no contraction anywhere on this path).
 
+#include "../../include/cfmm_amd.h"
 #include "sweep.h"
 #include "curve_pool.h"
 
@@ -1193,8 +1194,45 @@ __global__ __launch_bounds__(BLOCK) void sweep_multi(MultiArgs ma)
 }
 
 // ---------------------------------------------------------------------------------------------
-// N-coin weighted geometric-mean pools -- GeometricMean / Product, src/cfmms.jl:57-64 (no find_arb! there)
+// N-coin pools: one lane per pool, coin-major columns (sweep.h NCoinPools), one launch per segment
 // ---------------------------------------------------------------------------------------------
+// The price of token t, from the LDS row stage_prices fills
+__device__ __forceinline__ double lds_price(const SweepArgs& a, const SweepLds& L, int t)
+{
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(L.vy) + ((size_t)t << a.v_shift));
+}
+
+// A pool inside its fee band: every Δ and Λ is +0.0
+template <int N, bool MAT>
+__device__ __forceinline__ void ncoin_no_trade(const NCoinPools& p, int64_t m, int64_t i)
+{
+    if (MAT) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            p.Delta[k * m + i] = 0.0;
+            p.Lambda[k * m + i] = 0.0;
+        }
+    }
+}
+
+// Coin k of pool i trades (Δ, Λ) = (del, lam): stored by a materialising sweep, its terms of the dual sums, its netflow
+// into this wavefront's LDS bins
+template <bool MAT>
+__device__ __forceinline__ void ncoin_emit(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t m, int64_t i, int k,
+                                           int tok, double lam, double del, double& sum_l, double& sum_d)
+{
+    if (MAT) {
+        p.Delta[k * m + i] = del;
+        p.Lambda[k * m + i] = lam;
+    }
+    const double v = lds_price(a, L, tok);
+    sum_l += lam * v;     // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
+    sum_d += del * v;
+    const double f = lam - del;   // src/router.jl:99  G[Ai] .+= Λ .- Δ
+    if (f != 0.0 || f != f) atomicAdd(&L.my_bins[tok], f);
+}
+
+// Weighted geometric-mean pools -- GeometricMean / Product, src/cfmms.jl:57-64 (no find_arb! there).
 // maximise Σ v_k(λ_k − δ_k) s.t. Π (R_k + γδ_k − λ_k)^{w_k} >= Π R_k^{w_k}, δ, λ >= 0 (the problem of the find_arb!
 // docstring, src/cfmms.jl:21-33).  With the multiplier μ = e^t the KKT conditions give, coin by coin,
 //     R_k'(t) = R_k · exp(min(0, t − s_k^λ) + max(0, t − s_k^δ)),   s_k^λ = log(R_k v_k / w_k),  s_k^δ = s_k^λ − log γ,
@@ -1208,8 +1246,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_multi(MultiArgs ma)
 // The coin count is a template argument of the per-pool code (registers sized for exactly N) and a segment-uniform
 // switch in the kernel.
 template <int N, bool MAT>
-__device__ __forceinline__ void weighted_pool(const WeightedPools& p, const SweepArgs& a, const SweepLds& L, int64_t i,
-                                              double& acc)
+__device__ __forceinline__ void weighted_pool(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
 {
     const int64_t m = a.m;
     double R[N], w[N], sl[N];   // (s^δ = s^λ − log γ and the prices are re-derived where needed: registers)
@@ -1218,29 +1255,22 @@ __device__ __forceinline__ void weighted_pool(const WeightedPools& p, const Swee
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         R[k] = p.R[k * m + i];
-        w[k] = p.w[k * m + i];
+        w[k] = p.par[k * m + i];
         sl[k] = p.q[k * m + i];
         tok[k] = p.tok[k * m + i];
     }
-    const char* base = reinterpret_cast<const char*>(L.vy);
     double lmax = -__builtin_inf(), dmin = __builtin_inf(), wsum = 0.0;
     bool nan_in = false;
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        sl[k] += a.need_logv ? L.lv[tok[k]] : log(*reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift)));
+        sl[k] += a.need_logv ? L.lv[tok[k]] : log(lds_price(a, L, tok[k]));
         nan_in = nan_in || sl[k] != sl[k];
         lmax = __builtin_fmax(lmax, sl[k]);
         dmin = __builtin_fmin(dmin, sl[k] - gl.y);
         wsum += w[k];
     }
     if (!nan_in && lmax <= dmin) {   // inside the fee band: no trade
-        if (MAT) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                p.Delta[k * m + i] = 0.0;
-                p.Lambda[k * m + i] = 0.0;
-            }
-        }
+        ncoin_no_trade<N, MAT>(p, m, i);
         return;
     }
     // bracket of the root of G among the 2N breakpoints
@@ -1276,90 +1306,34 @@ __device__ __forceinline__ void weighted_pool(const WeightedPools& p, const Swee
         const double lam = nan_in ? t : (t < sl[k] ? -(R[k] * expm1(t - sl[k])) : 0.0);
         const double sd = sl[k] - gl.y;
         const double del = nan_in ? t : (t > sd ? (R[k] * expm1(t - sd)) * rg : 0.0);
-        const double v = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
-        if (MAT) {
-            p.Delta[k * m + i] = del;
-            p.Lambda[k * m + i] = lam;
-        }
-        sum_l += lam * v;     // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
-        sum_d += del * v;
-        const double f = lam - del;   // src/router.jl:99  G[Ai] .+= Λ .- Δ
-        if (f != 0.0 || f != f) atomicAdd(&L.my_bins[tok[k]], f);
+        ncoin_emit<MAT>(p, a, L, m, i, k, tok[k], lam, del, sum_l, sum_d);
     }
     acc += sum_l - sum_d;
 }
 
+// Curve (StableSwap) pools -- Curve{T}, src/cfmms.jl:66-70 (no find_arb! there): φ(R) = α·Σ R − β·Π R⁻¹.
+// The solve (outer safeguarded Newton on E2, inner exact E1 root) is curve_pool.h's curve_solve, the derivation there.
+// Prices come from the LDS row stage_prices fills (v itself: no log v row).  Trades: λ_k = −R_k·expm1(log r_k − ρ_k) for a
+// coin that leaves, δ_k = R_k·expm1(log r_k − ρ_k)/γ for one that enters; a coin that does not trade has log r_k = ρ_k
+// exactly, hence +0.0.
 template <int N, bool MAT>
-__device__ __forceinline__ void weighted_tiles(const WeightedPools& p, const SweepArgs& a, const SweepLds& L, int64_t i,
-                                               int64_t step, int64_t left, double& acc)
-{
-    for (; left > 0; --left, i += step) weighted_pool<N, MAT>(p, a, L, i, acc);
-}
-
-// One launch per weighted segment; prologue (carve_lds, stage_prices: arm word, cancel, give-up report) and epilogue
-// (finish_row: the partial row reduce_partials / reduce_gather fold) are the other families' own.
-template <bool MAT>
-__global__ __launch_bounds__(kMidBlock) void sweep_weighted(WeightedPools p, SweepArgs a)
-{
-    constexpr int BLOCK = kMidBlock;
-    const SweepLds L = carve_lds<BLOCK, false>(a);
-    const int staged = stage_prices<BLOCK, false>(a, L);
-    const bool poison = (staged & kStageLive) == 0;
-    const bool live = !poison || (staged & kStageGaveUp) != 0;
-    if (staged & kStageGaveUp) report(a, kFlagGaveUp);
-    double acc = 0.0;
-    if (!poison) {
-        const int64_t stride = (int64_t)gridDim.x * BLOCK;
-        const int64_t i0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-        const int64_t left = i0 < a.m ? (a.m - i0 + stride - 1) / stride : 0;
-        const int64_t step = a.reverse ? -stride : stride;
-        const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
-        switch (p.n_coins) {
-        case 2: weighted_tiles<2, MAT>(p, a, L, i, step, left, acc); break;
-        case 3: weighted_tiles<3, MAT>(p, a, L, i, step, left, acc); break;
-        case 4: weighted_tiles<4, MAT>(p, a, L, i, step, left, acc); break;
-        case 5: weighted_tiles<5, MAT>(p, a, L, i, step, left, acc); break;
-        case 6: weighted_tiles<6, MAT>(p, a, L, i, step, left, acc); break;
-        case 7: weighted_tiles<7, MAT>(p, a, L, i, step, left, acc); break;
-        case 8: weighted_tiles<8, MAT>(p, a, L, i, step, left, acc); break;
-        default: break;
-        }
-    }
-    finish_row<BLOCK, false>(a, L, acc, (int)blockIdx.x, poison, live);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Curve (StableSwap) pools -- Curve{T}, src/cfmms.jl:66-70 (no find_arb! there): φ(R) = α·Σ R − β·Π R⁻¹
-// ---------------------------------------------------------------------------------------------
-// One lane per pool; the solve (outer safeguarded Newton on E2, inner exact E1 root) is curve_pool.h's curve_solve, the
-// derivation there.  Prices come from the LDS row stage_prices fills (v itself: no log v row).  Trades: λ_k = −R_k·expm1(
-// log r_k − ρ_k) for a coin that leaves, δ_k = R_k·expm1(log r_k − ρ_k)/γ for one that enters; a coin that does not trade
-// has log r_k = ρ_k exactly, hence +0.0.  Ψ and acc as weighted_pool (LDS bins of the wavefront, per-lane dual).
-template <int N, bool MAT>
-__device__ __forceinline__ void curve_pool(const CurvePools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
+__device__ __forceinline__ void curve_pool(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
 {
     const int64_t m = a.m;
     double R[N], rho[N], v[N], lr[N];
     int tok[N];   // (v is re-read from LDS after the solve: fewer registers live across it)
-    const double2 ab = p.ab[i];
+    const double2 ab = reinterpret_cast<const double2*>(p.par)[i];
     const double2 gl = p.glg[i];
-    const char* base = reinterpret_cast<const char*>(L.vy);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         R[k] = p.R[k * m + i];
-        rho[k] = p.lR[k * m + i];
+        rho[k] = p.q[k * m + i];
         tok[k] = p.tok[k * m + i];
     }
 #pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
+    for (int k = 0; k < N; ++k) v[k] = lds_price(a, L, tok[k]);
     if (!curve_solve<N>(rho, R, v, ab.x, ab.y, gl.x, lr)) {   // inside the fee band: no trade
-        if (MAT) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) {
-                p.Delta[k * m + i] = 0.0;
-                p.Lambda[k * m + i] = 0.0;
-            }
-        }
+        ncoin_no_trade<N, MAT>(p, m, i);
         return;
     }
     const double rg = 1.0 / gl.x;
@@ -1370,29 +1344,41 @@ __device__ __forceinline__ void curve_pool(const CurvePools& p, const SweepArgs&
         const double em = expm1(lr[k] - rho[k]);
         const double lam = nan_k ? lr[k] : (lr[k] < rho[k] ? -(R[k] * em) : 0.0);
         const double del = nan_k ? lr[k] : (lr[k] > rho[k] ? (R[k] * em) * rg : 0.0);
-        if (MAT) {
-            p.Delta[k * m + i] = del;
-            p.Lambda[k * m + i] = lam;
-        }
-        const double vk = *reinterpret_cast<const double*>(base + ((size_t)tok[k] << a.v_shift));
-        sum_l += lam * vk;     // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
-        sum_d += del * vk;
-        const double f = lam - del;   // src/router.jl:99  G[Ai] .+= Λ .- Δ
-        if (f != 0.0 || f != f) atomicAdd(&L.my_bins[tok[k]], f);
+        ncoin_emit<MAT>(p, a, L, m, i, k, tok[k], lam, del, sum_l, sum_d);
     }
     acc += sum_l - sum_d;
 }
 
-template <int N, bool MAT>
-__device__ __forceinline__ void curve_tiles(const CurvePools& p, const SweepArgs& a, const SweepLds& L, int64_t i, int64_t step,
+// The two families: the per-pool solve and the per-coin constant q that update_ncoin refreshes (the upload's expression)
+struct WeightedFamily {
+    template <int N, bool MAT>
+    static __device__ __forceinline__ void pool(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
+    {
+        weighted_pool<N, MAT>(p, a, L, i, acc);
+    }
+    static __device__ __forceinline__ double q_of(double r, const double* par, long long j) { return log(r / par[j]); }
+};
+struct CurveFamily {
+    template <int N, bool MAT>
+    static __device__ __forceinline__ void pool(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t i, double& acc)
+    {
+        curve_pool<N, MAT>(p, a, L, i, acc);
+    }
+    static __device__ __forceinline__ double q_of(double r, const double*, long long) { return log(r); }
+};
+
+template <class F, int N, bool MAT>
+__device__ __forceinline__ void ncoin_tiles(const NCoinPools& p, const SweepArgs& a, const SweepLds& L, int64_t i, int64_t step,
                                             int64_t left, double& acc)
 {
-    for (; left > 0; --left, i += step) curve_pool<N, MAT>(p, a, L, i, acc);
+    for (; left > 0; --left, i += step) F::template pool<N, MAT>(p, a, L, i, acc);
 }
 
-// One launch per Curve segment; prologue and epilogue are sweep_weighted's (the other families' own).
-template <bool MAT>
-__global__ __launch_bounds__(kMidBlock) void sweep_curve(CurvePools p, SweepArgs a)
+// One launch per N-coin segment; prologue (carve_lds, stage_prices: arm word, cancel, give-up report) and epilogue
+// (finish_row: the partial row reduce_partials / reduce_gather fold) are the other families' own.  Ψ and acc: LDS bins of
+// the wavefront, per-lane dual.
+template <class F, bool MAT>
+__global__ __launch_bounds__(kMidBlock) void sweep_ncoin(NCoinPools p, SweepArgs a)
 {
     constexpr int BLOCK = kMidBlock;
     const SweepLds L = carve_lds<BLOCK, false>(a);
@@ -1408,13 +1394,13 @@ __global__ __launch_bounds__(kMidBlock) void sweep_curve(CurvePools p, SweepArgs
         const int64_t step = a.reverse ? -stride : stride;
         const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
         switch (p.n_coins) {
-        case 2: curve_tiles<2, MAT>(p, a, L, i, step, left, acc); break;
-        case 3: curve_tiles<3, MAT>(p, a, L, i, step, left, acc); break;
-        case 4: curve_tiles<4, MAT>(p, a, L, i, step, left, acc); break;
-        case 5: curve_tiles<5, MAT>(p, a, L, i, step, left, acc); break;
-        case 6: curve_tiles<6, MAT>(p, a, L, i, step, left, acc); break;
-        case 7: curve_tiles<7, MAT>(p, a, L, i, step, left, acc); break;
-        case 8: curve_tiles<8, MAT>(p, a, L, i, step, left, acc); break;
+        case 2: ncoin_tiles<F, 2, MAT>(p, a, L, i, step, left, acc); break;
+        case 3: ncoin_tiles<F, 3, MAT>(p, a, L, i, step, left, acc); break;
+        case 4: ncoin_tiles<F, 4, MAT>(p, a, L, i, step, left, acc); break;
+        case 5: ncoin_tiles<F, 5, MAT>(p, a, L, i, step, left, acc); break;
+        case 6: ncoin_tiles<F, 6, MAT>(p, a, L, i, step, left, acc); break;
+        case 7: ncoin_tiles<F, 7, MAT>(p, a, L, i, step, left, acc); break;
+        case 8: ncoin_tiles<F, 8, MAT>(p, a, L, i, step, left, acc); break;
         default: break;
         }
     }
@@ -1717,14 +1703,14 @@ hipError_t prepare_kernels(size_t max_lds_bytes)
 #undef CFMM_SETM4
 #undef CFMM_SETM
     hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_weighted<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_curve<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_curve<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)max_lds_bytes)) != hipSuccess)
+    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<WeightedFamily, true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<WeightedFamily, false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<CurveFamily, true>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
+        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<CurveFamily, false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess)
         return e;
     if ((e = set_lds_attr<ProductOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<ProductOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
@@ -1869,10 +1855,12 @@ __global__ __launch_bounds__(256) void expand_trades(const double2* __restrict__
     Lambda[i] = l;
 }
 
-// update_reserves! for weighted segments: R <- (R + γΔ) − Λ per coin, q <- log(R / w) (the upload's expression)
-__global__ __launch_bounds__(256) void update_weighted(double* __restrict__ R, double* __restrict__ q, const double* __restrict__ w,
-                                                       const double2* __restrict__ glg, const double* __restrict__ Delta,
-                                                       const double* __restrict__ Lambda, int n_coins, long long m)
+// update_reserves! for N-coin segments: R <- (R + γΔ) − Λ per coin, q <- the family's constant (F::q_of); par stays (the
+// weights, or Curve's α and β: the pool's parameters)
+template <class F>
+__global__ __launch_bounds__(256) void update_ncoin(double* __restrict__ R, double* __restrict__ q, const double* __restrict__ par,
+                                                    const double2* __restrict__ glg, const double* __restrict__ Delta,
+                                                    const double* __restrict__ Lambda, int n_coins, long long m)
 {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
@@ -1881,59 +1869,31 @@ __global__ __launch_bounds__(256) void update_weighted(double* __restrict__ R, d
         const long long j = (long long)k * m + i;
         const double rn = (R[j] + g * Delta[j]) - Lambda[j];
         R[j] = rn;
-        q[j] = log(rn / w[j]);
+        q[j] = F::q_of(rn, par, j);
     }
 }
 
-// update_reserves! for Curve segments: R <- (R + γΔ) − Λ per coin, lR <- log R; α, β stay (the pool's parameters)
-__global__ __launch_bounds__(256) void update_curve(double* __restrict__ R, double* __restrict__ lR, const double2* __restrict__ glg,
-                                                    const double* __restrict__ Delta, const double* __restrict__ Lambda, int n_coins,
-                                                    long long m)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= m) return;
-    const double g = glg[i].x;
-    for (int k = 0; k < n_coins; ++k) {
-        const long long j = (long long)k * m + i;
-        const double rn = (R[j] + g * Delta[j]) - Lambda[j];
-        R[j] = rn;
-        lR[j] = log(rn);
-    }
-}
-
-hipError_t launch_sweep(const CurvePools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+hipError_t launch_sweep_ncoin(int kind, const NCoinPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
 {
     if (a.m <= 0) return hipSuccess;
     dim3 g(c.grid), b(kMidBlock);
-    if (mat) launch_k(&sweep_curve<true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    else launch_k(&sweep_curve<false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    const bool curve = kind == CFMM_KIND_CURVE;
+    if (curve && mat) launch_k(&sweep_ncoin<CurveFamily, true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    else if (curve) launch_k(&sweep_ncoin<CurveFamily, false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    else if (mat) launch_k(&sweep_ncoin<WeightedFamily, true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
+    else launch_k(&sweep_ncoin<WeightedFamily, false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
     return hipGetLastError();
 }
 
-hipError_t launch_update_curve(double* R, double* lR, const double2* glg, const double* Delta, const double* Lambda,
-                               int n_coins, int64_t m, hipStream_t s)
+hipError_t launch_update_ncoin(int kind, double* R, double* q, const double* par, const double2* glg, const double* Delta,
+                               const double* Lambda, int n_coins, int64_t m, hipStream_t s)
 {
     if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(update_curve, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, R, lR, glg, Delta, Lambda, n_coins,
-                       (long long)m);
-    return hipGetLastError();
-}
-
-hipError_t launch_sweep(const WeightedPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (a.m <= 0) return hipSuccess;
-    dim3 g(c.grid), b(kMidBlock);
-    if (mat) launch_k(&sweep_weighted<true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    else launch_k(&sweep_weighted<false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_update_weighted(double* R, double* q, const double* w, const double2* glg, const double* Delta,
-                                  const double* Lambda, int n_coins, int64_t m, hipStream_t s)
-{
-    if (m <= 0) return hipSuccess;
-    hipLaunchKernelGGL(update_weighted, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, R, q, w, glg, Delta, Lambda,
-                       n_coins, (long long)m);
+    const dim3 g((unsigned)((m + 255) / 256)), b(256);
+    if (kind == CFMM_KIND_CURVE)
+        hipLaunchKernelGGL(update_ncoin<CurveFamily>, g, b, 0, s, R, q, par, glg, Delta, Lambda, n_coins, (long long)m);
+    else
+        hipLaunchKernelGGL(update_ncoin<WeightedFamily>, g, b, 0, s, R, q, par, glg, Delta, Lambda, n_coins, (long long)m);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
-"""N-coin weighted pools (CFMM_KIND_WEIGHTED, sweep_weighted) against the roofline: 1M pools at N = 2, 3, 4, 8 coins,
-256 tokens, fused (cfmm_eval: no trade write-back) and materialising (cfmm_find_arb) sweeps, cache-warm (one market swept
+"""N-coin weighted pools (CFMM_KIND_WEIGHTED, sweep_ncoin<WeightedFamily>) against the roofline: 1M pools at N = 2, 3, 4, 8
+coins, 256 tokens, fused (cfmm_eval: no trade write-back) and materialising (cfmm_find_arb) sweeps, cache-warm (one market swept
 again and again) and HBM-resident (a ring of market copies touching >= 2 x the 256 MiB Infinity Cache).  Kernel span from
 the command processor's start / stop events (option "time_kernels").
 

@@ -41,6 +41,22 @@ def rel_to_max(a, b):
     return float(np.max(np.abs(np.asarray(a) - np.asarray(b))) / scale)
 
 
+def device_sweep(n, batches, v, device=0):
+    """One materialising sweep of `batches` on the device: flat Δ, flat Λ, Ψ, acc."""
+    be = cr.DeviceBackend(n, batches, device=device)
+    try:
+        psi, acc = be.find_arb(v)
+        D, L = be.trades()
+    finally:
+        be.close()
+    return np.ravel(D), np.ravel(L), psi, acc
+
+
+def coin_scale(b):
+    """Per-pool trade scale of an N-coin batch: its largest reserve, [m, 1]."""
+    return b.R.max(axis=1, keepdims=True)
+
+
 class OracleBackend:
     """TEST-ONLY stand-in for DeviceBackend so the host logic (route loop, packing order, sharded
     reduction) can be exercised on a box with no GPU.  Lives in tests/, never in the package."""

@@ -1,4 +1,4 @@
-"""Curve (StableSwap) pools on the device (CFMM_KIND_CURVE, sweep_curve): N = 2..8 against the CPU reference
+"""Curve (StableSwap) pools on the device (CFMM_KIND_CURVE, sweep_ncoin<CurveFamily>): N = 2..8 against the CPU reference
 (tests/curve_ref.py), α = 0 against the device's own ProductTwoCoin and equal-weight weighted segments, edge cases, mixed
 markets, route! against the host plugin seam, update_reserves!, multi-device parents and the error paths."""
 import math
@@ -9,25 +9,11 @@ import pytest
 import cfmmrouter_amd as cr
 from cfmmrouter_amd import chain, synth
 from cfmmrouter_amd._lib import KIND_CURVE, KIND_PRODUCT, KIND_WEIGHTED
-from helpers import rel_to_max
+from helpers import coin_scale, device_sweep, rel_to_max
 
 import curve_ref as cv
 
 pytestmark = pytest.mark.gpu
-
-
-def _sweep(n, batches, v, device=0):
-    be = cr.DeviceBackend(n, batches, device=device)
-    try:
-        psi, acc = be.find_arb(v)
-        D, L = be.trades()
-    finally:
-        be.close()
-    return np.ravel(D), np.ravel(L), psi, acc
-
-
-def _scale(b):
-    return b.R.max(axis=1, keepdims=True)
 
 
 def _near_prices(n, seed):
@@ -41,10 +27,10 @@ def test_n_coin_pools_match_the_cpu_reference(nc, prices, m):
     n = 128
     b = synth.curve_pools(m, n, nc, seed=10 + nc)
     v = synth.sweep_prices(n, seed=20 + nc, spread=0.5) if prices == "spread" else _near_prices(n, 20 + nc)
-    D, L, psi, acc = _sweep(n, [b], v)
+    D, L, psi, acc = device_sweep(n, [b], v)
     D, L = D.reshape(m, nc), L.reshape(m, nc)
     Do, Lo = cv.sweep(b, v)
-    s = _scale(b)
+    s = coin_scale(b)
     assert np.max(np.abs(D - Do) / s) <= 1e-10 and np.max(np.abs(L - Lo) / s) <= 1e-10
     assert np.all(D >= 0) and np.all(L >= 0)
     assert np.mean(np.any(L > 0, axis=1)) > 0.3
@@ -69,9 +55,9 @@ def test_alpha_zero_matches_device_product_and_weighted():
             other = cr.PoolBatch(KIND_PRODUCT, R=b.R, γ=b.γ, Ai=b.Ai)
         else:
             other = cr.PoolBatch(KIND_WEIGHTED, R=b.R, w=np.full((m, nc), 1.0 / nc), γ=b.γ, Ai=b.Ai)
-        Dc, Lc, psic, accc = _sweep(n, [b], v)
-        Do, Lo, psio, acco = _sweep(n, [other], v)
-        s = np.repeat(_scale(b), nc, axis=1).ravel()
+        Dc, Lc, psic, accc = device_sweep(n, [b], v)
+        Do, Lo, psio, acco = device_sweep(n, [other], v)
+        s = np.repeat(coin_scale(b), nc, axis=1).ravel()
         assert np.max(np.abs(Dc - Do) / s) <= 1e-12 and np.max(np.abs(Lc - Lo) / s) <= 1e-12, nc
         assert rel_to_max(psic, psio) <= 1e-12
         assert abs(accc - acco) <= 1e-12 * abs(acco)
@@ -92,11 +78,11 @@ def test_edge_cases():
     g = np.array([0.9996, 1.0, 0.997, 0.9996, 1.0, 0.997, 0.9996])
     al, be = chain.stableswap_params(bal, A)
     b = cr.Curve.batch(bal, g, Ai, al, be)
-    D, L, psi, acc = _sweep(n, [b], v)
+    D, L, psi, acc = device_sweep(n, [b], v)
     D, L = D.reshape(-1, 3), L.reshape(-1, 3)
     assert np.all(D[0] == 0) and np.all(L[0] == 0) and not np.any(np.signbit(D[0])) and not np.any(np.signbit(L[0]))
     Do, Lo = cv.sweep(b, v)
-    s = _scale(b)
+    s = coin_scale(b)
     assert np.max(np.abs(D - Do) / s) <= 1e-10 and np.max(np.abs(L - Lo) / s) <= 1e-10
     for i in range(1, len(b)):
         assert np.any(D[i] > 0) and np.any(L[i] > 0), i
@@ -144,7 +130,7 @@ def test_mixed_market_other_rows_unchanged_and_reproducible():
         assert a3 == a4
         assert be.ctx._L.cfmm_segment_count(be.ctx._h) == 6
         Dc = D1[nw:nw + 3 * 25_000].reshape(-1, 3)
-        np.testing.assert_allclose(Dc, cv.sweep(curves[0], v)[0], rtol=0, atol=1e-10 * _scale(curves[0]).max())
+        np.testing.assert_allclose(Dc, cv.sweep(curves[0], v)[0], rtol=0, atol=1e-10 * coin_scale(curves[0]).max())
     finally:
         be0.close()
         be.close()
@@ -236,8 +222,8 @@ def test_multi_device_parent_matches_single_context():
     bs = [synth.product_pools(10_001, n, seed=51), synth.curve_pools(30_001, n, 4, seed=52),
           synth.curve_pools(7_777, n, 3, seed=53)]
     v = synth.sweep_prices(n, seed=54, spread=0.5)
-    D1, L1, psi1, acc1 = _sweep(n, bs, v)
-    D3, L3, psi3, acc3 = _sweep(n, bs, v, device=[0, 0, 0])
+    D1, L1, psi1, acc1 = device_sweep(n, bs, v)
+    D3, L3, psi3, acc3 = device_sweep(n, bs, v, device=[0, 0, 0])
     np.testing.assert_array_equal(D1, D3)
     np.testing.assert_array_equal(L1, L3)
     assert rel_to_max(psi3, psi1) <= 1e-12

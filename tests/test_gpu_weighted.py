@@ -1,5 +1,5 @@
-"""N-coin weighted geometric-mean pools on the device (CFMM_KIND_WEIGHTED, sweep_weighted): parity with the device's own
-two-coin families at N = 2, with the CPU reference (tests/weighted_ref.py) at N = 3..8, edge cases, mixed markets,
+"""N-coin weighted geometric-mean pools on the device (CFMM_KIND_WEIGHTED, sweep_ncoin<WeightedFamily>): parity with the
+device's own two-coin families at N = 2, with the CPU reference (tests/weighted_ref.py) at N = 3..8, edge cases, mixed markets,
 route! against the host plugin seam, update_reserves!, multi-device parents and the error paths."""
 import math
 
@@ -9,25 +9,11 @@ import pytest
 import cfmmrouter_amd as cr
 from cfmmrouter_amd import synth
 from cfmmrouter_amd._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_WEIGHTED
-from helpers import rel_to_max
+from helpers import coin_scale, device_sweep, rel_to_max
 
 import weighted_ref as wr
 
 pytestmark = pytest.mark.gpu
-
-
-def _sweep(n, batches, v, device=0):
-    be = cr.DeviceBackend(n, batches, device=device)
-    try:
-        psi, acc = be.find_arb(v)
-        D, L = be.trades()
-    finally:
-        be.close()
-    return np.ravel(D), np.ravel(L), psi, acc
-
-
-def _scale(b):
-    return b.R.max(axis=1, keepdims=True)
 
 
 def test_two_coin_weighted_matches_device_two_coin_families():
@@ -38,9 +24,9 @@ def test_two_coin_weighted_matches_device_two_coin_families():
     v = synth.sweep_prices(n, seed=3, spread=0.5)
     for two, wt in [(bp, cr.PoolBatch(KIND_WEIGHTED, R=bp.R, w=np.full((m, 2), 0.5), γ=bp.γ, Ai=bp.Ai)),
                     (bg, cr.PoolBatch(KIND_WEIGHTED, R=bg.R, w=bg.w, γ=bg.γ, Ai=bg.Ai))]:
-        D2, L2, psi2, acc2 = _sweep(n, [two], v)
-        Dw, Lw, psiw, accw = _sweep(n, [wt], v)
-        s = np.repeat(_scale(two), 2, axis=1).ravel()
+        D2, L2, psi2, acc2 = device_sweep(n, [two], v)
+        Dw, Lw, psiw, accw = device_sweep(n, [wt], v)
+        s = np.repeat(coin_scale(two), 2, axis=1).ravel()
         assert np.max(np.abs(Dw - D2) / s) <= 1e-12 and np.max(np.abs(Lw - L2) / s) <= 1e-12
         assert rel_to_max(psiw, psi2) <= 1e-12
         assert abs(accw - acc2) <= 1e-12 * abs(acc2)
@@ -51,10 +37,10 @@ def test_n_coin_pools_match_the_cpu_reference(nc):
     n, m = 128, 200_000
     b = synth.weighted_pools(m, n, nc, seed=10 + nc)
     v = synth.sweep_prices(n, seed=20 + nc, spread=0.5)
-    D, L, psi, acc = _sweep(n, [b], v)
+    D, L, psi, acc = device_sweep(n, [b], v)
     D, L = D.reshape(m, nc), L.reshape(m, nc)
     Do, Lo = wr.sweep(b, v)
-    s = _scale(b)
+    s = coin_scale(b)
     assert np.max(np.abs(D - Do) / s) <= 1e-11 and np.max(np.abs(L - Lo) / s) <= 1e-11
     assert np.all(D >= 0) and np.all(L >= 0)
     Ai0 = b.Ai - 1
@@ -83,12 +69,12 @@ def test_edge_cases():
     R[5] = [1e-6, 1.0, 1e12]
     g = np.array([0.997, 0.99, 0.997, 0.997, 1.0, 1.0])
     b = cr.PoolBatch(KIND_WEIGHTED, R=R, w=w, γ=g, Ai=Ai)
-    D, L, psi, acc = _sweep(n, [b], v)
+    D, L, psi, acc = device_sweep(n, [b], v)
     D, L = D.reshape(-1, 3), L.reshape(-1, 3)
     for i in (0, 1, 2):   # equilibrium / fee band: exact +0.0
         assert np.all(D[i] == 0) and np.all(L[i] == 0) and not np.any(np.signbit(D[i])) and not np.any(np.signbit(L[i]))
     Do, Lo = wr.sweep(b, v)
-    s = _scale(b)
+    s = coin_scale(b)
     assert np.max(np.abs(D - Do) / s) <= 1e-11 and np.max(np.abs(L - Lo) / s) <= 1e-11
     for i in (3, 4, 5):
         assert np.any(D[i] > 0) and np.any(L[i] > 0)
@@ -134,7 +120,7 @@ def test_mixed_market_two_coin_rows_unchanged_and_reproducible():
         kinds = [be.ctx._L.cfmm_segment_count(be.ctx._h)]
         assert kinds == [5]
         Dw = D1[2 * m2:2 * m2 + 3 * 25_000].reshape(-1, 3)
-        np.testing.assert_allclose(Dw, wr.sweep(wts[0], v)[0], rtol=0, atol=1e-11 * _scale(wts[0]).max())
+        np.testing.assert_allclose(Dw, wr.sweep(wts[0], v)[0], rtol=0, atol=1e-11 * coin_scale(wts[0]).max())
     finally:
         be0.close()
         be.close()
@@ -218,8 +204,8 @@ def test_multi_device_parent_matches_single_context():
     bs = [synth.product_pools(10_001, n, seed=51), synth.weighted_pools(30_001, n, 4, seed=52),
           synth.weighted_pools(7_777, n, 3, seed=53)]
     v = synth.sweep_prices(n, seed=54, spread=0.5)
-    D1, L1, psi1, acc1 = _sweep(n, bs, v)
-    D3, L3, psi3, acc3 = _sweep(n, bs, v, device=[0, 0, 0])
+    D1, L1, psi1, acc1 = device_sweep(n, bs, v)
+    D3, L3, psi3, acc3 = device_sweep(n, bs, v, device=[0, 0, 0])
     np.testing.assert_array_equal(D1, D3)
     np.testing.assert_array_equal(L1, L3)
     assert rel_to_max(psi3, psi1) <= 1e-12
