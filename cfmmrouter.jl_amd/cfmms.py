@@ -151,6 +151,19 @@ def _curve_check_cast(α, β):
     return α, β
 
 
+CURVE_LOG_RANGE = 600.0   # curve_pool.h kCurveLogRange
+
+
+def _curve_range_check(R, α, β):
+    """The upload's range check (cfmm_pools_add_curve): at α > 0 every log(P₀/R_k) = log β − Σ log R − log R_k must lie
+    within ±CURVE_LOG_RANGE.  R [m, n]; α, β [m]."""
+    R = np.asarray(R, dtype=np.float64).reshape(np.size(β), -1)
+    lr = np.log(R)
+    x = (np.log(np.asarray(β, dtype=np.float64).reshape(-1)) - lr.sum(axis=1))[:, None] - lr
+    if np.any((np.asarray(α).reshape(-1) > 0) & ~np.all(np.abs(x) <= CURVE_LOG_RANGE, axis=1)):
+        raise ArgumentError(f"log(P₀/R_k) = log β − Σ log R − log R_k must lie within ±{CURVE_LOG_RANGE:g} when α > 0")
+
+
 class Curve(CFMM):
     """Curve(R, γ, Ai, α, β): φ(R) = α·Σ R_i − β·Π R_i⁻¹, 2..8 coins -- src/cfmms.jl:66-70 (the fields of Curve{T}, in
     the order of its default constructor).  Curve's StableSwap invariant with D held fixed: α = A·nⁿ, β = D^{n+1}/nⁿ
@@ -161,6 +174,7 @@ class Curve(CFMM):
     def __init__(self, R, γ, Ai, α, β):
         self.R, self.γ, self.Ai, _ = _n_coin_check_cast(R, γ, Ai, family="Curve")
         self.α, self.β = _curve_check_cast(α, β)
+        _curve_range_check(self.R[None], [self.α], [self.β])
 
     gamma = property(lambda self: self.γ)
     alpha = property(lambda self: self.α)
@@ -329,6 +343,8 @@ class PoolBatch:
             raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
         if m and np.any(np.sort(self.Ai, axis=1)[:, 1:] == np.sort(self.Ai, axis=1)[:, :-1]):
             raise ArgumentError("the token indices of a pool must be distinct")
+        if self.kind == KIND_CURVE and m:
+            _curve_range_check(self.R, self.α, self.β)
 
     n_coins = property(lambda self: self.Ai.shape[1])
 

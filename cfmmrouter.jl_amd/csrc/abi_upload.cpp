@@ -3,6 +3,7 @@
 // the packed fee + token records, and the v-independent constants of the GeometricMean / UniV3 closed forms,
 // prepared once on the host with the same IEEE operations the reference applies per sweep.
 #include "ctx.h"
+#include "curve_pool.h"
 
 #include <algorithm>
 #include <cmath>
@@ -562,6 +563,14 @@ int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* 
         if (!std::isfinite(alpha[i]) || alpha[i] < 0.0)
             return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: alpha must be finite and >= 0", (long long)i);
         if (!finite_pos(beta[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: beta must be finite and > 0", (long long)i);
+        if (alpha[i] > 0.0) {
+            double rho[kMaxCoins];
+            for (int k = 0; k < n_coins; ++k) rho[k] = std::log(R[(size_t)(i * n_coins + k)]);
+            if (!cfmm::curve_in_range(std::log(beta[i]), rho, n_coins))
+                return fail(c, CFMM_ERR_INVALID_ARG,
+                            "pool %lld: log(P0/R_k) = log(beta) - sum log R - log R_k must lie within +-%g when alpha > 0",
+                            (long long)i, cfmm::kCurveLogRange);
+        }
         return CFMM_OK;
     };
     int rc = ncoin_check(c, CFMM_KIND_CURVE, m, n_coins, R, gamma, Ai, R && gamma && Ai && alpha && beta,
@@ -572,11 +581,11 @@ int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* 
         return multi_add(c, CFMM_KIND_CURVE, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
             return cfmm_pools_add_curve(child, hi - lo, n_coins, R + nc * lo, gamma + lo, Ai + nc * lo, alpha + lo, beta + lo);
         }, nc);
-    // q = log R; per pool {α, log β}
+    // q = log R; per pool {α, log β} (curve_solve_lbeta: at α = 0, one that keeps P₀/R_k inside the solve's range)
     return ncoin_add(c, CFMM_KIND_CURVE, m, nc, R, gamma, Ai, [&](int64_t i, double* q, double* ab) {
         for (int k = 0; k < nc; ++k) q[k] = std::log(R[(size_t)(i * nc + k)]);
         ab[0] = alpha[i];
-        ab[1] = std::log(beta[i]);
+        ab[1] = cfmm::curve_solve_lbeta(alpha[i], std::log(beta[i]), q, nc);
     });
 }
 

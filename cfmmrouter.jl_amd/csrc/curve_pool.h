@@ -23,13 +23,42 @@
 // residual matters for speed, not accuracy: a lane that bisects its bracket down to the last bit runs ~60 steps, and a
 // wavefront runs at the pace of its slowest lane.)
 // No trade iff max_k γ·∇φ_k(R)/v_k <= min_k ∇φ_k(R)/v_k (the fee band): every trade is exactly +0.0.
+// Range: the band check and the start form P₀/R_k = exp(log β − Σρ − ρ_k) in linear space.  The upload refuses a pool with
+// α > 0 where one of them lies outside e^±kCurveLogRange (curve_in_range), and gives a pool with α = 0 -- Product, whose
+// trades do not depend on β -- a log β that centres them instead (curve_solve_lbeta).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
 namespace cfmm {
 
 constexpr int kCurveMaxIter = 64;
+constexpr double kCurveLogRange = 600.0;
+constexpr double kCurveFarStart = 64.0;   // log α − log(P₀/R_ref) beyond which the solve starts midway between them
+constexpr double kCurveReach = 16.0;      // longest Newton step before the bracket closes, in units of the doubling step
+constexpr double kCurveSMax = 680.0;      // |s| the iterates keep to: eˢ·c_k stays finite for price ratios up to e^29
+
+// Host: false iff some |log(P₀/R_k)| = |lbeta − Σρ − ρ_k| exceeds kCurveLogRange (or is NaN).
+inline bool curve_in_range(double lbeta, const double* rho, int n)
+{
+    double sr = 0.0;
+    for (int k = 0; k < n; ++k) sr += rho[k];
+    for (int k = 0; k < n; ++k)
+        if (!(std::fabs(lbeta - sr - rho[k]) <= kCurveLogRange)) return false;
+    return true;
+}
+
+// Host: log β as curve_solve takes it.  Unchanged, except at α = 0 outside the range: Σρ + mean ρ, which puts every
+// log(P₀/R_k) at mean ρ − ρ_k (the same level sets ΠR = const, hence the same trades).
+inline double curve_solve_lbeta(double alpha, double lbeta, const double* rho, int n)
+{
+    if (alpha != 0.0 || curve_in_range(lbeta, rho, n)) return lbeta;
+    double sr = 0.0;
+    for (int k = 0; k < n; ++k) sr += rho[k];
+    return sr + sr / n;
+}
 
 // Returns false inside the fee band (no trade).  Otherwise lr[k] = log r_k at the optimum (exactly ρ_k for a coin that
 // does not trade).  A NaN price gives NaN everywhere (as the other families propagate it).
@@ -69,6 +98,13 @@ __host__ __device__ inline bool curve_solve(const double (&rho)[N], const double
         e[k] = (v[k] - vmin) / vmin;
     }
     double s = L0 - rho[ref];   // eˢ = P₀/R_ref: the cheapest coin at the edge of entering
+    // A pool far from the product regime (α ≫ P₀/R_ref: near constant sum) drains one coin, to r ≈ P/(α·δ) for its price
+    // offset δ; E1 then puts s* a fraction (N − 1)/N of the way from log(P₀/R_ref) to log α (up to log δ / N): start there,
+    // not hundreds of units off
+    if (alpha > 0.0) {
+        const double la = log(alpha);
+        if (la - s > kCurveFarStart) s += (la - s) * ((N - 1.0) / N);
+    }
     double lo = -__builtin_inf(), hi = __builtin_inf(), step = 1.0, dx_old = __builtin_inf();
     for (int it = 0; it < kCurveMaxIter; ++it) {
         // ---- state at s: the terms, E1's root L, log r, E2 and its derivative
@@ -137,11 +173,16 @@ __host__ __device__ inline bool curve_solve(const double (&rho)[N], const double
         if (h > 0.0) lo = s; else hi = s;
         double sn = s - h / dh;
         const bool bracketed = lo != -__builtin_inf() && hi != __builtin_inf();
-        if (!(sn > lo && sn < hi) || (bracketed && !(2.0 * __builtin_fabs(sn - s) <= dx_old))) {
+        // (before the bracket closes, a Newton step longer than kCurveReach·step -- E2 is flat where few coins are live --
+        //  or one that leaves |s| <= kCurveSMax is a doubling step instead: beyond it eˢ overflows, and a state built from
+        //  infinite terms reads as converged with no trade)
+        if (!(sn > lo && sn < hi) || (bracketed && !(2.0 * __builtin_fabs(sn - s) <= dx_old)) ||
+            (!bracketed && !(__builtin_fabs(sn - s) <= kCurveReach * step && __builtin_fabs(sn) <= kCurveSMax))) {
             if (bracketed) {
                 sn = lo + 0.5 * (hi - lo);
             } else {
                 sn = h > 0.0 ? s + step : s - step;   // expand towards the sign change
+                sn = __builtin_fmin(__builtin_fmax(sn, -kCurveSMax), kCurveSMax);
                 step *= 2.0;
             }
         }

@@ -212,3 +212,23 @@ def optimality_ok(v_local, D, L, R, alpha, beta, gamma, rtol=1e-10):
     g = (alpha + Pp / Rp) / v
     band = np.max(gamma * g) <= np.min(g) + rtol * np.max(g)
     return bool(tight and band)
+
+
+def optimality_ok_mp(v_local, D, L, R, alpha, beta, gamma, rtol, Rp=None):
+    """optimality_ok's conditions in mpmath at the caller's precision, on trades given as mpf (the 60-digit truth before
+    it is rounded): primal feasibility, E2 tight and the fee band at R⁺, both relative to their own scales.  Rp: R⁺ itself
+    where R + γΔ − Λ would cancel (a coin drained to far below the working precision of its old reserve)."""
+    import mpmath as mp
+    M = lambda x: x if isinstance(x, mp.mpf) else mp.mpf(float(x))
+    R, v, D, L = [M(x) for x in R], [M(x) for x in v_local], [M(x) for x in D], [M(x) for x in L]
+    a, b, g = M(alpha), M(beta), M(gamma)
+    n = len(R)
+    Rp = [R[k] + g * D[k] - L[k] for k in range(n)] if Rp is None else [M(x) for x in Rp]
+    if not (all(x >= 0 for x in D + L) and all(x > 0 for x in Rp)):
+        return False
+    P0, Pp = b / mp.fprod(R), b / mp.fprod(Rp)
+    scale = a * mp.fsum(R[k] + abs(Rp[k] - R[k]) + g * D[k] + L[k] for k in range(n)) + P0 + Pp
+    tight = abs(a * mp.fsum(Rp[k] - R[k] for k in range(n)) - (Pp - P0)) <= rtol * scale
+    gr = [(a + Pp / Rp[k]) / v[k] for k in range(n)]
+    band = max(g * x for x in gr) <= min(gr) + rtol * max(gr)
+    return bool(tight and band)

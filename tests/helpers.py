@@ -1,4 +1,6 @@
 """Shared test helpers: bridge between the host mirror's PoolBatch containers and the CPU oracle."""
+import math
+
 import numpy as np
 
 import cfmmrouter_amd as cr
@@ -106,3 +108,32 @@ def route_converged(obj, market, n, v0=None, nthreads=1, solver="native", router
             "device_moved": rel_to_max(psi_default, psi_dev), "oracle_moved": rel_to_max(ref["psi"], psi_ref),
             "evaluations_device": int(evals), "evaluations_oracle": int(ref["info"]["funcalls"]),
             "polish_device": pol_dev, "polish_oracle": dict(ro.info["polish"]), "psi_scale": float(np.max(np.abs(psi_ref)))}
+
+
+def reduction_checks(c, rows, D, L, psi, acc, kk, bD, bL, check_self=True):
+    """Ψ / acc of a 60-digit fixture case (dict: v, Ai, truth D / L) against the device's own trades (math.fsum: the LDS
+    scatter and the folds, (c + 2)·u·Σ|terms| for c nonzero terms) and against the truth (the per-pool bounds K·(bD + bL)
+    summed, plus that reduction bound).  rows: the case's rows that were swept; D, L: the device's trades, or None."""
+    U = 2.0 ** -53
+    Ai0 = (c["Ai"][rows] - 1).ravel()
+    n = len(c["v"])
+    vl = c["v"][Ai0]
+    Dt, Lt = c["D"][rows].ravel(), c["L"][rows].ravel()
+    if check_self:
+        f = (L.ravel() - D.ravel())
+        for j in range(n):
+            t = f[Ai0 == j]
+            cj = np.count_nonzero(t)
+            assert abs(psi[j] - math.fsum(t)) <= (cj + 2) * U * np.sum(np.abs(t)), j
+        terms = np.concatenate([L.ravel() * vl, -(D.ravel() * vl)])
+        assert abs(acc - math.fsum(terms)) <= (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
+    ft = Lt - Dt
+    per = (kk[:, None] * (bD + bL)).ravel()
+    for j in range(n):
+        sel = Ai0 == j
+        t = ft[sel]
+        red = (np.count_nonzero(t) + 2) * U * np.sum(np.abs(t))
+        assert abs(psi[j] - math.fsum(t)) <= np.sum(per[sel]) + red, j
+    terms = np.concatenate([Lt * vl, -(Dt * vl)])
+    red = (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
+    assert abs(acc - math.fsum(terms)) <= np.sum(per * vl) + red

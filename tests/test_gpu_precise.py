@@ -15,7 +15,6 @@ trades (isolates the LDS scatter and the folds: (c + 2)·u·Σ|terms| for c nonz
 of the per-pool bounds plus that reduction bound).
 """
 import ctypes
-import math
 
 import numpy as np
 import pytest
@@ -24,6 +23,7 @@ import cfmmrouter_amd as cr
 import precise_ref as P
 import weighted_ref as wr
 from cfmmrouter_amd._lib import KIND_WEIGHTED
+from helpers import reduction_checks as _reduction_checks
 
 pytestmark = pytest.mark.gpu
 
@@ -117,32 +117,6 @@ def _scales(c, rows=slice(None)):
     if "weighted" in c:
         return P.weighted_scale(R, w, g, vl, Dt, Lt)
     return P.two_coin_scale(R, w, g, vl, Dt, Lt)
-
-
-def _reduction_checks(c, rows, D, L, psi, acc, kk, bD, bL, check_self=True):
-    """Ψ / acc against the device's own trades (fsum) and against the truth."""
-    Ai0 = (c["Ai"][rows] - 1).ravel()
-    n = len(c["v"])
-    vl = c["v"][Ai0]
-    Dt, Lt = c["D"][rows].ravel(), c["L"][rows].ravel()
-    if check_self:
-        f = (L.ravel() - D.ravel())
-        for j in range(n):
-            t = f[Ai0 == j]
-            cj = np.count_nonzero(t)
-            assert abs(psi[j] - math.fsum(t)) <= (cj + 2) * U * np.sum(np.abs(t)), j
-        terms = np.concatenate([L.ravel() * vl, -(D.ravel() * vl)])
-        assert abs(acc - math.fsum(terms)) <= (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
-    ft = Lt - Dt
-    per = (kk[:, None] * (bD + bL)).ravel()
-    for j in range(n):
-        sel = Ai0 == j
-        t = ft[sel]
-        red = (np.count_nonzero(t) + 2) * U * np.sum(np.abs(t))
-        assert abs(psi[j] - math.fsum(t)) <= np.sum(per[sel]) + red, j
-    terms = np.concatenate([Lt * vl, -(Dt * vl)])
-    red = (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
-    assert abs(acc - math.fsum(terms)) <= np.sum(per * vl) + red
 
 
 # ---- one pass over every case and path, shared by the tests below -----------------------------------------------
