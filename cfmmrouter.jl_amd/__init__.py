@@ -6,7 +6,7 @@ through libcfmm_amd.so (include/cfmm_amd.h); there is no CPU fallback in this pa
 """
 from ._lib import ArgumentError, CFMMDeviceError, Context, build, lib
 from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwoCoin, PoolBatch, Product, ProductTwoCoin,
-                    UniV3, find_arb_ as _find_arb_pool,
+                    SolidlyStableTwoCoin, UniV3, find_arb_ as _find_arb_pool,
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
@@ -23,6 +23,7 @@ def find_arb_(*args, **kw):
 
 __all__ = [
     "CFMM", "ProductTwoCoin", "GeometricMeanTwoCoin", "UniV3", "BoundedProduct", "GeometricMean", "Product", "Curve",
+    "SolidlyStableTwoCoin",
     "PoolBatch", "find_arb_",
     "update_reserves_", "Objective", "LinearNonnegative", "BasketLiquidation", "Swap", "f", "grad_",
     "lower_limit", "upper_limit", "Router", "route_", "netflows_", "netflows", "ArgumentError",

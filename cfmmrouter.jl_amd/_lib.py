@@ -22,7 +22,7 @@ ERR_HIP = -2
 ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 
-KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE = 0, 1, 2, 3, 4
+KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
 _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
@@ -105,6 +105,7 @@ def lib():
     L.cfmm_set_option.argtypes = [_ctx, C.c_char_p, C.c_int64]
     L.cfmm_get_option.argtypes = [_ctx, C.c_char_p, _i64p]
     L.cfmm_pools_add_product.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p]
+    L.cfmm_pools_add_solidly.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p]
     L.cfmm_pools_add_geomean.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _f64p, _i32p]
     L.cfmm_pools_add_univ3.argtypes = [_ctx, C.c_int64, _f64p, _f64p, _i32p, _i64p, _f64p, _f64p]
     L.cfmm_pools_add_weighted.argtypes = [_ctx, C.c_int64, C.c_int32, _f64p, _f64p, _f64p, _i32p]
@@ -256,6 +257,15 @@ class Context:
         if R.size != 2 * m or Ai0.size != 2 * m:
             raise ArgumentError("R and Ai must have shape [m, 2]")
         self._check(self._L.cfmm_pools_add_product(self._h, m, ptr(R), ptr(gamma), ptr(Ai0)))
+
+    def add_solidly(self, R, gamma, Ai0):
+        """m Solidly-style stable pairs (φ = x³y + xy³): the arrays of add_product (cfmm_pools_add_solidly)."""
+        R, gamma = f64(R), f64(gamma)
+        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
+        m = gamma.size
+        if R.size != 2 * m or Ai0.size != 2 * m:
+            raise ArgumentError("R and Ai must have shape [m, 2]")
+        self._check(self._L.cfmm_pools_add_solidly(self._h, m, ptr(R), ptr(gamma), ptr(Ai0)))
 
     def add_geomean(self, R, w, gamma, Ai0):
         R, w, gamma = f64(R), f64(w), f64(gamma)

@@ -10,6 +10,8 @@ tests written against the reference read the same here:
                                                          them without a find_arb!, the device solves them exactly)
     Curve(R, γ, Ai, α, β)                    src/cfmms.jl:66-70 (2..8 coins, φ = α·ΣR − β·ΠR⁻¹: StableSwap at
                                              fixed D; no find_arb! in the reference either)
+    SolidlyStableTwoCoin(R, γ, idx)          the Solidly family's stable pair, φ = R₁³R₂ + R₁R₂³ (not in the
+                                             reference; ProductTwoCoin's constructor, closed-form find_arb!)
 
 Token indices are 1-BASED, exactly as in the reference (`Ai[j]` is the global id of the pool's
 j-th coin); they are converted to 0-based int32 once, when a Router packs the pools for the
@@ -24,7 +26,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
 
 MAX_COINS = 8   # sweep.h kMaxCoins
 
@@ -64,6 +66,37 @@ class ProductTwoCoin(CFMM):
     @staticmethod
     def batch(R, γ, idx):
         return PoolBatch(KIND_PRODUCT, R=R, γ=γ, Ai=idx)
+
+
+SOLIDLY_EXP_RANGE = 150   # sweep.h kFastExp: reserves of a Solidly stable pair lie within [2^-150, 2^150]
+
+
+def _solidly_check(R, γ):
+    """The upload's own checks of a Solidly stable pair (cfmm_pools_add_solidly): γ <= 1 and the reserve range."""
+    R, γ = np.asarray(R, dtype=np.float64), np.asarray(γ, dtype=np.float64)
+    if np.any(~(γ > 0)) or np.any(γ > 1):
+        raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the arbitrage problem unbounded)")
+    lo, hi = 2.0 ** -SOLIDLY_EXP_RANGE, 2.0 ** SOLIDLY_EXP_RANGE
+    if R.size and not np.all((R >= lo) & (R < 2 * hi)):   # (the exponent test of the upload: [2^-150, 2^151))
+        raise ArgumentError(f"reserves of a Solidly stable pair must lie within [2^-{SOLIDLY_EXP_RANGE}, 2^{SOLIDLY_EXP_RANGE}]")
+
+
+class SolidlyStableTwoCoin(CFMM):
+    """SolidlyStableTwoCoin(R, γ, idx): φ(R) = R₁³R₂ + R₁R₂³, the "stable" pair of the Solidly family (Velodrome,
+    Aerodrome and forks) on decimal-normalised balances.  Not in the reference; constructor of ProductTwoCoin
+    (src/cfmms.jl:76-111) plus 0 < γ <= 1 and the upload's reserve range."""
+
+    kind = KIND_SOLIDLY
+
+    def __init__(self, R, γ, idx):
+        self.R, self.γ, self.Ai = _two_coin_check_cast(R, γ, idx)
+        _solidly_check(self.R, self.γ)
+
+    gamma = property(lambda self: self.γ)
+
+    @staticmethod
+    def batch(R, γ, idx):
+        return PoolBatch(KIND_SOLIDLY, R=R, γ=γ, Ai=idx)
 
 
 class GeometricMeanTwoCoin(CFMM):
@@ -189,9 +222,11 @@ def ϕ(cfmm, R=None):
     """ϕ(c::CFMM; R=nothing): the trading function -- src/cfmms.jl:36-42, :113-116 (ProductTwoCoin:
     R₁R₂), :167-171 (GeometricMeanTwoCoin: R₁^w₁ R₂^w₂).  The reference defines no method for UniV3.
     Host-side definition (O(1) per pool, used by the optimality tests, not by the sweep)."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve, SolidlyStableTwoCoin)):
         raise ArgumentError("ϕ has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, SolidlyStableTwoCoin):
+        return R[0] * R[1] * (R[0] * R[0] + R[1] * R[1])
     if isinstance(cfmm, Curve):
         return float(cfmm.α * np.sum(R) - cfmm.β / np.prod(R))
     if isinstance(cfmm, Product):
@@ -208,9 +243,13 @@ def ϕ(cfmm, R=None):
 def ϕ_grad_(out, cfmm, R=None):
     """∇ϕ!(x, c::CFMM; R=nothing): gradient of the trading function, stored in `out` --
     src/cfmms.jl:44-50, :117-122, :172-178."""
-    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve)):
+    if not isinstance(cfmm, (ProductTwoCoin, GeometricMeanTwoCoin, GeometricMean, Curve, SolidlyStableTwoCoin)):
         raise ArgumentError("∇ϕ! has no method for this pool type (as in the reference)")
     R = cfmm.R if R is None else np.asarray(R, dtype=np.float64)
+    if isinstance(cfmm, SolidlyStableTwoCoin):
+        x, y = R[0], R[1]
+        out[0], out[1] = y * (3.0 * x * x + y * y), x * (x * x + 3.0 * y * y)
+        return None
     if isinstance(cfmm, Curve):
         out[:] = cfmm.α + cfmm.β / np.prod(R) / R
         return None
@@ -277,13 +316,15 @@ def BoundedProduct(current_price, p_lower, p_upper, liquidity, γ, Ai):
 # (tick_off [m + 1], lower_ticks, liquidity).
 _FIELDS = {
     KIND_PRODUCT: ("R", "γ", "Ai"),
+    KIND_SOLIDLY: ("R", "γ", "Ai"),
     KIND_GEOMEAN: ("R", "w", "γ", "Ai"),
     KIND_WEIGHTED: ("R", "w", "γ", "Ai"),
     KIND_CURVE: ("R", "γ", "Ai", "α", "β"),
     KIND_UNIV3: ("current_price", "γ", "Ai"),
 }
 _COIN_FIELDS = ("R", "w", "Ai")
-_POOL_TYPE = {KIND_PRODUCT: ProductTwoCoin, KIND_GEOMEAN: GeometricMeanTwoCoin, KIND_WEIGHTED: GeometricMean, KIND_CURVE: Curve}
+_POOL_TYPE = {KIND_PRODUCT: ProductTwoCoin, KIND_GEOMEAN: GeometricMeanTwoCoin, KIND_WEIGHTED: GeometricMean, KIND_CURVE: Curve,
+              KIND_SOLIDLY: SolidlyStableTwoCoin}
 _NCOIN_NAME = {KIND_WEIGHTED: "weighted", KIND_CURVE: "Curve"}
 # value checks of N-coin batches, in order: field, zero allowed, message
 _NCOIN_CHECKS = (("R", False, "reserves must be finite and > 0"), ("w", False, "weights must be finite and > 0"),
@@ -310,6 +351,8 @@ class PoolBatch:
         for f in _FIELDS[kind]:
             if f != "γ":
                 self._set(f, a, m, 2)
+        if kind == KIND_SOLIDLY:
+            _solidly_check(self.R, self.γ)
         if kind == KIND_UNIV3:
             self.tick_off = np.ascontiguousarray(a["tick_off"], dtype=np.int64).reshape(m + 1)
             self.lower_ticks = np.ascontiguousarray(a["lower_ticks"], dtype=np.float64).reshape(-1)
@@ -431,6 +474,8 @@ def find_arb_(Δ, Λ, cfmm, v, device=0):
 def _with_local_idx(c):
     if c.kind == KIND_PRODUCT:
         return ProductTwoCoin(c.R, c.γ, [1, 2])
+    if c.kind == KIND_SOLIDLY:
+        return SolidlyStableTwoCoin(c.R, c.γ, [1, 2])
     if c.kind == KIND_GEOMEAN:
         return GeometricMeanTwoCoin(c.R, c.w, c.γ, [1, 2])
     if c.kind == KIND_WEIGHTED:
@@ -447,6 +492,8 @@ def _upload(ctx, batch: PoolBatch):
         raise ArgumentError(f"token index out of range 1:{ctx.n_tokens}")
     if batch.kind == KIND_PRODUCT:
         ctx.add_product(batch.R, batch.γ, Ai0)
+    elif batch.kind == KIND_SOLIDLY:
+        ctx.add_solidly(batch.R, batch.γ, Ai0)
     elif batch.kind == KIND_GEOMEAN:
         ctx.add_geomean(batch.R, batch.w, batch.γ, Ai0)
     elif batch.kind == KIND_WEIGHTED:

@@ -15,6 +15,9 @@ One line per pool:
                                      (3..8 tokens: one GeometricMean batch per token count, weights normalised)
     {"type": "curve", "tokens": [...], "decimals": [...], "balances": [...], "A": 200,
      "fee": 0.0004}                                                                     StableSwap pools, 2..8 tokens
+    {"type": "solidly_stable", "tokens": ["0xA..", "0xB.."], "decimals": [18, 6],
+     "reserves": ["123..", "456.."], "fee_bps": 5}                                     Solidly-family stable pairs
+                                     (Velodrome, Aerodrome, ...: x³y + xy³ on the decimal-normalised balances)
     {"type": "concentrated", "tokens": [token0, token1], "decimals": [d0, d1], "fee_pips": 3000,
      "sqrt_price_x96": "...", "liquidity": "...", "ticks": [[index, liquidity_net], ...]}   Uniswap-v3 style pools
 
@@ -45,7 +48,7 @@ from fractions import Fraction
 import numpy as np
 
 from ._lib import ArgumentError
-from .cfmms import MAX_COINS, Curve, GeometricMean, GeometricMeanTwoCoin, ProductTwoCoin, UniV3
+from .cfmms import MAX_COINS, Curve, GeometricMean, GeometricMeanTwoCoin, ProductTwoCoin, SolidlyStableTwoCoin, UniV3
 
 Q96 = 1 << 96
 TICK_BASE = 1.0001
@@ -121,7 +124,8 @@ def concentrated_to_univ3(sqrt_price_x96, ticks, d0, d1, liquidity=None, where="
 def load_snapshot(source):
     """source: path to a JSON-lines file, or an iterable of dicts / JSON strings.
     -> (tokens, batches): the token identifiers in index order (index k+1 is the reference's 1-based token id) and the
-    pool batches [ProductTwoCoin..., GeometricMeanTwoCoin..., UniV3...] (families that do not occur are omitted)."""
+    pool batches [ProductTwoCoin..., GeometricMeanTwoCoin..., UniV3..., SolidlyStableTwoCoin..., then the N-coin
+    families] (families that do not occur are omitted)."""
     if isinstance(source, (str, bytes)):
         with open(source) as f:
             records = [json.loads(line) for line in f if line.strip() and not line.lstrip().startswith("#")]
@@ -135,7 +139,7 @@ def load_snapshot(source):
             tokens.append(name)
         return index[name]
 
-    prod, geo, conc, multi, curve = [], [], [], {}, {}
+    prod, geo, conc, multi, curve, solid = [], [], [], {}, {}, []
     for k, rec in enumerate(records):
         where = f"pool {k}"
         toks = rec.get("tokens")
@@ -157,6 +161,12 @@ def load_snapshot(source):
         if kind == "constant_product":
             r = rec.get("reserves")
             prod.append(([_amount(r[0], dec[0], where), _amount(r[1], dec[1], where)], g, ai))
+        elif kind == "solidly_stable":
+            # whole-token amounts: the normalisation these contracts apply before they evaluate x³y + xy³
+            r = rec.get("reserves")
+            if r is None or len(r) != 2:
+                raise ArgumentError(f"{where}: reserves must have two entries")
+            solid.append(([_amount(r[0], dec[0], where), _amount(r[1], dec[1], where)], g, ai))
         elif kind == "weighted":
             r, w = rec.get("balances"), [float(x) for x in rec.get("weights", ())]
             if len(w) != 2 or min(w) <= 0:
@@ -180,6 +190,8 @@ def load_snapshot(source):
         np.cumsum([len(c[1]) for c in conc], out=off[1:])
         batches.append(UniV3.batch([c[0] for c in conc], off, np.concatenate([c[1] for c in conc]),
                                    np.concatenate([c[2] for c in conc]), [c[3] for c in conc], [c[4] for c in conc]))
+    if solid:
+        batches.append(SolidlyStableTwoCoin.batch([p[0] for p in solid], [p[1] for p in solid], [p[2] for p in solid]))
     for n in sorted(multi):   # 3..8-token weighted pools: one batch per coin count (GeometricMean, src/cfmms.jl:60-63)
         pools = multi[n]
         batches.append(GeometricMean.batch([p[0] for p in pools], [p[1] for p in pools], [p[2] for p in pools],

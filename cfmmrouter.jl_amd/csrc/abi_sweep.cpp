@@ -208,21 +208,22 @@ int ensure_geometry(cfmm_ctx* c)
     for (auto& s : c->segs) {
         plan_segment(c, s);
         const bool wt = ragged_kind(s.kind);
+        const bool own = own_launch_kind(s.kind);   // (Solidly: two-coin trade rows, but never in a fused launch)
         s.trade_off = trades;           // (weighted / Curve segments have no rows in the two-coin trade buffers)
         s.flat_off = flat;
         if (!wt) trades += s.m;
         pools += s.m;
         flat += s.m * (wt ? s.n_coins : 2);
-        if (!wt) ++n_two_coin;
+        if (!own) ++n_two_coin;
         c->any_ragged = c->any_ragged || wt;
-        any_big = any_big || (!wt && s.block == kBigBlock);
+        any_big = any_big || (!own && s.block == kBigBlock);
     }
     c->groups.clear();
     const bool fusable = c->opt_fuse_segments != 0 && n_two_coin >= 2 && c->opt_geomean_exact == 0;
-    // launch groups: every N-coin segment alone (sweep_ncoin); runs of consecutive two-coin segments
-    // fused by up to kMaxMulti (sweep_multi) or one launch each
+    // launch groups: every N-coin and every Solidly segment alone (own_launch_kind); runs of consecutive segments of the
+    // other two-coin families fused by up to kMaxMulti (sweep_multi) or one launch each
     for (size_t run = 0; run < c->segs.size();) {
-        if (ragged_kind(c->segs[run].kind)) {
+        if (own_launch_kind(c->segs[run].kind)) {
             Segment& sg = c->segs[run];
             Group g;
             g.first = (int)run;
@@ -236,7 +237,7 @@ int ensure_geometry(cfmm_ctx* c)
             continue;
         }
         size_t run_end = run;
-        while (run_end < c->segs.size() && !ragged_kind(c->segs[run_end].kind)) ++run_end;
+        while (run_end < c->segs.size() && !own_launch_kind(c->segs[run_end].kind)) ++run_end;
         if (fusable) {
             // fused launches use 512-thread blocks (Product / GeoMean blocks interleave on every CU) unless asked otherwise
             const int block = (any_big && c->opt_block == kBigBlock) ? kBigBlock : kMidBlock;
@@ -320,7 +321,8 @@ int ensure_geometry(cfmm_ctx* c)
     c->touched_bytes = 0;
     for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3)
         c->touched_bytes += s.m * (ragged_kind(s.kind) ? ncoin_family(s.kind).bytes_per_pool(s.n_coins)
-                                   : (int64_t)(s.kind == CFMM_KIND_PRODUCT ? 24 + 16 : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
+                                   : (int64_t)(s.kind == CFMM_KIND_PRODUCT || s.kind == CFMM_KIND_SOLIDLY ? 24 + 16
+                                               : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
                                                : (s.has_walk ? 104 : 56) + 16));
     if (rows > c->rows_cap) {
         (void)hipFree(c->d_partials);
@@ -490,6 +492,7 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
             if (ragged_kind(s.kind)) e = launch_sweep_ncoin(s.kind, ncoin_of(s), a, cfg, materialize, c->stream);
             else if (s.kind == CFMM_KIND_PRODUCT) e = launch_sweep(product_of(s), a, cfg, materialize, c->stream);
             else if (s.kind == CFMM_KIND_GEOMEAN) e = launch_sweep(geomean_of(s), a, cfg, materialize, c->stream);
+            else if (s.kind == CFMM_KIND_SOLIDLY) e = launch_sweep_solidly(product_of(s), a, cfg, materialize, c->stream);
             else e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream);
         }
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));

@@ -456,6 +456,38 @@ int cfmm_pools_add_product(cfmm_ctx* c, int64_t m, const double* R, const double
     return add_segment_common(c, std::move(s), Ai);
 }
 
+int cfmm_pools_add_solidly(cfmm_ctx* c, int64_t m, const double* R, const double* gamma, const int32_t* Ai)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    int rc = check_two_coin(c, m, R, gamma, Ai);
+    if (rc != CFMM_OK) return rc;
+    for (int64_t i = 0; i < m; ++i) {
+        if (gamma[i] > 1.0)
+            return fail(c, CFMM_ERR_INVALID_ARG,
+                        "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
+                        (long long)i);
+        // the closed form cubes R2/R1 (SolidlyOps): 2^±300 cubed is finite, anything wider need not be
+        if (!in_fast_window(R[2 * i]) || !in_fast_window(R[2 * i + 1]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves of a Solidly stable pair must lie within [2^-%d, 2^%d]",
+                        (long long)i, kFastExp, kFastExp);
+    }
+    if (!c->shards.empty())
+        return multi_add(c, CFMM_KIND_SOLIDLY, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
+            return cfmm_pools_add_solidly(child, hi - lo, R + 2 * lo, gamma + lo, Ai + 2 * lo);
+        });
+    HIP_TRY(c, hipSetDevice(c->device));
+    Segment s;
+    s.kind = CFMM_KIND_SOLIDLY;
+    s.m = m;
+    s.fast_ok = 0;   // one arithmetic only (the compiler's)
+    if ((rc = upload(c, &s.R, R, (size_t)m)) || (rc = upload(c, &s.gamma, gamma, (size_t)m)) ||
+        (rc = upload(c, &s.Ai, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai))) {
+        free_segment(s);
+        return rc;
+    }
+    return add_segment_common(c, std::move(s), Ai);
+}
+
 int cfmm_pools_add_geomean(cfmm_ctx* c, int64_t m, const double* R, const double* w, const double* gamma,
                            const int32_t* Ai)
 {

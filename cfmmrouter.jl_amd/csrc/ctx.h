@@ -83,6 +83,10 @@ struct Segment {
 // Segments whose trades are ragged (n_coins per pool, kept in the segment's own nc.D / nc.L): their own launch each.
 inline bool ragged_kind(int kind) { return kind == CFMM_KIND_WEIGHTED || kind == CFMM_KIND_CURVE; }
 
+// Segments that are always their own launch (never in a fused sweep_multi group): the ragged kinds, and Solidly stable
+// pairs -- a two-coin kind (trades in the common [m][2] buffers) whose kernel is kept out of the fused launches
+inline bool own_launch_kind(int kind) { return ragged_kind(kind) || kind == CFMM_KIND_SOLIDLY; }
+
 // What the host knows of an N-coin family (ragged_kind); the device side is sweep_kernels.hip's WeightedFamily / CurveFamily.
 struct NCoinFamily {
     const char* name;          // in error texts

@@ -218,6 +218,10 @@ hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchC
                         hipStream_t s);
 hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
                         hipStream_t s);
+// Solidly-style stable pairs (kind CFMM_KIND_SOLIDLY, φ = x³y + xy³): ProductTwoCoin's pool layout, their own launch
+// (full-range arithmetic, never fused; single-block direct and large-market mode like any two-coin family)
+hipError_t launch_sweep_solidly(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+                                hipStream_t s);
 
 // N-coin segments (kind CFMM_KIND_WEIGHTED or CFMM_KIND_CURVE) are their own launch (kMidBlock threads, full-range
 // arithmetic, never fused, never single-block direct): a.Delta / a.Lambda / a.Over / a.gflow are unused (the trades go to

@@ -455,6 +455,62 @@ struct GeoMeanLogOps {
 };
 
 // ---------------------------------------------------------------------------------------------
+// Solidly-style stable pair, φ(x, y) = x³y + xy³.  The reference declares no such pool; the arbitrage
+// problem is find_arb!'s (src/cfmms.jl:21-33) and has a closed form.
+// ---------------------------------------------------------------------------------------------
+// φ is homogeneous, so the marginal price of coin 1 in coin 2 depends on t = y/x only: p(t) = t(3 + t²)/(1 + 3t²), and
+// with a = t + 1, b = t − 1 it is (a³ + b³)/(a³ − b³), hence p(t) = π ⇔ (t − 1)/(t + 1) = c, c = cbrt((π − 1)/(π + 1)).
+// Written for the TENDERED coin a and the received coin b (φ is symmetric, so direction 2 is direction 1 with the coins
+// swapped): the pool trades iff γ·p(r_b/r_a) > v_a/v_b, and the optimum has π = v_a/(γ·v_b), i.e.
+//     c³ = (v_a − γ·v_b)/(v_a + γ·v_b)             the numerator with ONE rounding (fma): it cancels near the band
+//     t  = (1 + c)/(1 − c) = π·(1 + c + c²)/(1 − c + c²)    (1 ± c = (1 ± c³)/(1 ∓ c + c²), and (1 + c³)/(1 − c³) = π: no
+//                                                            cancellation for any π; both quadratics lie in [3/4, 3])
+// for the ratio r_b′/r_a′ of the new reserves; φ(r′) = φ(r) then gives r_a′ = r_a·(t₀(1 + t₀²)/(t(1 + t²)))^¼ with
+// t₀ = r_b/r_a (two square roots; k = φ(R) itself is never formed: it overflows at R ≈ 1e77) and r_b′ = t·r_a′.
+// With γ <= 1 (checked at upload) the two directions exclude each other, in floating point too: the two tests share
+// their products A, B, and g·A > B implies A >= fl(g·A) > B >= fl(g·B).  One arithmetic (the compiler's full-range
+// division, square root and cbrt): upload range R ∈ [2^-150, 2^150] keeps t₀³ finite.
+struct SolidlyOps {
+    static constexpr bool kNeedsLogPrices = false;
+    static constexpr bool kPrefetch = true;
+    using Raw = ProductOps::Raw;     // ProductTwoCoin's pool layout and loads: only the solve differs
+    ProductPools p;
+    template <bool GBINS>
+    __device__ __forceinline__ Raw load(int64_t i) const { return ProductOps{p}.template load<GBINS>(i); }
+    template <bool GBINS, bool FAST>
+    __device__ __forceinline__ void resolve(Raw& r, const double2* gtab_lds) const
+    {
+        ProductOps{p}.template resolve<GBINS, FAST>(r, gtab_lds);
+    }
+    __device__ __forceinline__ int2 tokens(const Raw& r) const { return r.ai; }
+    template <bool FAST>   // (no fast variant)
+    __device__ __forceinline__ int solve_dir(const Raw& r, const Px& px, double& d, double& l, Trade& t) const
+    {
+        const double R1 = r.R.x, R2 = r.R.y, g = r.g, v1 = px.v1, v2 = px.v2;
+        d = l = 0.0;
+        if (v1 != v1 || v2 != v2) { t.d1 = t.d2 = t.l1 = t.l2 = v1 + v2; return kDirBoth; }   // NaN prices propagate
+        // direction without a division: γ·v₂·φₓ(R) > v₁·φ_y(R) (1), v₂·φₓ(R) < γ·v₁·φ_y(R) (2); inside the band neither
+        const double s1 = R1 * R1, s2 = R2 * R2;
+        const double A = v2 * (R2 * __builtin_fma(3.0, s1, s2));
+        const double B = v1 * (R1 * __builtin_fma(3.0, s2, s1));
+        const bool p1 = g * A > B, p2 = A < g * B;
+        if (!(p1 || p2)) return kDirNone;
+        const double va = p1 ? v1 : v2, vb = p1 ? v2 : v1;     // prices of the tendered / received coin
+        const double ra = p1 ? R1 : R2, rb = p1 ? R2 : R1;
+        const double num = __builtin_fma(-g, vb, va), den = __builtin_fma(g, vb, va);
+        const double c = cbrt(num / den);
+        const double c2 = c * c;
+        const double tt = (va * ((1.0 + c) + c2)) / ((g * vb) * ((1.0 - c) + c2));   // r_b′/r_a′
+        const double t0 = rb / ra;
+        const double rho = (t0 * __builtin_fma(t0, t0, 1.0)) / (tt * __builtin_fma(tt, tt, 1.0));
+        const double xa = ra * sqrt(sqrt(rho));                // the tendered coin's new reserve
+        d = max0(xa - ra) / g;
+        l = max0(rb - tt * xa);
+        return p1 ? kDir1 : kDir2;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // UniV3 / BoundedProduct -- src/cfmms.jl:294-395 (lane per pool, serial tick walk)
 // ---------------------------------------------------------------------------------------------
 // Everything compute_at_tick (:294-313) derives is independent of v, so it is evaluated ONCE at
@@ -1716,6 +1772,7 @@ hipError_t prepare_kernels(size_t max_lds_bytes)
     if ((e = set_lds_attr<ProductOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<ProductOps, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<GeoMeanOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
+    if ((e = set_lds_attr<SolidlyOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<GeoMeanLogOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<GeoMeanLogOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
     if ((e = set_lds_attr<GeoMeanLogOps, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
@@ -1768,6 +1825,10 @@ hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchC
 {
     if (p.reference_order) return launch_any<GeoMeanOps, false>(GeoMeanOps{p}, a, c, mat, s);
     return launch_any(GeoMeanLogOps{p}, a, c, mat, s);
+}
+hipError_t launch_sweep_solidly(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+{
+    return launch_any<SolidlyOps, false>(SolidlyOps{p}, a, c, mat, s);
 }
 hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
 {

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
 from .cfmms import CFMM, PoolBatch, _upload
 
 
@@ -83,7 +83,7 @@ def _segments_of(cfmms):
         if not isinstance(c, CFMM):
             raise ArgumentError("cfmms must hold CFMM objects or PoolBatch containers")
     batches, order = [], []
-    for kind in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3):
+    for kind in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_SOLIDLY):   # (Solidly last: it never joins a fused launch)
         idx = [i for i, c in enumerate(cfmms) if c.kind == kind]
         if idx:
             batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
@@ -94,7 +94,8 @@ def _segments_of(cfmms):
             if idx:
                 batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
                 order.extend(idx)
-    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE)]
+    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE,
+                                                             KIND_SOLIDLY)]
     for i in host:
         if not callable(getattr(cfmms[i], "find_arb_", None)) or not hasattr(cfmms[i], "Ai"):
             raise ArgumentError(f"cfmms[{i}] ({type(cfmms[i]).__name__}): a pool type without a device kernel needs its own "

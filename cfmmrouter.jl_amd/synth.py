@@ -19,7 +19,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3, KIND_WEIGHTED
+from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED
 from .cfmms import PoolBatch
 
 _M64 = np.uint64(0xFFFFFFFFFFFFFFFF)
@@ -74,6 +74,17 @@ def geomean_pools(m, n_tokens, seed=1234, first=0):
     w1 = np.clip(uniform(seed, 25, m, first), 0.02, 0.98)  # keep η = w₁/w₂ in [1/49, 49]
     w = np.stack([w1, 1.0 - w1], axis=1)
     return PoolBatch(KIND_GEOMEAN, R=R, w=w, γ=γ, Ai=token_pairs(seed, 23, m, n_tokens, first))
+
+
+def solidly_pools(m, n_tokens, seed=1234, first=0, spread=0.05, wide=False):
+    """m Solidly-style stable pairs (KIND_SOLIDLY, φ = x³y + xy³): R₁ = 1000·U + 1 and R₂ = R₁·t₀ with
+    t₀ = exp(spread·(2U − 1)) -- near balance (default: t₀ within e^±0.05), the regime the curve is built for;
+    `wide`: t₀ over e^±3.  Fees: half the pools 0.9995 (5 bp), half 1."""
+    s = 3.0 if wide else float(spread)
+    R1 = 1000.0 * uniform(seed, 50, m, first) + 1.0
+    R = np.stack([R1, R1 * np.exp(s * (2.0 * uniform(seed, 51, m, first) - 1.0))], axis=1)
+    γ = np.where(uniform(seed, 52, m, first) < 0.5, 0.9995, 1.0)
+    return PoolBatch(KIND_SOLIDLY, R=R, γ=γ, Ai=token_pairs(seed, 53, m, n_tokens, first))
 
 
 def token_price_vector(n_tokens, seed=1234):

@@ -43,6 +43,7 @@ extern "C" {
 #define CFMM_KIND_UNIV3 2   /* UniV3/BoundedProduct  src/cfmms.jl:226-395 */
 #define CFMM_KIND_WEIGHTED 3 /* GeometricMean / Product with 2..8 coins  src/cfmms.jl:57-64 (no find_arb! there) */
 #define CFMM_KIND_CURVE 4    /* Curve (StableSwap) with 2..8 coins       src/cfmms.jl:66-70 (no find_arb! there) */
+#define CFMM_KIND_SOLIDLY 5  /* Solidly-style stable pair, phi = x^3 y + x y^3 (no such pool in the reference) */
 
 typedef struct cfmm_ctx cfmm_ctx;
 
@@ -193,6 +194,19 @@ int cfmm_pools_add_weighted(cfmm_ctx* ctx, int64_t m, int32_t n_coins, const dou
 int cfmm_pools_add_curve(cfmm_ctx* ctx, int64_t m, int32_t n_coins, const double* R, const double* gamma,
                          const int32_t* Ai, const double* alpha, const double* beta);
 
+/* m x SolidlyStableTwoCoin(R, gamma, idx): the "stable" pair of the Solidly family (Velodrome, Aerodrome and forks),
+ *     phi(x, y) = x^3 y + x y^3   on decimal-normalised balances.
+ * The reference has no such pool; solved here is the problem of its find_arb! docstring (src/cfmms.jl:21-33), which has a
+ * closed form for this phi: one cbrt, two square roots and five divisions per trading pool.  The
+ * fee is the reference's input-side gamma, as for every family.
+ * Array shapes and checks of cfmm_pools_add_product, plus: gamma <= 1 (gamma > 1 is refused, as for the N-coin families:
+ * the closed form assumes that at most one direction trades) and every reserve within [2^-150, 2^150] (the cube of
+ * R2/R1 must stay finite).  A two-coin kind: its trades live in the common [m][2] buffers (cfmm_get_trades,
+ * cfmm_trades_dev), large-market mode (n_tokens > 8192) works, cfmm_update_reserves applies R <- (R + gamma Delta) - Lambda.
+ * Every call is its own segment and its own launch (never fused with other families); one arithmetic (the compiler's
+ * full-range division, square root and cbrt; option "fast_math" does not apply). */
+int cfmm_pools_add_solidly(cfmm_ctx* ctx, int64_t m, const double* R, const double* gamma, const int32_t* Ai);
+
 int cfmm_pools_clear(cfmm_ctx* ctx);
 int64_t cfmm_pools_count(const cfmm_ctx* ctx); /* length(r.cfmms) */
 int32_t cfmm_n_tokens(const cfmm_ctx* ctx);    /* length(r.v) */
@@ -226,6 +240,7 @@ int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t cou
  * src/cfmms.jl:26-31: the pool ends at R + γΔ − Λ), applied IN PLACE ON THE DEVICE from the trades of
  * the latest materialising sweep (cfmm_find_arb, cfmm_route; consumed by this call):
  *   ProductTwoCoin / GeometricMeanTwoCoin:  R <- (R + γΔ) − Λ            (one kernel, no host traffic)
+ *   Solidly stable pairs (CFMM_KIND_SOLIDLY): R <- (R + γΔ) − Λ           (the same kernel)
  *   weighted (CFMM_KIND_WEIGHTED):          R <- (R + γΔ) − Λ per coin    (one kernel, no host traffic)
  *   Curve (CFMM_KIND_CURVE):                R <- (R + γΔ) − Λ per coin    (one kernel; α, β unchanged)
  *   UniV3 / BoundedProduct: the state is the price.  A pool that traded moves to the internal price

@@ -20,9 +20,32 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
 
-export AMDRouter, route_native!, polish!
+export AMDRouter, route_native!, polish!, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
+
+# The "stable" pair of the Solidly family (Velodrome, Aerodrome and forks): φ(R) = R₁³R₂ + R₁R₂³ on decimal-normalised
+# balances.  CFMMRouter.jl has no such pool; this type exists for the device, which solves its arbitrage problem in
+# closed form (include/cfmm_amd.h, cfmm_pools_add_solidly).  Fields and constructor arguments of ProductTwoCoin
+# (src/cfmms.jl:101-111); 0 < γ <= 1 and reserves within [2^-150, 2^150] are checked at upload.
+struct SolidlyStableTwoCoin{T} <: CFMM{T}
+    R::Vector{T}
+    γ::T
+    Ai::Vector{UInt}
+    function SolidlyStableTwoCoin(R, γ, idx)
+        length(R) == 2 || throw(ArgumentError("length of R must be 2 for *TwoCoin constructors"))
+        length(idx) == 2 || throw(ArgumentError("length of idx must be 2 for *TwoCoin constructors"))
+        T = eltype(float.(R))
+        return new{T}(collect(T, R), convert(T, γ), convert.(UInt, collect(idx)))
+    end
+end
+CFMMRouter.ϕ(c::SolidlyStableTwoCoin; R=nothing) = (R = isnothing(R) ? c.R : R; R[1] * R[2] * (R[1]^2 + R[2]^2))
+function CFMMRouter.∇ϕ!(x, c::SolidlyStableTwoCoin; R=nothing)
+    R = isnothing(R) ? c.R : R
+    x[1] = R[2] * (3 * R[1]^2 + R[2]^2)
+    x[2] = R[1] * (R[1]^2 + 3 * R[2]^2)
+    return nothing
+end
 
 struct CFMMAMDError <: Exception
     code::Cint
@@ -108,6 +131,16 @@ function build_router(objective::O, cfmms::Vector{C}, n_tokens, ctx::Ptr{Cvoid})
         GC.@preserve cp γ Ai off ticks liq check(ctx, ccall((:cfmm_pools_add_univ3, LIB), Cint,
             (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
             ctx, length(idx), cp, γ, Ai, off, ticks, liq))
+        append!(order, idx)
+    end
+    # --- Solidly stable pairs (φ = R₁³R₂ + R₁R₂³; this module's own type): ProductTwoCoin's arrays ---
+    idx = findall(c -> c isa SolidlyStableTwoCoin, cfmms)
+    if !isempty(idx)
+        R = Float64[c.R[j] for j in 1:2, c in cfmms[idx]]
+        γ = Float64[c.γ for c in cfmms[idx]]
+        Ai = Int32[c.Ai[j] - 1 for j in 1:2, c in cfmms[idx]]
+        GC.@preserve R γ Ai check(ctx, ccall((:cfmm_pools_add_solidly, LIB), Cint,
+            (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ctx, length(idx), R, γ, Ai))
         append!(order, idx)
     end
     # --- N-coin GeometricMean / Product pools (src/cfmms.jl:56-63): one weighted segment per coin count ---
@@ -247,7 +280,7 @@ function update_reserves!(r::AMDRouter; sync::Bool=true)
     check(r.ctx, ccall((:cfmm_update_reserves, LIB), Cint, (Ptr{Cvoid},), r.ctx))
     if sync
         seg, pos = Int32(0), 0
-        for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3)
+        for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3, SolidlyStableTwoCoin)
             idx = [i for i in r.order[pos+1:end] if r.cfmms[i] isa T]   # r.order is grouped by family
             isempty(idx) && continue
             if T === UniV3
