@@ -59,7 +59,7 @@ int cfmm_ctx_create(int device_id, int32_t n_tokens, cfmm_ctx** out)
     cfmm_ctx* c = new cfmm_ctx();
     c->device = device_id;
     c->n = n_tokens;
-    c->n_pad = (n_tokens + 1) & ~1;
+    c->n_pad = n_pad_of(n_tokens);
     auto bail = [&](int code) {
         g_create_error = c->err;
         cfmm_ctx_destroy(c);
@@ -133,7 +133,7 @@ int cfmm_ctx_create_multi(int32_t n_devices, const int32_t* device_ids, int32_t 
     cfmm_ctx* c = new cfmm_ctx();
     c->device = -1;
     c->n = n_tokens;
-    c->n_pad = (n_tokens + 1) & ~1;
+    c->n_pad = n_pad_of(n_tokens);
     c->workers.reset(new Workers());
     c->workers->rc.assign((size_t)n_devices, CFMM_OK);
     for (int d = 0; d < n_devices; ++d) {
@@ -209,14 +209,14 @@ static int64_t* option_slot(cfmm_ctx* c, const char* key)
 {
     if (!key) return nullptr;
     struct { const char* name; int64_t* slot; } table[] = {
-        {"max_grid", &c->opt_max_grid}, {"block", &c->opt_block}, {"bin_copies", &c->opt_bin_copies},
-        {"time_kernels", &c->opt_time_kernels}, {"geomean_exact", &c->opt_geomean_exact},
-        {"fuse_segments", &c->opt_fuse_segments}, {"zero_copy", &c->opt_zero_copy},
-        {"alternate", &c->opt_alternate}, {"pack", &c->opt_pack}, {"compact_trades", &c->opt_compact_trades},
+        {"max_grid", &c->geo.max_grid}, {"block", &c->geo.block}, {"bin_copies", &c->geo.bin_copies},
+        {"time_kernels", &c->opt_time_kernels}, {"geomean_exact", &c->geo.geomean_exact},
+        {"fuse_segments", &c->geo.fuse_segments}, {"zero_copy", &c->opt_zero_copy},
+        {"alternate", &c->opt_alternate}, {"pack", &c->geo.pack}, {"compact_trades", &c->opt_compact_trades},
         {"fast_math", &c->opt_fast_math}, {"armed", &c->opt_armed}, {"arm_timeout_ms", &c->opt_arm_timeout_ms},
-        {"cost_geomean", &c->opt_cost_geomean}, {"cost_univ3", &c->opt_cost_univ3}, {"host_flag", &c->opt_host_flag},
+        {"cost_geomean", &c->geo.cost_geomean}, {"cost_univ3", &c->geo.cost_univ3}, {"host_flag", &c->opt_host_flag},
         {"stop_in_noise", &c->opt_stop_in_noise}, {"multi_threads", &c->opt_multi_threads},
-        {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->opt_direct_small}, {"stream_stores", &c->opt_stream_stores},
+        {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->geo.direct_small}, {"stream_stores", &c->opt_stream_stores},
 #ifdef CFMM_TEST_HOOKS
         {"debug_stall_ms", &c->opt_debug_stall_ms},
 #endif
@@ -231,10 +231,10 @@ int cfmm_set_option(cfmm_ctx* c, const char* key, int64_t value)
     if (!c) return CFMM_ERR_INVALID_ARG;
     int64_t* slot = option_slot(c, key);
     if (!slot) return fail(c, CFMM_ERR_INVALID_ARG, "unknown option '%s'", key ? key : "(null)");
-    if (slot == &c->opt_max_grid && value < 0) return fail(c, CFMM_ERR_INVALID_ARG, "max_grid must be >= 0 (0 = auto)");
-    if (slot == &c->opt_block && !(value == 0 || value == kMidBlock || value == kBigBlock))
+    if (slot == &c->geo.max_grid && value < 0) return fail(c, CFMM_ERR_INVALID_ARG, "max_grid must be >= 0 (0 = auto)");
+    if (slot == &c->geo.block && !(value == 0 || value == kMidBlock || value == kBigBlock))
         return fail(c, CFMM_ERR_INVALID_ARG, "block must be 0 (auto), %d or %d", kMidBlock, kBigBlock);
-    if (slot == &c->opt_bin_copies && !(value == 0 || value == 1 || value == 2))
+    if (slot == &c->geo.bin_copies && !(value == 0 || value == 1 || value == 2))
         return fail(c, CFMM_ERR_INVALID_ARG, "bin_copies must be 0 (auto), 1 (shared) or 2 (per wavefront)");
     if (slot == &c->opt_stream_stores && !(value == 0 || value == 1 || value == 2))
         return fail(c, CFMM_ERR_INVALID_ARG, "stream_stores must be 0 (auto), 1 (write-through) or 2 (non-temporal)");
@@ -244,9 +244,9 @@ int cfmm_set_option(cfmm_ctx* c, const char* key, int64_t value)
             int rc = cfmm_set_option(child, key, value);
             if (rc != CFMM_OK) return fail(c, rc, "%s", child->err.c_str());
         }
-    if (slot == &c->opt_max_grid || slot == &c->opt_block || slot == &c->opt_fuse_segments ||
-        slot == &c->opt_geomean_exact || slot == &c->opt_pack ||
-        slot == &c->opt_cost_geomean || slot == &c->opt_cost_univ3 || slot == &c->opt_direct_small)
+    if (slot == &c->geo.max_grid || slot == &c->geo.block || slot == &c->geo.fuse_segments ||
+        slot == &c->geo.geomean_exact || slot == &c->geo.pack ||
+        slot == &c->geo.cost_geomean || slot == &c->geo.cost_univ3 || slot == &c->geo.direct_small)
         c->geometry_dirty = true;
     return CFMM_OK;
 }

@@ -14,140 +14,6 @@ using namespace cfmm;
 
 namespace {
 
-// Grid cap for the fat (512/1024-thread) blocks: HALF a machine of resident threads -- one 1024-thread block
-// (16 wavefronts) per CU.  Round 1 ran a full machine (two blocks per CU); with consecutive sweeps walking the
-// tiles in alternating directions (option "alternate") fewer, longer lanes win: each lane owns 2x the tiles, so
-// more of a sweep starts on L2-resident data, and there are half as many partial rows and LDS prologues
-// (measured, sweep span us at 256 / 384 / 512 blocks: product1m 9.7 / 10.6 / 10.6, config5 19.1 / 22.6 / 21.7,
-// config-4 shard 7.1 / - / 8.1; 128 blocks: 14.9 / 24.5 / 9.2).
-int fat_grid_cap(const cfmm_ctx* c, int block)
-{
-    (void)c;
-    return kResidentThreads / 2 / block;
-}
-
-// Fused multi-family launches: 512 blocks of 512 threads in total measured best on config3
-// (19.9 us per step vs 21.9 at 1024 blocks and 21.4 at 256; bench.py --opt block=.. --opt max_grid=..).
-int fused_grid_cap(const cfmm_ctx* c, int block)
-{
-    return std::min(fat_grid_cap(c, block), kResidentThreads / 2 / block);
-}
-
-// Launch geometry for a segment of m pools.  Small markets: 512-thread blocks, one tile each.  Large markets:
-// 1024-thread blocks, at most one per CU, each striding over many tiles -- this keeps the number of partial rows
-// (and the fold kernel) small.  Large-market mode (global bins) uses 512-thread blocks throughout.
-void plan_segment(const cfmm_ctx* c, Segment& s)
-{
-    // N-coin segments (weighted, Curve): their own launch of 512-thread blocks (sweep_ncoin), never single-block direct
-    if (ragged_kind(s.kind)) {
-        const int64_t tiles = std::max<int64_t>(1, (s.m + kMidBlock - 1) / kMidBlock);
-        s.block = kMidBlock;
-        s.grid = (int)std::min<int64_t>(tiles, c->opt_max_grid > 0 ? c->opt_max_grid : fat_grid_cap(c, kMidBlock));
-        return;
-    }
-    // tiny single-family markets: ONE block, whose row is the result (SweepArgs::direct: no fold launch)
-    if (c->opt_direct_small != 0 && c->segs.size() == 1 && s.m <= kDirectPools && !global_bins(c) && c->opt_block == 0 &&
-        c->opt_max_grid == 0) {
-        s.block = kBigBlock;
-        s.grid = 1;
-        return;
-    }
-    const int64_t tiles_mid = std::max<int64_t>(1, (s.m + kMidBlock - 1) / kMidBlock);
-    const bool small = global_bins(c) || c->opt_block == kMidBlock || (c->opt_block == 0 && tiles_mid <= 256);
-    if (small) {
-        s.block = kMidBlock;
-        const int64_t cap = c->opt_max_grid > 0 ? c->opt_max_grid : (tiles_mid <= 256 ? 256 : fat_grid_cap(c, kMidBlock));
-        s.grid = (int)std::min<int64_t>(tiles_mid, cap);
-    } else {
-        s.block = kBigBlock;
-        const int64_t tiles = std::max<int64_t>(1, (s.m + kBigBlock - 1) / kBigBlock);
-        s.grid = (int)std::min<int64_t>(tiles, c->opt_max_grid > 0 ? c->opt_max_grid : fat_grid_cap(c, s.block));
-    }
-}
-
-// Relative cost of one pool evaluation per family, in tenths of a ProductTwoCoin evaluation (options
-// "cost_geomean" / "cost_univ3"; measured on config3 / mixed markets, see DESIGN).  Used only to divide
-// the blocks of a fused launch among its segments so that they finish together.
-int64_t family_cost(const cfmm_ctx* c, const Segment& s)
-{
-    switch (s.kind) {
-    case CFMM_KIND_PRODUCT: return 10;
-    case CFMM_KIND_GEOMEAN: return c->opt_cost_geomean;
-    default: return c->opt_cost_univ3 + (s.m > 0 && s.n_ticks_total / s.m > 2 ? 6 : 0);   // multi-tick ladders: a threshold scan + one more record
-    }
-}
-
-// XCD-aware, cost-weighted map of a fused launch (grid a multiple of 256 blocks): 32-deal pattern in
-// which segment s appears seg_w[s] times, spread evenly (largest-remainder weights, Bresenham order).
-void plan_xcd_map(cfmm_ctx* c, Group& g)
-{
-    g.xcd_map = false;
-    if (!g.multi || g.grid % 256 != 0 || global_bins(c)) return;
-    double cost[kMaxMulti], total = 0.0;
-    for (int k = 0; k < g.nseg; ++k) {
-        const Segment& s = c->segs[(size_t)g.first + k];
-        cost[k] = (double)s.m * (double)family_cost(c, s);
-        total += cost[k];
-    }
-    if (!(total > 0.0)) return;
-    int w[kMaxMulti], sum = 0;
-    double frac[kMaxMulti];
-    for (int k = 0; k < g.nseg; ++k) {
-        const double share = 32.0 * cost[k] / total;
-        w[k] = std::max(1, (int)share);
-        frac[k] = share - (int)share;
-        sum += w[k];
-    }
-    while (sum < 32) {   // hand the remaining deals to the largest remainders
-        int best = 0;
-        for (int k = 1; k < g.nseg; ++k) if (frac[k] > frac[best]) best = k;
-        ++w[best]; frac[best] = -1.0; ++sum;
-    }
-    while (sum > 32) {   // (only when several tiny segments were rounded up to one deal each)
-        int big = 0;
-        for (int k = 1; k < g.nseg; ++k) if (w[k] > w[big]) big = k;
-        --w[big]; --sum;
-    }
-    // Bresenham spread: at every position pick the segment that is furthest behind its share
-    int given[kMaxMulti] = {0};
-    for (int p = 0; p < 32; ++p) {
-        int best = -1;
-        double lag_best = -1e30;
-        for (int k = 0; k < g.nseg; ++k) {
-            if (given[k] >= w[k]) continue;
-            const double lag = (double)(p + 1) * w[k] / 32.0 - given[k];
-            if (lag > lag_best) { lag_best = lag; best = k; }
-        }
-        g.pattern[p] = (unsigned char)best;
-        g.rank[p] = (unsigned char)given[best];
-        ++given[best];
-    }
-    for (int k = 0; k < g.nseg; ++k) {
-        g.seg_w[k] = w[k];
-        c->segs[(size_t)g.first + k].grid = (g.grid / 256) * w[k] * 8;
-    }
-    g.xcd_map = true;
-}
-
-// Prices are staged in LDS as {v, rcp_refined(v)} pairs unless the market is too wide for them (sweep.h SweepArgs::v_shift)
-bool stage_pairs(const cfmm_ctx* c, int block)
-{
-    return !global_bins(c) && sweep_lds_bytes(c->n_pad, 1, block, 1, kMaxFeeTable, 1) <= 160 * 1024;
-}
-
-int bin_copies(const cfmm_ctx* c, int block)
-{
-    if (global_bins(c)) return 1;
-    const int waves = block / 64;
-    if (c->opt_bin_copies == 1) return 1;
-    // incl. the log-price row and the fee table a launch may stage
-    const size_t per_wave = sweep_lds_bytes(c->n_pad, waves, block, 1, kMaxFeeTable, stage_pairs(c, block) ? 1 : 0);
-    if (c->opt_bin_copies == 2) return per_wave <= 160 * 1024 ? waves : 1;
-    // auto: one private copy per wavefront while the launch geometry's blocks still fit a CU's 160 KiB of LDS together
-    // (1024-thread blocks: one per CU; 512-thread blocks: two)
-    return per_wave <= (block == kBigBlock ? 128 : 64) * 1024 ? waves : 1;
-}
-
 // Large-market mode: token -> (pool, side) incidence in CSR form, cut into chunks of at most
 // kGatherChunk entries (hub tokens are spread over many wavefronts), plus the flow scratch.
 int build_incidence(cfmm_ctx* c)
@@ -194,152 +60,70 @@ hipEvent_t take_event(cfmm_ctx* c)
     return c->ev_pool[c->ev_used++];
 }
 
+// a start / stop pair for one timed launch (both null when none could be had)
+void take_events(cfmm_ctx* c, hipEvent_t& a, hipEvent_t& b)
+{
+    a = take_event(c);
+    b = take_event(c);
+    if (!a || !b) a = b = nullptr;
+}
+
 } // namespace
 
 namespace cfmm {
 
+// The launch plan of the current segments (launch_plan.h), then what needs the device: the launches' fee tables and the buffers.
 int ensure_geometry(cfmm_ctx* c)
 {
     if (!c->geometry_dirty) return CFMM_OK;
-    int64_t rows = 0, trades = 0, pools = 0, flat = 0;
-    size_t n_two_coin = 0;
-    bool any_big = false;
-    c->any_ragged = false;
-    for (auto& s : c->segs) {
-        plan_segment(c, s);
-        const bool wt = ragged_kind(s.kind);
-        const bool own = own_launch_kind(s.kind);   // (Solidly: two-coin trade rows, but never in a fused launch)
-        s.trade_off = trades;           // (weighted / Curve segments have no rows in the two-coin trade buffers)
-        s.flat_off = flat;
-        if (!wt) trades += s.m;
-        pools += s.m;
-        flat += s.m * (wt ? s.n_coins : 2);
-        if (!own) ++n_two_coin;
-        c->any_ragged = c->any_ragged || wt;
-        any_big = any_big || (!own && s.block == kBigBlock);
-    }
-    c->groups.clear();
-    const bool fusable = c->opt_fuse_segments != 0 && n_two_coin >= 2 && c->opt_geomean_exact == 0;
-    // launch groups: every N-coin and every Solidly segment alone (own_launch_kind); runs of consecutive segments of the
-    // other two-coin families fused by up to kMaxMulti (sweep_multi) or one launch each
-    for (size_t run = 0; run < c->segs.size();) {
-        if (own_launch_kind(c->segs[run].kind)) {
-            Segment& sg = c->segs[run];
-            Group g;
-            g.first = (int)run;
-            g.block = sg.block;
-            g.grid = sg.grid;
-            g.row_off = rows;
-            sg.row_off = rows;
-            rows += sg.grid;
-            c->groups.push_back(g);
-            ++run;
-            continue;
-        }
-        size_t run_end = run;
-        while (run_end < c->segs.size() && !own_launch_kind(c->segs[run_end].kind)) ++run_end;
-        if (fusable) {
-            // fused launches use 512-thread blocks (Product / GeoMean blocks interleave on every CU) unless asked otherwise
-            const int block = (any_big && c->opt_block == kBigBlock) ? kBigBlock : kMidBlock;
-            (void)any_big;
-            for (size_t first = run; first < run_end; first += kMaxMulti) {
-                Group g;
-                g.first = (int)first;
-                g.nseg = (int)std::min<size_t>(kMaxMulti, run_end - first);
-                g.multi = g.nseg >= 2;
-                g.block = block;
-                int64_t tiles = 1;
-                for (int k = 0; k < g.nseg; ++k) {
-                    Segment& sg = c->segs[first + k];
-                    sg.block = block;
-                    tiles = std::max<int64_t>(tiles, (sg.m + block - 1) / block);
-                }
-                const int64_t cap = std::max<int64_t>(
-                    1, (c->opt_max_grid > 0 ? c->opt_max_grid : fused_grid_cap(c, block)) / g.nseg);
-                const int per_seg = (int)std::min<int64_t>(tiles, cap);
-                for (int k = 0; k < g.nseg; ++k) c->segs[first + k].grid = per_seg;
-                g.grid = per_seg * g.nseg;
-                plan_xcd_map(c, g);   // may re-divide the same number of blocks among the segments by cost
-                g.row_off = rows;
-                c->segs[first].row_off = rows;
-                rows += g.grid;
-                c->groups.push_back(g);
-            }
-        } else {
-            for (size_t i = run; i < run_end; ++i) {
-                Segment& sg = c->segs[i];
-                Group g;
-                g.first = (int)i;
-                g.block = sg.block;
-                g.grid = sg.grid;
-                g.row_off = rows;
-                sg.row_off = rows;
-                rows += sg.grid;
-                c->groups.push_back(g);
-            }
-        }
-        run = run_end;
-    }
-    // fee tables of the launches: the packed records of a launch's segments index ONE table staged in LDS
-    {
-        std::vector<double> tabs(c->groups.size() * (size_t)kMaxFeeTable, 1.0);
-        for (size_t gi = 0; gi < c->groups.size(); ++gi) {
-            Group& g = c->groups[gi];
-            int total = 0;
-            bool ok = c->opt_pack != 0 && !global_bins(c);
-            for (int k = 0; k < g.nseg && ok; ++k) {
-                const Segment& sg = c->segs[(size_t)g.first + k];
-                if (!sg.pk || sg.gvals.empty()) ok = false;   // (empty: the segment has more fee tiers than a table holds)
-                total += (int)sg.gvals.size();
-            }
-            g.gtab_n = ok && total <= kMaxFeeTable ? total : 0;
-            if (g.gtab_n == 0) continue;
-            int base = 0;
-            for (int k = 0; k < g.nseg; ++k) {
-                Segment& sg = c->segs[(size_t)g.first + k];
-                sg.gbase = base;
-                std::copy(sg.gvals.begin(), sg.gvals.end(), tabs.begin() + (std::ptrdiff_t)(gi * kMaxFeeTable + (size_t)base));
-                base += (int)sg.gvals.size();
-            }
-        }
-        if (tabs.size() > c->gtab_cap) {
-            (void)hipFree(c->d_gtab);
-            c->d_gtab = nullptr;
-            c->gtab_cap = 0;
-            HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_gtab), tabs.size() * sizeof(double)));
-            c->gtab_cap = tabs.size();
-        }
-        if (!tabs.empty()) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, hipMemcpy(c->d_gtab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<PlanSeg> shapes;
+    for (const Segment& s : c->segs)
+        shapes.push_back({s.kind, s.m, s.n_coins, s.n_ticks_total, s.has_walk, s.pk != nullptr, (int)s.gvals.size()});
+    LaunchPlan plan = plan_launches(shapes, c->n, c->geo);
+    for (size_t i = 0; i < c->segs.size(); ++i) static_cast<SegPlan&>(c->segs[i]) = plan.segs[i];
+    c->groups = std::move(plan.groups);
+    c->any_ragged = plan.any_ragged;
+    c->rows_total = plan.rows;
+    c->m_total = plan.pools;
+    c->trade_rows = plan.trades;
+    c->flat_total = plan.flat;
+    c->touched_bytes = plan.touched_bytes;
+    // fee tables of the launches, one kMaxFeeTable slot each
+    std::vector<double> tabs(c->groups.size() * (size_t)kMaxFeeTable, 1.0);
+    for (size_t gi = 0; gi < c->groups.size(); ++gi) {
+        const Group& g = c->groups[gi];
+        for (int k = 0; k < g.nseg && g.gtab_n != 0; ++k) {
+            const Segment& sg = c->segs[(size_t)g.first + k];
+            std::copy(sg.gvals.begin(), sg.gvals.end(), tabs.begin() + (std::ptrdiff_t)(gi * kMaxFeeTable + (size_t)sg.gbase));
         }
     }
-    c->rows_total = rows;
-    c->m_total = pools;
-    c->trade_rows = trades;
-    c->flat_total = flat;
-    c->touched_bytes = 0;
-    for (const auto& s : c->segs)   // bytes read per pool in the packed layout + one 16-byte trade record (a lower bound for multi-tick UniV3)
-        c->touched_bytes += s.m * (ragged_kind(s.kind) ? ncoin_family(s.kind).bytes_per_pool(s.n_coins)
-                                   : (int64_t)(s.kind == CFMM_KIND_PRODUCT || s.kind == CFMM_KIND_SOLIDLY ? 24 + 16
-                                               : s.kind == CFMM_KIND_GEOMEAN ? 48 + 16
-                                               : (s.has_walk ? 104 : 56) + 16));
-    if (rows > c->rows_cap) {
+    if (tabs.size() > c->gtab_cap) {
+        (void)hipFree(c->d_gtab);
+        c->d_gtab = nullptr;
+        c->gtab_cap = 0;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_gtab), tabs.size() * sizeof(double)));
+        c->gtab_cap = tabs.size();
+    }
+    if (!tabs.empty()) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpy(c->d_gtab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+    }
+    if (plan.rows > c->rows_cap) {
         (void)hipFree(c->d_partials);
         c->d_partials = nullptr;
         c->rows_cap = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_partials), (size_t)rows * row_width(c) * sizeof(double)));
-        HIP_TRY(c, hipMemset(c->d_partials, 0, (size_t)rows * row_width(c) * sizeof(double)));
-        c->rows_cap = rows;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_partials), (size_t)plan.rows * row_width(c) * sizeof(double)));
+        HIP_TRY(c, hipMemset(c->d_partials, 0, (size_t)plan.rows * row_width(c) * sizeof(double)));
+        c->rows_cap = plan.rows;
     }
-    if (trades > c->trade_cap) {   // (two-coin rows only)
+    if (plan.trades > c->trade_cap) {   // (two-coin rows only)
         (void)hipFree(c->d_delta); (void)hipFree(c->d_lambda); (void)hipFree(c->d_over);
         c->d_delta = c->d_lambda = c->d_over = nullptr;
         c->trade_cap = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_delta), (size_t)trades * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_lambda), (size_t)trades * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_over), (size_t)trades * sizeof(double2)));
-        c->trade_cap = trades;
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_delta), (size_t)plan.trades * sizeof(double2)));
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_lambda), (size_t)plan.trades * sizeof(double2)));
+        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_over), (size_t)plan.trades * sizeof(double2)));
+        c->trade_cap = plan.trades;
     }
     if (global_bins(c)) {
         int rc = build_incidence(c);
@@ -351,6 +135,197 @@ int ensure_geometry(cfmm_ctx* c)
     c->have_out = false;
     return CFMM_OK;
 }
+namespace {
+
+// What the launches of one evaluation share (enqueue_sweep)
+struct Eval {
+    const double* d_v;
+    double* d_out;
+    bool materialize;
+    int price_window;
+    // large-market mode; fold + all-reduce over the peer mappings in one launch; the sweep's only block publishes {Ψ, acc}
+    // itself (no fold); harvest with cfmm_kernel_times
+    bool gb, sharded, direct, timed;
+    ArmWord arm;
+    HostOut ho;
+};
+
+// the option "geomean_exact" form of a kind: neither log v from LDS nor a fast arithmetic
+bool exact_form(const cfmm_ctx* c, int kind) { return kind_info(kind).exact_form && c->geo.geomean_exact != 0; }
+
+// The SweepArgs every segment of launch g (the gi-th) shares
+SweepArgs group_args(const cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
+{
+    SweepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.v = ev.d_v;
+    a.n = c->n;
+    a.n_pad = c->n_pad;
+    a.v_shift = stage_pairs(c->n, g.block) ? 4 : 3;
+    a.gtab = c->d_gtab ? c->d_gtab + gi * kMaxFeeTable : nullptr;
+    a.gtab_n = a.gtab ? g.gtab_n : 0;
+    for (int k = 0; k < g.nseg && !ev.gb; ++k) {
+        const int kind = c->segs[(size_t)g.first + k].kind;
+        if (kind_info(kind).logv && !exact_form(c, kind)) a.need_logv = 1;
+    }
+    if (a.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, a.gtab_n, a.v_shift == 4 ? 1 : 0) > 160 * 1024)
+        a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
+    a.copies = bin_copies(c->n, c->geo, g.block);
+    a.compact = (c->opt_compact_trades != 0 && !ev.gb) ? 1 : 0;
+    a.partials = c->d_partials + (size_t)g.row_off * row_width(c);
+    a.row_pitch = row_width(c);
+    a.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
+    a.arm_word = ev.arm.word;
+    a.arm_seq = ev.arm.seq;
+    a.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
+    // sharded (cfmm_set_peers): a rank whose host is late by less than the peer timeout must not lose the evaluation --
+    // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
+    // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
+    if (ev.sharded) a.arm_timeout = std::max<long long>(a.arm_timeout, c->peer_timeout_ticks);
+    a.flags = c->d_stage ? reinterpret_cast<unsigned long long*>(c->d_stage + c->flag_off) : nullptr;
+    a.nt_stores = c->opt_stream_stores == 2 || (c->opt_stream_stores == 0 && c->touched_bytes > (int64_t)256 << 20) ? 1 : 0;
+    if (ev.direct) {
+        a.direct = 1;
+        a.direct_out = ev.d_out;
+        a.direct_host = ev.ho;
+        a.reverse = 0;   // two tiles at most, the whole market in one CU's L1: nothing for the alternation to reuse -- and every
+                         // evaluation of such a market, fused or materialising, then returns the same bits at the same prices
+    }
+    return a;
+}
+
+// The kernel's arithmetic (LaunchCfg::arith).  Fast: every pool constant of the launch inside the window (checked at upload),
+// prices staged as {v, rcp(v)} pairs, and the prices themselves inside it as far as the host knows ...
+int arith_of(const cfmm_ctx* c, const Eval& ev, const Group& g, const SweepArgs& a)
+{
+    bool fast = c->opt_fast_math != 0 && !ev.gb && a.v_shift == 4 && ev.price_window != kPricesOutside;
+    for (int k = 0; k < g.nseg && fast; ++k) {
+        const Segment& s = c->segs[(size_t)g.first + k];
+        fast = s.fast_ok != 0 && kind_info(s.kind).has_fast && !exact_form(c, s.kind);
+    }
+    // ... which the host knows for host-pointer sweeps and cfmm_route (pre-armed launches: armed_eval checks the prices before
+    // it signals and cancels a launch whose prices turn out to be outside); a device-pointer sweep (prices unknown) gets the
+    // kernel that carries both loops and decides per block from the prices it stages
+    return !fast ? 0 : (ev.price_window == kPricesUnknown && ev.arm.seq == 0 && c->opt_dev_prices_in_window == 0) ? 2 : 1;
+}
+
+// The per-segment part of a launch's arguments: SweepArgs (a segment's own launch) and MultiSeg (fused) carry the same fields
+template <class SegArgs>
+void fill_segment(const cfmm_ctx* c, const Eval& ev, const Segment& s, SegArgs& t)
+{
+    t.m = s.m;
+    t.Delta = ev.materialize ? c->d_delta + s.trade_off : nullptr;
+    t.Lambda = ev.materialize ? c->d_lambda + s.trade_off : nullptr;
+    t.Over = ev.materialize ? c->d_over + s.trade_off : nullptr;
+    t.gflow = ev.gb ? c->d_flow + s.trade_off : nullptr;
+}
+
+AnyPools pools_of(const cfmm_ctx* c, const Eval& ev, const Segment& s, int gtab_n)
+{
+    const int gbase = gtab_n ? s.gbase : -1;   // -1: fees from the gamma array
+    AnyPools p;
+    switch (s.kind) {
+    case CFMM_KIND_PRODUCT:
+    case CFMM_KIND_SOLIDLY: p.p = ProductPools{s.R, s.gamma, s.Ai, s.pk, gbase}; break;
+    case CFMM_KIND_GEOMEAN: p.g = GeoMeanPools{s.R, s.w, s.gamma, s.Ai, s.eta, s.lR, (int)c->geo.geomean_exact, s.pk, gbase}; break;
+    case CFMM_KIND_UNIV3:
+        p.u = UniV3Pools{s.pg, s.Ai, s.cur_a, s.cur_b, s.cur_c, s.curR, s.walk, s.ticks, s.thr,
+                         c->opt_univ3_heads != 0 ? s.head : nullptr, s.has_walk, s.cp, s.pk, gbase};
+        break;
+    default:
+        p.n = NCoinPools{s.nc.R, s.nc.q, s.nc.tok, s.nc.glg, s.nc.par, s.n_coins, ev.materialize ? s.nc.D : nullptr,
+                         ev.materialize ? s.nc.L : nullptr};
+        break;
+    }
+    return p;
+}
+
+// One sweep launch: launch group g, the gi-th of the evaluation
+int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
+{
+    SweepArgs a = group_args(c, ev, g, gi);
+    const size_t lds = ev.gb ? (size_t)(g.block / 64) * sizeof(double)
+                             : sweep_lds_bytes(c->n_pad, a.copies, g.block, a.need_logv, a.gtab_n, a.v_shift == 4 ? 1 : 0);
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (ev.timed) take_events(c, ea, eb);   // start/stop written by the command processor around this launch (hipExtLaunchKernel)
+    const LaunchCfg cfg{g.block, g.grid, lds, arith_of(c, ev, g, a), ea, eb};
+    const Segment* segs = &c->segs[(size_t)g.first];
+    hipError_t e;
+    if (g.multi) {
+        MultiArgs ma;
+        std::memset(&ma, 0, sizeof ma);
+        ma.nseg = g.nseg;
+        ma.xcd_map = g.xcd_map ? 1 : 0;
+        std::memcpy(ma.pattern, g.pattern, sizeof ma.pattern);
+        std::memcpy(ma.rank, g.rank, sizeof ma.rank);
+        std::memcpy(ma.seg_w, g.seg_w, sizeof ma.seg_w);
+        ma.common = a;
+        ma.common.gflow = ev.gb ? c->d_flow : nullptr; // mode flag for the launcher; per-segment bases below
+        for (int k = 0; k < g.nseg; ++k) {
+            ma.seg[k].kind = segs[k].kind;
+            ma.seg[k].pools = pools_of(c, ev, segs[k], a.gtab_n);
+            fill_segment(c, ev, segs[k], ma.seg[k]);
+        }
+        e = launch_multi(ma, cfg, ev.materialize, c->stream);
+    } else {
+        fill_segment(c, ev, segs[0], a);
+        e = launch_sweep(segs[0].kind, pools_of(c, ev, segs[0], a.gtab_n), a, cfg, ev.materialize, c->stream);
+    }
+    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
+    if (ea && eb) c->pending.push_back({ea, eb, 0});
+    return CFMM_OK;
+}
+
+// The row fold behind the sweeps: {Ψ, acc} to ev.d_out (and, ev.ho set, to the host as granules)
+int launch_fold(cfmm_ctx* c, const Eval& ev)
+{
+    hipEvent_t ra = nullptr, rb = nullptr;
+    const bool bracket = ev.gb || (c->rows_total == 0 && !ev.sharded);   // several launches / a memset: bracket them with plain events
+    if (ev.timed && !ev.direct) take_events(c, ra, rb);
+    if (ra && bracket) HIP_TRY(c, hipEventRecord(ra, c->stream));
+    hipEvent_t ka = bracket ? nullptr : ra, kb = bracket ? nullptr : rb;   // else: written by the command processor around the fold
+    const int rows = (int)c->rows_total, n1 = c->n + 1;
+    if (ev.direct) {
+        // (the sweep's only block has published {Ψ, acc} itself)
+    } else if (ev.sharded) {
+        PeerSet ps;
+        std::memset(&ps, 0, sizeof ps);
+        for (size_t p = 0; p < c->peers.size(); ++p)
+            ps.gran[p] = reinterpret_cast<unsigned long long*>(c->peers[p]);
+        ps.world = (int)c->peers.size();
+        ps.rank = c->peer_rank;
+        ps.count = n1;
+        ps.seq = ++c->peer_seq;
+        ps.timeout_ticks = c->peer_timeout_ticks;
+        ps.host = ev.ho;
+        ps.arm = ev.arm;
+        // a world of ONE rank has nobody to exchange with: the plain fold (same columns, same order; measured 0.6 us per step
+        // less than the gather launch with its 200-byte peer table -- N = 1 under a launcher then costs what plain N = 1 costs)
+        hipError_t e = (ps.world == 1 && rows > 0 && !ev.gb)
+            ? launch_reduce(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm)
+            : launch_reduce_gather(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ps, ka, kb);
+        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "fold + gather launch failed: %s", hipGetErrorString(e));
+    } else if (rows > 0) {
+        hipError_t e;
+        if (ev.gb) { // pull Ψ per token over the incidence list, then fold the dual-scalar column
+            e = launch_gather(c->d_chunks, c->d_entries, reinterpret_cast<const double*>(c->d_flow), c->d_chunk_sums,
+                              c->n_chunks, c->d_tok_chunk_off, ev.d_out, c->n, c->d_partials, rows, c->stream);
+        } else {
+            e = launch_reduce(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm);
+        }
+        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "reduce launch failed: %s", hipGetErrorString(e));
+    } else {
+        HIP_TRY(c, hipMemsetAsync(ev.d_out, 0, (size_t)n1 * sizeof(double), c->stream));
+    }
+    if (ra && rb) {
+        if (bracket) HIP_TRY(c, hipEventRecord(rb, c->stream));
+        c->pending.push_back({ra, rb, 1});
+    }
+    return CFMM_OK;
+}
+
+} // namespace
+
 // Enqueue one full evaluation on c->stream: every segment's sweep, then the row fold.
 //   want_host_out: the fold delivers {Ψ, acc} to the pinned staging buffer as self-validating granules (the caller
 //                  polls them: host_sweep_end / armed_wait) instead of writing d_out;
@@ -363,195 +338,32 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
 {
     int rc = ensure_geometry(c);
     if (rc != CFMM_OK) return rc;
-    const bool timed = c->opt_time_kernels != 0 && c->pending.size() < (1u << 20); // harvest with cfmm_kernel_times
-    const bool gb = global_bins(c);
-    const bool sharded = !c->peers.empty();   // fold + all-reduce over the peer mappings in one launch
-    const unsigned long long* arm_word = arm_seq ? reinterpret_cast<const unsigned long long*>(c->d_arm + c->n_pad) : nullptr;
+    Eval ev{d_v, d_out, materialize, price_window};
+    ev.gb = global_bins(c);
+    ev.sharded = !c->peers.empty();
+    ev.timed = c->opt_time_kernels != 0 && c->pending.size() < (1u << 20);
+    ev.arm = ArmWord{arm_seq ? reinterpret_cast<const unsigned long long*>(c->d_arm + c->n_pad) : nullptr, arm_seq};
     const bool rccl = c->rccl_comm != nullptr;   // the fold's {Ψ, acc} are this rank's part: all-reduced in-stream behind it
-    const bool host_out = want_host_out && !gb && !rccl && (sharded || c->rows_total > 0) && c->d_stage != nullptr;
-    HostOut ho{nullptr, 0};
+    const bool host_out = want_host_out && !ev.gb && !rccl && (ev.sharded || c->rows_total > 0) && c->d_stage != nullptr;
     if (host_out) {
         ++c->out_seq;
-        ho.gran = reinterpret_cast<unsigned long long*>(c->d_stage + c->gran_off);
-        ho.tag = c->out_seq % 0xffffffffull + 1ull;
+        ev.ho.gran = reinterpret_cast<unsigned long long*>(c->d_stage + c->gran_off);
+        ev.ho.tag = c->out_seq % 0xffffffffull + 1ull;
     }
     HIP_TRY(c, hipSetDevice(c->device));
     // a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
     // exchanges, and RCCL all-reduces d_out behind the fold)
-    const bool direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !gb && !sharded &&
-                        !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
-    size_t group_index = 0;
-    for (const Group& g : c->groups) {
-        const size_t gi = group_index++;
-        SweepArgs a;
-        std::memset(&a, 0, sizeof a);
-        a.v = d_v;
-        a.n = c->n;
-        a.n_pad = c->n_pad;
-        a.v_shift = stage_pairs(c, g.block) ? 4 : 3;
-        a.gtab = c->d_gtab ? c->d_gtab + gi * kMaxFeeTable : nullptr;
-        a.gtab_n = a.gtab ? g.gtab_n : 0;
-        a.need_logv = 0;
-        if (!gb)
-            for (int k = 0; k < g.nseg; ++k) {
-                const int kind = c->segs[(size_t)g.first + k].kind;
-                if ((kind == CFMM_KIND_GEOMEAN && c->opt_geomean_exact == 0) || (ragged_kind(kind) && ncoin_family(kind).need_logv))
-                    a.need_logv = 1;
-            }
-        if (a.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, a.gtab_n, a.v_shift == 4 ? 1 : 0) > 160 * 1024)
-            a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
-        a.copies = bin_copies(c, g.block);
-        a.compact = (c->opt_compact_trades != 0 && !gb) ? 1 : 0;
-        a.partials = c->d_partials + (size_t)g.row_off * row_width(c);
-        a.row_pitch = row_width(c);
-        a.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
-        a.arm_word = arm_word;
-        a.arm_seq = arm_seq;
-        a.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
-        // sharded (cfmm_set_peers): a rank whose host is late by less than the peer timeout must not lose the evaluation --
-        // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
-        // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
-        if (sharded) a.arm_timeout = std::max<long long>(a.arm_timeout, c->peer_timeout_ticks);
-        a.flags = c->d_stage ? reinterpret_cast<unsigned long long*>(c->d_stage + c->flag_off) : nullptr;
-        a.nt_stores = c->opt_stream_stores == 2 || (c->opt_stream_stores == 0 && c->touched_bytes > (int64_t)256 << 20) ? 1 : 0;
-        if (direct) {
-            a.direct = 1;
-            a.direct_out = d_out;
-            a.direct_host = ho;
-            a.reverse = 0;   // two tiles at most, the whole market in one CU's L1: nothing for the alternation to reuse -- and every
-                             // evaluation of such a market, fused or materialising, then returns the same bits at the same prices
-        }
-        const size_t lds = gb ? (size_t)(g.block / 64) * sizeof(double)
-                              : sweep_lds_bytes(c->n_pad, a.copies, g.block, a.need_logv, a.gtab_n, a.v_shift == 4 ? 1 : 0);
-        hipEvent_t ea = nullptr, eb = nullptr;
-        if (timed) { // start/stop written by the command processor around this launch (hipExtLaunchKernel)
-            ea = take_event(c);
-            eb = take_event(c);
-            if (!ea || !eb) ea = eb = nullptr;
-        }
-        // the kernel on the fast arithmetic: every pool constant of the launch inside the window (checked at upload), prices
-        // staged as {v, rcp(v)} pairs, and the prices themselves inside it as far as the host knows
-        bool fast = c->opt_fast_math != 0 && !gb && a.v_shift == 4 && price_window != kPricesOutside;
-        for (int k = 0; k < g.nseg && fast; ++k) {
-            const Segment& s = c->segs[(size_t)g.first + k];
-            fast = s.fast_ok != 0 && !(s.kind == CFMM_KIND_GEOMEAN && c->opt_geomean_exact != 0);
-        }
-        // ... which the host knows for host-pointer sweeps and cfmm_route (pre-armed launches: armed_eval checks the prices before
-        // it signals and cancels a launch whose prices turn out to be outside); a device-pointer sweep (prices unknown) gets the
-        // kernel that carries both loops and decides per block from the prices it stages
-        const int arith = !fast ? 0 : (price_window == kPricesUnknown && arm_seq == 0 && c->opt_dev_prices_in_window == 0) ? 2 : 1;
-        const auto gbase_of = [&](const Segment& s) { return a.gtab_n ? s.gbase : -1; };   // -1: fees from the gamma array
-        auto product_of = [&](const Segment& s) { return ProductPools{s.R, s.gamma, s.Ai, s.pk, gbase_of(s)}; };
-        auto geomean_of = [&](const Segment& s) {
-            return GeoMeanPools{s.R, s.w, s.gamma, s.Ai, s.eta, s.lR, (int)c->opt_geomean_exact, s.pk, gbase_of(s)};
-        };
-        auto univ3_of = [&](const Segment& s) {
-            return UniV3Pools{s.pg, s.Ai, s.cur_a, s.cur_b, s.cur_c, s.curR, s.walk, s.ticks, s.thr,
-                              c->opt_univ3_heads != 0 ? s.head : nullptr, s.has_walk, s.cp, s.pk, gbase_of(s)};
-        };
-        auto ncoin_of = [&](const Segment& s) {
-            return NCoinPools{s.nc.R, s.nc.q, s.nc.tok, s.nc.glg, s.nc.par, s.n_coins, materialize ? s.nc.D : nullptr,
-                              materialize ? s.nc.L : nullptr};
-        };
-        hipError_t e = hipSuccess;
-        if (g.multi) {
-            MultiArgs ma;
-            std::memset(&ma, 0, sizeof ma);
-            ma.nseg = g.nseg;
-            ma.xcd_map = g.xcd_map ? 1 : 0;
-            std::memcpy(ma.pattern, g.pattern, sizeof ma.pattern);
-            std::memcpy(ma.rank, g.rank, sizeof ma.rank);
-            for (int k = 0; k < kMaxMulti; ++k) ma.seg_w[k] = g.seg_w[k];
-            ma.common = a;
-            ma.common.gflow = gb ? c->d_flow : nullptr; // mode flag for the launcher; per-segment bases below
-            for (int k = 0; k < g.nseg; ++k) {
-                const Segment& s = c->segs[(size_t)g.first + k];
-                MultiSeg& ms = ma.seg[k];
-                ms.kind = s.kind;
-                ms.m = s.m;
-                ms.Delta = materialize ? c->d_delta + s.trade_off : nullptr;
-                ms.Lambda = materialize ? c->d_lambda + s.trade_off : nullptr;
-                ms.Over = materialize ? c->d_over + s.trade_off : nullptr;
-                ms.gflow = gb ? c->d_flow + s.trade_off : nullptr;
-                switch (s.kind) {
-                case CFMM_KIND_PRODUCT: ms.pools.p = product_of(s); break;
-                case CFMM_KIND_GEOMEAN: ms.pools.g = geomean_of(s); break;
-                default: ms.pools.u = univ3_of(s); break;
-                }
-            }
-            LaunchCfg cfg{g.block, g.grid, lds, arith, ea, eb};
-            e = launch_multi(ma, cfg, materialize, c->stream);
-        } else {
-            const Segment& s = c->segs[(size_t)g.first];
-            a.m = s.m;
-            a.Delta = materialize ? c->d_delta + s.trade_off : nullptr;
-            a.Lambda = materialize ? c->d_lambda + s.trade_off : nullptr;
-            a.Over = materialize ? c->d_over + s.trade_off : nullptr;
-            a.gflow = gb ? c->d_flow + s.trade_off : nullptr;
-            LaunchCfg cfg{g.block, g.grid, lds, arith, ea, eb};
-            if (ragged_kind(s.kind)) e = launch_sweep_ncoin(s.kind, ncoin_of(s), a, cfg, materialize, c->stream);
-            else if (s.kind == CFMM_KIND_PRODUCT) e = launch_sweep(product_of(s), a, cfg, materialize, c->stream);
-            else if (s.kind == CFMM_KIND_GEOMEAN) e = launch_sweep(geomean_of(s), a, cfg, materialize, c->stream);
-            else if (s.kind == CFMM_KIND_SOLIDLY) e = launch_sweep_solidly(product_of(s), a, cfg, materialize, c->stream);
-            else e = launch_sweep(univ3_of(s), a, cfg, materialize, c->stream);
-        }
-        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
-        if (ea && eb) c->pending.push_back({ea, eb, 0});
-    }
+    ev.direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !ev.gb && !ev.sharded &&
+                !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
+    for (size_t gi = 0; gi < c->groups.size(); ++gi)
+        if ((rc = launch_group(c, ev, c->groups[gi], gi)) != CFMM_OK) return rc;
     c->last_host_out = host_out;
-    hipEvent_t ra = nullptr, rb = nullptr;
-    const bool bracket = gb || (c->rows_total == 0 && !sharded);   // several launches / a memset: bracket them with plain events
-    if (timed && !direct) {
-        ra = take_event(c);
-        rb = take_event(c);
-        if (!ra || !rb) ra = rb = nullptr;
-        if (ra && bracket) HIP_TRY(c, hipEventRecord(ra, c->stream));
-    }
-    if (direct) {
-        // (the sweep's only block has published {Ψ, acc} itself)
-    } else if (sharded) {
-        PeerSet ps;
-        std::memset(&ps, 0, sizeof ps);
-        const int64_t count = c->n + 1;
-        for (size_t p = 0; p < c->peers.size(); ++p)
-            ps.gran[p] = reinterpret_cast<unsigned long long*>(c->peers[p]);
-        ps.world = (int)c->peers.size();
-        ps.rank = c->peer_rank;
-        ps.count = count;
-        ps.seq = ++c->peer_seq;
-        ps.timeout_ticks = c->peer_timeout_ticks;
-        ps.host = ho;
-        ps.arm = ArmWord{arm_word, arm_seq};
-        // a world of ONE rank has nobody to exchange with: the plain fold (same columns, same order; measured 0.6 us per step
-        // less than the gather launch with its 200-byte peer table -- N = 1 under a launcher then costs what plain N = 1 costs)
-        hipError_t e = (ps.world == 1 && c->rows_total > 0 && !gb)
-            ? launch_reduce(c->d_partials, (int)c->rows_total, c->n + 1, row_width(c), d_out, c->stream, bracket ? nullptr : ra,
-                            bracket ? nullptr : rb, ho, ArmWord{arm_word, arm_seq})
-            : launch_reduce_gather(c->d_partials, (int)c->rows_total, c->n + 1, row_width(c), d_out, c->stream, ps,
-                                   bracket ? nullptr : ra, bracket ? nullptr : rb);
-        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "fold + gather launch failed: %s", hipGetErrorString(e));
-    } else if (c->rows_total > 0) {
-        hipError_t e;
-        if (gb) { // pull Ψ per token over the incidence list, then fold the dual-scalar column
-            e = launch_gather(c->d_chunks, c->d_entries, reinterpret_cast<const double*>(c->d_flow), c->d_chunk_sums,
-                              c->n_chunks, c->d_tok_chunk_off, d_out, c->n, c->d_partials, (int)c->rows_total, c->stream);
-        } else {
-            e = launch_reduce(c->d_partials, (int)c->rows_total, c->n + 1, row_width(c), d_out, c->stream, bracket ? nullptr : ra,
-                              bracket ? nullptr : rb, ho, ArmWord{arm_word, arm_seq});
-        }
-        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "reduce launch failed: %s", hipGetErrorString(e));
-    } else {
-        HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)(c->n + 1) * sizeof(double), c->stream));
-    }
-    if (ra && rb) {
-        if (bracket) HIP_TRY(c, hipEventRecord(rb, c->stream));
-        c->pending.push_back({ra, rb, 1});
-    }
+    if ((rc = launch_fold(c, ev)) != CFMM_OK) return rc;
     // the sweep and its fold ARE on the stream from here on: the context's bookkeeping says so whatever the collective does
     if (materialize) {
         c->have_trades = true;
         c->x_valid = false;
-        c->trades_compact = (c->opt_compact_trades != 0 && !gb) ? 1 : 0;
+        c->trades_compact = (c->opt_compact_trades != 0 && !ev.gb) ? 1 : 0;
     }
     ++c->sweep_count;
     if (rccl) {   // north_star: "RCCL all-reduce of Ψ and ∇g over xGMI per outer iteration" -- n + 1 doubles, on the same stream

@@ -162,7 +162,7 @@ template <class CoinOk, class PoolOk>
 int ncoin_check(cfmm_ctx* c, int kind, int64_t m, int32_t n_coins, const double* R, const double* gamma, const int32_t* Ai,
                 bool arrays, CoinOk coin_ok, PoolOk pool_ok)
 {
-    const char* fam = ncoin_family(kind).name;
+    const char* fam = kind_info(kind).name;
     if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
     if (n_coins < 2 || n_coins > kMaxCoins)
         return fail(c, CFMM_ERR_INVALID_ARG, "n_coins = %d: %s pools have 2 .. %d coins", (int)n_coins, fam, kMaxCoins);
@@ -200,7 +200,7 @@ int ncoin_check(cfmm_ctx* c, int kind, int64_t m, int32_t n_coins, const double*
 template <class Fill>
 int ncoin_add(cfmm_ctx* c, int kind, int64_t m, int nc, const double* R, const double* gamma, const int32_t* Ai, Fill fill)
 {
-    const NCoinFamily fam = ncoin_family(kind);
+    const KindInfo& fam = kind_info(kind);
     const size_t cells = (size_t)m * (size_t)nc, np = (size_t)fam.par_per_pool(nc);
     std::vector<double> cR(cells), cq(cells), cpar((size_t)m * np);
     std::vector<int32_t> ct(cells);

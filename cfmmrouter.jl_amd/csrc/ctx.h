@@ -4,8 +4,9 @@
 //
 //   abi_context.cpp   create / destroy / options / streams / introspection
 //   abi_upload.cpp    pool validation + upload (src/cfmms.jl:76-111, :152-165, :226-245), prepared constants
-//   abi_sweep.cpp     launch geometry, one evaluation = sweep launches + row fold, host-pointer sweeps,
-//                     pre-armed evaluations
+//   launch_plan.cpp   the launch geometry of one evaluation, as a pure function (launch_plan.h: no HIP, no context)
+//   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold, host-pointer
+//                     sweeps, pre-armed evaluations
 //   abi_trades.cpp    trade download / device views, update_reserves!, reserves / prices read-back
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
@@ -14,6 +15,7 @@
 #pragma once
 
 #include "../../include/cfmm_amd.h"
+#include "launch_plan.h"
 #include "sweep.h"
 
 #include <atomic>
@@ -30,10 +32,9 @@
 
 namespace cfmm {
 
-struct Segment {
+struct Segment : SegPlan {   // (SegPlan: the launch geometry, decided by ensure_geometry)
     int kind = 0;
     int64_t m = 0;
-    int64_t trade_off = 0; // first row of this segment in the (two-coin) trade buffers
     int64_t n_ticks_total = 0;
     int fast_ok = 0; // every constant the sweep divides by / takes roots of lies in [2^-kFastExp, 2^kFastExp] (sweep.h)
     // device arrays (owned)
@@ -54,66 +55,63 @@ struct Segment {
     TickRec* ticks = nullptr;   // univ3: walk lists (sweep.h TickRec)
     double* thr = nullptr;      // univ3: drain thresholds, one per record
     uint4* head = nullptr;      // univ3: per pool the first four thresholds of both walk lists as rounded-down floats (sweep.h UniV3Pools)
-    // launch geometry (decided by ensure_geometry)
-    int block = kMidBlock;
-    int grid = 0;
-    int64_t row_off = 0; // first partial row
     PackedFeeTok* pk = nullptr;     // {i1 | i2 << 16, fee-table index} per pool, or null (too many distinct fees / tokens)
     std::vector<double> gvals;      // the segment's distinct fees, in order of first appearance (index = PackedFeeTok::gidx)
-    int gbase = 0;                  // first entry of this segment in its launch's fee table (ensure_geometry)
     std::vector<int32_t> h_ai; // host copy of Ai: large-market mode (incidence build) and UniV3 segments
     // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
     std::vector<double> h_cp, h_gamma, h_lt, h_liq;
     std::vector<int64_t> h_tick_off;
-    // N-coin kinds (ragged_kind: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE) only: the coin-major columns and the segment's own
+    // N-coin kinds (KindInfo::ragged: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE) only: the coin-major columns and the segment's own
     // trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
     int n_coins = 2;
-    int64_t flat_off = 0;      // first double of this segment in the ragged trade layout of cfmm_get_trades (Σ coins before it)
     struct {
         double* R = nullptr;   // [n_coins][m] (sweep.h NCoinPools)
         double* q = nullptr;   // [n_coins][m] the family's per-coin constant
         int32_t* tok = nullptr;
         double2* glg = nullptr;   // [m] {γ, log γ}
-        double* par = nullptr;    // the family's own column (NCoinFamily::par_per_pool doubles per pool)
+        double* par = nullptr;    // the family's own column (KindInfo::par_per_pool doubles per pool)
         double* D = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
         double* L = nullptr;      // [n_coins][m] Λ
     } nc;
 };
 
-// Segments whose trades are ragged (n_coins per pool, kept in the segment's own nc.D / nc.L): their own launch each.
-inline bool ragged_kind(int kind) { return kind == CFMM_KIND_WEIGHTED || kind == CFMM_KIND_CURVE; }
-
-// Segments that are always their own launch (never in a fused sweep_multi group): the ragged kinds, and Solidly stable
-// pairs -- a two-coin kind (trades in the common [m][2] buffers) whose kernel is kept out of the fused launches
-inline bool own_launch_kind(int kind) { return ragged_kind(kind) || kind == CFMM_KIND_SOLIDLY; }
-
-// What the host knows of an N-coin family (ragged_kind); the device side is sweep_kernels.hip's WeightedFamily / CurveFamily.
-struct NCoinFamily {
+// What the library knows of a pool kind, in ONE place: the plan (launch_plan.cpp), the sweep (abi_sweep.cpp), the upload and
+// the trade paths all read this table.  The device side of a kind is its Ops / Family struct in sweep_kernels.hip.
+struct KindInfo {
     const char* name;          // in error texts
-    bool par_coin_major;       // the family's own column (NCoinPools::par): [n_coins][m] (weights) or [m] pairs ({α, log β})
-    bool need_logv;            // the sweep reads log v from LDS (SweepArgs::need_logv)
+    bool ragged;               // n_coins per pool: trades kept in the segment's own nc.D / nc.L, swept by sweep_ncoin
+    bool fusable;              // may share a sweep_multi launch with its neighbours; false: always its own launch (the ragged
+                               // kinds, and Solidly: a two-coin kind whose kernel is kept out of the fused launches)
+    bool has_fast;             // has kernels on the fast arithmetic (Segment::fast_ok says whether a segment may use them)
+    bool logv;                 // the sweep reads log v from LDS (SweepArgs::need_logv)
+    bool exact_form;           // option "geomean_exact" swaps in the pow-based form, which has neither of the two above
+    // relative cost of one pool evaluation in tenths of a ProductTwoCoin one: a constant or an option ("cost_geomean" /
+    // "cost_univ3"; measured on config3 / mixed markets, see DESIGN), plus multi_tick_cost when the segment averages more
+    // than 2 ticks per pool (a threshold scan + one more record).  Divides the blocks of a fused launch among its segments.
+    int cost;
+    int64_t PlanOpts::*cost_opt;
+    int multi_tick_cost;
+    bool par_coin_major;       // ragged kinds: the family's own column (NCoinPools::par) is [n_coins][m] (weights) or [m] pairs ({α, log β})
+    // bytes one materialising sweep moves per pool: two-coin kinds the packed record + one 16-byte trade record (a lower bound
+    // for multi-tick UniV3); ragged kinds per coin R, q, token (20 B) read and Δ, Λ (16 B) written, {γ, log γ}, par
+    int64_t (*bytes_per_pool)(int n_coins, int has_walk);
     int64_t par_per_pool(int n_coins) const { return par_coin_major ? n_coins : 2; }
-    // bytes one materialising sweep moves per pool: per coin R, q, token (20 B) read and Δ, Λ (16 B) written, {γ, log γ}, par
-    int64_t bytes_per_pool(int n_coins) const { return 36 * n_coins + 16 + 8 * par_per_pool(n_coins); }
 };
-inline NCoinFamily ncoin_family(int kind)
+inline const KindInfo& kind_info(int kind)
 {
-    return kind == CFMM_KIND_CURVE ? NCoinFamily{"Curve", false, false} : NCoinFamily{"weighted", true, true};
+    static const KindInfo table[] = {
+        /* CFMM_KIND_PRODUCT  */ {"ProductTwoCoin", false, true, true, false, false, 10, nullptr, 0, false, [](int, int) -> int64_t { return 24 + 16; }},
+        /* CFMM_KIND_GEOMEAN  */ {"GeometricMeanTwoCoin", false, true, true, true, true, 0, &PlanOpts::cost_geomean, 0, false, [](int, int) -> int64_t { return 48 + 16; }},
+        /* CFMM_KIND_UNIV3    */ {"UniV3", false, true, true, false, false, 0, &PlanOpts::cost_univ3, 6, false, [](int, int walk) -> int64_t { return (walk ? 104 : 56) + 16; }},
+        /* CFMM_KIND_WEIGHTED */ {"weighted", true, false, false, true, false, 0, nullptr, 0, true, [](int n, int) -> int64_t { return 36 * n + 16 + 8 * n; }},
+        /* CFMM_KIND_CURVE    */ {"Curve", true, false, false, false, false, 0, nullptr, 0, false, [](int n, int) -> int64_t { return 36 * n + 16 + 8 * 2; }},
+        /* CFMM_KIND_SOLIDLY  */ {"Solidly", false, false, false, false, false, 0, nullptr, 0, false, [](int, int) -> int64_t { return 24 + 16; }},
+    };
+    static_assert(CFMM_KIND_PRODUCT == 0 && CFMM_KIND_GEOMEAN == 1 && CFMM_KIND_UNIV3 == 2 && CFMM_KIND_WEIGHTED == 3 &&
+                  CFMM_KIND_CURVE == 4 && CFMM_KIND_SOLIDLY == 5 && sizeof table / sizeof table[0] == 6, "one row per CFMM_KIND_*");
+    return table[kind];
 }
-
-// A launch: either one segment (sweep_kernel) or up to kMaxMulti segments fused (sweep_multi).
-struct Group {
-    int first = 0, nseg = 1;
-    bool multi = false;
-    int block = kMidBlock;
-    int grid = 0;       // total blocks of the launch
-    int64_t row_off = 0;
-    int gtab_n = 0;     // entries of this launch's fee table (0: its segments use the plain gamma / Ai arrays)
-    // XCD-aware weighted block -> segment map of a fused launch (see sweep_multi); xcd_map == false: block b -> segment b % nseg
-    bool xcd_map = false;
-    unsigned char pattern[32] = {0}, rank[32] = {0};
-    int seg_w[kMaxMulti] = {0};
-};
+inline bool ragged_kind(int kind) { return kind_info(kind).ragged; }
 
 struct Workers {
     // Multi-device parents: one persistent thread per shard >= 1 (shard 0 runs on the calling thread).  A call publishes
@@ -154,7 +152,7 @@ struct cfmm_ctx {
     int64_t m_total = 0;
     int64_t trade_rows = 0;       // rows of the two-coin trade buffers (pools of the two-coin segments; weighted segments keep their own)
     int64_t flat_total = 0;       // Σ over segments of m × coins: the length of each ragged trade array (cfmm_trades_len)
-    bool any_ragged = false;      // some segment is ragged_kind (weighted, Curve): its trades are ragged
+    bool any_ragged = false;      // some segment is ragged (KindInfo::ragged: weighted, Curve): its trades are ragged
     int64_t touched_bytes = 0;    // what one materialising sweep moves by construction (packed layout; ensure_geometry): decides "stream_stores" = auto
     int64_t rows_total = 0;
 
@@ -216,17 +214,10 @@ struct cfmm_ctx {
     bool geometry_dirty = true;
 
     // options (cfmm_set_option)
-    int64_t opt_max_grid = 0;    // 0 = auto
-    int64_t opt_block = 0;       // 0 = auto, else kMidBlock or kBigBlock
-    int64_t opt_bin_copies = 0;  // 0 = auto, 1 = one shared copy, 2 = one copy per wavefront
+    cfmm::PlanOpts geo;          // the options the launch geometry depends on (launch_plan.h)
     int64_t opt_time_kernels = 0;
-    int64_t opt_geomean_exact = 0; // 1: pow-based reference-order forms instead of log-space
-    int64_t opt_fuse_segments = 1; // 1: sweep all pool families in one launch (sweep_multi)
     int64_t opt_zero_copy = 1;     // 1: host-pointer calls read v / receive Ψ through mapped pinned memory
-    int64_t opt_cost_geomean = 10; // cost of a GeometricMean / UniV3 evaluation in tenths of a ProductTwoCoin one (10 = blocks in
-    int64_t opt_cost_univ3 = 10;   // proportion to pool counts)
     int64_t opt_compact_trades = 1; // 1: a materialising sweep writes one 16-byte trade record per pool (+ overflow rows)
-    int64_t opt_pack = 1;          // 1: sweeps read the packed fee + token record when the launch's distinct fees fit the LDS table
     int64_t opt_alternate = 1;     // 1: consecutive sweeps walk the tiles in alternating directions (L2 reuse across sweeps)
     int64_t opt_fast_math = 1;     // 1: division / square root without range scaffolding where operands are inside the window (same bits)
     int64_t opt_armed = 1;         // 1: cfmm_route enqueues evaluation k+1 while evaluation k runs (see abi_sweep.cpp)
@@ -239,8 +230,6 @@ struct cfmm_ctx {
     int64_t opt_stream_stores = 0; // trade-record stores: 0 = auto (non-temporal when one sweep touches more than the 256 MiB Infinity Cache,
                                    //    i.e. the pool state cannot stay cache-resident between sweeps; write-through otherwise), 1 = always
                                    //    write-through, 2 = always non-temporal (a caller that rotates over many markets says so)
-    int64_t opt_direct_small = 1;  // 1: single-family markets of up to kDirectPools pools are swept by ONE block that publishes {Ψ, acc}
-                                   //    itself (no fold launch); 0: the general two-launch geometry
     int64_t opt_univ3_heads = 1;   // 1: multi-tick UniV3 walks decide their first four list ticks from the per-pool float threshold heads
     int64_t opt_dev_prices_in_window = 0; // 1 = the CALLER vouches that the prices of device-pointer sweeps lie in [2^-kFastExp, 2^kFastExp]
                                      //    (what the host checks itself for host-pointer calls): cfmm_sweep_dev launches the fast kernels
@@ -295,7 +284,7 @@ int upload(cfmm_ctx* c, T** dst, const void* src, size_t count)
     return CFMM_OK;
 }
 
-inline bool global_bins(const cfmm_ctx* c) { return c->n > kMaxLdsTokens; }
+inline bool global_bins(const cfmm_ctx* c) { return global_bins(c->n); }
 inline int row_width(const cfmm_ctx* c) { return global_bins(c) ? 1 : row_pitch_of(c->n + 1); }   // doubles between partial rows
 inline bool is_parent(const cfmm_ctx* c) { return !c->shards.empty() || c->device < 0; }
 

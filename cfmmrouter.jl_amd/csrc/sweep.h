@@ -177,7 +177,9 @@ union AnyPools {
     ProductPools p;
     GeoMeanPools g;
     UniV3Pools u;
+    NCoinPools n;                // (single launches only: never in a MultiSeg)
 };
+static_assert(sizeof(AnyPools) == sizeof(UniV3Pools), "MultiSeg's layout is the widest two-coin family's");
 struct MultiSeg {
     int kind;
     int64_t m;
@@ -212,22 +214,16 @@ struct LaunchCfg {
     hipEvent_t ev_stop = nullptr;  // (hipExtLaunchKernel), i.e. the kernel's own execution span
 };
 
-hipError_t launch_sweep(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+// One segment's own launch.  `kind` picks the member of `pools` and the kernel family: ProductTwoCoin (pools.p),
+// GeometricMeanTwoCoin (pools.g; reference_order picks the pow-based form), UniV3 (pools.u; the threshold-head kernel when
+// pools.u.head is set outside large-market mode), Solidly-style stable pairs (kind CFMM_KIND_SOLIDLY, φ = x³y + xy³:
+// ProductTwoCoin's pool layout in pools.p, full-range arithmetic), and the N-coin kinds CFMM_KIND_WEIGHTED / CFMM_KIND_CURVE
+// (pools.n; kMidBlock threads, full-range arithmetic, never single-block direct: a.Delta / a.Lambda / a.Over / a.gflow are
+// unused, the trades go to pools.n.Delta / pools.n.Lambda).  Large-market mode (a.gflow set) runs kMidBlock threads on the
+// full-range arithmetic.  A combination of family, arithmetic, block and mode that has no kernel (sweep_kernels.hip, the
+// kernel table) returns hipErrorInvalidDeviceFunction.
+hipError_t launch_sweep(int kind, const AnyPools& pools, const SweepArgs& a, const LaunchCfg& c, bool materialize,
                         hipStream_t s);
-hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                        hipStream_t s);
-hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                        hipStream_t s);
-// Solidly-style stable pairs (kind CFMM_KIND_SOLIDLY, φ = x³y + xy³): ProductTwoCoin's pool layout, their own launch
-// (full-range arithmetic, never fused; single-block direct and large-market mode like any two-coin family)
-hipError_t launch_sweep_solidly(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                                hipStream_t s);
-
-// N-coin segments (kind CFMM_KIND_WEIGHTED or CFMM_KIND_CURVE) are their own launch (kMidBlock threads, full-range
-// arithmetic, never fused, never single-block direct): a.Delta / a.Lambda / a.Over / a.gflow are unused (the trades go to
-// p.Delta / p.Lambda).
-hipError_t launch_sweep_ncoin(int kind, const NCoinPools& p, const SweepArgs& a, const LaunchCfg& c, bool materialize,
-                              hipStream_t s);
 // R <- (R + γΔ) − Λ per coin, in place, then q <- the family's constant for the new R (par: unchanged)
 hipError_t launch_update_ncoin(int kind, double* R, double* q, const double* par, const double2* glg, const double* Delta,
                                const double* Lambda, int n_coins, int64_t m, hipStream_t s);
@@ -279,7 +275,13 @@ hipError_t launch_update_two_coin(double2* R, const double* gamma, const double2
 hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const double2* ovB, double2* Delta, double2* Lambda,
                                 int64_t m, hipStream_t s);
 
-size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y);
+// dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
+// two doubles per wavefront and the block's two scalars
+inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)
+{
+    const size_t words = (size_t)n_pad * ((stage_y ? 2 : 1) + (need_logv ? 1 : 0) + copies) + 2 * (size_t)gtab_n + 2 * (size_t)(block / 64) + 2;
+    return words * sizeof(double);
+}
 hipError_t prepare_kernels(size_t max_lds_bytes);
 
 } // namespace cfmm

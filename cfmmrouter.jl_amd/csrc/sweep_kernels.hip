@@ -1689,159 +1689,138 @@ hipError_t launch_gather(const int2* chunks, const int* entries, const double* f
 // the command processor at the kernel's first and last wavefront (hipExtLaunchKernel): that is the
 // kernel's own execution span, the quantity rocprofv3 reports, without the ~2.5 us that a
 // hipEventRecord / launch / hipEventRecord bracket adds.
-template <class K, class... A>
-static void launch_k(K kernel, dim3 g, dim3 b, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, A... args)
+static hipError_t launch_k(const void* kernel, dim3 g, dim3 b, size_t lds, hipStream_t s, hipEvent_t e0, hipEvent_t e1, void** args)
 {
-    if (e0 && e1) hipExtLaunchKernelGGL(kernel, g, b, (std::uint32_t)lds, s, e0, e1, 0u, args...);
-    else hipLaunchKernelGGL(kernel, g, b, lds, s, args...);
+    if (e0 && e1) return hipExtLaunchKernel(kernel, g, b, args, lds, s, e0, e1, 0);
+    return hipLaunchKernel(kernel, g, b, args, lds, s);
 }
 
-size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)
-{
-    const size_t words = (size_t)n_pad * ((stage_y ? 2 : 1) + (need_logv ? 1 : 0) + copies) + 2 * (size_t)gtab_n + 2 * (size_t)(block / 64) + 2;
-    return words * sizeof(double);
-}
+// The sweep kernels (round 5: 82 two-coin instantiations, + 4 N-coin), written down ONCE: this table is what the launchers
+// look a kernel up in AND what prepare_kernels walks, so a kernel that can be launched cannot miss its LDS attribute.
+// Which (family, arithmetic) pairs exist is the constructor below: per family {full-range, fast, auto} x {materialising,
+// fused} x {512, 1024 threads}; the reference-order GeometricMean forms, Solidly and the N-coin families run full-range
+// only (the N-coin ones at 512 threads), and so does the large-market mode (GBINS) of every family, at 512 threads.
+enum KernelFamily { kFamProduct, kFamGeoMean, kFamGeoMeanLog, kFamSolidly, kFamUniV3, kFamUniV3Lean, kFamMulti, kFamWeighted, kFamCurve, kFamilies };
+struct SweepKernelTable {
+    static constexpr int kGbinsSlot = 3;   // large-market mode sits behind the three arithmetics
+    // [family][arithmetic, or kGbinsSlot][block == kBigBlock][materialising]; null: no such kernel
+    const void* fn[kFamilies][4][2][2] = {};
 
-// Kernel instantiations (round 5: 82).  Per family {full-range, fast, auto} x {materialising, fused} x {512, 1024 threads};
-// the reference-order GeometricMean forms and the large-market mode (GBINS, 512 threads) run full-range only.
-template <class Ops, int FASTK>
-static hipError_t set_lds_attr(size_t bytes)
+    template <class K> static const void* ptr(K* kernel) { return reinterpret_cast<const void*>(kernel); }
+    template <class Ops, int ARITH> void sweep(int f)
+    {
+        fn[f][ARITH][0][1] = ptr(&sweep_kernel<Ops, true, kMidBlock, false, ARITH>);
+        fn[f][ARITH][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, false, ARITH>);
+        fn[f][ARITH][1][1] = ptr(&sweep_kernel<Ops, true, kBigBlock, false, ARITH>);
+        fn[f][ARITH][1][0] = ptr(&sweep_kernel<Ops, false, kBigBlock, false, ARITH>);
+    }
+    template <class Ops> void sweep_all(int f) { sweep<Ops, kArithFull>(f); sweep<Ops, kArithFast>(f); sweep<Ops, kArithAuto>(f); }
+    template <class Ops> void sweep_gbins(int f)
+    {
+        fn[f][kGbinsSlot][0][1] = ptr(&sweep_kernel<Ops, true, kMidBlock, true, kArithFull>);
+        fn[f][kGbinsSlot][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, true, kArithFull>);
+    }
+    template <int ARITH> void multi()
+    {
+        fn[kFamMulti][ARITH][1][1] = ptr(&sweep_multi<true, kBigBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][1][0] = ptr(&sweep_multi<false, kBigBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][0][1] = ptr(&sweep_multi<true, kMidBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][0][0] = ptr(&sweep_multi<false, kMidBlock, false, ARITH>);
+    }
+    template <class F> void ncoin(int f)
+    {
+        fn[f][kArithFull][0][1] = ptr(&sweep_ncoin<F, true>);
+        fn[f][kArithFull][0][0] = ptr(&sweep_ncoin<F, false>);
+    }
+    SweepKernelTable()
+    {
+        fn[kFamMulti][kGbinsSlot][0][1] = ptr(&sweep_multi<true, kMidBlock, true, kArithFull>);
+        fn[kFamMulti][kGbinsSlot][0][0] = ptr(&sweep_multi<false, kMidBlock, true, kArithFull>);
+        multi<kArithFull>(); multi<kArithFast>(); multi<kArithAuto>();
+        ncoin<WeightedFamily>(kFamWeighted);
+        ncoin<CurveFamily>(kFamCurve);
+        sweep_all<ProductOps>(kFamProduct);
+        sweep<GeoMeanOps, kArithFull>(kFamGeoMean);
+        sweep<SolidlyOps, kArithFull>(kFamSolidly);
+        sweep_all<GeoMeanLogOps>(kFamGeoMeanLog);
+        sweep_all<UniV3Ops>(kFamUniV3);
+        sweep_all<UniV3OpsLean>(kFamUniV3Lean);
+        sweep_gbins<ProductOps>(kFamProduct);
+        sweep_gbins<GeoMeanOps>(kFamGeoMean);
+        sweep_gbins<GeoMeanLogOps>(kFamGeoMeanLog);
+        sweep_gbins<SolidlyOps>(kFamSolidly);
+        sweep_gbins<UniV3Ops>(kFamUniV3);   // (never requested: launch_sweep sends large markets to the lean walk)
+        sweep_gbins<UniV3OpsLean>(kFamUniV3Lean);
+    }
+    // null: no such kernel -- there is no falling through to another one
+    const void* find(int f, bool mat, int block, bool gbins, int arith) const
+    {
+        if ((block != kMidBlock && block != kBigBlock) || arith < kArithFull || arith > kArithAuto || (gbins && arith != kArithFull))
+            return nullptr;
+        return fn[f][gbins ? kGbinsSlot : arith][block == kBigBlock][mat];
+    }
+};
+static const SweepKernelTable kSweepKernels;
+
+// every kernel of the table may use the whole LDS of a CU
+hipError_t prepare_kernels(size_t max_lds_bytes)
 {
-    hipError_t e;
-#define CFMM_SET(MAT, B)                                                                              \
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_kernel<Ops, MAT, B, false, FASTK>),  \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);                  \
-    if (e != hipSuccess) return e;
-    CFMM_SET(true, kMidBlock) CFMM_SET(false, kMidBlock) CFMM_SET(true, kBigBlock) CFMM_SET(false, kBigBlock)
-#undef CFMM_SET
+    const void* const* kernels = &kSweepKernels.fn[0][0][0][0];
+    for (size_t k = 0; k < sizeof(SweepKernelTable::fn) / sizeof(void*); ++k) {
+        if (!kernels[k]) continue;
+        hipError_t e = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);
+        if (e != hipSuccess) return e;
+    }
     return hipSuccess;
 }
 
-template <int B, int FASTK>
-static void launch_multi_b(const MultiArgs& ma, const LaunchCfg& c, bool mat, hipStream_t s)
+// every sweep launch: the kernel comes from the table or the launch fails
+static hipError_t launch_family(int family, bool gbins, const LaunchCfg& c, bool mat, hipStream_t s, void** args)
 {
-    dim3 g(c.grid), b(B);
-    if (mat) launch_k(&sweep_multi<true, B, false, FASTK>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, ma);
-    else launch_k(&sweep_multi<false, B, false, FASTK>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, ma);
-}
-
-template <int B>
-static void launch_multi_a(const MultiArgs& ma, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (c.arith == kArithFast) launch_multi_b<B, kArithFast>(ma, c, mat, s);
-    else if (c.arith == kArithAuto) launch_multi_b<B, kArithAuto>(ma, c, mat, s);
-    else launch_multi_b<B, kArithFull>(ma, c, mat, s);
+    const void* kernel = kSweepKernels.find(family, mat, c.block, gbins, c.arith);
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    return launch_k(kernel, dim3(c.grid), dim3(c.block), c.lds_bytes, s, c.ev_start, c.ev_stop, args);
 }
 
 hipError_t launch_multi(const MultiArgs& ma, const LaunchCfg& c, bool mat, hipStream_t s)
 {
-    if (ma.common.gflow) {   // large-market mode: kMidBlock, full-range arithmetic
-        dim3 g(c.grid), b(kMidBlock);
-        if (mat) launch_k(&sweep_multi<true, kMidBlock, true, kArithFull>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, ma);
-        else launch_k(&sweep_multi<false, kMidBlock, true, kArithFull>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, ma);
-    } else if (c.block == kBigBlock) {
-        launch_multi_a<kBigBlock>(ma, c, mat, s);
-    } else {
-        launch_multi_a<kMidBlock>(ma, c, mat, s);
-    }
-    return hipGetLastError();
+    void* args[] = {const_cast<MultiArgs*>(&ma)};
+    return launch_family(kFamMulti, ma.common.gflow != nullptr, c, mat, s, args);
 }
 
-hipError_t prepare_kernels(size_t max_lds_bytes)
+// Ops: the kernel's first argument, built from the segment's pools (an Ops struct, or the N-coin pools themselves)
+template <class Ops, class Pools>
+static hipError_t launch_ops(int family, const Pools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
 {
-    hipError_t em;
-#define CFMM_SETM(MAT, B, F)                                                                          \
-    em = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_multi<MAT, B, false, F>),           \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);         \
-    if (em != hipSuccess) return em;
-#define CFMM_SETM4(F) CFMM_SETM(true, kBigBlock, F) CFMM_SETM(false, kBigBlock, F) CFMM_SETM(true, kMidBlock, F) CFMM_SETM(false, kMidBlock, F)
-    CFMM_SETM4(kArithFull) CFMM_SETM4(kArithFast) CFMM_SETM4(kArithAuto)
-#undef CFMM_SETM4
-#undef CFMM_SETM
-    hipError_t e;
-    if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<WeightedFamily, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<WeightedFamily, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<CurveFamily, true>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess ||
-        (e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_ncoin<CurveFamily, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes)) != hipSuccess)
-        return e;
-    if ((e = set_lds_attr<ProductOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<ProductOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<ProductOps, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<GeoMeanOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<SolidlyOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<GeoMeanLogOps, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<GeoMeanLogOps, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<GeoMeanLogOps, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<UniV3Ops, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<UniV3Ops, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<UniV3Ops, kArithAuto>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<UniV3OpsLean, kArithFull>(max_lds_bytes)) != hipSuccess) return e;
-    if ((e = set_lds_attr<UniV3OpsLean, kArithFast>(max_lds_bytes)) != hipSuccess) return e;
-    return set_lds_attr<UniV3OpsLean, kArithAuto>(max_lds_bytes);
+    Ops ops{p};
+    void* args[] = {&ops, const_cast<SweepArgs*>(&a)};
+    return launch_family(family, a.gflow != nullptr, c, mat, s, args);
 }
 
-template <class Ops, int FASTK>
-static void launch_any_f(const Ops& ops, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    dim3 g(c.grid);
-    hipEvent_t e0 = c.ev_start, e1 = c.ev_stop;
-    if (c.block == kBigBlock) {
-        if (mat) launch_k(&sweep_kernel<Ops, true, kBigBlock, false, FASTK>, g, dim3(kBigBlock), c.lds_bytes, s, e0, e1, ops, a);
-        else launch_k(&sweep_kernel<Ops, false, kBigBlock, false, FASTK>, g, dim3(kBigBlock), c.lds_bytes, s, e0, e1, ops, a);
-    } else {
-        if (mat) launch_k(&sweep_kernel<Ops, true, kMidBlock, false, FASTK>, g, dim3(kMidBlock), c.lds_bytes, s, e0, e1, ops, a);
-        else launch_k(&sweep_kernel<Ops, false, kMidBlock, false, FASTK>, g, dim3(kMidBlock), c.lds_bytes, s, e0, e1, ops, a);
-    }
-}
-
-template <class Ops, bool HAS_FAST = true>
-static hipError_t launch_any(const Ops& ops, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+hipError_t launch_sweep(int kind, const AnyPools& pools, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
 {
     if (a.m <= 0) return hipSuccess;
-    if (a.gflow) { // large-market mode: kMidBlock, full-range arithmetic
-        dim3 g(c.grid);
-        hipEvent_t e0 = c.ev_start, e1 = c.ev_stop;
-        if (mat) launch_k(&sweep_kernel<Ops, true, kMidBlock, true, kArithFull>, g, dim3(kMidBlock), c.lds_bytes, s, e0, e1, ops, a);
-        else launch_k(&sweep_kernel<Ops, false, kMidBlock, true, kArithFull>, g, dim3(kMidBlock), c.lds_bytes, s, e0, e1, ops, a);
-    } else if constexpr (HAS_FAST) {
-        if (c.arith == kArithFast) launch_any_f<Ops, kArithFast>(ops, a, c, mat, s);
-        else if (c.arith == kArithAuto) launch_any_f<Ops, kArithAuto>(ops, a, c, mat, s);
-        else launch_any_f<Ops, kArithFull>(ops, a, c, mat, s);
-    } else {
-        launch_any_f<Ops, kArithFull>(ops, a, c, mat, s);
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: return launch_ops<ProductOps>(kFamProduct, pools.p, a, c, mat, s);
+    case CFMM_KIND_GEOMEAN:
+        return pools.g.reference_order ? launch_ops<GeoMeanOps>(kFamGeoMean, pools.g, a, c, mat, s)
+                                       : launch_ops<GeoMeanLogOps>(kFamGeoMeanLog, pools.g, a, c, mat, s);
+    case CFMM_KIND_UNIV3:
+        return pools.u.head && !a.gflow ? launch_ops<UniV3Ops>(kFamUniV3, pools.u, a, c, mat, s)
+                                        : launch_ops<UniV3OpsLean>(kFamUniV3Lean, pools.u, a, c, mat, s);
+    case CFMM_KIND_SOLIDLY: return launch_ops<SolidlyOps>(kFamSolidly, pools.p, a, c, mat, s);
+    case CFMM_KIND_WEIGHTED: return launch_ops<NCoinPools>(kFamWeighted, pools.n, a, c, mat, s);
+    case CFMM_KIND_CURVE: return launch_ops<NCoinPools>(kFamCurve, pools.n, a, c, mat, s);
+    default: return hipErrorInvalidDeviceFunction;
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_sweep(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    return launch_any(ProductOps{p}, a, c, mat, s);
-}
-hipError_t launch_sweep(const GeoMeanPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (p.reference_order) return launch_any<GeoMeanOps, false>(GeoMeanOps{p}, a, c, mat, s);
-    return launch_any(GeoMeanLogOps{p}, a, c, mat, s);
-}
-hipError_t launch_sweep_solidly(const ProductPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    return launch_any<SolidlyOps, false>(SolidlyOps{p}, a, c, mat, s);
-}
-hipError_t launch_sweep(const UniV3Pools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (p.head && !a.gflow) return launch_any(UniV3Ops{p}, a, c, mat, s);
-    return launch_any(UniV3OpsLean{p}, a, c, mat, s);
 }
 
 hipError_t launch_reduce(const double* partials, int rows, int n1, int pitch, double* out, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
                          HostOut host, ArmWord arm)
 {
     dim3 g(fold_grid(n1));
-    launch_k(&reduce_partials<kFoldBlock>, g, dim3(kFoldBlock), 0, s, e0, e1, partials, rows, n1, pitch, out, host, arm);
-    return hipGetLastError();
+    void* args[] = {&partials, &rows, &n1, &pitch, &out, &host, &arm};
+    return launch_k(reinterpret_cast<const void*>(&reduce_partials<kFoldBlock>), g, dim3(kFoldBlock), 0, s, e0, e1, args);
 }
 
 // update_reserves!(r) for the two-coin families -- src/router.jl:127-132 with the update the routing
@@ -1934,18 +1913,6 @@ __global__ __launch_bounds__(256) void update_ncoin(double* __restrict__ R, doub
     }
 }
 
-hipError_t launch_sweep_ncoin(int kind, const NCoinPools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (a.m <= 0) return hipSuccess;
-    dim3 g(c.grid), b(kMidBlock);
-    const bool curve = kind == CFMM_KIND_CURVE;
-    if (curve && mat) launch_k(&sweep_ncoin<CurveFamily, true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    else if (curve) launch_k(&sweep_ncoin<CurveFamily, false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    else if (mat) launch_k(&sweep_ncoin<WeightedFamily, true>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    else launch_k(&sweep_ncoin<WeightedFamily, false>, g, b, c.lds_bytes, s, c.ev_start, c.ev_stop, p, a);
-    return hipGetLastError();
-}
-
 hipError_t launch_update_ncoin(int kind, double* R, double* q, const double* par, const double2* glg, const double* Delta,
                                const double* Lambda, int n_coins, int64_t m, hipStream_t s)
 {
@@ -1971,8 +1938,8 @@ hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pi
                                 hipEvent_t e0, hipEvent_t e1)
 {
     dim3 g(fold_grid(n1));
-    launch_k(&reduce_gather<kFoldBlock>, g, dim3(kFoldBlock), 0, s, e0, e1, partials, rows, n1, pitch, out, ps);
-    return hipGetLastError();
+    void* args[] = {&partials, &rows, &n1, &pitch, &out, const_cast<PeerSet*>(&ps)};
+    return launch_k(reinterpret_cast<const void*>(&reduce_gather<kFoldBlock>), g, dim3(kFoldBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm
