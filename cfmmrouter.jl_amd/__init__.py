@@ -11,7 +11,7 @@ from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwo
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
 from .router import (DeviceBackend, Router, dual_jacobian, find_arb_ as _find_arb_router, netflows, netflows_, polish_, route_,
-                     update_reserves_)
+                     update_pools_, update_reserves_)
 
 
 def find_arb_(*args, **kw):
@@ -25,7 +25,7 @@ __all__ = [
     "CFMM", "ProductTwoCoin", "GeometricMeanTwoCoin", "UniV3", "BoundedProduct", "GeometricMean", "Product", "Curve",
     "SolidlyStableTwoCoin",
     "PoolBatch", "find_arb_",
-    "update_reserves_", "Objective", "LinearNonnegative", "BasketLiquidation", "Swap", "f", "grad_",
+    "update_reserves_", "update_pools_", "Objective", "LinearNonnegative", "BasketLiquidation", "Swap", "f", "grad_",
     "lower_limit", "upper_limit", "Router", "route_", "netflows_", "netflows", "ArgumentError",
     "CFMMDeviceError", "Context", "DeviceBackend", "build", "lib", "zerotrade", "ϕ", "ϕ_grad_", "phi", "grad_phi_",
     "polish_", "dual_jacobian",

@@ -126,6 +126,9 @@ def lib():
     L.cfmm_update_reserves.argtypes = [_ctx]
     L.cfmm_get_reserves.argtypes = [_ctx, C.c_int32, _f64p]
     L.cfmm_get_prices.argtypes = [_ctx, C.c_int32, _f64p]
+    L.cfmm_pools_set_reserves.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p]
+    L.cfmm_pools_set_curve.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, _f64p]
+    L.cfmm_pools_set_prices.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -401,6 +404,31 @@ class Context:
         p = np.empty(int(m))
         self._check(self._L.cfmm_get_prices(self._h, int(seg), ptr(p)))
         return p
+
+    # -- sparse pool-state updates (cfmm_pools_set_*): rows `idx` of segment `seg`, nothing re-uploaded ----------------
+    def set_reserves(self, seg: int, idx, R):
+        """New reserves R [count, n_coins] of pools idx of a Product / GeoMean / Solidly / weighted segment."""
+        idx, R = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1), f64(R)
+        if idx.size == 0 or R.size % idx.size:
+            if idx.size == 0 and R.size == 0:
+                return self._check(self._L.cfmm_pools_set_reserves(self._h, int(seg), 0, ptr(idx), ptr(R)))
+            raise ArgumentError("R must have shape [len(idx), n_coins]")
+        self._check(self._L.cfmm_pools_set_reserves(self._h, int(seg), idx.size, ptr(idx), ptr(R)))
+
+    def set_curve(self, seg: int, idx, R, alpha, beta):
+        """New reserves R [count, n_coins] and parameters alpha, beta [count] of pools idx of a Curve segment."""
+        idx, R = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1), f64(R)
+        alpha, beta = f64(alpha).reshape(-1), f64(beta).reshape(-1)
+        if alpha.size != idx.size or beta.size != idx.size or (idx.size and R.size % idx.size) or (not idx.size and R.size):
+            raise ArgumentError("R must have shape [len(idx), n_coins], alpha and beta shape [len(idx)]")
+        self._check(self._L.cfmm_pools_set_curve(self._h, int(seg), idx.size, ptr(idx), ptr(R), ptr(alpha), ptr(beta)))
+
+    def set_prices(self, seg: int, idx, current_price):
+        """New current prices [count] of pools idx of a UniV3 segment (ticks and liquidity unchanged)."""
+        idx, p = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1), f64(current_price).reshape(-1)
+        if p.size != idx.size:
+            raise ArgumentError("current_price must have len(idx) entries")
+        self._check(self._L.cfmm_pools_set_prices(self._h, int(seg), idx.size, ptr(idx), ptr(p)))
 
     def set_peers(self, peer_ptrs, world: int, rank: int, seq: int):
         """Sharded operation: every host-pointer sweep of this context ends with the one-shot peer

@@ -445,6 +445,37 @@ class PoolBatch:
         return PoolBatch(kind, **fields)
 
 
+def _set_pool_state(ctx, seg, batch: PoolBatch, rows, states):
+    """New state of pools `rows` of `batch` (device segment `seg`; ctx None: host mirror only): a reserve vector per pool,
+    (R, α, β) for Curve, a price for UniV3.  The device call (cfmm_pools_set_*) checks every row before anything changes;
+    the batch's arrays follow only when it accepted."""
+    rows = np.asarray(rows, dtype=np.int64)
+    try:
+        if batch.kind == KIND_UNIV3:
+            p = np.array([float(s) for s in states], dtype=np.float64)
+            if ctx is not None:
+                ctx.set_prices(seg, rows, p)
+            batch.current_price[rows] = p
+        elif batch.kind == KIND_CURVE:
+            R = np.array([np.asarray(s[0], dtype=np.float64).reshape(batch.n_coins) for s in states]).reshape(len(rows), batch.n_coins)
+            α = np.array([float(s[1]) for s in states], dtype=np.float64)
+            β = np.array([float(s[2]) for s in states], dtype=np.float64)
+            if ctx is not None:
+                ctx.set_curve(seg, rows, R, α, β)
+            batch.R[rows], batch.α[rows], batch.β[rows] = R, α, β
+        else:
+            n = batch.R.shape[1]
+            R = np.array([np.asarray(s, dtype=np.float64).reshape(n) for s in states]).reshape(len(rows), n)
+            if ctx is not None:
+                ctx.set_reserves(seg, rows, R)
+            batch.R[rows] = R
+    except (TypeError, ValueError, IndexError) as e:
+        if isinstance(e, ArgumentError):
+            raise
+        raise ArgumentError(f"new state of a {type(batch[0]).__name__ if len(batch) else 'pool'}: an R vector per pool, (R, α, β) "
+                            f"for Curve, a price for UniV3 ({e})") from None
+
+
 def zerotrade(c):
     """zerotrade(c) -- src/cfmms.jl:73,248"""
     return np.zeros(2)

@@ -202,6 +202,57 @@ def load_snapshot(source):
     return tokens, batches
 
 
+def snapshot_delta(old, new):
+    """What moved between two snapshots of the SAME pool set: `old` and `new` are `load_snapshot` results (or their batch
+    lists).  -> {position: new state} for the pools whose state differs, in the form `update_pools_(router, changes)` takes
+    for a router built from these batches: position = the pool's index in the concatenated batches; state = a reserve vector,
+    `(R, α, β)` for Curve, the price for concentrated-liquidity pools.  Anything else that differs -- the pool set, a pool's
+    family, tokens, fee, weights or tick ladder -- is a structural change (a re-upload): ArgumentError naming the pool."""
+    def batches_of(snap):
+        if isinstance(snap, tuple) and len(snap) == 2 and not hasattr(snap[0], "kind"):
+            return snap[0], list(snap[1])
+        return None, list(snap)
+
+    (tok_a, a), (tok_b, b) = batches_of(old), batches_of(new)
+    if len(a) != len(b) or any(x.kind != y.kind or len(x) != len(y) or x.Ai.shape != y.Ai.shape for x, y in zip(a, b)):
+        raise ArgumentError("the snapshots hold different pool sets (pools per family: "
+                            f"{[len(x) for x in a]} vs {[len(y) for y in b]})")
+    changes, base = {}, 0
+    for x, y in zip(a, b):
+        # tokens: by identifier when the snapshots carry them (the numbering follows first appearance and may shift), else by index
+        if tok_a is not None and tok_b is not None:
+            same_tok = np.asarray(tok_a, dtype=object)[x.Ai - 1] == np.asarray(tok_b, dtype=object)[y.Ai - 1]
+        else:
+            same_tok = x.Ai == y.Ai
+        fixed = [("tokens", ~same_tok), ("fee", x.γ != y.γ)] + ([("weights", x.w != y.w)] if hasattr(x, "w") else [])
+        for what, differs in fixed:
+            bad = np.nonzero(np.any(np.asarray(differs).reshape(len(x), -1), axis=1))[0]
+            if bad.size:
+                raise ArgumentError(f"pool {base + int(bad[0])}: {what} changed between the snapshots (a structural change: re-upload)")
+        if hasattr(x, "tick_off"):
+            ragged = not np.array_equal(x.tick_off, y.tick_off)
+            nt = np.diff(x.tick_off)
+            same = np.ones(len(x), dtype=bool)
+            if ragged:
+                same = np.diff(y.tick_off) == nt
+            if same.all():
+                diff = (x.lower_ticks != y.lower_ticks) | (x.liquidity != y.liquidity)
+                same = np.add.reduceat(diff.astype(np.int64), x.tick_off[:-1]) == 0 if diff.size else same
+            if not same.all():
+                raise ArgumentError(f"pool {base + int(np.nonzero(~same)[0][0])}: tick ladder changed between the snapshots "
+                                    "(a mint / burn is a structural change: re-upload)")
+            for i in np.nonzero(x.current_price != y.current_price)[0]:
+                changes[base + int(i)] = float(y.current_price[i])
+        else:
+            moved = np.any(x.R != y.R, axis=1)
+            if hasattr(x, "α"):
+                moved |= (x.α != y.α) | (x.β != y.β)
+            for i in np.nonzero(moved)[0]:
+                changes[base + int(i)] = (y.R[i].copy(), float(y.α[i]), float(y.β[i])) if hasattr(x, "α") else y.R[i].copy()
+        base += len(x)
+    return changes
+
+
 def stableswap_D(x, A):
     """StableSwap's invariant D of balances x [..., n] at amplification A [...]: the root of
     A·nⁿ·Σx + D = A·D·nⁿ + D^{n+1}/(nⁿ·Πx), by the contracts' own Newton iteration in float64 (vectorised)."""

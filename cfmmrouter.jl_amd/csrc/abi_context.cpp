@@ -184,6 +184,8 @@ void cfmm_ctx_destroy(cfmm_ctx* c)
     (void)hipFree(c->d_flow); (void)hipFree(c->d_entries); (void)hipFree(c->d_chunks);
     (void)hipFree(c->d_tok_chunk_off); (void)hipFree(c->d_chunk_sums);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
+    if (c->h_upd) (void)hipHostFree(c->h_upd);
+    if (c->upd_done) (void)hipEventDestroy(c->upd_done);
     if (c->d_arm) (void)hipFree(c->d_arm);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -256,6 +258,11 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (!c || !value) return CFMM_ERR_INVALID_ARG;
     if (key && !std::strcmp(key, "peer_seq")) {   // read-only: sharded sweeps performed on the current peer buffers
         *value = (int64_t)c->peer_seq;            // (cfmm_set_peers' `seq` to continue from; ranks re-align on the maximum)
+        return CFMM_OK;
+    }
+    if (key && !std::strcmp(key, "pool_update_regrows")) {   // read-only: compactions + regrows of UniV3 tick arrays (cfmm_pools_set_prices)
+        *value = c->pool_update_regrows;
+        for (const cfmm_ctx* child : c->shards) *value += child->pool_update_regrows;
         return CFMM_OK;
     }
     int64_t* slot = option_slot(const_cast<cfmm_ctx*>(c), key);

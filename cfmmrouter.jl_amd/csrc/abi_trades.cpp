@@ -335,6 +335,7 @@ int cfmm_update_reserves(cfmm_ctx* c)
         s.walk = ns.walk; s.ticks = ns.ticks; s.thr = ns.thr; s.has_walk = ns.has_walk;
         s.cp = ns.cp; s.pk = ns.pk; s.gvals.swap(ns.gvals); s.fast_ok = ns.fast_ok;
         s.h_cp.swap(new_cp[k]);
+        s.h_walk.swap(ns.h_walk); s.tick_used = ns.tick_used; s.tick_cap = ns.tick_cap;
         ns = Segment{};   // ownership moved
     }
     return CFMM_OK;

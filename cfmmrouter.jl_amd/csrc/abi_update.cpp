@@ -1,0 +1,435 @@
+// abi_update.cpp -- sparse pool-state updates (include/cfmm_amd.h: cfmm_pools_set_reserves, cfmm_pools_set_curve,
+// cfmm_pools_set_prices): the reference's `cfmm.R .= ...` on a few pools of a router, without re-uploading the market.
+// Every row is checked with the upload's own checks (pool_checks.h) before anything changes; the prepared constants are
+// computed on the host with the upload's own expressions (pool_checks.h, univ3_pool.h), packed column by column into the
+// context's pinned staging buffer and scattered into the segment's columns by ONE launch (sweep.h ScatterArgs) on the
+// context's stream.  A moved UniV3 pool's walk lists are appended at the tail of the segment's record arrays.
+#include "ctx.h"
+#include "pool_checks.h"
+
+#include <algorithm>
+#include <cstring>
+
+using namespace cfmm;
+
+namespace {
+
+enum Entry { kSetReserves, kSetCurve, kSetPrices };
+const char* const kEntryName[] = {"cfmm_pools_set_reserves", "cfmm_pools_set_curve", "cfmm_pools_set_prices"};
+
+struct Update {
+    Entry entry;
+    int32_t seg;
+    int64_t count;
+    const int64_t* idx;
+    const double* R;        // [count][n_coins]        (kSetReserves, kSetCurve)
+    const double* alpha;    // [count]                 (kSetCurve)
+    const double* beta;
+    const double* price;    // [count]                 (kSetPrices)
+};
+
+Entry entry_of_kind(int kind) { return kind == CFMM_KIND_UNIV3 ? kSetPrices : kind == CFMM_KIND_CURVE ? kSetCurve : kSetReserves; }
+
+// the entry fits the segment's kind, or the refusal that names the one that does
+int check_entry(const cfmm_ctx* c, Entry entry, int kind)
+{
+    const Entry right = entry_of_kind(kind);
+    if (entry == right) return CFMM_OK;
+    return fail(c, CFMM_ERR_INVALID_ARG, "%s: segment of %s pools: %s", kEntryName[entry], kind_info(kind).name, kEntryName[right]);
+}
+
+int check_args(const cfmm_ctx* c, const Update& u, int64_t n_segs)
+{
+    if (u.count < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
+    if (u.seg < 0 || u.seg >= n_segs) return fail(c, CFMM_ERR_INVALID_ARG, "segment out of range");
+    return CFMM_OK;
+}
+int check_arrays(const cfmm_ctx* c, const Update& u)
+{
+    const bool ok = u.idx && (u.entry == kSetPrices ? u.price != nullptr : u.R != nullptr) && (u.entry != kSetCurve || (u.alpha && u.beta));
+    return u.count > 0 && !ok ? fail(c, CFMM_ERR_INVALID_ARG, "null pool array") : CFMM_OK;
+}
+
+// Every check of one single-device update, nothing changed: the rows in the caller's order, each with the checks of the
+// matching cfmm_pools_add_* on the values given.  row_base: what a shard adds to its rows in error texts (the parent's rows).
+int validate(const cfmm_ctx* c, const Update& u, int64_t row_base)
+{
+    int rc = check_args(c, u, (int64_t)c->segs.size());
+    if (rc != CFMM_OK) return rc;
+    const Segment& s = c->segs[(size_t)u.seg];
+    if ((rc = check_entry(c, u.entry, s.kind)) != CFMM_OK || (rc = check_arrays(c, u)) != CFMM_OK) return rc;
+    const int nc = ragged_kind(s.kind) ? s.n_coins : 2;
+    for (int64_t j = 0; j < u.count; ++j) {
+        const int64_t i = u.idx[j], row = row_base + i;
+        if (i < 0 || i >= s.m) return fail(c, CFMM_ERR_INVALID_ARG, "pool index %lld out of range [0, %lld)", (long long)row, (long long)(row_base + s.m));
+        if (u.entry == kSetPrices) {
+            int64_t ct;
+            const int64_t o = s.h_tick_off[(size_t)i];
+            if ((rc = check_univ3_price(c, row, u.price[j])) != CFMM_OK ||
+                (rc = check_univ3_tick(c, row, s.h_lt.data() + o, s.h_tick_off[(size_t)i + 1] - o, u.price[j], ct)) != CFMM_OK)
+                return rc;
+            continue;
+        }
+        const double* R = u.R + j * nc;
+        if ((rc = check_reserves(c, row, R, nc)) != CFMM_OK) return rc;
+        if (s.kind == CFMM_KIND_SOLIDLY && (rc = check_solidly_range(c, row, R)) != CFMM_OK) return rc;
+        if (s.kind == CFMM_KIND_CURVE && (rc = check_curve_params(c, row, u.alpha[j], u.beta[j], R, nc)) != CFMM_OK) return rc;
+    }
+    return CFMM_OK;
+}
+
+// The distinct rows of an update in ascending order, each with the position of its LAST occurrence in the caller's arrays
+// (a row named twice takes its last value; decided here, on the host, so the result does not depend on the launch)
+struct Rows {
+    std::vector<int64_t> idx, src;
+};
+Rows distinct_rows(int64_t count, const int64_t* idx)
+{
+    std::vector<std::pair<int64_t, int64_t>> a((size_t)count);
+    for (int64_t j = 0; j < count; ++j) a[(size_t)j] = {idx[j], j};
+    std::sort(a.begin(), a.end());
+    Rows r;
+    for (size_t k = 0; k < a.size(); ++k)
+        if (k + 1 == a.size() || a[k + 1].first != a[k].first) {
+            r.idx.push_back(a[k].first);
+            r.src.push_back(a[k].second);
+        }
+    return r;
+}
+
+// The staging buffer with room for `words` 8-byte words, free for the host to fill: the previous scatter has read it
+int staging_reserve(cfmm_ctx* c, size_t words)
+{
+    if (c->upd_busy) {
+        HIP_TRY(c, hipEventSynchronize(c->upd_done));
+        c->upd_busy = false;
+    }
+    if (!c->upd_done) HIP_TRY(c, hipEventCreateWithFlags(&c->upd_done, hipEventDisableTiming));
+    const size_t bytes = (words + 8 * (size_t)kMaxScatterCols) * 8;   // (+ the columns' alignment)
+    if (bytes <= c->upd_cap) return CFMM_OK;
+    size_t cap = std::max<size_t>(c->upd_cap * 2, 1 << 16);
+    while (cap < bytes) cap *= 2;
+    void *h = nullptr, *d = nullptr;
+    if (hipHostMalloc(&h, cap, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        if (h) (void)hipHostFree(h);
+        return fail(c, CFMM_ERR_HIP, "pool update: staging allocation of %zu bytes failed", cap);
+    }
+    if (c->h_upd) (void)hipHostFree(c->h_upd);
+    c->h_upd = h;
+    c->d_upd = d;
+    c->upd_cap = cap;
+    return CFMM_OK;
+}
+
+// Columns of one scatter launch, laid out in the staging buffer in the order they are added
+struct Packer {
+    ScatterArgs a{};
+    unsigned long long* h;
+    explicit Packer(cfmm_ctx* c) : h(static_cast<unsigned long long*>(c->h_upd)) { a.stage = static_cast<const unsigned long long*>(c->d_upd); }
+    // -> the host side of a column of `rows` rows, `width` words each
+    template <class T>
+    T* add(void* dst, int width, int64_t rows, int64_t dense_base = -1)
+    {
+        ScatterCol& col = a.col[a.ncols++];
+        a.total = (a.total + 7) & ~7ll;   // every column on a 64-byte boundary of the staging buffer
+        col.dst = static_cast<unsigned long long*>(dst);
+        col.begin = a.total;
+        col.rows = rows;
+        col.dense_base = dense_base;
+        col.width = width;
+        T* p = reinterpret_cast<T*>(h + a.total);
+        a.total += rows * width;
+        return p;
+    }
+    // the rows themselves, after the columns
+    void set_rows(const std::vector<int64_t>& idx)
+    {
+        std::memcpy(h + a.total, idx.data(), idx.size() * 8);
+        a.idx = reinterpret_cast<const long long*>(a.stage + a.total);
+    }
+};
+
+int launch(cfmm_ctx* c, const Packer& p)
+{
+    HIP_TRY(c, launch_scatter_records(p.a, c->stream));
+    HIP_TRY(c, hipEventRecord(c->upd_done, c->stream));
+    c->upd_busy = true;
+    return CFMM_OK;
+}
+
+// Room for `need` more records at the tail of a UniV3 segment's ticks / thr.  When it runs out: wait for the stream, fetch the
+// records in use, rebuild the arrays tightly from the host's walk spans (the lists of moved pools are garbage) and allocate
+// half as much again (at least 4096 records).  Nothing of the segment changes unless every allocation succeeded.
+int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
+{
+    if (s.tick_used + need <= s.tick_cap) return CFMM_OK;
+    constexpr int64_t kMaxRecords = 0x3fffffff / 2;   // the sweep's index arithmetic (univ3_build: 2·(T + 2m) <= 0x3fffffff)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<TickRec> old((size_t)s.tick_used), tight;
+    if (s.tick_used > 0) HIP_TRY(c, hipMemcpy(old.data(), s.ticks, old.size() * sizeof(TickRec), hipMemcpyDeviceToHost));
+    std::vector<int4> walk = s.h_walk;
+    tight.reserve(old.size());
+    for (int4& w : walk) {   // a pool's two lists lie back to back: [x, x + y] and [z, z + w], z = x + y + 1
+        const size_t n = (size_t)w.y + (size_t)w.w + 2;
+        const int base = (int)tight.size();
+        tight.insert(tight.end(), old.begin() + w.x, old.begin() + w.x + (ptrdiff_t)n);
+        w = make_int4(base, w.y, base + w.y + 1, w.w);
+    }
+    const int64_t want = (int64_t)tight.size() + need;
+    if (want > kMaxRecords) return fail(c, CFMM_ERR_UNSUPPORTED, "too many ticks in one segment");
+    const int64_t cap = std::min(kMaxRecords, want + std::max<int64_t>(want / 2, 4096));
+    std::vector<double> thr((size_t)cap + 4, 0.0);   // (the scan reads four thresholds at a time: zeros behind the tail)
+    for (size_t e = 0; e < tight.size(); ++e) thr[e] = tight[e].thr;
+    TickRec* d_ticks = nullptr;
+    double* d_thr = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d_ticks), (size_t)cap * sizeof(TickRec)) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&d_thr), thr.size() * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(d_ticks);
+        return fail(c, CFMM_ERR_HIP, "pool update: allocation of %lld tick records failed", (long long)cap);
+    }
+    hipError_t e = hipMemcpy(d_ticks, tight.data(), tight.size() * sizeof(TickRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_thr, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s.walk, walk.data(), walk.size() * sizeof(int4), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {   // (s.walk may be half written: it still names records of the OLD arrays only if nothing was copied)
+        (void)hipFree(d_ticks);
+        (void)hipFree(d_thr);
+        return fail(c, CFMM_ERR_HIP, "pool update: re-upload of the tick records failed: %s", hipGetErrorString(e));
+    }
+    (void)hipFree(s.ticks);
+    (void)hipFree(s.thr);
+    s.ticks = d_ticks;
+    s.thr = d_thr;
+    s.h_walk.swap(walk);
+    s.tick_used = (int64_t)tight.size();
+    s.tick_cap = cap;
+    ++c->pool_update_regrows;
+    return CFMM_OK;
+}
+
+int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
+{
+    const int64_t k = (int64_t)rows.idx.size();
+    // the moved pools' records, prepared as at upload (univ3_pool.h); list offsets relative to `ticks` until the tail is known
+    std::vector<UniV3PoolRec> rec((size_t)k);
+    std::vector<TickRec> ticks;
+    std::vector<double> thr;
+    bool fast = true, lists = false;
+    for (int64_t j = 0; j < k; ++j) {
+        const int64_t i = rows.idx[(size_t)j], o = s.h_tick_off[(size_t)i], nt = s.h_tick_off[(size_t)i + 1] - o;
+        const double cp = u.price[rows.src[(size_t)j]];
+        const int64_t ct = univ3_current_tick(s.h_lt.data() + o, nt, cp);   // (>= 1: validated)
+        univ3_prepare_pool(cp, s.h_gamma[(size_t)i], ct, nt, s.h_lt.data() + o, s.h_liq.data() + o, rec[(size_t)j], ticks);
+        fast = fast && in_fast_window(cp);
+        lists = lists || rec[(size_t)j].walk.y > 0 || rec[(size_t)j].walk.w > 0;
+    }
+    univ3_all_thresholds(ticks, thr);
+    thr.resize(ticks.size() + 4, 0.0);
+    const int64_t nrec = (int64_t)ticks.size();
+    int rc = univ3_make_room(c, s, nrec);
+    if (rc != CFMM_OK) return rc;
+    // has_walk can only turn on: a segment uploaded without any list (no heads either) gets its heads now, all "never"
+    uint4* new_head = nullptr;
+    if (!s.has_walk && lists) {
+        if (hipMalloc(reinterpret_cast<void**>(&new_head), 2 * (size_t)s.m * sizeof(uint4)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, CFMM_ERR_HIP, "pool update: allocation of the threshold heads failed");
+        }
+    }
+    const size_t words = (size_t)k * (2 + 1 + 2 + 2 + 1 + 2 + 2 + 4 + 1) + (size_t)nrec * 9;
+    if ((rc = staging_reserve(c, words)) != CFMM_OK) {
+        (void)hipFree(new_head);
+        return rc;
+    }
+    if (new_head) {
+        HIP_TRY(c, hipMemsetAsync(new_head, 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
+        s.head = new_head;
+        s.has_walk = 1;
+        c->geometry_dirty = true;   // (the plan reads has_walk: bytes per pool, hence "stream_stores" = auto)
+    }
+    const int base = (int)s.tick_used;
+    Packer p(c);
+    double2* pg = p.add<double2>(s.pg, 2, k);
+    double* cp = p.add<double>(s.cp, 1, k);
+    double2* cur_a = p.add<double2>(s.cur_a, 2, k);
+    double2* cur_b = p.add<double2>(s.cur_b, 2, k);
+    double* cur_c = p.add<double>(s.cur_c, 1, k);
+    double2* curR = p.add<double2>(s.curR, 2, k);
+    int4* walk = p.add<int4>(s.walk, 2, k);
+    uint4* head = s.head ? p.add<uint4>(s.head, 4, k) : nullptr;
+    TickRec* t_out = p.add<TickRec>(s.ticks, 8, nrec, base);
+    double* thr_out = p.add<double>(s.thr, 1, nrec, base);
+    for (int64_t j = 0; j < k; ++j) {
+        const UniV3PoolRec& r = rec[(size_t)j];
+        pg[j] = r.pg;
+        cp[j] = r.pg.x;
+        cur_a[j] = r.cur_a;
+        cur_b[j] = r.cur_b;
+        cur_c[j] = r.cur_c;
+        curR[j] = r.curR;
+        if (head) univ3_heads(r.walk, thr.data(), head + 2 * j);
+        walk[j] = make_int4(r.walk.x + base, r.walk.y, r.walk.z + base, r.walk.w);
+    }
+    std::memcpy(static_cast<void*>(t_out), ticks.data(), (size_t)nrec * sizeof(TickRec));
+    std::memcpy(thr_out, thr.data(), (size_t)nrec * sizeof(double));
+    p.set_rows(rows.idx);
+    if ((rc = launch(c, p)) != CFMM_OK) return rc;
+    for (int64_t j = 0; j < k; ++j) {
+        s.h_cp[(size_t)rows.idx[(size_t)j]] = rec[(size_t)j].pg.x;   // a later cfmm_update_reserves starts from the new prices
+        s.h_walk[(size_t)rows.idx[(size_t)j]] = walk[j];
+    }
+    s.tick_used += nrec;
+    if (!fast) s.fast_ok = 0;
+    return CFMM_OK;
+}
+
+int apply_reserves(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
+{
+    const int64_t k = (int64_t)rows.idx.size(), m = s.m;
+    const bool ragged = ragged_kind(s.kind);
+    const int nc = ragged ? s.n_coins : 2;
+    int rc = staging_reserve(c, (size_t)k * (2 * (size_t)nc + 2 + 1));
+    if (rc != CFMM_OK) return rc;
+    Packer p(c);
+    bool fast = true;
+    if (!ragged) {
+        double2* R = p.add<double2>(s.R, 2, k);
+        double2* Q = s.kind == CFMM_KIND_GEOMEAN ? p.add<double2>(s.lR, 2, k) : nullptr;
+        for (int64_t j = 0; j < k; ++j) {
+            const double* r = u.R + 2 * rows.src[(size_t)j];
+            const size_t i = (size_t)rows.idx[(size_t)j];
+            R[j] = make_double2(r[0], r[1]);
+            fast = fast && in_fast_window(r[0]) && in_fast_window(r[1]);
+            if (Q) Q[j] = geomean_q(s.h_gamma[i], s.h_eta[i], r[0], r[1]);
+        }
+    } else {
+        // coin-major columns: one staging column per coin
+        double *R[kMaxCoins], *q[kMaxCoins];
+        for (int c2 = 0; c2 < nc; ++c2) R[c2] = p.add<double>(s.nc.R + (size_t)c2 * (size_t)m, 1, k);
+        for (int c2 = 0; c2 < nc; ++c2) q[c2] = p.add<double>(s.nc.q + (size_t)c2 * (size_t)m, 1, k);
+        double2* ab = s.kind == CFMM_KIND_CURVE ? p.add<double2>(s.nc.par, 2, k) : nullptr;
+        for (int64_t j = 0; j < k; ++j) {
+            const int64_t src = rows.src[(size_t)j];
+            const double* r = u.R + nc * src;
+            const size_t i = (size_t)rows.idx[(size_t)j];
+            double qq[kMaxCoins], par[2];
+            if (ab) {
+                curve_fill(r, u.alpha[src], u.beta[src], nc, qq, par);
+                ab[j] = make_double2(par[0], par[1]);
+            } else {
+                for (int c2 = 0; c2 < nc; ++c2) qq[c2] = weighted_q(r[c2], s.h_par[(size_t)c2 * (size_t)m + i]);
+            }
+            for (int c2 = 0; c2 < nc; ++c2) {
+                R[c2][j] = r[c2];
+                q[c2][j] = qq[c2];
+            }
+        }
+    }
+    p.set_rows(rows.idx);
+    if ((rc = launch(c, p)) != CFMM_OK) return rc;
+    if (!fast) s.fast_ok = 0;   // (the kinds with one arithmetic have fast_ok = 0 already)
+    return CFMM_OK;
+}
+
+// One validated update on a single-device context
+int apply(cfmm_ctx* c, const Update& u)
+{
+    if (u.count == 0) return CFMM_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    armed_cancel(c);
+    Segment& s = c->segs[(size_t)u.seg];
+    const Rows rows = distinct_rows(u.count, u.idx);
+    const int rc = u.entry == kSetPrices ? apply_univ3(c, s, u, rows) : apply_reserves(c, s, u, rows);
+    if (rc != CFMM_OK) return rc;
+    // as cfmm_update_reserves: the trades and outputs on the device describe the market before the update
+    c->have_trades = false;
+    c->have_out = false;
+    c->x_valid = false;
+    c->trade_v.clear();
+    return CFMM_OK;
+}
+
+// Multi-device parents: the rows split by shard_range, every shard's part checked before any shard changes
+int multi_update(cfmm_ctx* c, const Update& u)
+{
+    int rc = check_args(c, u, (int64_t)c->psegs.size());
+    if (rc != CFMM_OK) return rc;
+    const auto& ps = c->psegs[(size_t)u.seg];
+    if ((rc = check_entry(c, u.entry, ps.kind)) != CFMM_OK || (rc = check_arrays(c, u)) != CFMM_OK) return rc;
+    if (u.count == 0) return CFMM_OK;
+    const int nd = (int)c->shards.size(), nc = ps.n_coins;
+    struct Part {
+        std::vector<int64_t> idx;
+        std::vector<double> R, alpha, beta, price;
+        int64_t lo = 0;
+        Update u{};
+    };
+    std::vector<Part> parts((size_t)nd);
+    std::vector<int64_t> los((size_t)nd), his((size_t)nd);
+    for (int d = 0; d < nd; ++d) shard_range(ps.m, d, nd, los[(size_t)d], his[(size_t)d]);
+    for (int64_t j = 0; j < u.count; ++j) {
+        const int64_t i = u.idx[j];
+        if (i < 0 || i >= ps.m) return fail(c, CFMM_ERR_INVALID_ARG, "pool index %lld out of range [0, %lld)", (long long)i, (long long)ps.m);
+        int d = 0;
+        while (i >= his[(size_t)d]) ++d;
+        Part& p = parts[(size_t)d];
+        p.idx.push_back(i - los[(size_t)d]);
+        if (u.entry == kSetPrices) p.price.push_back(u.price[j]);
+        else p.R.insert(p.R.end(), u.R + j * nc, u.R + (j + 1) * nc);
+        if (u.entry == kSetCurve) {
+            p.alpha.push_back(u.alpha[j]);
+            p.beta.push_back(u.beta[j]);
+        }
+    }
+    for (int d = 0; d < nd; ++d) {
+        Part& p = parts[(size_t)d];
+        p.lo = los[(size_t)d];
+        p.u = Update{u.entry, (int32_t)child_segment(c, u.seg, d), (int64_t)p.idx.size(), p.idx.data(), p.R.data(), p.alpha.data(),
+                     p.beta.data(), p.price.data()};
+        if (p.idx.empty()) continue;
+        cfmm_ctx* child = c->shards[(size_t)d];
+        if ((rc = validate(child, p.u, p.lo)) != CFMM_OK) return fail(c, rc, "%s", child->err.c_str());
+    }
+    for (int d = 0; d < nd; ++d) {
+        Part& p = parts[(size_t)d];
+        if (p.idx.empty()) continue;
+        cfmm_ctx* child = c->shards[(size_t)d];
+        if ((rc = apply(child, p.u)) != CFMM_OK) {
+            c->have_trades = c->have_out = false;   // some shards may have moved
+            return fail(c, rc, "shard %d: %s", d, child->err.c_str());
+        }
+    }
+    c->have_trades = c->have_out = false;
+    return CFMM_OK;
+}
+
+int update(cfmm_ctx* c, const Update& u)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (!c->shards.empty()) return multi_update(c, u);
+    const int rc = validate(c, u, 0);
+    return rc != CFMM_OK ? rc : apply(c, u);
+}
+
+} // namespace
+
+extern "C" {
+
+int cfmm_pools_set_reserves(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* R)
+{
+    return update(c, Update{kSetReserves, seg, count, idx, R, nullptr, nullptr, nullptr});
+}
+
+int cfmm_pools_set_curve(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* R, const double* alpha,
+                         const double* beta)
+{
+    return update(c, Update{kSetCurve, seg, count, idx, R, alpha, beta, nullptr});
+}
+
+int cfmm_pools_set_prices(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* current_price)
+{
+    return update(c, Update{kSetPrices, seg, count, idx, nullptr, nullptr, nullptr, current_price});
+}
+
+} // extern "C"

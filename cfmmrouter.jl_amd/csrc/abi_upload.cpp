@@ -3,7 +3,7 @@
 // the packed fee + token records, and the v-independent constants of the GeometricMean / UniV3 closed forms,
 // prepared once on the host with the same IEEE operations the reference applies per sweep.
 #include "ctx.h"
-#include "curve_pool.h"
+#include "pool_checks.h"
 
 #include <algorithm>
 #include <cmath>
@@ -12,17 +12,6 @@
 using namespace cfmm;
 
 namespace {
-
-bool finite_pos(double x) { return std::isfinite(x) && x > 0.0; }
-
-// |x| in [2^-kFastExp, 2^kFastExp]: the operand window of the sweep's fast division / square root (sweep.h)
-bool in_fast_window(double x)
-{
-    uint64_t bits;
-    std::memcpy(&bits, &x, sizeof bits);
-    const int e = (int)((bits >> 52) & 0x7ff);
-    return e >= 1023 - kFastExp && e <= 1023 + kFastExp;
-}
 
 // Packed fee + token record of a segment (sweep.h PackedFeeTok): {i1 | i2 << 16, index of the pool's fee among the
 // segment's distinct fees}.  Built for every segment outside large-market mode (token ids fit 16 bits there); a segment
@@ -75,8 +64,8 @@ int check_two_coin(cfmm_ctx* c, int64_t m, const double* R, const double* gamma,
     if (m < 0) return fail(c, CFMM_ERR_INVALID_ARG, "negative pool count");
     if (m > 0 && (!R || !gamma || !Ai)) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
     for (int64_t i = 0; i < m; ++i) {
-        if (!finite_pos(R[2 * i]) || !finite_pos(R[2 * i + 1]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
+        const int rc = check_reserves(c, i, R + 2 * i, 2);
+        if (rc != CFMM_OK) return rc;
         if (!finite_pos(gamma[i]))
             return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
         const int32_t a = Ai[2 * i], b = Ai[2 * i + 1];
@@ -86,58 +75,6 @@ int check_two_coin(cfmm_ctx* c, int64_t m, const double* R, const double* gamma,
             return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the two token indices must differ", (long long)i);
     }
     return CFMM_OK;
-}
-
-// Largest price P for which find_arb_pos (src/cfmms.jl:321-337) DRAINS a tick with the prepared constants k, s_in = R_in + α,
-// δmax: dd = sqrt(k/P) − s_in is > 0 and >= δmax.  The test is monotone in P (IEEE division, square root and subtraction are
-// correctly rounded, hence monotone), so there is exactly one such double; it is found on the test ITSELF -- gallop from the
-// algebraic boundary k/(s_in + δmax)², then bisect on the bit patterns -- so that `price <= T` on the device is the
-// reference's floating-point decision, not an approximation of it.  0: the tick never drains for a positive price.
-double drain_threshold(double k, double s_in, double dmax)
-{
-    auto drains = [&](double P) {
-        const double dd = std::sqrt(k / P) - s_in;
-        return dd > 0 && dd >= dmax;
-    };
-    auto bits = [](double x) { int64_t b; std::memcpy(&b, &x, sizeof b); return b; };
-    auto from = [](int64_t b) { double x; std::memcpy(&x, &b, sizeof x); return x; };
-    const int64_t lo_lim = bits(0x1p-1000), hi_lim = bits(0x1p1000);
-    double c0 = k / ((s_in + dmax) * (s_in + dmax));
-    if (!(c0 > 0x1p-1000)) c0 = 0x1p-1000;     // (also catches NaN)
-    if (!(c0 < 0x1p1000)) c0 = 0x1p1000;
-    int64_t lo, hi;                            // drains(lo), !drains(hi)
-    const int64_t cb = bits(c0);
-    if (drains(c0)) {
-        lo = cb;
-        for (int64_t step = 1;; step *= 2) {
-            const int64_t nb = lo + step;
-            if (nb >= hi_lim) {
-                if (drains(from(hi_lim))) return from(hi_lim);
-                hi = hi_lim;
-                break;
-            }
-            if (!drains(from(nb))) { hi = nb; break; }
-            lo = nb;
-        }
-    } else {
-        hi = cb;
-        for (int64_t step = 1;; step *= 2) {
-            const int64_t nb = hi - step;
-            if (nb <= lo_lim) {
-                if (!drains(from(lo_lim))) return 0.0;
-                lo = lo_lim;
-                break;
-            }
-            if (drains(from(nb))) { lo = nb; break; }
-            hi = nb;
-        }
-    }
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (drains(from(mid))) lo = mid;
-        else hi = mid;
-    }
-    return from(lo);
 }
 
 int add_segment_common(cfmm_ctx* c, Segment&& s, const int32_t* Ai)
@@ -175,7 +112,7 @@ int ncoin_check(cfmm_ctx* c, int kind, int64_t m, int32_t n_coins, const double*
     for (int64_t i = 0; i < m; ++i) {
         for (int k = 0; k < nc; ++k) {
             const size_t j = (size_t)(i * nc + k);
-            if (!finite_pos(R[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves must be finite and > 0", (long long)i);
+            if ((rc = check_reserves(c, i, R + j, 1)) != CFMM_OK) return rc;
             if ((rc = coin_ok(i, j)) != CFMM_OK) return rc;
             const int32_t a = Ai[j];
             if (a < 0 || a >= c->n)
@@ -223,6 +160,7 @@ int ncoin_add(cfmm_ctx* c, int kind, int64_t m, int nc, const double* R, const d
     s.m = m;
     s.n_coins = nc;
     s.fast_ok = 0;   // one arithmetic only (the compiler's)
+    if (kind == CFMM_KIND_WEIGHTED) s.h_par = cpar;   // the normalised weights q is prepared from (cfmm_pools_set_reserves)
     int rc;
     if ((rc = upload(c, &s.nc.R, cR.data(), cells)) || (rc = upload(c, &s.nc.q, cq.data(), cells)) ||
         (rc = upload(c, &s.nc.tok, ct.data(), cells)) || (rc = upload(c, &s.nc.par, cpar.data(), cpar.size())) ||
@@ -271,8 +209,8 @@ int univ3_build(cfmm_ctx* c, Segment& s, int64_t m, const double* current_price,
     for (int64_t i = 0; i < m; ++i) {
         const int64_t o = tick_off[i], nt = tick_off[i + 1] - o;
         if (nt < 1) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: needs at least one tick", (long long)i);
-        if (!finite_pos(current_price[i]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: current_price must be finite and > 0", (long long)i);
+        int rc = check_univ3_price(c, i, current_price[i]);
+        if (rc != CFMM_OK) return rc;
         if (!finite_pos(gamma[i]))
             return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: fee gamma must be finite and > 0", (long long)i);
         const int32_t a = Ai[2 * i], b = Ai[2 * i + 1];
@@ -291,130 +229,36 @@ int univ3_build(cfmm_ctx* c, Segment& s, int64_t m, const double* current_price,
         const double cp = current_price[i];
         fast = fast && in_fast_window(cp) && in_fast_window(gamma[i]);
         for (int64_t j = 0; j < nt; ++j) fast = fast && (lq[j] == 0.0 || in_fast_window(lq[j]));
-        // src/cfmms.jl:235: searchsortedlast(lower_ticks, current_price, rev=true)
-        int64_t lo = 0, hi = nt + 1;
-        while (lo < hi - 1) {
-            const int64_t mid = lo + ((hi - lo) >> 1);
-            if (lt[mid - 1] < cp) hi = mid;
-            else lo = mid;
-        }
-        const int64_t ct = lo;
-        if (ct < 1)
-            return fail(c, CFMM_ERR_INVALID_ARG,
-                        "pool %lld: current_price above the first tick (the reference would index tick 0)", (long long)i);
-        // compute_at_tick(cfmm, idx), src/cfmms.jl:294-313 (idx 1-based)
-        auto at_tick = [&](int64_t idx, double& k, double& al, double& be, double& R1, double& R2) {
-            k = lq[idx - 1];
-            const double pplus = lt[idx - 1];                 // :251
-            const double pminus = idx < nt ? lt[idx] : 0.0;   // :254-259
-            al = std::sqrt(k / pplus);
-            be = std::sqrt(k * pminus);
-            const double p = idx > ct ? pplus : (idx < ct ? pminus : cp);
-            R1 = std::sqrt(k / p) - al;
-            R2 = std::sqrt(k * p) - be;
-        };
-        {   // the current tick, shared by both walks
-            double k, al, be, R1, R2;
-            at_tick(ct, k, al, be, R1, R2);
-            const double sA = R1 + al, sB = R2 + be;
-            cur_a[(size_t)i] = make_double2(k, sA);
-            cur_b[(size_t)i] = make_double2(sB, k / be - sA);   // :329
-            cur_c[(size_t)i] = k / al - sB;                     // :329 on the flipped pool (:289)
-            curR[(size_t)i] = make_double2(R1, R2);
-            if (k == 0) { cur_b[(size_t)i].y = 0.0; cur_c[(size_t)i] = 0.0; } // 0/0: never read (k == 0 is skipped)
-        }
-        // Walk lists (UniV3Ops::solve_dir): the non-empty ticks beyond the current one, in walk order; every record also
-        // carries the sums of the drained ticks BEFORE it, starting from what the current tick contributes when it drains
-        // ({δmax, R_out}; nothing if it is empty) and accumulated with the walk's own additions; one closing record per
-        // list carries the sums of the whole list.
-        double kc, alc, bec, R1c, R2c;
-        at_tick(ct, kc, alc, bec, R1c, R2c);
-        int4 w;
-        w.x = (int)ticks.size();
-        int cnt = 0;
-        double2 run = kc != 0 ? make_double2(cur_b[(size_t)i].y, R2c) : make_double2(0.0, 0.0);   // price falling: δmax↑, R₂ out
-        for (int64_t idx = ct + 1; idx <= nt; ++idx) {        // get_upper_pools beyond the current tick, :316
-            double k, al, be, R1, R2;
-            at_tick(idx, k, al, be, R1, R2);
-            if (k == 0) continue;                             // is_empty_pool, :288
-            const double s_in = R1 + al, dmax = k / be - s_in;
-            ticks.push_back(TickRec{make_double2(k, s_in), make_double2(dmax, R2 + be), R2, 0.0, run});   // :329, :334
-            run.x += dmax;
-            run.y += R2;
-            ++cnt;
-        }
-        ticks.push_back(TickRec{make_double2(0.0, 0.0), make_double2(0.0, 0.0), 0.0, 1.0, run});           // closing record (pad = 1 marks it)
-        w.y = cnt;
-        w.z = (int)ticks.size();
-        cnt = 0;
-        run = kc != 0 ? make_double2(cur_c[(size_t)i], R1c) : make_double2(0.0, 0.0);                      // price rising (flipped pool, :289)
-        for (int64_t idx = ct - 1; idx >= 1; --idx) {         // flip_sides.(get_lower_pools), :317,:289
-            double k, al, be, R1, R2;
-            at_tick(idx, k, al, be, R1, R2);
-            if (k == 0) continue;
-            const double s_in = R2 + be, dmax = k / al - s_in;
-            ticks.push_back(TickRec{make_double2(k, s_in), make_double2(dmax, R1 + al), R1, 0.0, run});
-            run.x += dmax;
-            run.y += R1;
-            ++cnt;
-        }
-        ticks.push_back(TickRec{make_double2(0.0, 0.0), make_double2(0.0, 0.0), 0.0, 1.0, run});
-        w.w = cnt;
-        longest = std::max(longest, std::max(w.y, w.w));
-        walk[(size_t)i] = w;
-        pg[(size_t)i] = make_double2(cp, gamma[i]);
+        int64_t ct;
+        if ((rc = check_univ3_tick(c, i, lt, nt, cp, ct)) != CFMM_OK) return rc;
+        UniV3PoolRec rec;
+        univ3_prepare_pool(cp, gamma[i], ct, nt, lt, lq, rec, ticks);   // (univ3_pool.h: both lists appended to `ticks`)
+        cur_a[(size_t)i] = rec.cur_a;
+        cur_b[(size_t)i] = rec.cur_b;
+        cur_c[(size_t)i] = rec.cur_c;
+        curR[(size_t)i] = rec.curR;
+        longest = std::max(longest, std::max(rec.walk.y, rec.walk.w));
+        walk[(size_t)i] = rec.walk;
+        pg[(size_t)i] = rec.pg;
     }
     HIP_TRY(c, hipSetDevice(c->device));
     s.kind = CFMM_KIND_UNIV3;
     s.m = m;
     s.n_ticks_total = T;
-    // drain thresholds of all records (the closing records and ticks that end the walk when reached -- δmax = 0 or R_out = 0,
-    // :363-365 -- get 0 = "never"), a few bisection steps each: spread over the host's cores
-    std::vector<double> thr(ticks.size(), 0.0);
-    {
-        const size_t nrec = ticks.size();
-        const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        const unsigned nthr = nrec > 65536 ? hw : 1;
-        auto work = [&](size_t lo, size_t hi) {
-            for (size_t e = lo; e < hi; ++e) {
-                const TickRec& r = ticks[e];
-                if (r.thr != 0.0 || r.dt.x == 0.0 || r.rout == 0.0) continue;   // (thr == 1 marks a closing record until here)
-                thr[e] = drain_threshold(r.ks.x, r.ks.y, r.dt.x);
-            }
-        };
-        std::vector<std::thread> pool;
-        for (unsigned t = 1; t < nthr; ++t) pool.emplace_back(work, nrec * t / nthr, nrec * (t + 1) / nthr);
-        work(0, nrec / nthr);
-        for (auto& th : pool) th.join();
-    }
-    for (size_t e = 0; e < ticks.size(); ++e) ticks[e].thr = thr[e];   // every record carries its own threshold (closing records: 0)
+    // drain thresholds of all records; every record also carries its own (univ3_pool.h)
+    std::vector<double> thr;
+    univ3_all_thresholds(ticks, thr);
     thr.resize(ticks.size() + 4, 0.0);   // the scan reads four thresholds at a time
     s.has_walk = longest > 0 ? 1 : 0;
     // threshold heads (sweep.h UniV3Pools::head): the first four thresholds of both lists of every pool as floats rounded DOWN
     std::vector<uint4> head;
     if (s.has_walk) {
         head.resize(2 * (size_t)m);
-        const auto enc = [](double T) -> unsigned {
-            if (T == 0.0) return 0u;                                   // never drains (also: closing record, past the list)
-            if (!(T >= 0x1p-120 && T <= 0x1p120)) return 0x7fc00000u;   // outside the comfortable binary32 range: NaN = "ask thr[]"
-            float f = (float)T;
-            if ((double)f > T) f = std::nextafterf(f, 0.0f);           // round toward zero = down (T > 0)
-            unsigned b;
-            std::memcpy(&b, &f, sizeof b);
-            return b;
-        };
-        for (int64_t i = 0; i < m; ++i) {
-            const int4 w = walk[(size_t)i];
-            unsigned h[8];
-            for (int k = 0; k < 4; ++k) {
-                h[k] = k < w.y ? enc(thr[(size_t)w.x + k]) : 0u;       // beyond the list: the closing record's "never"
-                h[4 + k] = k < w.w ? enc(thr[(size_t)w.z + k]) : 0u;
-            }
-            head[2 * (size_t)i] = make_uint4(h[0], h[1], h[2], h[3]);
-            head[2 * (size_t)i + 1] = make_uint4(h[4], h[5], h[6], h[7]);
-        }
+        for (int64_t i = 0; i < m; ++i) univ3_heads(walk[(size_t)i], thr.data(), &head[2 * (size_t)i]);
     }
     s.fast_ok = fast ? 1 : 0;
+    s.tick_used = s.tick_cap = (int64_t)ticks.size();   // no spare records: the first price update that needs some regrows (abi_update.cpp)
+    s.h_walk = walk;
     int rc;
     if ((rc = upload(c, &s.pg, pg.data(), (size_t)m)) || (rc = upload(c, &s.Ai, Ai, (size_t)m)) ||
         (rc = upload(c, &s.cur_a, cur_a.data(), (size_t)m)) || (rc = upload(c, &s.cur_b, cur_b.data(), (size_t)m)) ||
@@ -466,10 +310,7 @@ int cfmm_pools_add_solidly(cfmm_ctx* c, int64_t m, const double* R, const double
             return fail(c, CFMM_ERR_INVALID_ARG,
                         "pool %lld: fee gamma must be <= 1 (gamma > 1 pays for round trips: the arbitrage problem is unbounded)",
                         (long long)i);
-        // the closed form cubes R2/R1 (SolidlyOps): 2^±300 cubed is finite, anything wider need not be
-        if (!in_fast_window(R[2 * i]) || !in_fast_window(R[2 * i + 1]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: reserves of a Solidly stable pair must lie within [2^-%d, 2^%d]",
-                        (long long)i, kFastExp, kFastExp);
+        if ((rc = check_solidly_range(c, i, R + 2 * i)) != CFMM_OK) return rc;
     }
     if (!c->shards.empty())
         return multi_add(c, CFMM_KIND_SOLIDLY, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
@@ -509,15 +350,16 @@ int cfmm_pools_add_geomean(cfmm_ctx* c, int64_t m, const double* R, const double
     for (int64_t i = 0; i < m; ++i) {
         const double e = w[2 * i] / w[2 * i + 1]; // src/cfmms.jl:188
         fast = fast && in_fast_window(R[2 * i]) && in_fast_window(R[2 * i + 1]) && in_fast_window(gamma[i]) && in_fast_window(e);
-        const double lg = std::log(gamma[i]), le = std::log(e), l1 = std::log(R[2 * i]), l2 = std::log(R[2 * i + 1]);
         etas[(size_t)i] = e;
-        lR[(size_t)i] = make_double2(((lg + le) + l2) + e * l1, e * ((lg + l1) - le) + l2);   // {Q1, Q2}
+        lR[(size_t)i] = geomean_q(gamma[i], e, R[2 * i], R[2 * i + 1]);   // {Q1, Q2}
     }
     HIP_TRY(c, hipSetDevice(c->device));
     Segment s;
     s.kind = CFMM_KIND_GEOMEAN;
     s.m = m;
     s.fast_ok = fast ? 1 : 0;
+    s.h_gamma.assign(gamma, gamma + m);   // host copies of what {Q1, Q2} are prepared from besides R (cfmm_pools_set_reserves)
+    s.h_eta = etas;
     if ((rc = upload(c, &s.eta, etas.data(), (size_t)m)) || (rc = upload(c, &s.lR, lR.data(), (size_t)m)) ||
         (rc = upload(c, &s.R, R, (size_t)m)) || (rc = upload(c, &s.w, w, (size_t)m)) ||
         (rc = upload(c, &s.gamma, gamma, (size_t)m)) || (rc = upload(c, &s.Ai, Ai, (size_t)m)) ||
@@ -582,7 +424,7 @@ int cfmm_pools_add_weighted(cfmm_ctx* c, int64_t m, int32_t n_coins, const doubl
         for (int k = 0; k < nc; ++k) {
             const size_t src = (size_t)(i * nc + k);
             wn[k] = w[src] / ws;
-            q[k] = std::log(R[src] / wn[k]);
+            q[k] = weighted_q(R[src], wn[k]);
         }
     });
 }
@@ -591,20 +433,7 @@ int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* 
                          const double* alpha, const double* beta)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    const auto ab_ok = [&](int64_t i) {
-        if (!std::isfinite(alpha[i]) || alpha[i] < 0.0)
-            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: alpha must be finite and >= 0", (long long)i);
-        if (!finite_pos(beta[i])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: beta must be finite and > 0", (long long)i);
-        if (alpha[i] > 0.0) {
-            double rho[kMaxCoins];
-            for (int k = 0; k < n_coins; ++k) rho[k] = std::log(R[(size_t)(i * n_coins + k)]);
-            if (!cfmm::curve_in_range(std::log(beta[i]), rho, n_coins))
-                return fail(c, CFMM_ERR_INVALID_ARG,
-                            "pool %lld: log(P0/R_k) = log(beta) - sum log R - log R_k must lie within +-%g when alpha > 0",
-                            (long long)i, cfmm::kCurveLogRange);
-        }
-        return CFMM_OK;
-    };
+    const auto ab_ok = [&](int64_t i) { return check_curve_params(c, i, alpha[i], beta[i], R + i * n_coins, n_coins); };
     int rc = ncoin_check(c, CFMM_KIND_CURVE, m, n_coins, R, gamma, Ai, R && gamma && Ai && alpha && beta,
                          [](int64_t, size_t) { return CFMM_OK; }, ab_ok);
     if (rc != CFMM_OK) return rc;
@@ -615,9 +444,7 @@ int cfmm_pools_add_curve(cfmm_ctx* c, int64_t m, int32_t n_coins, const double* 
         }, nc);
     // q = log R; per pool {α, log β} (curve_solve_lbeta: at α = 0, one that keeps P₀/R_k inside the solve's range)
     return ncoin_add(c, CFMM_KIND_CURVE, m, nc, R, gamma, Ai, [&](int64_t i, double* q, double* ab) {
-        for (int k = 0; k < nc; ++k) q[k] = std::log(R[(size_t)(i * nc + k)]);
-        ab[0] = alpha[i];
-        ab[1] = cfmm::curve_solve_lbeta(alpha[i], std::log(beta[i]), q, nc);
+        curve_fill(R + i * nc, alpha[i], beta[i], nc, q, ab);
     });
 }
 

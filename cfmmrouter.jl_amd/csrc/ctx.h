@@ -8,6 +8,7 @@
 //   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold, host-pointer
 //                     sweeps, pre-armed evaluations
 //   abi_trades.cpp    trade download / device views, update_reserves!, reserves / prices read-back
+//   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -61,6 +62,14 @@ struct Segment : SegPlan {   // (SegPlan: the launch geometry, decided by ensure
     // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
     std::vector<double> h_cp, h_gamma, h_lt, h_liq;
     std::vector<int64_t> h_tick_off;
+    // UniV3 only: the walk lists of a pool whose price cfmm_pools_set_prices moves are rewritten at the TAIL of ticks / thr
+    // (abi_update.cpp): records in use (garbage of moved pools included) and allocated (thr: + 4 of read-ahead), and the host
+    // copy of `walk` a compaction rebuilds the arrays from
+    int64_t tick_used = 0, tick_cap = 0;
+    std::vector<int4> h_walk;
+    // host copies of the pool constants that cfmm_pools_set_reserves prepares q / {Q1, Q2} from besides the new reserves:
+    // GeometricMeanTwoCoin h_gamma (above) and η, weighted the normalised weights ([n_coins][m] like nc.par)
+    std::vector<double> h_eta, h_par;
     // N-coin kinds (KindInfo::ragged: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE) only: the coin-major columns and the segment's own
     // trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
     int n_coins = 2;
@@ -238,6 +247,15 @@ struct cfmm_ctx {
     int64_t opt_debug_stall_ms = 0; // test hook, reachable only in libcfmm_amd_hooks.so (-DCFMM_TEST_HOOKS: the option key and the stall
                                     //    exist there alone; the FIELD is unconditional so that every translation unit sees one layout)
     uint64_t sweep_count = 0;
+
+    // sparse pool-state updates (abi_update.cpp, cfmm_pools_set_*): pinned + device-mapped staging of the prepared records, grown
+    // geometrically; upd_done marks the end of the latest scatter launch (the staging is reused only after it)
+    void* h_upd = nullptr;
+    void* d_upd = nullptr;        // device address of h_upd
+    size_t upd_cap = 0;           // bytes
+    hipEvent_t upd_done = nullptr;
+    bool upd_busy = false;
+    int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
 
     // kernel timing
     std::vector<hipEvent_t> ev_pool;

@@ -271,6 +271,28 @@ hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pi
 hipError_t launch_update_two_coin(double2* R, const double* gamma, const double2* Delta, const double2* Lambda,
                                   const double2* Over, int compact, double2* Q, const double* eta, int64_t m, int* left_window,
                                   hipStream_t s);
+// Sparse pool-state updates (cfmm_pools_set_*, abi_update.cpp): one launch scatters the host-prepared records of `count` pools
+// into every affected column of ONE segment.  The staging buffer (device-visible, 8-byte words) holds the columns one after
+// the other, column c as rows x width words from word `begin`; row j of a column goes to row idx[j] of the column's device
+// array (dst, `width` words per row) -- or, for a column appended to an array (UniV3 walk records and thresholds at the
+// tail), to row dense_base + j.  Coin-major columns ([n_coins][m]) are n_coins columns of width 1.  The host has checked
+// every idx and the tail's capacity.
+constexpr int kMaxScatterCols = 2 * kMaxCoins + 2;
+struct ScatterCol {
+    unsigned long long* dst;
+    long long begin;             // first word of the column in the staging buffer (columns in ascending order; gaps allowed)
+    long long rows;
+    long long dense_base;        // >= 0: the column's rows are dense_base + j, not idx[j]
+    int width;                   // 8-byte words per row
+};
+struct ScatterArgs {
+    const unsigned long long* stage;
+    const long long* idx;        // [count] rows within the segment, distinct (staging)
+    long long total;             // words of all columns together
+    int ncols;
+    ScatterCol col[kMaxScatterCols];
+};
+hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s);
 // compact trade records -> full {Δ₁, Δ₂} / {Λ₁, Λ₂} arrays (cfmm_trades_dev, cfmm_get_trades*)
 hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const double2* ovB, double2* Delta, double2* Lambda,
                                 int64_t m, hipStream_t s);

@@ -1934,6 +1934,29 @@ hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const do
     return hipGetLastError();
 }
 
+// Sparse pool-state updates (sweep.h ScatterArgs): one lane moves one 8-byte word of one (pool, column) from the staging
+// buffer -- read as one contiguous stream -- to the pool's row of the column; the rows are sorted by the host, so the words of
+// neighbouring pools land in the same 128-byte lines where the update is dense.  Plain vector stores.
+__global__ __launch_bounds__(256) void scatter_records(ScatterArgs a)
+{
+    const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (g >= a.total) return;
+    int c = 0;
+    for (int k = 1; k < a.ncols; ++k) c = g >= a.col[k].begin ? k : c;   // (columns in staging order)
+    const ScatterCol col = a.col[c];
+    const long long local = g - col.begin, j = local / col.width, t = local - j * col.width;
+    if (j >= col.rows) return;                                            // (a gap between two columns)
+    const long long row = col.dense_base >= 0 ? col.dense_base + j : a.idx[j];
+    col.dst[row * col.width + t] = a.stage[g];
+}
+
+hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s)
+{
+    if (a.total <= 0) return hipSuccess;
+    hipLaunchKernelGGL(scatter_records, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pitch, double* out, hipStream_t s, const PeerSet& ps,
                                 hipEvent_t e0, hipEvent_t e1)
 {

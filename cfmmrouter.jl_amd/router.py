@@ -23,7 +23,7 @@ import numpy as np
 
 from . import objectives as _obj
 from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
-from .cfmms import CFMM, PoolBatch, _upload
+from .cfmms import CFMM, PoolBatch, _set_pool_state, _upload
 
 
 _BOXED_INF = 1e100   # stands in for the reference's u = Inf under nbd = 2 (see route_)
@@ -629,6 +629,74 @@ def update_reserves_(r: Router, sync_host=True):
                     else:
                         pool.R[:] = b.R[k]
     r._zero_trades()
+    r._psi = np.zeros(r.n_tokens)
+    r._acc = 0.0
+    r._trades_stale = False
+    return None
+
+
+def update_pools_(r: Router, changes):
+    """New state for a few pools of a router, on the host mirror AND on the device, without re-uploading the market -- the
+    reference's `r.cfmms[i].R .= ...` followed by another route! (there the pools ARE the router's state).
+
+    `changes` maps positions in `r.cfmms` to new state: a reserve vector (ProductTwoCoin, GeometricMeanTwoCoin, Solidly,
+    weighted pools), `(R, α, β)` (Curve), a price (UniV3; ticks and liquidity stay).  The pools are grouped by device segment;
+    each segment's rows go through one cfmm_pools_set_* call, which checks all of them before anything changes (a refused
+    segment is left as it was, and so are the segments after it).  Host-evaluated plugin pools (their own find_arb_) are
+    updated on the host only: `pool.set_state_(state)` if the type defines it, else `pool.R[:] = state`.  The router's trades
+    are those of the old market: they are zeroed, as by update_reserves_."""
+    m_all = r._m + len(r._host_idx)
+    pos_of = {int(i): k for k, i in enumerate(r._order)} if r._order is not None else None
+    host_of = {int(i): j for j, i in enumerate(r._host_idx)}
+    offsets = np.cumsum([0] + [len(b) for b in r._batches])
+    per_batch, host = {}, []
+    for i, state in changes.items():
+        i = int(i)
+        if not 0 <= i < m_all:
+            raise ArgumentError(f"pool {i} out of range 0:{m_all - 1}")
+        if i in host_of:
+            host.append((r._host.pools[host_of[i]], state))
+            continue
+        k = pos_of[i] if pos_of is not None else i
+        b = int(np.searchsorted(offsets, k, side="right") - 1)
+        rows, states, where = per_batch.setdefault(b, ([], [], []))
+        rows.append(k - int(offsets[b]))
+        states.append(state)
+        where.append(i)
+    ctx = getattr(r._backend, "ctx", None)
+    seg_of, seg = {}, 0
+    for b, batch in enumerate(r._batches):   # (an empty batch has no device segment)
+        if len(batch):
+            seg_of[b] = seg
+            seg += 1
+    for b in sorted(per_batch):
+        rows, states, where = per_batch[b]
+        batch = r._batches[b]
+        _set_pool_state(ctx, seg_of[b], batch, rows, states)
+        if isinstance(r.cfmms, list):                     # keep the per-pool objects in step
+            for i, row in zip(where, rows):
+                pool = r.cfmms[i]
+                if batch.kind == KIND_UNIV3:
+                    pool.current_price = float(batch.current_price[row])
+                    pool.current_tick = int(np.count_nonzero(pool.lower_ticks >= pool.current_price))
+                else:
+                    pool.R[:] = batch.R[row]
+                    if batch.kind == KIND_CURVE:
+                        pool.α, pool.β = float(batch.α[row]), float(batch.β[row])
+    if ctx is None and per_batch:   # test-injected backends: the only door is a reload
+        getattr(r._backend, "inner", r._backend).reload(r._batches)
+    for pool, state in host:
+        if callable(getattr(pool, "set_state_", None)):
+            pool.set_state_(state)
+        elif hasattr(pool, "R"):
+            pool.R[:] = np.asarray(state, dtype=np.float64)
+        else:
+            raise ArgumentError(f"{type(pool).__name__} has neither set_state_(state) nor an R field")
+    r._zero_trades()
+    if r._host is not None:
+        for D, L in zip(r._host.Δs, r._host.Λs):
+            D[:] = 0.0
+            L[:] = 0.0
     r._psi = np.zeros(r.n_tokens)
     r._acc = 0.0
     r._trades_stale = False

@@ -254,6 +254,40 @@ int cfmm_update_reserves(cfmm_ctx* ctx);
 int cfmm_get_reserves(cfmm_ctx* ctx, int32_t seg, double* R);
 int cfmm_get_prices(cfmm_ctx* ctx, int32_t seg, double* current_price);
 
+/* Sparse pool-state updates: the reference's `cfmm.R .= ...` (or a new `current_price`) on a few pools of a router,
+ * followed by another route! -- what a router that follows a chain does every block.  The new state of `count` pools of
+ * ONE segment replaces the old one on the device; everything else of the market (tokens, fees, weights, tick ladders,
+ * the launch plan, fee tables, packed records, large-market incidence lists) stays as uploaded, and nothing is re-uploaded.
+ *   seg   segment index as in cfmm_segment_info / cfmm_get_reserves; idx[0..count) rows within it, in any order.  A row
+ *         named more than once takes the value of its LAST occurrence (decided on the host).  count == 0: a no-op.
+ *   cfmm_pools_set_reserves  ProductTwoCoin, GeometricMeanTwoCoin, Solidly and weighted segments: R[count][n_coins]
+ *   cfmm_pools_set_curve     Curve segments: R[count][n_coins] with the pools' alpha[count], beta[count] (A ramps; D, hence
+ *                            beta, moves with liquidity and fees)
+ *   cfmm_pools_set_prices    UniV3 segments: current_price[count]; ticks and liquidity stay (a mint / burn is a re-add)
+ * The entry that does not fit the segment's kind returns CFMM_ERR_INVALID_ARG and names the one that does; so does a seg or
+ * an idx out of range.
+ * Checks: those of the matching cfmm_pools_add_*, in its order and with its error texts (the pool number is the row), on
+ * the values given: reserves finite and > 0; Solidly reserves within [2^-150, 2^150]; Curve alpha >= 0, beta > 0 and, with
+ * alpha > 0, log(P0/R_k) within the solve's range; a price finite, > 0 and not above the pool's first tick.  ALL rows are
+ * checked before anything changes: a refused call leaves the context exactly as it was.
+ * Prepared constants (GeometricMean {Q1, Q2}, weighted log(R / w), Curve log R and {alpha, log beta}, every UniV3 record:
+ * current-tick constants, walk lists with their running sums, drain thresholds, heads) are computed ON THE HOST with the
+ * upload's own code, so an updated context equals, bit for bit on every output, a context freshly uploaded with the new
+ * state (cfmm_update_reserves, whose logarithms run on the device, promises no such thing).
+ * A value outside [2^-150, 2^150] sends a Product / GeometricMean / UniV3 segment to the full-range arithmetic (same bits),
+ * as cfmm_update_reserves does; an update never sends it back: only cfmm_pools_clear + a re-add does.
+ * The update is enqueued on the context's stream behind earlier sweeps; the trades and outputs of earlier sweeps are
+ * invalidated as by cfmm_update_reserves (cfmm_get_trades then fails with "no materialised trades" until the next
+ * cfmm_find_arb / cfmm_route).  The walk lists of a moved UniV3 pool are appended to the segment's record arrays, whose
+ * spare room is grown geometrically and compacted when it runs out (one stream synchronisation and a re-upload of the
+ * segment's records; counted by the read-only option "pool_update_regrows").
+ * Multi-device contexts: the rows are split over the shards; every shard checks its rows before any shard changes.
+ * Limits: not for adding or removing pools, nor for tokens, fees, weights or tick ladders (cfmm_pools_clear + re-add). */
+int cfmm_pools_set_reserves(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* R);
+int cfmm_pools_set_curve(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* R,
+                         const double* alpha, const double* beta);
+int cfmm_pools_set_prices(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* current_price);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

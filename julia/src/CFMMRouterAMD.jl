@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
 
-export AMDRouter, route_native!, polish!, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -267,6 +267,78 @@ function route!(r::AMDRouter; v=nothing, verbose=false, m=5, factr=1e1, pgtol=1e
                         maxfun=maxfun, maxiter=maxiter)
     r.v .= vopt
     find_arb!(r, vopt)                                          # src/router.jl:107
+end
+
+# update_pools!(r, changes): new state for a few pools WITHOUT re-uploading the market -- the reference's `cfmm.R .= ...` on some
+# pools followed by another route!.  `changes` maps positions in r.cfmms to a reserve vector (two-coin and weighted pools),
+# a tuple (R, α, β) (Curve) or a price (UniV3; ticks and liquidity stay).  The pools are grouped by device segment; every
+# segment's rows go through one cfmm_pools_set_* call, which checks all of them before anything changes.  The host-side pool
+# objects follow.  Host-evaluated pool types are updated on the host only (their R).
+function update_pools!(r::AMDRouter, changes::AbstractDict)
+    segs = Dict{Int32,Vector{Tuple{Int64,Int,Any}}}()     # segment => (row, router index, state)
+    seg, pos = Int32(0), 0
+    groups = Vector{Vector{Int}}()
+    for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3, SolidlyStableTwoCoin)
+        idx = [i for i in r.order[pos+1:end] if r.cfmms[i] isa T]   # r.order is grouped by family
+        isempty(idx) && continue
+        push!(groups, idx); pos += length(idx)
+    end
+    for curve in (false, true), n in 2:8
+        idx = [i for i in r.order[pos+1:end] if (curve ? r.cfmms[i] isa Curve :
+                                                 (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product)) &&
+                                                length(r.cfmms[i].Ai) == n]
+        isempty(idx) && continue
+        push!(groups, idx); pos += length(idx)
+    end
+    where = Dict{Int,Tuple{Int32,Int64}}()
+    for (s, idx) in enumerate(groups), (k, i) in enumerate(idx)
+        where[i] = (Int32(s - 1), Int64(k - 1))
+    end
+    for (i, state) in changes
+        if i in r.host
+            r.cfmms[i].R .= state
+            continue
+        end
+        haskey(where, i) || throw(ArgumentError("pool $i out of range"))
+        s, row = where[i]
+        push!(get!(segs, s, Tuple{Int64,Int,Any}[]), (row, i, state))
+    end
+    for s in sort(collect(keys(segs)))
+        items = segs[s]
+        idx = Int64[t[1] for t in items]
+        c1 = r.cfmms[items[1][2]]
+        if c1 isa UniV3
+            p = Float64[Float64(t[3]) for t in items]
+            GC.@preserve idx p check(r.ctx, ccall((:cfmm_pools_set_prices, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}), r.ctx, s, length(idx), idx, p))
+            for (k, t) in enumerate(items)
+                c = r.cfmms[t[2]]
+                r.cfmms[t[2]] = UniV3(p[k], c.lower_ticks, c.liquidity, c.γ, c.Ai)   # re-derives current_tick (:235)
+            end
+        elseif c1 isa Curve
+            R = reduce(hcat, [Float64.(t[3][1]) for t in items])        # [n_coins, count] column-major = [count][n_coins]
+            α = Float64[Float64(t[3][2]) for t in items]
+            β = Float64[Float64(t[3][3]) for t in items]
+            GC.@preserve idx R α β check(r.ctx, ccall((:cfmm_pools_set_curve, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), r.ctx, s, length(idx), idx, R, α, β))
+            for (k, t) in enumerate(items)
+                c = r.cfmms[t[2]]
+                r.cfmms[t[2]] = Curve(R[:, k], c.γ, c.Ai, α[k], β[k])
+            end
+        else
+            R = reduce(hcat, [Float64.(t[3]) for t in items])
+            GC.@preserve idx R check(r.ctx, ccall((:cfmm_pools_set_reserves, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}), r.ctx, s, length(idx), idx, R))
+            for (k, t) in enumerate(items)
+                r.cfmms[t[2]].R .= @view R[:, k]
+            end
+        end
+    end
+    for i in eachindex(r.Δs)      # the trades are those of the old market
+        r.Δs[i] .= 0
+        r.Λs[i] .= 0
+    end
+    return nothing
 end
 
 # update_reserves!(r) -- src/router.jl:127-132 (upstream calls a per-pool method that exists nowhere).  Here:
