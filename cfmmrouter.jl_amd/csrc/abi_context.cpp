@@ -27,6 +27,34 @@ int fail(const cfmm_ctx* c, int code, const char* fmt, ...)
     return code;
 }
 
+// Every device allocation of the library and its release (DevBuf, devbuf.h).  The hooks build counts the live ones
+// (read-only option "debug_live_allocs"; tests/test_gpu_ownership.py).
+#ifdef CFMM_TEST_HOOKS
+static std::atomic<int64_t> g_live_allocs{0};
+#endif
+
+hipError_t dev_alloc(void** p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        return e;
+    }
+#ifdef CFMM_TEST_HOOKS
+    ++g_live_allocs;
+#endif
+    return e;
+}
+
+void dev_free(void* p)
+{
+    (void)hipFree(p);
+#ifdef CFMM_TEST_HOOKS
+    --g_live_allocs;
+#endif
+}
+
 } // namespace cfmm
 
 extern "C" {
@@ -75,8 +103,7 @@ int cfmm_ctx_create(int device_id, int32_t n_tokens, cfmm_ctx** out)
     } while (0)
     HIP_TRY_C(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     c->stream = c->own_stream;
-    HIP_TRY_C(hipMalloc(reinterpret_cast<void**>(&c->d_v), (size_t)c->n * sizeof(double)));
-    HIP_TRY_C(hipMalloc(reinterpret_cast<void**>(&c->d_out), (size_t)(c->n + 1) * sizeof(double)));
+    if (c->d_v.alloc(c, (size_t)c->n) != CFMM_OK || c->d_out.alloc(c, (size_t)c->n + 1) != CFMM_OK) return bail(CFMM_ERR_HIP);
     // [n] v, [n+1] {psi, acc}, padding to a 128-byte boundary, then the output granules: 16 per fold
     // block = 2 per column, columns padded to a multiple of 8 (see fold_finish)
     c->gran_off = (size_t)((2 * c->n + 2 + 15) & ~15);
@@ -175,20 +202,16 @@ void cfmm_ctx_destroy(cfmm_ctx* c)
     if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
     rccl_release(c);          // a communicator created by cfmm_rccl_init_rank goes with the context
-    for (auto& s : c->segs) free_segment(s);
+    c->segs.clear();
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     free_trade_staging(c);
-    (void)hipFree(c->d_v); (void)hipFree(c->d_out); (void)hipFree(c->d_partials); (void)hipFree(c->d_gtab);
-    (void)hipFree(c->d_delta); (void)hipFree(c->d_lambda); (void)hipFree(c->d_over);
-    (void)hipFree(c->d_xdelta); (void)hipFree(c->d_xlambda);
-    (void)hipFree(c->d_flow); (void)hipFree(c->d_entries); (void)hipFree(c->d_chunks);
-    (void)hipFree(c->d_tok_chunk_off); (void)hipFree(c->d_chunk_sums);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_upd) (void)hipHostFree(c->h_upd);
     if (c->upd_done) (void)hipEventDestroy(c->upd_done);
     if (c->d_arm) (void)hipFree(c->d_arm);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    const hipStream_t own_stream = c->own_stream;
+    delete c;   // the context's DevBufs go here: before the stream, as every release above
+    if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 int cfmm_set_stream(cfmm_ctx* c, void* hip_stream)
@@ -265,6 +288,12 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
         for (const cfmm_ctx* child : c->shards) *value += child->pool_update_regrows;
         return CFMM_OK;
     }
+#ifdef CFMM_TEST_HOOKS
+    if (key && !std::strcmp(key, "debug_live_allocs")) {   // read-only, process-wide: device allocations made and not yet released
+        *value = g_live_allocs.load();
+        return CFMM_OK;
+    }
+#endif
     int64_t* slot = option_slot(const_cast<cfmm_ctx*>(c), key);
     if (!slot) return fail(c, CFMM_ERR_INVALID_ARG, "unknown option '%s'", key ? key : "(null)");
     *value = *slot;

@@ -41,7 +41,6 @@ void pop_last_segment(cfmm_ctx* child)
 {
     (void)hipSetDevice(child->device);
     (void)hipStreamSynchronize(child->stream);
-    free_segment(child->segs.back());
     child->segs.pop_back();
     child->geometry_dirty = true;
     child->have_out = child->have_trades = false;

@@ -36,17 +36,15 @@ int build_incidence(cfmm_ctx* c)
             chunks.push_back(make_int2(b, std::min(b + kGatherChunk, off[(size_t)t + 1])));
         tok_chunk_off[(size_t)t + 1] = (int)chunks.size();
     }
-    (void)hipFree(c->d_flow); (void)hipFree(c->d_entries); (void)hipFree(c->d_chunks);
-    (void)hipFree(c->d_tok_chunk_off); (void)hipFree(c->d_chunk_sums);
-    c->d_flow = nullptr; c->d_entries = nullptr; c->d_chunks = nullptr; c->d_tok_chunk_off = nullptr; c->d_chunk_sums = nullptr;
+    // all five go before the first of the new ones comes (the old and the new incidence never coexist)
+    c->d_flow.reset(); c->d_entries.reset(); c->d_chunks.reset(); c->d_tok_chunk_off.reset(); c->d_chunk_sums.reset();
     c->n_chunks = (int)chunks.size();
     int rc;
-    if ((rc = upload(c, &c->d_entries, entries.data(), entries.size())) ||
-        (rc = upload(c, &c->d_chunks, chunks.data(), chunks.size())) ||
-        (rc = upload(c, &c->d_tok_chunk_off, tok_chunk_off.data(), tok_chunk_off.size())))
+    if ((rc = c->d_entries.upload(c, entries.data(), entries.size())) ||
+        (rc = c->d_chunks.upload(c, chunks.data(), chunks.size())) ||
+        (rc = c->d_tok_chunk_off.upload(c, tok_chunk_off.data(), tok_chunk_off.size())) ||
+        (rc = c->d_flow.alloc(c, (size_t)m)) || (rc = c->d_chunk_sums.alloc(c, chunks.size())))
         return rc;
-    if (m > 0) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_flow), (size_t)m * sizeof(double2)));
-    if (c->n_chunks > 0) HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_chunk_sums), (size_t)c->n_chunks * sizeof(double)));
     return CFMM_OK;
 }
 
@@ -78,7 +76,7 @@ int ensure_geometry(cfmm_ctx* c)
     if (!c->geometry_dirty) return CFMM_OK;
     std::vector<PlanSeg> shapes;
     for (const Segment& s : c->segs)
-        shapes.push_back({s.kind, s.m, s.n_coins, s.n_ticks_total, s.has_walk, s.pk != nullptr, (int)s.gvals.size()});
+        shapes.push_back({s.kind, s.m, s.n_coins, s.n_ticks_total, s.u.has_walk, (bool)s.pk, (int)s.gvals.size()});
     LaunchPlan plan = plan_launches(shapes, c->n, c->geo);
     for (size_t i = 0; i < c->segs.size(); ++i) static_cast<SegPlan&>(c->segs[i]) = plan.segs[i];
     c->groups = std::move(plan.groups);
@@ -97,38 +95,20 @@ int ensure_geometry(cfmm_ctx* c)
             std::copy(sg.gvals.begin(), sg.gvals.end(), tabs.begin() + (std::ptrdiff_t)(gi * kMaxFeeTable + (size_t)sg.gbase));
         }
     }
-    if (tabs.size() > c->gtab_cap) {
-        (void)hipFree(c->d_gtab);
-        c->d_gtab = nullptr;
-        c->gtab_cap = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_gtab), tabs.size() * sizeof(double)));
-        c->gtab_cap = tabs.size();
-    }
+    int rc = c->d_gtab.grow(c, tabs.size());
+    if (rc != CFMM_OK) return rc;
     if (!tabs.empty()) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipMemcpy(c->d_gtab, tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_gtab.get(), tabs.data(), tabs.size() * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (plan.rows > c->rows_cap) {
-        (void)hipFree(c->d_partials);
-        c->d_partials = nullptr;
-        c->rows_cap = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_partials), (size_t)plan.rows * row_width(c) * sizeof(double)));
-        HIP_TRY(c, hipMemset(c->d_partials, 0, (size_t)plan.rows * row_width(c) * sizeof(double)));
-        c->rows_cap = plan.rows;
+    const size_t partials = (size_t)plan.rows * (size_t)row_width(c);
+    if (partials > c->d_partials.size()) {
+        if ((rc = c->d_partials.grow(c, partials)) != CFMM_OK) return rc;
+        HIP_TRY(c, hipMemset(c->d_partials.get(), 0, partials * sizeof(double)));
     }
-    if (plan.trades > c->trade_cap) {   // (two-coin rows only)
-        (void)hipFree(c->d_delta); (void)hipFree(c->d_lambda); (void)hipFree(c->d_over);
-        c->d_delta = c->d_lambda = c->d_over = nullptr;
-        c->trade_cap = 0;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_delta), (size_t)plan.trades * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_lambda), (size_t)plan.trades * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_over), (size_t)plan.trades * sizeof(double2)));
-        c->trade_cap = plan.trades;
-    }
-    if (global_bins(c)) {
-        int rc = build_incidence(c);
-        if (rc != CFMM_OK) return rc;
-    }
+    const size_t trades = (size_t)plan.trades;   // (two-coin rows only)
+    if ((rc = c->d_delta.grow(c, trades)) || (rc = c->d_lambda.grow(c, trades)) || (rc = c->d_over.grow(c, trades))) return rc;
+    if (global_bins(c) && (rc = build_incidence(c)) != CFMM_OK) return rc;
     c->geometry_dirty = false;
     c->have_trades = false;
     c->x_valid = false;
@@ -162,7 +142,7 @@ SweepArgs group_args(const cfmm_ctx* c, const Eval& ev, const Group& g, size_t g
     a.n = c->n;
     a.n_pad = c->n_pad;
     a.v_shift = stage_pairs(c->n, g.block) ? 4 : 3;
-    a.gtab = c->d_gtab ? c->d_gtab + gi * kMaxFeeTable : nullptr;
+    a.gtab = c->d_gtab ? c->d_gtab.get() + gi * kMaxFeeTable : nullptr;
     a.gtab_n = a.gtab ? g.gtab_n : 0;
     for (int k = 0; k < g.nseg && !ev.gb; ++k) {
         const int kind = c->segs[(size_t)g.first + k].kind;
@@ -172,7 +152,7 @@ SweepArgs group_args(const cfmm_ctx* c, const Eval& ev, const Group& g, size_t g
         a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
     a.copies = bin_copies(c->n, c->geo, g.block);
     a.compact = (c->opt_compact_trades != 0 && !ev.gb) ? 1 : 0;
-    a.partials = c->d_partials + (size_t)g.row_off * row_width(c);
+    a.partials = c->d_partials.get() + (size_t)g.row_off * row_width(c);
     a.row_pitch = row_width(c);
     a.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
     a.arm_word = ev.arm.word;
@@ -214,10 +194,10 @@ template <class SegArgs>
 void fill_segment(const cfmm_ctx* c, const Eval& ev, const Segment& s, SegArgs& t)
 {
     t.m = s.m;
-    t.Delta = ev.materialize ? c->d_delta + s.trade_off : nullptr;
-    t.Lambda = ev.materialize ? c->d_lambda + s.trade_off : nullptr;
-    t.Over = ev.materialize ? c->d_over + s.trade_off : nullptr;
-    t.gflow = ev.gb ? c->d_flow + s.trade_off : nullptr;
+    t.Delta = ev.materialize ? c->d_delta.get() + s.trade_off : nullptr;
+    t.Lambda = ev.materialize ? c->d_lambda.get() + s.trade_off : nullptr;
+    t.Over = ev.materialize ? c->d_over.get() + s.trade_off : nullptr;
+    t.gflow = ev.gb ? c->d_flow.get() + s.trade_off : nullptr;
 }
 
 AnyPools pools_of(const cfmm_ctx* c, const Eval& ev, const Segment& s, int gtab_n)
@@ -226,15 +206,21 @@ AnyPools pools_of(const cfmm_ctx* c, const Eval& ev, const Segment& s, int gtab_
     AnyPools p;
     switch (s.kind) {
     case CFMM_KIND_PRODUCT:
-    case CFMM_KIND_SOLIDLY: p.p = ProductPools{s.R, s.gamma, s.Ai, s.pk, gbase}; break;
-    case CFMM_KIND_GEOMEAN: p.g = GeoMeanPools{s.R, s.w, s.gamma, s.Ai, s.eta, s.lR, (int)c->geo.geomean_exact, s.pk, gbase}; break;
-    case CFMM_KIND_UNIV3:
-        p.u = UniV3Pools{s.pg, s.Ai, s.cur_a, s.cur_b, s.cur_c, s.curR, s.walk, s.ticks, s.thr,
-                         c->opt_univ3_heads != 0 ? s.head : nullptr, s.has_walk, s.cp, s.pk, gbase};
+    case CFMM_KIND_SOLIDLY: p.p = ProductPools{s.R.get(), s.gamma.get(), s.Ai.get(), s.pk.get(), gbase}; break;
+    case CFMM_KIND_GEOMEAN:
+        p.g = GeoMeanPools{s.R.get(), s.w.get(), s.gamma.get(), s.Ai.get(), s.eta.get(), s.lR.get(), (int)c->geo.geomean_exact,
+                           s.pk.get(), gbase};
         break;
+    case CFMM_KIND_UNIV3: {
+        const UniV3State& u = s.u;
+        p.u = UniV3Pools{u.pg.get(), s.Ai.get(), u.cur_a.get(), u.cur_b.get(), u.cur_c.get(), u.curR.get(), u.walk.get(),
+                         u.ticks.get(), u.thr.get(), c->opt_univ3_heads != 0 ? u.head.get() : nullptr, u.has_walk, u.cp.get(),
+                         s.pk.get(), gbase};
+        break;
+    }
     default:
-        p.n = NCoinPools{s.nc.R, s.nc.q, s.nc.tok, s.nc.glg, s.nc.par, s.n_coins, ev.materialize ? s.nc.D : nullptr,
-                         ev.materialize ? s.nc.L : nullptr};
+        p.n = NCoinPools{s.nc.R.get(), s.nc.q.get(), s.nc.tok.get(), s.nc.glg.get(), s.nc.par.get(), s.n_coins,
+                         ev.materialize ? s.nc.D.get() : nullptr, ev.materialize ? s.nc.L.get() : nullptr};
         break;
     }
     return p;
@@ -260,7 +246,7 @@ int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
         std::memcpy(ma.rank, g.rank, sizeof ma.rank);
         std::memcpy(ma.seg_w, g.seg_w, sizeof ma.seg_w);
         ma.common = a;
-        ma.common.gflow = ev.gb ? c->d_flow : nullptr; // mode flag for the launcher; per-segment bases below
+        ma.common.gflow = ev.gb ? c->d_flow.get() : nullptr; // mode flag for the launcher; per-segment bases below
         for (int k = 0; k < g.nseg; ++k) {
             ma.seg[k].kind = segs[k].kind;
             ma.seg[k].pools = pools_of(c, ev, segs[k], a.gtab_n);
@@ -302,16 +288,17 @@ int launch_fold(cfmm_ctx* c, const Eval& ev)
         // a world of ONE rank has nobody to exchange with: the plain fold (same columns, same order; measured 0.6 us per step
         // less than the gather launch with its 200-byte peer table -- N = 1 under a launcher then costs what plain N = 1 costs)
         hipError_t e = (ps.world == 1 && rows > 0 && !ev.gb)
-            ? launch_reduce(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm)
-            : launch_reduce_gather(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ps, ka, kb);
+            ? launch_reduce(c->d_partials.get(), rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm)
+            : launch_reduce_gather(c->d_partials.get(), rows, n1, row_width(c), ev.d_out, c->stream, ps, ka, kb);
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "fold + gather launch failed: %s", hipGetErrorString(e));
     } else if (rows > 0) {
         hipError_t e;
         if (ev.gb) { // pull Ψ per token over the incidence list, then fold the dual-scalar column
-            e = launch_gather(c->d_chunks, c->d_entries, reinterpret_cast<const double*>(c->d_flow), c->d_chunk_sums,
-                              c->n_chunks, c->d_tok_chunk_off, ev.d_out, c->n, c->d_partials, rows, c->stream);
+            e = launch_gather(c->d_chunks.get(), c->d_entries.get(), reinterpret_cast<const double*>(c->d_flow.get()),
+                              c->d_chunk_sums.get(), c->n_chunks, c->d_tok_chunk_off.get(), ev.d_out, c->n, c->d_partials.get(), rows,
+                              c->stream);
         } else {
-            e = launch_reduce(c->d_partials, rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm);
+            e = launch_reduce(c->d_partials.get(), rows, n1, row_width(c), ev.d_out, c->stream, ka, kb, ev.ho, ev.arm);
         }
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "reduce launch failed: %s", hipGetErrorString(e));
     } else {
@@ -427,16 +414,16 @@ int host_sweep_begin(cfmm_ctx* c, const double* v, bool materialize)
     // round trip hides behind the first tile's pool loads); larger ones go through one H2D copy.
     const double* v_src = c->d_stage;
     if (!zero_copy || c->n > 1024 || global_bins(c)) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_v, c->h_stage, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        v_src = c->d_v;
+        HIP_TRY(c, hipMemcpyAsync(c->d_v.get(), c->h_stage, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        v_src = c->d_v.get();
     }
     // {Ψ, acc}: as output granules in the mapped pinned buffer when it can (polled by host_sweep_end), else d_out + a copy
     const bool want_host_out = zero_copy && c->opt_host_flag != 0;
-    int rc = enqueue_sweep(c, v_src, c->d_out, materialize, want_host_out, 0,
+    int rc = enqueue_sweep(c, v_src, c->d_out.get(), materialize, want_host_out, 0,
                            prices_in_fast_window(v, c->n) ? kPricesInWindow : kPricesOutside);
     if (rc != CFMM_OK) return rc;
     if (!c->last_host_out)
-        HIP_TRY(c, hipMemcpyAsync(h_out, c->d_out, (size_t)(c->n + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_out, c->d_out.get(), (size_t)(c->n + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     return CFMM_OK;
 }
 
@@ -562,7 +549,7 @@ void armed_write(cfmm_ctx* c, const double* v, uint64_t word)
 int armed_enqueue(cfmm_ctx* c)
 {
     const uint64_t seq = ++c->arm_seq;
-    int rc = enqueue_sweep(c, c->d_arm, c->d_out, false, true, seq);
+    int rc = enqueue_sweep(c, c->d_arm, c->d_out.get(), false, true, seq);
     if (rc != CFMM_OK) return rc;
     c->arm_tag = c->out_seq;
     c->arm_pending = true;

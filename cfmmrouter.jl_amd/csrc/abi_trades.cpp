@@ -16,26 +16,24 @@ namespace {
 int expanded_trades(cfmm_ctx* c, const double2** dD, const double2** dL)
 {
     if (!c->trades_compact) {
-        *dD = c->d_delta;
-        *dL = c->d_lambda;
+        *dD = c->d_delta.get();
+        *dL = c->d_lambda.get();
         return CFMM_OK;
     }
-    if (c->trade_rows > c->x_cap) {
-        (void)hipFree(c->d_xdelta); (void)hipFree(c->d_xlambda);
-        c->d_xdelta = c->d_xlambda = nullptr;
-        c->x_cap = 0;
+    const size_t rows = (size_t)c->trade_rows;
+    if (rows > c->d_xdelta.size() || rows > c->d_xlambda.size()) {
         c->x_valid = false;
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xdelta), (size_t)c->trade_rows * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&c->d_xlambda), (size_t)c->trade_rows * sizeof(double2)));
-        c->x_cap = c->trade_rows;
+        int rc;
+        if ((rc = c->d_xdelta.grow(c, rows)) || (rc = c->d_xlambda.grow(c, rows))) return rc;
     }
     if (!c->x_valid && c->have_trades) {
-        hipError_t e = launch_expand_trades(c->d_delta, c->d_lambda, c->d_over, c->d_xdelta, c->d_xlambda, c->trade_rows, c->stream);
+        hipError_t e = launch_expand_trades(c->d_delta.get(), c->d_lambda.get(), c->d_over.get(), c->d_xdelta.get(), c->d_xlambda.get(),
+                                            c->trade_rows, c->stream);
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "expand launch failed: %s", hipGetErrorString(e));
         c->x_valid = true;
     }
-    *dD = c->d_xdelta;
-    *dL = c->d_xlambda;
+    *dD = c->d_xdelta.get();
+    *dL = c->d_xlambda.get();
     return CFMM_OK;
 }
 
@@ -138,8 +136,8 @@ int download_segment(cfmm_ctx* c, const Segment& s, int64_t first, int64_t count
 {
     if (!ragged_kind(s.kind)) return download_trades(c, s.trade_off + first, count, Delta, Lambda);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    int rc = download_coin_major(c, s.nc.D, s.m, s.n_coins, first, count, Delta);
-    return rc != CFMM_OK ? rc : download_coin_major(c, s.nc.L, s.m, s.n_coins, first, count, Lambda);
+    int rc = download_coin_major(c, s.nc.D.get(), s.m, s.n_coins, first, count, Delta);
+    return rc != CFMM_OK ? rc : download_coin_major(c, s.nc.L.get(), s.m, s.n_coins, first, count, Lambda);
 }
 
 } // namespace
@@ -264,14 +262,17 @@ int cfmm_update_reserves(cfmm_ctx* c)
     // leaves a pool inside its no-arbitrage band (:347-349) alone.  P above the first tick means the pool ran out of
     // liquidity on that side and rests at the first tick's upper price.  Tick constants are then re-derived exactly
     // as at upload (compute_at_tick, :294-313).  A failure here leaves the context untouched (the call can be retried).
-    std::vector<Segment> fresh(c->segs.size());
-    std::vector<std::vector<double>> new_cp(c->segs.size());
-    auto drop_fresh = [&]() { for (Segment& ns : fresh) free_segment(ns); };
+    struct Fresh {
+        UniV3State u;
+        int fast_ok = 0;
+        std::vector<double> cp;
+    };
+    std::vector<Fresh> fresh(c->segs.size());   // (releases what it still holds on every early return)
     const double* v = c->trade_v.data();
     for (size_t k = 0; k < c->segs.size(); ++k) {
         const Segment& s = c->segs[k];
         if (s.kind != CFMM_KIND_UNIV3) continue;
-        std::vector<double>& cp = new_cp[k];
+        std::vector<double>& cp = fresh[k].cp;
         cp = s.h_cp;
         for (int64_t i = 0; i < s.m; ++i) {
             const double g = s.h_gamma[(size_t)i], q = s.h_cp[(size_t)i];
@@ -281,21 +282,19 @@ int cfmm_update_reserves(cfmm_ctx* c)
             const double top = s.h_lt[(size_t)s.h_tick_off[(size_t)i]];
             cp[(size_t)i] = P > top ? top : P;
         }
-        const int rc = univ3_build(c, fresh[k], s.m, cp.data(), s.h_gamma.data(), s.h_ai.data(), s.h_tick_off.data(),
-                                   s.h_lt.data(), s.h_liq.data());
-        if (rc != CFMM_OK) { drop_fresh(); return rc; }
+        const int rc = univ3_build(c, fresh[k].u, fresh[k].fast_ok, s.m, cp.data(), s.h_gamma.data(), s.h_ai.data(),
+                                   s.h_tick_off.data(), s.h_lt.data(), s.h_liq.data());
+        if (rc != CFMM_OK) return rc;
     }
     // Phase 2: R <- R + γΔ − Λ for the two-coin families on the device (no host traffic); from the first launch on the
     // trades count as consumed, so that a failure cannot lead to a second application of the same trades.
     c->have_trades = false;
     c->have_out = false;
-    int* d_left = nullptr;   // per segment: 1 = a new reserve left the operand window of the fast arithmetic
+    DevBuf<int> d_left;   // per segment: 1 = a new reserve left the operand window of the fast arithmetic
     std::vector<int> left(c->segs.size(), 0);
-    if (hipMalloc(reinterpret_cast<void**>(&d_left), c->segs.size() * sizeof(int)) != hipSuccess ||
-        hipMemsetAsync(d_left, 0, c->segs.size() * sizeof(int), c->stream) != hipSuccess) {
+    if (d_left.alloc(c, c->segs.size()) != CFMM_OK ||
+        hipMemsetAsync(d_left.get(), 0, c->segs.size() * sizeof(int), c->stream) != hipSuccess) {
         (void)hipGetLastError();
-        (void)hipFree(d_left);
-        drop_fresh();
         c->trade_v.clear();
         return fail(c, CFMM_ERR_HIP, "update_reserves: scratch allocation failed");
     }
@@ -304,39 +303,31 @@ int cfmm_update_reserves(cfmm_ctx* c)
         Segment& s = c->segs[k];
         if (s.kind == CFMM_KIND_UNIV3) continue;
         if (ragged_kind(s.kind)) {
-            e = launch_update_ncoin(s.kind, s.nc.R, s.nc.q, s.nc.par, s.nc.glg, s.nc.D, s.nc.L, s.n_coins, s.m, c->stream);
+            e = launch_update_ncoin(s.kind, s.nc.R.get(), s.nc.q.get(), s.nc.par.get(), s.nc.glg.get(), s.nc.D.get(), s.nc.L.get(),
+                                    s.n_coins, s.m, c->stream);
             continue;
         }
-        e = launch_update_two_coin(s.R, s.gamma, c->d_delta + s.trade_off, c->d_lambda + s.trade_off, c->d_over + s.trade_off,
-                                   c->trades_compact, s.kind == CFMM_KIND_GEOMEAN ? s.lR : nullptr, s.eta, s.m, d_left + k, c->stream);
+        e = launch_update_two_coin(s.R.get(), s.gamma.get(), c->d_delta.get() + s.trade_off, c->d_lambda.get() + s.trade_off,
+                                   c->d_over.get() + s.trade_off, c->trades_compact, s.kind == CFMM_KIND_GEOMEAN ? s.lR.get() : nullptr,
+                                   s.eta.get(), s.m, d_left.get() + k, c->stream);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(left.data(), d_left, left.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(left.data(), d_left.get(), left.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);   // also: nothing in flight still reads the old UniV3 constants
-    (void)hipFree(d_left);
+    d_left.reset();
     c->trade_v.clear();
     c->x_valid = false;
-    if (e != hipSuccess) {
-        drop_fresh();
+    if (e != hipSuccess)
         return fail(c, CFMM_ERR_HIP, "update launch failed: %s (two-coin reserves may have moved; the trades are consumed)", hipGetErrorString(e));
-    }
-    // Phase 3: swap in the UniV3 replacements (pointer moves only: cannot fail).
+    // Phase 3: move in the UniV3 replacements (cannot fail); the move assignment releases exactly what it replaces.
     for (size_t k = 0; k < c->segs.size(); ++k) {
         Segment& s = c->segs[k];
         if (s.kind != CFMM_KIND_UNIV3) {
             if (left[k]) s.fast_ok = 0;
             continue;
         }
-        Segment& ns = fresh[k];
-        (void)hipFree(s.pg); (void)hipFree(s.Ai); (void)hipFree(s.cur_a); (void)hipFree(s.cur_b); (void)hipFree(s.cur_c);
-        (void)hipFree(s.curR); (void)hipFree(s.walk); (void)hipFree(s.ticks); (void)hipFree(s.thr);
-        (void)hipFree(s.cp); (void)hipFree(s.pk); (void)hipFree(s.head);
-        s.head = ns.head;
-        s.pg = ns.pg; s.Ai = ns.Ai; s.cur_a = ns.cur_a; s.cur_b = ns.cur_b; s.cur_c = ns.cur_c; s.curR = ns.curR;
-        s.walk = ns.walk; s.ticks = ns.ticks; s.thr = ns.thr; s.has_walk = ns.has_walk;
-        s.cp = ns.cp; s.pk = ns.pk; s.gvals.swap(ns.gvals); s.fast_ok = ns.fast_ok;
-        s.h_cp.swap(new_cp[k]);
-        s.h_walk.swap(ns.h_walk); s.tick_used = ns.tick_used; s.tick_cap = ns.tick_cap;
-        ns = Segment{};   // ownership moved
+        s.u = std::move(fresh[k].u);
+        s.fast_ok = fresh[k].fast_ok;
+        s.h_cp.swap(fresh[k].cp);
     }
     return CFMM_OK;
 }
@@ -361,8 +352,8 @@ int cfmm_get_reserves(cfmm_ctx* c, int32_t seg, double* R)
     if (s.kind == CFMM_KIND_UNIV3) return fail(c, CFMM_ERR_INVALID_ARG, "UniV3 segments have prices, not reserves: cfmm_get_prices");
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (ragged_kind(s.kind)) return download_coin_major(c, s.nc.R, s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
-    HIP_TRY(c, hipMemcpy(R, s.R, (size_t)s.m * sizeof(double2), hipMemcpyDeviceToHost));
+    if (ragged_kind(s.kind)) return download_coin_major(c, s.nc.R.get(), s.m, s.n_coins, 0, s.m, R);   // [m][n_coins]
+    HIP_TRY(c, hipMemcpy(R, s.R.get(), (size_t)s.m * sizeof(double2), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }
 

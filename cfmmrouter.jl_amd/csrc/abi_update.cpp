@@ -163,12 +163,13 @@ int launch(cfmm_ctx* c, const Packer& p)
 // half as much again (at least 4096 records).  Nothing of the segment changes unless every allocation succeeded.
 int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
 {
-    if (s.tick_used + need <= s.tick_cap) return CFMM_OK;
+    UniV3State& u = s.u;
+    if (u.tick_used + need <= u.tick_cap) return CFMM_OK;
     constexpr int64_t kMaxRecords = 0x3fffffff / 2;   // the sweep's index arithmetic (univ3_build: 2·(T + 2m) <= 0x3fffffff)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<TickRec> old((size_t)s.tick_used), tight;
-    if (s.tick_used > 0) HIP_TRY(c, hipMemcpy(old.data(), s.ticks, old.size() * sizeof(TickRec), hipMemcpyDeviceToHost));
-    std::vector<int4> walk = s.h_walk;
+    std::vector<TickRec> old((size_t)u.tick_used), tight;
+    if (u.tick_used > 0) HIP_TRY(c, hipMemcpy(old.data(), u.ticks.get(), old.size() * sizeof(TickRec), hipMemcpyDeviceToHost));
+    std::vector<int4> walk = u.h_walk;
     tight.reserve(old.size());
     for (int4& w : walk) {   // a pool's two lists lie back to back: [x, x + y] and [z, z + w], z = x + y + 1
         const size_t n = (size_t)w.y + (size_t)w.w + 2;
@@ -181,29 +182,20 @@ int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
     const int64_t cap = std::min(kMaxRecords, want + std::max<int64_t>(want / 2, 4096));
     std::vector<double> thr((size_t)cap + 4, 0.0);   // (the scan reads four thresholds at a time: zeros behind the tail)
     for (size_t e = 0; e < tight.size(); ++e) thr[e] = tight[e].thr;
-    TickRec* d_ticks = nullptr;
-    double* d_thr = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d_ticks), (size_t)cap * sizeof(TickRec)) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&d_thr), thr.size() * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(d_ticks);
+    DevBuf<TickRec> d_ticks;   // (the segment's own arrays stay until all three copies have succeeded)
+    DevBuf<double> d_thr;
+    if (d_ticks.alloc(c, (size_t)cap) != CFMM_OK || d_thr.alloc(c, thr.size()) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "pool update: allocation of %lld tick records failed", (long long)cap);
-    }
-    hipError_t e = hipMemcpy(d_ticks, tight.data(), tight.size() * sizeof(TickRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_thr, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(s.walk, walk.data(), walk.size() * sizeof(int4), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {   // (s.walk may be half written: it still names records of the OLD arrays only if nothing was copied)
-        (void)hipFree(d_ticks);
-        (void)hipFree(d_thr);
+    hipError_t e = hipMemcpy(d_ticks.get(), tight.data(), tight.size() * sizeof(TickRec), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_thr.get(), thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(u.walk.get(), walk.data(), walk.size() * sizeof(int4), hipMemcpyHostToDevice);
+    if (e != hipSuccess)   // (u.walk may be half written: it still names records of the OLD arrays only if nothing was copied)
         return fail(c, CFMM_ERR_HIP, "pool update: re-upload of the tick records failed: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(s.ticks);
-    (void)hipFree(s.thr);
-    s.ticks = d_ticks;
-    s.thr = d_thr;
-    s.h_walk.swap(walk);
-    s.tick_used = (int64_t)tight.size();
-    s.tick_cap = cap;
+    u.ticks = std::move(d_ticks);
+    u.thr = std::move(d_thr);
+    u.h_walk.swap(walk);
+    u.tick_used = (int64_t)tight.size();
+    u.tick_cap = cap;
     ++c->pool_update_regrows;
     return CFMM_OK;
 }
@@ -229,37 +221,31 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     const int64_t nrec = (int64_t)ticks.size();
     int rc = univ3_make_room(c, s, nrec);
     if (rc != CFMM_OK) return rc;
+    UniV3State& st = s.u;
     // has_walk can only turn on: a segment uploaded without any list (no heads either) gets its heads now, all "never"
-    uint4* new_head = nullptr;
-    if (!s.has_walk && lists) {
-        if (hipMalloc(reinterpret_cast<void**>(&new_head), 2 * (size_t)s.m * sizeof(uint4)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, CFMM_ERR_HIP, "pool update: allocation of the threshold heads failed");
-        }
-    }
+    DevBuf<uint4> new_head;
+    if (!st.has_walk && lists && new_head.alloc(c, 2 * (size_t)s.m) != CFMM_OK)
+        return fail(c, CFMM_ERR_HIP, "pool update: allocation of the threshold heads failed");
     const size_t words = (size_t)k * (2 + 1 + 2 + 2 + 1 + 2 + 2 + 4 + 1) + (size_t)nrec * 9;
-    if ((rc = staging_reserve(c, words)) != CFMM_OK) {
-        (void)hipFree(new_head);
-        return rc;
-    }
+    if ((rc = staging_reserve(c, words)) != CFMM_OK) return rc;
     if (new_head) {
-        HIP_TRY(c, hipMemsetAsync(new_head, 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
-        s.head = new_head;
-        s.has_walk = 1;
+        HIP_TRY(c, hipMemsetAsync(new_head.get(), 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
+        st.head = std::move(new_head);
+        st.has_walk = 1;
         c->geometry_dirty = true;   // (the plan reads has_walk: bytes per pool, hence "stream_stores" = auto)
     }
-    const int base = (int)s.tick_used;
+    const int base = (int)st.tick_used;
     Packer p(c);
-    double2* pg = p.add<double2>(s.pg, 2, k);
-    double* cp = p.add<double>(s.cp, 1, k);
-    double2* cur_a = p.add<double2>(s.cur_a, 2, k);
-    double2* cur_b = p.add<double2>(s.cur_b, 2, k);
-    double* cur_c = p.add<double>(s.cur_c, 1, k);
-    double2* curR = p.add<double2>(s.curR, 2, k);
-    int4* walk = p.add<int4>(s.walk, 2, k);
-    uint4* head = s.head ? p.add<uint4>(s.head, 4, k) : nullptr;
-    TickRec* t_out = p.add<TickRec>(s.ticks, 8, nrec, base);
-    double* thr_out = p.add<double>(s.thr, 1, nrec, base);
+    double2* pg = p.add<double2>(st.pg.get(), 2, k);
+    double* cp = p.add<double>(st.cp.get(), 1, k);
+    double2* cur_a = p.add<double2>(st.cur_a.get(), 2, k);
+    double2* cur_b = p.add<double2>(st.cur_b.get(), 2, k);
+    double* cur_c = p.add<double>(st.cur_c.get(), 1, k);
+    double2* curR = p.add<double2>(st.curR.get(), 2, k);
+    int4* walk = p.add<int4>(st.walk.get(), 2, k);
+    uint4* head = st.head ? p.add<uint4>(st.head.get(), 4, k) : nullptr;
+    TickRec* t_out = p.add<TickRec>(st.ticks.get(), 8, nrec, base);
+    double* thr_out = p.add<double>(st.thr.get(), 1, nrec, base);
     for (int64_t j = 0; j < k; ++j) {
         const UniV3PoolRec& r = rec[(size_t)j];
         pg[j] = r.pg;
@@ -277,9 +263,9 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     if ((rc = launch(c, p)) != CFMM_OK) return rc;
     for (int64_t j = 0; j < k; ++j) {
         s.h_cp[(size_t)rows.idx[(size_t)j]] = rec[(size_t)j].pg.x;   // a later cfmm_update_reserves starts from the new prices
-        s.h_walk[(size_t)rows.idx[(size_t)j]] = walk[j];
+        st.h_walk[(size_t)rows.idx[(size_t)j]] = walk[j];
     }
-    s.tick_used += nrec;
+    st.tick_used += nrec;
     if (!fast) s.fast_ok = 0;
     return CFMM_OK;
 }
@@ -294,8 +280,8 @@ int apply_reserves(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     Packer p(c);
     bool fast = true;
     if (!ragged) {
-        double2* R = p.add<double2>(s.R, 2, k);
-        double2* Q = s.kind == CFMM_KIND_GEOMEAN ? p.add<double2>(s.lR, 2, k) : nullptr;
+        double2* R = p.add<double2>(s.R.get(), 2, k);
+        double2* Q = s.kind == CFMM_KIND_GEOMEAN ? p.add<double2>(s.lR.get(), 2, k) : nullptr;
         for (int64_t j = 0; j < k; ++j) {
             const double* r = u.R + 2 * rows.src[(size_t)j];
             const size_t i = (size_t)rows.idx[(size_t)j];
@@ -306,9 +292,9 @@ int apply_reserves(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     } else {
         // coin-major columns: one staging column per coin
         double *R[kMaxCoins], *q[kMaxCoins];
-        for (int c2 = 0; c2 < nc; ++c2) R[c2] = p.add<double>(s.nc.R + (size_t)c2 * (size_t)m, 1, k);
-        for (int c2 = 0; c2 < nc; ++c2) q[c2] = p.add<double>(s.nc.q + (size_t)c2 * (size_t)m, 1, k);
-        double2* ab = s.kind == CFMM_KIND_CURVE ? p.add<double2>(s.nc.par, 2, k) : nullptr;
+        for (int c2 = 0; c2 < nc; ++c2) R[c2] = p.add<double>(s.nc.R.get() + (size_t)c2 * (size_t)m, 1, k);
+        for (int c2 = 0; c2 < nc; ++c2) q[c2] = p.add<double>(s.nc.q.get() + (size_t)c2 * (size_t)m, 1, k);
+        double2* ab = s.kind == CFMM_KIND_CURVE ? p.add<double2>(s.nc.par.get(), 2, k) : nullptr;
         for (int64_t j = 0; j < k; ++j) {
             const int64_t src = rows.src[(size_t)j];
             const double* r = u.R + nc * src;

@@ -19,7 +19,7 @@ namespace {
 // fee from the gamma array).
 int build_packed(cfmm_ctx* c, Segment& s, int64_t m, const double* gamma, const int32_t* Ai)
 {
-    s.pk = nullptr;
+    s.pk.reset();
     s.gvals.clear();
     if (global_bins(c) || m == 0) return CFMM_OK;
     std::vector<PackedFeeTok> pk((size_t)m);
@@ -51,7 +51,7 @@ int build_packed(cfmm_ctx* c, Segment& s, int64_t m, const double* gamma, const 
         pk[(size_t)i].tok = (uint32_t)Ai[2 * i] | ((uint32_t)Ai[2 * i + 1] << 16);
         pk[(size_t)i].gidx = idx;
     }
-    int rc = upload(c, &s.pk, pk.data(), (size_t)m);
+    int rc = s.pk.upload(c, pk.data(), (size_t)m);
     if (rc != CFMM_OK) return rc;
     if (table) s.gvals.swap(vals);
     return CFMM_OK;
@@ -79,10 +79,7 @@ int check_two_coin(cfmm_ctx* c, int64_t m, const double* R, const double* gamma,
 
 int add_segment_common(cfmm_ctx* c, Segment&& s, const int32_t* Ai)
 {
-    if (s.m == 0) {   // an empty batch contributes no pools, no trades and no partial rows: not stored
-        free_segment(s);
-        return CFMM_OK;
-    }
+    if (s.m == 0) return CFMM_OK;   // an empty batch contributes no pools, no trades and no partial rows: not stored
     if (global_bins(c) && s.m > 0) s.h_ai.assign(Ai, Ai + 2 * s.m);
     c->segs.push_back(std::move(s));
     c->geometry_dirty = true;
@@ -162,18 +159,12 @@ int ncoin_add(cfmm_ctx* c, int kind, int64_t m, int nc, const double* R, const d
     s.fast_ok = 0;   // one arithmetic only (the compiler's)
     if (kind == CFMM_KIND_WEIGHTED) s.h_par = cpar;   // the normalised weights q is prepared from (cfmm_pools_set_reserves)
     int rc;
-    if ((rc = upload(c, &s.nc.R, cR.data(), cells)) || (rc = upload(c, &s.nc.q, cq.data(), cells)) ||
-        (rc = upload(c, &s.nc.tok, ct.data(), cells)) || (rc = upload(c, &s.nc.par, cpar.data(), cpar.size())) ||
-        (rc = upload(c, &s.nc.glg, glg.data(), (size_t)m))) {
-        free_segment(s);
+    if ((rc = s.nc.R.upload(c, cR.data(), cells)) || (rc = s.nc.q.upload(c, cq.data(), cells)) ||
+        (rc = s.nc.tok.upload(c, ct.data(), cells)) || (rc = s.nc.par.upload(c, cpar.data(), cpar.size())) ||
+        (rc = s.nc.glg.upload(c, glg.data(), (size_t)m)))
         return rc;
-    }
-    if (cells > 0 && (hipMalloc(reinterpret_cast<void**>(&s.nc.D), cells * sizeof(double)) != hipSuccess ||
-                      hipMalloc(reinterpret_cast<void**>(&s.nc.L), cells * sizeof(double)) != hipSuccess)) {
-        (void)hipGetLastError();
-        free_segment(s);
+    if (s.nc.D.alloc(c, cells) != CFMM_OK || s.nc.L.alloc(c, cells) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "trade buffers of a %s segment: allocation failed", fam.name);
-    }
     return add_segment_common(c, std::move(s), Ai);
 }
 
@@ -181,20 +172,9 @@ int ncoin_add(cfmm_ctx* c, int kind, int64_t m, int nc, const double* R, const d
 
 namespace cfmm {
 
-void free_segment(Segment& s)
-{
-    (void)hipFree(s.R); (void)hipFree(s.w); (void)hipFree(s.gamma); (void)hipFree(s.Ai);
-    (void)hipFree(s.eta); (void)hipFree(s.lR); (void)hipFree(s.pk);
-    (void)hipFree(s.cur_a); (void)hipFree(s.cur_b); (void)hipFree(s.cur_c); (void)hipFree(s.curR);
-    (void)hipFree(s.pg); (void)hipFree(s.cp); (void)hipFree(s.walk); (void)hipFree(s.ticks); (void)hipFree(s.thr);
-    (void)hipFree(s.head);
-    (void)hipFree(s.nc.R); (void)hipFree(s.nc.q); (void)hipFree(s.nc.tok); (void)hipFree(s.nc.glg); (void)hipFree(s.nc.par);
-    (void)hipFree(s.nc.D); (void)hipFree(s.nc.L);
-    s = Segment{};
-}
-
-// Validates m UniV3 pools and prepares + uploads the find_arb_pos constants (see UniV3Ops) into `s`.
-int univ3_build(cfmm_ctx* c, Segment& s, int64_t m, const double* current_price, const double* gamma, const int32_t* Ai,
+// Validates m UniV3 pools and prepares + uploads the find_arb_pos constants (see UniV3Ops) into `u`; fast_ok: Segment::fast_ok
+// of these constants.  What does not depend on the prices (Ai, the packed records) is the caller's.
+int univ3_build(cfmm_ctx* c, UniV3State& u, int& fast_ok, int64_t m, const double* current_price, const double* gamma, const int32_t* Ai,
                 const int64_t* tick_off, const double* lower_ticks, const double* liquidity)
 {
     const int64_t T = m > 0 ? tick_off[m] : 0;
@@ -242,33 +222,28 @@ int univ3_build(cfmm_ctx* c, Segment& s, int64_t m, const double* current_price,
         pg[(size_t)i] = rec.pg;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    s.kind = CFMM_KIND_UNIV3;
-    s.m = m;
-    s.n_ticks_total = T;
     // drain thresholds of all records; every record also carries its own (univ3_pool.h)
     std::vector<double> thr;
     univ3_all_thresholds(ticks, thr);
     thr.resize(ticks.size() + 4, 0.0);   // the scan reads four thresholds at a time
-    s.has_walk = longest > 0 ? 1 : 0;
+    u.has_walk = longest > 0 ? 1 : 0;
     // threshold heads (sweep.h UniV3Pools::head): the first four thresholds of both lists of every pool as floats rounded DOWN
     std::vector<uint4> head;
-    if (s.has_walk) {
+    if (u.has_walk) {
         head.resize(2 * (size_t)m);
         for (int64_t i = 0; i < m; ++i) univ3_heads(walk[(size_t)i], thr.data(), &head[2 * (size_t)i]);
     }
-    s.fast_ok = fast ? 1 : 0;
-    s.tick_used = s.tick_cap = (int64_t)ticks.size();   // no spare records: the first price update that needs some regrows (abi_update.cpp)
-    s.h_walk = walk;
+    fast_ok = fast ? 1 : 0;
+    u.tick_used = u.tick_cap = (int64_t)ticks.size();   // no spare records: the first price update that needs some regrows (abi_update.cpp)
+    u.h_walk = walk;
     int rc;
-    if ((rc = upload(c, &s.pg, pg.data(), (size_t)m)) || (rc = upload(c, &s.Ai, Ai, (size_t)m)) ||
-        (rc = upload(c, &s.cur_a, cur_a.data(), (size_t)m)) || (rc = upload(c, &s.cur_b, cur_b.data(), (size_t)m)) ||
-        (rc = upload(c, &s.cur_c, cur_c.data(), (size_t)m)) || (rc = upload(c, &s.curR, curR.data(), (size_t)m)) ||
-        (rc = upload(c, &s.walk, walk.data(), (size_t)m)) || (rc = upload(c, &s.ticks, ticks.data(), ticks.size())) ||
-        (rc = upload(c, &s.thr, thr.data(), thr.size())) || (rc = upload(c, &s.head, head.data(), head.size())) ||
-        (rc = upload(c, &s.cp, current_price, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai))) {
-        free_segment(s);
+    if ((rc = u.pg.upload(c, pg.data(), (size_t)m)) ||
+        (rc = u.cur_a.upload(c, cur_a.data(), (size_t)m)) || (rc = u.cur_b.upload(c, cur_b.data(), (size_t)m)) ||
+        (rc = u.cur_c.upload(c, cur_c.data(), (size_t)m)) || (rc = u.curR.upload(c, curR.data(), (size_t)m)) ||
+        (rc = u.walk.upload(c, walk.data(), (size_t)m)) || (rc = u.ticks.upload(c, ticks.data(), ticks.size())) ||
+        (rc = u.thr.upload(c, thr.data(), thr.size())) || (rc = u.head.upload(c, head.data(), head.size())) ||
+        (rc = u.cp.upload(c, current_price, (size_t)m)))
         return rc;
-    }
     return CFMM_OK;
 }
 
@@ -292,11 +267,9 @@ int cfmm_pools_add_product(cfmm_ctx* c, int64_t m, const double* R, const double
     s.fast_ok = 1;
     for (int64_t i = 0; i < m && s.fast_ok; ++i)
         s.fast_ok = in_fast_window(R[2 * i]) && in_fast_window(R[2 * i + 1]) && in_fast_window(gamma[i]);
-    if ((rc = upload(c, &s.R, R, (size_t)m)) || (rc = upload(c, &s.gamma, gamma, (size_t)m)) ||
-        (rc = upload(c, &s.Ai, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai))) {
-        free_segment(s);
+    if ((rc = s.R.upload(c, R, (size_t)m)) || (rc = s.gamma.upload(c, gamma, (size_t)m)) ||
+        (rc = s.Ai.upload(c, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai)))
         return rc;
-    }
     return add_segment_common(c, std::move(s), Ai);
 }
 
@@ -321,11 +294,9 @@ int cfmm_pools_add_solidly(cfmm_ctx* c, int64_t m, const double* R, const double
     s.kind = CFMM_KIND_SOLIDLY;
     s.m = m;
     s.fast_ok = 0;   // one arithmetic only (the compiler's)
-    if ((rc = upload(c, &s.R, R, (size_t)m)) || (rc = upload(c, &s.gamma, gamma, (size_t)m)) ||
-        (rc = upload(c, &s.Ai, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai))) {
-        free_segment(s);
+    if ((rc = s.R.upload(c, R, (size_t)m)) || (rc = s.gamma.upload(c, gamma, (size_t)m)) ||
+        (rc = s.Ai.upload(c, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai)))
         return rc;
-    }
     return add_segment_common(c, std::move(s), Ai);
 }
 
@@ -360,13 +331,11 @@ int cfmm_pools_add_geomean(cfmm_ctx* c, int64_t m, const double* R, const double
     s.fast_ok = fast ? 1 : 0;
     s.h_gamma.assign(gamma, gamma + m);   // host copies of what {Q1, Q2} are prepared from besides R (cfmm_pools_set_reserves)
     s.h_eta = etas;
-    if ((rc = upload(c, &s.eta, etas.data(), (size_t)m)) || (rc = upload(c, &s.lR, lR.data(), (size_t)m)) ||
-        (rc = upload(c, &s.R, R, (size_t)m)) || (rc = upload(c, &s.w, w, (size_t)m)) ||
-        (rc = upload(c, &s.gamma, gamma, (size_t)m)) || (rc = upload(c, &s.Ai, Ai, (size_t)m)) ||
-        (rc = build_packed(c, s, m, gamma, Ai))) {
-        free_segment(s);
+    if ((rc = s.eta.upload(c, etas.data(), (size_t)m)) || (rc = s.lR.upload(c, lR.data(), (size_t)m)) ||
+        (rc = s.R.upload(c, R, (size_t)m)) || (rc = s.w.upload(c, w, (size_t)m)) ||
+        (rc = s.gamma.upload(c, gamma, (size_t)m)) || (rc = s.Ai.upload(c, Ai, (size_t)m)) ||
+        (rc = build_packed(c, s, m, gamma, Ai)))
         return rc;
-    }
     return add_segment_common(c, std::move(s), Ai);
 }
 
@@ -390,8 +359,11 @@ int cfmm_pools_add_univ3(cfmm_ctx* c, int64_t m, const double* current_price, co
         });
     }
     Segment s;
-    int rcb = univ3_build(c, s, m, current_price, gamma, Ai, tick_off, lower_ticks, liquidity);
-    if (rcb != CFMM_OK) return rcb;
+    s.kind = CFMM_KIND_UNIV3;
+    s.m = m;
+    s.n_ticks_total = m > 0 ? tick_off[m] : 0;
+    int rc = univ3_build(c, s.u, s.fast_ok, m, current_price, gamma, Ai, tick_off, lower_ticks, liquidity);
+    if (rc != CFMM_OK || (rc = s.Ai.upload(c, Ai, (size_t)m)) || (rc = build_packed(c, s, m, gamma, Ai))) return rc;
     // host copy of the pool definitions: update_reserves! re-derives the tick constants from them
     s.h_cp.assign(current_price, current_price + m);
     s.h_gamma.assign(gamma, gamma + m);
@@ -462,7 +434,6 @@ int cfmm_pools_clear(cfmm_ctx* c)
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    for (auto& s : c->segs) free_segment(s);
     c->segs.clear();
     c->m_total = 0;
     c->flat_total = 0;

@@ -2,7 +2,8 @@
 // share.  Host-side only.  There is no CPU fallback anywhere behind this header: without a gfx950 device every
 // entry point that needs one fails with CFMM_ERR_HIP.
 //
-//   abi_context.cpp   create / destroy / options / streams / introspection
+//   devbuf.h          DevBuf<T>: the one owner of a device array (every Segment / context array below is one)
+//   abi_context.cpp   create / destroy / options / streams / introspection, dev_alloc / dev_free
 //   abi_upload.cpp    pool validation + upload (src/cfmms.jl:76-111, :152-165, :226-245), prepared constants
 //   launch_plan.cpp   the launch geometry of one evaluation, as a pure function (launch_plan.h: no HIP, no context)
 //   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold, host-pointer
@@ -16,6 +17,7 @@
 #pragma once
 
 #include "../../include/cfmm_amd.h"
+#include "devbuf.h"
 #include "launch_plan.h"
 #include "sweep.h"
 
@@ -33,55 +35,66 @@
 
 namespace cfmm {
 
+// Device memory has one owner (devbuf.h): every device array below is a DevBuf member and goes with the object that holds
+// it -- Segment destruction, a move assignment, segs.clear() -- so no list of frees exists anywhere.  The view structs of
+// sweep.h that cross into a kernel are built from `.get()` per launch (abi_sweep.cpp pools_of) and never own.
+// A segment of one kind leaves the groups of the other kinds empty.
+
+// UniV3: everything a price change of the whole segment replaces.  univ3_build fills one; cfmm_update_reserves builds a fresh
+// one per segment and moves it in.
+struct UniV3State {
+    DevBuf<double2> pg;
+    DevBuf<double> cp;          // current_price alone (packed records)
+    DevBuf<double2> cur_a, cur_b;
+    DevBuf<double> cur_c;
+    DevBuf<double2> curR;
+    DevBuf<int4> walk;
+    DevBuf<TickRec> ticks;      // walk lists (sweep.h TickRec)
+    DevBuf<double> thr;         // drain thresholds, one per record
+    DevBuf<uint4> head;         // per pool the first four thresholds of both walk lists as rounded-down floats (sweep.h UniV3Pools)
+    int has_walk = 1;           // some pool has a tick beyond its current one
+    // the walk lists of a pool whose price cfmm_pools_set_prices moves are rewritten at the TAIL of ticks / thr (abi_update.cpp):
+    // records in use (garbage of moved pools included) and allocated (thr: + 4 of read-ahead), and the host copy of `walk` a
+    // compaction rebuilds the arrays from
+    int64_t tick_used = 0, tick_cap = 0;
+    std::vector<int4> h_walk;
+};
+
+// N-coin kinds (KindInfo::ragged: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE): the coin-major columns and the segment's own trade
+// arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
+struct NCoinState {
+    DevBuf<double> R;        // [n_coins][m] (sweep.h NCoinPools)
+    DevBuf<double> q;        // [n_coins][m] the family's per-coin constant
+    DevBuf<int32_t> tok;
+    DevBuf<double2> glg;     // [m] {γ, log γ}
+    DevBuf<double> par;      // the family's own column (KindInfo::par_per_pool doubles per pool)
+    DevBuf<double> D, L;     // [n_coins][m] Δ, Λ of the latest materialising sweep
+};
+
 struct Segment : SegPlan {   // (SegPlan: the launch geometry, decided by ensure_geometry)
     int kind = 0;
     int64_t m = 0;
     int64_t n_ticks_total = 0;
     int fast_ok = 0; // every constant the sweep divides by / takes roots of lies in [2^-kFastExp, 2^kFastExp] (sweep.h)
-    // device arrays (owned)
-    double2* R = nullptr;
-    double2* w = nullptr;
-    double* eta = nullptr;   // geomean: η = w1/w2
-    double2* lR = nullptr;   // geomean: {Q1, Q2}, the v-independent constants of the log-space exponents (GeoMeanLogOps)
-    double* gamma = nullptr;
-    int2* Ai = nullptr;
-    double2* pg = nullptr;
-    double* cp = nullptr;    // univ3: current_price alone (packed records)
-    int has_walk = 1;        // univ3: some pool has a tick beyond its current one
-    double2* cur_a = nullptr;
-    double2* cur_b = nullptr;
-    double* cur_c = nullptr;
-    double2* curR = nullptr;
-    int4* walk = nullptr;
-    TickRec* ticks = nullptr;   // univ3: walk lists (sweep.h TickRec)
-    double* thr = nullptr;      // univ3: drain thresholds, one per record
-    uint4* head = nullptr;      // univ3: per pool the first four thresholds of both walk lists as rounded-down floats (sweep.h UniV3Pools)
-    PackedFeeTok* pk = nullptr;     // {i1 | i2 << 16, fee-table index} per pool, or null (too many distinct fees / tokens)
+    int n_coins = 2;
+    // the two-coin kinds (UniV3: Ai, pk, gvals and the host copies only)
+    DevBuf<double2> R, w;
+    DevBuf<double> gamma;
+    DevBuf<double> eta;      // geomean: η = w1/w2
+    DevBuf<double2> lR;      // geomean: {Q1, Q2}, the v-independent constants of the log-space exponents (GeoMeanLogOps)
+    DevBuf<int2> Ai;
+    DevBuf<PackedFeeTok> pk;        // {i1 | i2 << 16, fee-table index} per pool, or empty (too many distinct fees / tokens)
     std::vector<double> gvals;      // the segment's distinct fees, in order of first appearance (index = PackedFeeTok::gidx)
     std::vector<int32_t> h_ai; // host copy of Ai: large-market mode (incidence build) and UniV3 segments
-    // UniV3 only: the pool definitions as uploaded (update_reserves! moves current_price and re-derives the constants)
-    std::vector<double> h_cp, h_gamma, h_lt, h_liq;
-    std::vector<int64_t> h_tick_off;
-    // UniV3 only: the walk lists of a pool whose price cfmm_pools_set_prices moves are rewritten at the TAIL of ticks / thr
-    // (abi_update.cpp): records in use (garbage of moved pools included) and allocated (thr: + 4 of read-ahead), and the host
-    // copy of `walk` a compaction rebuilds the arrays from
-    int64_t tick_used = 0, tick_cap = 0;
-    std::vector<int4> h_walk;
     // host copies of the pool constants that cfmm_pools_set_reserves prepares q / {Q1, Q2} from besides the new reserves:
-    // GeometricMeanTwoCoin h_gamma (above) and η, weighted the normalised weights ([n_coins][m] like nc.par)
-    std::vector<double> h_eta, h_par;
-    // N-coin kinds (KindInfo::ragged: CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE) only: the coin-major columns and the segment's own
-    // trade arrays; such a segment has no rows in the two-coin trade buffers (trade_off is unused)
-    int n_coins = 2;
-    struct {
-        double* R = nullptr;   // [n_coins][m] (sweep.h NCoinPools)
-        double* q = nullptr;   // [n_coins][m] the family's per-coin constant
-        int32_t* tok = nullptr;
-        double2* glg = nullptr;   // [m] {γ, log γ}
-        double* par = nullptr;    // the family's own column (KindInfo::par_per_pool doubles per pool)
-        double* D = nullptr;      // [n_coins][m] Δ of the latest materialising sweep
-        double* L = nullptr;      // [n_coins][m] Λ
-    } nc;
+    // GeometricMeanTwoCoin γ and η, weighted the normalised weights ([n_coins][m] like nc.par)
+    std::vector<double> h_gamma, h_eta, h_par;
+    // UniV3: the prepared state, and the pool definitions as uploaded (update_reserves! moves current_price and re-derives
+    // the state from them)
+    UniV3State u;
+    std::vector<double> h_cp, h_lt, h_liq;
+    std::vector<int64_t> h_tick_off;
+    NCoinState nc;
 };
 
 // What the library knows of a pool kind, in ONE place: the plan (launch_plan.cpp), the sweep (abi_sweep.cpp), the upload and
@@ -165,30 +178,25 @@ struct cfmm_ctx {
     int64_t touched_bytes = 0;    // what one materialising sweep moves by construction (packed layout; ensure_geometry): decides "stream_stores" = auto
     int64_t rows_total = 0;
 
-    double* d_v = nullptr;        // [n]
-    double* d_out = nullptr;      // [n+1]
-    double* d_partials = nullptr; // [rows_cap][row_width]: n+1 columns, rows padded to 128 bytes
-    int64_t rows_cap = 0;
-    // trade buffers [trade_cap] each.  Compact layout (option "compact_trades", default): d_delta holds ONE 16-byte
+    // device buffers: DevBufs, grown on demand (DevBuf::grow: the old contents go) and released with the context
+    cfmm::DevBuf<double> d_v;        // [n]
+    cfmm::DevBuf<double> d_out;      // [n+1]
+    cfmm::DevBuf<double> d_partials; // [rows][row_width]: n+1 columns, rows padded to 128 bytes
+    // trade buffers, one size each.  Compact layout (option "compact_trades", default): d_delta holds ONE 16-byte
     // record per pool, d_lambda / d_over the four values of the rare pools that trade in both directions (sweep.h
     // SweepArgs); plain layout: d_delta = {Δ₁, Δ₂}, d_lambda = {Λ₁, Λ₂}.  d_xdelta / d_xlambda: expanded copies, for
     // cfmm_trades_dev and the trade download.
-    double2* d_delta = nullptr;
-    double2* d_lambda = nullptr;
-    double2* d_over = nullptr;
-    double2* d_xdelta = nullptr;
-    double2* d_xlambda = nullptr;
-    int64_t x_cap = 0;
+    cfmm::DevBuf<double2> d_delta, d_lambda, d_over;
+    cfmm::DevBuf<double2> d_xdelta, d_xlambda;
     bool x_valid = false;         // d_xdelta / d_xlambda hold the expansion of the trades currently on the device
     int trades_compact = 0;       // layout of the trades currently on the device
-    int64_t trade_cap = 0;
     cfmm::TradeStaging tstage;
     // large-market mode (n > kMaxLdsTokens): token -> (pool, side) incidence and flow scratch
-    double2* d_flow = nullptr;    // [m_total] {Λ₁−Δ₁, Λ₂−Δ₂}
-    int* d_entries = nullptr;     // [2·m_total] flat flow indices grouped by token
-    int2* d_chunks = nullptr;     // [n_chunks] {begin, end} into d_entries
-    int* d_tok_chunk_off = nullptr; // [n+1]
-    double* d_chunk_sums = nullptr; // [n_chunks]
+    cfmm::DevBuf<double2> d_flow;       // [m_total] {Λ₁−Δ₁, Λ₂−Δ₂}
+    cfmm::DevBuf<int> d_entries;        // [2·m_total] flat flow indices grouped by token
+    cfmm::DevBuf<int2> d_chunks;        // [n_chunks] {begin, end} into d_entries
+    cfmm::DevBuf<int> d_tok_chunk_off;  // [n+1]
+    cfmm::DevBuf<double> d_chunk_sums;  // [n_chunks]
     int n_chunks = 0;
     // sharded operation (cfmm_set_peers): the fold launch of every sweep also gathers the peers' {Ψ, acc} over xGMI
     // (reduce_gather), so eval / find_arb / route return GLOBAL {Ψ, acc}
@@ -206,8 +214,7 @@ struct cfmm_ctx {
     double* d_stage = nullptr;    // device address of h_stage
     size_t gran_off = 0;          // first output granule in h_stage / d_stage (doubles)
     size_t flag_off = 0;          // the sweeps' sticky report word (sweep.h kFlagWindow / kFlagGaveUp), its own 128-byte line
-    double* d_gtab = nullptr;     // [groups][kMaxFeeTable] fee tables of the launches (packed pool records)
-    size_t gtab_cap = 0;
+    cfmm::DevBuf<double> d_gtab;  // [groups][kMaxFeeTable] fee tables of the launches (packed pool records)
     // pre-armed evaluations of cfmm_route (sweep.h SweepArgs::arm_word): [n_pad] v, then the word, in FINE-GRAINED
     // device memory that the host writes through the PCIe BAR (null: no large BAR, or the self-check failed)
     double* d_arm = nullptr;
@@ -279,8 +286,6 @@ namespace cfmm {
 
 extern thread_local std::string g_create_error;
 
-int fail(const cfmm_ctx* c, int code, const char* fmt, ...);
-
 #define HIP_TRY(ctx, expr)                                                                            \
     do {                                                                                              \
         hipError_t _e = (expr);                                                                       \
@@ -292,23 +297,12 @@ int fail(const cfmm_ctx* c, int code, const char* fmt, ...);
     if (!(c)->shards.empty() || (c)->device < 0)                                                      \
         return ::cfmm::fail(c, CFMM_ERR_UNSUPPORTED, what " is not available on a multi-device context (host-pointer calls only)")
 
-template <class T>
-int upload(cfmm_ctx* c, T** dst, const void* src, size_t count)
-{
-    *dst = nullptr;
-    if (count == 0) return CFMM_OK;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(dst), count * sizeof(T)));
-    HIP_TRY(c, hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return CFMM_OK;
-}
-
 inline bool global_bins(const cfmm_ctx* c) { return global_bins(c->n); }
 inline int row_width(const cfmm_ctx* c) { return global_bins(c) ? 1 : row_pitch_of(c->n + 1); }   // doubles between partial rows
 inline bool is_parent(const cfmm_ctx* c) { return !c->shards.empty() || c->device < 0; }
 
 // abi_upload.cpp
-void free_segment(Segment& s);
-int univ3_build(cfmm_ctx* c, Segment& s, int64_t m, const double* current_price, const double* gamma, const int32_t* Ai,
+int univ3_build(cfmm_ctx* c, UniV3State& u, int& fast_ok, int64_t m, const double* current_price, const double* gamma, const int32_t* Ai,
                 const int64_t* tick_off, const double* lower_ticks, const double* liquidity);
 
 // abi_sweep.cpp
