@@ -1,5 +1,5 @@
 // abi_peers.cpp -- one process per GPU: rank-to-rank buffers and cfmm_set_peers (include/cfmm_amd.h).
-// The exchange itself is reduce_gather (sweep_kernels.hip): the launch that folds a rank's partial rows publishes
+// The exchange itself is reduce_gather (fold_kernels.h): the launch that folds a rank's partial rows publishes
 // its {Ψ, acc} as self-validating granules in the rank's buffer and reads every peer's over xGMI.
 #include "ctx.h"
 

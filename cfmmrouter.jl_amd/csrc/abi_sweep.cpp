@@ -786,7 +786,7 @@ int cfmm_sweep_dev(cfmm_ctx* c, const double* d_v, double* d_out, int materializ
     c->have_out = false; // results live on the device; the host copy is stale
     if (materialize) c->trade_v.clear();   // the library has not seen these prices
     // The library cannot see these prices: the launch carries both arithmetics and every block picks from the prices it
-    // stages (sweep_kernels.hip kArithAuto) -- prices outside [2^-150, 2^150], NaN included, take the full-range loop and
+    // stages (sweep_core.h kArithAuto) -- prices outside [2^-150, 2^150], NaN included, take the full-range loop and
     // propagate like the reference's arithmetic.  (Round 4 launched the fast kernels on trust and reported a refusal on a
     // LATER call: ADVICE r4.)
     return enqueue_sweep(c, d_v, d_out, materialize != 0, false, 0, kPricesUnknown);

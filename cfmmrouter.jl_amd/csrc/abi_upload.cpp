@@ -314,7 +314,7 @@ int cfmm_pools_add_geomean(cfmm_ctx* c, int64_t m, const double* R, const double
         return multi_add(c, CFMM_KIND_GEOMEAN, m, [&](cfmm_ctx* child, int64_t lo, int64_t hi) -> int {
             return cfmm_pools_add_geomean(child, hi - lo, R + 2 * lo, w + 2 * lo, gamma + lo, Ai + 2 * lo);
         });
-    // v-independent pieces of the log-space closed forms (sweep_kernels.hip, GeoMeanLogOps)
+    // v-independent pieces of the log-space closed forms (ops_two_coin.h, GeoMeanLogOps)
     std::vector<double2> lR((size_t)m);
     std::vector<double> etas((size_t)m);
     bool fast = true;

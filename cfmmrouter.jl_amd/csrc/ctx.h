@@ -98,7 +98,7 @@ struct Segment : SegPlan {   // (SegPlan: the launch geometry, decided by ensure
 };
 
 // What the library knows of a pool kind, in ONE place: the plan (launch_plan.cpp), the sweep (abi_sweep.cpp), the upload and
-// the trade paths all read this table.  The device side of a kind is its Ops / Family struct in sweep_kernels.hip.
+// the trade paths all read this table.  The device side of a kind is its Ops / Family struct in ops_two_coin.h, ops_univ3.h or sweep_ncoin.h.
 struct KindInfo {
     const char* name;          // in error texts
     bool ragged;               // n_coins per pool: trades kept in the segment's own nc.D / nc.L, swept by sweep_ncoin

@@ -1,5 +1,5 @@
 // curve_pool.h -- the per-pool solve of Curve (StableSwap) pools, src/cfmms.jl:66-70 (Curve{T}: R, γ, Ai, α, β; no
-// find_arb! there).  Host + device code: sweep_ncoin<CurveFamily> (sweep_kernels.hip) runs it one lane per pool.
+// find_arb! there).  Host + device code: sweep_ncoin<CurveFamily> (sweep_ncoin.h) runs it one lane per pool.
 //
 // Trading function φ(R) = α·Σ R_k − β·Π R_k⁻¹ (α >= 0, β > 0): StableSwap's invariant with D held fixed, α = A·nⁿ,
 // β = D^{n+1}/nⁿ.  The problem of the find_arb! docstring (src/cfmms.jl:21-33): maximise Σ v_k(λ_k − δ_k) s.t.

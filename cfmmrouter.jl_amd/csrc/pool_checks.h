@@ -58,7 +58,7 @@ inline int check_univ3_tick(const cfmm_ctx* c, int64_t i, const double* lt, int6
     return CFMM_OK;
 }
 
-// GeometricMeanTwoCoin: {Q1, Q2}, the v-independent pieces of the log-space closed forms (sweep_kernels.hip, GeoMeanLogOps);
+// GeometricMeanTwoCoin: {Q1, Q2}, the v-independent pieces of the log-space closed forms (ops_two_coin.h, GeoMeanLogOps);
 // e = η = w1/w2 (src/cfmms.jl:188)
 inline double2 geomean_q(double gamma, double e, double r1, double r2)
 {

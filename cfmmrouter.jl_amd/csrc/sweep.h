@@ -1,5 +1,5 @@
 // sweep.h -- internal C++ interface between the C ABI (abi_*.cpp) and the gfx950 kernels
-// (sweep_kernels.hip).  Not installed; the public surface is include/cfmm_amd.h.
+// (sweep_kernels.hip and the device headers it includes).  Not installed; the public surface is include/cfmm_amd.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,7 +12,7 @@ constexpr int kBigBlock = 1024;      // 16 wavefronts: single-family launches, f
 constexpr int kFoldBlock = 512;      // reduce_partials / reduce_gather
 constexpr int kResidentThreads = 2048 * 256; // one machine of resident threads (256 CUs x 2048)
 constexpr int kReduceCols = 8;       // tokens per fold block (64 B = half a 128-byte line of each partial row; the two blocks that share
-                                     // a line run on the SAME XCD, i.e. behind the same L2: fold_colblock in sweep_kernels.hip)
+                                     // a line run on the SAME XCD, i.e. behind the same L2: fold_colblock in fold_kernels.h)
 constexpr int kRowAlign = 16;        // partial rows are padded to a multiple of this many doubles (128 B)
 constexpr int kMaxLdsTokens = 8192;  // up to here the prices + one bin copy fit the 160 KiB LDS of a CU;
                                      // larger markets pull Ψ per token (sweep_body<..., GBINS=true>)
@@ -28,7 +28,7 @@ struct PackedFeeTok {
 };
 constexpr int kMaxFeeTable = 256;
 
-// Window of the "fast" arithmetic (sweep_kernels.hip, div_by / fast_sqrt): when every reserve, fee, liquidity and
+// Window of the "fast" arithmetic (fast_arith.h, div_by / fast_sqrt): when every reserve, fee, liquidity and
 // price of a launch lies in [2^-kFastExp, 2^kFastExp], the IEEE division / square-root sequences run without their
 // range scaffolding (v_div_scale, v_div_fmas, v_div_fixup, ldexp pairs) and still return the correctly rounded bits.
 constexpr int kFastExp = 150;
@@ -206,7 +206,7 @@ struct LaunchCfg {
     int block;                   // kMidBlock or kBigBlock
     int grid;
     size_t lds_bytes;
-    int arith = 0;               // the kernel's arithmetic (sweep_kernels.hip, FASTK): 0 = the compiler's full-range sequences,
+    int arith = 0;               // the kernel's arithmetic (sweep_core.h, FASTK): 0 = the compiler's full-range sequences,
                                  // 1 = fast (every pool constant of the launch and -- the host KNOWS -- every price inside the
                                  // kFastExp window), 2 = auto (pool constants inside the window, prices unknown to the host:
                                  // device-pointer sweeps; every block picks the loop from the prices it stages)
@@ -250,7 +250,7 @@ hipError_t launch_reduce(const double* partials, int rows, int n1, int pitch, do
                          ArmWord arm = ArmWord{nullptr, 0});
 
 // Sharded runs (cfmm_set_peers): the row fold fused with the one-shot all-reduce over xGMI peer
-// mappings (reduce_gather in sweep_kernels.hip): block b folds its kReduceCols columns, publishes
+// mappings (reduce_gather in fold_kernels.h): block b folds its kReduceCols columns, publishes
 // them as self-validating granules in this rank's symmetric buffer and adds the same columns of
 // every peer in rank order -- one launch, one hop on the critical path, no hand-off between the blocks of a rank.
 constexpr int kMaxPeers = 16;

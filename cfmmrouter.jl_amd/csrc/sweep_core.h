@@ -1,0 +1,489 @@
+// sweep_core.h -- the fused two-coin sweep: trade and row stores, the LDS layout, price staging, one pool's epilogue
+// (process_pool), the tile loops, the block epilogue and the kernels sweep_kernel (one segment) / sweep_multi (several).
+#pragma once
+
+#include "ops_two_coin.h"
+#include "ops_univ3.h"
+
+namespace cfmm {
+
+// ---------------------------------------------------------------------------------------------
+// The sweep: src/router.jl:38-42 fused with :79-83 and :98-100
+// ---------------------------------------------------------------------------------------------
+// Trade stores (Δ, Λ: 16 B per lane, written once, never re-read by the sweep) are write-through (`sc1`): the bytes
+// leave during the sweep instead of in a serial flush of dirty L2 lines at its end (MI355X_MICROARCH.md, boundary row:
+// + B / 6 TB/s for B dirty bytes; measured against plain and non-temporal stores in rounds 1 and 2: -1..-2 us per
+// 1M-pool sweep).
+// The s_nop is part of the store: a VMEM store of more than 8 bytes reads its upper data registers one cycle after
+// issue, and the VALU must not overwrite them in that cycle (gfx9 hazard "VMEM store > 8 bytes followed by a write of
+// the VGPRs holding the write data: 1 wait state").  The compiler inserts that wait state for its own stores; it
+// cannot see through inline asm -- and the values stored here are selects computed right before the next store, so the
+// next v_cndmask may land in the registers of this one (found as 9 % wrong rows in the two-row trade layout).
+typedef double d2v __attribute__((ext_vector_type(2)));
+// nt (SweepArgs::nt_stores, launch-uniform): non-temporal instead of write-through -- for markets whose pool state comes from
+// HBM on every sweep (too large for the Infinity Cache, or a caller that rotates over many markets): the trade lines then
+// bypass the cache hierarchy instead of displacing pool state that is about to be read.
+__device__ __forceinline__ void store_pair(double2* dst, double x, double y, int nt)
+{
+    d2v val = {x, y};
+    if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" : : "v"(dst), "v"(val) : "memory");
+    else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(val) : "memory");
+}
+
+// Partial rows are written through as well: no dirty line is left for the end-of-kernel release in front of the fold
+// launch (A/B: -0.3..-0.45 us per step on single-family launches, +-0.1 on config3; profiles/r03_ab_row_write_through.txt).
+__device__ __forceinline__ void store_row(double* dst, double x)
+{
+    asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(dst), "v"(x) : "memory");
+}
+
+// One block's share of a segment: tiles bid, bid+nblocks, ... of the segment's pools; its
+// partial row goes to partials[row].
+// GBINS = true is the large-market mode (n_tokens > kMaxLdsTokens, v and the bins no longer fit
+// LDS): v is gathered straight from global memory (it stays L2-resident) and every pool's two
+// flows Λ−Δ are written to a flow array; Ψ is then PULLED per token over a token -> (pool, side)
+// incidence list built at upload (gather_chunks / token_fold below) -- no float atomics, fixed
+// summation order.  The partial rows carry only the dual scalar.
+// LDS of a sweeping block: the prices {v, rcp_refined(v)} per token, the launch's fee table {γ, rcp_refined(γ)},
+// log v (launches with a log-space GeometricMean segment), the netflow bins (one copy per wavefront, or one
+// shared copy) and one slot per wavefront for the dual-scalar fold.
+struct SweepLds {
+    double2* vy;       // [n_pad] {v, rcp_refined(v)}  (a.v_shift == 3: [n_pad] doubles, the prices alone)
+    double2* gtab;     // [gtab_n] {γ, rcp_refined(γ)}
+    double* lv;        // [n_pad] log v (only when a.need_logv)
+    double* bins;      // [copies][n_pad]
+    double* wsum;      // [kWaves] dual-scalar fold
+    double* flags;     // [kWaves + 1] stage_prices: per-wavefront "prices in the fast window", then "launch is live"
+    double* my_bins;   // this wavefront's copy
+};
+
+template <int BLOCK, bool GBINS>
+__device__ __forceinline__ SweepLds carve_lds(const SweepArgs& a)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    SweepLds L;
+    if constexpr (GBINS) {
+        L.vy = nullptr;
+        L.gtab = nullptr;
+        L.lv = L.bins = L.my_bins = L.flags = nullptr;
+        L.wsum = lds;
+        return L;
+    }
+    L.vy = reinterpret_cast<double2*>(lds);
+    L.gtab = reinterpret_cast<double2*>(lds + ((size_t)a.n_pad << (a.v_shift - 3)));
+    L.lv = reinterpret_cast<double*>(L.gtab + a.gtab_n);
+    L.bins = L.lv + (a.need_logv ? a.n_pad : 0);
+    L.wsum = L.bins + (size_t)a.copies * a.n_pad;
+    L.flags = L.wsum + BLOCK / 64;
+    L.my_bins = L.bins + (size_t)(a.copies == 1 ? 0 : (threadIdx.x >> 6)) * a.n_pad;
+    return L;
+}
+
+// Pre-armed launch: one lane waits for the host's word (see SweepArgs::arm_word).  1 = v is in place, 0 = the launch is
+// cancelled -- this sequence number with the cancel bit, or ANY later sequence number: the host has moved on (it
+// overwrites the one word while blocks of an abandoned launch may still be starting) --, -1 = gave up waiting.
+__device__ __forceinline__ int wait_armed(const SweepArgs& a)
+{
+    const long long t0 = (long long)wall_clock64();
+    for (;;) {
+        const unsigned long long w = __hip_atomic_load(a.arm_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (w == a.arm_seq) return 1;
+        if ((w & ~kArmCancel) > a.arm_seq || w == (a.arm_seq | kArmCancel)) return 0;
+        if ((long long)wall_clock64() - t0 > a.arm_timeout) return -1;
+        __builtin_amdgcn_s_sleep(1);
+    }
+}
+
+// A block reports WHY it poisons its row (NaN in every column): one sticky word in mapped host memory, read by the
+// host when it meets a non-finite result (abi_sweep.cpp).  Rare paths only.
+__device__ __forceinline__ void report(const SweepArgs& a, unsigned long long bit)
+{
+    if (a.flags && threadIdx.x == 0) __hip_atomic_fetch_or(a.flags, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// bins <- 0, fee table and prices -> LDS, barrier.  Whole block.  Result (block-uniform): kStageLive unless this is a
+// pre-armed launch that was cancelled or gave up waiting for its prices (then also kStageGaveUp); kStageFast when every
+// staged price lies in the window of the fast arithmetic.
+constexpr int kStageLive = 1, kStageFast = 2, kStageGaveUp = 4;
+template <int BLOCK, bool GBINS>
+__device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& L)
+{
+    if constexpr (GBINS) {
+        __syncthreads();
+        return kStageLive;
+    }
+    const int tid = threadIdx.x;
+    const int n_zero = a.copies * a.n_pad;                // LDS bins to clear
+    const bool logs = a.need_logv != 0;
+    const bool armed = a.arm_word != nullptr;             // kernel argument: block-uniform
+    bool live = true, gave_up = false;
+    if (armed) {
+        // pre-armed launch: everything that does not need the prices first, then the wait
+        for (int j = tid; j < n_zero; j += BLOCK) L.bins[j] = 0.0;
+        for (int j = tid; j < a.gtab_n; j += BLOCK) {
+            const double g = a.gtab[j];
+            L.gtab[j] = make_double2(g, rcp_refined(g));
+        }
+        if (tid == 0) L.flags[BLOCK / 64] = (double)wait_armed(a);
+        __syncthreads();
+        live = L.flags[BLOCK / 64] > 0.0;
+        gave_up = L.flags[BLOCK / 64] < 0.0;
+    }
+    bool in_window = true;
+    for (int j = tid; j < a.n; j += BLOCK) {
+        // armed: the host wrote v through the PCIe BAR after this kernel may have started -- system-scope loads
+        const double vj = armed ? __hip_atomic_load(a.v + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : a.v[j];
+        if (a.v_shift == 4) L.vy[j] = make_double2(vj, rcp_refined(vj));
+        else reinterpret_cast<double*>(L.vy)[j] = vj;
+        in_window = in_window && in_fast_window(vj);
+        if (logs) L.lv[j] = log(vj);     // once per token per block: the only logarithm of a GeometricMean sweep
+    }
+    if (!armed) {
+        // the price loads are in flight while the bins are cleared
+        for (int j = tid; j < n_zero; j += BLOCK) L.bins[j] = 0.0;
+        for (int j = tid; j < a.gtab_n; j += BLOCK) {
+            const double g = a.gtab[j];
+            L.gtab[j] = make_double2(g, rcp_refined(g));
+        }
+    }
+    // block-wide AND of in_window through LDS (the library's __syncthreads_and would add 256 bytes of STATIC LDS to
+    // every kernel, which the 160 KiB dynamic ceiling of hipFuncSetAttribute then no longer leaves room for)
+    const bool wave_in = __all(in_window ? 1 : 0) != 0;
+    if ((tid & 63) == 0) L.flags[tid >> 6] = wave_in ? 1.0 : 0.0;
+    __syncthreads();
+    bool all_in = true;
+#pragma unroll
+    for (int w = 0; w < BLOCK / 64; ++w) all_in = all_in && L.flags[w] != 0.0;
+    return (live ? kStageLive : 0) | (all_in ? kStageFast : 0) | (gave_up ? kStageGaveUp : 0);
+}
+
+// One pool: prices from LDS, closed form, trade record, dual scalar, netflow bins.
+template <class Ops, bool MAT, bool GBINS, bool FAST>
+__device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a, const SweepLds& L,
+                                             const typename Ops::Raw& raw_in, int64_t i, double& acc)
+{
+    typename Ops::Raw raw = raw_in;
+    ops.template resolve<GBINS, FAST>(raw, L.gtab);   // packed records: {tokens, fee-table index} -> tokens, fee
+    const int2 tok = ops.tokens(raw);
+    Px px;                                            // v[r.cfmms[i].Ai]
+    px.yg = raw.yg;
+    if constexpr (GBINS) {
+        px.v1 = a.v[tok.x];
+        px.v2 = a.v[tok.y];
+        px.y1 = px.y2 = 0.0;
+        px.dlv = Ops::kNeedsLogPrices ? log(px.v2 / px.v1) : 0.0;   // large markets: v is not staged, one logarithm per pool
+    } else {
+        if constexpr (FAST) {   // {v, rcp_refined(v)} pairs (FAST implies a.stage_y)
+            const double2 a1 = L.vy[tok.x], a2 = L.vy[tok.y];
+            px.v1 = a1.x; px.y1 = a1.y;
+            px.v2 = a2.x; px.y2 = a2.y;
+        } else {                // pairs, or -- markets too wide for them -- the prices alone (a.v_shift = 4 / 3)
+            const char* base = reinterpret_cast<const char*>(L.vy);
+            px.v1 = *reinterpret_cast<const double*>(base + ((size_t)tok.x << a.v_shift));
+            px.v2 = *reinterpret_cast<const double*>(base + ((size_t)tok.y << a.v_shift));
+            px.y1 = px.y2 = 0.0;
+        }
+        px.dlv = 0.0;
+        if constexpr (Ops::kNeedsLogPrices)   // log v staged per token, or -- markets too wide for that row -- one logarithm per pool
+            px.dlv = a.need_logv ? L.lv[tok.y] - L.lv[tok.x] : log(px.v2 / px.v1);
+    }
+    Trade t;
+    double d, l;
+    int dir;
+    dir = ops.template solve_dir<FAST>(raw, px, d, l, t);
+    const double v1 = px.v1, v2 = px.v2;
+    // One direction (the common case): the tendered token's bin gets −d, the received token's +l, the dual scalar
+    // l·v_out − d·v_in -- the reference's expressions (src/router.jl:82, :99) with their zero terms dropped: same bits.
+    // A compact trade record needs two values with a clear sign bit; the tiny negative / −0.0 amounts the reference's
+    // tick arithmetic leaves on degenerate UniV3 boundaries (and anything kDirBoth) take the general path below.
+    const bool one = dir == kDir1 || dir == kDir2;
+    const bool plain = one && (!MAT || !a.compact || (__double2hiint(d) | __double2hiint(l)) >= 0);
+    if (plain) {
+        const bool d1 = dir == kDir1;
+        if (MAT) {
+            if (a.compact) {
+                store_pair(a.Delta + i, d1 ? d : -d, l, a.nt_stores);   // {+Δ₁, Λ₂} or {−Δ₂, Λ₁}: the sign bit carries the direction
+            } else {
+                store_pair(a.Delta + i, d1 ? d : 0.0, d1 ? 0.0 : d, a.nt_stores);
+                store_pair(a.Lambda + i, d1 ? 0.0 : l, d1 ? l : 0.0, a.nt_stores);
+            }
+        }
+        acc += l * (d1 ? v2 : v1) - d * (d1 ? v1 : v2);
+        if constexpr (GBINS) {
+            a.gflow[i] = d1 ? make_double2(0.0 - d, l) : make_double2(l, 0.0 - d);
+        } else {
+            const double f_in = 0.0 - d;                       // Λ − Δ of the tendered token
+            if (f_in != 0.0) atomicAdd(&L.my_bins[d1 ? tok.x : tok.y], f_in);   // ds_add_f64
+            if (l != 0.0) atomicAdd(&L.my_bins[d1 ? tok.y : tok.x], l);
+        }
+        return;
+    }
+    if (dir == kDirNone) {
+        if (MAT) {
+            if (a.compact) {
+                store_pair(a.Delta + i, 0.0, 0.0, a.nt_stores);
+            } else {
+                store_pair(a.Delta + i, 0.0, 0.0, a.nt_stores);
+                store_pair(a.Lambda + i, 0.0, 0.0, a.nt_stores);
+            }
+        }
+        if constexpr (GBINS) a.gflow[i] = make_double2(0.0, 0.0);
+        return;
+    }
+    expand_dir(dir, d, l, t);
+    if (MAT) {
+        if (a.compact) {   // one 16-byte record per pool (see SweepArgs)
+            // a record can carry one direction whose two values have a clear sign bit (NaN payloads survive the
+            // sign flip) while the other direction is exactly +0; everything else -- both directions trading and
+            // the tiny negative / -0.0 values the reference's tick arithmetic produces on degenerate UniV3
+            // boundaries -- takes the overflow rows, so the encoding is lossless bit for bit
+            const int d1h = __double2hiint(t.d1), d2h = __double2hiint(t.d2), l1h = __double2hiint(t.l1), l2h = __double2hiint(t.l2);
+            const int z1 = d2h | __double2loint(t.d2) | l1h | __double2loint(t.l1);   // 0 <=> Δ₂ and Λ₁ are +0.0
+            const int z2 = d1h | __double2loint(t.d1) | l2h | __double2loint(t.l2);   // 0 <=> Δ₁ and Λ₂ are +0.0
+            const bool dir1 = (z1 == 0) & ((d1h | l2h) >= 0);
+            const bool dir2 = (z2 == 0) & ((d2h | l1h) >= 0);
+            double ra = t.d1, rb = t.l2;
+            if (!dir1) {
+                if (dir2) {
+                    ra = -t.d2;          // sign bit set (−0.0 included): direction 2
+                    rb = t.l1;
+                } else {
+                    a.Lambda[i] = make_double2(t.d1, t.d2);
+                    a.Over[i] = make_double2(t.l1, t.l2);
+                    ra = 0.0;
+                    rb = -1.0;
+                }
+            }
+            store_pair(a.Delta + i, ra, rb, a.nt_stores);
+        } else {
+            store_pair(a.Delta + i, t.d1, t.d2, a.nt_stores);
+            store_pair(a.Lambda + i, t.l1, t.l2, a.nt_stores);
+        }
+    }
+    // src/router.jl:82  dot(Λ, v[Ai]) - dot(Δ, v[Ai])
+    acc += (t.l1 * v1 + t.l2 * v2) - (t.d1 * v1 + t.d2 * v2);
+    // src/router.jl:99 / :115  G[Ai] .+= Λ .- Δ
+    const double f1 = t.l1 - t.d1, f2 = t.l2 - t.d2;
+    if constexpr (GBINS) {
+        a.gflow[i] = make_double2(f1, f2);
+    } else {
+        if (f1 != 0.0) atomicAdd(&L.my_bins[tok.x], f1);   // ds_add_f64
+        if (f2 != 0.0) atomicAdd(&L.my_bins[tok.y], f2);
+    }
+}
+
+// The tile loop of one pool family over a block's share of a segment: lane tid takes pools
+// (bid + k·nblocks)·BLOCK + tid, k = 0, 1, ...  Returns this lane's dual-scalar part.
+// The first tile's pool state is requested BEFORE v and the bins are staged in LDS, so that HBM round trip is not
+// exposed behind the staging barrier.  Tile order alternates between consecutive sweeps (a.reverse): block-strided
+// "phases" are walked first-to-last by one sweep and last-to-first by the next, so each sweep begins on the pool data
+// the previous one touched last -- the part that is still in the XCD's 4 MB L2 (a forward-only walk over a
+// 5.5 MB-per-XCD working set is the LRU worst case: 0 % hits; measured on a plain read stream of the
+// same 44 MB: 9.6 -> 6.9 us, profiles/r02_launch_floor.txt).
+// Requesting tile k+1 before tile k is solved (Ops::kPrefetch, single-family launches): +-0.1 us cache-warm, -4..-6 %
+// HBM-resident on the two-coin families at +6..8 VGPRs (round 3 measured the same and dropped it for the registers; since round 4's per-kernel
+// arithmetic they are free: profiles/r04_ab_prefetch_stores.txt); +4 % on the multi-tick UniV3 walk, which keeps the plain loop.
+template <class Ops, bool MAT, int BLOCK, bool GBINS, bool FAST, bool PREFETCH>
+__device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, const SweepLds& L, typename Ops::Raw cur,
+                                          int64_t i, int64_t step, int64_t left, double& acc)
+{
+    if constexpr (PREFETCH) {
+        // tile k+1's pool state is requested before tile k is solved: two tiles' loads in flight per lane
+        bool ok = left > 0;
+        while (ok) {
+            const bool more = left > 1;
+            typename Ops::Raw nxt = cur;
+            if (more) nxt = ops.template load<GBINS>(i + step);
+            process_pool<Ops, MAT, GBINS, FAST>(ops, a, L, cur, i, acc);
+            i += step;
+            --left;
+            ok = more;
+            cur = nxt;
+        }
+    } else {
+        bool ok = left > 0;
+        while (ok) {
+            process_pool<Ops, MAT, GBINS, FAST>(ops, a, L, cur, i, acc);
+            i += step;
+            ok = --left > 0;
+            if (ok) cur = ops.template load<GBINS>(i);
+        }
+    }
+}
+
+// FASTK selects the arithmetic of the WHOLE kernel (round 4).  Rounds 1-3 compiled both tile loops into every kernel and
+// chose per block; the two copies cost 12-36 VGPRs over the larger of the two alone (ProductTwoCoin 70 vs 56 / 58,
+// UniV3 84 vs 63 / 63, the fused materialising launch 116 vs 80 / 97: profiles/r04_kernel_resources.txt), i.e. one to
+// three wavefronts per SIMD.  Now the HOST picks the kernel wherever it can:
+//   kArithFull  the compiler's full-range sequences (fast_math = 0, pool constants or prices outside the window);
+//   kArithFast  the fast arithmetic: every pool constant of the launch is inside the window (Segment::fast_ok, checked at
+//               upload) and so are the prices -- which the host KNOWS (host-pointer sweeps, cfmm_route).  Every block still
+//               checks the prices it stages; outside the window it does NOT compute: it poisons its row (NaN in every column
+//               -- an error, never a wrong number) and reports kFlagWindow (reachable only through a pre-armed launch whose
+//               host-side check raced; abi_sweep.cpp cancels such launches before they run);
+//   kArithAuto  round 5, device-pointer sweeps (cfmm_sweep_dev): the library cannot see these prices, so the kernel carries
+//               BOTH tile loops and every block chooses from the prices it staged (block-uniform, and the same choice in every
+//               block: all stage the same vector) -- prices outside the window, NaN included, take the full-range loop and
+//               behave like the reference's arithmetic, instead of round 4's "refuse, report on a later call" protocol
+//               (ADVICE r4, medium).  Costs the registers of rounds 1-3 again, which the default geometry (4 wavefronts per
+//               SIMD) never needed.
+constexpr int kArithFull = 0, kArithFast = 1, kArithAuto = 2;
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
+__device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a, const SweepLds& L, int bid, int nblocks,
+                                              bool& poison, bool& live)
+{
+    static_assert(!(GBINS && FASTK != kArithFull), "large-market mode runs on the compiler's sequences");
+    double acc = 0.0;
+    const int64_t stride = (int64_t)nblocks * BLOCK;
+    const int64_t i0 = (int64_t)bid * BLOCK + threadIdx.x;
+    int64_t left = i0 < a.m ? (a.m - i0 + stride - 1) / stride : 0;      // tiles of this lane
+    const int64_t step = a.reverse ? -stride : stride;
+    const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
+    typename Ops::Raw cur = {};
+    if (left > 0) cur = ops.template load<GBINS>(i);
+    const int staged = stage_prices<BLOCK, GBINS>(a, L);
+    poison = (staged & kStageLive) == 0;              // a pre-armed launch that is not needed (or gave up)
+    live = !poison || (staged & kStageGaveUp) != 0;   // false: CANCELLED by the host (a launch that gave up waiting still reports NaN)
+    if (staged & kStageGaveUp) report(a, kFlagGaveUp);
+    if (FASTK == kArithFast && !poison && (staged & kStageFast) == 0) {
+        poison = true;                                // prices outside the window of this kernel's arithmetic
+        report(a, kFlagWindow);
+    }
+    if (poison) left = 0;
+    // next-tile prefetch: single-family launches of the two-coin families (HBM-resident -4..-6 %, cache-warm +-0.1 us); the
+    // fused multi-family launch keeps the plain loop (same-box A/B on config3: -2 % HBM-resident but +1.5 % on the warm step)
+    constexpr bool kPre = Ops::kPrefetch && !MULTI;
+    if constexpr (FASTK == kArithAuto) {
+        if (staged & kStageFast) tile_loop<Ops, MAT, BLOCK, GBINS, true, kPre>(ops, a, L, cur, i, step, left, acc);
+        else tile_loop<Ops, MAT, BLOCK, GBINS, false, kPre>(ops, a, L, cur, i, step, left, acc);
+    } else {
+        tile_loop<Ops, MAT, BLOCK, GBINS, FASTK == kArithFast, kPre>(ops, a, L, cur, i, step, left, acc);
+    }
+    return acc;
+}
+
+// Block epilogue: fold the dual scalar (lanes by wave shuffles, waves through LDS, fixed order), fold
+// the bin copies in a fixed order and write the block's partial row.
+// Column j of a single-block launch's result, straight to its consumer (SweepArgs::direct): a plain store for device
+// consumers, or the column's two self-validating granules {tag, 32 bits} as ONE 16-byte system-scope store -- adjacent lanes
+// write adjacent columns, so a wavefront's store covers full 64-byte lines on the PCIe side (see fold_finish).
+typedef unsigned long long u2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void publish_column(const SweepArgs& a, int j, double val)
+{
+    if (a.direct_host.gran) {
+        const unsigned long long tag = (a.direct_host.tag & 0xffffffffull) << 32, u = (unsigned long long)__double_as_longlong(val);
+        u2v g = {tag | (u & 0xffffffffull), tag | (u >> 32)};
+        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(a.direct_host.gran + 2 * (size_t)j), "v"(g) : "memory");
+    } else {
+        a.direct_out[j] = val;
+    }
+}
+
+template <int BLOCK, bool GBINS>
+__device__ __forceinline__ void finish_row(const SweepArgs& a, const SweepLds& L, double acc, int row_id, bool poison, bool publish)
+{
+    const double nan = __builtin_nan("");
+    if (poison) acc = nan;                               // every column of a poisoned row is NaN: whoever folds it sees an error
+    constexpr int kWaves = BLOCK / 64;
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((tid & 63) == 0) L.wsum[wave] = acc;
+    __syncthreads();
+
+    const int n_cols = GBINS ? 0 : a.n;                  // Ψ columns of the partial row
+    if (!GBINS && a.direct) {
+        // the only block of its launch: the row is the result.  A cancelled pre-armed launch publishes nothing (the fold of
+        // such an evaluation returns without output as well: the host has moved on and may reuse the sequence tag)
+        if (!publish) return;
+        for (int j = tid; j < n_cols; j += BLOCK) {
+            double s = L.bins[j];
+            for (int c = 1; c < a.copies; ++c) s += L.bins[(size_t)c * a.n_pad + j];
+            publish_column(a, j, poison ? nan : s);
+        }
+        if (tid == 0) {
+            double s = L.wsum[0];
+            for (int w = 1; w < kWaves; ++w) s += L.wsum[w];
+            publish_column(a, n_cols, poison ? nan : s);
+        }
+        return;
+    }
+    double* row = a.partials + (size_t)row_id * a.row_pitch;   // 128-byte aligned rows (SweepArgs::row_pitch)
+    for (int j = tid; j < n_cols; j += BLOCK) {
+        double s = L.bins[j];
+        for (int c = 1; c < a.copies; ++c) s += L.bins[(size_t)c * a.n_pad + j];
+        store_row(row + j, poison ? nan : s);
+    }
+    if (tid == 0) {
+        double s = L.wsum[0];
+        for (int w = 1; w < kWaves; ++w) s += L.wsum[w];
+        store_row(row + n_cols, poison ? nan : s);
+    }
+}
+
+// One block's share of ONE segment: tiles bid, bid+nblocks, ... of the segment's pools; its partial
+// row goes to partials[row_id].
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
+__device__ __forceinline__ void sweep_body(const Ops& ops, const SweepArgs& a, int bid, int nblocks, int row_id)
+{
+    const SweepLds L = carve_lds<BLOCK, GBINS>(a);
+    bool poison, live;
+    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, bid, nblocks, poison, live);
+    finish_row<BLOCK, GBINS>(a, L, acc, row_id, poison, live);
+}
+
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK>
+__global__ __launch_bounds__(BLOCK) void sweep_kernel(Ops ops, SweepArgs a)
+{
+    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(ops, a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+}
+
+// Several segments (pool families) in ONE launch, so HBM-bound ProductTwoCoin blocks and ALU-bound GeometricMean /
+// UniV3 blocks are co-resident on every CU and overlap, and the sweep pays one launch + one kernel boundary instead of nseg.
+template <bool MAT, int BLOCK, bool GBINS, int FASTK>
+__global__ __launch_bounds__(BLOCK) void sweep_multi(MultiArgs ma)
+{
+    const int bidx = (int)blockIdx.x;
+    int sidx, local, nblocks;
+    if (ma.xcd_map) {
+        // XCD-aware, cost-weighted block -> segment map.  Blocks are dealt round-robin to the 8 XCDs (block
+        // b runs on XCD b % 8), so "segment = b % nseg" would put ALL blocks of one pool family on the same
+        // XCDs (nseg = 2: ProductTwoCoin on XCDs 0,2,4,6, GeometricMean on 1,3,5,7 -- half the chip does all
+        // the arithmetic).  Here the 8 blocks of one deal (one per XCD) share a segment, consecutive deals
+        // walk through a 32-entry pattern in which segment s appears seg_w[s] times (its share of the
+        // launch's work: pools x cost per pool, so that all blocks finish together), and the pattern is
+        // rotated by one every 32 deals (one pass over an XCD's 32 CUs), so every XCD -- and, as the
+        // dispatcher fills CUs in order, every CU -- hosts all families.  Placement is only a performance
+        // assumption: any placement computes the same result.
+        const int x = bidx & 7, j = bidx >> 3, q = j >> 5, p = (j + q) & 31;
+        sidx = ma.pattern[p];
+        const int w = ma.seg_w[sidx];
+        local = (q * w + ma.rank[p]) * 8 + x;
+        nblocks = ((int)gridDim.x >> 8) * w * 8;
+    } else {   // small grids (not a multiple of 256 blocks): block b -> segment b % nseg
+        nblocks = (int)gridDim.x / ma.nseg;
+        sidx = bidx % ma.nseg;
+        local = bidx / ma.nseg;
+    }
+    const MultiSeg& sg = ma.seg[sidx];
+    SweepArgs a = ma.common;
+    a.m = sg.m;
+    a.Delta = sg.Delta;
+    a.Lambda = sg.Lambda;
+    a.Over = sg.Over;
+    a.gflow = sg.gflow;
+    switch (sg.kind) {
+    case 0:
+        sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(ProductOps{sg.pools.p}, a, local, nblocks, bidx);
+        break;
+    case 1: // log-space forms only; geomean_exact routers are swept by per-segment launches
+        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(GeoMeanLogOps{sg.pools.g}, a, local, nblocks, bidx);
+        break;
+    default:
+        sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(UniV3Ops{sg.pools.u}, a, local, nblocks, bidx);
+        break;
+    }
+}
+
+} // namespace cfmm

@@ -1,6 +1,6 @@
 // curve_host.cpp -- TEST-ONLY host build of the Curve (StableSwap) per-pool solve: curve_pool.h's curve_solve<N>, the very
 // template sweep_ncoin<CurveFamily> runs on the device, for N = 2..8, with the same inputs (log R and log β as the upload
-// computes them: curve_solve_lbeta; pools it refuses, curve_in_range at α > 0, are flagged and get NaN trades) and the same turn of log r into trades as curve_pool in sweep_kernels.hip.  Only exp, log and expm1 differ
+// computes them: curve_solve_lbeta; pools it refuses, curve_in_range at α > 0, are flagged and get NaN trades) and the same turn of log r into trades as curve_pool in sweep_ncoin.h.  Only exp, log and expm1 differ
 // from the device (the host's libm here).  Built and loaded (ctypes) by tests/test_curve_precise_cpu.py with the
 // Makefile's host flags.
 #include <cmath>

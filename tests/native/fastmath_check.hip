@@ -1,5 +1,6 @@
-// fastmath_check.hip -- the claim behind the sweep's fast arithmetic (sweep_kernels.hip: rcp_refined / div_by /
-// fast_sqrt), checked on the device against the compiler's own IEEE sequences: for operands inside
+// fastmath_check.hip -- the claim behind the sweep's fast arithmetic (csrc/fast_arith.h: rcp_refined / div_by /
+// fast_sqrt, included here: the very functions the kernels call), checked on the device against the compiler's own
+// IEEE sequences: for operands inside
 // [2^-150, 2^150] (products / quotients of such operands included, as they occur in the closed forms of
 // src/cfmms.jl:125-126, :321-337) the quotient and the square root are THE SAME BITS, over N random operand pairs
 // per launch.  Compiled and run by tests/test_gpu_fastmath.py (hipcc is part of the image on the GPU box).
@@ -7,6 +8,8 @@
 // with the device library's exp over |x| <= 320 (ulp distance) and, on a sample, with the host's long-double expl.
 // Prints "FASTMATH_CHECK pairs=<n> div_mismatch=<k> sqrt_mismatch=<k> zero_mismatch=<k> exp_max_ulp_vs_lib=<k>
 // exp_over_1ulp_vs_lib=<k> exp_max_err_ulp_vs_expl=<x>".
+#include "fast_arith.h"
+
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,59 +18,7 @@
 #include <cstdlib>
 #include <vector>
 
-__device__ __forceinline__ double rcp_refined(double b)
-{
-    double y = __builtin_amdgcn_rcp(b);
-    double e = __builtin_fma(-b, y, 1.0);
-    y = __builtin_fma(y, e, y);
-    e = __builtin_fma(-b, y, 1.0);
-    return __builtin_fma(y, e, y);
-}
-__device__ __forceinline__ double div_by(double a, double b, double yb)
-{
-    const double q = a * yb;
-    const double r = __builtin_fma(-b, q, a);
-    return __builtin_fma(r, yb, q);
-}
-__device__ __forceinline__ double fast_sqrt(double x)
-{
-    const double y = __builtin_amdgcn_rsq(x);
-    double s = x * y;
-    double h = y * 0.5;
-    const double r = __builtin_fma(-h, s, 0.5);
-    s = __builtin_fma(s, r, s);
-    double d = __builtin_fma(-s, s, x);
-    h = __builtin_fma(h, r, h);
-    s = __builtin_fma(d, h, s);
-    d = __builtin_fma(-s, s, x);
-    return __builtin_fma(d, h, s);
-}
-
-__device__ __forceinline__ double fma_sc(double x, double acc, double c)
-{
-    double r;
-    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(x), "v"(acc), "s"(c));
-    return r;
-}
-__device__ __forceinline__ double fast_exp(double x)
-{
-    const double k = __builtin_rint(x * 0x1.71547652b82fep+0);
-    double r = __builtin_fma(-k, 0x1.62e42fefa39efp-1, x);
-    r = __builtin_fma(-k, 0x1.abc9e3b39803fp-56, r);
-    double p = 0x1.af39091a8441ap-26;
-    p = fma_sc(r, p, 0x1.2891d2ecb3ed9p-22);
-    p = fma_sc(r, p, 0x1.71de0d863c737p-19);
-    p = fma_sc(r, p, 0x1.a019b8cbe6585p-16);
-    p = fma_sc(r, p, 0x1.a01a01a7ce75dp-13);
-    p = fma_sc(r, p, 0x1.6c16c1789caa1p-10);
-    p = fma_sc(r, p, 0x1.11111111109a6p-7);
-    p = fma_sc(r, p, 0x1.5555555553d38p-5);
-    p = fma_sc(r, p, 0x1.5555555555556p-3);
-    p = fma_sc(r, p, 0x1.0000000000001p-1);
-    p = __builtin_fma(r, p, 1.0);
-    p = __builtin_fma(r, p, 1.0);
-    return __builtin_ldexp(p, (int)k);
-}
+using namespace cfmm;   // rcp_refined, div_by, fast_sqrt, fast_exp: the functions the sweep kernels call
 
 __device__ __forceinline__ uint64_t splitmix(uint64_t& s)
 {

@@ -1,4 +1,4 @@
-"""The arithmetic claim behind option "fast_math": rcp_refined / div_by / fast_sqrt of sweep_kernels.hip return the
+"""The arithmetic claim behind option "fast_math": rcp_refined / div_by / fast_sqrt of csrc/fast_arith.h return the
 bits of the compiler's IEEE / and sqrt for every operand inside the window -- tests/native/fastmath_check.hip, a
 stand-alone HIP program (2^30 random operand pairs on the MI355X)."""
 import os
@@ -8,10 +8,11 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "native", "fastmath_check.hip")
+CSRC = os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc")   # fast_arith.h: the functions under test
 
 
 def _build(exe):
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", SRC, "-o", exe], check=True)
+    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-I", CSRC, SRC, "-o", exe], check=True)
 
 
 def test_fastmath_check_compiles(tmp_path):
