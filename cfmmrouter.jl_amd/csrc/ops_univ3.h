@@ -244,6 +244,9 @@ struct UniV3OpsT {
             sd += dj;
             sl += lj;
             if (jump && price > thr_j * (1.0 + 0x1p-40)) break;            // the next tick cannot be entered (see above)
+            // (a safety net, never seen to trigger: on every fixture and parity row, targets 0..3 ulps beside a boundary included,
+            //  the reference itself enters no tick after a partial one, so a band of 0 gives the same bits --
+            //  tests/test_cp_precise_cpu.py::test_no_tick_is_entered_after_a_partial_one; the band is NOT covered by a failing mutant)
         }
         d = FAST ? div_by_signed_zero(sd, g, yg) : sd / g;                 // :366-372 / :386-391
         l = sl;

@@ -1,4 +1,5 @@
 """Shared test helpers: bridge between the host mirror's PoolBatch containers and the CPU oracle."""
+import ctypes
 import math
 
 import numpy as np
@@ -137,3 +138,40 @@ def reduction_checks(c, rows, D, L, psi, acc, kk, bD, bL, check_self=True):
     terms = np.concatenate([Lt * vl, -(Dt * vl)])
     red = (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
     assert abs(acc - math.fsum(terms)) <= np.sum(per * vl) + red
+
+
+def hip_runtime():
+    """The HIP runtime the library already loaded, for tests that hand the library device pointers."""
+    import cfmmrouter_amd._lib as lib
+    lib.lib()
+    path = None
+    with open("/proc/self/maps") as f:
+        for line in f:
+            if "libamdhip64.so" in line:
+                path = line.split()[-1]
+                break
+    assert path, "libamdhip64 is not loaded"
+    h = ctypes.CDLL(path)
+    h.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    h.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    h.hipFree.argtypes = [ctypes.c_void_p]
+    return h
+
+
+def dev_sweep(be, v, materialize=True):
+    """One device-pointer sweep (cfmm_sweep_dev) of the backend's pools at prices v -> (Ψ, acc)."""
+    h = hip_runtime()
+    n = len(v)
+    dv, dout = ctypes.c_void_p(), ctypes.c_void_p()
+    assert h.hipMalloc(ctypes.byref(dv), 8 * n) == 0 and h.hipMalloc(ctypes.byref(dout), 8 * (n + 1)) == 0
+    try:
+        vh = np.ascontiguousarray(v, dtype=np.float64)
+        out = np.empty(n + 1)
+        assert h.hipMemcpy(dv, vh.ctypes.data, 8 * n, 1) == 0
+        be.ctx.sweep_dev(dv.value, dout.value, materialize)
+        assert h.hipDeviceSynchronize() == 0
+        assert h.hipMemcpy(out.ctypes.data, dout, 8 * (n + 1), 2) == 0
+        return out[:n], float(out[n])
+    finally:
+        h.hipFree(dv)
+        h.hipFree(dout)
