@@ -121,6 +121,7 @@ def lib():
     L.cfmm_eval.argtypes = [_ctx, _f64p, _f64p, _f64p]
     L.cfmm_get_trades.argtypes = [_ctx, _f64p, _f64p]
     L.cfmm_get_trades_range.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_int64, _f64p, _f64p]
+    L.cfmm_select_trades.argtypes = [_ctx, C.c_int32, _f64p, C.c_double, C.c_int64, _i64p, _i64p, _f64p, _f64p, _f64p]
     L.cfmm_netflows.argtypes = [_ctx, _f64p]
     L.cfmm_dual_value.argtypes = [_ctx, _f64p]
     L.cfmm_update_reserves.argtypes = [_ctx]
@@ -357,6 +358,40 @@ class Context:
         D, Lm = np.empty((count, n_coins)), np.empty((count, n_coins))
         self._check(self._L.cfmm_get_trades_range(self._h, int(seg), int(first), int(count), ptr(D), ptr(Lm)))
         return D, Lm
+
+    def select_trades(self, seg, min_value=0.0, v=None, capacity=None, n_coins=2):
+        """The rows of segment `seg` that trade in the latest materialising sweep and are worth at least min_value, compacted
+        on the device (cfmm_select_trades) -> (idx, Δ, Λ, value): rows within the segment in ascending order, their
+        [count, n_coins] trade rows and value = Σ_k (Λ_k − Δ_k)·v[A_k].  v=None: the prices of that sweep.  capacity=None
+        starts at min(m, 65536) rows and repeats the call once with the returned count if that was too small; an explicit
+        capacity returns the first min(count, capacity) rows (the count itself: select_count)."""
+        if capacity is not None and int(capacity) < 0:
+            raise ArgumentError("capacity must be >= 0")
+        if v is not None:
+            v = f64(v)
+            if v.size != self.n_tokens:
+                raise ArgumentError("v must have n_tokens entries")
+        n_coins = int(n_coins)
+        cap = min(int(self.segments()[int(seg)]["m"]), 65536) if capacity is None else int(capacity)
+        while True:
+            idx, val = np.empty(cap, dtype=np.int64), np.empty(cap)
+            D, Lm = np.empty((cap, n_coins)), np.empty((cap, n_coins))
+            count = C.c_int64()
+            self._check(self._L.cfmm_select_trades(self._h, int(seg), ptr(v), float(min_value), cap, C.byref(count),
+                                                   ptr(idx), ptr(D), ptr(Lm), ptr(val)))
+            if count.value <= cap or capacity is not None:
+                k = min(count.value, cap)
+                return idx[:k], D[:k], Lm[:k], val[:k]
+            cap = count.value
+
+    def select_count(self, seg, min_value=0.0, v=None) -> int:
+        """How many rows select_trades would return (cfmm_select_trades with capacity 0: nothing is copied)."""
+        v = None if v is None else f64(v)
+        if v is not None and v.size != self.n_tokens:
+            raise ArgumentError("v must have n_tokens entries")
+        count = C.c_int64()
+        self._check(self._L.cfmm_select_trades(self._h, int(seg), ptr(v), float(min_value), 0, C.byref(count), None, None, None, None))
+        return count.value
 
     def netflows(self):
         psi = np.empty(self.n_tokens)

@@ -288,6 +288,17 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
         for (const cfmm_ctx* child : c->shards) *value += child->pool_update_regrows;
         return CFMM_OK;
     }
+    // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
+    // option "time_kernels" (a parent reports its first shard's)
+    if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }
+    if (key && !std::strcmp(key, "select_scan_chunk")) { *value = kSelScanChunk; return CFMM_OK; }
+    for (int k = 0; k < 3; ++k) {
+        static const char* const names[3] = {"select_flag_ns", "select_scan_ns", "select_emit_ns"};
+        if (key && !std::strcmp(key, names[k])) {
+            *value = c->shards.empty() ? c->sel_ns[k] : c->shards[0]->sel_ns[k];
+            return CFMM_OK;
+        }
+    }
 #ifdef CFMM_TEST_HOOKS
     if (key && !std::strcmp(key, "debug_live_allocs")) {   // read-only, process-wide: device allocations made and not yet released
         *value = g_live_allocs.load();

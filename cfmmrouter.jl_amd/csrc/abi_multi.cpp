@@ -163,4 +163,36 @@ int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t coun
     return CFMM_OK;
 }
 
+// cfmm_select_trades on a parent: the shards that hold rows of `seg`, in device order (= pool order); every shard gets the
+// capacity that is left, its rows within the segment are its own plus the shard's first row, and every count is summed.
+int multi_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_value, int64_t capacity, int64_t* count, int64_t* idx,
+                        double* Delta, double* Lambda, double* value)
+{
+    if (!c->have_trades) return fail(c, CFMM_ERR_STATE, "no materialised trades: call cfmm_find_arb first");
+    if (seg < 0 || seg >= (int32_t)c->psegs.size()) return fail(c, CFMM_ERR_INVALID_ARG, "segment out of range");
+    if (capacity < 0 || !count) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_select_trades: capacity must be >= 0 and count non-null");
+    const int64_t m = c->psegs[(size_t)seg].m;
+    const int nc = c->psegs[(size_t)seg].n_coins;
+    const int nd = (int)c->shards.size();
+    int64_t total = 0, written = 0;
+    for (int d = 0; d < nd; ++d) {
+        int64_t lo, hi;
+        shard_range(m, d, nd, lo, hi);
+        if (hi == lo) continue;
+        cfmm_ctx* child = c->shards[(size_t)d];
+        int64_t got = 0;
+        const int rc = cfmm_select_trades(child, child_segment(c, seg, d), v, min_value, capacity - written, &got,
+                                          idx ? idx + written : nullptr, Delta ? Delta + nc * written : nullptr,
+                                          Lambda ? Lambda + nc * written : nullptr, value ? value + written : nullptr);
+        if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s", d, child->err.c_str());
+        const int64_t rows = std::min(got, capacity - written);
+        if (idx)
+            for (int64_t j = 0; j < rows; ++j) idx[written + j] += lo;
+        written += rows;
+        total += got;
+    }
+    *count = total;
+    return CFMM_OK;
+}
+
 } // namespace cfmm

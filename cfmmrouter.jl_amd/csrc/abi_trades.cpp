@@ -158,6 +158,12 @@ void free_trade_staging(cfmm_ctx* c)
         t.stream[k] = nullptr;
     }
     t.ready = false;
+    if (c->h_sel_total) (void)hipHostFree(c->h_sel_total);
+    c->h_sel_total = c->d_sel_total = nullptr;
+    for (hipEvent_t& e : c->sel_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
 }
 
 } // namespace cfmm
@@ -198,6 +204,103 @@ int cfmm_get_trades(cfmm_ctx* c, double* Delta, double* Lambda)
         const int rc = download_segment(c, s, 0, s.m, Delta ? Delta + s.flat_off : nullptr, Lambda ? Lambda + s.flat_off : nullptr);
         if (rc != CFMM_OK) return rc;
     }
+    return CFMM_OK;
+}
+
+// Three launches on the context's stream behind the sweep (select_kernels.h), one synchronisation, then exactly
+// min(count, capacity) rows of every requested output come back.  Reads the trades; changes nothing the other calls see.
+int cfmm_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_value, int64_t capacity, int64_t* count, int64_t* idx,
+                       double* Delta, double* Lambda, double* value)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (!c->shards.empty()) return multi_select_trades(c, seg, v, min_value, capacity, count, idx, Delta, Lambda, value);
+    if (!c->have_trades) return fail(c, CFMM_ERR_STATE, "no materialised trades: call cfmm_find_arb first");
+    if (seg < 0 || seg >= (int32_t)c->segs.size()) return fail(c, CFMM_ERR_INVALID_ARG, "segment out of range");
+    if (capacity < 0 || !count) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_select_trades: capacity must be >= 0 and count non-null");
+    if (!v) {
+        if ((int)c->trade_v.size() != c->n)
+            return fail(c, CFMM_ERR_STATE, "cfmm_select_trades: v is null and the trades come from cfmm_sweep_dev, whose prices the "
+                                           "library has not seen: pass the prices to value the trades at");
+        v = c->trade_v.data();
+    }
+    const Segment& s = c->segs[(size_t)seg];
+    *count = 0;
+    if (s.m == 0) return CFMM_OK;
+    const bool ragged = ragged_kind(s.kind);
+    const int nc = ragged ? s.n_coins : 2;
+    const size_t blocks = (size_t)select_blocks(s.m);
+    const int64_t rows = std::min(capacity, s.m);   // what the emit may write
+    const bool emit = rows > 0 && (idx || Delta || Lambda || value);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = c->d_sel_mask.grow(c, blocks * (kSelBlock / 64))) || (rc = c->d_sel_counts.grow(c, blocks)) ||
+        (rc = c->d_sel_base.grow(c, blocks)) || (rc = c->d_sel_v.grow(c, (size_t)c->n)))
+        return rc;
+    if (emit && ((idx && (rc = c->d_sel_idx.grow(c, (size_t)rows))) || (Delta && (rc = c->d_sel_D.grow(c, (size_t)rows * nc))) ||
+                 (Lambda && (rc = c->d_sel_L.grow(c, (size_t)rows * nc))) || (value && (rc = c->d_sel_value.grow(c, (size_t)rows)))))
+        return rc;
+    if (!c->h_sel_total) {
+        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sel_total), 128, hipHostMallocMapped));
+        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_sel_total), c->h_sel_total, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipHostFree(c->h_sel_total);
+            c->h_sel_total = c->d_sel_total = nullptr;
+            return fail(c, CFMM_ERR_HIP, "cfmm_select_trades: pinned host memory is not device-mapped");
+        }
+    }
+    const bool timed = c->opt_time_kernels != 0;
+    if (timed)
+        for (hipEvent_t& e : c->sel_ev)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    // the prices: uploaded per call (n doubles; a pageable source is staged by the runtime before the call returns)
+    HIP_TRY(c, hipMemcpyAsync(c->d_sel_v.get(), v, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    SelectArgs a{};
+    a.m = s.m;
+    a.n_coins = nc;
+    a.v = c->d_sel_v.get();
+    a.min_value = min_value;
+    if (ragged) {
+        a.ncD = s.nc.D.get();
+        a.ncL = s.nc.L.get();
+        a.nctok = s.nc.tok.get();
+    } else {
+        a.Delta = c->d_delta.get() + s.trade_off;
+        a.Lambda = c->d_lambda.get() + s.trade_off;
+        a.Over = c->d_over.get() + s.trade_off;
+        a.compact = c->trades_compact;
+        a.pk = s.pk.get();
+        a.Ai = s.Ai.get();
+    }
+    a.mask = c->d_sel_mask.get();
+    a.counts = c->d_sel_counts.get();
+    a.base = c->d_sel_base.get();
+    a.capacity = rows;
+    a.out_idx = idx ? c->d_sel_idx.get() : nullptr;
+    a.out_D = Delta ? c->d_sel_D.get() : nullptr;
+    a.out_L = Lambda ? c->d_sel_L.get() : nullptr;
+    a.out_value = value ? c->d_sel_value.get() : nullptr;
+    *c->h_sel_total = -1;
+    hipError_t e = launch_select_count(a, ragged, c->d_sel_total, c->stream, timed ? c->sel_ev : nullptr);
+    if (e == hipSuccess && emit) e = launch_select_emit(a, ragged, c->stream, timed ? c->sel_ev : nullptr);
+    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "select launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int64_t total = *static_cast<volatile long long*>(c->h_sel_total);
+    if (total < 0 || total > s.m) return fail(c, CFMM_ERR_HIP, "cfmm_select_trades: the count did not arrive");
+    if (timed)
+        for (int k = 0; k < 3; ++k) {
+            float ms = 0.f;
+            c->sel_ns[k] = 0;
+            if (k == 2 && !emit) continue;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c->sel_ev[2 * k], c->sel_ev[2 * k + 1]));
+            c->sel_ns[k] = (int64_t)((double)ms * 1e6);
+        }
+    *count = total;
+    const size_t w = (size_t)std::min(total, rows);   // rows to copy back: exactly these, and nothing when there are none
+    if (!emit || w == 0) return CFMM_OK;
+    if (idx) HIP_TRY(c, hipMemcpy(idx, c->d_sel_idx.get(), w * sizeof(long long), hipMemcpyDeviceToHost));
+    if (Delta) HIP_TRY(c, hipMemcpy(Delta, c->d_sel_D.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (Lambda) HIP_TRY(c, hipMemcpy(Lambda, c->d_sel_L.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (value) HIP_TRY(c, hipMemcpy(value, c->d_sel_value.get(), w * sizeof(double), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }
 

@@ -8,7 +8,8 @@
 //   launch_plan.cpp   the launch geometry of one evaluation, as a pure function (launch_plan.h: no HIP, no context)
 //   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold, host-pointer
 //                     sweeps, pre-armed evaluations
-//   abi_trades.cpp    trade download / device views, update_reserves!, reserves / prices read-back
+//   abi_trades.cpp    trade download / device views, the selection of the trades worth executing, update_reserves!,
+//                     reserves / prices read-back
 //   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
@@ -264,6 +265,21 @@ struct cfmm_ctx {
     bool upd_busy = false;
     int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
 
+    // cfmm_select_trades (abi_trades.cpp, select_kernels.h): scratch, the device copy of the valuing prices and the compacted
+    // rows, grown on demand and kept for the next call; the scan delivers the count to one pinned, device-mapped word
+    cfmm::DevBuf<unsigned long long> d_sel_mask;   // [blocks][kSelBlock / 64]
+    cfmm::DevBuf<int> d_sel_counts;                // [blocks]
+    cfmm::DevBuf<long long> d_sel_base;            // [blocks]
+    cfmm::DevBuf<double> d_sel_v;                  // [n]
+    cfmm::DevBuf<long long> d_sel_idx;             // [rows]
+    cfmm::DevBuf<double> d_sel_D, d_sel_L;         // [rows][n_coins]
+    cfmm::DevBuf<double> d_sel_value;              // [rows]
+    long long* h_sel_total = nullptr;
+    long long* d_sel_total = nullptr;              // device address of h_sel_total
+    hipEvent_t sel_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // option "time_kernels": {start, stop} per kernel
+    int64_t sel_ns[3] = {0, 0, 0};                 // read-only options "select_flag_ns" / "select_scan_ns" / "select_emit_ns": the
+                                                   // latest timed call's kernel spans (emit: 0 when the call only counted)
+
     // kernel timing
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -327,9 +343,11 @@ int multi_host_sweep(cfmm_ctx* c, const double* v, bool materialize);
 int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add, int n_coins = 2);
 int child_segment(const cfmm_ctx* c, int pseg, int d);
 int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t count, double* Delta, double* Lambda);
+int multi_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_value, int64_t capacity, int64_t* count, int64_t* idx,
+                        double* Delta, double* Lambda, double* value);
 
 // abi_trades.cpp
-void free_trade_staging(cfmm_ctx* c);
+void free_trade_staging(cfmm_ctx* c);   // (and the pinned word and events of cfmm_select_trades)
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

@@ -297,6 +297,43 @@ hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s);
 hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const double2* ovB, double2* Delta, double2* Lambda,
                                 int64_t m, hipStream_t s);
 
+// cfmm_select_trades (select_kernels.h, abi_trades.cpp): the rows of ONE segment that trade and are worth min_value, compacted
+// in pool order by three launches.  The view of one call; all pointers are device pointers.
+constexpr int kSelBlock = 256;        // pools per block of select_flag / select_emit: one lane per pool, 4 mask words per block
+constexpr int kSelScanChunk = 1024;   // block counts the single block of select_scan folds per step
+struct SelectArgs {
+    int64_t m;                   // pools of the segment
+    int n_coins;                 // doubles per output row: 2, or the ragged segment's coin count
+    const double* v;             // [n_tokens] the prices the trades are valued at
+    double min_value;
+    // two-coin kinds: the segment's rows of the trade buffers (SweepArgs: plain or compact layout) and its tokens
+    const double2* Delta;
+    const double2* Lambda;
+    const double2* Over;
+    int compact;
+    const PackedFeeTok* pk;      // the packed records, or null: Ai
+    const int2* Ai;
+    // ragged kinds: the coin-major columns ([n_coins][m], NCoinPools)
+    const double* ncD;
+    const double* ncL;
+    const int32_t* nctok;
+    // scratch
+    unsigned long long* mask;    // [blocks][kSelBlock / 64] one bit per pool
+    int* counts;                 // [blocks]
+    long long* base;             // [blocks] exclusive prefix sums of counts
+    // outputs (select_emit): the first `capacity` selected rows; each may be null
+    long long capacity;
+    long long* out_idx;          // [capacity] rows within the segment
+    double* out_D;               // [capacity][n_coins]
+    double* out_L;
+    double* out_value;           // [capacity]
+};
+inline int64_t select_blocks(int64_t m) { return (m + kSelBlock - 1) / kSelBlock; }
+// flag + count, then the scan, which stores the total to *total_host (device address of pinned host memory); `ragged` picks
+// the instantiation.  ev: null, or three {start, stop} pairs for the three kernels (launch_select_emit takes ev[4], ev[5]).
+hipError_t launch_select_count(const SelectArgs& a, bool ragged, long long* total_host, hipStream_t s, hipEvent_t* ev);
+hipError_t launch_select_emit(const SelectArgs& a, bool ragged, hipStream_t s, hipEvent_t* ev);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

@@ -40,6 +40,7 @@
 //   sweep_ncoin.h     weighted_pool, curve_pool (curve_pool.h: the solve), sweep_ncoin
 //   fold_kernels.h    reduce_partials, reduce_gather, gather_chunks, token_fold
 //   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records
+//   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -52,6 +53,7 @@
 #include "sweep_ncoin.h"
 #include "fold_kernels.h"
 #include "update_kernels.h"
+#include "select_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -245,6 +247,29 @@ hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s)
     if (a.total <= 0) return hipSuccess;
     hipLaunchKernelGGL(scatter_records, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+hipError_t launch_select_count(const SelectArgs& a, bool ragged, long long* total_host, hipStream_t s, hipEvent_t* ev)
+{
+    if (a.m <= 0) return hipErrorInvalidValue;
+    long long blocks = select_blocks(a.m);
+    const int* counts = a.counts;
+    long long* base = a.base;
+    void* flag_args[] = {const_cast<SelectArgs*>(&a)};
+    const void* flag = ragged ? reinterpret_cast<const void*>(&select_flag<true>) : reinterpret_cast<const void*>(&select_flag<false>);
+    hipError_t e = launch_k(flag, dim3((unsigned)blocks), dim3(kSelBlock), 0, s, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr, flag_args);
+    if (e != hipSuccess) return e;
+    void* scan_args[] = {&counts, &base, &blocks, &total_host};
+    return launch_k(reinterpret_cast<const void*>(&select_scan), dim3(1), dim3(kSelScanChunk), 0, s, ev ? ev[2] : nullptr,
+                    ev ? ev[3] : nullptr, scan_args);
+}
+
+hipError_t launch_select_emit(const SelectArgs& a, bool ragged, hipStream_t s, hipEvent_t* ev)
+{
+    if (a.m <= 0) return hipErrorInvalidValue;
+    void* args[] = {const_cast<SelectArgs*>(&a)};
+    const void* emit = ragged ? reinterpret_cast<const void*>(&select_emit<true>) : reinterpret_cast<const void*>(&select_emit<false>);
+    return launch_k(emit, dim3((unsigned)select_blocks(a.m)), dim3(kSelBlock), 0, s, ev ? ev[4] : nullptr, ev ? ev[5] : nullptr, args);
 }
 
 hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pitch, double* out, hipStream_t s, const PeerSet& ps,

@@ -35,6 +35,7 @@ class DeviceBackend:
     def __init__(self, n_tokens, batches, device=0):
         self.ctx = Context(n_tokens, device)
         self.n_tokens = int(n_tokens)
+        self._seg_shape = [(len(b), int(b.Ai.shape[1])) for b in batches if len(b)]   # (pools, coins) per device segment
         for b in batches:
             if len(b):
                 _upload(self.ctx, b)
@@ -51,9 +52,21 @@ class DeviceBackend:
     def trades(self, out=None):
         return self.ctx.trades(out)
 
+    def active_trades(self, min_value=0.0):
+        """The pools that trade in the latest find_arb! and are worth at least min_value, selected on the device segment by
+        segment (cfmm_select_trades) -> a list of blocks (idx, Δ, Λ, value): idx = positions in packed (segment) order,
+        ascending; Δ, Λ = [count, coins] rows."""
+        blocks, first = [], 0
+        for seg, (m, coins) in enumerate(self._seg_shape):
+            idx, D, Lm, val = self.ctx.select_trades(seg, min_value, n_coins=coins)
+            blocks.append((idx + first, D, Lm, val))
+            first += m
+        return blocks
+
     def reload(self, batches):
         """Replace the device pool store (used after update_reserves_)."""
         self.ctx.clear()
+        self._seg_shape = [(len(b), int(b.Ai.shape[1])) for b in batches if len(b)]
         for b in batches:
             if len(b):
                 _upload(self.ctx, b)
@@ -134,12 +147,35 @@ class HostSegment:
         pools' trades (the reference overwrites ALL pools' trades in every evaluation; here NONE move between find_arb!s)."""
         psi, acc = np.zeros(self.n_tokens), 0.0
         Ds, Ls = (self.Δs, self.Λs) if materialize else (self._sΔ, self._sΛ)
+        if materialize:
+            self.v = np.array(v, dtype=np.float64)       # the prices self.Δs / self.Λs belong to (active_trades)
         for c, ai, D, L in zip(self.pools, self.Ai0, Ds, Ls):
             vl = v[ai]                                   # v[r.cfmms[i].Ai]
             c.find_arb_(D, L, vl)                        # the user's method: overwrites Δ, Λ
             acc += float(np.dot(L, vl) - np.dot(D, vl))  # src/router.jl:82
             np.add.at(psi, ai, L - D)                    # src/router.jl:99
         return psi, acc
+
+    def active_trades(self, min_value=0.0):
+        """The host-evaluated pools that trade in the latest materialising sweep and are worth at least min_value, by the
+        rule and the arithmetic of cfmm_select_trades: some entry of Δ or Λ compares != 0.0, value = Σ_k (Λ_k − Δ_k)·v[A_k]
+        summed in coin order from +0.0, selected unless value < min_value -> (idx, Δ rows, Λ rows, value), idx = positions
+        among the host pools."""
+        idx, Ds, Ls, vals = [], [], [], []
+        v = getattr(self, "v", None)
+        for j, (ai, D, L) in enumerate(zip(self.Ai0, self.Δs, self.Λs)):
+            if not (np.any(D != 0.0) or np.any(L != 0.0)):
+                continue
+            value = np.float64(0.0)
+            for k in range(ai.size):
+                value = value + (L[k] - D[k]) * v[ai[k]]
+            if value < min_value:
+                continue
+            idx.append(j)
+            Ds.append(D.copy())
+            Ls.append(L.copy())
+            vals.append(value)
+        return np.array(idx, dtype=np.int64), Ds, Ls, np.array(vals, dtype=np.float64)
 
 
 class MixedBackend:
@@ -149,6 +185,7 @@ class MixedBackend:
     def __init__(self, inner, host: HostSegment):
         self.inner, self.host = inner, host
         self.n_tokens = host.n_tokens
+        self.inner_pools = 0      # pools of the inner backend (set by the Router: host positions are numbered behind them)
 
     def _add(self, res, v, materialize):
         psi, acc = res
@@ -163,6 +200,17 @@ class MixedBackend:
 
     def trades(self, out=None):
         return self.inner.trades() if out is None else self.inner.trades(out)
+
+    def active_trades(self, min_value=0.0):
+        """The inner backend's blocks, then the host pools' (their positions follow the inner backend's pools)."""
+        if hasattr(self.inner, "active_trades"):
+            blocks = list(self.inner.active_trades(min_value))
+        elif self.inner_pools == 0:                # every pool of the router is host-evaluated
+            blocks = []
+        else:
+            raise NotImplementedError(f"{type(self.inner).__name__} has no active_trades")
+        idx, Ds, Ls, vals = self.host.active_trades(min_value)
+        return blocks + [(idx + self.inner_pools, Ds, Ls, vals)]
 
     def reload(self, batches):
         self.inner.reload(batches)
@@ -220,6 +268,7 @@ class Router:
         self._host_idx = list(host)
         if self._host is not None:
             self._backend = MixedBackend(self._backend, self._host)
+            self._backend.inner_pools = self._m
         self._psi = np.zeros(self.n_tokens)
         self._acc = 0.0
         # weighted / Curve pools: r.Δs / r.Λs are per-pool vectors (the reference's ragged Vector{Vector}, src/router.jl:7-8)
@@ -534,6 +583,43 @@ def polish_(r: Router, iters=8, jacobian=None, rel_step=1e-7, native=None):
     info["polish"] = {"residual0": res0, "residual": res, "iterations": done, "sweeps": r.n_sweeps - sweeps0}
     r.info = info
     return None
+
+
+def active_trades(r: Router, min_value=0.0):
+    """The short list a router that follows a chain executes: the pools that trade in the latest find_arb! / route! and are
+    worth at least min_value, without fetching r.Δs / r.Λs -> (idx, Δ, Λ, value).
+
+    A pool trades iff some entry of its Δ or Λ compares != 0.0 (−0.0 does not count, NaN does); its value is its term of the
+    dual, Σ_k (Λ_k − Δ_k)·v[A_k] at the prices of that find_arb!, summed in coin order from +0.0 with every operation rounded on
+    its own; it is selected unless value < min_value (min_value = -inf: every trading pool).  The device pools are selected on
+    the device (cfmm_select_trades: three small launches per segment, then only the selected rows cross PCIe); host-evaluated
+    plugin pools are filtered on the host by the same rule and the same arithmetic.
+
+    idx: positions in r.cfmms, ascending.  Δ, Λ: their trade rows -- [count, 2] arrays for routers of two-coin device pools,
+    a list of per-pool vectors otherwise (weighted / Curve pools, host-evaluated pools), as r.Δs is.  value: [count]."""
+    if not hasattr(r._backend, "active_trades"):
+        raise NotImplementedError(f"{type(r._backend).__name__} has no active_trades")
+    blocks = r._backend.active_trades(min_value)
+    order = r._order
+    place = np.concatenate([np.arange(r._m, dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64),
+                            np.asarray(r._host_idx, dtype=np.int64)])   # backend position -> position in r.cfmms
+    idx = place[np.concatenate([b[0] for b in blocks])] if blocks else np.zeros(0, dtype=np.int64)
+    value = np.concatenate([b[3] for b in blocks]) if blocks else np.zeros(0)
+    per_pool = r._ragged or r._host is not None
+    if per_pool:                                   # per-pool vectors, split as _split does
+        Ds = [np.array(row) for b in blocks for row in b[1]]
+        Ls = [np.array(row) for b in blocks for row in b[2]]
+    else:
+        Ds = np.concatenate([b[1] for b in blocks]) if blocks else np.zeros((0, 2))
+        Ls = np.concatenate([b[2] for b in blocks]) if blocks else np.zeros((0, 2))
+    if idx.size and np.any(np.diff(idx) < 0):      # packed (family-grouped) order -> r.cfmms order
+        perm = np.argsort(idx, kind="stable")
+        idx, value = idx[perm], value[perm]
+        if per_pool:
+            Ds, Ls = [Ds[k] for k in perm], [Ls[k] for k in perm]
+        else:
+            Ds, Ls = Ds[perm], Ls[perm]
+    return idx, Ds, Ls, value
 
 
 def netflows_(ψ, r: Router, exact=False):

@@ -234,6 +234,36 @@ int64_t cfmm_trades_len(const cfmm_ctx* ctx);
 int cfmm_get_trades_range(cfmm_ctx* ctx, int32_t seg, int64_t first, int64_t count, double* Delta,
                           double* Lambda);
 
+/* The rows of segment `seg` that trade in the latest materialising sweep and are worth at least min_value,
+ * in pool order: the short list a router that follows a chain executes, compacted ON THE DEVICE (three small launches: flag +
+ * count, scan, emit; no block waits for another) instead of downloading and scanning every pool's rows.
+ *   Rule       pool i trades iff some entry of its Delta or Lambda compares != 0.0 (-0.0 does not count, NaN does).
+ *   Value      value_i = sum_k (Lambda_ik - Delta_ik) * v[A_ik], the pool's term of the dual acc: summed in the pool's coin
+ *              order from +0.0, every subtraction, product and addition rounded on its own (no FMA), so that the host can
+ *              reproduce it bit for bit.
+ *   Selection  a row is selected iff it trades and !(value_i < min_value): a NaN value is never hidden, and
+ *              min_value = -INFINITY selects every trading pool.
+ *   v          n_tokens host doubles, the prices the trades are valued at; not range-checked (NaN propagates into value).
+ *              NULL: the prices of the latest materialising host-pointer sweep (cfmm_find_arb, cfmm_route).  After a
+ *              materialising cfmm_sweep_dev the library has not seen the prices: NULL is then CFMM_ERR_STATE, an explicit v works.
+ *   Outputs    *count = the number of selected rows, whatever `capacity` is.  The first min(count, capacity) selected rows, in
+ *              ascending pool order, go to idx[] (rows within the segment, as in cfmm_get_trades_range), Delta[][n_coins] and
+ *              Lambda[][n_coins] (the reference's rows, bit-identical to cfmm_get_trades_range for those rows; n_coins = 2, or
+ *              the coin count of a weighted / Curve segment) and value[].  idx, Delta, Lambda and value may each be NULL;
+ *              capacity == 0 counts only; exactly min(count, capacity) rows are written, the rest of the arrays stays untouched.
+ *              capacity < 0, count == NULL or a bad seg: CFMM_ERR_INVALID_ARG.
+ *   State      needs materialised trades (else CFMM_ERR_STATE, "no materialised trades", as cfmm_get_trades); consumes nothing and
+ *              invalidates nothing: cfmm_get_trades, cfmm_update_reserves and cfmm_trades_dev behave afterwards as if it had not
+ *              been called.  Synchronous, on the context's stream, behind the sweep.
+ * Works on every kind, both trade layouts (option "compact_trades"), large-market mode and multi-device contexts (the shards
+ * that hold rows of `seg` are asked in device order, which is pool order; counts are summed).  On a context sharded with
+ * cfmm_set_peers or RCCL the call is LOCAL to the rank's own pools and is not collective: no other rank needs to make it.
+ * Read-only options: "select_block_pools" and "select_scan_chunk" (the launch geometry: pools per block, block counts per scan
+ * step), and, under option "time_kernels", "select_flag_ns" / "select_scan_ns" / "select_emit_ns": the kernel spans of the
+ * latest call. */
+int cfmm_select_trades(cfmm_ctx* ctx, int32_t seg, const double* v, double min_value, int64_t capacity,
+                       int64_t* count, int64_t* idx, double* Delta, double* Lambda, double* value);
+
 /* update_reserves!(r) -- src/router.jl:127-132.  The reference's router method calls a per-pool
  * update_reserves!(c, Δ, Λ, v) that is defined nowhere (its own test is disabled, test/arb.jl:30-39);
  * implemented here is the update the routing problem prescribes (find_arb! docstring,

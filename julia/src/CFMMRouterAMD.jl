@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
 
-export AMDRouter, route_native!, polish!, update_pools!, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, select_trades, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -387,6 +387,31 @@ function update_reserves!(r::AMDRouter; sync::Bool=true)
     end
     foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
     return nothing
+end
+
+# select_trades(r, seg; min_value, v, capacity): the pools of device segment `seg` (0-based, the order of build_router) that
+# trade in the latest find_arb! / route! and are worth at least min_value, compacted on the device (cfmm_select_trades):
+# a pool trades iff some entry of its Δ or Λ compares != 0.0, value = Σ_k (Λ_k − Δ_k)·v[A_k] in coin order, selected unless
+# value < min_value.  -> (idx, Δ, Λ, value): idx = 1-based rows within the segment, ascending; Δ, Λ = n_coins × count matrices
+# (column j = the trade of pool idx[j]).  v = nothing: the prices of that sweep.  capacity = nothing: min(m, 65536) rows
+# first, then once more with the returned count if that was too small.
+function select_trades(r::AMDRouter, seg::Integer; min_value::Real=0.0, v=nothing, capacity=nothing, n_coins::Integer=2)
+    isnothing(capacity) || capacity >= 0 || throw(ArgumentError("capacity must be >= 0"))
+    vv = isnothing(v) ? Float64[] : Vector{Float64}(v)
+    cap = isnothing(capacity) ? 65536 : Int64(capacity)
+    while true
+        idx = Vector{Int64}(undef, cap); val = Vector{Float64}(undef, cap)
+        D = Matrix{Float64}(undef, n_coins, cap); L = Matrix{Float64}(undef, n_coins, cap)
+        count = Ref{Int64}(0)
+        GC.@preserve vv idx val D L check(r.ctx, ccall((:cfmm_select_trades, LIB), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Int64, Ref{Int64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+            r.ctx, Int32(seg), isnothing(v) ? C_NULL : pointer(vv), Float64(min_value), cap, count, idx, D, L, val))
+        if count[] <= cap || !isnothing(capacity)
+            k = min(count[], cap)
+            return idx[1:k] .+ 1, D[:, 1:k], L[:, 1:k], val[1:k]
+        end
+        cap = count[]
+    end
 end
 
 # Optional fast path: the whole of route! inside the library (cfmm_route: its own L-BFGS-B, the

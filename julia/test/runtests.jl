@@ -236,4 +236,19 @@ end
     @test all(maximum(abs.(Δ)) <= 1e-9 for Δ in r.Δs)
 end
 
+@testset "select_trades: the pools that trade, selected on the device" begin
+    pools = random_product_market(300, 8; seed=7, fee=0.997)
+    r = AMDRouter(LinearNonnegative(rand(8)), pools, 8)
+    v = rand(8) .+ 0.5
+    find_arb!(r, v)
+    value(i) = foldl((acc, k) -> acc + (r.Λs[i][k] - r.Δs[i][k]) * v[pools[i].Ai[k]], 1:2; init=0.0)
+    for τ in (-Inf, 0.0, 1.0)
+        want = [i for i in 1:300 if (any(r.Δs[i] .!= 0) || any(r.Λs[i] .!= 0)) && !(value(i) < τ)]
+        idx, Δ, Λ, val = select_trades(r, 0; min_value=τ)        # one ProductTwoCoin segment: its rows are r.order
+        @test r.order[idx] == want
+        @test all(Δ[:, j] == r.Δs[want[j]] && Λ[:, j] == r.Λs[want[j]] && val[j] == value(want[j]) for j in eachindex(want))
+        @test length(select_trades(r, 0; min_value=τ, capacity=0)[1]) == 0
+    end
+end
+
 end
