@@ -7,6 +7,7 @@ import numpy as np
 import cfmmrouter_amd as cr
 from cfmmrouter_amd._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_UNIV3
 from oracle import cfmm_oracle as orc
+from reduction_ref import assert_reduction_exact
 
 
 def oracle_poolset(batches, n_tokens):
@@ -112,22 +113,17 @@ def route_converged(obj, market, n, v0=None, nthreads=1, solver="native", router
 
 
 def reduction_checks(c, rows, D, L, psi, acc, kk, bD, bL, check_self=True):
-    """Ψ / acc of a 60-digit fixture case (dict: v, Ai, truth D / L) against the device's own trades (math.fsum: the LDS
-    scatter and the folds, (c + 2)·u·Σ|terms| for c nonzero terms) and against the truth (the per-pool bounds K·(bD + bL)
-    summed, plus that reduction bound).  rows: the case's rows that were swept; D, L: the device's trades, or None."""
+    """Ψ / acc of a 60-digit fixture case (dict: v, Ai, truth D / L) against the device's own trades (reduction_ref.
+    assert_reduction_exact: the LDS scatter and the folds, (c + 2)·u·Σ|terms| for c nonzero terms, exact for c <= 1) and
+    against the truth (the per-pool bounds K·(bD + bL) summed, plus that reduction bound).  rows: the case's rows that were
+    swept; D, L: the device's trades, or None."""
     U = 2.0 ** -53
     Ai0 = (c["Ai"][rows] - 1).ravel()
     n = len(c["v"])
     vl = c["v"][Ai0]
     Dt, Lt = c["D"][rows].ravel(), c["L"][rows].ravel()
     if check_self:
-        f = (L.ravel() - D.ravel())
-        for j in range(n):
-            t = f[Ai0 == j]
-            cj = np.count_nonzero(t)
-            assert abs(psi[j] - math.fsum(t)) <= (cj + 2) * U * np.sum(np.abs(t)), j
-        terms = np.concatenate([L.ravel() * vl, -(D.ravel() * vl)])
-        assert abs(acc - math.fsum(terms)) <= (np.count_nonzero(terms) + 2) * U * np.sum(np.abs(terms))
+        assert_reduction_exact(D, L, Ai0, c["v"], n, psi, acc)
     ft = Lt - Dt
     per = (kk[:, None] * (bD + bL)).ravel()
     for j in range(n):

@@ -41,3 +41,12 @@ extern "C" int launch_plan_host(int n, const int64_t* opts, int n_seg, const int
     for (int k = 0; k < 6; ++k) totals[k] = t[k];
     return (int)plan.groups.size();
 }
+
+// launch_plan.cpp's bin_copies (how many LDS bin copies a block of `block` threads keeps for n tokens under option
+// bin_copies = 0 / 1 / 2): tests/test_reduction_exact_cpu.py holds its NumPy restatement against this
+extern "C" int launch_plan_bin_copies(int n, int option, int block)
+{
+    PlanOpts o;
+    o.bin_copies = option;
+    return bin_copies(n, o, block);
+}

@@ -11,6 +11,7 @@ import cfmmrouter_amd as cr
 from cfmmrouter_amd import synth
 from cfmmrouter_amd._lib import KIND_SOLIDLY
 from helpers import device_sweep, rel_to_max
+from reduction_ref import assert_reduction_exact
 
 import solidly_ref as sr
 from solidly_dev import dev_sweep, read_trades_dev
@@ -37,6 +38,7 @@ def _check_against_reference(b, v, D, L, psi, acc, n, sample=4001):
     vl = v[Ai0]
     acc_exact = math.fsum(np.concatenate([(L * vl).ravel(), -(D * vl).ravel()]))
     assert abs(acc - acc_exact) <= 1e-12 * max(np.max(np.abs(psi_exact)), abs(acc_exact))
+    assert_reduction_exact(D, L, Ai0, v, n, psi, acc)   # per token: exact for <= 1 flow, (c + 2)·u·Σ|t| otherwise
     return D, L
 
 
@@ -118,7 +120,7 @@ def test_large_market_mode_with_a_hub_token():
         psi_ref = np.bincount((b.Ai - 1).ravel(), weights=flows, minlength=n)
         t = flows.reshape(m, 2)[b.Ai == 1]
         assert len(t) >= m // 3
-        assert abs(psi[0] - math.fsum(t)) <= (np.count_nonzero(t) + 2) * 2.0 ** -53 * np.sum(np.abs(t))
+        assert_reduction_exact(D, L, b.Ai - 1, v, n, psi, acc, be.ctx.segments())   # the hub and every other token
         assert rel_to_max(psi, psi_ref) <= 1e-11
         p2, a2 = be.eval(v)
         assert rel_to_max(p2, psi) <= 1e-12 and abs(a2 - acc) <= 1e-12 * abs(acc)

@@ -10,6 +10,7 @@ import cfmmrouter_amd as cr
 from cfmmrouter_amd import synth
 from cfmmrouter_amd._lib import KIND_GEOMEAN, KIND_PRODUCT, KIND_WEIGHTED
 from helpers import coin_scale, device_sweep, rel_to_max
+from reduction_ref import assert_reduction_exact
 
 import weighted_ref as wr
 
@@ -53,6 +54,7 @@ def test_n_coin_pools_match_the_cpu_reference(nc):
     vl = v[Ai0]
     acc_exact = math.fsum(np.concatenate([(L * vl).ravel(), -(D * vl).ravel()]))
     assert abs(acc - acc_exact) <= 1e-12 * max(abs(acc_exact), 1.0)
+    assert_reduction_exact(D, L, Ai0, v, n, psi, acc)   # per token: exact for <= 1 flow, (c + 2)·u·Σ|t| otherwise
 
 
 def test_edge_cases():
