@@ -130,6 +130,7 @@ def lib():
     L.cfmm_pools_set_reserves.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p]
     L.cfmm_pools_set_curve.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, _f64p]
     L.cfmm_pools_set_prices.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p]
+    L.cfmm_pools_set_ticks.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _i64p, _f64p, _f64p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -464,6 +465,18 @@ class Context:
         if p.size != idx.size:
             raise ArgumentError("current_price must have len(idx) entries")
         self._check(self._L.cfmm_pools_set_prices(self._h, int(seg), idx.size, ptr(idx), ptr(p)))
+
+    def set_ticks(self, seg: int, idx, current_price, tick_off, lower_ticks, liquidity):
+        """A mint / burn: new tick ladders of pools idx of a UniV3 segment, in CSR form over the rows (tick_off [count + 1],
+        lower_ticks and liquidity [tick_off[-1]], as add_univ3 takes them), and a current price per row (cfmm_pools_set_ticks)."""
+        idx, p = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1), f64(current_price).reshape(-1)
+        off = np.ascontiguousarray(tick_off, dtype=np.int64).reshape(-1)
+        lt, lq = f64(lower_ticks).reshape(-1), f64(liquidity).reshape(-1)
+        if p.size != idx.size or off.size != idx.size + 1:
+            raise ArgumentError("current_price must have len(idx) entries, tick_off len(idx) + 1")
+        if lt.size != off[-1] or lq.size != off[-1]:
+            raise ArgumentError("tick arrays must have tick_off[-1] entries")
+        self._check(self._L.cfmm_pools_set_ticks(self._h, int(seg), idx.size, ptr(idx), ptr(p), ptr(off), ptr(lt), ptr(lq)))
 
     def set_peers(self, peer_ptrs, world: int, rank: int, seq: int):
         """Sharded operation: every host-pointer sweep of this context ends with the one-shot peer

@@ -447,11 +447,13 @@ class PoolBatch:
 
 def _set_pool_state(ctx, seg, batch: PoolBatch, rows, states):
     """New state of pools `rows` of `batch` (device segment `seg`; ctx None: host mirror only): a reserve vector per pool,
-    (R, α, β) for Curve, a price for UniV3.  The device call (cfmm_pools_set_*) checks every row before anything changes;
-    the batch's arrays follow only when it accepted."""
+    (R, α, β) for Curve, a price for UniV3 -- or (price, lower_ticks, liquidity), a mint / burn.  The device call
+    (cfmm_pools_set_*) checks every row before anything changes; the batch's arrays follow only when it accepted."""
     rows = np.asarray(rows, dtype=np.int64)
     try:
-        if batch.kind == KIND_UNIV3:
+        if batch.kind == KIND_UNIV3 and any(_is_ladder_state(s) for s in states):
+            _set_univ3_ladders(ctx, seg, batch, rows, states)
+        elif batch.kind == KIND_UNIV3:
             p = np.array([float(s) for s in states], dtype=np.float64)
             if ctx is not None:
                 ctx.set_prices(seg, rows, p)
@@ -473,7 +475,50 @@ def _set_pool_state(ctx, seg, batch: PoolBatch, rows, states):
         if isinstance(e, ArgumentError):
             raise
         raise ArgumentError(f"new state of a {type(batch[0]).__name__ if len(batch) else 'pool'}: an R vector per pool, (R, α, β) "
-                            f"for Curve, a price for UniV3 ({e})") from None
+                            f"for Curve, a price or (price, lower_ticks, liquidity) for UniV3 ({e})") from None
+
+
+def _is_ladder_state(s):
+    return isinstance(s, (tuple, list)) and len(s) == 3 and np.ndim(s[0]) == 0 and np.ndim(s[1]) == 1
+
+
+def _set_univ3_ladders(ctx, seg, batch, rows, states):
+    """UniV3 rows of which some bring a new ladder: ALL of them go through one cfmm_pools_set_ticks call (a bare price with
+    the pool's own ladder), so the segment's rows are still checked together; then the batch's CSR arrays are rebuilt."""
+    if ctx is None:
+        raise NotImplementedError("this backend cannot change a UniV3 pool's tick ladder (the device context does: "
+                                  "cfmm_pools_set_ticks)")
+    p, lts, lqs = [], [], []
+    for r, s in zip(rows, states):
+        if _is_ladder_state(s):
+            lt, lq = np.asarray(s[1], dtype=np.float64).reshape(-1), np.asarray(s[2], dtype=np.float64).reshape(-1)
+            if lt.size != lq.size:
+                raise ValueError("lower_ticks and liquidity must have the same length")
+            p.append(float(s[0]))
+        else:
+            o, e = batch.tick_off[r], batch.tick_off[r + 1]
+            lt, lq = batch.lower_ticks[o:e], batch.liquidity[o:e]
+            p.append(float(s))
+        lts.append(lt)
+        lqs.append(lq)
+    p = np.array(p, dtype=np.float64)
+    off = np.zeros(len(rows) + 1, dtype=np.int64)
+    np.cumsum([a.size for a in lts], out=off[1:])
+    ctx.set_ticks(seg, rows, p, off, np.concatenate(lts), np.concatenate(lqs))
+    # the host mirror: untouched ladders keep their order, the rows' ladders take their new lengths
+    m, old_len = len(batch), np.diff(batch.tick_off)
+    new_len, keep = old_len.copy(), np.ones(m, dtype=bool)
+    new_len[rows] = np.diff(off)
+    keep[rows] = False
+    new_off = np.zeros(m + 1, dtype=np.int64)
+    np.cumsum(new_len, out=new_off[1:])
+    lt, lq = np.empty(new_off[-1]), np.empty(new_off[-1])
+    src, dst = np.repeat(keep, old_len), np.repeat(keep, new_len)
+    lt[dst], lq[dst] = batch.lower_ticks[src], batch.liquidity[src]
+    for r, a, b in zip(rows, lts, lqs):
+        lt[new_off[r]:new_off[r + 1]], lq[new_off[r]:new_off[r + 1]] = a, b
+    batch.tick_off, batch.lower_ticks, batch.liquidity = new_off, lt, lq
+    batch.current_price[rows] = p
 
 
 def zerotrade(c):

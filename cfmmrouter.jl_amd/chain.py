@@ -202,12 +202,14 @@ def load_snapshot(source):
     return tokens, batches
 
 
-def snapshot_delta(old, new):
+def snapshot_delta(old, new, ladders=False):
     """What moved between two snapshots of the SAME pool set: `old` and `new` are `load_snapshot` results (or their batch
     lists).  -> {position: new state} for the pools whose state differs, in the form `update_pools_(router, changes)` takes
     for a router built from these batches: position = the pool's index in the concatenated batches; state = a reserve vector,
     `(R, α, β)` for Curve, the price for concentrated-liquidity pools.  Anything else that differs -- the pool set, a pool's
-    family, tokens, fee, weights or tick ladder -- is a structural change (a re-upload): ArgumentError naming the pool."""
+    family, tokens, fee, weights or tick ladder -- is a structural change (a re-upload): ArgumentError naming the pool.
+    ladders=True: a concentrated-liquidity pool whose tick ladder differs (a mint, a burn) is a change like any other; its
+    state is `(price, lower_ticks, liquidity)`, the pool's whole new ladder (cfmm_pools_set_ticks)."""
     def batches_of(snap):
         if isinstance(snap, tuple) and len(snap) == 2 and not hasattr(snap[0], "kind"):
             return snap[0], list(snap[1])
@@ -230,18 +232,20 @@ def snapshot_delta(old, new):
             if bad.size:
                 raise ArgumentError(f"pool {base + int(bad[0])}: {what} changed between the snapshots (a structural change: re-upload)")
         if hasattr(x, "tick_off"):
-            ragged = not np.array_equal(x.tick_off, y.tick_off)
             nt = np.diff(x.tick_off)
-            same = np.ones(len(x), dtype=bool)
-            if ragged:
-                same = np.diff(y.tick_off) == nt
-            if same.all():
-                diff = (x.lower_ticks != y.lower_ticks) | (x.liquidity != y.liquidity)
-                same = np.add.reduceat(diff.astype(np.int64), x.tick_off[:-1]) == 0 if diff.size else same
-            if not same.all():
+            same = np.diff(y.tick_off) == nt                        # per pool: the same tick count ...
+            px, py = np.repeat(np.arange(len(x)), nt), np.repeat(np.arange(len(y)), np.diff(y.tick_off))
+            kx, ky = same[px], same[py]                             # ... and, tick by tick, the same prices and liquidity
+            diff = (x.lower_ticks[kx] != y.lower_ticks[ky]) | (x.liquidity[kx] != y.liquidity[ky])
+            same &= np.bincount(px[kx][diff], minlength=len(x)) == 0
+            if not same.all() and ladders:
+                for i in np.nonzero(~same)[0]:
+                    o, e = y.tick_off[i], y.tick_off[i + 1]
+                    changes[base + int(i)] = (float(y.current_price[i]), y.lower_ticks[o:e].copy(), y.liquidity[o:e].copy())
+            elif not same.all():
                 raise ArgumentError(f"pool {base + int(np.nonzero(~same)[0][0])}: tick ladder changed between the snapshots "
                                     "(a mint / burn is a structural change: re-upload)")
-            for i in np.nonzero(x.current_price != y.current_price)[0]:
+            for i in np.nonzero((x.current_price != y.current_price) & same)[0]:
                 changes[base + int(i)] = float(y.current_price[i])
         else:
             moved = np.any(x.R != y.R, axis=1)

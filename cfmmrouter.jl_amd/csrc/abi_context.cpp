@@ -208,6 +208,8 @@ void cfmm_ctx_destroy(cfmm_ctx* c)
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_upd) (void)hipHostFree(c->h_upd);
     if (c->upd_done) (void)hipEventDestroy(c->upd_done);
+    for (hipEvent_t e : c->compact_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->d_arm) (void)hipFree(c->d_arm);
     const hipStream_t own_stream = c->own_stream;
     delete c;   // the context's DevBufs go here: before the stream, as every release above
@@ -286,6 +288,10 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (key && !std::strcmp(key, "pool_update_regrows")) {   // read-only: compactions + regrows of UniV3 tick arrays (cfmm_pools_set_prices)
         *value = c->pool_update_regrows;
         for (const cfmm_ctx* child : c->shards) *value += child->pool_update_regrows;
+        return CFMM_OK;
+    }
+    if (key && !std::strcmp(key, "compact_walks_ns")) {   // read-only: the span of the latest compact_walks launch timed under "time_kernels"
+        *value = c->shards.empty() ? c->compact_ns : c->shards[0]->compact_ns;
         return CFMM_OK;
     }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under

@@ -373,8 +373,9 @@ int cfmm_update_reserves(cfmm_ctx* c)
     std::vector<Fresh> fresh(c->segs.size());   // (releases what it still holds on every early return)
     const double* v = c->trade_v.data();
     for (size_t k = 0; k < c->segs.size(); ++k) {
-        const Segment& s = c->segs[k];
+        Segment& s = c->segs[k];
         if (s.kind != CFMM_KIND_UNIV3) continue;
+        const LadderStore::Csr lad = s.lad.csr();   // (re-tightened first when cfmm_pools_set_ticks has replaced ladders)
         std::vector<double>& cp = fresh[k].cp;
         cp = s.h_cp;
         for (int64_t i = 0; i < s.m; ++i) {
@@ -382,11 +383,11 @@ int cfmm_update_reserves(cfmm_ctx* c)
             const double pr = v[s.h_ai[(size_t)(2 * i)]] / v[s.h_ai[(size_t)(2 * i + 1)]];   // :340
             if (g * q <= pr && pr <= q / g) continue;                                        // :347-349
             const double P = pr < g * q ? pr / g : g * pr;
-            const double top = s.h_lt[(size_t)s.h_tick_off[(size_t)i]];
+            const double top = lad.lower_ticks[lad.tick_off[i]];
             cp[(size_t)i] = P > top ? top : P;
         }
         const int rc = univ3_build(c, fresh[k].u, fresh[k].fast_ok, s.m, cp.data(), s.h_gamma.data(), s.h_ai.data(),
-                                   s.h_tick_off.data(), s.h_lt.data(), s.h_liq.data());
+                                   lad.tick_off, lad.lower_ticks, lad.liquidity);
         if (rc != CFMM_OK) return rc;
     }
     // Phase 2: R <- R + γΔ − Λ for the two-coin families on the device (no host traffic); from the first launch on the

@@ -1,9 +1,11 @@
 // abi_update.cpp -- sparse pool-state updates (include/cfmm_amd.h: cfmm_pools_set_reserves, cfmm_pools_set_curve,
-// cfmm_pools_set_prices): the reference's `cfmm.R .= ...` on a few pools of a router, without re-uploading the market.
+// cfmm_pools_set_prices, cfmm_pools_set_ticks): the reference's `cfmm.R .= ...` on a few pools of a router -- and a UniV3
+// mint / burn, a pool's new tick ladder -- without re-uploading the market.
 // Every row is checked with the upload's own checks (pool_checks.h) before anything changes; the prepared constants are
 // computed on the host with the upload's own expressions (pool_checks.h, univ3_pool.h), packed column by column into the
 // context's pinned staging buffer and scattered into the segment's columns by ONE launch (sweep.h ScatterArgs) on the
-// context's stream.  A moved UniV3 pool's walk lists are appended at the tail of the segment's record arrays.
+// context's stream.  A moved UniV3 pool's walk lists are appended at the tail of the segment's record arrays; when the tail
+// is full the records are compacted on the device (compact_walks).
 #include "ctx.h"
 #include "pool_checks.h"
 
@@ -14,8 +16,8 @@ using namespace cfmm;
 
 namespace {
 
-enum Entry { kSetReserves, kSetCurve, kSetPrices };
-const char* const kEntryName[] = {"cfmm_pools_set_reserves", "cfmm_pools_set_curve", "cfmm_pools_set_prices"};
+enum Entry { kSetReserves, kSetCurve, kSetPrices, kSetTicks };
+const char* const kEntryName[] = {"cfmm_pools_set_reserves", "cfmm_pools_set_curve", "cfmm_pools_set_prices", "cfmm_pools_set_ticks"};
 
 struct Update {
     Entry entry;
@@ -25,8 +27,13 @@ struct Update {
     const double* R;        // [count][n_coins]        (kSetReserves, kSetCurve)
     const double* alpha;    // [count]                 (kSetCurve)
     const double* beta;
-    const double* price;    // [count]                 (kSetPrices)
+    const double* price;    // [count]                 (kSetPrices, kSetTicks)
+    const int64_t* tick_off; // [count + 1]            (kSetTicks: the rows' new ladders in CSR form, as cfmm_pools_add_univ3)
+    const double* lt;       // [tick_off[count]]
+    const double* liq;
 };
+const double kNoTick = 0.0;
+bool univ3_entry(Entry e) { return e == kSetPrices || e == kSetTicks; }
 
 Entry entry_of_kind(int kind) { return kind == CFMM_KIND_UNIV3 ? kSetPrices : kind == CFMM_KIND_CURVE ? kSetCurve : kSetReserves; }
 
@@ -34,7 +41,7 @@ Entry entry_of_kind(int kind) { return kind == CFMM_KIND_UNIV3 ? kSetPrices : ki
 int check_entry(const cfmm_ctx* c, Entry entry, int kind)
 {
     const Entry right = entry_of_kind(kind);
-    if (entry == right) return CFMM_OK;
+    if (entry == right || (entry == kSetTicks && kind == CFMM_KIND_UNIV3)) return CFMM_OK;
     return fail(c, CFMM_ERR_INVALID_ARG, "%s: segment of %s pools: %s", kEntryName[entry], kind_info(kind).name, kEntryName[right]);
 }
 
@@ -46,9 +53,17 @@ int check_args(const cfmm_ctx* c, const Update& u, int64_t n_segs)
 }
 int check_arrays(const cfmm_ctx* c, const Update& u)
 {
-    const bool ok = u.idx && (u.entry == kSetPrices ? u.price != nullptr : u.R != nullptr) && (u.entry != kSetCurve || (u.alpha && u.beta));
-    return u.count > 0 && !ok ? fail(c, CFMM_ERR_INVALID_ARG, "null pool array") : CFMM_OK;
+    const bool ok = u.idx && (univ3_entry(u.entry) ? u.price != nullptr : u.R != nullptr) && (u.entry != kSetCurve || (u.alpha && u.beta)) &&
+                    (u.entry != kSetTicks || (u.tick_off && u.lt && u.liq));
+    if (u.count > 0 && !ok) return fail(c, CFMM_ERR_INVALID_ARG, "null pool array");
+    if (u.count > 0 && u.entry == kSetTicks && u.tick_off[0] != 0) return fail(c, CFMM_ERR_INVALID_ARG, "tick_off[0] must be 0");
+    return CFMM_OK;
 }
+
+struct Rows {
+    std::vector<int64_t> idx, src;
+};
+Rows distinct_rows(int64_t count, const int64_t* idx);
 
 // Every check of one single-device update, nothing changed: the rows in the caller's order, each with the checks of the
 // matching cfmm_pools_add_* on the values given.  row_base: what a shard adds to its rows in error texts (the parent's rows).
@@ -64,9 +79,18 @@ int validate(const cfmm_ctx* c, const Update& u, int64_t row_base)
         if (i < 0 || i >= s.m) return fail(c, CFMM_ERR_INVALID_ARG, "pool index %lld out of range [0, %lld)", (long long)row, (long long)(row_base + s.m));
         if (u.entry == kSetPrices) {
             int64_t ct;
-            const int64_t o = s.h_tick_off[(size_t)i];
             if ((rc = check_univ3_price(c, row, u.price[j])) != CFMM_OK ||
-                (rc = check_univ3_tick(c, row, s.h_lt.data() + o, s.h_tick_off[(size_t)i + 1] - o, u.price[j], ct)) != CFMM_OK)
+                (rc = check_univ3_tick(c, row, s.lad.lower_ticks(i), s.lad.count(i), u.price[j], ct)) != CFMM_OK)
+                return rc;
+            continue;
+        }
+        if (u.entry == kSetTicks) {   // univ3_build's checks of a pool's state, in its order
+            int64_t ct;
+            const int64_t o = u.tick_off[j], nt = u.tick_off[j + 1] - o;
+            if (nt < 1) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: needs at least one tick", (long long)row);
+            if ((rc = check_univ3_price(c, row, u.price[j])) != CFMM_OK ||
+                (rc = check_univ3_ladder(c, row, u.lt + o, u.liq + o, nt)) != CFMM_OK ||
+                (rc = check_univ3_tick(c, row, u.lt + o, nt, u.price[j], ct)) != CFMM_OK)
                 return rc;
             continue;
         }
@@ -75,14 +99,18 @@ int validate(const cfmm_ctx* c, const Update& u, int64_t row_base)
         if (s.kind == CFMM_KIND_SOLIDLY && (rc = check_solidly_range(c, row, R)) != CFMM_OK) return rc;
         if (s.kind == CFMM_KIND_CURVE && (rc = check_curve_params(c, row, u.alpha[j], u.beta[j], R, nc)) != CFMM_OK) return rc;
     }
+    if (u.entry == kSetTicks && u.count > 0) {   // the segment's limit (univ3_build) on the new total: every row's last occurrence counts
+        const Rows rows = distinct_rows(u.count, u.idx);
+        int64_t T = s.lad.ticks_total();
+        for (size_t k = 0; k < rows.idx.size(); ++k)
+            T += (u.tick_off[rows.src[k] + 1] - u.tick_off[rows.src[k]]) - s.lad.count(rows.idx[k]);
+        if (2 * (T + 2 * s.m) > (int64_t)0x3fffffff) return fail(c, CFMM_ERR_UNSUPPORTED, "too many ticks in one segment");
+    }
     return CFMM_OK;
 }
 
 // The distinct rows of an update in ascending order, each with the position of its LAST occurrence in the caller's arrays
 // (a row named twice takes its last value; decided here, on the host, so the result does not depend on the launch)
-struct Rows {
-    std::vector<int64_t> idx, src;
-};
 Rows distinct_rows(int64_t count, const int64_t* idx)
 {
     std::vector<std::pair<int64_t, int64_t>> a((size_t)count);
@@ -158,45 +186,59 @@ int launch(cfmm_ctx* c, const Packer& p)
     return CFMM_OK;
 }
 
-// Room for `need` more records at the tail of a UniV3 segment's ticks / thr.  When it runs out: wait for the stream, fetch the
-// records in use, rebuild the arrays tightly from the host's walk spans (the lists of moved pools are garbage) and allocate
-// half as much again (at least 4096 records).  Nothing of the segment changes unless every allocation succeeded.
+// Room for `need` more records at the tail of a UniV3 segment's ticks / thr.  When it runs out the records in use are compacted
+// ON THE DEVICE: the host lays the pools' spans out tightly in pool order (O(m), from its copy of `walk`; the lists of moved
+// pools are garbage), stages the new spans in the pinned buffer, and one compact_walks launch copies every pool's records
+// into fresh arrays with half as much again (at least 4096 records), rewrites thr and the device's walk array.  No record
+// crosses PCIe and nothing is waited for BEFORE the launch: it is ordered behind the scatters that wrote the old arrays.
+// The host waits once, for the kernel's end, before it releases the old arrays.  Nothing of the segment changes unless every
+// allocation succeeded.
 int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
 {
     UniV3State& u = s.u;
     if (u.tick_used + need <= u.tick_cap) return CFMM_OK;
     constexpr int64_t kMaxRecords = 0x3fffffff / 2;   // the sweep's index arithmetic (univ3_build: 2·(T + 2m) <= 0x3fffffff)
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    std::vector<TickRec> old((size_t)u.tick_used), tight;
-    if (u.tick_used > 0) HIP_TRY(c, hipMemcpy(old.data(), u.ticks.get(), old.size() * sizeof(TickRec), hipMemcpyDeviceToHost));
     std::vector<int4> walk = u.h_walk;
-    tight.reserve(old.size());
+    int64_t tight = 0;
     for (int4& w : walk) {   // a pool's two lists lie back to back: [x, x + y] and [z, z + w], z = x + y + 1
-        const size_t n = (size_t)w.y + (size_t)w.w + 2;
-        const int base = (int)tight.size();
-        tight.insert(tight.end(), old.begin() + w.x, old.begin() + w.x + (ptrdiff_t)n);
+        const int base = (int)tight;
+        tight += (int64_t)w.y + (int64_t)w.w + 2;
         w = make_int4(base, w.y, base + w.y + 1, w.w);
     }
-    const int64_t want = (int64_t)tight.size() + need;
+    const int64_t want = tight + need;
     if (want > kMaxRecords) return fail(c, CFMM_ERR_UNSUPPORTED, "too many ticks in one segment");
     const int64_t cap = std::min(kMaxRecords, want + std::max<int64_t>(want / 2, 4096));
-    std::vector<double> thr((size_t)cap + 4, 0.0);   // (the scan reads four thresholds at a time: zeros behind the tail)
-    for (size_t e = 0; e < tight.size(); ++e) thr[e] = tight[e].thr;
-    DevBuf<TickRec> d_ticks;   // (the segment's own arrays stay until all three copies have succeeded)
-    DevBuf<double> d_thr;
-    if (d_ticks.alloc(c, (size_t)cap) != CFMM_OK || d_thr.alloc(c, thr.size()) != CFMM_OK)
+    DevBuf<TickRec> d_ticks;   // (the segment's own arrays stay until the launch is enqueued)
+    DevBuf<double> d_thr;      // (the scan reads four thresholds at a time: + 4 behind the tail)
+    DevBuf<int4> d_walk;
+    if (d_ticks.alloc(c, (size_t)cap) != CFMM_OK || d_thr.alloc(c, (size_t)cap + 4) != CFMM_OK || d_walk.alloc(c, walk.size()) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "pool update: allocation of %lld tick records failed", (long long)cap);
-    hipError_t e = hipMemcpy(d_ticks.get(), tight.data(), tight.size() * sizeof(TickRec), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_thr.get(), thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(u.walk.get(), walk.data(), walk.size() * sizeof(int4), hipMemcpyHostToDevice);
-    if (e != hipSuccess)   // (u.walk may be half written: it still names records of the OLD arrays only if nothing was copied)
-        return fail(c, CFMM_ERR_HIP, "pool update: re-upload of the tick records failed: %s", hipGetErrorString(e));
-    u.ticks = std::move(d_ticks);
+    int rc = staging_reserve(c, 2 * walk.size());
+    if (rc != CFMM_OK) return rc;
+    std::memcpy(c->h_upd, walk.data(), walk.size() * sizeof(int4));
+    const bool timed = c->opt_time_kernels != 0;
+    if (timed)
+        for (hipEvent_t& e : c->compact_ev)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, launch_compact_walks(u.walk.get(), static_cast<const int4*>(c->d_upd), d_walk.get(), u.ticks.get(), d_ticks.get(), d_thr.get(),
+                                    s.m, tight, c->stream, timed ? c->compact_ev[0] : nullptr, timed ? c->compact_ev[1] : nullptr));
+    // One wait is kept, for the kernel itself: the old arrays are released below and the staging is refilled by the scatter that
+    // follows, and both must outlive the kernel's reads (hipFree would wait for the device anyway; this says so).
+    HIP_TRY(c, hipEventRecord(c->upd_done, c->stream));
+    HIP_TRY(c, hipEventSynchronize(c->upd_done));
+    c->upd_busy = false;
+    u.ticks = std::move(d_ticks);   // (releases the old arrays)
     u.thr = std::move(d_thr);
+    u.walk = std::move(d_walk);
     u.h_walk.swap(walk);
-    u.tick_used = (int64_t)tight.size();
+    u.tick_used = tight;
     u.tick_cap = cap;
     ++c->pool_update_regrows;
+    if (timed) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->compact_ev[0], c->compact_ev[1]));
+        c->compact_ns = (int64_t)((double)ms * 1e6);
+    }
     return CFMM_OK;
 }
 
@@ -208,12 +250,16 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     std::vector<TickRec> ticks;
     std::vector<double> thr;
     bool fast = true, lists = false;
+    const bool ladders = u.entry == kSetTicks;   // the rows bring their ladders; else the host's own (ladder_store.h)
     for (int64_t j = 0; j < k; ++j) {
-        const int64_t i = rows.idx[(size_t)j], o = s.h_tick_off[(size_t)i], nt = s.h_tick_off[(size_t)i + 1] - o;
-        const double cp = u.price[rows.src[(size_t)j]];
-        const int64_t ct = univ3_current_tick(s.h_lt.data() + o, nt, cp);   // (>= 1: validated)
-        univ3_prepare_pool(cp, s.h_gamma[(size_t)i], ct, nt, s.h_lt.data() + o, s.h_liq.data() + o, rec[(size_t)j], ticks);
-        fast = fast && in_fast_window(cp);
+        const int64_t i = rows.idx[(size_t)j], src = rows.src[(size_t)j];
+        const int64_t nt = ladders ? u.tick_off[src + 1] - u.tick_off[src] : s.lad.count(i);
+        const double* lt = ladders ? u.lt + u.tick_off[src] : s.lad.lower_ticks(i);
+        const double* lq = ladders ? u.liq + u.tick_off[src] : s.lad.liquidity(i);
+        const double cp = u.price[src];
+        const int64_t ct = univ3_current_tick(lt, nt, cp);   // (>= 1: validated)
+        univ3_prepare_pool(cp, s.h_gamma[(size_t)i], ct, nt, lt, lq, rec[(size_t)j], ticks);
+        fast = fast && in_fast_window(cp) && (!ladders || univ3_liquidity_in_window(lq, nt));
         lists = lists || rec[(size_t)j].walk.y > 0 || rec[(size_t)j].walk.w > 0;
     }
     univ3_all_thresholds(ticks, thr);
@@ -226,7 +272,7 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     DevBuf<uint4> new_head;
     if (!st.has_walk && lists && new_head.alloc(c, 2 * (size_t)s.m) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "pool update: allocation of the threshold heads failed");
-    const size_t words = (size_t)k * (2 + 1 + 2 + 2 + 1 + 2 + 2 + 4 + 1) + (size_t)nrec * 9;
+    const size_t words = (size_t)k * (2 + 1 + 2 + 2 + 1 + 2 + 2 + 4 + 1) + (size_t)nrec * 9 + 4;
     if ((rc = staging_reserve(c, words)) != CFMM_OK) return rc;
     if (new_head) {
         HIP_TRY(c, hipMemsetAsync(new_head.get(), 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
@@ -245,7 +291,7 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     int4* walk = p.add<int4>(st.walk.get(), 2, k);
     uint4* head = st.head ? p.add<uint4>(st.head.get(), 4, k) : nullptr;
     TickRec* t_out = p.add<TickRec>(st.ticks.get(), 8, nrec, base);
-    double* thr_out = p.add<double>(st.thr.get(), 1, nrec, base);
+    double* thr_out = p.add<double>(st.thr.get(), 1, nrec + 4, base);   // (+ the four read-ahead zeros behind the new tail)
     for (int64_t j = 0; j < k; ++j) {
         const UniV3PoolRec& r = rec[(size_t)j];
         pg[j] = r.pg;
@@ -258,7 +304,7 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
         walk[j] = make_int4(r.walk.x + base, r.walk.y, r.walk.z + base, r.walk.w);
     }
     std::memcpy(static_cast<void*>(t_out), ticks.data(), (size_t)nrec * sizeof(TickRec));
-    std::memcpy(thr_out, thr.data(), (size_t)nrec * sizeof(double));
+    std::memcpy(thr_out, thr.data(), ((size_t)nrec + 4) * sizeof(double));
     p.set_rows(rows.idx);
     if ((rc = launch(c, p)) != CFMM_OK) return rc;
     for (int64_t j = 0; j < k; ++j) {
@@ -267,6 +313,15 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     }
     st.tick_used += nrec;
     if (!fast) s.fast_ok = 0;
+    if (ladders) {   // the host's ladders follow; the plan reads n_ticks_total only through "more than 2 ticks per pool"
+        const bool multi = s.n_ticks_total / s.m > 2;
+        for (int64_t j = 0; j < k; ++j) {
+            const int64_t src = rows.src[(size_t)j], o = u.tick_off[src];
+            s.lad.replace(rows.idx[(size_t)j], u.tick_off[src + 1] - o, u.lt + o, u.liq + o);
+        }
+        s.n_ticks_total = s.lad.ticks_total();
+        if ((s.n_ticks_total / s.m > 2) != multi) c->geometry_dirty = true;
+    }
     return CFMM_OK;
 }
 
@@ -326,7 +381,7 @@ int apply(cfmm_ctx* c, const Update& u)
     armed_cancel(c);
     Segment& s = c->segs[(size_t)u.seg];
     const Rows rows = distinct_rows(u.count, u.idx);
-    const int rc = u.entry == kSetPrices ? apply_univ3(c, s, u, rows) : apply_reserves(c, s, u, rows);
+    const int rc = univ3_entry(u.entry) ? apply_univ3(c, s, u, rows) : apply_reserves(c, s, u, rows);
     if (rc != CFMM_OK) return rc;
     // as cfmm_update_reserves: the trades and outputs on the device describe the market before the update
     c->have_trades = false;
@@ -347,7 +402,8 @@ int multi_update(cfmm_ctx* c, const Update& u)
     const int nd = (int)c->shards.size(), nc = ps.n_coins;
     struct Part {
         std::vector<int64_t> idx;
-        std::vector<double> R, alpha, beta, price;
+        std::vector<double> R, alpha, beta, price, lt, liq;
+        std::vector<int64_t> tick_off;
         int64_t lo = 0;
         Update u{};
     };
@@ -361,8 +417,15 @@ int multi_update(cfmm_ctx* c, const Update& u)
         while (i >= his[(size_t)d]) ++d;
         Part& p = parts[(size_t)d];
         p.idx.push_back(i - los[(size_t)d]);
-        if (u.entry == kSetPrices) p.price.push_back(u.price[j]);
-        else p.R.insert(p.R.end(), u.R + j * nc, u.R + (j + 1) * nc);
+        if (univ3_entry(u.entry)) p.price.push_back(u.price[j]);
+        if (u.entry == kSetTicks) {   // the shard's own CSR; offsets that run backwards become an empty ladder ("needs at least one tick")
+            const int64_t o = u.tick_off[j], nt = o >= 0 && u.tick_off[j + 1] > o ? u.tick_off[j + 1] - o : 0;
+            if (p.tick_off.empty()) p.tick_off.push_back(0);
+            p.lt.insert(p.lt.end(), u.lt + o, u.lt + o + nt);
+            p.liq.insert(p.liq.end(), u.liq + o, u.liq + o + nt);
+            p.tick_off.push_back((int64_t)p.lt.size());
+        }
+        if (!univ3_entry(u.entry)) p.R.insert(p.R.end(), u.R + j * nc, u.R + (j + 1) * nc);
         if (u.entry == kSetCurve) {
             p.alpha.push_back(u.alpha[j]);
             p.beta.push_back(u.beta[j]);
@@ -372,7 +435,8 @@ int multi_update(cfmm_ctx* c, const Update& u)
         Part& p = parts[(size_t)d];
         p.lo = los[(size_t)d];
         p.u = Update{u.entry, (int32_t)child_segment(c, u.seg, d), (int64_t)p.idx.size(), p.idx.data(), p.R.data(), p.alpha.data(),
-                     p.beta.data(), p.price.data()};
+                     p.beta.data(), p.price.data(), p.tick_off.data(), p.lt.data(), p.liq.data()};
+        if (u.entry == kSetTicks && p.lt.empty()) p.u.lt = p.u.liq = &kNoTick;   // (rows without a tick: refused by row, not as a null array)
         if (p.idx.empty()) continue;
         cfmm_ctx* child = c->shards[(size_t)d];
         if ((rc = validate(child, p.u, p.lo)) != CFMM_OK) return fail(c, rc, "%s", child->err.c_str());
@@ -404,18 +468,24 @@ extern "C" {
 
 int cfmm_pools_set_reserves(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* R)
 {
-    return update(c, Update{kSetReserves, seg, count, idx, R, nullptr, nullptr, nullptr});
+    return update(c, Update{kSetReserves, seg, count, idx, R, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr});
 }
 
 int cfmm_pools_set_curve(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* R, const double* alpha,
                          const double* beta)
 {
-    return update(c, Update{kSetCurve, seg, count, idx, R, alpha, beta, nullptr});
+    return update(c, Update{kSetCurve, seg, count, idx, R, alpha, beta, nullptr, nullptr, nullptr, nullptr});
 }
 
 int cfmm_pools_set_prices(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* current_price)
 {
-    return update(c, Update{kSetPrices, seg, count, idx, nullptr, nullptr, nullptr, current_price});
+    return update(c, Update{kSetPrices, seg, count, idx, nullptr, nullptr, nullptr, current_price, nullptr, nullptr, nullptr});
+}
+
+int cfmm_pools_set_ticks(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const double* current_price,
+                         const int64_t* tick_off, const double* lower_ticks, const double* liquidity)
+{
+    return update(c, Update{kSetTicks, seg, count, idx, nullptr, nullptr, nullptr, current_price, tick_off, lower_ticks, liquidity});
 }
 
 } // extern "C"

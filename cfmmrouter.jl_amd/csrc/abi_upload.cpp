@@ -199,16 +199,9 @@ int univ3_build(cfmm_ctx* c, UniV3State& u, int& fast_ok, int64_t m, const doubl
         if (a == b) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: the two token indices must differ", (long long)i);
         const double* lt = lower_ticks + o;
         const double* lq = liquidity + o;
-        for (int64_t j = 0; j < nt; ++j) {
-            if (!finite_pos(lt[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld tick %lld: price must be finite and > 0", (long long)i, (long long)j);
-            if (j > 0 && !(lt[j] < lt[j - 1]))
-                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: lower_ticks must be strictly descending", (long long)i);
-            if (!(lq[j] >= 0.0) || !std::isfinite(lq[j]))
-                return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld tick %lld: liquidity must be finite and >= 0", (long long)i, (long long)j);
-        }
+        if ((rc = check_univ3_ladder(c, i, lt, lq, nt)) != CFMM_OK) return rc;
         const double cp = current_price[i];
-        fast = fast && in_fast_window(cp) && in_fast_window(gamma[i]);
-        for (int64_t j = 0; j < nt; ++j) fast = fast && (lq[j] == 0.0 || in_fast_window(lq[j]));
+        fast = fast && in_fast_window(cp) && in_fast_window(gamma[i]) && univ3_liquidity_in_window(lq, nt);
         int64_t ct;
         if ((rc = check_univ3_tick(c, i, lt, nt, cp, ct)) != CFMM_OK) return rc;
         UniV3PoolRec rec;
@@ -368,9 +361,7 @@ int cfmm_pools_add_univ3(cfmm_ctx* c, int64_t m, const double* current_price, co
     s.h_cp.assign(current_price, current_price + m);
     s.h_gamma.assign(gamma, gamma + m);
     s.h_ai.assign(Ai, Ai + 2 * m);
-    s.h_tick_off.assign(tick_off, tick_off + m + 1);
-    s.h_lt.assign(lower_ticks, lower_ticks + tick_off[m]);
-    s.h_liq.assign(liquidity, liquidity + tick_off[m]);
+    s.lad.assign(m, tick_off, lower_ticks, liquidity);
     return add_segment_common(c, std::move(s), Ai);
 }
 

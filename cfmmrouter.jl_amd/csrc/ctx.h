@@ -10,7 +10,8 @@
 //                     sweeps, pre-armed evaluations
 //   abi_trades.cpp    trade download / device views, the selection of the trades worth executing, update_reserves!,
 //                     reserves / prices read-back
-//   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices)
+//   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices / _set_ticks)
+//   ladder_store.h    LadderStore: a UniV3 segment's tick ladders on the host, one pool's replaceable (no HIP)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -19,6 +20,7 @@
 
 #include "../../include/cfmm_amd.h"
 #include "devbuf.h"
+#include "ladder_store.h"
 #include "launch_plan.h"
 #include "sweep.h"
 
@@ -54,9 +56,9 @@ struct UniV3State {
     DevBuf<double> thr;         // drain thresholds, one per record
     DevBuf<uint4> head;         // per pool the first four thresholds of both walk lists as rounded-down floats (sweep.h UniV3Pools)
     int has_walk = 1;           // some pool has a tick beyond its current one
-    // the walk lists of a pool whose price cfmm_pools_set_prices moves are rewritten at the TAIL of ticks / thr (abi_update.cpp):
-    // records in use (garbage of moved pools included) and allocated (thr: + 4 of read-ahead), and the host copy of `walk` a
-    // compaction rebuilds the arrays from
+    // the walk lists of a pool that cfmm_pools_set_prices / _set_ticks moves are rewritten at the TAIL of ticks / thr
+    // (abi_update.cpp): records in use (garbage of moved pools included) and allocated (thr: + 4 of read-ahead), and the host
+    // copy of `walk` from which a compaction (compact_walks, update_kernels.h) lays the arrays out afresh
     int64_t tick_used = 0, tick_cap = 0;
     std::vector<int4> h_walk;
 };
@@ -90,11 +92,11 @@ struct Segment : SegPlan {   // (SegPlan: the launch geometry, decided by ensure
     // host copies of the pool constants that cfmm_pools_set_reserves prepares q / {Q1, Q2} from besides the new reserves:
     // GeometricMeanTwoCoin γ and η, weighted the normalised weights ([n_coins][m] like nc.par)
     std::vector<double> h_gamma, h_eta, h_par;
-    // UniV3: the prepared state, and the pool definitions as uploaded (update_reserves! moves current_price and re-derives
-    // the state from them)
+    // UniV3: the prepared state, and the pool definitions (update_reserves! moves current_price and re-derives the state from
+    // them; cfmm_pools_set_ticks replaces single ladders: ladder_store.h).  n_ticks_total == lad.ticks_total().
     UniV3State u;
-    std::vector<double> h_cp, h_lt, h_liq;
-    std::vector<int64_t> h_tick_off;
+    std::vector<double> h_cp;
+    LadderStore lad;
     NCoinState nc;
 };
 
@@ -264,6 +266,8 @@ struct cfmm_ctx {
     hipEvent_t upd_done = nullptr;
     bool upd_busy = false;
     int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
+    hipEvent_t compact_ev[2] = {nullptr, nullptr};   // option "time_kernels": {start, stop} of the latest compact_walks launch
+    int64_t compact_ns = 0;            // read-only option "compact_walks_ns": that launch's span
 
     // cfmm_select_trades (abi_trades.cpp, select_kernels.h): scratch, the device copy of the valuing prices and the compacted
     // rows, grown on demand and kept for the next call; the scan delivers the count to one pinned, device-mapped word

@@ -48,6 +48,25 @@ inline int check_univ3_price(const cfmm_ctx* c, int64_t i, double cp)
     if (!finite_pos(cp)) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: current_price must be finite and > 0", (long long)i);
     return CFMM_OK;
 }
+// a pool's ladder of nt >= 1 ticks, tick by tick: the price bound, the ordering, the liquidity
+inline int check_univ3_ladder(const cfmm_ctx* c, int64_t i, const double* lt, const double* lq, int64_t nt)
+{
+    for (int64_t j = 0; j < nt; ++j) {
+        if (!finite_pos(lt[j])) return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld tick %lld: price must be finite and > 0", (long long)i, (long long)j);
+        if (j > 0 && !(lt[j] < lt[j - 1]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld: lower_ticks must be strictly descending", (long long)i);
+        if (!(lq[j] >= 0.0) || !std::isfinite(lq[j]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "pool %lld tick %lld: liquidity must be finite and >= 0", (long long)i, (long long)j);
+    }
+    return CFMM_OK;
+}
+// every non-empty tick's liquidity inside the window of the fast arithmetic (Segment::fast_ok)
+inline bool univ3_liquidity_in_window(const double* lq, int64_t nt)
+{
+    bool fast = true;
+    for (int64_t j = 0; j < nt; ++j) fast = fast && (lq[j] == 0.0 || in_fast_window(lq[j]));
+    return fast;
+}
 // the pool's current tick (univ3_current_tick) into ct, or the refusal of a price above the first tick
 inline int check_univ3_tick(const cfmm_ctx* c, int64_t i, const double* lt, int64_t nt, double cp, int64_t& ct)
 {

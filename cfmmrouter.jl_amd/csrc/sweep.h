@@ -293,6 +293,12 @@ struct ScatterArgs {
     ScatterCol col[kMaxScatterCols];
 };
 hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s);
+// Compaction of a UniV3 segment's tick records (update_kernels.h compact_walks): pool i's walk.y + walk.w + 2 records move from
+// old_ticks + old_walk[i].x to ticks + new_walk[i].x; thr[e] <- record e's thr, thr[tail .. tail + 4) <- 0, walk_out <- new_walk.
+// new_walk may be device-visible host memory; the other arrays are device arrays, old and new distinct.  e0, e1: both set =
+// the launch is timed by the command processor.
+hipError_t launch_compact_walks(const int4* old_walk, const int4* new_walk, int4* walk_out, const TickRec* old_ticks, TickRec* ticks,
+                                double* thr, int64_t m, int64_t tail, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 // compact trade records -> full {Δ₁, Δ₂} / {Λ₁, Λ₂} arrays (cfmm_trades_dev, cfmm_get_trades*)
 hipError_t launch_expand_trades(const double2* rec, const double2* ovA, const double2* ovB, double2* Delta, double2* Lambda,
                                 int64_t m, hipStream_t s);

@@ -39,7 +39,7 @@
 //   sweep_core.h      LDS layout, stage_prices, process_pool, tile loops, finish_row, sweep_kernel, sweep_multi
 //   sweep_ncoin.h     weighted_pool, curve_pool (curve_pool.h: the solve), sweep_ncoin
 //   fold_kernels.h    reduce_partials, reduce_gather, gather_chunks, token_fold
-//   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records
+//   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records, compact_walks
 //   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
@@ -56,6 +56,8 @@
 #include "select_kernels.h"
 
 #include <hip/hip_ext.h>
+
+#include <cstddef>
 
 namespace cfmm {
 
@@ -247,6 +249,17 @@ hipError_t launch_scatter_records(const ScatterArgs& a, hipStream_t s)
     if (a.total <= 0) return hipSuccess;
     hipLaunchKernelGGL(scatter_records, dim3((unsigned)((a.total + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+hipError_t launch_compact_walks(const int4* old_walk, const int4* new_walk, int4* walk_out, const TickRec* old_ticks, TickRec* ticks,
+                                double* thr, int64_t m, int64_t tail, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (m <= 0) return hipErrorInvalidValue;
+    static_assert(sizeof(TickRec) == 64 && offsetof(TickRec, thr) == 40, "compact_walks: piece 2 of a record is {rout, thr}");
+    long long mm = m, tt = tail;
+    void* args[] = {&old_walk, &new_walk, &walk_out, &old_ticks, &ticks, &thr, &mm, &tt};
+    const long long blocks = (mm * kCompactGroup + 255) / 256;
+    return launch_k(reinterpret_cast<const void*>(&compact_walks), dim3((unsigned)blocks), dim3(256), 0, s, e0, e1, args);
 }
 
 hipError_t launch_select_count(const SelectArgs& a, bool ragged, long long* total_host, hipStream_t s, hipEvent_t* ev)

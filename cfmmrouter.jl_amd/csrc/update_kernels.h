@@ -1,5 +1,6 @@
 // update_kernels.h -- kernels that rewrite pool state or trade buffers in place: update_reserves! for the two-coin and
-// N-coin families (F::q_of: sweep_ncoin.h), the expansion of compact trade records, sparse pool-state updates.
+// N-coin families (F::q_of: sweep_ncoin.h), the expansion of compact trade records, sparse pool-state updates, the
+// compaction of a UniV3 segment's tick records.
 #pragma once
 
 #include "fast_arith.h"
@@ -100,6 +101,37 @@ __global__ __launch_bounds__(256) void scatter_records(ScatterArgs a)
     if (j >= col.rows) return;                                            // (a gap between two columns)
     const long long row = col.dense_base >= 0 ? col.dense_base + j : a.idx[j];
     col.dst[row * col.width + t] = a.stage[g];
+}
+
+// Compaction of a UniV3 segment's tick records (abi_update.cpp univ3_make_room): every pool's two walk lists -- back to back
+// in the old array, walk.y + walk.w + 2 records of 64 bytes from walk.x -- move to the pool's base in a fresh, tight array;
+// thr[e] is rewritten from record e's own thr field, the pool's new span goes to the fresh walk array, and the four
+// read-ahead thresholds behind the new tail are zeroed.  The host computed the new spans (new_walk: pinned staging, read once).
+// kCompactGroup = 16 lanes per pool, 16 bytes per lane and step: a group's step is 256 contiguous bytes = four records = two
+// full 128-byte lines on either side (records are 64-byte aligned), the mean list of the 1M-pool market (19 records) takes
+// 5 steps, and a wavefront waits for the longest of 4 pools, not of 8 or 16.  Plain vector loads and stores: no atomics, no
+// LDS, no block reads what another writes (source and destination are different allocations).
+constexpr int kCompactGroup = 16;
+__global__ __launch_bounds__(256) void compact_walks(const int4* __restrict__ old_walk, const int4* __restrict__ new_walk,
+                                                     int4* __restrict__ walk_out, const TickRec* __restrict__ old_ticks,
+                                                     TickRec* __restrict__ ticks, double* __restrict__ thr, long long m,
+                                                     long long tail)
+{
+    if (blockIdx.x == 0 && threadIdx.x < 4) thr[tail + threadIdx.x] = 0.0;
+    const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) / kCompactGroup;
+    const int lane = (int)threadIdx.x % kCompactGroup;
+    if (i >= m) return;
+    const int4 wo = old_walk[i], wn = new_walk[i];
+    if (lane == 0) walk_out[i] = wn;
+    const int pieces = 4 * (wo.y + wo.w + 2);                                  // 16-byte pieces of the pool's records
+    const double2* __restrict__ src = reinterpret_cast<const double2*>(old_ticks + wo.x);
+    double2* __restrict__ dst = reinterpret_cast<double2*>(ticks + wn.x);
+    double* __restrict__ t = thr + wn.x;
+    for (int k = lane; k < pieces; k += kCompactGroup) {
+        const double2 q = src[k];
+        dst[k] = q;
+        if ((k & 3) == 2) t[k >> 2] = q.y;                                     // piece 2 of a record is {rout, thr}
+    }
 }
 
 } // namespace cfmm

@@ -726,7 +726,8 @@ def update_pools_(r: Router, changes):
     reference's `r.cfmms[i].R .= ...` followed by another route! (there the pools ARE the router's state).
 
     `changes` maps positions in `r.cfmms` to new state: a reserve vector (ProductTwoCoin, GeometricMeanTwoCoin, Solidly,
-    weighted pools), `(R, α, β)` (Curve), a price (UniV3; ticks and liquidity stay).  The pools are grouped by device segment;
+    weighted pools), `(R, α, β)` (Curve), a price (UniV3; ticks and liquidity stay) or `(price, lower_ticks, liquidity)` (UniV3:
+    a mint / burn, the pool's new ladder; cfmm_pools_set_ticks).  The pools are grouped by device segment;
     each segment's rows go through one cfmm_pools_set_* call, which checks all of them before anything changes (a refused
     segment is left as it was, and so are the segments after it).  Host-evaluated plugin pools (their own find_arb_) are
     updated on the host only: `pool.set_state_(state)` if the type defines it, else `pool.R[:] = state`.  The router's trades
@@ -763,6 +764,8 @@ def update_pools_(r: Router, changes):
             for i, row in zip(where, rows):
                 pool = r.cfmms[i]
                 if batch.kind == KIND_UNIV3:
+                    o, e = batch.tick_off[row], batch.tick_off[row + 1]
+                    pool.lower_ticks, pool.liquidity = batch.lower_ticks[o:e].copy(), batch.liquidity[o:e].copy()
                     pool.current_price = float(batch.current_price[row])
                     pool.current_tick = int(np.count_nonzero(pool.lower_ticks >= pool.current_price))
                 else:

@@ -293,13 +293,20 @@ int cfmm_get_prices(cfmm_ctx* ctx, int32_t seg, double* current_price);
  *   cfmm_pools_set_reserves  ProductTwoCoin, GeometricMeanTwoCoin, Solidly and weighted segments: R[count][n_coins]
  *   cfmm_pools_set_curve     Curve segments: R[count][n_coins] with the pools' alpha[count], beta[count] (A ramps; D, hence
  *                            beta, moves with liquidity and fees)
- *   cfmm_pools_set_prices    UniV3 segments: current_price[count]; ticks and liquidity stay (a mint / burn is a re-add)
+ *   cfmm_pools_set_prices    UniV3 segments: current_price[count]; ticks and liquidity stay (a mint / burn:
+ *                            cfmm_pools_set_ticks)
+ *   cfmm_pools_set_ticks     UniV3 segments: a mint or a burn.  The rows' NEW tick ladders in CSR form over the count rows
+ *                            (tick_off[count + 1], tick_off[0] == 0; lower_ticks and liquidity [tick_off[count]], in the
+ *                            parametrisation of cfmm_pools_add_univ3) and a current price per row (the old one for a pure
+ *                            mint / burn).  A ladder may grow, shrink or move; the segment's tick total 2·(T + 2m) <=
+ *                            0x3fffffff is checked on the new total (CFMM_ERR_UNSUPPORTED)
  * The entry that does not fit the segment's kind returns CFMM_ERR_INVALID_ARG and names the one that does; so does a seg or
  * an idx out of range.
  * Checks: those of the matching cfmm_pools_add_*, in its order and with its error texts (the pool number is the row), on
  * the values given: reserves finite and > 0; Solidly reserves within [2^-150, 2^150]; Curve alpha >= 0, beta > 0 and, with
- * alpha > 0, log(P0/R_k) within the solve's range; a price finite, > 0 and not above the pool's first tick.  ALL rows are
- * checked before anything changes: a refused call leaves the context exactly as it was.
+ * alpha > 0, log(P0/R_k) within the solve's range; a price finite, > 0 and not above the pool's first tick; a new ladder
+ * of at least one tick, tick prices finite, > 0 and strictly descending, liquidity finite and >= 0.  ALL rows are
+ * checked before anything changes: a refused call leaves the context exactly as it was, on the host and on the device.
  * Prepared constants (GeometricMean {Q1, Q2}, weighted log(R / w), Curve log R and {alpha, log beta}, every UniV3 record:
  * current-tick constants, walk lists with their running sums, drain thresholds, heads) are computed ON THE HOST with the
  * upload's own code, so an updated context equals, bit for bit on every output, a context freshly uploaded with the new
@@ -309,14 +316,19 @@ int cfmm_get_prices(cfmm_ctx* ctx, int32_t seg, double* current_price);
  * The update is enqueued on the context's stream behind earlier sweeps; the trades and outputs of earlier sweeps are
  * invalidated as by cfmm_update_reserves (cfmm_get_trades then fails with "no materialised trades" until the next
  * cfmm_find_arb / cfmm_route).  The walk lists of a moved UniV3 pool are appended to the segment's record arrays, whose
- * spare room is grown geometrically and compacted when it runs out (one stream synchronisation and a re-upload of the
- * segment's records; counted by the read-only option "pool_update_regrows").
+ * spare room is grown geometrically and compacted when it runs out: one kernel on the stream (compact_walks) copies the
+ * records in use into fresh arrays, no record crosses PCIe (counted by the read-only option "pool_update_regrows"; with
+ * "time_kernels" the kernel's span is the read-only option "compact_walks_ns").  An upload allocates no spare room, so the
+ * first update of a UniV3 segment compacts.  cfmm_pools_set_ticks keeps the launch plan unless the segment's mean ticks
+ * per pool crosses 2 or its first walk list appears; then the plan is rebuilt at the next sweep, as after an upload.
  * Multi-device contexts: the rows are split over the shards; every shard checks its rows before any shard changes.
- * Limits: not for adding or removing pools, nor for tokens, fees, weights or tick ladders (cfmm_pools_clear + re-add). */
+ * Limits: not for adding or removing pools, nor for tokens, fees or weights (cfmm_pools_clear + re-add). */
 int cfmm_pools_set_reserves(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* R);
 int cfmm_pools_set_curve(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* R,
                          const double* alpha, const double* beta);
 int cfmm_pools_set_prices(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* current_price);
+int cfmm_pools_set_ticks(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* current_price,
+                         const int64_t* tick_off, const double* lower_ticks, const double* liquidity);
 
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);

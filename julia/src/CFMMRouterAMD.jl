@@ -271,7 +271,8 @@ end
 
 # update_pools!(r, changes): new state for a few pools WITHOUT re-uploading the market -- the reference's `cfmm.R .= ...` on some
 # pools followed by another route!.  `changes` maps positions in r.cfmms to a reserve vector (two-coin and weighted pools),
-# a tuple (R, α, β) (Curve) or a price (UniV3; ticks and liquidity stay).  The pools are grouped by device segment; every
+# a tuple (R, α, β) (Curve), a price (UniV3; ticks and liquidity stay) or a tuple (price, lower_ticks, liquidity) (UniV3: a
+# mint / burn, the pool's new ladder).  The pools are grouped by device segment; every
 # segment's rows go through one cfmm_pools_set_* call, which checks all of them before anything changes.  The host-side pool
 # objects follow.  Host-evaluated pool types are updated on the host only (their R).
 function update_pools!(r::AMDRouter, changes::AbstractDict)
@@ -307,7 +308,22 @@ function update_pools!(r::AMDRouter, changes::AbstractDict)
         items = segs[s]
         idx = Int64[t[1] for t in items]
         c1 = r.cfmms[items[1][2]]
-        if c1 isa UniV3
+        if c1 isa UniV3 && any(t -> t[3] isa Tuple, items)
+            # a mint / burn: (price, lower_ticks, liquidity); every row of the segment goes through ONE call (a bare price
+            # with the pool's own ladder), so they are checked together
+            p = Float64[Float64(t[3] isa Tuple ? t[3][1] : t[3]) for t in items]
+            lts = [Float64.(t[3] isa Tuple ? t[3][2] : r.cfmms[t[2]].lower_ticks) for t in items]
+            lqs = [Float64.(t[3] isa Tuple ? t[3][3] : r.cfmms[t[2]].liquidity) for t in items]
+            off = Int64[0; cumsum(length.(lts))]
+            lt, lq = reduce(vcat, lts), reduce(vcat, lqs)
+            GC.@preserve idx p off lt lq check(r.ctx, ccall((:cfmm_pools_set_ticks, LIB), Cint,
+                (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}),
+                r.ctx, s, length(idx), idx, p, off, lt, lq))
+            for (k, t) in enumerate(items)
+                c = r.cfmms[t[2]]
+                r.cfmms[t[2]] = UniV3(p[k], lts[k], lqs[k], c.γ, c.Ai)
+            end
+        elseif c1 isa UniV3
             p = Float64[Float64(t[3]) for t in items]
             GC.@preserve idx p check(r.ctx, ccall((:cfmm_pools_set_prices, LIB), Cint,
                 (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Float64}), r.ctx, s, length(idx), idx, p))
