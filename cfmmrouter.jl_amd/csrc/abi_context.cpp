@@ -27,32 +27,103 @@ int fail(const cfmm_ctx* c, int code, const char* fmt, ...)
     return code;
 }
 
-// Every device allocation of the library and its release (DevBuf, devbuf.h).  The hooks build counts the live ones
-// (read-only option "debug_live_allocs"; tests/test_gpu_ownership.py).
+// Every raw create and destroy of the library's own resources, each the only caller of its HIP function: device arrays
+// (DevBuf, devbuf.h), pinned memory, events and streams (PinnedBuf, Event, Stream, hostres.h).  The hooks build counts the
+// live ones per family (read-only options "debug_live_allocs" / "_pinned" / "_events" / "_streams"; tests/test_gpu_ownership.py).
+enum { kLiveAllocs, kLivePinned, kLiveEvents, kLiveStreams, kLiveFamilies };
 #ifdef CFMM_TEST_HOOKS
-static std::atomic<int64_t> g_live_allocs{0};
+static std::atomic<int64_t> g_live[kLiveFamilies];
+static void count(int family, int by) { g_live[family] += by; }
+#else
+static void count(int, int) {}
 #endif
 
-hipError_t dev_alloc(void** p, size_t bytes)
+// a failed create leaves *p null and no sticky error behind
+template <class T>
+static hipError_t created(hipError_t e, T* p, int family)
 {
-    const hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         *p = nullptr;
-        return e;
+    } else {
+        count(family, 1);
     }
-#ifdef CFMM_TEST_HOOKS
-    ++g_live_allocs;
-#endif
     return e;
 }
 
-void dev_free(void* p)
+hipError_t dev_alloc(void** p, size_t bytes) { return created(hipMalloc(p, bytes), p, kLiveAllocs); }
+hipError_t dev_alloc_fine(void** p, size_t bytes) { return created(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained), p, kLiveAllocs); }
+void dev_free(void* p) { (void)hipFree(p); count(kLiveAllocs, -1); }
+
+hipError_t pinned_alloc(void** h, void** d, size_t bytes, bool mapped)
 {
-    (void)hipFree(p);
-#ifdef CFMM_TEST_HOOKS
-    --g_live_allocs;
-#endif
+    *d = nullptr;
+    const hipError_t e = created(hipHostMalloc(h, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault), h, kLivePinned);
+    if (e == hipSuccess && mapped && hipHostGetDevicePointer(d, *h, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        *d = nullptr;
+    }
+    return e;
+}
+void pinned_free(void* h) { (void)hipHostFree(h); count(kLivePinned, -1); }
+
+hipError_t event_create(hipEvent_t* e, unsigned flags) { return created(hipEventCreateWithFlags(e, flags), e, kLiveEvents); }
+void event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); count(kLiveEvents, -1); }
+
+hipError_t stream_create(hipStream_t* s) { return created(hipStreamCreateWithFlags(s, hipStreamNonBlocking), s, kLiveStreams); }
+void stream_destroy(hipStream_t s) { (void)hipStreamDestroy(s); count(kLiveStreams, -1); }
+
+int HostStage::alloc(const cfmm_ctx* c, int n_tokens)
+{
+    n = n_tokens;
+    gran_off = (size_t)((2 * n + 2 + 15) & ~15);
+    flag_off = gran_off + 2 * (size_t)((n + 1 + 7) & ~7);
+    const int rc = buf.alloc(c, flag_off + 16, true);
+    if (rc == CFMM_OK) std::memset(buf.host(), 0, buf.size() * sizeof(double));
+    return rc;
+}
+
+// optional: without a large BAR (or with CFMM_AMD_ARMED=0, or when the self-check fails) the buffer stays empty
+void ArmState::alloc(int device, int n_tokens, int n_padded)
+{
+    n = n_tokens;
+    n_pad = n_padded;
+    int large_bar = 0;
+    const char* env = std::getenv("CFMM_AMD_ARMED");
+    if ((env && env[0] == '0') || hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) != hipSuccess || large_bar == 0) return;
+    const size_t words = (size_t)n_pad + 8;
+    if (!buf.alloc_fine(words)) return;
+    // self-check: what the host stores must be what the device holds
+    std::vector<double> probe(words), back(words, 0.0);
+    for (size_t j = 0; j < words; ++j) probe[j] = 1.0 + (double)j;
+    std::memcpy(buf.get(), probe.data(), words * sizeof(double));
+    __builtin_ia32_sfence();
+    if (hipMemcpy(back.data(), buf.get(), words * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess || back != probe) {
+        (void)hipGetLastError();
+        buf.reset();
+        return;
+    }
+    std::memset(buf.get(), 0, words * sizeof(double));
+    __builtin_ia32_sfence();
+}
+
+int KernelTimer::harvest(cfmm_ctx* c, int64_t* sweep_launches, double* sweep_ms_out, int64_t* reduce_launches, double* reduce_ms_out)
+{
+    for (auto& p : pending) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
+        if (p.what == 0) { sweep_n++; sweep_ms += ms; }
+        else { reduce_n++; reduce_ms += ms; }
+    }
+    pending.clear();
+    used = 0;
+    if (sweep_launches) *sweep_launches = sweep_n;
+    if (sweep_ms_out) *sweep_ms_out = sweep_ms;
+    if (reduce_launches) *reduce_launches = reduce_n;
+    if (reduce_ms_out) *reduce_ms_out = reduce_ms;
+    sweep_n = reduce_n = 0;
+    sweep_ms = reduce_ms = 0;
+    return CFMM_OK;
 }
 
 } // namespace cfmm
@@ -101,46 +172,11 @@ int cfmm_ctx_create(int device_id, int32_t n_tokens, cfmm_ctx** out)
             return bail(CFMM_ERR_HIP);                                                                \
         }                                                                                             \
     } while (0)
-    HIP_TRY_C(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-    c->stream = c->own_stream;
-    if (c->d_v.alloc(c, (size_t)c->n) != CFMM_OK || c->d_out.alloc(c, (size_t)c->n + 1) != CFMM_OK) return bail(CFMM_ERR_HIP);
-    // [n] v, [n+1] {psi, acc}, padding to a 128-byte boundary, then the output granules: 16 per fold
-    // block = 2 per column, columns padded to a multiple of 8 (see fold_finish)
-    c->gran_off = (size_t)((2 * c->n + 2 + 15) & ~15);
-    c->flag_off = c->gran_off + 2 * (size_t)((c->n + 1 + 7) & ~7);
-    const size_t stage_words = c->flag_off + 16;
-    HIP_TRY_C(hipHostMalloc(reinterpret_cast<void**>(&c->h_stage), stage_words * sizeof(double), hipHostMallocMapped));
-    std::memset(c->h_stage, 0, stage_words * sizeof(double));
-    if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_stage), c->h_stage, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_stage = nullptr; // fall back to explicit copies
-    }
-    {   // armed evaluations: fine-grained device memory the host can write through the PCIe BAR (optional)
-        int large_bar = 0;
-        const char* env = std::getenv("CFMM_AMD_ARMED");
-        if (!(env && env[0] == '0') &&
-            hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, c->device) == hipSuccess && large_bar != 0) {
-            const size_t words = (size_t)c->n_pad + 8;
-            if (hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_arm), words * sizeof(double), hipDeviceMallocFinegrained) == hipSuccess) {
-                // self-check: what the host stores must be what the device holds
-                std::vector<double> probe(words), back(words, 0.0);
-                for (size_t j = 0; j < words; ++j) probe[j] = 1.0 + (double)j;
-                std::memcpy(c->d_arm, probe.data(), words * sizeof(double));
-                __builtin_ia32_sfence();
-                if (hipMemcpy(back.data(), c->d_arm, words * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess || back != probe) {
-                    (void)hipGetLastError();
-                    (void)hipFree(c->d_arm);
-                    c->d_arm = nullptr;
-                } else {
-                    std::memset(c->d_arm, 0, words * sizeof(double));
-                    __builtin_ia32_sfence();
-                }
-            } else {
-                (void)hipGetLastError();
-                c->d_arm = nullptr;
-            }
-        }
-    }
+    if (c->own_stream.create(c) != CFMM_OK) return bail(CFMM_ERR_HIP);
+    c->stream = c->own_stream.get();
+    if (c->d_v.alloc(c, (size_t)c->n) != CFMM_OK || c->d_out.alloc(c, (size_t)c->n + 1) != CFMM_OK || c->stage.alloc(c, c->n) != CFMM_OK)
+        return bail(CFMM_ERR_HIP);
+    c->arm.alloc(c->device, c->n, c->n_pad);
     // the dynamic-LDS ceiling is a per-function, process-wide attribute: always raise it to the
     // full 160 KiB so that contexts with different n_tokens cannot shrink each other's limit
     HIP_TRY_C(prepare_kernels(160 * 1024));
@@ -199,21 +235,10 @@ void cfmm_ctx_destroy(cfmm_ctx* c)
     }
     (void)hipSetDevice(c->device);
     armed_cancel(c);
-    if (c->stream && c->stream != c->own_stream) (void)hipStreamSynchronize(c->stream);
-    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
+    if (c->stream && c->stream != c->own_stream.get()) (void)hipStreamSynchronize(c->stream);
+    if (c->own_stream) (void)hipStreamSynchronize(c->own_stream.get());
     rccl_release(c);          // a communicator created by cfmm_rccl_init_rank goes with the context
-    c->segs.clear();
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    free_trade_staging(c);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_upd) (void)hipHostFree(c->h_upd);
-    if (c->upd_done) (void)hipEventDestroy(c->upd_done);
-    for (hipEvent_t e : c->compact_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->d_arm) (void)hipFree(c->d_arm);
-    const hipStream_t own_stream = c->own_stream;
-    delete c;   // the context's DevBufs go here: before the stream, as every release above
-    if (own_stream) (void)hipStreamDestroy(own_stream);
+    delete c;                 // every member releases what it owns, the own stream last (ctx.h)
 }
 
 int cfmm_set_stream(cfmm_ctx* c, void* hip_stream)
@@ -228,7 +253,7 @@ int cfmm_reset_stream(cfmm_ctx* c)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
     CFMM_SINGLE_ONLY(c, "cfmm_reset_stream");
-    c->stream = c->own_stream;
+    c->stream = c->own_stream.get();
     return CFMM_OK;
 }
 
@@ -291,7 +316,7 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
         return CFMM_OK;
     }
     if (key && !std::strcmp(key, "compact_walks_ns")) {   // read-only: the span of the latest compact_walks launch timed under "time_kernels"
-        *value = c->shards.empty() ? c->compact_ns : c->shards[0]->compact_ns;
+        *value = c->shards.empty() ? c->upd.compact_ns : c->shards[0]->upd.compact_ns;
         return CFMM_OK;
     }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
@@ -301,14 +326,17 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     for (int k = 0; k < 3; ++k) {
         static const char* const names[3] = {"select_flag_ns", "select_scan_ns", "select_emit_ns"};
         if (key && !std::strcmp(key, names[k])) {
-            *value = c->shards.empty() ? c->sel_ns[k] : c->shards[0]->sel_ns[k];
+            *value = c->shards.empty() ? c->sel.ns[k] : c->shards[0]->sel.ns[k];
             return CFMM_OK;
         }
     }
 #ifdef CFMM_TEST_HOOKS
-    if (key && !std::strcmp(key, "debug_live_allocs")) {   // read-only, process-wide: device allocations made and not yet released
-        *value = g_live_allocs.load();
-        return CFMM_OK;
+    for (int k = 0; k < kLiveFamilies; ++k) {   // read-only, process-wide: resources of one family created and not yet released
+        static const char* const names[kLiveFamilies] = {"debug_live_allocs", "debug_live_pinned", "debug_live_events", "debug_live_streams"};
+        if (key && !std::strcmp(key, names[k])) {
+            *value = g_live[k].load();
+            return CFMM_OK;
+        }
     }
 #endif
     int64_t* slot = option_slot(const_cast<cfmm_ctx*>(c), key);
@@ -350,21 +378,7 @@ int cfmm_kernel_times(cfmm_ctx* c, int64_t* sweep_launches, double* sweep_ms, in
     }
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (auto& p : c->pending) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, p.a, p.b));
-        if (p.what == 0) { c->t_sweep_n++; c->t_sweep_ms += ms; }
-        else { c->t_reduce_n++; c->t_reduce_ms += ms; }
-    }
-    c->pending.clear();
-    c->ev_used = 0;
-    if (sweep_launches) *sweep_launches = c->t_sweep_n;
-    if (sweep_ms) *sweep_ms = c->t_sweep_ms;
-    if (reduce_launches) *reduce_launches = c->t_reduce_n;
-    if (reduce_ms) *reduce_ms = c->t_reduce_ms;
-    c->t_sweep_n = c->t_reduce_n = 0;
-    c->t_sweep_ms = c->t_reduce_ms = 0;
-    return CFMM_OK;
+    return c->timer.harvest(c, sweep_launches, sweep_ms, reduce_launches, reduce_ms);
 }
 
 int32_t cfmm_segment_count(const cfmm_ctx* c)

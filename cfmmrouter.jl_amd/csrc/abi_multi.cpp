@@ -6,7 +6,7 @@
 // the shards' {Ψ, acc} ON THE HOST in shard order: v comes from the host and Ψ returns to it on
 // every evaluation anyway, so the "all-reduce" of SURVEY 8e degenerates to N·(n+1) additions --
 // no peer access, no IPC, no torch.  One L-BFGS-B (cfmm_route) drives all shards; its evaluations are pre-armed on
-// every shard when the shards sit on distinct devices (abi_sweep.cpp, armed_eval).
+// every shard when the shards sit on distinct devices (abi_handover.cpp, armed_eval).
 #include "ctx.h"
 
 #include <algorithm>

@@ -1,13 +1,9 @@
 // abi_sweep.cpp -- one evaluation on the device: launch geometry, the sweep launches of every pool family, the row
-// fold; host-pointer sweeps (cfmm_find_arb / cfmm_eval) and the pre-armed evaluations cfmm_route uses.
-//   find_arb!(r, v)          src/router.jl:38-42     -> enqueue_sweep(materialize = true)
-//   fn / g! per evaluation   src/router.jl:73-102    -> enqueue_sweep(materialize = false): {Ψ, acc}
-//   netflows(r)              src/router.jl:111-125   -> cfmm_netflows (the Ψ of the latest sweep)
+// fold.  (How its result crosses to the host, and the pre-armed evaluations: abi_handover.cpp.)
 #include "ctx.h"
+#include "granule.h"
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
 #include <cstring>
 
 using namespace cfmm;
@@ -48,27 +44,22 @@ int build_incidence(cfmm_ctx* c)
     return CFMM_OK;
 }
 
-hipEvent_t take_event(cfmm_ctx* c)
-{
-    if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(e);
-    }
-    return c->ev_pool[c->ev_used++];
-}
-
-// a start / stop pair for one timed launch (both null when none could be had)
-void take_events(cfmm_ctx* c, hipEvent_t& a, hipEvent_t& b)
-{
-    a = take_event(c);
-    b = take_event(c);
-    if (!a || !b) a = b = nullptr;
-}
-
 } // namespace
 
 namespace cfmm {
+
+void KernelTimer::take_events(hipEvent_t& a, hipEvent_t& b)
+{
+    hipEvent_t* out[2] = {&a, &b};
+    for (hipEvent_t* e : out) {
+        if (used == pool.size()) {
+            Event fresh;
+            if (fresh.create() == hipSuccess) pool.push_back(std::move(fresh));
+        }
+        *e = used < pool.size() ? pool[used++].get() : nullptr;
+    }
+    if (!a || !b) a = b = nullptr;
+}
 
 // The launch plan of the current segments (launch_plan.h), then what needs the device: the launches' fee tables and the buffers.
 int ensure_geometry(cfmm_ctx* c)
@@ -162,7 +153,7 @@ SweepArgs group_args(const cfmm_ctx* c, const Eval& ev, const Group& g, size_t g
     // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
     // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
     if (ev.sharded) a.arm_timeout = std::max<long long>(a.arm_timeout, c->peer_timeout_ticks);
-    a.flags = c->d_stage ? reinterpret_cast<unsigned long long*>(c->d_stage + c->flag_off) : nullptr;
+    a.flags = c->stage.buf.dev() ? reinterpret_cast<unsigned long long*>(c->stage.buf.dev() + c->stage.flag_off) : nullptr;
     a.nt_stores = c->opt_stream_stores == 2 || (c->opt_stream_stores == 0 && c->touched_bytes > (int64_t)256 << 20) ? 1 : 0;
     if (ev.direct) {
         a.direct = 1;
@@ -233,7 +224,7 @@ int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
     const size_t lds = ev.gb ? (size_t)(g.block / 64) * sizeof(double)
                              : sweep_lds_bytes(c->n_pad, a.copies, g.block, a.need_logv, a.gtab_n, a.v_shift == 4 ? 1 : 0);
     hipEvent_t ea = nullptr, eb = nullptr;
-    if (ev.timed) take_events(c, ea, eb);   // start/stop written by the command processor around this launch (hipExtLaunchKernel)
+    if (ev.timed) c->timer.take_events(ea, eb);   // start/stop written by the command processor around this launch (hipExtLaunchKernel)
     const LaunchCfg cfg{g.block, g.grid, lds, arith_of(c, ev, g, a), ea, eb};
     const Segment* segs = &c->segs[(size_t)g.first];
     hipError_t e;
@@ -258,7 +249,7 @@ int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
         e = launch_sweep(segs[0].kind, pools_of(c, ev, segs[0], a.gtab_n), a, cfg, ev.materialize, c->stream);
     }
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
-    if (ea && eb) c->pending.push_back({ea, eb, 0});
+    if (ea && eb) c->timer.pending.push_back({ea, eb, 0});
     return CFMM_OK;
 }
 
@@ -267,7 +258,7 @@ int launch_fold(cfmm_ctx* c, const Eval& ev)
 {
     hipEvent_t ra = nullptr, rb = nullptr;
     const bool bracket = ev.gb || (c->rows_total == 0 && !ev.sharded);   // several launches / a memset: bracket them with plain events
-    if (ev.timed && !ev.direct) take_events(c, ra, rb);
+    if (ev.timed && !ev.direct) c->timer.take_events(ra, rb);
     if (ra && bracket) HIP_TRY(c, hipEventRecord(ra, c->stream));
     hipEvent_t ka = bracket ? nullptr : ra, kb = bracket ? nullptr : rb;   // else: written by the command processor around the fold
     const int rows = (int)c->rows_total, n1 = c->n + 1;
@@ -306,7 +297,7 @@ int launch_fold(cfmm_ctx* c, const Eval& ev)
     }
     if (ra && rb) {
         if (bracket) HIP_TRY(c, hipEventRecord(rb, c->stream));
-        c->pending.push_back({ra, rb, 1});
+        c->timer.pending.push_back({ra, rb, 1});
     }
     return CFMM_OK;
 }
@@ -315,8 +306,8 @@ int launch_fold(cfmm_ctx* c, const Eval& ev)
 
 // Enqueue one full evaluation on c->stream: every segment's sweep, then the row fold.
 //   want_host_out: the fold delivers {Ψ, acc} to the pinned staging buffer as self-validating granules (the caller
-//                  polls them: host_sweep_end / armed_wait) instead of writing d_out;
-//   arm_seq != 0:  pre-armed launch (SweepArgs::arm_word): v arrives later through c->d_arm.
+//                  polls them: HostStage::wait) instead of writing d_out;
+//   arm_seq != 0:  pre-armed launch (SweepArgs::arm_word): v arrives later through c->arm.buf.
 //   price_window:  what the host knows about v -- kPricesInWindow (host-pointer sweeps whose prices lie inside the
 //                  window of the fast arithmetic), kPricesOutside, or kPricesUnknown (device-pointer sweeps, pre-armed
 //                  launches: the fast kernel is launched and its blocks verify, see sweep_tiles).
@@ -328,14 +319,13 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
     Eval ev{d_v, d_out, materialize, price_window};
     ev.gb = global_bins(c);
     ev.sharded = !c->peers.empty();
-    ev.timed = c->opt_time_kernels != 0 && c->pending.size() < (1u << 20);
-    ev.arm = ArmWord{arm_seq ? reinterpret_cast<const unsigned long long*>(c->d_arm + c->n_pad) : nullptr, arm_seq};
+    ev.timed = c->opt_time_kernels != 0 && c->timer.pending.size() < (1u << 20);
+    ev.arm = ArmWord{arm_seq ? c->arm.word() : nullptr, arm_seq};
     const bool rccl = c->rccl_comm != nullptr;   // the fold's {Ψ, acc} are this rank's part: all-reduced in-stream behind it
-    const bool host_out = want_host_out && !ev.gb && !rccl && (ev.sharded || c->rows_total > 0) && c->d_stage != nullptr;
+    const bool host_out = want_host_out && !ev.gb && !rccl && (ev.sharded || c->rows_total > 0) && c->stage.buf.dev() != nullptr;
     if (host_out) {
-        ++c->out_seq;
-        ev.ho.gran = reinterpret_cast<unsigned long long*>(c->d_stage + c->gran_off);
-        ev.ho.tag = c->out_seq % 0xffffffffull + 1ull;
+        ev.ho.gran = reinterpret_cast<unsigned long long*>(c->stage.buf.dev() + c->stage.gran_off);
+        ev.ho.tag = granule_tag(++c->stage.out_seq);
     }
     HIP_TRY(c, hipSetDevice(c->device));
     // a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
@@ -344,7 +334,7 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
                 !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
     for (size_t gi = 0; gi < c->groups.size(); ++gi)
         if ((rc = launch_group(c, ev, c->groups[gi], gi)) != CFMM_OK) return rc;
-    c->last_host_out = host_out;
+    c->stage.last_host_out = host_out;
     if ((rc = launch_fold(c, ev)) != CFMM_OK) return rc;
     // the sweep and its fold ARE on the stream from here on: the context's bookkeeping says so whatever the collective does
     if (materialize) {
@@ -363,421 +353,9 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
     return CFMM_OK;
 }
 
-int check_prices(cfmm_ctx* c, const double* v)
-{
-    if (!v) return fail(c, CFMM_ERR_INVALID_ARG, "v is null");
-    for (int j = 0; j < c->n; ++j)
-        if (!(v[j] > 0.0) || !std::isfinite(v[j]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "v[%d] must be finite and > 0 (src/cfmms.jl:129)", j);
-    return CFMM_OK;
-}
-
-// every price in [2^-kFastExp, 2^kFastExp] (sweep.h): the host's half of the fast kernels' precondition
-bool prices_in_fast_window(const double* v, int n)
-{
-    for (int j = 0; j < n; ++j) {
-        uint64_t bits;
-        std::memcpy(&bits, v + j, sizeof bits);
-        const int e = (int)((bits >> 52) & 0x7ff);
-        if (e < 1023 - kFastExp || e > 1023 + kFastExp) return false;
-    }
-    return true;
-}
-
-// Why did a sweep deliver NaN?  The blocks report through the sticky word (sweep.h kFlagWindow / kFlagGaveUp).
-// Returns the reported bits among `mask` and clears exactly those (a report nobody asked about stays for whoever does).
-unsigned long long take_flags(cfmm_ctx* c, unsigned long long mask)
-{
-    if (!c->h_stage) return 0;
-    // atomic on the mapped word: launches queued behind the current one may report (system-scope fetch_or over PCIe) while the
-    // host clears -- a plain read-modify-write could lose their bit
-    unsigned long long* w = reinterpret_cast<unsigned long long*>(c->h_stage + c->flag_off);
-    if ((__atomic_load_n(w, __ATOMIC_ACQUIRE) & mask) == 0) return 0;
-    return __atomic_fetch_and(w, ~mask, __ATOMIC_ACQ_REL) & mask;
-}
-
-// First half of a host-pointer sweep: stage v, enqueue the evaluation (asynchronous).
-int host_sweep_begin(cfmm_ctx* c, const double* v, bool materialize)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    (void)take_flags(c, kFlagWindow);     // a stale report must not label a later overflow of THIS call
-    std::memcpy(c->h_stage, v, (size_t)c->n * sizeof(double));
-    if (materialize) {
-        c->trade_v.assign(v, v + c->n);   // the prices the device trades belong to (update_reserves!)
-        // find_arb!(r, v) is a function of v alone (test/arb.jl:16 compares its netflows exactly): a materialising host call
-        // always walks forwards, whatever ran before; the alternation (option "alternate") restarts behind it.
-        c->sweep_count = 0;
-    }
-    double* h_out = c->h_stage + c->n;
-    const bool zero_copy = c->opt_zero_copy != 0 && c->d_stage != nullptr;
-    // v: small vectors are read by every block straight from the mapped pinned buffer (the PCIe
-    // round trip hides behind the first tile's pool loads); larger ones go through one H2D copy.
-    const double* v_src = c->d_stage;
-    if (!zero_copy || c->n > 1024 || global_bins(c)) {
-        HIP_TRY(c, hipMemcpyAsync(c->d_v.get(), c->h_stage, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        v_src = c->d_v.get();
-    }
-    // {Ψ, acc}: as output granules in the mapped pinned buffer when it can (polled by host_sweep_end), else d_out + a copy
-    const bool want_host_out = zero_copy && c->opt_host_flag != 0;
-    int rc = enqueue_sweep(c, v_src, c->d_out.get(), materialize, want_host_out, 0,
-                           prices_in_fast_window(v, c->n) ? kPricesInWindow : kPricesOutside);
-    if (rc != CFMM_OK) return rc;
-    if (!c->last_host_out)
-        HIP_TRY(c, hipMemcpyAsync(h_out, c->d_out.get(), (size_t)(c->n + 1) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    return CFMM_OK;
-}
-
-namespace {
-
-// Output granules of the sweep with sequence number `seq` (fold_finish): true once all 2(n+1) carry its tag; the
-// doubles are then reassembled into the {Ψ, acc} slots of the staging buffer.
-bool granules_arrived(cfmm_ctx* c, uint64_t seq)
-{
-    const unsigned long long tag = seq % 0xffffffffull + 1ull;
-    const volatile unsigned long long* g = reinterpret_cast<const volatile unsigned long long*>(c->h_stage + c->gran_off);
-    const int n1 = c->n + 1;
-    if ((g[2 * n1 - 1] >> 32) != tag || (g[0] >> 32) != tag) return false;   // cheap rejects: last and first granule
-    double* h_out = c->h_stage + c->n;
-    for (int j = 0; j < n1; ++j) {
-        const unsigned long long a = g[2 * j], b = g[2 * j + 1];
-        if ((a >> 32) != tag || (b >> 32) != tag) return false;
-        const unsigned long long bits = (a & 0xffffffffull) | (b << 32);
-        std::memcpy(h_out + j, &bits, sizeof(double));
-    }
-    return true;
-}
-
-// {Ψ, acc} have arrived in the pinned staging buffer: take them over into last_out.
-int take_host_out(cfmm_ctx* c)
-{
-    const double* h_out = c->h_stage + c->n;
-    c->last_out.assign(h_out, h_out + c->n + 1);
-    for (int j = 0; j <= c->n; ++j)
-        if (!std::isfinite(c->last_out[(size_t)j])) {
-            c->have_out = false;
-            (void)hipStreamSynchronize(c->stream);
-            const unsigned long long why = take_flags(c, kFlagWindow);
-            if (why & kFlagWindow)     // (a fast kernel met prices the host had vouched for: cannot happen unless v changed under the call)
-                return fail(c, CFMM_ERR_STATE, "non-finite {psi, acc}: a price lies outside the window of the fast arithmetic "
-                                               "(the price vector changed while the call ran?)");
-            if (c->rccl_comm)
-                return fail(c, CFMM_ERR_STATE, "non-finite {psi, acc}[%d] after the RCCL all-reduce: a shard overflowed (on some rank)", j);
-            if (!c->peers.empty())
-                return fail(c, CFMM_ERR_STATE, "non-finite {psi, acc}[%d]: the peer all-reduce timed out (a rank did not "
-                                               "publish within CFMM_AMD_PEER_TIMEOUT_S) or a shard overflowed", j);
-            return fail(c, CFMM_ERR_STATE, "non-finite {psi, acc}[%d]: pool arithmetic overflowed", j);
-        }
-    c->have_out = true;
-    return CFMM_OK;
-}
-
-} // namespace
-
-// Second half: wait for {Ψ, acc} to be on the host and take them over into last_out.
-int host_sweep_end(cfmm_ctx* c)
-{
-    bool seen = false;
-    if (c->last_host_out) {
-        // the fold blocks wrote {Ψ, acc} as self-validating granules into this pinned buffer: poll them instead of
-        // waiting for the kernel's end-of-pipe processing and its completion signal.  Bounded; falls back to a stream wait.
-        const uint64_t want = c->out_seq;
-        for (long spins = 0; spins < 400000000L; ++spins) {
-            if (granules_arrived(c, want)) { seen = true; break; }
-            __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (!seen) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->last_host_out && !granules_arrived(c, c->out_seq)) {
-            c->have_out = false;
-            return fail(c, CFMM_ERR_STATE, "the sweep retired without delivering its outputs");
-        }
-    }
-    return take_host_out(c);
-}
-
-int single_host_sweep(cfmm_ctx* c, const double* v, bool materialize)
-{
-    int rc = host_sweep_begin(c, v, materialize);
-    return rc != CFMM_OK ? rc : host_sweep_end(c);
-}
-
-int host_sweep(cfmm_ctx* c, const double* v, bool materialize)
-{
-    int rc = check_prices(c, v);
-    if (rc != CFMM_OK) return rc;
-    return c->shards.empty() ? single_host_sweep(c, v, materialize) : multi_host_sweep(c, v, materialize);
-}
-
-// ---- pre-armed evaluations (cfmm_route; sweep.h SweepArgs::arm_word) ---------------------------
-// cfmm_route's evaluations are strictly sequential (the solver needs {Ψ, acc} of v_k to choose v_k+1), so the ~5 us
-// between "v is ready" and "the kernel's first wavefront runs" (launch call, doorbell, command processor, dispatch)
-// sit on the critical path of every evaluation.  Armed operation takes them off it: evaluation k+1 -- sweep and
-// fold -- is enqueued right after evaluation k has been signalled, becomes resident when k's fold retires, issues its
-// first pool loads, clears its LDS bins and then polls a word in device memory; the host writes v_k+1 and the word
-// straight into (fine-grained) device memory through the PCIe BAR.  Measured on the handoff alone
-// (scripts/native/handoff.hip, profiles/r02_handoff.txt): 11.2 us launch-when-ready vs 6.3 us armed.
-// The one launch left over when the solver stops is cancelled through the same word.
-//
-// Sharded contexts arm as well (round 3).  cfmm_set_peers: every rank arms its own launches; the ranks run the same
-// solver on bit-identical {Ψ, acc}, so they signal and cancel the same evaluations, and a cancelled fold + gather
-// publishes nothing (its sequence number is reused).  Multi-device parents: the calling thread writes v into every
-// shard's BAR window, then polls every shard's output granules and sums them in device order -- no worker threads on
-// this path.  NOT armed: parents whose shards share a device, and therefore the ranks-on-one-GPU test set-ups (they
-// switch the option off): a polling launch occupies its CUs, and a shard of the SAME evaluation queued behind it on
-// the same device would wait for an evaluation that waits for it.
-namespace {
-
-bool can_arm_single(cfmm_ctx* c)
-{
-    if (c->opt_armed == 0 || !c->d_arm || c->opt_zero_copy == 0 || !c->d_stage || c->opt_host_flag == 0 ||
-        c->opt_time_kernels != 0 || c->n > 1024 || c->stream != c->own_stream || global_bins(c) || c->rccl_comm != nullptr)
-        return false;
-    return ensure_geometry(c) == CFMM_OK && c->rows_total > 0;
-}
-
-void armed_write(cfmm_ctx* c, const double* v, uint64_t word)
-{
-    if (v) std::memcpy(c->d_arm, v, (size_t)c->n * sizeof(double));   // write-combining stores through the BAR
-    __builtin_ia32_sfence();                                            // v before the word (WC buffers flush out of order)
-    *reinterpret_cast<volatile unsigned long long*>(c->d_arm + c->n_pad) = word;
-    __builtin_ia32_sfence();                                            // and out now
-}
-
-int armed_enqueue(cfmm_ctx* c)
-{
-    const uint64_t seq = ++c->arm_seq;
-    int rc = enqueue_sweep(c, c->d_arm, c->d_out.get(), false, true, seq);
-    if (rc != CFMM_OK) return rc;
-    c->arm_tag = c->out_seq;
-    c->arm_pending = true;
-    return CFMM_OK;
-}
-
-void armed_cancel_single(cfmm_ctx* c)
-{
-    if (!c->arm_pending) return;
-    armed_write(c, nullptr, c->arm_seq | kArmCancel);
-    c->arm_pending = false;
-    --c->sweep_count;   // the cancelled launch swept nothing: later sweeps keep the tile directions of an unarmed run
-    if (!c->peers.empty()) --c->peer_seq;   // ... and the peers' sequence number is reused (every rank cancels the same launch)
-}
-
-// Signal the waiting launch (enqueuing it first if none is waiting) and enqueue the next one behind it.
-// `signalled` = an evaluation is now running whose outputs carry the sequence number `want` (a failure after that point
-// concerns the NEXT launch only).
-int armed_signal(cfmm_ctx* c, const double* v, uint64_t& want, bool& signalled)
-{
-    signalled = false;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->arm_pending) {
-        int rc = armed_enqueue(c);
-        if (rc != CFMM_OK) return rc;
-    }
-    want = c->arm_tag;
-    armed_write(c, v, c->arm_seq);
-    c->arm_pending = false;
-    signalled = true;
-    return armed_enqueue(c);   // evaluation k+1 goes out while k runs
-}
-
-// The signalled evaluation is lost: cancel the launch queued behind it, drain the stream, and put the bookkeeping back
-// to where an unarmed run would be (the lost launch swept nothing useful: the retry takes its tile direction).  On a
-// cfmm_set_peers context a lost evaluation is fatal -- the other ranks have moved on with it.
-void armed_lost(cfmm_ctx* c, bool& retry)
-{
-    armed_cancel_single(c);
-    (void)hipStreamSynchronize(c->stream);
-    c->have_out = false;
-    retry = c->peers.empty();
-    if (retry) --c->sweep_count;
-}
-
-// Wait for the signalled evaluation's granules.  CFMM_ERR_STATE with `lost` set: the device never delivered (host
-// stalled past the arm timeout between two evaluations, or the device never saw the word): the caller may retry unarmed.
-// The bound: the device-side wait of the launch (arm_timeout_ms; on cfmm_set_peers contexts at least the peer timeout,
-// see enqueue_sweep) plus, on peers contexts, the time its fold + gather may legitimately wait for a slower rank.
-int armed_wait(cfmm_ctx* c, uint64_t want, bool& lost)
-{
-    lost = false;
-    bool seen = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    const double arm_s = 1e-3 * (double)std::min<int64_t>(std::max<int64_t>(c->opt_arm_timeout_ms, 1), 10000);
-    const double peer_s = 1e-8 * (double)c->peer_timeout_ticks;
-    const double limit = c->peers.empty() ? 2.0 * arm_s + 1.0 : std::max(arm_s, peer_s) + peer_s + 2.0;
-    for (long spins = 0;; ++spins) {
-        if (granules_arrived(c, want)) { seen = true; break; }
-        __builtin_ia32_pause();
-        if ((spins & 0xffff) == 0xffff && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit)
-            break;
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!seen) {
-        armed_lost(c, lost);
-        (void)take_flags(c, kFlagGaveUp);
-        return fail(c, CFMM_ERR_STATE, c->peers.empty()
-                        ? "armed evaluation did not complete (the device never saw its price vector)"
-                        : "armed evaluation did not complete within the arm + peer timeouts (this rank's launch never saw its "
-                          "price vector, or a peer never published)");
-    }
-    // NaN in the dual column: the blocks say why through the sticky report word.  A launch that gave up waiting for its
-    // prices is a LOST evaluation (retried unarmed by the caller); anything else -- arithmetic overflow, a peer gather that
-    // timed out -- is reported by take_host_out as what it is.
-    const double acc = c->h_stage[2 * c->n];
-    if (acc != acc) {
-        const unsigned long long why = take_flags(c, kFlagGaveUp);
-        if (why & kFlagGaveUp) {
-            armed_lost(c, lost);
-            return fail(c, CFMM_ERR_STATE, "armed evaluation gave up waiting for its price vector (host stalled longer than the arm timeout)");
-        }
-    }
-    int rc = take_host_out(c);
-    if (rc != CFMM_OK) armed_cancel_single(c);
-    return rc;
-}
-
-} // namespace
-
-bool can_arm(cfmm_ctx* c)
-{
-    if (!is_parent(c)) return can_arm_single(c);
-    if (c->opt_armed == 0 || !c->shards_distinct) return false;
-    for (cfmm_ctx* child : c->shards)
-        if (!child->segs.empty() && !can_arm_single(child)) return false;
-    return true;
-}
-
-void armed_cancel(cfmm_ctx* c)
-{
-    if (!c) return;
-    if (!is_parent(c)) return armed_cancel_single(c);
-    for (cfmm_ctx* child : c->shards) armed_cancel_single(child);
-}
-
-// One fused evaluation at v through the armed launches.  A lost evaluation (see armed_wait) is retried ONCE through the
-// launch-when-ready path before the call fails: a host that was paused between two evaluations (debugger, SIGSTOP,
-// oversubscription) costs a retry, not the route.  *lost_out tells the caller (cfmm_route stops arming for the rest of
-// the call: whatever stalled the hand-over once -- e.g. another process's launches holding this GPU's CUs -- may do so again).
-int armed_eval(cfmm_ctx* c, const double* v, bool* lost_out)
-{
-    if (lost_out) *lost_out = false;
-    int rc = check_prices(c, v);
-    if (rc != CFMM_OK) return rc;
-    if (!prices_in_fast_window(v, c->n)) {
-        // the waiting launch runs the fast arithmetic (its kernel was chosen before these prices existed): cancel it and
-        // evaluate launch-when-ready on the full-range kernels; the caller stops arming (prices this extreme stay extreme)
-        armed_cancel(c);
-        if (lost_out) *lost_out = true;
-        return is_parent(c) ? multi_host_sweep(c, v, false) : single_host_sweep(c, v, false);
-    }
-#ifdef CFMM_TEST_HOOKS
-    if (c->opt_debug_stall_ms > 0 && c->arm_pending) {   // test hook: the host "stalls" once while a launch waits for its prices
-        std::this_thread::sleep_for(std::chrono::milliseconds(c->opt_debug_stall_ms));
-        c->opt_debug_stall_ms = 0;
-    }
-#endif
-    if (!is_parent(c)) {
-        uint64_t want = 0;
-        bool signalled = false;
-        const int rc_next = armed_signal(c, v, want, signalled);
-        if (!signalled) return rc_next;
-        bool lost = false;
-        rc = armed_wait(c, want, lost);
-        if (rc != CFMM_OK && lost) {
-            armed_cancel_single(c);
-            if (lost_out) *lost_out = true;
-            return single_host_sweep(c, v, false);
-        }
-        if (rc != CFMM_OK) return rc;
-        return rc_next;
-    }
-    const int nd = (int)c->shards.size();
-    std::vector<uint64_t> want((size_t)nd, 0);
-    std::vector<int> rcs((size_t)nd, CFMM_OK);
-    std::vector<char> running((size_t)nd, 0);
-    for (int d = 0; d < nd; ++d)
-        if (!c->shards[(size_t)d]->segs.empty()) {
-            bool signalled = false;
-            rcs[(size_t)d] = armed_signal(c->shards[(size_t)d], v, want[(size_t)d], signalled);
-            running[(size_t)d] = signalled ? 1 : 0;
-        }
-    bool any_lost = false;
-    int first_err = CFMM_OK, err_shard = -1;
-    for (int d = 0; d < nd; ++d) {
-        cfmm_ctx* child = c->shards[(size_t)d];
-        if (child->segs.empty()) continue;
-        if (!running[(size_t)d]) {
-            if (first_err == CFMM_OK) { first_err = rcs[(size_t)d]; err_shard = d; }
-            continue;
-        }
-        bool lost = false;
-        const int rw = armed_wait(child, want[(size_t)d], lost);
-        any_lost = any_lost || lost;
-        running[(size_t)d] = (rw == CFMM_OK && !lost) ? 2 : 1;   // 2: this shard delivered the evaluation
-        const int r = rw != CFMM_OK ? rw : rcs[(size_t)d];
-        if (r != CFMM_OK && first_err == CFMM_OK) { first_err = r; err_shard = d; }
-    }
-    if (any_lost) {
-        armed_cancel(c);
-        for (int d = 0; d < nd; ++d)   // shards that did deliver repeat the evaluation too: it takes the same tile direction
-            if (running[(size_t)d] == 2) --c->shards[(size_t)d]->sweep_count;
-        if (lost_out) *lost_out = true;
-        return multi_host_sweep(c, v, false);
-    }
-    if (first_err != CFMM_OK) {
-        armed_cancel(c);
-        c->have_out = false;
-        return fail(c, first_err, "shard %d: %s", err_shard, c->shards[(size_t)err_shard]->err.c_str());
-    }
-    c->last_out.assign((size_t)c->n + 1, 0.0);   // the all-reduce: shard order, on the host
-    for (int d = 0; d < nd; ++d) {
-        const cfmm_ctx* child = c->shards[(size_t)d];
-        if (child->segs.empty()) continue;
-        for (int j = 0; j <= c->n; ++j) c->last_out[(size_t)j] += child->last_out[(size_t)j];
-    }
-    c->have_out = true;
-    c->have_trades = false;
-    return CFMM_OK;
-}
-
 } // namespace cfmm
 
 extern "C" {
-
-int cfmm_find_arb(cfmm_ctx* c, const double* v)
-{
-    if (!c) return CFMM_ERR_INVALID_ARG;
-    return host_sweep(c, v, true);
-}
-
-int cfmm_eval(cfmm_ctx* c, const double* v, double* psi_out, double* acc_out)
-{
-    if (!c) return CFMM_ERR_INVALID_ARG;
-    int rc = host_sweep(c, v, false);
-    if (rc != CFMM_OK) return rc;
-    c->have_trades = false; // trades on the device no longer correspond to the latest v
-    if (psi_out) std::memcpy(psi_out, c->last_out.data(), (size_t)c->n * sizeof(double));
-    if (acc_out) *acc_out = c->last_out[(size_t)c->n];
-    return CFMM_OK;
-}
-
-int cfmm_netflows(cfmm_ctx* c, double* psi)
-{
-    if (!c || !psi) return CFMM_ERR_INVALID_ARG;
-    if (!c->have_out) return fail(c, CFMM_ERR_STATE, "no sweep has been run yet");
-    std::memcpy(psi, c->last_out.data(), (size_t)c->n * sizeof(double));
-    return CFMM_OK;
-}
-
-int cfmm_dual_value(cfmm_ctx* c, double* acc)
-{
-    if (!c || !acc) return CFMM_ERR_INVALID_ARG;
-    if (!c->have_out) return fail(c, CFMM_ERR_STATE, "no sweep has been run yet");
-    *acc = c->last_out[(size_t)c->n];
-    return CFMM_OK;
-}
 
 int cfmm_sweep_dev(cfmm_ctx* c, const double* d_v, double* d_out, int materialize)
 {

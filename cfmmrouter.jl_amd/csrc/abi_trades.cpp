@@ -37,21 +37,6 @@ int expanded_trades(cfmm_ctx* c, const double2** dD, const double2** dL)
     return CFMM_OK;
 }
 
-int ensure_staging(cfmm_ctx* c)
-{
-    TradeStaging& t = c->tstage;
-    if (t.ready) return CFMM_OK;
-    for (int k = 0; k < TradeStaging::kThreads; ++k) {
-        HIP_TRY(c, hipStreamCreateWithFlags(&t.stream[k], hipStreamNonBlocking));
-        for (int s = 0; s < TradeStaging::kSlots; ++s) {
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&t.slot[k][s]), (size_t)TradeStaging::kChunkRows * sizeof(double2), hipHostMallocDefault));
-            HIP_TRY(c, hipEventCreateWithFlags(&t.done[k][s], hipEventDisableTiming));
-        }
-    }
-    t.ready = true;
-    return CFMM_OK;
-}
-
 // D2H of trade rows [row0, row0 + count) into Delta / Lambda ([count][2] each, either may be null).
 // Round 2 copied the 16-byte records into a pageable vector and decoded them on one thread (8 ms per 1M pools, and two
 // more full copies whenever a single pool had used the overflow rows).  Now the records are expanded on the DEVICE
@@ -70,7 +55,7 @@ int download_trades(cfmm_ctx* c, int64_t row0, int64_t count, double* Delta, dou
         if (Lambda) HIP_TRY(c, hipMemcpy(Lambda, dL + row0, (size_t)count * sizeof(double2), hipMemcpyDeviceToHost));
         return CFMM_OK;
     }
-    rc = ensure_staging(c);
+    rc = c->tstage.ensure(c);
     if (rc != CFMM_OK) return rc;
     struct Chunk { const double2* src; double* dst; int64_t rows; };
     std::vector<Chunk> chunks;
@@ -92,8 +77,8 @@ int download_trades(cfmm_ctx* c, int64_t row0, int64_t count, double* Delta, dou
         auto issue = [&](size_t idx) {
             const Chunk& ch = chunks[mine[idx]];
             const int s = (int)(idx % TradeStaging::kSlots);
-            hipError_t ee = hipMemcpyAsync(t.slot[k][s], ch.src, (size_t)ch.rows * sizeof(double2), hipMemcpyDeviceToHost, t.stream[k]);
-            if (ee == hipSuccess) ee = hipEventRecord(t.done[k][s], t.stream[k]);
+            hipError_t ee = hipMemcpyAsync(t.slot[k][s].host(), ch.src, (size_t)ch.rows * sizeof(double2), hipMemcpyDeviceToHost, t.stream[k].get());
+            if (ee == hipSuccess) ee = hipEventRecord(t.done[k][s].get(), t.stream[k].get());
             return ee;
         };
         if (e == hipSuccess && !mine.empty()) e = issue(0);
@@ -101,12 +86,12 @@ int download_trades(cfmm_ctx* c, int64_t row0, int64_t count, double* Delta, dou
             if (idx + 1 < mine.size()) e = issue(idx + 1);
             if (e != hipSuccess) break;
             const int s = (int)(idx % TradeStaging::kSlots);
-            e = hipEventSynchronize(t.done[k][s]);
+            e = hipEventSynchronize(t.done[k][s].get());
             if (e != hipSuccess) break;
             const Chunk& ch = chunks[mine[idx]];
-            std::memcpy(ch.dst, t.slot[k][s], (size_t)ch.rows * sizeof(double2));
+            std::memcpy(ch.dst, t.slot[k][s].host(), (size_t)ch.rows * sizeof(double2));
         }
-        if (e != hipSuccess) (void)hipStreamSynchronize(t.stream[k]);
+        if (e != hipSuccess) (void)hipStreamSynchronize(t.stream[k].get());
         errs[(size_t)k] = e;
     };
     std::vector<std::thread> helpers;
@@ -141,32 +126,6 @@ int download_segment(cfmm_ctx* c, const Segment& s, int64_t first, int64_t count
 }
 
 } // namespace
-
-namespace cfmm {
-
-void free_trade_staging(cfmm_ctx* c)
-{
-    TradeStaging& t = c->tstage;
-    for (int k = 0; k < TradeStaging::kThreads; ++k) {
-        for (int s = 0; s < TradeStaging::kSlots; ++s) {
-            if (t.slot[k][s]) (void)hipHostFree(t.slot[k][s]);
-            if (t.done[k][s]) (void)hipEventDestroy(t.done[k][s]);
-            t.slot[k][s] = nullptr;
-            t.done[k][s] = nullptr;
-        }
-        if (t.stream[k]) (void)hipStreamDestroy(t.stream[k]);
-        t.stream[k] = nullptr;
-    }
-    t.ready = false;
-    if (c->h_sel_total) (void)hipHostFree(c->h_sel_total);
-    c->h_sel_total = c->d_sel_total = nullptr;
-    for (hipEvent_t& e : c->sel_ev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-}
-
-} // namespace cfmm
 
 extern "C" {
 
@@ -232,32 +191,31 @@ int cfmm_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_val
     const int64_t rows = std::min(capacity, s.m);   // what the emit may write
     const bool emit = rows > 0 && (idx || Delta || Lambda || value);
     HIP_TRY(c, hipSetDevice(c->device));
+    SelectScratch& sc = c->sel;
     int rc;
-    if ((rc = c->d_sel_mask.grow(c, blocks * (kSelBlock / 64))) || (rc = c->d_sel_counts.grow(c, blocks)) ||
-        (rc = c->d_sel_base.grow(c, blocks)) || (rc = c->d_sel_v.grow(c, (size_t)c->n)))
+    if ((rc = sc.mask.grow(c, blocks * (kSelBlock / 64))) || (rc = sc.counts.grow(c, blocks)) || (rc = sc.base.grow(c, blocks)) ||
+        (rc = sc.v.grow(c, (size_t)c->n)))
         return rc;
-    if (emit && ((idx && (rc = c->d_sel_idx.grow(c, (size_t)rows))) || (Delta && (rc = c->d_sel_D.grow(c, (size_t)rows * nc))) ||
-                 (Lambda && (rc = c->d_sel_L.grow(c, (size_t)rows * nc))) || (value && (rc = c->d_sel_value.grow(c, (size_t)rows)))))
+    if (emit && ((idx && (rc = sc.idx.grow(c, (size_t)rows))) || (Delta && (rc = sc.D.grow(c, (size_t)rows * nc))) ||
+                 (Lambda && (rc = sc.L.grow(c, (size_t)rows * nc))) || (value && (rc = sc.value.grow(c, (size_t)rows)))))
         return rc;
-    if (!c->h_sel_total) {
-        HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_sel_total), 128, hipHostMallocMapped));
-        if (hipHostGetDevicePointer(reinterpret_cast<void**>(&c->d_sel_total), c->h_sel_total, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipHostFree(c->h_sel_total);
-            c->h_sel_total = c->d_sel_total = nullptr;
-            return fail(c, CFMM_ERR_HIP, "cfmm_select_trades: pinned host memory is not device-mapped");
-        }
+    if ((rc = sc.total.grow(c, 16, true)) != CFMM_OK) return rc;   // (its own 128-byte line)
+    if (!sc.total.dev()) {
+        sc.total.reset();
+        return fail(c, CFMM_ERR_HIP, "cfmm_select_trades: pinned host memory is not device-mapped");
     }
     const bool timed = c->opt_time_kernels != 0;
-    if (timed)
-        for (hipEvent_t& e : c->sel_ev)
-            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    hipEvent_t sel_ev[6] = {};
+    for (int k = 0; k < 6 && timed; ++k) {
+        if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
+        sel_ev[k] = sc.ev[k].get();
+    }
     // the prices: uploaded per call (n doubles; a pageable source is staged by the runtime before the call returns)
-    HIP_TRY(c, hipMemcpyAsync(c->d_sel_v.get(), v, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.v.get(), v, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     SelectArgs a{};
     a.m = s.m;
     a.n_coins = nc;
-    a.v = c->d_sel_v.get();
+    a.v = sc.v.get();
     a.min_value = min_value;
     if (ragged) {
         a.ncD = s.nc.D.get();
@@ -271,36 +229,36 @@ int cfmm_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_val
         a.pk = s.pk.get();
         a.Ai = s.Ai.get();
     }
-    a.mask = c->d_sel_mask.get();
-    a.counts = c->d_sel_counts.get();
-    a.base = c->d_sel_base.get();
+    a.mask = sc.mask.get();
+    a.counts = sc.counts.get();
+    a.base = sc.base.get();
     a.capacity = rows;
-    a.out_idx = idx ? c->d_sel_idx.get() : nullptr;
-    a.out_D = Delta ? c->d_sel_D.get() : nullptr;
-    a.out_L = Lambda ? c->d_sel_L.get() : nullptr;
-    a.out_value = value ? c->d_sel_value.get() : nullptr;
-    *c->h_sel_total = -1;
-    hipError_t e = launch_select_count(a, ragged, c->d_sel_total, c->stream, timed ? c->sel_ev : nullptr);
-    if (e == hipSuccess && emit) e = launch_select_emit(a, ragged, c->stream, timed ? c->sel_ev : nullptr);
+    a.out_idx = idx ? sc.idx.get() : nullptr;
+    a.out_D = Delta ? sc.D.get() : nullptr;
+    a.out_L = Lambda ? sc.L.get() : nullptr;
+    a.out_value = value ? sc.value.get() : nullptr;
+    *sc.total.host() = -1;
+    hipError_t e = launch_select_count(a, ragged, sc.total.dev(), c->stream, timed ? sel_ev : nullptr);
+    if (e == hipSuccess && emit) e = launch_select_emit(a, ragged, c->stream, timed ? sel_ev : nullptr);
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "select launch failed: %s", hipGetErrorString(e));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const int64_t total = *static_cast<volatile long long*>(c->h_sel_total);
+    const int64_t total = *static_cast<volatile long long*>(sc.total.host());
     if (total < 0 || total > s.m) return fail(c, CFMM_ERR_HIP, "cfmm_select_trades: the count did not arrive");
     if (timed)
         for (int k = 0; k < 3; ++k) {
             float ms = 0.f;
-            c->sel_ns[k] = 0;
+            sc.ns[k] = 0;
             if (k == 2 && !emit) continue;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->sel_ev[2 * k], c->sel_ev[2 * k + 1]));
-            c->sel_ns[k] = (int64_t)((double)ms * 1e6);
+            HIP_TRY(c, hipEventElapsedTime(&ms, sel_ev[2 * k], sel_ev[2 * k + 1]));
+            sc.ns[k] = (int64_t)((double)ms * 1e6);
         }
     *count = total;
     const size_t w = (size_t)std::min(total, rows);   // rows to copy back: exactly these, and nothing when there are none
     if (!emit || w == 0) return CFMM_OK;
-    if (idx) HIP_TRY(c, hipMemcpy(idx, c->d_sel_idx.get(), w * sizeof(long long), hipMemcpyDeviceToHost));
-    if (Delta) HIP_TRY(c, hipMemcpy(Delta, c->d_sel_D.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (Lambda) HIP_TRY(c, hipMemcpy(Lambda, c->d_sel_L.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
-    if (value) HIP_TRY(c, hipMemcpy(value, c->d_sel_value.get(), w * sizeof(double), hipMemcpyDeviceToHost));
+    if (idx) HIP_TRY(c, hipMemcpy(idx, sc.idx.get(), w * sizeof(long long), hipMemcpyDeviceToHost));
+    if (Delta) HIP_TRY(c, hipMemcpy(Delta, sc.D.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (Lambda) HIP_TRY(c, hipMemcpy(Lambda, sc.L.get(), w * nc * sizeof(double), hipMemcpyDeviceToHost));
+    if (value) HIP_TRY(c, hipMemcpy(value, sc.value.get(), w * sizeof(double), hipMemcpyDeviceToHost));
     return CFMM_OK;
 }
 

@@ -125,36 +125,11 @@ Rows distinct_rows(int64_t count, const int64_t* idx)
     return r;
 }
 
-// The staging buffer with room for `words` 8-byte words, free for the host to fill: the previous scatter has read it
-int staging_reserve(cfmm_ctx* c, size_t words)
-{
-    if (c->upd_busy) {
-        HIP_TRY(c, hipEventSynchronize(c->upd_done));
-        c->upd_busy = false;
-    }
-    if (!c->upd_done) HIP_TRY(c, hipEventCreateWithFlags(&c->upd_done, hipEventDisableTiming));
-    const size_t bytes = (words + 8 * (size_t)kMaxScatterCols) * 8;   // (+ the columns' alignment)
-    if (bytes <= c->upd_cap) return CFMM_OK;
-    size_t cap = std::max<size_t>(c->upd_cap * 2, 1 << 16);
-    while (cap < bytes) cap *= 2;
-    void *h = nullptr, *d = nullptr;
-    if (hipHostMalloc(&h, cap, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        if (h) (void)hipHostFree(h);
-        return fail(c, CFMM_ERR_HIP, "pool update: staging allocation of %zu bytes failed", cap);
-    }
-    if (c->h_upd) (void)hipHostFree(c->h_upd);
-    c->h_upd = h;
-    c->d_upd = d;
-    c->upd_cap = cap;
-    return CFMM_OK;
-}
-
 // Columns of one scatter launch, laid out in the staging buffer in the order they are added
 struct Packer {
     ScatterArgs a{};
     unsigned long long* h;
-    explicit Packer(cfmm_ctx* c) : h(static_cast<unsigned long long*>(c->h_upd)) { a.stage = static_cast<const unsigned long long*>(c->d_upd); }
+    explicit Packer(cfmm_ctx* c) : h(c->upd.buf.host()) { a.stage = c->upd.buf.dev(); }
     // -> the host side of a column of `rows` rows, `width` words each
     template <class T>
     T* add(void* dst, int width, int64_t rows, int64_t dense_base = -1)
@@ -181,8 +156,8 @@ struct Packer {
 int launch(cfmm_ctx* c, const Packer& p)
 {
     HIP_TRY(c, launch_scatter_records(p.a, c->stream));
-    HIP_TRY(c, hipEventRecord(c->upd_done, c->stream));
-    c->upd_busy = true;
+    HIP_TRY(c, hipEventRecord(c->upd.done.get(), c->stream));
+    c->upd.busy = true;
     return CFMM_OK;
 }
 
@@ -213,20 +188,20 @@ int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
     DevBuf<int4> d_walk;
     if (d_ticks.alloc(c, (size_t)cap) != CFMM_OK || d_thr.alloc(c, (size_t)cap + 4) != CFMM_OK || d_walk.alloc(c, walk.size()) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "pool update: allocation of %lld tick records failed", (long long)cap);
-    int rc = staging_reserve(c, 2 * walk.size());
+    UpdateStaging& st = c->upd;
+    int rc = st.reserve(c, 2 * walk.size());
     if (rc != CFMM_OK) return rc;
-    std::memcpy(c->h_upd, walk.data(), walk.size() * sizeof(int4));
+    std::memcpy(st.buf.host(), walk.data(), walk.size() * sizeof(int4));
     const bool timed = c->opt_time_kernels != 0;
-    if (timed)
-        for (hipEvent_t& e : c->compact_ev)
-            if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, launch_compact_walks(u.walk.get(), static_cast<const int4*>(c->d_upd), d_walk.get(), u.ticks.get(), d_ticks.get(), d_thr.get(),
-                                    s.m, tight, c->stream, timed ? c->compact_ev[0] : nullptr, timed ? c->compact_ev[1] : nullptr));
+    for (Event& e : st.compact_ev)
+        if (timed && (rc = e.create(c, hipEventDefault)) != CFMM_OK) return rc;
+    HIP_TRY(c, launch_compact_walks(u.walk.get(), reinterpret_cast<const int4*>(st.buf.dev()), d_walk.get(), u.ticks.get(), d_ticks.get(), d_thr.get(),
+                                    s.m, tight, c->stream, timed ? st.compact_ev[0].get() : nullptr, timed ? st.compact_ev[1].get() : nullptr));
     // One wait is kept, for the kernel itself: the old arrays are released below and the staging is refilled by the scatter that
     // follows, and both must outlive the kernel's reads (hipFree would wait for the device anyway; this says so).
-    HIP_TRY(c, hipEventRecord(c->upd_done, c->stream));
-    HIP_TRY(c, hipEventSynchronize(c->upd_done));
-    c->upd_busy = false;
+    HIP_TRY(c, hipEventRecord(st.done.get(), c->stream));
+    HIP_TRY(c, hipEventSynchronize(st.done.get()));
+    st.busy = false;
     u.ticks = std::move(d_ticks);   // (releases the old arrays)
     u.thr = std::move(d_thr);
     u.walk = std::move(d_walk);
@@ -236,8 +211,8 @@ int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
     ++c->pool_update_regrows;
     if (timed) {
         float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->compact_ev[0], c->compact_ev[1]));
-        c->compact_ns = (int64_t)((double)ms * 1e6);
+        HIP_TRY(c, hipEventElapsedTime(&ms, st.compact_ev[0].get(), st.compact_ev[1].get()));
+        st.compact_ns = (int64_t)((double)ms * 1e6);
     }
     return CFMM_OK;
 }
@@ -273,7 +248,7 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     if (!st.has_walk && lists && new_head.alloc(c, 2 * (size_t)s.m) != CFMM_OK)
         return fail(c, CFMM_ERR_HIP, "pool update: allocation of the threshold heads failed");
     const size_t words = (size_t)k * (2 + 1 + 2 + 2 + 1 + 2 + 2 + 4 + 1) + (size_t)nrec * 9 + 4;
-    if ((rc = staging_reserve(c, words)) != CFMM_OK) return rc;
+    if ((rc = c->upd.reserve(c, words)) != CFMM_OK) return rc;
     if (new_head) {
         HIP_TRY(c, hipMemsetAsync(new_head.get(), 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
         st.head = std::move(new_head);
@@ -330,7 +305,7 @@ int apply_reserves(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
     const int64_t k = (int64_t)rows.idx.size(), m = s.m;
     const bool ragged = ragged_kind(s.kind);
     const int nc = ragged ? s.n_coins : 2;
-    int rc = staging_reserve(c, (size_t)k * (2 * (size_t)nc + 2 + 1));
+    int rc = c->upd.reserve(c, (size_t)k * (2 * (size_t)nc + 2 + 1));
     if (rc != CFMM_OK) return rc;
     Packer p(c);
     bool fast = true;
@@ -463,6 +438,25 @@ int update(cfmm_ctx* c, const Update& u)
 }
 
 } // namespace
+
+// The staging buffer with room for `words` 8-byte words, free for the host to fill: the previous scatter has read it
+int cfmm::UpdateStaging::reserve(cfmm_ctx* c, size_t words)
+{
+    if (busy) {
+        HIP_TRY(c, hipEventSynchronize(done.get()));
+        busy = false;
+    }
+    if (const int rc = done.create(c, hipEventDisableTiming)) return rc;
+    words += 8 * (size_t)kMaxScatterCols;   // (+ the columns' alignment)
+    if (words <= buf.size()) return CFMM_OK;
+    size_t cap = std::max<size_t>(buf.size() * 2, 1 << 13);
+    while (cap < words) cap *= 2;
+    if (buf.alloc(c, cap, true) != CFMM_OK || !buf.dev()) {
+        buf.reset();
+        return fail(c, CFMM_ERR_HIP, "pool update: staging allocation of %zu bytes failed", cap * 8);
+    }
+    return CFMM_OK;
+}
 
 extern "C" {
 

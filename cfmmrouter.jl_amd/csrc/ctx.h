@@ -3,11 +3,13 @@
 // entry point that needs one fails with CFMM_ERR_HIP.
 //
 //   devbuf.h          DevBuf<T>: the one owner of a device array (every Segment / context array below is one)
-//   abi_context.cpp   create / destroy / options / streams / introspection, dev_alloc / dev_free
+//   hostres.h         PinnedBuf<T>, Event, Stream: the owners of pinned memory, events and streams; TradeStaging
+//   granule.h         the self-validating output granule {tag, 32 bits}, for host and device code
+//   abi_context.cpp   create / destroy / options / streams / introspection, the raw create / destroy calls of every owner
 //   abi_upload.cpp    pool validation + upload (src/cfmms.jl:76-111, :152-165, :226-245), prepared constants
 //   launch_plan.cpp   the launch geometry of one evaluation, as a pure function (launch_plan.h: no HIP, no context)
-//   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold, host-pointer
-//                     sweeps, pre-armed evaluations
+//   abi_sweep.cpp     applies the plan (fee tables, buffers), one evaluation = sweep launches + row fold
+//   abi_handover.cpp  how an evaluation's result crosses to the host: host-pointer sweeps, the granule wait, pre-armed evaluations
 //   abi_trades.cpp    trade download / device views, the selection of the trades worth executing, update_reserves!,
 //                     reserves / prices read-back
 //   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices / _set_ticks)
@@ -20,6 +22,7 @@
 
 #include "../../include/cfmm_amd.h"
 #include "devbuf.h"
+#include "hostres.h"
 #include "ladder_store.h"
 #include "launch_plan.h"
 #include "sweep.h"
@@ -38,8 +41,8 @@
 
 namespace cfmm {
 
-// Device memory has one owner (devbuf.h): every device array below is a DevBuf member and goes with the object that holds
-// it -- Segment destruction, a move assignment, segs.clear() -- so no list of frees exists anywhere.  The view structs of
+// Every resource has one owner (devbuf.h, hostres.h): every device array below is a DevBuf member and goes with the object
+// that holds it -- Segment destruction, a move assignment, segs.clear() -- so no list of frees exists anywhere.  The view structs of
 // sweep.h that cross into a kernel are built from `.get()` per launch (abi_sweep.cpp pools_of) and never own.
 // A segment of one kind leaves the groups of the other kinds empty.
 
@@ -154,14 +157,75 @@ struct Workers {
     std::vector<int> rc;
 };
 
-// Pinned staging of the trade download (abi_trades.cpp): a few worker threads, each with its own stream and two slots.
-struct TradeStaging {
-    static constexpr int kThreads = 4, kSlots = 2;
-    static constexpr int64_t kChunkRows = 1 << 16;   // 1 MiB per slot
-    double2* slot[kThreads][kSlots] = {{nullptr}};
-    hipStream_t stream[kThreads] = {nullptr};
-    hipEvent_t done[kThreads][kSlots] = {{nullptr}};
-    bool ready = false;
+// The hand-over concerns of a context: each owns its resources (hostres.h, devbuf.h) and carries the few functions that
+// touch them; all of it goes with the context.
+
+// Zero-copy stage (abi_handover.cpp), pinned + device-mapped: [n] v in, [n+1] {Ψ, acc} out, padding to a 128-byte boundary,
+// then the output granules (granule.h; 16 per fold block = 2 per column, columns padded to a multiple of 8; see fold_finish)
+struct HostStage {
+    PinnedBuf<double> buf;        // dev() null: no mapping, explicit copies
+    int n = 0;
+    size_t gran_off = 0;          // first output granule (doubles)
+    size_t flag_off = 0;          // the sweeps' sticky report word (sweep.h kFlagWindow / kFlagGaveUp), its own 128-byte line
+    uint64_t out_seq = 0;         // sequence number of the latest granule-delivering sweep
+    bool last_host_out = false;   // the latest enqueue_sweep delivers {psi, acc} as granules (the caller polls them)
+    double* out() const { return buf.host() + n; }   // the {Ψ, acc} slots
+    int alloc(const cfmm_ctx* c, int n_tokens);
+    unsigned long long take_flags(unsigned long long mask);
+    bool granules_arrived(uint64_t seq);
+    bool wait(uint64_t seq, long max_spins, double limit_s);
+};
+
+// Pre-armed evaluations of cfmm_route (sweep.h SweepArgs::arm_word): [n_pad] v, then the word, in FINE-GRAINED device
+// memory that the host writes through the PCIe BAR (empty: no large BAR, or the self-check failed)
+struct ArmState {
+    DevBuf<double> buf;
+    int n = 0, n_pad = 0;
+    uint64_t seq = 0;             // sequence number of the latest armed launch
+    bool pending = false;         // an armed launch is enqueued and has not been signalled or cancelled yet
+    uint64_t tag = 0;             // output sequence number that launch will deliver
+    const unsigned long long* word() const { return reinterpret_cast<const unsigned long long*>(buf.get() + n_pad); }
+    void alloc(int device, int n_tokens, int n_padded);
+    void write(const double* v, uint64_t word);
+};
+
+// Sparse pool-state updates (abi_update.cpp, cfmm_pools_set_*): pinned + device-mapped staging of the prepared records in
+// 8-byte words, grown geometrically; `done` marks the end of the latest scatter launch (the staging is reused only after it)
+struct UpdateStaging {
+    PinnedBuf<unsigned long long> buf;
+    Event done;
+    bool busy = false;
+    Event compact_ev[2];          // option "time_kernels": {start, stop} of the latest compact_walks launch
+    int64_t compact_ns = 0;       // read-only option "compact_walks_ns": that launch's span
+    int reserve(cfmm_ctx* c, size_t words);
+};
+
+// cfmm_select_trades (abi_trades.cpp, select_kernels.h): scratch, the device copy of the valuing prices and the compacted
+// rows, grown on demand and kept for the next call; the scan delivers the count to one pinned, device-mapped word
+struct SelectScratch {
+    DevBuf<unsigned long long> mask;   // [blocks][kSelBlock / 64]
+    DevBuf<int> counts;                // [blocks]
+    DevBuf<long long> base;            // [blocks]
+    DevBuf<double> v;                  // [n]
+    DevBuf<long long> idx;             // [rows]
+    DevBuf<double> D, L;               // [rows][n_coins]
+    DevBuf<double> value;              // [rows]
+    PinnedBuf<long long> total;
+    Event ev[6];                       // option "time_kernels": {start, stop} per kernel
+    int64_t ns[3] = {0, 0, 0};         // read-only options "select_flag_ns" / "select_scan_ns" / "select_emit_ns": the
+                                       // latest timed call's kernel spans (emit: 0 when the call only counted)
+};
+
+// Kernel timing (option "time_kernels"): a pool of events, the {start, stop} pairs not yet read, the totals
+struct KernelTimer {
+    std::vector<Event> pool;
+    size_t used = 0;
+    struct Pending { hipEvent_t a, b; int what; };
+    std::vector<Pending> pending;
+    int64_t sweep_n = 0, reduce_n = 0;
+    double sweep_ms = 0, reduce_ms = 0;
+    void take_events(hipEvent_t& a, hipEvent_t& b);   // a start / stop pair for one timed launch (both null when none could be had)
+    int harvest(cfmm_ctx* c, int64_t* sweep_launches, double* sweep_ms_out, int64_t* reduce_launches, double* reduce_ms_out);
 };
 
 } // namespace cfmm
@@ -170,7 +234,9 @@ struct cfmm_ctx {
     int device = 0;
     int n = 0;
     int n_pad = 0;
-    hipStream_t own_stream = nullptr;
+    // FIRST among the members that own a HIP resource: members go in reverse order, so the context's own stream is
+    // released after every DevBuf, pinned buffer and event below
+    cfmm::Stream own_stream;
     hipStream_t stream = nullptr;
     std::vector<cfmm::Segment> segs;
     std::vector<cfmm::Group> groups;
@@ -211,21 +277,9 @@ struct cfmm_ctx {
     // in-stream, by ncclAllReduce(d_out, n + 1 doubles) -- same contract as `peers`, one exchange at a time
     void* rccl_comm = nullptr;    // ncclComm_t
     bool rccl_owned = false;      // created by cfmm_rccl_init_rank: destroyed with the context
-    // pinned + device-mapped staging: [n] v in, [n+1] {Ψ, acc} out, padding to a 128-byte boundary, then the output
-    // granules (16 per fold block = 2 per column, columns padded to a multiple of 8; see fold_finish)
-    double* h_stage = nullptr;
-    double* d_stage = nullptr;    // device address of h_stage
-    size_t gran_off = 0;          // first output granule in h_stage / d_stage (doubles)
-    size_t flag_off = 0;          // the sweeps' sticky report word (sweep.h kFlagWindow / kFlagGaveUp), its own 128-byte line
+    cfmm::HostStage stage;
     cfmm::DevBuf<double> d_gtab;  // [groups][kMaxFeeTable] fee tables of the launches (packed pool records)
-    // pre-armed evaluations of cfmm_route (sweep.h SweepArgs::arm_word): [n_pad] v, then the word, in FINE-GRAINED
-    // device memory that the host writes through the PCIe BAR (null: no large BAR, or the self-check failed)
-    double* d_arm = nullptr;
-    uint64_t arm_seq = 0;         // sequence number of the latest armed launch
-    bool arm_pending = false;     // an armed launch is enqueued and has not been signalled or cancelled yet
-    uint64_t arm_tag = 0;         // output tag that launch will deliver
-    uint64_t out_seq = 0;         // host-visible outputs: sequence number of the latest granule-delivering sweep
-    bool last_host_out = false;   // the latest enqueue_sweep delivers {psi, acc} as granules (the caller polls them)
+    cfmm::ArmState arm;
     std::vector<double> last_out; // psi..., acc of the latest host-pointer sweep
     std::vector<double> trade_v;  // v of the latest MATERIALISING host-pointer sweep (empty: none / device-pointer sweep)
     bool have_out = false;
@@ -239,7 +293,7 @@ struct cfmm_ctx {
     int64_t opt_compact_trades = 1; // 1: a materialising sweep writes one 16-byte trade record per pool (+ overflow rows)
     int64_t opt_alternate = 1;     // 1: consecutive sweeps walk the tiles in alternating directions (L2 reuse across sweeps)
     int64_t opt_fast_math = 1;     // 1: division / square root without range scaffolding where operands are inside the window (same bits)
-    int64_t opt_armed = 1;         // 1: cfmm_route enqueues evaluation k+1 while evaluation k runs (see abi_sweep.cpp)
+    int64_t opt_armed = 1;         // 1: cfmm_route enqueues evaluation k+1 while evaluation k runs (see abi_handover.cpp)
     int64_t opt_arm_timeout_ms = 2000; // bound of that wait
     int64_t opt_host_flag = 1;     // 1: zero-copy host-pointer sweeps deliver {Ψ, acc} as self-validating granules that the caller
                                    //    polls, instead of waiting for the stream (saves the end-of-kernel + signal path)
@@ -258,39 +312,10 @@ struct cfmm_ctx {
                                     //    exist there alone; the FIELD is unconditional so that every translation unit sees one layout)
     uint64_t sweep_count = 0;
 
-    // sparse pool-state updates (abi_update.cpp, cfmm_pools_set_*): pinned + device-mapped staging of the prepared records, grown
-    // geometrically; upd_done marks the end of the latest scatter launch (the staging is reused only after it)
-    void* h_upd = nullptr;
-    void* d_upd = nullptr;        // device address of h_upd
-    size_t upd_cap = 0;           // bytes
-    hipEvent_t upd_done = nullptr;
-    bool upd_busy = false;
+    cfmm::UpdateStaging upd;
     int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
-    hipEvent_t compact_ev[2] = {nullptr, nullptr};   // option "time_kernels": {start, stop} of the latest compact_walks launch
-    int64_t compact_ns = 0;            // read-only option "compact_walks_ns": that launch's span
-
-    // cfmm_select_trades (abi_trades.cpp, select_kernels.h): scratch, the device copy of the valuing prices and the compacted
-    // rows, grown on demand and kept for the next call; the scan delivers the count to one pinned, device-mapped word
-    cfmm::DevBuf<unsigned long long> d_sel_mask;   // [blocks][kSelBlock / 64]
-    cfmm::DevBuf<int> d_sel_counts;                // [blocks]
-    cfmm::DevBuf<long long> d_sel_base;            // [blocks]
-    cfmm::DevBuf<double> d_sel_v;                  // [n]
-    cfmm::DevBuf<long long> d_sel_idx;             // [rows]
-    cfmm::DevBuf<double> d_sel_D, d_sel_L;         // [rows][n_coins]
-    cfmm::DevBuf<double> d_sel_value;              // [rows]
-    long long* h_sel_total = nullptr;
-    long long* d_sel_total = nullptr;              // device address of h_sel_total
-    hipEvent_t sel_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // option "time_kernels": {start, stop} per kernel
-    int64_t sel_ns[3] = {0, 0, 0};                 // read-only options "select_flag_ns" / "select_scan_ns" / "select_emit_ns": the
-                                                   // latest timed call's kernel spans (emit: 0 when the call only counted)
-
-    // kernel timing
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    struct Pending { hipEvent_t a, b; int what; };
-    std::vector<Pending> pending;
-    int64_t t_sweep_n = 0, t_reduce_n = 0;
-    double t_sweep_ms = 0, t_reduce_ms = 0;
+    cfmm::SelectScratch sel;
+    cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
     std::vector<cfmm_ctx*> shards;
@@ -330,8 +355,9 @@ int ensure_geometry(cfmm_ctx* c);
 constexpr int kPricesUnknown = 0, kPricesInWindow = 1, kPricesOutside = 2;
 int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materialize, bool want_host_out = false,
                   uint64_t arm_seq = 0, int price_window = kPricesUnknown);
+
+// abi_handover.cpp
 bool prices_in_fast_window(const double* v, int n);
-unsigned long long take_flags(cfmm_ctx* c, unsigned long long mask);
 int check_prices(cfmm_ctx* c, const double* v);
 int host_sweep_begin(cfmm_ctx* c, const double* v, bool materialize);
 int host_sweep_end(cfmm_ctx* c);
@@ -349,9 +375,6 @@ int child_segment(const cfmm_ctx* c, int pseg, int d);
 int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t count, double* Delta, double* Lambda);
 int multi_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_value, int64_t capacity, int64_t* count, int64_t* idx,
                         double* Delta, double* Lambda, double* value);
-
-// abi_trades.cpp
-void free_trade_staging(cfmm_ctx* c);   // (and the pinned word and events of cfmm_select_trades)
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

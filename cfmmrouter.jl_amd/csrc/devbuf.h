@@ -2,7 +2,8 @@
 // The rule it carries: a DevBuf ALWAYS owns what it points to -- it frees in its destructor, a move hands the array over,
 // nothing copies it -- and a device view struct (sweep.h: ProductPools, UniV3Pools, NCoinPools, ScatterArgs, ...) NEVER
 // does: a view takes `.get()` for the length of one launch.  Every allocation and release goes through dev_alloc /
-// dev_free (abi_context.cpp), the only callers of hipMalloc / hipFree for the library's own arrays.
+// dev_alloc_fine / dev_free (abi_context.cpp), the only callers of hipMalloc / hipExtMallocWithFlags / hipFree for the
+// library's own arrays.  (The owners of pinned memory, events and streams: hostres.h.)
 #pragma once
 
 #include "../../include/cfmm_amd.h"
@@ -17,6 +18,7 @@ int fail(const cfmm_ctx* c, int code, const char* fmt, ...);
 
 // abi_context.cpp
 hipError_t dev_alloc(void** p, size_t bytes);   // *p = nullptr on failure
+hipError_t dev_alloc_fine(void** p, size_t bytes);   // the same in FINE-GRAINED device memory (the host writes it through the PCIe BAR)
 void dev_free(void* p);
 
 template <class T>
@@ -62,6 +64,16 @@ public:
         p_ = static_cast<T*>(p);
         n_ = count;
         return CFMM_OK;
+    }
+    // `count` elements of fine-grained memory.  Optional wherever it is used: a failure leaves the buffer empty and sets no error
+    bool alloc_fine(size_t count)
+    {
+        reset();
+        void* p = nullptr;
+        if (count == 0 || dev_alloc_fine(&p, count * sizeof(T)) != hipSuccess) return false;
+        p_ = static_cast<T*>(p);
+        n_ = count;
+        return true;
     }
     // alloc + a blocking copy of `count` elements from the host
     int upload(const cfmm_ctx* c, const void* src, size_t count)

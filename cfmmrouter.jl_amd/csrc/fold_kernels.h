@@ -2,6 +2,7 @@
 // of a sharded run) and the large-market gather.
 #pragma once
 
+#include "granule.h"
 #include "sweep.h"
 
 namespace cfmm {
@@ -83,9 +84,8 @@ __device__ __forceinline__ void fold_finish(double tsum, bool ok, int n1, int co
         const double val = (tid < kReduceCols && col < n1) ? (ok ? tsum : __builtin_nan("")) : 0.0;
         const long long bits = __shfl(__double_as_longlong(val), (tid >> 1) & (kReduceCols - 1), 64);
         if (tid < 2 * kReduceCols) {
-            const unsigned long long tag = (host.tag & 0xffffffffull) << 32, u = (unsigned long long)bits;
             __hip_atomic_store(host.gran + 2 * (size_t)colblock * kReduceCols + tid,
-                               tag | ((tid & 1) ? (u >> 32) : (u & 0xffffffffull)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                               granule_of_bits(host.tag, (unsigned long long)bits, tid & 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     } else if (tid < kReduceCols && col < n1) {
         out[col] = ok ? tsum : __builtin_nan("");
@@ -129,7 +129,9 @@ __global__ __launch_bounds__(BLOCK) void reduce_gather(const double* __restrict_
     const int tid = threadIdx.x;
     if (tid >= 64) return;                                // the exchange is wavefront 0's business
     const int parity = (int)(ps.seq & 1ull);
-    const unsigned long long tag = (ps.seq % 0xffffffffull + 1ull) << 32;   // never 0 (= an empty buffer)
+    // (the store and the peers' check below stay written out: through granule.h's granule / granule_join this kernel's
+    // assembly changes, profiles/host_owners_digest.txt)
+    const unsigned long long tag = granule_tag(ps.seq) << 32;
     const int col = colblock * kReduceCols + tid;
     if (tid < kReduceCols && col < n1 && ps.world > 1) {
         const unsigned long long bits = (unsigned long long)__double_as_longlong(tsum);

@@ -2,6 +2,7 @@
 // (process_pool), the tile loops, the block epilogue and the kernels sweep_kernel (one segment) / sweep_multi (several).
 #pragma once
 
+#include "granule.h"
 #include "ops_two_coin.h"
 #include "ops_univ3.h"
 
@@ -95,7 +96,7 @@ __device__ __forceinline__ int wait_armed(const SweepArgs& a)
 }
 
 // A block reports WHY it poisons its row (NaN in every column): one sticky word in mapped host memory, read by the
-// host when it meets a non-finite result (abi_sweep.cpp).  Rare paths only.
+// host when it meets a non-finite result (abi_handover.cpp).  Rare paths only.
 __device__ __forceinline__ void report(const SweepArgs& a, unsigned long long bit)
 {
     if (a.flags && threadIdx.x == 0) __hip_atomic_fetch_or(a.flags, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -320,7 +321,7 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
 //               upload) and so are the prices -- which the host KNOWS (host-pointer sweeps, cfmm_route).  Every block still
 //               checks the prices it stages; outside the window it does NOT compute: it poisons its row (NaN in every column
 //               -- an error, never a wrong number) and reports kFlagWindow (reachable only through a pre-armed launch whose
-//               host-side check raced; abi_sweep.cpp cancels such launches before they run);
+//               host-side check raced; abi_handover.cpp cancels such launches before they run);
 //   kArithAuto  round 5, device-pointer sweeps (cfmm_sweep_dev): the library cannot see these prices, so the kernel carries
 //               BOTH tile loops and every block chooses from the prices it staged (block-uniform, and the same choice in every
 //               block: all stage the same vector) -- prices outside the window, NaN included, take the full-range loop and
@@ -371,8 +372,7 @@ typedef unsigned long long u2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void publish_column(const SweepArgs& a, int j, double val)
 {
     if (a.direct_host.gran) {
-        const unsigned long long tag = (a.direct_host.tag & 0xffffffffull) << 32, u = (unsigned long long)__double_as_longlong(val);
-        u2v g = {tag | (u & 0xffffffffull), tag | (u >> 32)};
+        u2v g = {granule(a.direct_host.tag, val, 0), granule(a.direct_host.tag, val, 1)};
         asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" : : "v"(a.direct_host.gran + 2 * (size_t)j), "v"(g) : "memory");
     } else {
         a.direct_out[j] = val;

@@ -1,5 +1,5 @@
 // Host build of csrc/devbuf.h for tests/test_devbuf_cpu.py: DevBuf<double> over malloc / free.  Not linked against the HIP
-// runtime: dev_alloc / dev_free are defined HERE (they count the live allocations, and the k-th allocation from
+// runtime: dev_alloc / dev_alloc_fine / dev_free are defined HERE (they count the live allocations, and the k-th allocation from
 // devbuf_fail_at(k) on fails), as are the stubs of hipMemcpy, hipGetErrorString and fail.  Nothing touches a GPU.
 #include "devbuf.h"
 
@@ -23,6 +23,8 @@ hipError_t dev_alloc(void** p, size_t bytes)
     ++g_live;
     return hipSuccess;
 }
+
+hipError_t dev_alloc_fine(void** p, size_t bytes) { return dev_alloc(p, bytes); }   // (the same counter and the same injected failures)
 
 void dev_free(void* p)
 {
@@ -61,6 +63,7 @@ void devbuf_delete(Buf* b) { delete b; }
 Buf* devbuf_move_new(Buf* src) { return new Buf(std::move(*src)); }
 void devbuf_move_assign(Buf* dst, Buf* src) { *dst = std::move(*src); }
 int devbuf_alloc(Buf* b, long long n) { return b->alloc(nullptr, (size_t)n); }
+int devbuf_alloc_fine(Buf* b, long long n) { return b->alloc_fine((size_t)n) ? 1 : 0; }
 int devbuf_upload(Buf* b, const double* src, long long n) { return b->upload(nullptr, src, (size_t)n); }
 int devbuf_grow(Buf* b, long long n) { return b->grow(nullptr, (size_t)n); }
 void devbuf_reset(Buf* b) { b->reset(); }

@@ -27,7 +27,7 @@ def lib(tmp_path_factory):
     L.devbuf_delete.argtypes = [vp]
     L.devbuf_move_new.restype, L.devbuf_move_new.argtypes = vp, [vp]
     L.devbuf_move_assign.argtypes = [vp, vp]
-    for f in (L.devbuf_alloc, L.devbuf_grow):
+    for f in (L.devbuf_alloc, L.devbuf_grow, L.devbuf_alloc_fine):
         f.restype, f.argtypes = ctypes.c_int, [vp, ll]
     L.devbuf_upload.restype, L.devbuf_upload.argtypes = ctypes.c_int, [vp, vp, ll]
     L.devbuf_reset.argtypes = [vp]
@@ -152,4 +152,22 @@ def test_four_uploads_in_one_scope_leave_nothing_behind(lib, k):
     lib.devbuf_fail_at(0)
     assert rc == (CFMM_ERR_HIP if k else CFMM_OK)
     assert inside.value == (k - 1 if k else 4)
+    assert lib.devbuf_live() == 0
+
+
+def test_alloc_fine_owns_like_alloc_and_fails_silently(lib):
+    """the fine-grained variant (the arm buffer): what the buffer held goes first, a count of 0 or a failure leaves it empty
+    -- and sets no error text, because the buffer is optional wherever it is used"""
+    b = lib.devbuf_new()
+    assert lib.devbuf_alloc_fine(b, 0) == 0 and state(lib, b) == (None, 0, 0) and lib.devbuf_live() == 0
+    assert lib.devbuf_alloc_fine(b, 9) == 1 and lib.devbuf_live() == 1 and lib.devbuf_size(b) == 9 and lib.devbuf_bool(b) == 1
+    assert lib.devbuf_alloc_fine(b, 17) == 1 and lib.devbuf_live() == 1 and lib.devbuf_size(b) == 17    # the old array went first
+    assert lib.devbuf_alloc(b, 3) == CFMM_OK and lib.devbuf_live() == 1                                  # ... whichever kind it was
+    err = lib.devbuf_last_error()
+    lib.devbuf_fail_at(1)
+    assert lib.devbuf_alloc_fine(b, 5) == 0 and state(lib, b) == (None, 0, 0) and lib.devbuf_live() == 0
+    lib.devbuf_fail_at(0)
+    assert lib.devbuf_last_error() == err                                                                 # no error text
+    assert lib.devbuf_alloc_fine(b, 5) == 1 and lib.devbuf_live() == 1
+    lib.devbuf_delete(b)
     assert lib.devbuf_live() == 0

@@ -31,13 +31,13 @@ def test_shipped_library_carries_no_test_hooks():
     """the test hooks "debug_stall_ms" and "debug_live_allocs" exist only in libcfmm_amd_hooks.so
     (-DCFMM_TEST_HOOKS), and the header documents no debug keys."""
     blob = open(LIB_PATH, "rb").read()
-    assert b"debug_stall_ms" not in blob and b"debug_dev_trust" not in blob and b"debug_live_allocs" not in blob
+    assert b"debug_stall_ms" not in blob and b"debug_dev_trust" not in blob and b"debug_live_" not in blob
     hdr = open(os.path.join(ROOT, "include", "cfmm_amd.h")).read()
     assert not re.findall(r'"debug_[a-z_]+"', hdr.split("EXPERIMENTAL")[0])
     hooks = os.path.join(os.path.dirname(LIB_PATH), "libcfmm_amd_hooks.so")
     if os.path.exists(hooks):
         hooked = open(hooks, "rb").read()
-        assert b"debug_stall_ms" in hooked and b"debug_live_allocs" in hooked
+        assert b"debug_stall_ms" in hooked and all(b"debug_live_" + k in hooked for k in (b"allocs", b"pinned", b"events", b"streams"))
 
 
 def test_unresolvable_rccl_is_an_error_code_not_a_crash():
