@@ -255,22 +255,20 @@ class Context:
         return v.value
 
     # -- pools ---------------------------------------------------------------------------------
-    def add_product(self, R, gamma, Ai0):
+    def _add_pairs(self, entry, R, gamma, Ai0):
         R, gamma = f64(R), f64(gamma)
         Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
         m = gamma.size
         if R.size != 2 * m or Ai0.size != 2 * m:
             raise ArgumentError("R and Ai must have shape [m, 2]")
-        self._check(self._L.cfmm_pools_add_product(self._h, m, ptr(R), ptr(gamma), ptr(Ai0)))
+        self._check(entry(self._h, m, ptr(R), ptr(gamma), ptr(Ai0)))
+
+    def add_product(self, R, gamma, Ai0):
+        self._add_pairs(self._L.cfmm_pools_add_product, R, gamma, Ai0)
 
     def add_solidly(self, R, gamma, Ai0):
         """m Solidly-style stable pairs (φ = x³y + xy³): the arrays of add_product (cfmm_pools_add_solidly)."""
-        R, gamma = f64(R), f64(gamma)
-        Ai0 = np.ascontiguousarray(Ai0, dtype=np.int32)
-        m = gamma.size
-        if R.size != 2 * m or Ai0.size != 2 * m:
-            raise ArgumentError("R and Ai must have shape [m, 2]")
-        self._check(self._L.cfmm_pools_add_solidly(self._h, m, ptr(R), ptr(gamma), ptr(Ai0)))
+        self._add_pairs(self._L.cfmm_pools_add_solidly, R, gamma, Ai0)
 
     def add_geomean(self, R, w, gamma, Ai0):
         R, w, gamma = f64(R), f64(w), f64(gamma)
@@ -312,16 +310,19 @@ class Context:
         return int(self._L.cfmm_pools_count(self._h))
 
     # -- hot path ------------------------------------------------------------------------------
-    def find_arb(self, v):
+    def _check_v(self, v):
+        """A price vector as the contiguous float64 array the entries take; it must have n_tokens entries."""
         v = f64(v)
         if v.size != self.n_tokens:
             raise ArgumentError("v must have n_tokens entries")
+        return v
+
+    def find_arb(self, v):
+        v = self._check_v(v)
         self._check(self._L.cfmm_find_arb(self._h, ptr(v)))
 
     def eval(self, v):
-        v = f64(v)
-        if v.size != self.n_tokens:
-            raise ArgumentError("v must have n_tokens entries")
+        v = self._check_v(v)
         psi = np.empty(self.n_tokens)
         acc = C.c_double()
         self._check(self._L.cfmm_eval(self._h, ptr(v), ptr(psi), C.byref(acc)))
@@ -368,10 +369,7 @@ class Context:
         capacity returns the first min(count, capacity) rows (the count itself: select_count)."""
         if capacity is not None and int(capacity) < 0:
             raise ArgumentError("capacity must be >= 0")
-        if v is not None:
-            v = f64(v)
-            if v.size != self.n_tokens:
-                raise ArgumentError("v must have n_tokens entries")
+        v = None if v is None else self._check_v(v)
         n_coins = int(n_coins)
         cap = min(int(self.segments()[int(seg)]["m"]), 65536) if capacity is None else int(capacity)
         while True:
@@ -387,9 +385,7 @@ class Context:
 
     def select_count(self, seg, min_value=0.0, v=None) -> int:
         """How many rows select_trades would return (cfmm_select_trades with capacity 0: nothing is copied)."""
-        v = None if v is None else f64(v)
-        if v is not None and v.size != self.n_tokens:
-            raise ArgumentError("v must have n_tokens entries")
+        v = None if v is None else self._check_v(v)
         count = C.c_int64()
         self._check(self._L.cfmm_select_trades(self._h, int(seg), ptr(v), float(min_value), 0, C.byref(count), None, None, None, None))
         return count.value

@@ -24,6 +24,8 @@ accepts directly; `batch[i]` materialises the i-th pool object on demand.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED, ArgumentError
@@ -40,6 +42,12 @@ class CFMM:
         return len(self.Ai)
 
 
+class _FeePool(CFMM):
+    """The built-in pool types (a user's own CFMM subclass names its fields as it likes): `gamma` reads the fee γ."""
+
+    gamma = property(lambda self: self.γ)
+
+
 def _two_coin_check_cast(R, γ, idx):
     """two_coin_check_cast -- src/cfmms.jl:76-90"""
     R = np.asarray(R)
@@ -53,15 +61,13 @@ def _two_coin_check_cast(R, γ, idx):
     return np.array(R, dtype=np.float64).reshape(2), float(γ), np.array(idx, dtype=np.int64).reshape(2)
 
 
-class ProductTwoCoin(CFMM):
+class ProductTwoCoin(_FeePool):
     """ProductTwoCoin(R, γ, idx): φ(R) = R₁R₂ -- src/cfmms.jl:92-111"""
 
     kind = KIND_PRODUCT
 
     def __init__(self, R, γ, idx):
         self.R, self.γ, self.Ai = _two_coin_check_cast(R, γ, idx)
-
-    gamma = property(lambda self: self.γ)
 
     @staticmethod
     def batch(R, γ, idx):
@@ -81,7 +87,7 @@ def _solidly_check(R, γ):
         raise ArgumentError(f"reserves of a Solidly stable pair must lie within [2^-{SOLIDLY_EXP_RANGE}, 2^{SOLIDLY_EXP_RANGE}]")
 
 
-class SolidlyStableTwoCoin(CFMM):
+class SolidlyStableTwoCoin(_FeePool):
     """SolidlyStableTwoCoin(R, γ, idx): φ(R) = R₁³R₂ + R₁R₂³, the "stable" pair of the Solidly family (Velodrome,
     Aerodrome and forks) on decimal-normalised balances.  Not in the reference; constructor of ProductTwoCoin
     (src/cfmms.jl:76-111) plus 0 < γ <= 1 and the upload's reserve range."""
@@ -92,14 +98,12 @@ class SolidlyStableTwoCoin(CFMM):
         self.R, self.γ, self.Ai = _two_coin_check_cast(R, γ, idx)
         _solidly_check(self.R, self.γ)
 
-    gamma = property(lambda self: self.γ)
-
     @staticmethod
     def batch(R, γ, idx):
         return PoolBatch(KIND_SOLIDLY, R=R, γ=γ, Ai=idx)
 
 
-class GeometricMeanTwoCoin(CFMM):
+class GeometricMeanTwoCoin(_FeePool):
     """GeometricMeanTwoCoin(R, w, γ, idx): φ(R) = R₁^w₁ R₂^w₂ -- src/cfmms.jl:142-165"""
 
     kind = KIND_GEOMEAN
@@ -110,8 +114,6 @@ class GeometricMeanTwoCoin(CFMM):
         if w.size != 2:
             raise ArgumentError("length of w must be 2")  # SVector{2,T}(w) would throw
         self.w = w.reshape(2)
-
-    gamma = property(lambda self: self.γ)
 
     @staticmethod
     def batch(R, w, γ, idx):
@@ -146,7 +148,7 @@ def _n_coin_check_cast(R, γ, Ai, w=None, family="weighted"):
     return R, γ, Ai.astype(np.int64), w
 
 
-class GeometricMean(CFMM):
+class GeometricMean(_FeePool):
     """GeometricMean(R, w, γ, Ai): φ(R) = Π R_i^{w_i}, 2..8 coins -- src/cfmms.jl:60-63.  Argument order of
     GeometricMeanTwoCoin; the device normalises w to sum to 1 (same level sets, same trades)."""
 
@@ -154,8 +156,6 @@ class GeometricMean(CFMM):
 
     def __init__(self, R, w, γ, Ai):
         self.R, self.γ, self.Ai, self.w = _n_coin_check_cast(R, γ, Ai, w)
-
-    gamma = property(lambda self: self.γ)
 
     @staticmethod
     def batch(R, w, γ, Ai):
@@ -197,7 +197,7 @@ def _curve_range_check(R, α, β):
         raise ArgumentError(f"log(P₀/R_k) = log β − Σ log R − log R_k must lie within ±{CURVE_LOG_RANGE:g} when α > 0")
 
 
-class Curve(CFMM):
+class Curve(_FeePool):
     """Curve(R, γ, Ai, α, β): φ(R) = α·Σ R_i − β·Π R_i⁻¹, 2..8 coins -- src/cfmms.jl:66-70 (the fields of Curve{T}, in
     the order of its default constructor).  Curve's StableSwap invariant with D held fixed: α = A·nⁿ, β = D^{n+1}/nⁿ
     (chain.stableswap_params).  α = 0 trades exactly like Product."""
@@ -209,7 +209,6 @@ class Curve(CFMM):
         self.α, self.β = _curve_check_cast(α, β)
         _curve_range_check(self.R[None], [self.α], [self.β])
 
-    gamma = property(lambda self: self.γ)
     alpha = property(lambda self: self.α)
     beta = property(lambda self: self.β)
 
@@ -274,7 +273,7 @@ def ϕ_grad_(out, cfmm, R=None):
 phi, grad_phi_ = ϕ, ϕ_grad_   # ASCII spellings ("∇" is not a valid Python identifier character, hence ϕ_grad_ for ∇ϕ!)
 
 
-class UniV3(CFMM):
+class UniV3(_FeePool):
     """UniV3(current_price, lower_ticks, liquidity, γ, Ai) -- src/cfmms.jl:206-245.
 
     `lower_ticks` is in decreasing order; `current_tick` is
@@ -292,10 +291,11 @@ class UniV3(CFMM):
         self.Ai = np.array(Ai, dtype=np.int64).reshape(-1)
         if self.Ai.size != 2:
             raise ArgumentError("length of Ai must be 2")
-        # number of ticks >= current_price in the descending vector (== searchsortedlast, rev=true)
-        self.current_tick = int(np.count_nonzero(self.lower_ticks >= self.current_price))
+        self._retick()
 
-    gamma = property(lambda self: self.γ)
+    def _retick(self):
+        """current_tick: the number of ticks >= current_price in the descending vector (== searchsortedlast, rev=true)"""
+        self.current_tick = int(np.count_nonzero(self.lower_ticks >= self.current_price))
 
     @staticmethod
     def batch(current_price, tick_off, lower_ticks, liquidity, γ, Ai):
@@ -311,21 +311,39 @@ def BoundedProduct(current_price, p_lower, p_upper, liquidity, γ, Ai):
     return UniV3(current_price, [p_upper, p_lower], [liquidity, 0.0], γ, Ai)
 
 
-# The per-pool fields of a batch of each kind, in the argument order of the kind's pool type (PoolBatch[i] builds one from
-# them).  "R", "w" and "Ai" are [m, n_coins], every other field [m]; a UniV3 batch also holds its pools' ticks as a CSR
-# (tick_off [m + 1], lower_ticks, liquidity).
-_FIELDS = {
-    KIND_PRODUCT: ("R", "γ", "Ai"),
-    KIND_SOLIDLY: ("R", "γ", "Ai"),
-    KIND_GEOMEAN: ("R", "w", "γ", "Ai"),
-    KIND_WEIGHTED: ("R", "w", "γ", "Ai"),
-    KIND_CURVE: ("R", "γ", "Ai", "α", "β"),
-    KIND_UNIV3: ("current_price", "γ", "Ai"),
+# What the host mirror knows about one pool family, a row of KINDS:
+#   pool    the pool type PoolBatch[i] builds;  ctor: a pool's fields in the argument order of that type
+#   family  None: two coins; else N coins (2..MAX_COINS, one batch per coin count), the family's name in error texts
+#   add     the Context method that uploads a batch; its arrays are the batch's fields in ctor order, then the tick CSR
+#   door    the sparse update a segment accepts: "reserves" (R), "curve" ((R, α, β)) or "prices" (a price or a new ladder)
+#   state   the fields that door moves;  check: further value checks of a whole batch (raises ArgumentError)
+Kind = namedtuple("Kind", "pool ctor family add door state check", defaults=(None,))
+_LADDER = ("lower_ticks", "liquidity")     # per-pool vectors of any length: a batch holds them as a CSR behind tick_off [m + 1]
+_COIN_FIELDS = ("R", "w", "Ai")            # [m, n_coins] in a batch; every other field [m]
+# One row per kind with a device kernel, in the order a Router packs a pool list: the two-coin kinds (Solidly last: it never
+# joins a fused launch), then the N-coin kinds.  THE place to edit when a family is added (with PoolLayout, if it changes
+# where pools live).
+KINDS = {
+    KIND_PRODUCT: Kind(ProductTwoCoin, ("R", "γ", "Ai"), None, "add_product", "reserves", ("R",)),
+    KIND_GEOMEAN: Kind(GeometricMeanTwoCoin, ("R", "w", "γ", "Ai"), None, "add_geomean", "reserves", ("R",)),
+    KIND_UNIV3: Kind(UniV3, ("current_price",) + _LADDER + ("γ", "Ai"), None, "add_univ3", "prices", ("current_price",)),
+    KIND_SOLIDLY: Kind(SolidlyStableTwoCoin, ("R", "γ", "Ai"), None, "add_solidly", "reserves", ("R",),
+                       lambda b: _solidly_check(b.R, b.γ)),
+    KIND_WEIGHTED: Kind(GeometricMean, ("R", "w", "γ", "Ai"), "weighted", "add_weighted", "reserves", ("R",)),
+    KIND_CURVE: Kind(Curve, ("R", "γ", "Ai", "α", "β"), "Curve", "add_curve", "curve", ("R", "α", "β"),
+                     lambda b: _curve_range_check(b.R, b.α, b.β) if len(b) else None),
 }
-_COIN_FIELDS = ("R", "w", "Ai")
-_POOL_TYPE = {KIND_PRODUCT: ProductTwoCoin, KIND_GEOMEAN: GeometricMeanTwoCoin, KIND_WEIGHTED: GeometricMean, KIND_CURVE: Curve,
-              KIND_SOLIDLY: SolidlyStableTwoCoin}
-_NCOIN_NAME = {KIND_WEIGHTED: "weighted", KIND_CURVE: "Curve"}
+
+
+def _fields(kind):
+    """the per-pool array fields of a batch, in the argument order of the kind's pool type"""
+    return tuple(f for f in KINDS[kind].ctor if f not in _LADDER)
+
+
+def _has_ladder(kind):
+    return _LADDER[0] in KINDS[kind].ctor
+
+
 # value checks of N-coin batches, in order: field, zero allowed, message
 _NCOIN_CHECKS = (("R", False, "reserves must be finite and > 0"), ("w", False, "weights must be finite and > 0"),
                  ("α", True, "α must be finite and >= 0"), ("β", False, "β must be finite and > 0"))
@@ -345,15 +363,15 @@ class PoolBatch:
         self.kind = kind
         self.γ = np.ascontiguousarray(a["γ"], dtype=np.float64).reshape(-1)
         m = self.γ.size
-        if kind in _NCOIN_NAME:
+        if KINDS[kind].family is not None:
             self._init_ncoin(m, a)
-            return
-        for f in _FIELDS[kind]:
-            if f != "γ":
-                self._set(f, a, m, 2)
-        if kind == KIND_SOLIDLY:
-            _solidly_check(self.R, self.γ)
-        if kind == KIND_UNIV3:
+        else:
+            for f in _fields(kind):
+                if f != "γ":
+                    self._set(f, a, m, 2)
+        if KINDS[kind].check is not None:
+            KINDS[kind].check(self)
+        if _has_ladder(kind):
             self.tick_off = np.ascontiguousarray(a["tick_off"], dtype=np.int64).reshape(m + 1)
             self.lower_ticks = np.ascontiguousarray(a["lower_ticks"], dtype=np.float64).reshape(-1)
             self.liquidity = np.ascontiguousarray(a["liquidity"], dtype=np.float64).reshape(-1)
@@ -365,8 +383,8 @@ class PoolBatch:
 
     def _init_ncoin(self, m, a):
         """KIND_WEIGHTED (R, w, Ai [m, n]) and KIND_CURVE (R, Ai [m, n]; α, β [m])"""
-        fam = _NCOIN_NAME[self.kind]
-        fields = [f for f in _FIELDS[self.kind] if f != "γ"]
+        fam = KINDS[self.kind].family
+        fields = [f for f in _fields(self.kind) if f != "γ"]
         R = np.asarray(a["R"], dtype=np.float64)
         n = R.shape[-1] if R.ndim == 2 else (R.size // m if m else 2)
         if not 2 <= n <= MAX_COINS:
@@ -386,8 +404,6 @@ class PoolBatch:
             raise ArgumentError("fee γ must lie in (0, 1] (γ > 1 makes the N-coin arbitrage problem unbounded)")
         if m and np.any(np.sort(self.Ai, axis=1)[:, 1:] == np.sort(self.Ai, axis=1)[:, :-1]):
             raise ArgumentError("the token indices of a pool must be distinct")
-        if self.kind == KIND_CURVE and m:
-            _curve_range_check(self.R, self.α, self.β)
 
     n_coins = property(lambda self: self.Ai.shape[1])
 
@@ -400,15 +416,14 @@ class PoolBatch:
         i = int(i)
         if i < 0:
             i += len(self)
-        if self.kind == KIND_UNIV3:
-            o, e = self.tick_off[i], self.tick_off[i + 1]
-            return UniV3(self.current_price[i], self.lower_ticks[o:e], self.liquidity[o:e], self.γ[i], self.Ai[i])
-        return _POOL_TYPE[self.kind](*(getattr(self, f)[i] for f in _FIELDS[self.kind]))
+        K = KINDS[self.kind]
+        o, e = (self.tick_off[i], self.tick_off[i + 1]) if _has_ladder(self.kind) else (i, i)
+        return K.pool(*(getattr(self, f)[o:e] if f in _LADDER else getattr(self, f)[i] for f in K.ctor))
 
     def slice(self, lo, hi):
         """Pools [lo, hi) as a new batch (used to shard a market across GPUs)."""
-        part = {f: getattr(self, f)[lo:hi] for f in _FIELDS[self.kind]}
-        if self.kind == KIND_UNIV3:
+        part = {f: getattr(self, f)[lo:hi] for f in _fields(self.kind)}
+        if _has_ladder(self.kind):
             o, e = self.tick_off[lo], self.tick_off[hi]
             part.update(tick_off=self.tick_off[lo:hi + 1] - o, lower_ticks=self.lower_ticks[o:e], liquidity=self.liquidity[o:e])
         return PoolBatch(self.kind, **part)
@@ -420,11 +435,11 @@ class PoolBatch:
         kind = batches[0].kind
         if any(b.kind != kind for b in batches):
             raise ArgumentError("concat needs batches of one pool family")
-        if kind in _NCOIN_NAME and len({b.n_coins for b in batches}) > 1:
+        if KINDS[kind].family is not None and len({b.n_coins for b in batches}) > 1:
             raise ArgumentError("concat needs weighted / Curve batches of one coin count")
         cat = lambda name: np.concatenate([getattr(b, name) for b in batches])
-        whole = {f: cat(f) for f in _FIELDS[kind]}
-        if kind == KIND_UNIV3:
+        whole = {f: cat(f) for f in _fields(kind)}
+        if _has_ladder(kind):
             off, base = [np.zeros(1, dtype=np.int64)], 0
             for b in batches:
                 off.append(b.tick_off[1:] + base)
@@ -434,10 +449,10 @@ class PoolBatch:
 
     @staticmethod
     def from_pools(kind, pools):
-        if kind in _NCOIN_NAME and len({len(p.Ai) for p in pools}) > 1:
-            raise ArgumentError(f"one {_NCOIN_NAME[kind]} batch holds pools of one coin count (group them by len(Ai))")
-        fields = {f: [getattr(p, f) for p in pools] for f in _FIELDS[kind]}
-        if kind == KIND_UNIV3:
+        if KINDS[kind].family is not None and len({len(p.Ai) for p in pools}) > 1:
+            raise ArgumentError(f"one {KINDS[kind].family} batch holds pools of one coin count (group them by len(Ai))")
+        fields = {f: [getattr(p, f) for p in pools] for f in _fields(kind)}
+        if _has_ladder(kind):
             off = np.zeros(len(pools) + 1, dtype=np.int64)
             np.cumsum([p.lower_ticks.size for p in pools], out=off[1:])
             fields.update(tick_off=off, lower_ticks=np.concatenate([p.lower_ticks for p in pools]) if pools else [],
@@ -449,25 +464,25 @@ def _set_pool_state(ctx, seg, batch: PoolBatch, rows, states):
     """New state of pools `rows` of `batch` (device segment `seg`; ctx None: host mirror only): a reserve vector per pool,
     (R, α, β) for Curve, a price for UniV3 -- or (price, lower_ticks, liquidity), a mint / burn.  The device call
     (cfmm_pools_set_*) checks every row before anything changes; the batch's arrays follow only when it accepted."""
-    rows = np.asarray(rows, dtype=np.int64)
+    rows, door, n = np.asarray(rows, dtype=np.int64), KINDS[batch.kind].door, batch.n_coins
+    reserves = lambda Rs: np.array([np.asarray(R, dtype=np.float64).reshape(n) for R in Rs]).reshape(len(rows), n)
     try:
-        if batch.kind == KIND_UNIV3 and any(_is_ladder_state(s) for s in states):
+        if door == "prices" and any(_is_ladder_state(s) for s in states):
             _set_univ3_ladders(ctx, seg, batch, rows, states)
-        elif batch.kind == KIND_UNIV3:
+        elif door == "prices":
             p = np.array([float(s) for s in states], dtype=np.float64)
             if ctx is not None:
                 ctx.set_prices(seg, rows, p)
             batch.current_price[rows] = p
-        elif batch.kind == KIND_CURVE:
-            R = np.array([np.asarray(s[0], dtype=np.float64).reshape(batch.n_coins) for s in states]).reshape(len(rows), batch.n_coins)
+        elif door == "curve":
+            R = reserves(s[0] for s in states)
             α = np.array([float(s[1]) for s in states], dtype=np.float64)
             β = np.array([float(s[2]) for s in states], dtype=np.float64)
             if ctx is not None:
                 ctx.set_curve(seg, rows, R, α, β)
             batch.R[rows], batch.α[rows], batch.β[rows] = R, α, β
         else:
-            n = batch.R.shape[1]
-            R = np.array([np.asarray(s, dtype=np.float64).reshape(n) for s in states]).reshape(len(rows), n)
+            R = reserves(states)
             if ctx is not None:
                 ctx.set_reserves(seg, rows, R)
             batch.R[rows] = R
@@ -548,17 +563,9 @@ def find_arb_(Δ, Λ, cfmm, v, device=0):
 
 
 def _with_local_idx(c):
-    if c.kind == KIND_PRODUCT:
-        return ProductTwoCoin(c.R, c.γ, [1, 2])
-    if c.kind == KIND_SOLIDLY:
-        return SolidlyStableTwoCoin(c.R, c.γ, [1, 2])
-    if c.kind == KIND_GEOMEAN:
-        return GeometricMeanTwoCoin(c.R, c.w, c.γ, [1, 2])
-    if c.kind == KIND_WEIGHTED:
-        return GeometricMean(c.R, c.w, c.γ, np.arange(1, len(c.Ai) + 1))
-    if c.kind == KIND_CURVE:
-        return Curve(c.R, c.γ, np.arange(1, len(c.Ai) + 1), c.α, c.β)
-    return UniV3(c.current_price, c.lower_ticks, c.liquidity, c.γ, [1, 2])
+    """the pool with token indices 1..n (a one-pool market)"""
+    K = KINDS[c.kind]
+    return K.pool(*(np.arange(1, len(c.Ai) + 1) if f == "Ai" else getattr(c, f) for f in K.ctor))
 
 
 def _upload(ctx, batch: PoolBatch):
@@ -566,17 +573,32 @@ def _upload(ctx, batch: PoolBatch):
     Ai0 = (batch.Ai - 1).astype(np.int32)
     if np.any(batch.Ai < 1) or np.any(batch.Ai > ctx.n_tokens):
         raise ArgumentError(f"token index out of range 1:{ctx.n_tokens}")
-    if batch.kind == KIND_PRODUCT:
-        ctx.add_product(batch.R, batch.γ, Ai0)
-    elif batch.kind == KIND_SOLIDLY:
-        ctx.add_solidly(batch.R, batch.γ, Ai0)
-    elif batch.kind == KIND_GEOMEAN:
-        ctx.add_geomean(batch.R, batch.w, batch.γ, Ai0)
-    elif batch.kind == KIND_WEIGHTED:
-        ctx.add_weighted(batch.R, batch.w, batch.γ, Ai0)
-    elif batch.kind == KIND_CURVE:
-        ctx.add_curve(batch.R, batch.γ, Ai0, batch.α, batch.β)
-    elif batch.kind == KIND_UNIV3:
-        ctx.add_univ3(batch.current_price, batch.γ, Ai0, batch.tick_off, batch.lower_ticks, batch.liquidity)
-    else:
+    if batch.kind not in KINDS:
         raise ArgumentError("unknown pool family")
+    arrays = _fields(batch.kind) + (("tick_off",) + _LADDER if _has_ladder(batch.kind) else ())
+    getattr(ctx, KINDS[batch.kind].add)(*(Ai0 if f == "Ai" else getattr(batch, f) for f in arrays))
+
+
+def _download_state(ctx, seg, batch: PoolBatch):
+    """The state update_reserves! moved, device segment `seg` -> batch: current prices (UniV3) or reserves."""
+    if KINDS[batch.kind].door == "prices":
+        batch.current_price[:] = ctx.prices(seg, len(batch))
+    else:
+        batch.R[:] = ctx.reserves(seg, len(batch), batch.R.shape[1])
+
+
+def _sync_pool(pool, batch: PoolBatch, row, full):
+    """pool <- row `row` of its batch.  full: everything update_pools_ can move (R; α, β; current_price and the ladder);
+    else what update_reserves! moves (R or current_price).  current_tick follows."""
+    state = KINDS[batch.kind].state
+    for f in state if full else state[:1]:
+        x = getattr(batch, f)[row]
+        if np.ndim(x):
+            getattr(pool, f)[:] = x
+        else:
+            setattr(pool, f, float(x))
+    if _has_ladder(batch.kind):
+        if full:
+            o, e = batch.tick_off[row], batch.tick_off[row + 1]
+            pool.lower_ticks, pool.liquidity = batch.lower_ticks[o:e].copy(), batch.liquidity[o:e].copy()
+        pool._retick()

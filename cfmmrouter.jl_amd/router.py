@@ -22,8 +22,9 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import KIND_CURVE, KIND_GEOMEAN, KIND_PRODUCT, KIND_SOLIDLY, KIND_UNIV3, KIND_WEIGHTED, ArgumentError, CFMMDeviceError, Context
-from .cfmms import CFMM, PoolBatch, _set_pool_state, _upload
+from ._lib import OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from .layout import PoolLayout
+from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
 
 _BOXED_INF = 1e100   # stands in for the reference's u = Inf under nbd = 2 (see route_)
@@ -35,10 +36,12 @@ class DeviceBackend:
     def __init__(self, n_tokens, batches, device=0):
         self.ctx = Context(n_tokens, device)
         self.n_tokens = int(n_tokens)
-        self._seg_shape = [(len(b), int(b.Ai.shape[1])) for b in batches if len(b)]   # (pools, coins) per device segment
-        for b in batches:
-            if len(b):
-                _upload(self.ctx, b)
+        self._load(batches)
+
+    def _load(self, batches):
+        self.layout = PoolLayout(batches)      # of THIS pool store, packed order only (a Router's own layout also knows its order)
+        for _, _, b in self.layout.segments():
+            _upload(self.ctx, b)
 
     def eval(self, v):
         """fn/g! evaluation without trade write-back -> (Ψ, acc)."""
@@ -56,20 +59,16 @@ class DeviceBackend:
         """The pools that trade in the latest find_arb! and are worth at least min_value, selected on the device segment by
         segment (cfmm_select_trades) -> a list of blocks (idx, Δ, Λ, value): idx = positions in packed (segment) order,
         ascending; Δ, Λ = [count, coins] rows."""
-        blocks, first = [], 0
-        for seg, (m, coins) in enumerate(self._seg_shape):
-            idx, D, Lm, val = self.ctx.select_trades(seg, min_value, n_coins=coins)
+        blocks = []
+        for seg, first, _ in self.layout.segments():
+            idx, D, Lm, val = self.ctx.select_trades(seg, min_value, n_coins=self.layout.coins[seg])
             blocks.append((idx + first, D, Lm, val))
-            first += m
         return blocks
 
     def reload(self, batches):
         """Replace the device pool store (used after update_reserves_)."""
         self.ctx.clear()
-        self._seg_shape = [(len(b), int(b.Ai.shape[1])) for b in batches if len(b)]
-        for b in batches:
-            if len(b):
-                _upload(self.ctx, b)
+        self._load(batches)
 
     def close(self):
         peer = getattr(self, "peer", None)
@@ -96,19 +95,13 @@ def _segments_of(cfmms):
         if not isinstance(c, CFMM):
             raise ArgumentError("cfmms must hold CFMM objects or PoolBatch containers")
     batches, order = [], []
-    for kind in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_SOLIDLY):   # (Solidly last: it never joins a fused launch)
-        idx = [i for i, c in enumerate(cfmms) if c.kind == kind]
-        if idx:
-            batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
-            order.extend(idx)
-    for kind in (KIND_WEIGHTED, KIND_CURVE):
-        for n in range(2, 9):   # weighted / Curve pools: one batch (one device segment) per coin count
-            idx = [i for i, c in enumerate(cfmms) if c.kind == kind and len(c.Ai) == n]
+    for kind, K in KINDS.items():   # the table's order; N-coin kinds: one batch (one device segment) per coin count
+        for n in (None,) if K.family is None else range(2, MAX_COINS + 1):
+            idx = [i for i, c in enumerate(cfmms) if c.kind == kind and (n is None or len(c.Ai) == n)]
             if idx:
                 batches.append(PoolBatch.from_pools(kind, [cfmms[i] for i in idx]))
                 order.extend(idx)
-    host = [i for i, c in enumerate(cfmms) if c.kind not in (KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE,
-                                                             KIND_SOLIDLY)]
+    host = [i for i, c in enumerate(cfmms) if c.kind not in KINDS]
     for i in host:
         if not callable(getattr(cfmms[i], "find_arb_", None)) or not hasattr(cfmms[i], "Ai"):
             raise ArgumentError(f"cfmms[{i}] ({type(cfmms[i]).__name__}): a pool type without a device kernel needs its own "
@@ -255,87 +248,61 @@ class Router:
         self.n_tokens = int(n_tokens)
         if not isinstance(cfmms, PoolBatch):
             cfmms = list(cfmms)
-        batches, self._order, host = _segments_of(cfmms)
+        batches, order, host = _segments_of(cfmms)
+        self._layout = PoolLayout(batches, order, host)
         self._batches = batches
-        from_batches = isinstance(cfmms, PoolBatch) or (
-            len(batches) > 0 and not isinstance(cfmms, PoolBatch) and all(isinstance(c, PoolBatch) for c in cfmms))
+        from_batches = isinstance(cfmms, PoolBatch) or (len(batches) > 0 and all(isinstance(c, PoolBatch) for c in cfmms))
         self.cfmms = _PoolView(batches) if from_batches else list(cfmms)
-        self._m = sum(len(b) for b in batches)       # pools with a device kernel
         self.v = np.zeros(self.n_tokens)  # :33
         self._backend = _backend if _backend is not None else DeviceBackend(self.n_tokens, batches, device)
         # the plugin seam: pools of any other CFMM subclass are evaluated by their own find_arb_ on the host
         self._host = HostSegment([cfmms[i] for i in host], self.n_tokens) if host else None
-        self._host_idx = list(host)
         if self._host is not None:
             self._backend = MixedBackend(self._backend, self._host)
-            self._backend.inner_pools = self._m
-        self._psi = np.zeros(self.n_tokens)
-        self._acc = 0.0
-        # weighted / Curve pools: r.Δs / r.Λs are per-pool vectors (the reference's ragged Vector{Vector}, src/router.jl:7-8)
-        self._ragged = any(b.kind in (KIND_WEIGHTED, KIND_CURVE) for b in batches)
-        self._zero_trades()
-        self._trades_stale = False
+            self._backend.inner_pools = self._layout.m
+        self._reset_trades()
         self.n_sweeps = 0
         self.info = None
 
-    # r.Δs / r.Λs: [m, 2] arrays in router order (rows are the reference's per-pool vectors); routers with host-evaluated
-    # pools: a list of per-pool vectors in router order (the reference's Vector{Vector}), host pools' vectors included
-    def _zero_trades(self):
-        """zerotrade per pool, src/router.jl:23-26"""
-        if self._ragged:
-            self._Δs = [np.zeros(b.Ai.shape[1]) for b in self._batches for _ in range(len(b))]
-            self._Λs = [np.zeros(b.Ai.shape[1]) for b in self._batches for _ in range(len(b))]
-        else:
-            self._Δs = np.zeros((self._m, 2))
-            self._Λs = np.zeros((self._m, 2))
-
-    def _split(self, flat):
-        """the ragged flat trade layout of cfmm_get_trades (packed order) -> per-pool vectors"""
-        flat = np.ravel(flat)
-        sizes = np.concatenate([np.full(len(b), b.Ai.shape[1], dtype=np.int64) for b in self._batches if len(b)] or
-                               [np.zeros(0, dtype=np.int64)])
-        return np.split(flat, np.cumsum(sizes)[:-1]) if sizes.size else []
+    def _reset_trades(self):
+        """zerotrade per pool (src/router.jl:23-26), the host-evaluated pools' included; no sweep's Ψ and dual value"""
+        self._trades = [self._layout.zero_trades(), self._layout.zero_trades()]      # Δ, Λ in packed order
+        if self._host is not None:
+            for x in self._host.Δs + self._host.Λs:
+                x[:] = 0.0
+        self._psi, self._acc, self._trades_stale = np.zeros(self.n_tokens), 0.0, False
 
     def _fetch(self):
-        if self._trades_stale:
-            if self._ragged:                  # packed order on the device; _rows() maps router index -> pool vector
-                D, Lm = self._backend.trades()
-                self._Δs, self._Λs = self._split(D), self._split(Lm)
-            elif self._host is not None:        # packed order on the device; _rows() maps router index -> row        # packed order on the device; _rows() maps router index -> row
-                self._Δs, self._Λs = self._backend.trades()
-            elif self._order is not None:
-                D, Lm = self._backend.trades()
-                self._Δs[self._order] = D
-                self._Λs[self._order] = Lm
-            else:           # find_arb! overwrites r.Δs / r.Λs in place (src/router.jl:40): the router's own arrays are filled
-                if isinstance(self._backend, DeviceBackend):
-                    self._backend.trades(out=(self._Δs, self._Λs))
-                else:                   # test-injected backends
-                    self._Δs, self._Λs = self._backend.trades()
-            self._trades_stale = False
+        """The trades of the latest find_arb!, once: per-pool vectors for a ragged router, the backend's packed arrays for
+        one with host pools, permuted into the router's arrays for a reordered one -- and an in-order DeviceBackend fills the
+        router's own arrays: find_arb! overwrites r.Δs / r.Λs in place (src/router.jl:40)."""
+        if not self._trades_stale:
+            return
+        L, own = self._layout, self._trades
+        if not L.per_pool and L.order is None and isinstance(self._backend, DeviceBackend):
+            self._backend.trades(out=tuple(own))
+        else:
+            got = self._backend.trades()
+            for k in (0, 1):
+                if L.ragged:
+                    own[k] = L.split(got[k])
+                elif L.per_pool or L.order is None:      # (host pools; test-injected backends)
+                    own[k] = got[k]
+                else:
+                    own[k][L.order] = got[k]
+        self._trades_stale = False
 
-    def _rows(self, dev, host=()):
-        out = [None] * (self._m + len(self._host_idx))
-        for k, i in enumerate(self._order if self._order is not None else range(self._m)):
-            out[int(i)] = dev[k]
-        for j, i in enumerate(self._host_idx):
-            out[i] = host[j]
-        return out
-
-    @property
-    def Δs(self):
+    def _router_trades(self, k):
+        """r.Δs (k = 0) / r.Λs (k = 1): [m, 2] arrays in router order (rows are the reference's per-pool vectors); ragged
+        routers and routers with host-evaluated pools: a list of per-pool vectors in router order (the reference's
+        Vector{Vector}), host pools' vectors included"""
         self._fetch()
-        if self._ragged:
-            return self._rows(self._Δs, self._host.Δs if self._host is not None else ())
-        return self._Δs if self._host is None else self._rows(self._Δs, self._host.Δs)
+        if not self._layout.per_pool:
+            return self._trades[k]
+        return self._layout.to_router(self._trades[k], () if self._host is None else (self._host.Δs, self._host.Λs)[k])
 
-    @property
-    def Λs(self):
-        self._fetch()
-        if self._ragged:
-            return self._rows(self._Λs, self._host.Λs if self._host is not None else ())
-        return self._Λs if self._host is None else self._rows(self._Λs, self._host.Λs)
-
+    Δs = property(lambda self: self._router_trades(0))
+    Λs = property(lambda self: self._router_trades(1))
     Deltas = Δs
     Lambdas = Λs
 
@@ -383,6 +350,23 @@ def route_(r: Router, v=None, verbose=False, m=5, factr=1e1, pgtol=1e-5, maxfun=
     # with a finite upper bound no iterate can reach (solver="native" emulates the same thing directly).
     bounds = [(lo[j], _BOXED_INF if math.isinf(up[j]) else up[j]) for j in range(n)]
 
+    sweep, fg = _dual_fg(r)
+    sweep(r.v)  # :104
+    kw = dict(bounds=bounds, m=m, factr=factr, pgtol=pgtol, maxfun=maxfun, maxiter=maxiter)
+    if verbose:
+        kw["iprint"] = 1
+    x, fmin, info = fmin_l_bfgs_b(fg, r.v.copy(), **kw)  # :105
+    r.v[:] = x  # :106
+    r.info = {"f": fmin, **{k: info[k] for k in ("warnflag", "task", "funcalls", "nit") if k in info}}
+    find_arb_(r, r.v)  # :107
+    return None
+
+
+def _dual_fg(r: Router):
+    """The dual function both solvers minimise -> (sweep, fg): sweep(x) evaluates the pools at x; fg(x) -> (g(x), ∇g(x))
+    = (f(x) + Σᵢ arbᵢ, ∇f(x) + Ψ), with one sweep unless x is where the latest one was."""
+    n = r.v.size
+
     def sweep(x):
         r._psi, r._acc = r._backend.eval(x)
         r.n_sweeps += 1
@@ -397,85 +381,74 @@ def route_(r: Router, v=None, verbose=False, m=5, factr=1e1, pgtol=1e-5, maxfun=
         G += r._psi  # :98-100
         return fval, G
 
-    sweep(r.v)  # :104
-    kw = dict(bounds=bounds, m=m, factr=factr, pgtol=pgtol, maxfun=maxfun, maxiter=maxiter)
-    if verbose:
-        kw["iprint"] = 1
-    x, fmin, info = fmin_l_bfgs_b(fg, r.v.copy(), **kw)  # :105
-    r.v[:] = x  # :106
-    r.info = {"f": fmin, **{k: info[k] for k in ("warnflag", "task", "funcalls", "nit") if k in info}}
-    find_arb_(r, r.v)  # :107
-    return None
+    return sweep, fg
+
+
+def _objective_args(obj):
+    """objective -> (kind, vector, index) as cfmm_route / cfmm_polish take it"""
+    if isinstance(obj, _obj.LinearNonnegative):
+        return OBJ_LINEAR_NONNEGATIVE, obj.c, 0
+    if isinstance(obj, _obj.BasketLiquidation):
+        return OBJ_BASKET_LIQUIDATION, obj.Δin, obj.i - 1
+    raise ArgumentError("solver='native' knows LinearNonnegative and BasketLiquidation objectives")
+
+
+def _native_info(info, **timing):
+    return {"f": info["f"], "funcalls": info["evaluations"], "nit": info["iterations"],
+            "warnflag": 0 if info["status"] in (0, 1) else 2, "task": info["status"], "solver": "native", **timing}
+
+
+def _call_in_lockstep(guard, ctx, call):
+    """A sharded router's (cfmm_set_peers) ranks run `call` in lockstep.  If ANY rank's call fails -- a lost pre-armed
+    hand-over, a peer that did not publish within the time limit -- every rank learns it through one vote, the exchange is
+    re-aligned, pre-arming goes off and the call is repeated launch-when-ready on all ranks -> (result, retried)."""
+    def attempt():
+        try:
+            return call(), None
+        except RuntimeError as e:      # CFMM_ERR_STATE (RuntimeError) or a HIP failure (CFMMDeviceError, its subclass)
+            return None, e
+
+    res, err = attempt()
+    if guard.vote(res is not None):
+        return res, False
+    guard.resync()
+    ctx.set_option("armed", 0)
+    res, err = attempt()
+    if not guard.vote(res is not None):
+        raise err if err is not None else CFMMDeviceError("sharded route! failed on another rank")
+    return res, True
 
 
 def _route_native(r: Router, v, m, factr, pgtol, maxfun, maxiter):
-    from ._lib import OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, lbfgsb_minimize
+    from ._lib import lbfgsb_minimize
 
-    n = r.v.size
-    obj = r.objective
     if isinstance(r._backend, DeviceBackend):   # everything in one library call
-        if isinstance(obj, _obj.LinearNonnegative):
-            kind, vec, idx = OBJ_LINEAR_NONNEGATIVE, obj.c, 0
-        elif isinstance(obj, _obj.BasketLiquidation):
-            kind, vec, idx = OBJ_BASKET_LIQUIDATION, obj.Δin, obj.i - 1
-        else:
-            raise ArgumentError("solver='native' knows LinearNonnegative and BasketLiquidation objectives")
+        kind, vec, idx = _objective_args(r.objective)
         ctx, guard = r._backend.ctx, getattr(r, "_guard", None)
         call = lambda: ctx.route(kind, vec, idx, v0=v, m=m, factr=factr, pgtol=pgtol, maxfun=maxfun, maxiter=maxiter)
         if guard is None:
             vout, psi, info = call()
         else:
-            # sharded (cfmm_set_peers): the ranks run this call in lockstep.  If ANY rank's call fails -- a lost pre-armed
-            # hand-over, a peer that did not publish within the time limit -- every rank learns it through one vote,
-            # the exchange is re-aligned, pre-arming goes off and the route is repeated launch-when-ready on all ranks.
-            res = err = None
-            try:
-                res = call()
-            except RuntimeError as e:      # CFMM_ERR_STATE (RuntimeError) or a HIP failure (CFMMDeviceError, its subclass)
-                err = e
-            if not guard.vote(res is not None):
-                guard.resync()
-                ctx.set_option("armed", 0)
-                res = err = None
-                try:
-                    res = call()
-                except RuntimeError as e:
-                    err = e
-                if not guard.vote(res is not None):
-                    raise err if err is not None else CFMMDeviceError("sharded route! failed on another rank")
+            (vout, psi, info), retried = _call_in_lockstep(guard, ctx, call)
+            if retried:
                 r.collective_retries = getattr(r, "collective_retries", 0) + 1
-            vout, psi, info = res
         r.v[:] = vout
         r._psi, r._acc = psi, r._backend.ctx.dual_value()
         r._trades_stale = True
         r.n_sweeps += info["sweeps"]
-        r.info = {"f": info["f"], "funcalls": info["evaluations"], "nit": info["iterations"],
-                  "warnflag": 0 if info["status"] in (0, 1) else 2, "task": info["status"], "solver": "native",
-                  "sweep_seconds": info["sweep_seconds"], "total_seconds": info["total_seconds"]}
+        r.info = _native_info(info, sweep_seconds=info["sweep_seconds"], total_seconds=info["total_seconds"])
         return None
     # any other backend (sharded, test-injected): same solver, Python callback per evaluation
+    n = r.v.size
     r.v[:] = np.ones(n) / n if v is None else v
     lo, up = _obj.lower_limit(r.objective), _obj.upper_limit(r.objective)
     bounds = [(lo[j], None if math.isinf(up[j]) else up[j]) for j in range(n)]
-
-    def sweep(x):
-        r._psi, r._acc = r._backend.eval(x)
-        r.n_sweeps += 1
-
-    def fg(x):
-        if not np.all(x == r.v):
-            sweep(x)
-            r.v[:] = x
-        G = np.zeros(n)
-        _obj.grad_(G, r.objective, x)
-        return _obj.f(r.objective, x) + r._acc, G + r._psi
-
+    sweep, fg = _dual_fg(r)
     sweep(r.v)
     x, info = lbfgsb_minimize(fg, r.v.copy(), bounds, m=m, factr=factr, pgtol=pgtol, maxfun=maxfun, maxiter=maxiter,
                               reference_boxed=True)   # nbd = 2 with u = Inf, as src/router.jl:67-70
     r.v[:] = x
-    r.info = {"f": info["f"], "funcalls": info["evaluations"], "nit": info["iterations"],
-              "warnflag": 0 if info["status"] in (0, 1) else 2, "task": info["status"], "solver": "native"}
+    r.info = _native_info(info)
     find_arb_(r, r.v)
     return None
 
@@ -531,12 +504,7 @@ def polish_(r: Router, iters=8, jacobian=None, rel_step=1e-7, native=None):
     if native:
         if jacobian is not None or not isinstance(r._backend, DeviceBackend):
             raise ArgumentError("native polish computes its own Jacobian on a DeviceBackend")
-        from ._lib import OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE
-        obj = r.objective
-        if isinstance(obj, _obj.LinearNonnegative):
-            kind, vec, idx = OBJ_LINEAR_NONNEGATIVE, obj.c, 0
-        else:
-            kind, vec, idx = OBJ_BASKET_LIQUIDATION, obj.Δin, obj.i - 1
+        kind, vec, idx = _objective_args(r.objective)
         vout, psi, pinfo = r._backend.ctx.polish(kind, vec, idx, r.v, max_iters=iters, rel_step=rel_step)
         r.v[:] = vout
         r._psi, r._acc = psi, r._backend.ctx.dual_value()
@@ -600,13 +568,11 @@ def active_trades(r: Router, min_value=0.0):
     if not hasattr(r._backend, "active_trades"):
         raise NotImplementedError(f"{type(r._backend).__name__} has no active_trades")
     blocks = r._backend.active_trades(min_value)
-    order = r._order
-    place = np.concatenate([np.arange(r._m, dtype=np.int64) if order is None else np.asarray(order, dtype=np.int64),
-                            np.asarray(r._host_idx, dtype=np.int64)])   # backend position -> position in r.cfmms
-    idx = place[np.concatenate([b[0] for b in blocks])] if blocks else np.zeros(0, dtype=np.int64)
+    # backend position -> position in r.cfmms
+    idx = r._layout.place[np.concatenate([b[0] for b in blocks])] if blocks else np.zeros(0, dtype=np.int64)
     value = np.concatenate([b[3] for b in blocks]) if blocks else np.zeros(0)
-    per_pool = r._ragged or r._host is not None
-    if per_pool:                                   # per-pool vectors, split as _split does
+    per_pool = r._layout.per_pool
+    if per_pool:                                   # per-pool vectors, as PoolLayout.split makes them
         Ds = [np.array(row) for b in blocks for row in b[1]]
         Ls = [np.array(row) for b in blocks for row in b[2]]
     else:
@@ -635,17 +601,13 @@ def netflows_(ψ, r: Router, exact=False):
         return None
     Δs, Λs = r.Δs, r.Λs
     ψ[:] = 0.0
-    if r._host is not None or r._ragged:         # per-pool vectors of any length, router order
+    if r._layout.per_pool:                       # per-pool vectors of any length, router order
         for Δ, Λ, c in zip(Δs, Λs, r.cfmms):
             ai = np.asarray(c.Ai, dtype=np.int64).reshape(-1) - 1
             for k in range(ai.size):             # broadcast assignment, element after element
                 ψ[ai[k]] += Λ[k] - Δ[k]
         return None
-    Ai = np.concatenate([b.Ai for b in r._batches]) if r._batches else np.zeros((0, 2), dtype=np.int64)
-    if r._order is not None:                     # packed (family-grouped) order -> router order
-        Ar = np.empty_like(Ai)
-        Ar[r._order] = Ai
-        Ai = Ar
+    Ai = r._layout.Ai_router_order()
     # np.bincount adds its weights to each bin one after another in input order: pool 1 coin 1, pool 1 coin 2, pool 2 coin 1, ...
     # -- the reference's loop, starting from zeros
     ψ[:] = np.bincount((Ai.astype(np.int64) - 1).ravel(), weights=(Λs - Δs).ravel(), minlength=r.n_tokens)[:r.n_tokens]
@@ -677,47 +639,21 @@ def update_reserves_(r: Router, sync_host=True):
         for c in r._host.pools:
             if not callable(getattr(c, "update_reserves_", None)):
                 raise ArgumentError(f"{type(c).__name__} has no update_reserves_(Δ, Λ, v) method (src/router.jl:129)")
-
-    def host_pools():
-        # AFTER the device half (which can still refuse: no trades, a UniV3 segment without host prices) -- a refused
-        # update then leaves every pool, host-evaluated ones included, as it was
-        if r._host is None:
-            return
-        for c, ai, D, L in zip(r._host.pools, r._host.Ai0, r._host.Δs, r._host.Λs):
-            c.update_reserves_(D, L, r.v[ai])
-            D[:] = 0.0
-            L[:] = 0.0
-
     ctx = getattr(r._backend, "ctx", None)
     if ctx is None:   # test-injected / sharded backends: host-side update of the two-coin families
         _update_reserves_host(r)
-        return host_pools()
-    ctx.update_reserves()
-    host_pools()
-    if sync_host:
-        seg = 0
-        for b in r._batches:
-            if len(b) == 0:
-                continue
-            if b.kind == KIND_UNIV3:
-                b.current_price[:] = ctx.prices(seg, len(b))
-            else:
-                b.R[:] = ctx.reserves(seg, len(b), b.R.shape[1])
-            seg += 1
-        if isinstance(r.cfmms, list):                     # keep the per-pool objects in step
-            it = iter(range(r._m)) if r._order is None else iter(r._order)
-            for b in r._batches:
-                for k in range(len(b)):
-                    pool = r.cfmms[next(it)]
-                    if b.kind == KIND_UNIV3:
-                        pool.current_price = float(b.current_price[k])
-                        pool.current_tick = int(np.count_nonzero(pool.lower_ticks >= pool.current_price))
-                    else:
-                        pool.R[:] = b.R[k]
-    r._zero_trades()
-    r._psi = np.zeros(r.n_tokens)
-    r._acc = 0.0
-    r._trades_stale = False
+    else:
+        ctx.update_reserves()
+    if r._host is not None:
+        # AFTER the device half (which can still refuse: no trades, a UniV3 segment without host prices) -- a refused
+        # update then leaves every pool, host-evaluated ones included, as it was
+        for c, ai, D, L in zip(r._host.pools, r._host.Ai0, r._host.Δs, r._host.Λs):
+            c.update_reserves_(D, L, r.v[ai])
+    if ctx is not None and sync_host:
+        for seg, _, b in r._layout.segments():
+            _download_state(ctx, seg, b)
+        r._layout.sync_pools(r.cfmms)
+    r._reset_trades()
     return None
 
 
@@ -732,46 +668,21 @@ def update_pools_(r: Router, changes):
     segment is left as it was, and so are the segments after it).  Host-evaluated plugin pools (their own find_arb_) are
     updated on the host only: `pool.set_state_(state)` if the type defines it, else `pool.R[:] = state`.  The router's trades
     are those of the old market: they are zeroed, as by update_reserves_."""
-    m_all = r._m + len(r._host_idx)
-    pos_of = {int(i): k for k, i in enumerate(r._order)} if r._order is not None else None
-    host_of = {int(i): j for j, i in enumerate(r._host_idx)}
-    offsets = np.cumsum([0] + [len(b) for b in r._batches])
+    L = r._layout
     per_batch, host = {}, []
     for i, state in changes.items():
-        i = int(i)
-        if not 0 <= i < m_all:
-            raise ArgumentError(f"pool {i} out of range 0:{m_all - 1}")
-        if i in host_of:
-            host.append((r._host.pools[host_of[i]], state))
+        where = L.locate(i)
+        if where[0] == "host":
+            host.append((r._host.pools[where[1]], state))
             continue
-        k = pos_of[i] if pos_of is not None else i
-        b = int(np.searchsorted(offsets, k, side="right") - 1)
-        rows, states, where = per_batch.setdefault(b, ([], [], []))
-        rows.append(k - int(offsets[b]))
+        rows, states = per_batch.setdefault(where[1], ([], []))
+        rows.append(where[2])
         states.append(state)
-        where.append(i)
     ctx = getattr(r._backend, "ctx", None)
-    seg_of, seg = {}, 0
-    for b, batch in enumerate(r._batches):   # (an empty batch has no device segment)
-        if len(batch):
-            seg_of[b] = seg
-            seg += 1
     for b in sorted(per_batch):
-        rows, states, where = per_batch[b]
-        batch = r._batches[b]
-        _set_pool_state(ctx, seg_of[b], batch, rows, states)
-        if isinstance(r.cfmms, list):                     # keep the per-pool objects in step
-            for i, row in zip(where, rows):
-                pool = r.cfmms[i]
-                if batch.kind == KIND_UNIV3:
-                    o, e = batch.tick_off[row], batch.tick_off[row + 1]
-                    pool.lower_ticks, pool.liquidity = batch.lower_ticks[o:e].copy(), batch.liquidity[o:e].copy()
-                    pool.current_price = float(batch.current_price[row])
-                    pool.current_tick = int(np.count_nonzero(pool.lower_ticks >= pool.current_price))
-                else:
-                    pool.R[:] = batch.R[row]
-                    if batch.kind == KIND_CURVE:
-                        pool.α, pool.β = float(batch.α[row]), float(batch.β[row])
+        rows, states = per_batch[b]
+        _set_pool_state(ctx, L.seg_of[b], L.batches[b], rows, states)
+        L.sync_pools(r.cfmms, b, rows)
     if ctx is None and per_batch:   # test-injected backends: the only door is a reload
         getattr(r._backend, "inner", r._backend).reload(r._batches)
     for pool, state in host:
@@ -781,40 +692,20 @@ def update_pools_(r: Router, changes):
             pool.R[:] = np.asarray(state, dtype=np.float64)
         else:
             raise ArgumentError(f"{type(pool).__name__} has neither set_state_(state) nor an R field")
-    r._zero_trades()
-    if r._host is not None:
-        for D, L in zip(r._host.Δs, r._host.Λs):
-            D[:] = 0.0
-            L[:] = 0.0
-    r._psi = np.zeros(r.n_tokens)
-    r._acc = 0.0
-    r._trades_stale = False
+    r._reset_trades()
     return None
 
 
 def _update_reserves_host(r: Router):
-    if any(b.kind == KIND_UNIV3 for b in r._batches):
+    if any(_has_ladder(b.kind) for b in r._batches):
         raise NotImplementedError("update_reserves! is not defined for UniV3 pools (nor in the reference)")
-    if r._ragged:
+    if r._layout.ragged:
         raise NotImplementedError("this backend cannot update weighted or Curve pools (the device context does: "
                                   "cfmm_update_reserves)")
     if not hasattr(getattr(r._backend, "inner", r._backend), "reload"):    # (MixedBackend forwards to its inner backend)
         raise NotImplementedError("this backend cannot reload pools")
     D, Lm = r._backend.trades()                       # packed (segment) order
-    off = 0
-    for b in r._batches:
-        m = len(b)
-        b.R[:] = b.R + b.γ[:, None] * D[off:off + m] - Lm[off:off + m]
-        off += m
+    for b, first in zip(r._batches, r._layout.offsets):
+        b.R[:] = b.R + b.γ[:, None] * D[first:first + len(b)] - Lm[first:first + len(b)]
     r._backend.reload(r._batches)
-    if isinstance(r.cfmms, list):                     # keep the per-pool objects in step
-        it = iter(range(r._m)) if r._order is None else iter(r._order)
-        for b in r._batches:
-            for k in range(len(b)):
-                r.cfmms[next(it)].R[:] = b.R[k]
-    r._Δs = np.zeros((r._m, 2))
-    r._Λs = np.zeros((r._m, 2))
-    r._psi = np.zeros(r.n_tokens)
-    r._acc = 0.0
-    r._trades_stale = False
-    return None
+    r._layout.sync_pools(r.cfmms)
