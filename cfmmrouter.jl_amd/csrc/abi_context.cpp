@@ -51,13 +51,18 @@ static hipError_t created(hipError_t e, T* p, int family)
     return e;
 }
 
-hipError_t dev_alloc(void** p, size_t bytes) { return created(hipMalloc(p, bytes), p, kLiveAllocs); }
-hipError_t dev_alloc_fine(void** p, size_t bytes) { return created(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained), p, kLiveAllocs); }
-void dev_free(void* p) { (void)hipFree(p); count(kLiveAllocs, -1); }
+static std::atomic<uint64_t> g_resource_epoch{1};
+uint64_t resource_epoch() { return g_resource_epoch.load(std::memory_order_relaxed); }
+static void moved() { g_resource_epoch.fetch_add(1, std::memory_order_relaxed); }
+
+hipError_t dev_alloc(void** p, size_t bytes) { moved(); return created(hipMalloc(p, bytes), p, kLiveAllocs); }
+hipError_t dev_alloc_fine(void** p, size_t bytes) { moved(); return created(hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained), p, kLiveAllocs); }
+void dev_free(void* p) { moved(); (void)hipFree(p); count(kLiveAllocs, -1); }
 
 hipError_t pinned_alloc(void** h, void** d, size_t bytes, bool mapped)
 {
     *d = nullptr;
+    moved();
     const hipError_t e = created(hipHostMalloc(h, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault), h, kLivePinned);
     if (e == hipSuccess && mapped && hipHostGetDevicePointer(d, *h, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -65,7 +70,7 @@ hipError_t pinned_alloc(void** h, void** d, size_t bytes, bool mapped)
     }
     return e;
 }
-void pinned_free(void* h) { (void)hipHostFree(h); count(kLivePinned, -1); }
+void pinned_free(void* h) { moved(); (void)hipHostFree(h); count(kLivePinned, -1); }
 
 hipError_t event_create(hipEvent_t* e, unsigned flags) { return created(hipEventCreateWithFlags(e, flags), e, kLiveEvents); }
 void event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); count(kLiveEvents, -1); }
@@ -246,6 +251,7 @@ int cfmm_set_stream(cfmm_ctx* c, void* hip_stream)
     if (!c) return CFMM_ERR_INVALID_ARG;
     CFMM_SINGLE_ONLY(c, "cfmm_set_stream");
     c->stream = static_cast<hipStream_t>(hip_stream); // NULL is HIP's default (null) stream
+    c->desc_dirty = true;   // (the descriptors are uploaded in stream order: again on the new stream)
     return CFMM_OK;
 }
 
@@ -254,6 +260,7 @@ int cfmm_reset_stream(cfmm_ctx* c)
     if (!c) return CFMM_ERR_INVALID_ARG;
     CFMM_SINGLE_ONLY(c, "cfmm_reset_stream");
     c->stream = c->own_stream.get();
+    c->desc_dirty = true;
     return CFMM_OK;
 }
 
@@ -291,6 +298,7 @@ int cfmm_set_option(cfmm_ctx* c, const char* key, int64_t value)
     if (slot == &c->opt_stream_stores && !(value == 0 || value == 1 || value == 2))
         return fail(c, CFMM_ERR_INVALID_ARG, "stream_stores must be 0 (auto), 1 (write-through) or 2 (non-temporal)");
     *slot = value;
+    c->desc_dirty = true;   // pack, compact_trades, block, max_grid, fuse_segments, bin_copies, stream_stores, univ3_heads, geomean_exact, cost_*: all copied
     if (slot != &c->opt_multi_threads)
         for (cfmm_ctx* child : c->shards) {
             int rc = cfmm_set_option(child, key, value);

@@ -42,7 +42,7 @@ void pop_last_segment(cfmm_ctx* child)
     (void)hipSetDevice(child->device);
     (void)hipStreamSynchronize(child->stream);
     child->segs.pop_back();
-    child->geometry_dirty = true;
+    child->geometry_dirty = child->desc_dirty = true;
     child->have_out = child->have_trades = false;
 }
 

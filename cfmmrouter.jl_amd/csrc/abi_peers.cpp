@@ -15,6 +15,7 @@ int cfmm_set_peers(cfmm_ctx* c, const uint64_t* peer_buffers, int32_t world, int
     if (!c) return CFMM_ERR_INVALID_ARG;
     CFMM_SINGLE_ONLY(c, "cfmm_set_peers");
     armed_cancel(c);
+    c->desc_dirty = true;   // (a sharded context has no single-block direct launch: SweepDesc::direct)
     if (world == 0) { // back to single-GPU operation
         c->peers.clear();
         return CFMM_OK;

@@ -86,7 +86,13 @@ int ensure_geometry(cfmm_ctx* c)
             std::copy(sg.gvals.begin(), sg.gvals.end(), tabs.begin() + (std::ptrdiff_t)(gi * kMaxFeeTable + (size_t)sg.gbase));
         }
     }
-    int rc = c->d_gtab.grow(c, tabs.size());
+    // ... followed, in the same array, by the launches' descriptors (sweep.h SweepDesc; ensure_desc fills them in)
+    size_t desc_bytes = 0;
+    for (const Group& g : c->groups)
+        if (!ragged_kind(c->segs[(size_t)g.first].kind)) desc_bytes += sweep_desc_bytes(g.grid);
+    c->desc.base = tabs.size() * sizeof(double);   // (a multiple of 128: kMaxFeeTable doubles per launch)
+    c->desc.bytes = desc_bytes;
+    int rc = c->d_gtab.grow(c, tabs.size() + desc_bytes / sizeof(double));
     if (rc != CFMM_OK) return rc;
     if (!tabs.empty()) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -101,6 +107,7 @@ int ensure_geometry(cfmm_ctx* c)
     if ((rc = c->d_delta.grow(c, trades)) || (rc = c->d_lambda.grow(c, trades)) || (rc = c->d_over.grow(c, trades))) return rc;
     if (global_bins(c) && (rc = build_incidence(c)) != CFMM_OK) return rc;
     c->geometry_dirty = false;
+    c->desc_dirty = true;
     c->have_trades = false;
     c->x_valid = false;
     c->have_out = false;
@@ -124,52 +131,120 @@ struct Eval {
 // the option "geomean_exact" form of a kind: neither log v from LDS nor a fast arithmetic
 bool exact_form(const cfmm_ctx* c, int kind) { return kind_info(kind).exact_form && c->geo.geomean_exact != 0; }
 
-// The SweepArgs every segment of launch g (the gi-th) shares
-SweepArgs group_args(const cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
+// a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
+// exchanges, and RCCL all-reduces d_out behind the fold)
+bool direct_launch(const cfmm_ctx* c)
 {
-    SweepArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.v = ev.d_v;
-    a.n = c->n;
-    a.n_pad = c->n_pad;
-    a.v_shift = stage_pairs(c->n, g.block) ? 4 : 3;
-    a.gtab = c->d_gtab ? c->d_gtab.get() + gi * kMaxFeeTable : nullptr;
-    a.gtab_n = a.gtab ? g.gtab_n : 0;
-    for (int k = 0; k < g.nseg && !ev.gb; ++k) {
+    return c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !global_bins(c) && c->peers.empty() &&
+           !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
+}
+
+// What every launch of group g (the gi-th) reads and no evaluation changes: the head of its descriptor (sweep.h SweepDesc)
+SweepDesc desc_head(const cfmm_ctx* c, const Group& g, size_t gi)
+{
+    const bool gb = global_bins(c);
+    SweepDesc d;
+    std::memset(&d, 0, sizeof d);
+    d.n = c->n;
+    d.n_pad = c->n_pad;
+    d.v_shift = stage_pairs(c->n, g.block) ? 4 : 3;
+    d.gtab = c->d_gtab ? c->d_gtab.get() + gi * kMaxFeeTable : nullptr;
+    d.gtab_n = d.gtab ? g.gtab_n : 0;
+    for (int k = 0; k < g.nseg && !gb; ++k) {
         const int kind = c->segs[(size_t)g.first + k].kind;
-        if (kind_info(kind).logv && !exact_form(c, kind)) a.need_logv = 1;
+        if (kind_info(kind).logv && !exact_form(c, kind)) d.need_logv = 1;
     }
-    if (a.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, a.gtab_n, a.v_shift == 4 ? 1 : 0) > 160 * 1024)
-        a.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
-    a.copies = bin_copies(c->n, c->geo, g.block);
-    a.compact = (c->opt_compact_trades != 0 && !ev.gb) ? 1 : 0;
-    a.partials = c->d_partials.get() + (size_t)g.row_off * row_width(c);
-    a.row_pitch = row_width(c);
-    a.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
-    a.arm_word = ev.arm.word;
-    a.arm_seq = ev.arm.seq;
-    a.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
-    // sharded (cfmm_set_peers): a rank whose host is late by less than the peer timeout must not lose the evaluation --
-    // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
-    // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
-    if (ev.sharded) a.arm_timeout = std::max<long long>(a.arm_timeout, c->peer_timeout_ticks);
-    a.flags = c->stage.buf.dev() ? reinterpret_cast<unsigned long long*>(c->stage.buf.dev() + c->stage.flag_off) : nullptr;
-    a.nt_stores = c->opt_stream_stores == 2 || (c->opt_stream_stores == 0 && c->touched_bytes > (int64_t)256 << 20) ? 1 : 0;
-    if (ev.direct) {
-        a.direct = 1;
-        a.direct_out = ev.d_out;
-        a.direct_host = ev.ho;
-        a.reverse = 0;   // two tiles at most, the whole market in one CU's L1: nothing for the alternation to reuse -- and every
-                         // evaluation of such a market, fused or materialising, then returns the same bits at the same prices
+    if (d.need_logv && sweep_lds_bytes(c->n_pad, 1, g.block, 1, d.gtab_n, d.v_shift == 4 ? 1 : 0) > 160 * 1024)
+        d.need_logv = 0;   // the log-price row does not fit next to v and one bin copy: one logarithm per pool instead
+    d.copies = bin_copies(c->n, c->geo, g.block);
+    d.compact = (c->opt_compact_trades != 0 && !gb) ? 1 : 0;
+    d.partials = c->d_partials.get() + (size_t)g.row_off * row_width(c);
+    d.row_pitch = row_width(c);
+    d.flags = c->stage.buf.dev() ? reinterpret_cast<unsigned long long*>(c->stage.buf.dev() + c->stage.flag_off) : nullptr;
+    d.nt_stores = c->opt_stream_stores == 2 || (c->opt_stream_stores == 0 && c->touched_bytes > (int64_t)256 << 20) ? 1 : 0;
+    d.direct = direct_launch(c) ? 1 : 0;
+    return d;
+}
+
+// a two-coin segment's pool streams (its member of AnyPools)
+AnyPools pools_of(const cfmm_ctx* c, const Segment& s, int gtab_n)
+{
+    const int gbase = gtab_n ? s.gbase : -1;   // -1: fees from the gamma array
+    AnyPools p;
+    std::memset(&p, 0, sizeof p);
+    switch (s.kind) {
+    case CFMM_KIND_PRODUCT:
+    case CFMM_KIND_SOLIDLY: p.p = ProductPools{s.R.get(), s.gamma.get(), s.Ai.get(), s.pk.get(), gbase}; break;
+    case CFMM_KIND_GEOMEAN:
+        p.g = GeoMeanPools{s.R.get(), s.w.get(), s.gamma.get(), s.Ai.get(), s.eta.get(), s.lR.get(), (int)c->geo.geomean_exact,
+                           s.pk.get(), gbase};
+        break;
+    default: {
+        const UniV3State& u = s.u;
+        p.u = UniV3Pools{u.pg.get(), s.Ai.get(), u.cur_a.get(), u.cur_b.get(), u.cur_c.get(), u.curR.get(), u.walk.get(),
+                         u.ticks.get(), u.thr.get(), c->opt_univ3_heads != 0 ? u.head.get() : nullptr, u.has_walk, u.cp.get(),
+                         s.pk.get(), gbase};
+        break;
     }
-    return a;
+    }
+    return p;
+}
+
+// The descriptors of the current geometry on the device, behind the fee tables in d_gtab (ctx.h SweepDescStore): rebuilt when something they copy has
+// changed -- desc_dirty (the geometry, an option, the peers, the stream, a swapped pool array), or a device array or pinned
+// buffer of the library created or released since (resource_epoch: a descriptor must never outlive an address it holds) --
+// and uploaded in stream order.  The steady state is the two comparisons of the first line.
+int ensure_desc(cfmm_ctx* c)
+{
+    SweepDescStore& ds = c->desc;
+    if (!c->desc_dirty && ds.epoch == resource_epoch()) return CFMM_OK;
+    const bool gb = global_bins(c);
+    ds.heads.clear();
+    std::vector<int> kinds;
+    for (const Segment& s : c->segs) kinds.push_back(s.kind);
+    for (size_t gi = 0; gi < c->groups.size(); ++gi) {
+        const Group& g = c->groups[gi];
+        SweepDesc d = desc_head(c, g, gi);
+        d.nseg = ragged_kind(c->segs[(size_t)g.first].kind) ? 0 : g.nseg;   // 0: sweep_ncoin takes plain arguments
+        for (int k = 0; k < d.nseg; ++k) {
+            const Segment& s = c->segs[(size_t)g.first + k];
+            SegRec& r = d.seg[k];
+            r.pools = pools_of(c, s, d.gtab_n);
+            r.m = s.m;
+            r.Delta = c->d_delta.get() + s.trade_off;
+            r.Lambda = c->d_lambda.get() + s.trade_off;
+            r.Over = c->d_over.get() + s.trade_off;
+            r.gflow = gb ? c->d_flow.get() + s.trade_off : nullptr;
+        }
+        ds.heads.push_back(d);
+    }
+    const std::vector<unsigned char> bytes = build_sweep_desc(c->groups, ds.heads, kinds, ds.off);
+    if (bytes.size() != ds.bytes || (ds.base + ds.bytes) > c->d_gtab.size() * sizeof(double))
+        return fail(c, CFMM_ERR_STATE, "sweep descriptors: %zu bytes built, room for %zu", bytes.size(), ds.bytes);
+    // The staging buffer may still be the source of the previous upload: wait for that copy.  The wait is bounded by the
+    // work that was on the stream in front of the copy.  That can include a pre-armed launch, but never one that is still
+    // waiting for its prices: cfmm_route has at most one such launch pending and signals or cancels it before it enqueues
+    // anything else (armed_eval, armed_cancel), and every other entry point cancels a pending launch first.
+    if (ds.in_flight) HIP_TRY(c, hipEventSynchronize(ds.uploaded.get()));
+    ds.in_flight = false;
+    int rc;
+    if ((rc = ds.stage.grow(c, bytes.size(), false)) || (rc = ds.uploaded.create(c, hipEventDisableTiming))) return rc;
+    if (!bytes.empty()) {
+        std::memcpy(ds.stage.host(), bytes.data(), bytes.size());
+        HIP_TRY(c, hipMemcpyAsync(ds.dev(c), ds.stage.host(), bytes.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipEventRecord(ds.uploaded.get(), c->stream));
+        ds.in_flight = true;
+    }
+    ds.epoch = resource_epoch();
+    c->desc_dirty = false;
+    return CFMM_OK;
 }
 
 // The kernel's arithmetic (LaunchCfg::arith).  Fast: every pool constant of the launch inside the window (checked at upload),
 // prices staged as {v, rcp(v)} pairs, and the prices themselves inside it as far as the host knows ...
-int arith_of(const cfmm_ctx* c, const Eval& ev, const Group& g, const SweepArgs& a)
+int arith_of(const cfmm_ctx* c, const Eval& ev, const Group& g, const SweepDesc& d)
 {
-    bool fast = c->opt_fast_math != 0 && !ev.gb && a.v_shift == 4 && ev.price_window != kPricesOutside;
+    bool fast = c->opt_fast_math != 0 && !ev.gb && d.v_shift == 4 && ev.price_window != kPricesOutside;
     for (int k = 0; k < g.nseg && fast; ++k) {
         const Segment& s = c->segs[(size_t)g.first + k];
         fast = s.fast_ok != 0 && kind_info(s.kind).has_fast && !exact_form(c, s.kind);
@@ -180,73 +255,77 @@ int arith_of(const cfmm_ctx* c, const Eval& ev, const Group& g, const SweepArgs&
     return !fast ? 0 : (ev.price_window == kPricesUnknown && ev.arm.seq == 0 && c->opt_dev_prices_in_window == 0) ? 2 : 1;
 }
 
-// The per-segment part of a launch's arguments: SweepArgs (a segment's own launch) and MultiSeg (fused) carry the same fields
-template <class SegArgs>
-void fill_segment(const cfmm_ctx* c, const Eval& ev, const Segment& s, SegArgs& t)
+// What differs from one evaluation to the next: the kernels' argument
+SweepLaunch launch_args(const cfmm_ctx* c, const Eval& ev, size_t gi)
 {
-    t.m = s.m;
-    t.Delta = ev.materialize ? c->d_delta.get() + s.trade_off : nullptr;
-    t.Lambda = ev.materialize ? c->d_lambda.get() + s.trade_off : nullptr;
-    t.Over = ev.materialize ? c->d_over.get() + s.trade_off : nullptr;
-    t.gflow = ev.gb ? c->d_flow.get() + s.trade_off : nullptr;
+    SweepLaunch la;
+    std::memset(&la, 0, sizeof la);
+    la.desc = c->desc.off[gi] == kNoDesc ? nullptr : reinterpret_cast<const SweepDesc*>(c->desc.dev(c) + c->desc.off[gi]);
+    la.v = ev.d_v;
+    la.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
+    la.arm_word = ev.arm.word;
+    la.arm_seq = ev.arm.seq;
+    la.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
+    // sharded (cfmm_set_peers): a rank whose host is late by less than the peer timeout must not lose the evaluation --
+    // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
+    // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
+    if (ev.sharded) la.arm_timeout = std::max<long long>(la.arm_timeout, c->peer_timeout_ticks);
+    if (ev.direct) {
+        la.direct_out = ev.d_out;
+        la.direct_host = ev.ho;
+        la.reverse = 0;   // two tiles at most, the whole market in one CU's L1: nothing for the alternation to reuse -- and every
+                          // evaluation of such a market, fused or materialising, then returns the same bits at the same prices
+    }
+    return la;
 }
 
-AnyPools pools_of(const cfmm_ctx* c, const Eval& ev, const Segment& s, int gtab_n)
+// An N-coin segment's launch keeps plain arguments (sweep_ncoin): the head's fields and the launch's in one SweepArgs
+SweepArgs ncoin_args(const SweepDesc& d, const SweepLaunch& la, const Segment& s)
 {
-    const int gbase = gtab_n ? s.gbase : -1;   // -1: fees from the gamma array
-    AnyPools p;
-    switch (s.kind) {
-    case CFMM_KIND_PRODUCT:
-    case CFMM_KIND_SOLIDLY: p.p = ProductPools{s.R.get(), s.gamma.get(), s.Ai.get(), s.pk.get(), gbase}; break;
-    case CFMM_KIND_GEOMEAN:
-        p.g = GeoMeanPools{s.R.get(), s.w.get(), s.gamma.get(), s.Ai.get(), s.eta.get(), s.lR.get(), (int)c->geo.geomean_exact,
-                           s.pk.get(), gbase};
-        break;
-    case CFMM_KIND_UNIV3: {
-        const UniV3State& u = s.u;
-        p.u = UniV3Pools{u.pg.get(), s.Ai.get(), u.cur_a.get(), u.cur_b.get(), u.cur_c.get(), u.curR.get(), u.walk.get(),
-                         u.ticks.get(), u.thr.get(), c->opt_univ3_heads != 0 ? u.head.get() : nullptr, u.has_walk, u.cp.get(),
-                         s.pk.get(), gbase};
-        break;
-    }
-    default:
-        p.n = NCoinPools{s.nc.R.get(), s.nc.q.get(), s.nc.tok.get(), s.nc.glg.get(), s.nc.par.get(), s.n_coins,
-                         ev.materialize ? s.nc.D.get() : nullptr, ev.materialize ? s.nc.L.get() : nullptr};
-        break;
-    }
-    return p;
+    SweepArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.v = la.v;
+    a.n = d.n;
+    a.n_pad = d.n_pad;
+    a.v_shift = d.v_shift;
+    a.need_logv = d.need_logv;
+    a.gtab = d.gtab;
+    a.gtab_n = d.gtab_n;
+    a.copies = d.copies;
+    a.flags = d.flags;
+    a.m = s.m;
+    a.compact = d.compact;
+    a.partials = d.partials;
+    a.row_pitch = d.row_pitch;
+    a.reverse = la.reverse;
+    a.arm_word = la.arm_word;
+    a.arm_seq = la.arm_seq;
+    a.arm_timeout = la.arm_timeout;
+    a.nt_stores = d.nt_stores;
+    return a;
 }
 
 // One sweep launch: launch group g, the gi-th of the evaluation
 int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
 {
-    SweepArgs a = group_args(c, ev, g, gi);
+    const SweepDesc& d = c->desc.heads[gi];
+    const SweepLaunch la = launch_args(c, ev, gi);
     const size_t lds = ev.gb ? (size_t)(g.block / 64) * sizeof(double)
-                             : sweep_lds_bytes(c->n_pad, a.copies, g.block, a.need_logv, a.gtab_n, a.v_shift == 4 ? 1 : 0);
+                             : sweep_lds_bytes(c->n_pad, d.copies, g.block, d.need_logv, d.gtab_n, d.v_shift == 4 ? 1 : 0);
     hipEvent_t ea = nullptr, eb = nullptr;
     if (ev.timed) c->timer.take_events(ea, eb);   // start/stop written by the command processor around this launch (hipExtLaunchKernel)
-    const LaunchCfg cfg{g.block, g.grid, lds, arith_of(c, ev, g, a), ea, eb};
-    const Segment* segs = &c->segs[(size_t)g.first];
+    const LaunchCfg cfg{g.block, g.grid, lds, arith_of(c, ev, g, d), ea, eb};
+    const Segment& s0 = c->segs[(size_t)g.first];
     hipError_t e;
     if (g.multi) {
-        MultiArgs ma;
-        std::memset(&ma, 0, sizeof ma);
-        ma.nseg = g.nseg;
-        ma.xcd_map = g.xcd_map ? 1 : 0;
-        std::memcpy(ma.pattern, g.pattern, sizeof ma.pattern);
-        std::memcpy(ma.rank, g.rank, sizeof ma.rank);
-        std::memcpy(ma.seg_w, g.seg_w, sizeof ma.seg_w);
-        ma.common = a;
-        ma.common.gflow = ev.gb ? c->d_flow.get() : nullptr; // mode flag for the launcher; per-segment bases below
-        for (int k = 0; k < g.nseg; ++k) {
-            ma.seg[k].kind = segs[k].kind;
-            ma.seg[k].pools = pools_of(c, ev, segs[k], a.gtab_n);
-            fill_segment(c, ev, segs[k], ma.seg[k]);
-        }
-        e = launch_multi(ma, cfg, ev.materialize, c->stream);
+        e = launch_multi(ev.gb, la, cfg, ev.materialize, c->stream);
+    } else if (ragged_kind(s0.kind)) {
+        const NCoinPools p{s0.nc.R.get(), s0.nc.q.get(), s0.nc.tok.get(), s0.nc.glg.get(), s0.nc.par.get(), s0.n_coins,
+                           ev.materialize ? s0.nc.D.get() : nullptr, ev.materialize ? s0.nc.L.get() : nullptr};
+        e = launch_ncoin(s0.kind, p, ncoin_args(d, la, s0), ev.gb, cfg, ev.materialize, c->stream);
     } else {
-        fill_segment(c, ev, segs[0], a);
-        e = launch_sweep(segs[0].kind, pools_of(c, ev, segs[0], a.gtab_n), a, cfg, ev.materialize, c->stream);
+        e = launch_sweep(s0.kind, c->geo.geomean_exact != 0, c->opt_univ3_heads != 0 && s0.u.head, ev.gb, la, cfg, ev.materialize,
+                         c->stream);
     }
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
     if (ea && eb) c->timer.pending.push_back({ea, eb, 0});
@@ -328,10 +407,8 @@ int enqueue_sweep(cfmm_ctx* c, const double* d_v, double* d_out, bool materializ
         ev.ho.tag = granule_tag(++c->stage.out_seq);
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    // a launch of one block needs no fold: its row goes straight to the consumer (single-GPU contexts: a sharded fold also
-    // exchanges, and RCCL all-reduces d_out behind the fold)
-    ev.direct = c->groups.size() == 1 && c->groups[0].grid == 1 && !c->groups[0].multi && !ev.gb && !ev.sharded &&
-                !ragged_kind(c->segs[(size_t)c->groups[0].first].kind);
+    if ((rc = ensure_desc(c)) != CFMM_OK) return rc;
+    ev.direct = direct_launch(c);
     for (size_t gi = 0; gi < c->groups.size(); ++gi)
         if ((rc = launch_group(c, ev, c->groups[gi], gi)) != CFMM_OK) return rc;
     c->stage.last_host_out = host_out;

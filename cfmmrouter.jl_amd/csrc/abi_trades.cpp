@@ -388,6 +388,7 @@ int cfmm_update_reserves(cfmm_ctx* c)
             continue;
         }
         s.u = std::move(fresh[k].u);
+        c->desc_dirty = true;   // the sweep descriptors hold the replaced arrays
         s.fast_ok = fresh[k].fast_ok;
         s.h_cp.swap(fresh[k].cp);
     }

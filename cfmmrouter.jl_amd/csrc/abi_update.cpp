@@ -205,6 +205,7 @@ int univ3_make_room(cfmm_ctx* c, Segment& s, int64_t need)
     u.ticks = std::move(d_ticks);   // (releases the old arrays)
     u.thr = std::move(d_thr);
     u.walk = std::move(d_walk);
+    c->desc_dirty = true;           // the sweep descriptors hold ticks / thr / walk
     u.h_walk.swap(walk);
     u.tick_used = tight;
     u.tick_cap = cap;
@@ -253,6 +254,7 @@ int apply_univ3(cfmm_ctx* c, Segment& s, const Update& u, const Rows& rows)
         HIP_TRY(c, hipMemsetAsync(new_head.get(), 0, 2 * (size_t)s.m * sizeof(uint4), c->stream));
         st.head = std::move(new_head);
         st.has_walk = 1;
+        c->desc_dirty = true;       // (the descriptors hold head and has_walk)
         c->geometry_dirty = true;   // (the plan reads has_walk: bytes per pool, hence "stream_stores" = auto)
     }
     const int base = (int)st.tick_used;

@@ -82,7 +82,7 @@ int add_segment_common(cfmm_ctx* c, Segment&& s, const int32_t* Ai)
     if (s.m == 0) return CFMM_OK;   // an empty batch contributes no pools, no trades and no partial rows: not stored
     if (global_bins(c) && s.m > 0) s.h_ai.assign(Ai, Ai + 2 * s.m);
     c->segs.push_back(std::move(s));
-    c->geometry_dirty = true;
+    c->geometry_dirty = c->desc_dirty = true;
     c->have_out = false;
     c->have_trades = false;
     return CFMM_OK;
@@ -430,7 +430,7 @@ int cfmm_pools_clear(cfmm_ctx* c)
     c->flat_total = 0;
     c->any_ragged = false;
     c->rows_total = 0;
-    c->geometry_dirty = true;
+    c->geometry_dirty = c->desc_dirty = true;
     c->have_out = c->have_trades = false;
     return CFMM_OK;
 }

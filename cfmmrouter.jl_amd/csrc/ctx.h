@@ -216,6 +216,22 @@ struct SelectScratch {
                                        // latest timed call's kernel spans (emit: 0 when the call only counted)
 };
 
+// The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
+// one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
+// a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
+// cfmm_ctx::desc_dirty is set or a resource of the library has been created or released since (resource_epoch, devbuf.h),
+// copied from the pinned staging in stream order.  Every device of a multi-device context owns one (its child context's).
+struct SweepDescStore {
+    size_t base = 0, bytes = 0;      // where the descriptors start in d_gtab (bytes), and their size
+    PinnedBuf<unsigned char> stage;
+    Event uploaded;                  // behind the latest copy stage -> device: the staging is rewritten only after it
+    bool in_flight = false;
+    uint64_t epoch = 0;              // resource_epoch() when the descriptors were built
+    std::vector<size_t> off;         // [groups] where each launch group's descriptor starts (kNoDesc: it takes none)
+    std::vector<SweepDesc> heads;    // [groups] host copies of the heads: LDS sizes, the arithmetic, sweep_ncoin's arguments
+    unsigned char* dev(const cfmm_ctx* c) const;
+};
+
 // Kernel timing (option "time_kernels"): a pool of events, the {start, stop} pairs not yet read, the totals
 struct KernelTimer {
     std::vector<Event> pool;
@@ -278,13 +294,18 @@ struct cfmm_ctx {
     void* rccl_comm = nullptr;    // ncclComm_t
     bool rccl_owned = false;      // created by cfmm_rccl_init_rank: destroyed with the context
     cfmm::HostStage stage;
-    cfmm::DevBuf<double> d_gtab;  // [groups][kMaxFeeTable] fee tables of the launches (packed pool records)
+    cfmm::DevBuf<double> d_gtab;  // [groups][kMaxFeeTable] fee tables of the launches (packed pool records), then their descriptors (desc)
     cfmm::ArmState arm;
     std::vector<double> last_out; // psi..., acc of the latest host-pointer sweep
     std::vector<double> trade_v;  // v of the latest MATERIALISING host-pointer sweep (empty: none / device-pointer sweep)
     bool have_out = false;
     bool have_trades = false;
     bool geometry_dirty = true;
+    // the sweep descriptors copy something that has changed.  Set wherever geometry_dirty is, by every cfmm_set_option, by
+    // cfmm_set_peers and cfmm_set_stream, and wherever an array a descriptor points to is swapped for another (UniV3 state
+    // replaced or regrown, tick compaction); ensure_desc also compares resource_epoch
+    bool desc_dirty = true;
+    cfmm::SweepDescStore desc;
 
     // options (cfmm_set_option)
     cfmm::PlanOpts geo;          // the options the launch geometry depends on (launch_plan.h)
@@ -343,6 +364,7 @@ extern thread_local std::string g_create_error;
         return ::cfmm::fail(c, CFMM_ERR_UNSUPPORTED, what " is not available on a multi-device context (host-pointer calls only)")
 
 inline bool global_bins(const cfmm_ctx* c) { return global_bins(c->n); }
+inline unsigned char* SweepDescStore::dev(const cfmm_ctx* c) const { return reinterpret_cast<unsigned char*>(c->d_gtab.get()) + base; }
 inline int row_width(const cfmm_ctx* c) { return global_bins(c) ? 1 : row_pitch_of(c->n + 1); }   // doubles between partial rows
 inline bool is_parent(const cfmm_ctx* c) { return !c->shards.empty() || c->device < 0; }
 

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 
 namespace cfmm {
 
@@ -20,6 +21,9 @@ int fail(const cfmm_ctx* c, int code, const char* fmt, ...);
 hipError_t dev_alloc(void** p, size_t bytes);   // *p = nullptr on failure
 hipError_t dev_alloc_fine(void** p, size_t bytes);   // the same in FINE-GRAINED device memory (the host writes it through the PCIe BAR)
 void dev_free(void* p);
+// counts every create and release of a device array or pinned buffer of the library (process-wide, monotonic): whoever
+// caches device addresses -- the sweep descriptors, abi_sweep.cpp ensure_desc -- compares it to know that none has gone
+uint64_t resource_epoch();
 
 template <class T>
 class DevBuf {

@@ -3,6 +3,7 @@
 #include "ctx.h"
 
 #include <algorithm>
+#include <cstring>
 
 namespace cfmm {
 
@@ -183,6 +184,63 @@ LaunchPlan plan_launches(const std::vector<PlanSeg>& segs, int n_tokens, const P
         first = run_end;
     }
     return plan;
+}
+
+// Block b of launch g: its segment and the block of that segment it is (the maps sweep_multi used to evaluate on the
+// device), then the tiles of that block: first + k·stride < m, all of them full but possibly the last
+BlockRec plan_block_rec(const Group& g, int b, const SweepDesc& head, const int* kinds)
+{
+    int sidx = 0, local = b, nblocks = g.grid;
+    if (g.multi && g.xcd_map) {
+        const int x = b & 7, j = b >> 3, q = j >> 5, p = (j + q) & 31;
+        sidx = g.pattern[p];
+        const int w = g.seg_w[sidx];
+        local = (q * w + g.rank[p]) * 8 + x;
+        nblocks = (g.grid >> 8) * w * 8;
+    } else if (g.multi) {
+        nblocks = g.grid / g.nseg;
+        sidx = b % g.nseg;
+        local = b / g.nseg;
+    }
+    const int64_t m = head.seg[sidx].m;
+    BlockRec r;
+    r.first = (int64_t)local * g.block;
+    r.stride = (int64_t)nblocks * g.block;
+    r.full = r.tail = 0;
+    if (r.first < m) {
+        const int64_t tiles = (m - r.first + r.stride - 1) / r.stride;       // tiles of lane 0
+        const int64_t rest = m - (r.first + (tiles - 1) * r.stride);          // pools of the last one, >= 1
+        r.full = (int32_t)(rest >= g.block ? tiles : tiles - 1);
+        r.tail = (int32_t)(rest >= g.block ? 0 : rest);
+    }
+    r.row = b;
+    r.seg = (int16_t)sidx;
+    r.kind = (int16_t)kinds[sidx];
+    return r;
+}
+
+std::vector<unsigned char> build_sweep_desc(const std::vector<Group>& groups, const std::vector<SweepDesc>& heads,
+                                            const std::vector<int>& seg_kinds, std::vector<size_t>& offsets)
+{
+    offsets.assign(groups.size(), kNoDesc);
+    size_t total = 0;
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        if (heads[gi].nseg == 0) continue;
+        offsets[gi] = total;
+        total += sweep_desc_bytes(groups[gi].grid);
+    }
+    std::vector<unsigned char> bytes(total, 0);
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        if (offsets[gi] == kNoDesc) continue;
+        const Group& g = groups[gi];
+        SweepDesc head = heads[gi];
+        head.nseg = g.nseg;
+        head.grid = g.grid;
+        std::memcpy(bytes.data() + offsets[gi], &head, sizeof head);
+        BlockRec* recs = reinterpret_cast<BlockRec*>(bytes.data() + offsets[gi] + kSweepDescHead);
+        for (int b = 0; b < g.grid; ++b) recs[b] = plan_block_rec(g, b, head, seg_kinds.data() + g.first);
+    }
+    return bytes;
 }
 
 bool stage_pairs(int n_tokens, int block)

@@ -72,6 +72,20 @@ struct LaunchPlan {
 
 LaunchPlan plan_launches(const std::vector<PlanSeg>& segs, int n_tokens, const PlanOpts& o);
 
+// The launch-invariant descriptors of an evaluation's sweep_kernel / sweep_multi launches (sweep.h SweepDesc) as ONE byte
+// block, ready to be copied to the device: per launch group the head -- heads[gi], filled by the caller: the launch's
+// LDS geometry and buffers, and per segment its size and device pointers -- followed by the group's block table, which is
+// computed here from the group's map and heads[gi].seg[k].m.  offsets[gi] is where group gi's descriptor starts (a multiple
+// of 128 bytes), or kNoDesc for a group that takes none (heads[gi].nseg == 0: the N-coin launches keep plain arguments).
+// The block records restate, block by block, what the kernels computed from blockIdx / gridDim before the table existed:
+// a segment's own launch gives block b the tiles b, b + grid, ...; a fused launch maps b to {segment, block of the
+// segment} through Group::pattern / rank / seg_w (xcd_map) or b % nseg, b / nseg.  kinds[gi][k]: the CFMM_KIND_* of the
+// segments.  Pure, like plan_launches; pinned on the CPU by tests/test_sweep_desc_cpu.py.
+constexpr size_t kNoDesc = ~(size_t)0;
+std::vector<unsigned char> build_sweep_desc(const std::vector<Group>& groups, const std::vector<SweepDesc>& heads,
+                                            const std::vector<int>& seg_kinds, std::vector<size_t>& offsets);
+BlockRec plan_block_rec(const Group& g, int b, const SweepDesc& head, const int* kinds);
+
 // Prices are staged in LDS as {v, rcp_refined(v)} pairs unless the market is too wide for them (sweep.h SweepArgs::v_shift)
 bool stage_pairs(int n_tokens, int block);
 // private bin copies per block (SweepArgs::copies)

@@ -177,30 +177,70 @@ union AnyPools {
     ProductPools p;
     GeoMeanPools g;
     UniV3Pools u;
-    NCoinPools n;                // (single launches only: never in a MultiSeg)
+    NCoinPools n;                // (sweep_ncoin launches only: never in a SegRec)
 };
-static_assert(sizeof(AnyPools) == sizeof(UniV3Pools), "MultiSeg's layout is the widest two-coin family's");
-struct MultiSeg {
-    int kind;
-    int64_t m;
+static_assert(sizeof(AnyPools) == sizeof(UniV3Pools), "SegRec's layout is the widest two-coin family's");
+
+// The launch-invariant descriptor of a sweep_kernel / sweep_multi launch.  Everything a launch of a given geometry reads
+// that does NOT change from one evaluation to the next -- pool pointers, segment sizes, the block -> segment map, trade and
+// row buffers, the fee table, the LDS geometry -- lives in DEVICE memory: built on the host by build_sweep_desc
+// (launch_plan.h) when the geometry, an option or an array it points to changes, uploaded once, and then read by every
+// launch through the scalar cache.  Nothing rewrites it between launches, so from the second sweep on its lines CAN be
+// served by each XCD's L2 (expected, not measured: what is measured is the entry's length); the kernel
+// arguments proper (SweepLaunch) are one 128-byte line.  Before, a fused launch carried 0x390
+// bytes of arguments (eight lines, written afresh and therefore cache-cold on every XCD for every launch) and walked
+// them in nine dependent waits -- xcd_map, pattern[] / rank[], seg_w[], seg[sidx]... -- before its first pool load.
+//
+// BlockRec, indexed by blockIdx.x: the block's segment, the first pool of its tile 0 (lane 0), the distance between two of
+// its tiles, and how many tiles a lane walks: lane t has `full + (t < tail)` -- no division on the device.  The records
+// restate the maps the kernels used to compute (sweep_multi's two forms, bid / gridDim for a segment's own launch): the
+// same block sweeps the same pools in the same order and writes the same row.
+struct BlockRec {
+    int64_t first;               // pool of lane 0 in the block's tile 0
+    int64_t stride;              // pools between two consecutive tiles of the block (blocks of the segment x block size)
+    int32_t full;                // tiles every lane of the block has
+    int32_t tail;                // lanes of one more, partial tile (0: none)
+    int32_t row;                 // partial row the block writes
+    int16_t seg;                 // segment of the launch
+    int16_t kind;                // its CFMM_KIND_*
+};
+static_assert(sizeof(BlockRec) == 32, "four block records per 128-byte line");
+// One segment of the launch: the pool streams first (what the first tile's loads need), then what the epilogues need
+struct SegRec {
     AnyPools pools;
-    double2* Delta;
+    int64_t m;
+    double2* Delta;              // the segment's rows of the trade buffers (always set; read by materialising kernels only)
     double2* Lambda;
     double2* Over;
-    double2* gflow;
+    double2* gflow;              // large-market mode: the segment's rows of the flow array, else null
 };
-struct MultiArgs {
-    int nseg;
-    int xcd_map;                 // 1: XCD-aware, cost-weighted block -> segment map (needs grid % 256 == 0): deal j = b / 8
-                                 //    (the 8 blocks that land on the 8 XCDs together) belongs to segment
-                                 //    pattern[(j + j / 32) % 32] and is that segment's deal number (j / 32)·w + rank[...];
-                                 // 0: block b -> segment b % nseg (grids that are no multiple of 256 blocks: small markets)
-    unsigned char pattern[32];   // segment of each of 32 consecutive deals; segment s appears seg_w[s] times
-    unsigned char rank[32];      // rank[p] = #{p' < p : pattern[p'] == pattern[p]}
-    int seg_w[kMaxMulti];        // deals out of 32 given to each segment (in proportion to pools x cost per pool)
-    MultiSeg seg[kMaxMulti];
-    SweepArgs common;            // v, n, n_pad, copies, partials (row 0 of this launch)
+struct SweepDesc {
+    int n, n_pad, v_shift, need_logv;           // SweepArgs' fields of the same names
+    const double* gtab;
+    int gtab_n, copies;
+    unsigned long long* flags;
+    double* partials;            // row 0 of this launch
+    int row_pitch, compact, nt_stores, direct;
+    int nseg, grid;              // segments, block records
+    SegRec seg[kMaxMulti];
+    // BlockRec[grid] follows at kSweepDescHead (128-byte aligned)
 };
+constexpr size_t kSweepDescHead = (sizeof(SweepDesc) + 127) / 128 * 128;
+inline size_t sweep_desc_bytes(int grid) { return kSweepDescHead + ((size_t)grid * sizeof(BlockRec) + 127) / 128 * 128; }
+// What differs between two launches of the same geometry: the kernels' one argument, inside the first 128 bytes of the
+// kernarg segment
+struct SweepLaunch {
+    const SweepDesc* desc;       // device
+    const double* v;             // [n] device
+    int reverse;                 // SweepArgs::reverse / arm_* / direct_out / direct_host; what the first tile's loads need (desc,
+                                 // reverse) in the first 64 bytes
+    const unsigned long long* arm_word;
+    unsigned long long arm_seq;
+    long long arm_timeout;
+    double* direct_out;
+    HostOut direct_host;
+};
+static_assert(sizeof(SweepLaunch) <= 128, "the per-launch arguments are one line of the kernarg segment");
 
 struct LaunchCfg {
     int block;                   // kMidBlock or kBigBlock
@@ -214,23 +254,25 @@ struct LaunchCfg {
     hipEvent_t ev_stop = nullptr;  // (hipExtLaunchKernel), i.e. the kernel's own execution span
 };
 
-// One segment's own launch.  `kind` picks the member of `pools` and the kernel family: ProductTwoCoin (pools.p),
-// GeometricMeanTwoCoin (pools.g; reference_order picks the pow-based form), UniV3 (pools.u; the threshold-head kernel when
-// pools.u.head is set outside large-market mode), Solidly-style stable pairs (kind CFMM_KIND_SOLIDLY, φ = x³y + xy³:
-// ProductTwoCoin's pool layout in pools.p, full-range arithmetic), and the N-coin kinds CFMM_KIND_WEIGHTED / CFMM_KIND_CURVE
-// (pools.n; kMidBlock threads, full-range arithmetic, never single-block direct: a.Delta / a.Lambda / a.Over / a.gflow are
-// unused, the trades go to pools.n.Delta / pools.n.Lambda).  Large-market mode (a.gflow set) runs kMidBlock threads on the
-// full-range arithmetic.  A combination of family, arithmetic, block and mode that has no kernel (sweep_kernels.hip, the
-// kernel table) returns hipErrorInvalidDeviceFunction.
-hipError_t launch_sweep(int kind, const AnyPools& pools, const SweepArgs& a, const LaunchCfg& c, bool materialize,
+// A two-coin segment's own launch (sweep_kernel) from its descriptor.  `kind` picks the kernel family: ProductTwoCoin,
+// GeometricMeanTwoCoin (reference_order picks the pow-based form), UniV3 (the threshold-head kernel when `heads` is set
+// outside large-market mode), Solidly-style stable pairs (CFMM_KIND_SOLIDLY, φ = x³y + xy³: ProductTwoCoin's pool layout,
+// full-range arithmetic).  Large-market mode (gbins) runs kMidBlock threads on the full-range arithmetic.  A combination of
+// family, arithmetic, block and mode that has no kernel (sweep_kernels.hip, the kernel table) returns
+// hipErrorInvalidDeviceFunction.
+hipError_t launch_sweep(int kind, bool reference_order, bool heads, bool gbins, const SweepLaunch& la, const LaunchCfg& c,
+                        bool materialize, hipStream_t s);
+// An N-coin segment's launch (sweep_ncoin; CFMM_KIND_WEIGHTED / CFMM_KIND_CURVE): kMidBlock threads, full-range arithmetic,
+// never single-block direct; there is no large-market kernel (gbins set: hipErrorInvalidDeviceFunction); a.Delta / a.Lambda / a.Over / a.gflow are unused, the trades go to pools.Delta /
+// pools.Lambda.
+hipError_t launch_ncoin(int kind, const NCoinPools& pools, const SweepArgs& a, bool gbins, const LaunchCfg& c, bool materialize,
                         hipStream_t s);
 // R <- (R + γΔ) − Λ per coin, in place, then q <- the family's constant for the new R (par: unchanged)
 hipError_t launch_update_ncoin(int kind, double* R, double* q, const double* par, const double2* glg, const double* Delta,
                                const double* Lambda, int n_coins, int64_t m, hipStream_t s);
 
-// block b writes partial row b (see sweep_multi for the block -> segment map); without xcd_map the grid must be a
-// multiple of ma.nseg.
-hipError_t launch_multi(const MultiArgs& ma, const LaunchCfg& c, bool materialize, hipStream_t s);
+// Several segments in one launch (sweep_multi) from the launch's descriptor; block b writes partial row b.
+hipError_t launch_multi(bool gbins, const SweepLaunch& la, const LaunchCfg& c, bool materialize, hipStream_t s);
 
 // Large markets: chunk_sums[c] = sum of flow[entries[chunks[c].x .. chunks[c].y)], then
 // out[t] = sum of chunk_sums[tok_chunk_off[t] .. tok_chunk_off[t+1]) for t < n and

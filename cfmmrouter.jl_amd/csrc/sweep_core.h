@@ -38,7 +38,7 @@ __device__ __forceinline__ void store_row(double* dst, double x)
     asm volatile("global_store_dwordx2 %0, %1, off sc1" : : "v"(dst), "v"(x) : "memory");
 }
 
-// One block's share of a segment: tiles bid, bid+nblocks, ... of the segment's pools; its
+// One block's share of a segment: the tiles its block record names (sweep.h BlockRec); its
 // partial row goes to partials[row].
 // GBINS = true is the large-market mode (n_tokens > kMaxLdsTokens, v and the bins no longer fit
 // LDS): v is gathered straight from global memory (it stays L2-resident) and every pool's two
@@ -274,7 +274,7 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
 }
 
 // The tile loop of one pool family over a block's share of a segment: lane tid takes pools
-// (bid + k·nblocks)·BLOCK + tid, k = 0, 1, ...  Returns this lane's dual-scalar part.
+// i + k·step, k = 0, 1, ... left - 1.  Returns this lane's dual-scalar part.
 // The first tile's pool state is requested BEFORE v and the bins are staged in LDS, so that HBM round trip is not
 // exposed behind the staging barrier.  Tile order alternates between consecutive sweeps (a.reverse): block-strided
 // "phases" are walked first-to-last by one sweep and last-to-first by the next, so each sweep begins on the pool data
@@ -330,18 +330,11 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
 //               SIMD) never needed.
 constexpr int kArithFull = 0, kArithFast = 1, kArithAuto = 2;
 template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
-__device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a, const SweepLds& L, int bid, int nblocks,
-                                              bool& poison, bool& live)
+__device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a, const SweepLds& L, const typename Ops::Raw& cur,
+                                              int64_t i, int64_t step, int64_t left, bool& poison, bool& live)
 {
     static_assert(!(GBINS && FASTK != kArithFull), "large-market mode runs on the compiler's sequences");
     double acc = 0.0;
-    const int64_t stride = (int64_t)nblocks * BLOCK;
-    const int64_t i0 = (int64_t)bid * BLOCK + threadIdx.x;
-    int64_t left = i0 < a.m ? (a.m - i0 + stride - 1) / stride : 0;      // tiles of this lane
-    const int64_t step = a.reverse ? -stride : stride;
-    const int64_t i = a.reverse ? i0 + (left - 1) * stride : i0;
-    typename Ops::Raw cur = {};
-    if (left > 0) cur = ops.template load<GBINS>(i);
     const int staged = stage_prices<BLOCK, GBINS>(a, L);
     poison = (staged & kStageLive) == 0;              // a pre-armed launch that is not needed (or gave up)
     live = !poison || (staged & kStageGaveUp) != 0;   // false: CANCELLED by the host (a launch that gave up waiting still reports NaN)
@@ -422,68 +415,140 @@ __device__ __forceinline__ void finish_row(const SweepArgs& a, const SweepLds& L
     }
 }
 
-// One block's share of ONE segment: tiles bid, bid+nblocks, ... of the segment's pools; its partial
-// row goes to partials[row_id].
-template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
-__device__ __forceinline__ void sweep_body(const Ops& ops, const SweepArgs& a, int bid, int nblocks, int row_id)
+// The kernels' entry.  Two dependent reads stand between a block and its first pool load: the per-launch arguments (one
+// line of the kernarg segment, the only memory of the entry that is new -- cache-cold -- for every launch), then the
+// block's record and its segment's, from the launch's descriptor in device memory (sweep.h SweepDesc), which nothing
+// rewrites between launches.  The descriptor is read through the CONSTANT address space: it does not change while a
+// kernel runs, so every one of its fields is a scalar load that the compiler may place where the field is first used.
+#define CFMM_CONST_AS __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ const CFMM_CONST_AS T* const_as(const T* p)
 {
-    const SweepLds L = carve_lds<BLOCK, GBINS>(a);
-    bool poison, live;
-    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, bid, nblocks, poison, live);
-    finish_row<BLOCK, GBINS>(a, L, acc, row_id, poison, live);
+    return (const CFMM_CONST_AS T*)(reinterpret_cast<uintptr_t>(p));
 }
-
-template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK>
-__global__ __launch_bounds__(BLOCK) void sweep_kernel(Ops ops, SweepArgs a)
+// The kernels' one argument, read where it lies: in the kernarg segment, through the constant address space.  (A by-value
+// kernel parameter is copied out of the segment at the kernel's FIRST instruction, all 72 bytes of it, and the words only the
+// epilogue needs -- arm_*, direct_* -- then sit in SGPRs, or spilled to VGPR lanes, in front of the first pool load.)
+typedef const CFMM_CONST_AS SweepLaunch& LaunchRef;
+__device__ __forceinline__ LaunchRef launch_args()
 {
-    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(ops, a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+    return *(const CFMM_CONST_AS SweepLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
 }
-
-// Several segments (pool families) in ONE launch, so HBM-bound ProductTwoCoin blocks and ALU-bound GeometricMean /
-// UniV3 blocks are co-resident on every CU and overlap, and the sweep pays one launch + one kernel boundary instead of nseg.
-template <bool MAT, int BLOCK, bool GBINS, int FASTK>
-__global__ __launch_bounds__(BLOCK) void sweep_multi(MultiArgs ma)
+__device__ __forceinline__ BlockRec block_rec(LaunchRef la)
 {
-    const int bidx = (int)blockIdx.x;
-    int sidx, local, nblocks;
-    if (ma.xcd_map) {
-        // XCD-aware, cost-weighted block -> segment map.  Blocks are dealt round-robin to the 8 XCDs (block
-        // b runs on XCD b % 8), so "segment = b % nseg" would put ALL blocks of one pool family on the same
-        // XCDs (nseg = 2: ProductTwoCoin on XCDs 0,2,4,6, GeometricMean on 1,3,5,7 -- half the chip does all
-        // the arithmetic).  Here the 8 blocks of one deal (one per XCD) share a segment, consecutive deals
-        // walk through a 32-entry pattern in which segment s appears seg_w[s] times (its share of the
-        // launch's work: pools x cost per pool, so that all blocks finish together), and the pattern is
-        // rotated by one every 32 deals (one pass over an XCD's 32 CUs), so every XCD -- and, as the
-        // dispatcher fills CUs in order, every CU -- hosts all families.  Placement is only a performance
-        // assumption: any placement computes the same result.
-        const int x = bidx & 7, j = bidx >> 3, q = j >> 5, p = (j + q) & 31;
-        sidx = ma.pattern[p];
-        const int w = ma.seg_w[sidx];
-        local = (q * w + ma.rank[p]) * 8 + x;
-        nblocks = ((int)gridDim.x >> 8) * w * 8;
-    } else {   // small grids (not a multiple of 256 blocks): block b -> segment b % nseg
-        nblocks = (int)gridDim.x / ma.nseg;
-        sidx = bidx % ma.nseg;
-        local = bidx / ma.nseg;
-    }
-    const MultiSeg& sg = ma.seg[sidx];
-    SweepArgs a = ma.common;
+    const CFMM_CONST_AS BlockRec* recs =
+        (const CFMM_CONST_AS BlockRec*)(reinterpret_cast<uintptr_t>(la.desc) + kSweepDescHead);
+    const CFMM_CONST_AS BlockRec& r = recs[blockIdx.x];
+    return BlockRec{r.first, r.stride, r.full, r.tail, r.row, r.seg, r.kind};
+}
+// The SweepArgs of this block: the launch's own fields, the descriptor's, its segment's
+__device__ __forceinline__ SweepArgs block_args(LaunchRef la, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg)
+{
+    SweepArgs a;
+    a.v = la.v;
+    a.n = d.n;
+    a.n_pad = d.n_pad;
+    a.v_shift = d.v_shift;
+    a.need_logv = d.need_logv;
+    a.gtab = d.gtab;
+    a.gtab_n = d.gtab_n;
+    a.copies = d.copies;
+    a.flags = d.flags;
     a.m = sg.m;
     a.Delta = sg.Delta;
     a.Lambda = sg.Lambda;
     a.Over = sg.Over;
+    a.compact = d.compact;
+    a.partials = d.partials;
+    a.row_pitch = d.row_pitch;
     a.gflow = sg.gflow;
-    switch (sg.kind) {
-    case 0:
-        sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(ProductOps{sg.pools.p}, a, local, nblocks, bidx);
-        break;
+    a.reverse = la.reverse;
+    a.arm_word = la.arm_word;
+    a.arm_seq = la.arm_seq;
+    a.arm_timeout = la.arm_timeout;
+    a.nt_stores = d.nt_stores;
+    a.direct = d.direct;
+    a.direct_out = la.direct_out;
+    a.direct_host = HostOut{la.direct_host.gran, la.direct_host.tag};
+    return a;
+}
+// a family's view of a segment record's pools
+template <class Pools> __device__ __forceinline__ Pools pools_of(const CFMM_CONST_AS AnyPools& u);
+template <> __device__ __forceinline__ ProductPools pools_of<ProductPools>(const CFMM_CONST_AS AnyPools& u)
+{
+    return ProductPools{u.p.R, u.p.gamma, u.p.Ai, u.p.pk, u.p.gbase};
+}
+template <> __device__ __forceinline__ GeoMeanPools pools_of<GeoMeanPools>(const CFMM_CONST_AS AnyPools& u)
+{
+    return GeoMeanPools{u.g.R, u.g.w, u.g.gamma, u.g.Ai, u.g.eta, u.g.Q, u.g.reference_order, u.g.pk, u.g.gbase};
+}
+template <> __device__ __forceinline__ UniV3Pools pools_of<UniV3Pools>(const CFMM_CONST_AS AnyPools& u)
+{
+    return UniV3Pools{u.u.pg, u.u.Ai, u.u.cur_a, u.u.cur_b, u.u.cur_c, u.u.curR, u.u.walk, u.u.ticks, u.u.thr, u.u.head,
+                      u.u.has_walk, u.u.cp, u.u.pk, u.u.gbase};
+}
+
+// One block's share of ONE segment (its BlockRec); its partial row goes to partials[br.row].
+// The order is the point: the first tile's pool state is requested from the block record, the segment's pool streams and
+// the launch's direction ALONE -- lane t takes pools first + t + k·stride, k < full + (t < tail): the host did the division
+// -- and only then is everything else read (block_args: the LDS geometry, the trade and row buffers, the fee table), while
+// those loads are in flight.
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
+__device__ __forceinline__ void sweep_body(LaunchRef la, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg,
+                                           const BlockRec& br)
+{
+    const Ops ops{pools_of<decltype(Ops::p)>(sg.pools)};
+    const int64_t stride = br.stride;
+    const int64_t i0 = br.first + threadIdx.x;
+    const int64_t left = br.full + ((int)threadIdx.x < br.tail ? 1 : 0);      // tiles of this lane
+    const bool reverse = la.reverse != 0;
+    const int64_t step = reverse ? -stride : stride;
+    const int64_t i = reverse ? i0 + (left - 1) * stride : i0;
+    typename Ops::Raw cur = {};
+    if (left > 0) cur = ops.template load<GBINS>(i);
+    const SweepArgs a = block_args(la, d, sg);
+    const SweepLds L = carve_lds<BLOCK, GBINS>(a);
+    bool poison, live;
+    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, cur, i, step, left, poison, live);
+    finish_row<BLOCK, GBINS>(a, L, acc, br.row, poison, live);
+}
+
+// One segment's own launch: segment 0 of the descriptor
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK>
+__global__ __launch_bounds__(BLOCK) void sweep_kernel(SweepLaunch)
+{
+    LaunchRef la = launch_args();
+    const BlockRec br = block_rec(la);
+    const CFMM_CONST_AS SweepDesc& d = *const_as(la.desc);
+    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(la, d, d.seg[0], br);
+}
+
+// Several segments (pool families) in ONE launch, so HBM-bound ProductTwoCoin blocks and ALU-bound GeometricMean /
+// UniV3 blocks are co-resident on every CU and overlap, and the sweep pays one launch + one kernel boundary instead of nseg.
+// The block -> segment map is the descriptor's block table.  With a grid that is a multiple of 256 blocks it is XCD-aware
+// and cost-weighted (launch_plan.cpp plan_xcd_map, build_sweep_desc): blocks are dealt round-robin to the 8 XCDs (block b
+// runs on XCD b % 8), so "segment = b % nseg" would put ALL blocks of one pool family on the same XCDs (nseg = 2:
+// ProductTwoCoin on XCDs 0,2,4,6, GeometricMean on 1,3,5,7 -- half the chip does all the arithmetic).  There the 8 blocks
+// of one deal (one per XCD) share a segment, consecutive deals walk through a 32-entry pattern in which segment s appears
+// seg_w[s] times (its share of the launch's work: pools x cost per pool, so that all blocks finish together), and the
+// pattern is rotated by one every 32 deals (one pass over an XCD's 32 CUs), so every XCD -- and, as the dispatcher fills
+// CUs in order, every CU -- hosts all families.  Placement is only a performance assumption: any placement computes the
+// same result.  Small grids: block b -> segment b % nseg.
+template <bool MAT, int BLOCK, bool GBINS, int FASTK>
+__global__ __launch_bounds__(BLOCK) void sweep_multi(SweepLaunch)
+{
+    LaunchRef la = launch_args();
+    const BlockRec br = block_rec(la);
+    const CFMM_CONST_AS SweepDesc& d = *const_as(la.desc);
+    const CFMM_CONST_AS SegRec& sg = d.seg[br.seg];
+    switch (br.kind) {
+    case 0: sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br); break;
     case 1: // log-space forms only; geomean_exact routers are swept by per-segment launches
-        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(GeoMeanLogOps{sg.pools.g}, a, local, nblocks, bidx);
+        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br);
         break;
-    default:
-        sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(UniV3Ops{sg.pools.u}, a, local, nblocks, bidx);
-        break;
+    default: sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br); break;
     }
 }
+#undef CFMM_CONST_AS
 
 } // namespace cfmm

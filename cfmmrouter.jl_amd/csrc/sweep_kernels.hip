@@ -172,37 +172,33 @@ static hipError_t launch_family(int family, bool gbins, const LaunchCfg& c, bool
     return launch_k(kernel, dim3(c.grid), dim3(c.block), c.lds_bytes, s, c.ev_start, c.ev_stop, args);
 }
 
-hipError_t launch_multi(const MultiArgs& ma, const LaunchCfg& c, bool mat, hipStream_t s)
+hipError_t launch_multi(bool gbins, const SweepLaunch& la, const LaunchCfg& c, bool mat, hipStream_t s)
 {
-    void* args[] = {const_cast<MultiArgs*>(&ma)};
-    return launch_family(kFamMulti, ma.common.gflow != nullptr, c, mat, s, args);
+    void* args[] = {const_cast<SweepLaunch*>(&la)};
+    return launch_family(kFamMulti, gbins, c, mat, s, args);
 }
 
-// Ops: the kernel's first argument, built from the segment's pools (an Ops struct, or the N-coin pools themselves)
-template <class Ops, class Pools>
-static hipError_t launch_ops(int family, const Pools& p, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
+hipError_t launch_sweep(int kind, bool reference_order, bool heads, bool gbins, const SweepLaunch& la, const LaunchCfg& c, bool mat,
+                        hipStream_t s)
 {
-    Ops ops{p};
-    void* args[] = {&ops, const_cast<SweepArgs*>(&a)};
-    return launch_family(family, a.gflow != nullptr, c, mat, s, args);
-}
-
-hipError_t launch_sweep(int kind, const AnyPools& pools, const SweepArgs& a, const LaunchCfg& c, bool mat, hipStream_t s)
-{
-    if (a.m <= 0) return hipSuccess;
+    int family;
     switch (kind) {
-    case CFMM_KIND_PRODUCT: return launch_ops<ProductOps>(kFamProduct, pools.p, a, c, mat, s);
-    case CFMM_KIND_GEOMEAN:
-        return pools.g.reference_order ? launch_ops<GeoMeanOps>(kFamGeoMean, pools.g, a, c, mat, s)
-                                       : launch_ops<GeoMeanLogOps>(kFamGeoMeanLog, pools.g, a, c, mat, s);
-    case CFMM_KIND_UNIV3:
-        return pools.u.head && !a.gflow ? launch_ops<UniV3Ops>(kFamUniV3, pools.u, a, c, mat, s)
-                                        : launch_ops<UniV3OpsLean>(kFamUniV3Lean, pools.u, a, c, mat, s);
-    case CFMM_KIND_SOLIDLY: return launch_ops<SolidlyOps>(kFamSolidly, pools.p, a, c, mat, s);
-    case CFMM_KIND_WEIGHTED: return launch_ops<NCoinPools>(kFamWeighted, pools.n, a, c, mat, s);
-    case CFMM_KIND_CURVE: return launch_ops<NCoinPools>(kFamCurve, pools.n, a, c, mat, s);
+    case CFMM_KIND_PRODUCT: family = kFamProduct; break;
+    case CFMM_KIND_GEOMEAN: family = reference_order ? kFamGeoMean : kFamGeoMeanLog; break;
+    case CFMM_KIND_UNIV3: family = heads && !gbins ? kFamUniV3 : kFamUniV3Lean; break;
+    case CFMM_KIND_SOLIDLY: family = kFamSolidly; break;
     default: return hipErrorInvalidDeviceFunction;
     }
+    void* args[] = {const_cast<SweepLaunch*>(&la)};
+    return launch_family(family, gbins, c, mat, s, args);
+}
+
+hipError_t launch_ncoin(int kind, const NCoinPools& pools, const SweepArgs& a, bool gbins, const LaunchCfg& c, bool mat, hipStream_t s)
+{
+    if (a.m <= 0) return hipSuccess;
+    if (kind != CFMM_KIND_WEIGHTED && kind != CFMM_KIND_CURVE) return hipErrorInvalidDeviceFunction;
+    void* args[] = {const_cast<NCoinPools*>(&pools), const_cast<SweepArgs*>(&a)};
+    return launch_family(kind == CFMM_KIND_WEIGHTED ? kFamWeighted : kFamCurve, gbins, c, mat, s, args);
 }
 
 hipError_t launch_reduce(const double* partials, int rows, int n1, int pitch, double* out, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
