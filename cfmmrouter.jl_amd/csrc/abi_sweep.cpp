@@ -262,17 +262,18 @@ SweepLaunch launch_args(const cfmm_ctx* c, const Eval& ev, size_t gi)
     std::memset(&la, 0, sizeof la);
     la.desc = c->desc.off[gi] == kNoDesc ? nullptr : reinterpret_cast<const SweepDesc*>(c->desc.dev(c) + c->desc.off[gi]);
     la.v = ev.d_v;
+    la.n = c->n;
     la.reverse = c->opt_alternate != 0 ? (int)(c->sweep_count & 1) : 0;
-    la.arm_word = ev.arm.word;
-    la.arm_seq = ev.arm.seq;
-    la.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
+    la.tail.arm_word = ev.arm.word;
+    la.tail.arm_seq = ev.arm.seq;
+    la.tail.arm_timeout = std::min<long long>(std::max<long long>(c->opt_arm_timeout_ms, 1), 10000) * 100000ll;   // ms -> ticks of the 100 MHz wall clock, at most 10 s
     // sharded (cfmm_set_peers): a rank whose host is late by less than the peer timeout must not lose the evaluation --
     // the other ranks' fold + gather launches wait that long for its granules anyway, so waiting for the price vector
     // equally long turns a stalled host into a slow evaluation on every rank instead of a failed route on all of them
-    if (ev.sharded) la.arm_timeout = std::max<long long>(la.arm_timeout, c->peer_timeout_ticks);
+    if (ev.sharded) la.tail.arm_timeout = std::max<long long>(la.tail.arm_timeout, c->peer_timeout_ticks);
     if (ev.direct) {
-        la.direct_out = ev.d_out;
-        la.direct_host = ev.ho;
+        la.tail.direct_out = ev.d_out;
+        la.tail.direct_host = ev.ho;
         la.reverse = 0;   // two tiles at most, the whole market in one CU's L1: nothing for the alternation to reuse -- and every
                           // evaluation of such a market, fused or materialising, then returns the same bits at the same prices
     }
@@ -298,9 +299,9 @@ SweepArgs ncoin_args(const SweepDesc& d, const SweepLaunch& la, const Segment& s
     a.partials = d.partials;
     a.row_pitch = d.row_pitch;
     a.reverse = la.reverse;
-    a.arm_word = la.arm_word;
-    a.arm_seq = la.arm_seq;
-    a.arm_timeout = la.arm_timeout;
+    a.arm_word = la.tail.arm_word;
+    a.arm_seq = la.tail.arm_seq;
+    a.arm_timeout = la.tail.arm_timeout;
     a.nt_stores = d.nt_stores;
     return a;
 }

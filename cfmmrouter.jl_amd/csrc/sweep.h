@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace cfmm {
@@ -227,20 +228,29 @@ struct SweepDesc {
 };
 constexpr size_t kSweepDescHead = (sizeof(SweepDesc) + 127) / 128 * 128;
 inline size_t sweep_desc_bytes(int grid) { return kSweepDescHead + ((size_t)grid * sizeof(BlockRec) + 127) / 128 * 128; }
-// What differs between two launches of the same geometry: the kernels' one argument, inside the first 128 bytes of the
-// kernarg segment
-struct SweepLaunch {
-    const SweepDesc* desc;       // device
-    const double* v;             // [n] device
-    int reverse;                 // SweepArgs::reverse / arm_* / direct_out / direct_host; what the first tile's loads need (desc,
-                                 // reverse) in the first 64 bytes
+// What differs between two launches of the same geometry: the kernels' arguments, inside the first 128 bytes of the
+// kernarg segment.  The kernels take the leading scalars as four parameters of their own -- what gfx950 hands over in
+// SGPRs before the first instruction (kernarg preload: csrc/Makefile KFLAGS) -- and the tail as one by-value struct that
+// is read from the segment where it is first used.
+struct SweepTail {               // SweepArgs::arm_* / direct_out / direct_host
     const unsigned long long* arm_word;
     unsigned long long arm_seq;
     long long arm_timeout;
     double* direct_out;
     HostOut direct_host;
 };
-static_assert(sizeof(SweepLaunch) <= 128, "the per-launch arguments are one line of the kernarg segment");
+struct SweepLaunch {
+    const SweepDesc* desc;       // device
+    const double* v;             // [n] device
+    int reverse;                 // SweepArgs::reverse
+    int n;                       // n_tokens (== desc->n)
+    SweepTail tail;
+};
+// (the Makefile's KFLAGS preload five arguments: the folds' partials, rows, n1, pitch, out; of the sweeps' arguments the four
+// scalars -- a by-value struct is not preloaded)
+constexpr int kSweepScalars = 4;
+static_assert(offsetof(SweepLaunch, tail) == 24 && sizeof(SweepLaunch) <= 128,
+              "the per-launch arguments are one line of the kernarg segment, the preloaded ones its first 6 dwords");
 
 struct LaunchCfg {
     int block;                   // kMidBlock or kBigBlock

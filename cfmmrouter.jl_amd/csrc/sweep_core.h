@@ -106,8 +106,32 @@ __device__ __forceinline__ void report(const SweepArgs& a, unsigned long long bi
 // pre-armed launch that was cancelled or gave up waiting for its prices (then also kStageGaveUp); kStageFast when every
 // staged price lies in the window of the fast arithmetic.
 constexpr int kStageLive = 1, kStageFast = 2, kStageGaveUp = 4;
-template <int BLOCK, bool GBINS>
-__device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& L)
+// Prices first (sweep_kernel / sweep_multi): a lane's first kPricePre prices, v[tid], v[tid + BLOCK], requested at the
+// kernel's FIRST instruction from the preloaded v and n, before the block's record is read -- behind them come a reciprocal
+// and a binary64 logarithm per token and the barrier every wavefront waits at before its first pool, and the first tile's
+// pool data is there when that barrier is passed (profiles/sweep_entry_preload.txt).  The indices are clamped to n - 1, so
+// every lane loads a valid price and there is no branch in front of the loads; a lane uses only those with an index < n.
+// A pre-armed launch requests them too and does not use them: its v is written after the kernel may have started.  Its
+// own loads behind wait_armed are system-scope (sc0 sc1) loads of fine-grained memory, which are served by the memory
+// itself and not by a line an earlier plain load -- these requests, or the previous evaluation's staging -- left in a cache:
+// the assumption every pre-armed evaluation after the first has always made (the buffer is reused), not a new one.
+constexpr int kPricePre = 2;
+struct PricePre {
+    double p[kPricePre];
+};
+template <int BLOCK>
+__device__ __forceinline__ PricePre request_prices(const double* v, int n)
+{
+    PricePre r;
+#pragma unroll
+    for (int k = 0; k < kPricePre; ++k) {
+        const int j = (int)threadIdx.x + k * BLOCK;
+        r.p[k] = v[j < n ? j : n - 1];
+    }
+    return r;
+}
+template <int BLOCK, bool GBINS, bool PRE = false>
+__device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& L, const PricePre& pre = PricePre{})
 {
     if constexpr (GBINS) {
         __syncthreads();
@@ -131,9 +155,12 @@ __device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& 
         gave_up = L.flags[BLOCK / 64] < 0.0;
     }
     bool in_window = true;
-    for (int j = tid; j < a.n; j += BLOCK) {
+    for (int j = tid, k = 0; j < a.n; j += BLOCK, ++k) {
         // armed: the host wrote v through the PCIe BAR after this kernel may have started -- system-scope loads
-        const double vj = armed ? __hip_atomic_load(a.v + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : a.v[j];
+        double vj;
+        if (armed) vj = __hip_atomic_load(a.v + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else if (PRE && k < kPricePre) vj = k == 0 ? pre.p[0] : pre.p[1];   // requested at the kernel's first instruction
+        else vj = a.v[j];
         if (a.v_shift == 4) L.vy[j] = make_double2(vj, rcp_refined(vj));
         else reinterpret_cast<double*>(L.vy)[j] = vj;
         in_window = in_window && in_fast_window(vj);
@@ -331,11 +358,11 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
 constexpr int kArithFull = 0, kArithFast = 1, kArithAuto = 2;
 template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
 __device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a, const SweepLds& L, const typename Ops::Raw& cur,
-                                              int64_t i, int64_t step, int64_t left, bool& poison, bool& live)
+                                              int64_t i, int64_t step, int64_t left, bool& poison, bool& live, const PricePre& pre)
 {
     static_assert(!(GBINS && FASTK != kArithFull), "large-market mode runs on the compiler's sequences");
     double acc = 0.0;
-    const int staged = stage_prices<BLOCK, GBINS>(a, L);
+    const int staged = stage_prices<BLOCK, GBINS, !GBINS>(a, L, pre);
     poison = (staged & kStageLive) == 0;              // a pre-armed launch that is not needed (or gave up)
     live = !poison || (staged & kStageGaveUp) != 0;   // false: CANCELLED by the host (a launch that gave up waiting still reports NaN)
     if (staged & kStageGaveUp) report(a, kFlagGaveUp);
@@ -415,35 +442,58 @@ __device__ __forceinline__ void finish_row(const SweepArgs& a, const SweepLds& L
     }
 }
 
-// The kernels' entry.  Two dependent reads stand between a block and its first pool load: the per-launch arguments (one
-// line of the kernarg segment, the only memory of the entry that is new -- cache-cold -- for every launch), then the
-// block's record and its segment's, from the launch's descriptor in device memory (sweep.h SweepDesc), which nothing
-// rewrites between launches.  The descriptor is read through the CONSTANT address space: it does not change while a
-// kernel runs, so every one of its fields is a scalar load that the compiler may place where the field is first used.
+// The kernels' entry.  The launch's leading arguments (the descriptor, v, the direction, n: sweep.h SweepLaunch) are kernel
+// parameters of their own and arrive in SGPRs (kernarg preload; a firmware that does not preload runs the compatibility
+// prologue, which loads them from the kernarg segment -- the only memory of the entry that is new, cache-cold, for every
+// launch).  With them a lane requests its first prices at once (request_prices), and a block its record -- and, in
+// sweep_kernel, segment 0's pool streams in the same batch; sweep_multi reads its segment's behind the record -- from the
+// launch's descriptor in device memory (sweep.h SweepDesc), which nothing rewrites between launches.  The descriptor is read
+// through the CONSTANT address space: it does not change while a kernel runs, so every one of its fields is a scalar load
+// that the compiler may place where the field is first used.
+// (A table with one 128-byte line of pool streams per block, which took sweep_multi's second dependent read away, was built
+// and measured: the step was 0.1 us SLOWER with it on the benchmark's fused market, in two sessions -- a block's own line is a
+// cold miss per block where the segment records are lines its neighbours have just fetched.  profiles/sweep_entry_preload.txt.)
 #define CFMM_CONST_AS __attribute__((address_space(4)))
 template <class T>
 __device__ __forceinline__ const CFMM_CONST_AS T* const_as(const T* p)
 {
     return (const CFMM_CONST_AS T*)(reinterpret_cast<uintptr_t>(p));
 }
-// The kernels' one argument, read where it lies: in the kernarg segment, through the constant address space.  (A by-value
-// kernel parameter is copied out of the segment at the kernel's FIRST instruction, all 72 bytes of it, and the words only the
-// epilogue needs -- arm_*, direct_* -- then sit in SGPRs, or spilled to VGPR lanes, in front of the first pool load.)
+// The preloaded arguments of a launch, as the kernels pass them on
+struct LaunchHead {
+    const SweepDesc* desc;
+    const double* v;
+    int reverse;
+    int n;
+};
+// The tail of the arguments, read where it lies: in the kernarg segment, through the constant address space.  (A by-value
+// kernel parameter is copied out of the segment at the kernel's FIRST instruction, and the words only the epilogue needs
+// -- arm_*, direct_* -- then sit in SGPRs, or spilled to VGPR lanes, in front of the first pool load.)
+// The same goes for v and n once the first prices are requested: what is used after that (v: prices beyond the requested
+// ones, pre-armed and large-market launches; n: staging and the row) is read again -- v from the segment, n from the
+// descriptor -- so the preloaded copies do not stay in SGPRs across the tile loop.
+// The kernels' parameter list (desc, v, reverse, n, SweepTail) IS a SweepLaunch field by field: the kernarg segment
+// lays parameters out by size and alignment as a struct lays out its members, and the launchers pass the fields' addresses.
+static_assert(offsetof(SweepLaunch, desc) == 0 && offsetof(SweepLaunch, v) == 8 && offsetof(SweepLaunch, reverse) == 16 &&
+                  offsetof(SweepLaunch, n) == 20 && offsetof(SweepLaunch, tail) == 24 && alignof(SweepTail) == 8,
+              "sweep_kernel / sweep_multi (pointer, pointer, int, int, SweepTail) read the segment as a SweepLaunch");
 typedef const CFMM_CONST_AS SweepLaunch& LaunchRef;
 __device__ __forceinline__ LaunchRef launch_args()
 {
     return *(const CFMM_CONST_AS SweepLaunch*)__builtin_amdgcn_kernarg_segment_ptr();
 }
-__device__ __forceinline__ BlockRec block_rec(LaunchRef la)
+__device__ __forceinline__ BlockRec block_rec(const SweepDesc* desc)
 {
     const CFMM_CONST_AS BlockRec* recs =
-        (const CFMM_CONST_AS BlockRec*)(reinterpret_cast<uintptr_t>(la.desc) + kSweepDescHead);
+        (const CFMM_CONST_AS BlockRec*)(reinterpret_cast<uintptr_t>(desc) + kSweepDescHead);
     const CFMM_CONST_AS BlockRec& r = recs[blockIdx.x];
     return BlockRec{r.first, r.stride, r.full, r.tail, r.row, r.seg, r.kind};
 }
 // The SweepArgs of this block: the launch's own fields, the descriptor's, its segment's
-__device__ __forceinline__ SweepArgs block_args(LaunchRef la, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg)
+__device__ __forceinline__ SweepArgs block_args(const LaunchHead& h, LaunchRef la, const CFMM_CONST_AS SweepDesc& d,
+                                                const CFMM_CONST_AS SegRec& sg)
 {
+    const CFMM_CONST_AS SweepTail& t = la.tail;
     SweepArgs a;
     a.v = la.v;
     a.n = d.n;
@@ -462,65 +512,65 @@ __device__ __forceinline__ SweepArgs block_args(LaunchRef la, const CFMM_CONST_A
     a.partials = d.partials;
     a.row_pitch = d.row_pitch;
     a.gflow = sg.gflow;
-    a.reverse = la.reverse;
-    a.arm_word = la.arm_word;
-    a.arm_seq = la.arm_seq;
-    a.arm_timeout = la.arm_timeout;
+    a.reverse = h.reverse;
+    a.arm_word = t.arm_word;
+    a.arm_seq = t.arm_seq;
+    a.arm_timeout = t.arm_timeout;
     a.nt_stores = d.nt_stores;
     a.direct = d.direct;
-    a.direct_out = la.direct_out;
-    a.direct_host = HostOut{la.direct_host.gran, la.direct_host.tag};
+    a.direct_out = t.direct_out;
+    a.direct_host = HostOut{t.direct_host.gran, t.direct_host.tag};
     return a;
 }
 // a family's view of a segment record's pools
-template <class Pools> __device__ __forceinline__ Pools pools_of(const CFMM_CONST_AS AnyPools& u);
-template <> __device__ __forceinline__ ProductPools pools_of<ProductPools>(const CFMM_CONST_AS AnyPools& u)
+__device__ __forceinline__ ProductPools pools_of(const CFMM_CONST_AS AnyPools& u, const ProductPools*)
 {
     return ProductPools{u.p.R, u.p.gamma, u.p.Ai, u.p.pk, u.p.gbase};
 }
-template <> __device__ __forceinline__ GeoMeanPools pools_of<GeoMeanPools>(const CFMM_CONST_AS AnyPools& u)
+__device__ __forceinline__ GeoMeanPools pools_of(const CFMM_CONST_AS AnyPools& u, const GeoMeanPools*)
 {
     return GeoMeanPools{u.g.R, u.g.w, u.g.gamma, u.g.Ai, u.g.eta, u.g.Q, u.g.reference_order, u.g.pk, u.g.gbase};
 }
-template <> __device__ __forceinline__ UniV3Pools pools_of<UniV3Pools>(const CFMM_CONST_AS AnyPools& u)
+__device__ __forceinline__ UniV3Pools pools_of(const CFMM_CONST_AS AnyPools& u, const UniV3Pools*)
 {
     return UniV3Pools{u.u.pg, u.u.Ai, u.u.cur_a, u.u.cur_b, u.u.cur_c, u.u.curR, u.u.walk, u.u.ticks, u.u.thr, u.u.head,
                       u.u.has_walk, u.u.cp, u.u.pk, u.u.gbase};
 }
-
 // One block's share of ONE segment (its BlockRec); its partial row goes to partials[br.row].
 // The order is the point: the first tile's pool state is requested from the block record, the segment's pool streams and
 // the launch's direction ALONE -- lane t takes pools first + t + k·stride, k < full + (t < tail): the host did the division
 // -- and only then is everything else read (block_args: the LDS geometry, the trade and row buffers, the fee table), while
 // those loads are in flight.
 template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
-__device__ __forceinline__ void sweep_body(LaunchRef la, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg,
-                                           const BlockRec& br)
+__device__ __forceinline__ void sweep_body(const LaunchHead& h, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg,
+                                           const BlockRec& br, const PricePre& pre)
 {
-    const Ops ops{pools_of<decltype(Ops::p)>(sg.pools)};
+    const Ops ops{pools_of(sg.pools, (const decltype(Ops::p)*)nullptr)};
     const int64_t stride = br.stride;
     const int64_t i0 = br.first + threadIdx.x;
     const int64_t left = br.full + ((int)threadIdx.x < br.tail ? 1 : 0);      // tiles of this lane
-    const bool reverse = la.reverse != 0;
+    const bool reverse = h.reverse != 0;
     const int64_t step = reverse ? -stride : stride;
     const int64_t i = reverse ? i0 + (left - 1) * stride : i0;
     typename Ops::Raw cur = {};
     if (left > 0) cur = ops.template load<GBINS>(i);
-    const SweepArgs a = block_args(la, d, sg);
+    const SweepArgs a = block_args(h, launch_args(), d, sg);
     const SweepLds L = carve_lds<BLOCK, GBINS>(a);
     bool poison, live;
-    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, cur, i, step, left, poison, live);
+    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, cur, i, step, left, poison, live, pre);
     finish_row<BLOCK, GBINS>(a, L, acc, br.row, poison, live);
 }
 
-// One segment's own launch: segment 0 of the descriptor
+// One segment's own launch: segment 0 of the descriptor, whose pool streams are requested together with the block's record
 template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK>
-__global__ __launch_bounds__(BLOCK) void sweep_kernel(SweepLaunch)
+__global__ __launch_bounds__(BLOCK) void sweep_kernel(const SweepDesc* desc, const double* v, int reverse, int n, SweepTail)
 {
-    LaunchRef la = launch_args();
-    const BlockRec br = block_rec(la);
-    const CFMM_CONST_AS SweepDesc& d = *const_as(la.desc);
-    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(la, d, d.seg[0], br);
+    const LaunchHead h{desc, v, reverse, n};
+    PricePre pre = {};
+    if constexpr (!GBINS) pre = request_prices<BLOCK>(v, n);
+    const BlockRec br = block_rec(desc);
+    const CFMM_CONST_AS SweepDesc& d = *const_as(desc);
+    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(h, d, d.seg[0], br, pre);
 }
 
 // Several segments (pool families) in ONE launch, so HBM-bound ProductTwoCoin blocks and ALU-bound GeometricMean /
@@ -535,18 +585,20 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(SweepLaunch)
 // CUs in order, every CU -- hosts all families.  Placement is only a performance assumption: any placement computes the
 // same result.  Small grids: block b -> segment b % nseg.
 template <bool MAT, int BLOCK, bool GBINS, int FASTK>
-__global__ __launch_bounds__(BLOCK) void sweep_multi(SweepLaunch)
+__global__ __launch_bounds__(BLOCK) void sweep_multi(const SweepDesc* desc, const double* v, int reverse, int n, SweepTail)
 {
-    LaunchRef la = launch_args();
-    const BlockRec br = block_rec(la);
-    const CFMM_CONST_AS SweepDesc& d = *const_as(la.desc);
+    const LaunchHead h{desc, v, reverse, n};
+    PricePre pre = {};
+    if constexpr (!GBINS) pre = request_prices<BLOCK>(v, n);
+    const BlockRec br = block_rec(desc);
+    const CFMM_CONST_AS SweepDesc& d = *const_as(desc);
     const CFMM_CONST_AS SegRec& sg = d.seg[br.seg];
     switch (br.kind) {
-    case 0: sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br); break;
+    case 0: sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre); break;
     case 1: // log-space forms only; geomean_exact routers are swept by per-segment launches
-        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br);
+        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre);
         break;
-    default: sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(la, d, sg, br); break;
+    default: sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre); break;
     }
 }
 #undef CFMM_CONST_AS

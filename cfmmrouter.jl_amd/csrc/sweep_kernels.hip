@@ -172,10 +172,17 @@ static hipError_t launch_family(int family, bool gbins, const LaunchCfg& c, bool
     return launch_k(kernel, dim3(c.grid), dim3(c.block), c.lds_bytes, s, c.ev_start, c.ev_stop, args);
 }
 
+// the kernels' parameters: SweepLaunch's four leading scalars, then its tail
+struct SweepParams {
+    SweepLaunch la;
+    void* args[kSweepScalars + 1];
+    explicit SweepParams(const SweepLaunch& l) : la(l), args{&la.desc, &la.v, &la.reverse, &la.n, &la.tail} {}
+};
+
 hipError_t launch_multi(bool gbins, const SweepLaunch& la, const LaunchCfg& c, bool mat, hipStream_t s)
 {
-    void* args[] = {const_cast<SweepLaunch*>(&la)};
-    return launch_family(kFamMulti, gbins, c, mat, s, args);
+    SweepParams p(la);
+    return launch_family(kFamMulti, gbins, c, mat, s, p.args);
 }
 
 hipError_t launch_sweep(int kind, bool reference_order, bool heads, bool gbins, const SweepLaunch& la, const LaunchCfg& c, bool mat,
@@ -189,8 +196,8 @@ hipError_t launch_sweep(int kind, bool reference_order, bool heads, bool gbins, 
     case CFMM_KIND_SOLIDLY: family = kFamSolidly; break;
     default: return hipErrorInvalidDeviceFunction;
     }
-    void* args[] = {const_cast<SweepLaunch*>(&la)};
-    return launch_family(family, gbins, c, mat, s, args);
+    SweepParams p(la);
+    return launch_family(family, gbins, c, mat, s, p.args);
 }
 
 hipError_t launch_ncoin(int kind, const NCoinPools& pools, const SweepArgs& a, bool gbins, const LaunchCfg& c, bool mat, hipStream_t s)

@@ -16,8 +16,11 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc", "sweep_kernels.hip")
 tmp = tempfile.mkdtemp()
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-save-temps",
-       "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", os.path.join(tmp, "k.o")]
+# the kernels' own flags (kernarg preload): what the Makefile's KFLAGS default says, so that the figures are the shipped build's
+with open(os.path.join(os.path.dirname(SRC), "Makefile"), encoding="utf-8") as f:
+    KFLAGS = re.search(r"^KFLAGS\s*\?=(.*)$", f.read(), re.M).group(1).split()
+cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"] + KFLAGS + [
+       "-save-temps", "-Rpass-analysis=kernel-resource-usage", "-c", SRC, "-o", os.path.join(tmp, "k.o")]
 r = subprocess.run(cmd, cwd=tmp, capture_output=True, text=True)
 blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
 asm = open(os.path.join(tmp, "sweep_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
@@ -38,7 +41,7 @@ def digest_report():
         if cur is not None and re.match(r"\.Lfunc_end\d+:", l):
             cur = None
 
-    print("# hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -save-temps -c csrc/sweep_kernels.hip")
+    print("# hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off %s -save-temps -c csrc/sweep_kernels.hip" % " ".join(KFLAGS))
     print(f"# {len(kernels)} kernels in the code object")
     for sym in sorted(kernels):
         if sym not in sha:
@@ -51,7 +54,7 @@ if "--digest" in sys.argv[1:]:
     digest_report()
     sys.exit(0)
 
-print("# hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -Rpass-analysis=kernel-resource-usage csrc/sweep_kernels.hip")
+print("# hipcc --offload-arch=gfx950 -O3 -ffp-contract=off %s -Rpass-analysis=kernel-resource-usage csrc/sweep_kernels.hip" % " ".join(KFLAGS))
 print(f"# {len(blocks)} kernels in the code object")
 print(f"{'VGPR':>5} {'SGPR':>5} {'scratch':>8} {'LDS(static)':>12} {'waves/SIMD':>11}  kernel")
 rows = []

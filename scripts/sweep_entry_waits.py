@@ -11,6 +11,11 @@ global_load_dword* in program text; the fused kernel's text begins with one fami
   spills    v_writelane (SGPRs parked in VGPR lanes),
   divs      reciprocal seeds of the integer-division expansions (v_rcp_iflag_f32, v_rcp_f32),
   instr     all instructions.
+A translation unit built with kernarg preload (csrc/Makefile KFLAGS) gives every kernel a 256-byte compatibility prologue --
+the loads of the preloaded arguments and one wait, for a firmware that does not preload, closed by `s_branch` and
+`.p2align 8`; a firmware that preloads enters behind it.  Counting starts behind that prologue (column `pro`: 1 = the kernel
+has one), so the table says what a preloading firmware runs.  Vector loads in front of the first wait are the price requests
+of the kernel's first instructions (sweep_core.h request_prices; column `prices`), not pool loads: counting goes on behind them.
 """
 import re
 import sys
@@ -34,13 +39,28 @@ def kernels(path):
         yield name, body
 
 
+def behind_prologue(body):
+    """the body behind the kernarg-preload prologue, if it has one: [loads, s_waitcnt, s_branch, .p2align 8] at the very top"""
+    code = [k for k, ins in enumerate(body) if ins and not ins.startswith(";") and not ins.endswith(":")]
+    for pos, k in enumerate(code[:24]):
+        if body[k].split()[0] == "s_branch" and pos + 1 < len(code) and body[code[pos + 1]].startswith(".p2align\t8"):
+            if all(body[j].split()[0].startswith(("s_load_dword", "s_waitcnt", "s_nop")) for j in code[:pos]):
+                return body[code[pos + 1] + 1:], 1
+    return body, 0
+
+
 def entry(body):
-    c = dict(waits=0, arg_vmem=0, spills=0, divs=0, instr=0)
+    body, pro = behind_prologue(body)
+    c = dict(waits=0, arg_vmem=0, spills=0, divs=0, instr=0, pro=pro, prices=0)
     for ins in body:
         if not ins or ins.startswith((";", ".")) or ins.endswith(":"):
             continue
         op = ins.split()[0]
         if re.match(r"global_load_dword", op):
+            if c["waits"] == 0 and pro:
+                c["prices"] += 1       # requested before anything was waited for: a lane's first prices, not pool state
+                c["instr"] += 1
+                continue
             return c
         c["instr"] += 1
         if op == "s_waitcnt" and ("lgkmcnt" in ins or "vmcnt" in ins):
@@ -55,7 +75,7 @@ def entry(body):
 
 
 def demangled(name):
-    m = re.match(r"_ZN4cfmm(\d+)(sweep_kernel|sweep_multi)I(.*)EEv", name)
+    m = re.match(r"_ZN4cfmm(\d+)(sweep_kernel|sweep_multi)I(.*?)EEv", name)
     return (m.group(2) + "<" + m.group(3) + ">") if m else name
 
 
@@ -67,10 +87,10 @@ def main():
         c = entry(body)
         if c:
             rows.append((demangled(name), c))
-    print("%-64s %5s %8s %6s %4s %5s" % ("kernel (mangled template arguments)", "waits", "arg_vmem", "spills", "divs", "instr"))
+    print("%-64s %5s %8s %6s %4s %5s %3s %6s" % ("kernel (mangled template arguments)", "waits", "arg_vmem", "spills", "divs", "instr", "pro", "prices"))
     for n, c in sorted(rows):
-        print("%-64s %5d %8d %6d %4d %5d" % (n[:64], c["waits"], c["arg_vmem"], c["spills"], c["divs"], c["instr"]))
-    for k in ("waits", "spills", "divs", "instr"):
+        print("%-64s %5d %8d %6d %4d %5d %3d %6d" % (n[:64], c["waits"], c["arg_vmem"], c["spills"], c["divs"], c["instr"], c["pro"], c["prices"]))
+    for k in ("waits", "spills", "divs", "instr", "pro", "prices"):
         v = [c[k] for _, c in rows]
         print("%s: min %d max %d over %d kernels" % (k, min(v), max(v), len(v)))
 
