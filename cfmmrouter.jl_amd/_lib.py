@@ -131,6 +131,8 @@ def lib():
     L.cfmm_pools_set_curve.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _f64p, _f64p]
     L.cfmm_pools_set_prices.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p]
     L.cfmm_pools_set_ticks.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _i64p, _f64p, _f64p]
+    L.cfmm_quote.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
+    L.cfmm_quote_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -473,6 +475,36 @@ class Context:
         if lt.size != off[-1] or lq.size != off[-1]:
             raise ArgumentError("tick arrays must have tick_off[-1] entries")
         self._check(self._L.cfmm_pools_set_ticks(self._h, int(seg), idx.size, ptr(idx), ptr(p), ptr(off), ptr(lt), ptr(lq)))
+
+    # -- exact-input swap quotes (cfmm_quote): read-only, on the pools as they stand on the device ---------------------
+    def quote(self, seg: int, amount_in, coin_in, coin_out=None, idx=None):
+        """amount_out [count] of tendering amount_in [count] of coin_in (positions in the pool's own coin order; a scalar
+        serves every query) to rows idx of segment `seg` (None: rows 0 .. count-1; any order, repeats allowed).
+        coin_out=None means 1 - coin_in on two-coin and UniV3 segments; weighted / Curve segments need it.  Everything is
+        checked before anything runs (ArgumentError names the query)."""
+        amt = f64(amount_in).reshape(-1)
+        n = amt.size
+        bcast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32).reshape(-1) if np.ndim(a) else
+                                                               np.int32(a), (n,)), dtype=np.int32)
+        try:
+            ci = bcast(coin_in)
+            co = None if coin_out is None else bcast(coin_out)
+        except ValueError:
+            raise ArgumentError("coin_in and coin_out must be scalars or have one entry per amount") from None
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if ix is not None and ix.size != n:
+            raise ArgumentError("idx must have one entry per amount")
+        out = np.empty(n)
+        self._check(self._L.cfmm_quote(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out)))
+        return out
+
+    def quote_dev(self, seg: int, count: int, d_amount_in: int, d_coin_in: int, d_amount_out: int, d_coin_out: int = 0,
+                  d_idx: int = 0):
+        """cfmm_quote_dev on device addresses (float64 amounts, int32 coins, int64 idx; 0 = NULL): asynchronous on the
+        context's stream, unchecked -- a bad query gets NaN, nothing is read out of bounds."""
+        self._check(self._L.cfmm_quote_dev(self._h, int(seg), int(count), C.c_void_p(d_idx or None), C.c_void_p(d_coin_in or None),
+                                           C.c_void_p(d_coin_out or None), C.c_void_p(d_amount_in or None),
+                                           C.c_void_p(d_amount_out or None)))
 
     def set_peers(self, peer_ptrs, world: int, rank: int, seq: int):
         """Sharded operation: every host-pointer sweep of this context ends with the one-shot peer

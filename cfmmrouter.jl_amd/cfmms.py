@@ -562,6 +562,44 @@ def find_arb_(Δ, Λ, cfmm, v, device=0):
     return None
 
 
+def forward_trade(Δ, cfmm, coin_out=None, device=0):
+    """forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449, there for UniV3 only; here for every device kind.
+
+    Δ (length len(cfmm.Ai)) has exactly one positive entry: the amount tendered, at the position of its coin.  Returns the
+    amount of the other coin -- of coin `coin_out` (0-based position; required on pools of more than two coins) -- that
+    comes out, fee on the input: the largest λ with φ(R + γΔ − λ·e_out) = φ(R).  Δ == 0 returns 0.0 (:440-442).  One
+    pool through the device (cfmm_quote), the way find_arb_(Δ, Λ, cfmm, v) works."""
+    from ._lib import Context
+
+    if not hasattr(cfmm, "kind") or cfmm.kind not in KINDS:
+        raise ArgumentError(f"{type(cfmm).__name__} has no device quote")
+    n = len(cfmm.Ai)
+    Δ = np.asarray(Δ, dtype=np.float64).reshape(-1)
+    if Δ.size != n:
+        raise ArgumentError(f"Δ must have {n} entries")
+    if not np.all(np.isfinite(Δ)) or np.any(Δ < 0):
+        raise ArgumentError("Δ must be finite and >= 0")
+    pos = np.flatnonzero(Δ > 0)
+    if pos.size > 1:
+        raise ArgumentError("Δ must have exactly one positive entry (one coin in)")
+    if coin_out is None and n > 2:
+        raise ArgumentError(f"coin_out= is required on a pool of {n} coins")
+    if coin_out is not None and not 0 <= int(coin_out) < n:
+        raise ArgumentError(f"coin_out {coin_out} out of range 0:{n - 1}")
+    if pos.size == 0:
+        return 0.0
+    cin = int(pos[0])
+    if coin_out is not None and int(coin_out) == cin:
+        raise ArgumentError("coin_out is the tendered coin")
+    ctx = Context(n, device)
+    try:
+        _upload(ctx, PoolBatch.from_pools(cfmm.kind, [_with_local_idx(cfmm)]))
+        out = ctx.quote(0, [Δ[cin]], cin, None if coin_out is None else int(coin_out))
+    finally:
+        ctx.close()
+    return float(out[0])
+
+
 def _with_local_idx(c):
     """the pool with token indices 1..n (a one-pool market)"""
     K = KINDS[c.kind]

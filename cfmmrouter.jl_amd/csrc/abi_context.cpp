@@ -327,6 +327,10 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
         *value = c->shards.empty() ? c->upd.compact_ns : c->shards[0]->upd.compact_ns;
         return CFMM_OK;
     }
+    // read-only, cfmm_quote / cfmm_quote_dev: the span of the latest call's kernel timed under "time_kernels".  A parent
+    // reports the longest span among the shards its latest call touched (abi_quote.cpp multi_quote).  After cfmm_quote_dev
+    // the span is not known until the kernel has run: the read waits for it and stores it, the one thing a getter changes
+    if (key && !std::strcmp(key, "quote_ns")) return quote_ns(const_cast<cfmm_ctx*>(c), value);
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
     // option "time_kernels" (a parent reports its first shard's)
     if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }

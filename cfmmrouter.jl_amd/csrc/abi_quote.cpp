@@ -1,0 +1,230 @@
+// abi_quote.cpp -- cfmm_quote / cfmm_quote_dev: exact-input swap quotes of one segment's pools as they stand on the device
+// (forward_trade, src/cfmms.jl:398-449, generalised to every kind; the forms: quote_pool.h, the kernel: quote_kernels.h).
+// Read-only: the pool streams are the segment's own arrays, the only memory of the feature is QuoteScratch (ctx.h), which is
+// proportional to the queries of a call and never to the pools.
+#include "ctx.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace cfmm;
+
+namespace {
+
+// the kernel's view of segment `s` for `count` queries; the query arrays are filled in by the caller
+hipError_t launch_for(const cfmm_ctx* c, const Segment& s, const QuoteArgs& q, hipEvent_t e0, hipEvent_t e1)
+{
+    QuoteArgs a = q;
+    a.m = s.m;
+    a.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
+    a.R = s.R.get();
+    a.w = s.w.get();
+    a.gamma = s.gamma.get();
+    UniV3Pools u;
+    NCoinPools n;
+    std::memset(&u, 0, sizeof u);
+    std::memset(&n, 0, sizeof n);
+    if (s.kind == CFMM_KIND_UNIV3) {
+        const UniV3State& st = s.u;
+        u.pg = st.pg.get();
+        u.cur_a = st.cur_a.get();
+        u.cur_b = st.cur_b.get();
+        u.cur_c = st.cur_c.get();
+        u.curR = st.curR.get();
+        u.walk = st.walk.get();
+        u.ticks = st.ticks.get();
+    } else if (ragged_kind(s.kind)) {
+        n.R = s.nc.R.get();
+        n.q = s.nc.q.get();
+        n.glg = s.nc.glg.get();
+        n.par = s.nc.par.get();
+        n.n_coins = s.n_coins;
+    }
+    return launch_quote(s.kind, a, u, n, c->stream, e0, e1);
+}
+
+int check_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t nseg)
+{
+    if (seg < 0 || seg >= nseg) return fail(c, CFMM_ERR_INVALID_ARG, "%s: segment out of range", who);
+    if (count < 0) return fail(c, CFMM_ERR_INVALID_ARG, "%s: count must be >= 0", who);
+    return CFMM_OK;
+}
+
+// every query of a host-pointer call, before anything is enqueued
+int check_queries(cfmm_ctx* c, int kind, int64_t m, int nc, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                  const int32_t* coin_out, const double* amount_in, const double* amount_out)
+{
+    if (count > 0 && (!coin_in || !amount_in || !amount_out)) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: null query array");
+    if (count > 0 && !coin_out && ragged_kind(kind))
+        return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: coin_out is required on a %s segment (query 0)", kind_info(kind).name);
+    for (int64_t q = 0; q < count; ++q) {
+        const int64_t row = idx ? idx[q] : q;
+        if (row < 0 || row >= m)
+            return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: row %lld out of range (segment has %lld pools)",
+                        (long long)q, (long long)row, (long long)m);
+        const int ci = coin_in[q], co = coin_out ? coin_out[q] : 1 - ci;
+        if (ci < 0 || ci >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_in %d out of range (pool has %d coins)", (long long)q, ci, nc);
+        if (co < 0 || co >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_out %d out of range (pool has %d coins)", (long long)q, co, nc);
+        if (ci == co) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_in and coin_out are both %d", (long long)q, ci);
+        if (!(amount_in[q] >= 0.0) || !std::isfinite(amount_in[q]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: amount_in must be finite and >= 0", (long long)q);
+    }
+    return CFMM_OK;
+}
+
+// A parent: the queries go to the shards that hold their rows (shard_range: contiguous blocks in device order) and the
+// answers return in query order, as cfmm_select_trades handles its rows.  Everything was checked by the caller.  One pass
+// buckets the queries by shard (a binary search on the blocks' ends per query), one call per shard that got any.
+int multi_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+                const double* amount_in, double* amount_out)
+{
+    const int64_t m = c->psegs[(size_t)seg].m;
+    const int nd = (int)c->shards.size();
+    std::vector<int64_t> first((size_t)nd), end((size_t)nd);
+    for (int d = 0; d < nd; ++d) shard_range(m, d, nd, first[(size_t)d], end[(size_t)d]);
+    struct Bucket {
+        std::vector<int64_t> where, rows;
+        std::vector<int32_t> ci, co;
+        std::vector<double> amt;
+    };
+    std::vector<Bucket> buckets((size_t)nd);
+    for (int64_t q = 0; q < count; ++q) {
+        const int64_t row = idx ? idx[q] : q;
+        const size_t d = (size_t)(std::upper_bound(end.begin(), end.end(), row) - end.begin());   // first shard whose end > row
+        Bucket& bk = buckets[d];
+        bk.where.push_back(q);
+        bk.rows.push_back(row - first[d]);
+        bk.ci.push_back(coin_in[q]);
+        if (coin_out) bk.co.push_back(coin_out[q]);
+        bk.amt.push_back(amount_in[q]);
+    }
+    std::vector<double> out;
+    int64_t ns = 0;
+    for (int d = 0; d < nd; ++d) {
+        const Bucket& bk = buckets[(size_t)d];
+        if (bk.where.empty()) continue;
+        out.resize(bk.where.size());
+        cfmm_ctx* child = c->shards[(size_t)d];
+        const int rc = cfmm_quote(child, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
+                                  coin_out ? bk.co.data() : nullptr, bk.amt.data(), out.data());
+        if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s", d, child->err.c_str());
+        for (size_t j = 0; j < bk.where.size(); ++j) amount_out[bk.where[j]] = out[j];
+        if (child->opt_time_kernels != 0) ns = std::max(ns, child->quote.ns);
+    }
+    c->quote.ns = ns;   // "quote_ns" of a parent: the longest kernel span among the shards THIS call touched
+    return CFMM_OK;
+}
+
+} // namespace
+
+// Pinned staging: [count] 8-byte words per column -- idx, amounts, {coin_in, coin_out} as two int32 columns packed into
+// one, and the answers -- copied to / from the scratch's device arrays in stream order; one synchronisation.
+int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+               const double* amount_in, double* amount_out)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    const bool parent = !c->shards.empty();
+    int rc = check_seg(c, "cfmm_quote", seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
+    if (rc != CFMM_OK) return rc;
+    const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
+    const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
+    const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
+    if ((rc = check_queries(c, kind, m, nc, count, idx, coin_in, coin_out, amount_in, amount_out)) != CFMM_OK) return rc;
+    if (count == 0) return CFMM_OK;
+    if (parent) return multi_quote(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out);
+
+    const Segment& s = c->segs[(size_t)seg];
+    HIP_TRY(c, hipSetDevice(c->device));
+    QuoteScratch& sc = c->quote;
+    const size_t n = (size_t)count;
+    const size_t ncol = 3 + (idx ? 1 : 0);                 // amounts, coins, answers (+ idx)
+    if ((rc = sc.stage.grow(c, ncol * n, false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) ||
+        (rc = sc.out.grow(c, n)) || (idx && (rc = sc.idx.grow(c, n))))
+        return rc;
+    const bool timed = c->opt_time_kernels != 0;
+    for (int k = 0; k < 2 && timed; ++k)
+        if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
+    unsigned long long* st = sc.stage.host();
+    double* h_amt = reinterpret_cast<double*>(st);
+    int32_t* h_coins = reinterpret_cast<int32_t*>(st + n);   // [count] coin_in, then [count] coin_out
+    double* h_out = reinterpret_cast<double*>(st + 2 * n);
+    long long* h_idx = reinterpret_cast<long long*>(st + 3 * n);
+    std::memcpy(h_amt, amount_in, n * sizeof(double));
+    std::memcpy(h_coins, coin_in, n * sizeof(int32_t));
+    if (coin_out) std::memcpy(h_coins + n, coin_out, n * sizeof(int32_t));
+    if (idx) std::memcpy(h_idx, idx, n * sizeof(long long));
+    HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.coins.get(), h_coins, (coin_out ? 2 : 1) * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (idx) HIP_TRY(c, hipMemcpyAsync(sc.idx.get(), h_idx, n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    QuoteArgs a{};
+    a.count = count;
+    a.idx = idx ? sc.idx.get() : nullptr;
+    a.coin_in = sc.coins.get();
+    a.coin_out = coin_out ? sc.coins.get() + n : nullptr;
+    a.amount_in = sc.amt.get();
+    a.amount_out = sc.out.get();
+    const hipError_t e = launch_for(c, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
+    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote launch failed: %s", hipGetErrorString(e));
+    HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (timed) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[0].get(), sc.ev[1].get()));
+        sc.ns = (int64_t)((double)ms * 1e6);
+        sc.dev_timed = false;
+    }
+    std::memcpy(amount_out, h_out, n * sizeof(double));
+    return CFMM_OK;
+}
+
+int cfmm_quote_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+                   const int32_t* d_coin_out, const double* d_amount_in, double* d_amount_out)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    CFMM_SINGLE_ONLY(c, "cfmm_quote_dev");
+    int rc = check_seg(c, "cfmm_quote_dev", seg, count, (int64_t)c->segs.size());
+    if (rc != CFMM_OK) return rc;
+    if (count == 0) return CFMM_OK;
+    const Segment& s = c->segs[(size_t)seg];
+    if (!d_coin_in || !d_amount_in || !d_amount_out) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: null query array");
+    if (!d_coin_out && ragged_kind(s.kind))
+        return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: coin_out is required on a %s segment", kind_info(s.kind).name);
+    if (s.m <= 0) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: the segment has no pools");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool timed = c->opt_time_kernels != 0;
+    QuoteScratch& sc = c->quote;
+    for (int k = 0; k < 2 && timed; ++k)
+        if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
+    QuoteArgs a{};
+    a.count = count;
+    a.idx = reinterpret_cast<const long long*>(d_idx);
+    a.coin_in = d_coin_in;
+    a.coin_out = d_coin_out;
+    a.amount_in = d_amount_in;
+    a.amount_out = d_amount_out;
+    const hipError_t e = launch_for(c, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
+    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote launch failed: %s", hipGetErrorString(e));
+    sc.dev_timed = timed;   // the span is read when "quote_ns" is asked for (the call itself does not wait)
+    return CFMM_OK;
+}
+
+namespace cfmm {
+
+// read-only option "quote_ns": the span of the latest call's kernel timed under "time_kernels"
+int quote_ns(cfmm_ctx* c, int64_t* value)
+{
+    QuoteScratch& sc = c->quote;
+    if (sc.dev_timed) {
+        float ms = 0.f;
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipEventSynchronize(sc.ev[1].get()));
+        HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[0].get(), sc.ev[1].get()));
+        sc.ns = (int64_t)((double)ms * 1e6);
+        sc.dev_timed = false;
+    }
+    *value = sc.ns;
+    return CFMM_OK;
+}
+
+} // namespace cfmm

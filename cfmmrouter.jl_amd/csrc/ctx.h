@@ -14,6 +14,7 @@
 //                     reserves / prices read-back
 //   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices / _set_ticks)
 //   ladder_store.h    LadderStore: a UniV3 segment's tick ladders on the host, one pool's replaceable (no HIP)
+//   abi_quote.cpp     exact-input swap quotes (cfmm_quote / cfmm_quote_dev; forward_trade generalised)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -216,6 +217,19 @@ struct SelectScratch {
                                        // latest timed call's kernel spans (emit: 0 when the call only counted)
 };
 
+// cfmm_quote (abi_quote.cpp, quote_kernels.h): the device copies of one call's queries and answers and their pinned staging,
+// grown on demand and kept for the next call -- proportional to the queries of the largest call, never to the pools.
+// cfmm_quote_dev uses the two events only.
+struct QuoteScratch {
+    DevBuf<long long> idx;             // [count]
+    DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out
+    DevBuf<double> amt, out;           // [count]
+    PinnedBuf<unsigned long long> stage;   // [4][count] 8-byte words: amounts, coins, answers, idx
+    Event ev[2];                       // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // read-only option "quote_ns": that kernel's span
+    bool dev_timed = false;            // the latest timed call was cfmm_quote_dev: its span is read when asked for
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -336,6 +350,7 @@ struct cfmm_ctx {
     cfmm::UpdateStaging upd;
     int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
     cfmm::SelectScratch sel;
+    cfmm::QuoteScratch quote;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
@@ -397,6 +412,9 @@ int child_segment(const cfmm_ctx* c, int pseg, int d);
 int multi_get_trades_range(cfmm_ctx* c, int32_t seg, int64_t first, int64_t count, double* Delta, double* Lambda);
 int multi_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_value, int64_t capacity, int64_t* count, int64_t* idx,
                         double* Delta, double* Lambda, double* value);
+
+// abi_quote.cpp
+int quote_ns(cfmm_ctx* c, int64_t* value);
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

@@ -392,6 +392,28 @@ inline int64_t select_blocks(int64_t m) { return (m + kSelBlock - 1) / kSelBlock
 hipError_t launch_select_count(const SelectArgs& a, bool ragged, long long* total_host, hipStream_t s, hipEvent_t* ev);
 hipError_t launch_select_emit(const SelectArgs& a, bool ragged, hipStream_t s, hipEvent_t* ev);
 
+// cfmm_quote / cfmm_quote_dev (quote_kernels.h, abi_quote.cpp): exact-input swap quotes of ONE segment, one lane per query.
+// All pointers are device pointers; the pool streams are the segment's own arrays (nothing is uploaded or kept per pool).
+constexpr int kQuoteBlock = 256;
+struct QuoteArgs {
+    int64_t count;               // queries
+    int64_t m;                   // pools of the segment
+    int n_coins;                 // 2, or the ragged segment's coin count
+    const long long* idx;        // [count] rows within the segment, any order, repeats allowed; null: query q is row q
+    const int32_t* coin_in;      // [count] positions in the pool's own coin order
+    const int32_t* coin_out;     // [count], or null (two-coin kinds, UniV3): 1 − coin_in
+    const double* amount_in;     // [count]
+    double* amount_out;          // [count]; NaN for a query whose row, coins or amount are out of range (never read out of bounds)
+    // two-coin kinds (Product, Solidly, GeometricMean): reserves, weights (GeometricMean only), fees
+    const double2* R;
+    const double2* w;
+    const double* gamma;
+};
+// `kind` picks the instantiation; u: UniV3 segments, n: weighted / Curve segments (the other members unused).  e0, e1: both
+// set = the launch is timed by the command processor.
+hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                        hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

@@ -41,6 +41,7 @@
 //   fold_kernels.h    reduce_partials, reduce_gather, gather_chunks, token_fold
 //   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records, compact_walks
 //   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
+//   quote_kernels.h   quote_kernel (cfmm_quote; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -54,9 +55,11 @@
 #include "fold_kernels.h"
 #include "update_kernels.h"
 #include "select_kernels.h"
+#include "quote_kernels.h"
 
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <cstddef>
 
 namespace cfmm {
@@ -294,6 +297,25 @@ hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pi
     dim3 g(fold_grid(n1));
     void* args[] = {&partials, &rows, &n1, &pitch, &out, const_cast<PeerSet*>(&ps)};
     return launch_k(reinterpret_cast<const void*>(&reduce_gather<kFoldBlock>), g, dim3(kFoldBlock), 0, s, e0, e1, args);
+}
+
+hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.count <= 0 || a.m <= 0) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_PRODUCT>); break;
+    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_GEOMEAN>); break;
+    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_UNIV3>); break;
+    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_WEIGHTED>); break;
+    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_CURVE>); break;
+    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_SOLIDLY>); break;
+    default: return hipErrorInvalidDeviceFunction;   // no such kernel: there is no falling through to another one
+    }
+    // one lane per query, at most one machine of resident threads (the lanes stride over the rest)
+    const int64_t blocks = std::min<int64_t>((a.count + kQuoteBlock - 1) / kQuoteBlock, kResidentThreads / kQuoteBlock);
+    void* args[] = {const_cast<QuoteArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_k(kernel, dim3((unsigned)blocks), dim3(kQuoteBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm

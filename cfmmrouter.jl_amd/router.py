@@ -696,6 +696,43 @@ def update_pools_(r: Router, changes):
     return None
 
 
+def quote(r: Router, pools, coin_in, amount_in, coin_out=None):
+    """Exact-input swap quotes on the pools as they stand on the device (cfmm_quote; forward_trade, src/cfmms.jl:436-449,
+    for every device kind): what comes out of pool `pools[q]` for `amount_in[q]` of its coin `coin_in[q]`.
+
+    `pools` are positions in `r.cfmms` (any order, repeats allowed: a ladder of sizes is the same pool many times);
+    coin_in / coin_out are 0-based positions in the pool's own coin order (scalars serve every query); coin_out=None means
+    the other coin of a two-coin or UniV3 pool.  The pools map to (segment, row) the way update_pools_ maps its changes,
+    each segment's queries go through one call, and the results come back in the caller's order.  Read-only: the router's
+    trades, prices and pools stay as they are.  A host-evaluated plugin pool has no device state to quote: ArgumentError."""
+    L = r._layout
+    pools = np.asarray(pools, dtype=np.int64).reshape(-1)
+    n = pools.size
+    try:
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (n,)))
+        ci = np.ascontiguousarray(np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,)))
+        co = None if coin_out is None else np.ascontiguousarray(np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,)))
+    except ValueError:
+        raise ArgumentError("amount_in, coin_in and coin_out must be scalars or have one entry per pool") from None
+    per_batch = {}
+    for q, i in enumerate(pools):
+        where = L.locate(i)
+        if where[0] == "host":
+            raise ArgumentError(f"pool {int(i)}: {type(r._host.pools[where[1]]).__name__} is evaluated on the host by its own "
+                                f"find_arb_ and has no device state to quote")
+        qs, rows = per_batch.setdefault(where[1], ([], []))
+        qs.append(q)
+        rows.append(where[2])
+    ctx = getattr(r._backend, "ctx", None)
+    if ctx is None and per_batch:
+        raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
+    out = np.empty(n)
+    for b in sorted(per_batch):
+        qs, rows = per_batch[b]
+        out[qs] = ctx.quote(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
+    return out
+
+
 def _update_reserves_host(r: Router):
     if any(_has_ladder(b.kind) for b in r._batches):
         raise NotImplementedError("update_reserves! is not defined for UniV3 pools (nor in the reference)")

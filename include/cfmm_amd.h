@@ -330,6 +330,39 @@ int cfmm_pools_set_prices(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64
 int cfmm_pools_set_ticks(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const double* current_price,
                          const int64_t* tick_off, const double* lower_ticks, const double* liquidity);
 
+/* Exact-input swap quotes: "if I tender amount_in of coin_in to this pool as it stands on the device now, how much of
+ * coin_out comes out?"  Generalises forward_trade(Δ, cfmm::UniV3), src/cfmms.jl:398-449 -- the reference's only quote -- to
+ * every kind: amount_out is the largest out >= 0 with φ(R + γ·a·e_in − out·e_out) = φ(R), the constraint of src/cfmms.jl:26-31
+ * (fee on the input) met with equality.  Closed forms, one lane per query, no iteration (UniV3: a search on the running sums
+ * of the walk records plus one closed form).  amount_in == 0 gives exactly +0.0.
+ *   seg        as in cfmm_segment_info.
+ *   idx        [count] rows within the segment, in any order, repeats allowed (a ladder of sizes through one pool is
+ *              `count` queries on the same row).  NULL: rows 0 .. count-1.
+ *   coin_in,   [count] positions in the pool's own coin order (0-based, < n_coins), NOT token numbers.  coin_out == NULL is
+ *   coin_out   allowed on two-coin and UniV3 segments and means 1 - coin_in; on weighted / Curve segments NULL is
+ *              CFMM_ERR_INVALID_ARG.
+ *   amount_in  [count], finite and >= 0.        amount_out  [count].
+ * cfmm_quote (host pointers) checks everything before anything is enqueued -- seg, count >= 0, every row in range, coins in
+ * range and distinct, amounts finite and >= 0; a failure is CFMM_ERR_INVALID_ARG, names the query in cfmm_last_error and
+ * leaves amount_out untouched.  Synchronous on the context's stream, behind earlier sweeps and updates.  count == 0: a no-op.
+ * UniV3: a tendered amount beyond all liquidity of the direction returns the whole of it ("exhausted all liquidity", :432); the
+ * unused input is not reported, as in the reference.
+ * Read-only: consumes nothing and invalidates nothing -- cfmm_get_trades*, cfmm_select_trades, cfmm_netflows,
+ * cfmm_update_reserves, a pre-armed cfmm_route and the next sweep behave as if it had not been called; needs no sweep to
+ * have run.  Works on every kind, in large-market mode and on multi-device contexts (the queries are split over the shards
+ * that hold their rows; the answers return in query order).  On a context sharded with cfmm_set_peers or RCCL the call is
+ * LOCAL to the rank's own pools and is not collective.  Device memory of the call is proportional to count, never to the pools.
+ * Read-only option under "time_kernels": "quote_ns", the span of the latest call's kernel (a multi-device context: the longest
+ * among the shards that call touched; after cfmm_quote_dev, reading it waits for the kernel). */
+int cfmm_quote(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+               const int32_t* coin_out, const double* amount_in, double* amount_out);
+/* The same on device arrays (src/cfmms.jl:398-449 generalised, as cfmm_quote): asynchronous on the context's stream; checks
+ * only seg and count (and that coin_out is given where it must be).  The library cannot validate device memory: an
+ * out-of-range row or coin, equal coins, or a negative or non-finite amount yields NaN for THAT query and correct answers
+ * for the rest; indices are clamped before any read, so the call never reads out of bounds.  Single-device contexts only. */
+int cfmm_quote_dev(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+                   const int32_t* d_coin_out, const double* d_amount_in, double* d_amount_out);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

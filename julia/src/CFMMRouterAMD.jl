@@ -18,9 +18,9 @@ module CFMMRouterAMD
 using CFMMRouter
 using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, Product, GeometricMean, Curve
 using LBFGSB
-import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!
+import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, select_trades, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, forward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -428,6 +428,86 @@ function select_trades(r::AMDRouter, seg::Integer; min_value::Real=0.0, v=nothin
         end
         cap = count[]
     end
+end
+
+# Device segment and 0-based row of every device pool of the router: the order of build_router (r.order grouped by family,
+# then weighted pools per coin count, then Curve pools per coin count), derived as update_pools! derives it (that function
+# keeps its own copy: it is left as it was).
+function segment_rows(r::AMDRouter)
+    pos = 0
+    groups = Vector{Vector{Int}}()
+    for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3, SolidlyStableTwoCoin)
+        idx = [i for i in r.order[pos+1:end] if r.cfmms[i] isa T]
+        isempty(idx) && continue
+        push!(groups, idx); pos += length(idx)
+    end
+    for curve in (false, true), n in 2:8
+        idx = [i for i in r.order[pos+1:end] if (curve ? r.cfmms[i] isa Curve :
+                                                 (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product)) &&
+                                                length(r.cfmms[i].Ai) == n]
+        isempty(idx) && continue
+        push!(groups, idx); pos += length(idx)
+    end
+    where = Dict{Int,Tuple{Int32,Int64}}()
+    for (s, idx) in enumerate(groups), (k, i) in enumerate(idx)
+        where[i] = (Int32(s - 1), Int64(k - 1))
+    end
+    return where
+end
+
+# quote_swaps(r, pools, coin_in, amount_in; coin_out) -- the Python host's router-level `quote` (a reserved word here): exact-input swap quotes on the pools as they stand on the device (cfmm_quote;
+# forward_trade, src/cfmms.jl:436-449, for every device kind): what comes out of pool pools[q] (positions in r.cfmms, any
+# order, repeats allowed) for amount_in[q] of its coin coin_in[q] (1-based positions in the pool's own coin order).
+# coin_out = nothing: the other coin of a two-coin or UniV3 pool.  Each segment's queries go through one call; the results
+# return in the caller's order.  Read-only.  A host-evaluated pool type has no device state to quote: ArgumentError.
+function quote_swaps(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
+                     amount_in::AbstractVector{<:Real}; coin_out=nothing)
+    n = length(pools)
+    (length(coin_in) == n && length(amount_in) == n && (isnothing(coin_out) || length(coin_out) == n)) ||
+        throw(ArgumentError("coin_in, amount_in and coin_out must have one entry per pool"))
+    where = segment_rows(r)
+    segs = Dict{Int32,Vector{Int}}()                      # segment => query numbers
+    for (q, i) in enumerate(pools)
+        i in r.host && throw(ArgumentError("pool $i: $(typeof(r.cfmms[i])) is evaluated on the host by its own find_arb! and has no device state to quote"))
+        haskey(where, i) || throw(ArgumentError("pool $i out of range"))
+        push!(get!(segs, where[i][1], Int[]), q)
+    end
+    out = Vector{Float64}(undef, n)
+    for s in sort(collect(keys(segs)))
+        qs = segs[s]
+        idx = Int64[where[pools[q]][2] for q in qs]
+        ci = Int32[coin_in[q] - 1 for q in qs]
+        co = isnothing(coin_out) ? Int32[] : Int32[coin_out[q] - 1 for q in qs]
+        amt = Float64[amount_in[q] for q in qs]
+        res = Vector{Float64}(undef, length(qs))
+        GC.@preserve idx ci co amt res check(r.ctx, ccall((:cfmm_quote, LIB), Cint,
+            (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+            r.ctx, s, length(qs), idx, ci, isnothing(coin_out) ? C_NULL : pointer(co), amt, res))
+        out[qs] .= res
+    end
+    return out
+end
+
+# forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449: methods of CFMMRouter's own function (imported above) for the pool kinds it
+# has none for, one pool through the device (a one-pool AMDRouter).  Δ has exactly one positive entry; on pools of more than
+# two coins the keyword coin_out (1-based) is required.  Δ == 0 returns 0.0 (:440-442).  UniV3 keeps the reference's own
+# method (:436): a method here for (AbstractVector, UniV3) would be ambiguous with it or replace it; the device's UniV3 quote
+# is quote_swaps on a router that holds the pool.
+const DeviceQuotedPool = Union{ProductTwoCoin{Float64},GeometricMeanTwoCoin{Float64},Product{Float64},GeometricMean{Float64},
+                               Curve{Float64},SolidlyStableTwoCoin{Float64}}
+function forward_trade(Δ::AbstractVector{<:Real}, cfmm::DeviceQuotedPool; coin_out=nothing, device=0)
+    n = length(cfmm.Ai)
+    length(Δ) == n || throw(ArgumentError("Δ must have $n entries"))
+    (all(isfinite, Δ) && all(>=(0), Δ)) || throw(ArgumentError("Δ must be finite and >= 0"))
+    pos = findall(>(0), Δ)
+    length(pos) <= 1 || throw(ArgumentError("Δ must have exactly one positive entry (one coin in)"))
+    (isnothing(coin_out) && n > 2) && throw(ArgumentError("coin_out is required on a pool of $n coins"))
+    (isnothing(coin_out) || 1 <= coin_out <= n) || throw(ArgumentError("coin_out $coin_out out of range 1:$n"))
+    isempty(pos) && return 0.0
+    (!isnothing(coin_out) && coin_out == pos[1]) && throw(ArgumentError("coin_out is the tendered coin"))
+    nt = Int(maximum(cfmm.Ai))
+    r = AMDRouter(CFMMRouter.LinearNonnegative(ones(nt)), [cfmm], nt; device=device)
+    return quote_swaps(r, [1], [pos[1]], [Float64(Δ[pos[1]])]; coin_out=isnothing(coin_out) ? nothing : [coin_out])[1]
 end
 
 # Optional fast path: the whole of route! inside the library (cfmm_route: its own L-BFGS-B, the
