@@ -6,11 +6,11 @@ through libcfmm_amd.so (include/cfmm_amd.h); there is no CPU fallback in this pa
 """
 from ._lib import ArgumentError, CFMMDeviceError, Context, build, lib
 from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwoCoin, PoolBatch, Product, ProductTwoCoin,
-                    SolidlyStableTwoCoin, UniV3, find_arb_ as _find_arb_pool, forward_trade,
+                    SolidlyStableTwoCoin, UniV3, backward_trade, find_arb_ as _find_arb_pool, forward_trade,
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
-from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, netflows, netflows_, polish_, quote, route_,
+from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, netflows, netflows_, polish_, quote, quote_out, route_,
                      update_pools_, update_reserves_)
 
 
@@ -28,5 +28,5 @@ __all__ = [
     "update_reserves_", "update_pools_", "Objective", "LinearNonnegative", "BasketLiquidation", "Swap", "f", "grad_",
     "lower_limit", "upper_limit", "Router", "route_", "netflows_", "netflows", "ArgumentError",
     "CFMMDeviceError", "Context", "DeviceBackend", "build", "lib", "zerotrade", "ϕ", "ϕ_grad_", "phi", "grad_phi_",
-    "polish_", "dual_jacobian", "active_trades", "forward_trade", "quote",
+    "polish_", "dual_jacobian", "active_trades", "forward_trade", "quote", "backward_trade", "quote_out",
 ]

@@ -133,6 +133,8 @@ def lib():
     L.cfmm_pools_set_ticks.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _f64p, _i64p, _f64p, _f64p]
     L.cfmm_quote.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_quote_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_quote_out.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
+    L.cfmm_quote_out_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -482,7 +484,15 @@ class Context:
         serves every query) to rows idx of segment `seg` (None: rows 0 .. count-1; any order, repeats allowed).
         coin_out=None means 1 - coin_in on two-coin and UniV3 segments; weighted / Curve segments need it.  Everything is
         checked before anything runs (ArgumentError names the query)."""
-        amt = f64(amount_in).reshape(-1)
+        return self._quote("cfmm_quote", seg, amount_in, coin_in, coin_out, idx)
+
+    def quote_out(self, seg: int, amount_out, coin_in, coin_out=None, idx=None):
+        """The inverse of quote (cfmm_quote_out): amount_in [count] of coin_in to tender so that exactly amount_out [count]
+        of coin_out comes out; same arguments and checks.  +inf where the pool cannot give that much (not an error)."""
+        return self._quote("cfmm_quote_out", seg, amount_out, coin_in, coin_out, idx)
+
+    def _quote(self, entry, seg, given, coin_in, coin_out, idx):
+        amt = f64(given).reshape(-1)
         n = amt.size
         bcast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32).reshape(-1) if np.ndim(a) else
                                                                np.int32(a), (n,)), dtype=np.int32)
@@ -495,7 +505,7 @@ class Context:
         if ix is not None and ix.size != n:
             raise ArgumentError("idx must have one entry per amount")
         out = np.empty(n)
-        self._check(self._L.cfmm_quote(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out)))
+        self._check(getattr(self._L, entry)(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out)))
         return out
 
     def quote_dev(self, seg: int, count: int, d_amount_in: int, d_coin_in: int, d_amount_out: int, d_coin_out: int = 0,
@@ -505,6 +515,14 @@ class Context:
         self._check(self._L.cfmm_quote_dev(self._h, int(seg), int(count), C.c_void_p(d_idx or None), C.c_void_p(d_coin_in or None),
                                            C.c_void_p(d_coin_out or None), C.c_void_p(d_amount_in or None),
                                            C.c_void_p(d_amount_out or None)))
+
+    def quote_out_dev(self, seg: int, count: int, d_amount_out: int, d_coin_in: int, d_amount_in: int, d_coin_out: int = 0,
+                      d_idx: int = 0):
+        """cfmm_quote_out_dev on device addresses, as quote_dev: d_amount_out [count] is read (the wanted outputs),
+        d_amount_in [count] is written (the inputs to tender; NaN for a bad query)."""
+        self._check(self._L.cfmm_quote_out_dev(self._h, int(seg), int(count), C.c_void_p(d_idx or None), C.c_void_p(d_coin_in or None),
+                                               C.c_void_p(d_coin_out or None), C.c_void_p(d_amount_out or None),
+                                               C.c_void_p(d_amount_in or None)))
 
     def set_peers(self, peer_ptrs, world: int, rank: int, seq: int):
         """Sharded operation: every host-pointer sweep of this context ends with the one-shot peer

@@ -600,6 +600,45 @@ def forward_trade(Δ, cfmm, coin_out=None, device=0):
     return float(out[0])
 
 
+def backward_trade(Λ, cfmm, coin_in=None, device=0):
+    """backward_trade(Λ, cfmm) -- the mirror of forward_trade (the reference has none): the exact-output quote of one pool.
+
+    Λ (length len(cfmm.Ai)) has exactly one positive entry: the amount wanted, at the position of its coin.  Returns the
+    amount of the other coin -- of coin `coin_in` (0-based position; required on pools of more than two coins) -- that must
+    be tendered, fee on the input: the smallest δ with φ(R + γδ·e_in − Λ) = φ(R); +inf where the pool cannot give Λ.
+    Λ == 0 returns 0.0.  One pool through the device (cfmm_quote_out)."""
+    from ._lib import Context
+
+    if not hasattr(cfmm, "kind") or cfmm.kind not in KINDS:
+        raise ArgumentError(f"{type(cfmm).__name__} has no device quote")
+    n = len(cfmm.Ai)
+    Λ = np.asarray(Λ, dtype=np.float64).reshape(-1)
+    if Λ.size != n:
+        raise ArgumentError(f"Λ must have {n} entries")
+    if not np.all(np.isfinite(Λ)) or np.any(Λ < 0):
+        raise ArgumentError("Λ must be finite and >= 0")
+    pos = np.flatnonzero(Λ > 0)
+    if pos.size > 1:
+        raise ArgumentError("Λ must have exactly one positive entry (one coin out)")
+    if coin_in is None and n > 2:
+        raise ArgumentError(f"coin_in= is required on a pool of {n} coins")
+    if coin_in is not None and not 0 <= int(coin_in) < n:
+        raise ArgumentError(f"coin_in {coin_in} out of range 0:{n - 1}")
+    if pos.size == 0:
+        return 0.0
+    cout = int(pos[0])
+    if coin_in is not None and int(coin_in) == cout:
+        raise ArgumentError("coin_in is the wanted coin")
+    cin = 1 - cout if coin_in is None else int(coin_in)
+    ctx = Context(n, device)
+    try:
+        _upload(ctx, PoolBatch.from_pools(cfmm.kind, [_with_local_idx(cfmm)]))
+        out = ctx.quote_out(0, [Λ[cout]], cin, cout)
+    finally:
+        ctx.close()
+    return float(out[0])
+
+
 def _with_local_idx(c):
     """the pool with token indices 1..n (a one-pool market)"""
     K = KINDS[c.kind]

@@ -1,5 +1,8 @@
 // abi_quote.cpp -- cfmm_quote / cfmm_quote_dev: exact-input swap quotes of one segment's pools as they stand on the device
-// (forward_trade, src/cfmms.jl:398-449, generalised to every kind; the forms: quote_pool.h, the kernel: quote_kernels.h).
+// (forward_trade, src/cfmms.jl:398-449, generalised to every kind; the forms: quote_pool.h, the kernel: quote_kernels.h), and
+// cfmm_quote_out / cfmm_quote_out_dev, their inverses (exact-output).  The two directions share every line here: a Dir names
+// the entry and its given amount in the messages and picks the launcher; `given` / `answer` below are amount_in / amount_out
+// of the forward entries and amount_out / amount_in of the inverse ones.
 // Read-only: the pool streams are the segment's own arrays, the only memory of the feature is QuoteScratch (ctx.h), which is
 // proportional to the queries of a call and never to the pools.
 #include "ctx.h"
@@ -12,8 +15,15 @@ using namespace cfmm;
 
 namespace {
 
+struct Dir {
+    bool exact_out;
+    const char *host, *dev, *given;   // the entries' names and the given amount's, as the messages spell them
+};
+constexpr Dir kForward{false, "cfmm_quote", "cfmm_quote_dev", "amount_in"};
+constexpr Dir kInverse{true, "cfmm_quote_out", "cfmm_quote_out_dev", "amount_out"};
+
 // the kernel's view of segment `s` for `count` queries; the query arrays are filled in by the caller
-hipError_t launch_for(const cfmm_ctx* c, const Segment& s, const QuoteArgs& q, hipEvent_t e0, hipEvent_t e1)
+hipError_t launch_for(const cfmm_ctx* c, const Dir& dir, const Segment& s, const QuoteArgs& q, hipEvent_t e0, hipEvent_t e1)
 {
     QuoteArgs a = q;
     a.m = s.m;
@@ -41,7 +51,7 @@ hipError_t launch_for(const cfmm_ctx* c, const Segment& s, const QuoteArgs& q, h
         n.par = s.nc.par.get();
         n.n_coins = s.n_coins;
     }
-    return launch_quote(s.kind, a, u, n, c->stream, e0, e1);
+    return (dir.exact_out ? launch_quote_out : launch_quote)(s.kind, a, u, n, c->stream, e0, e1);
 }
 
 int check_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t nseg)
@@ -52,32 +62,36 @@ int check_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t 
 }
 
 // every query of a host-pointer call, before anything is enqueued
-int check_queries(cfmm_ctx* c, int kind, int64_t m, int nc, int64_t count, const int64_t* idx, const int32_t* coin_in,
-                  const int32_t* coin_out, const double* amount_in, const double* amount_out)
+int check_queries(cfmm_ctx* c, const Dir& dir, int kind, int64_t m, int nc, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                  const int32_t* coin_out, const double* given, const double* answer)
 {
-    if (count > 0 && (!coin_in || !amount_in || !amount_out)) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: null query array");
+    const char* who = dir.host;
+    if (count > 0 && (!coin_in || !given || !answer)) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null query array", who);
     if (count > 0 && !coin_out && ragged_kind(kind))
-        return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: coin_out is required on a %s segment (query 0)", kind_info(kind).name);
+        return fail(c, CFMM_ERR_INVALID_ARG, "%s: coin_out is required on a %s segment (query 0)", who, kind_info(kind).name);
     for (int64_t q = 0; q < count; ++q) {
         const int64_t row = idx ? idx[q] : q;
         if (row < 0 || row >= m)
-            return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: row %lld out of range (segment has %lld pools)",
+            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: row %lld out of range (segment has %lld pools)", who,
                         (long long)q, (long long)row, (long long)m);
         const int ci = coin_in[q], co = coin_out ? coin_out[q] : 1 - ci;
-        if (ci < 0 || ci >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_in %d out of range (pool has %d coins)", (long long)q, ci, nc);
-        if (co < 0 || co >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_out %d out of range (pool has %d coins)", (long long)q, co, nc);
-        if (ci == co) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: coin_in and coin_out are both %d", (long long)q, ci);
-        if (!(amount_in[q] >= 0.0) || !std::isfinite(amount_in[q]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote: query %lld: amount_in must be finite and >= 0", (long long)q);
+        if (ci < 0 || ci >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in %d out of range (pool has %d coins)", who, (long long)q, ci, nc);
+        if (co < 0 || co >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_out %d out of range (pool has %d coins)", who, (long long)q, co, nc);
+        if (ci == co) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in and coin_out are both %d", who, (long long)q, ci);
+        if (!(given[q] >= 0.0) || !std::isfinite(given[q]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: %s must be finite and >= 0", who, (long long)q, dir.given);
     }
     return CFMM_OK;
 }
 
+int quote_host(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+               const int32_t* coin_out, const double* given, double* answer);
+
 // A parent: the queries go to the shards that hold their rows (shard_range: contiguous blocks in device order) and the
 // answers return in query order, as cfmm_select_trades handles its rows.  Everything was checked by the caller.  One pass
 // buckets the queries by shard (a binary search on the blocks' ends per query), one call per shard that got any.
-int multi_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
-                const double* amount_in, double* amount_out)
+int multi_quote(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                const int32_t* coin_out, const double* given, double* answer)
 {
     const int64_t m = c->psegs[(size_t)seg].m;
     const int nd = (int)c->shards.size();
@@ -97,7 +111,7 @@ int multi_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
         bk.rows.push_back(row - first[d]);
         bk.ci.push_back(coin_in[q]);
         if (coin_out) bk.co.push_back(coin_out[q]);
-        bk.amt.push_back(amount_in[q]);
+        bk.amt.push_back(given[q]);
     }
     std::vector<double> out;
     int64_t ns = 0;
@@ -106,33 +120,31 @@ int multi_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
         if (bk.where.empty()) continue;
         out.resize(bk.where.size());
         cfmm_ctx* child = c->shards[(size_t)d];
-        const int rc = cfmm_quote(child, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
+        const int rc = quote_host(child, dir, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
                                   coin_out ? bk.co.data() : nullptr, bk.amt.data(), out.data());
         if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s", d, child->err.c_str());
-        for (size_t j = 0; j < bk.where.size(); ++j) amount_out[bk.where[j]] = out[j];
+        for (size_t j = 0; j < bk.where.size(); ++j) answer[bk.where[j]] = out[j];
         if (child->opt_time_kernels != 0) ns = std::max(ns, child->quote.ns);
     }
     c->quote.ns = ns;   // "quote_ns" of a parent: the longest kernel span among the shards THIS call touched
     return CFMM_OK;
 }
 
-} // namespace
-
 // Pinned staging: [count] 8-byte words per column -- idx, amounts, {coin_in, coin_out} as two int32 columns packed into
 // one, and the answers -- copied to / from the scratch's device arrays in stream order; one synchronisation.
-int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
-               const double* amount_in, double* amount_out)
+int quote_host(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+               const int32_t* coin_out, const double* given, double* answer)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
     const bool parent = !c->shards.empty();
-    int rc = check_seg(c, "cfmm_quote", seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
+    int rc = check_seg(c, dir.host, seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
     if (rc != CFMM_OK) return rc;
     const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
     const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
     const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
-    if ((rc = check_queries(c, kind, m, nc, count, idx, coin_in, coin_out, amount_in, amount_out)) != CFMM_OK) return rc;
+    if ((rc = check_queries(c, dir, kind, m, nc, count, idx, coin_in, coin_out, given, answer)) != CFMM_OK) return rc;
     if (count == 0) return CFMM_OK;
-    if (parent) return multi_quote(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out);
+    if (parent) return multi_quote(c, dir, seg, count, idx, coin_in, coin_out, given, answer);
 
     const Segment& s = c->segs[(size_t)seg];
     HIP_TRY(c, hipSetDevice(c->device));
@@ -150,7 +162,7 @@ int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
     int32_t* h_coins = reinterpret_cast<int32_t*>(st + n);   // [count] coin_in, then [count] coin_out
     double* h_out = reinterpret_cast<double*>(st + 2 * n);
     long long* h_idx = reinterpret_cast<long long*>(st + 3 * n);
-    std::memcpy(h_amt, amount_in, n * sizeof(double));
+    std::memcpy(h_amt, given, n * sizeof(double));
     std::memcpy(h_coins, coin_in, n * sizeof(int32_t));
     if (coin_out) std::memcpy(h_coins + n, coin_out, n * sizeof(int32_t));
     if (idx) std::memcpy(h_idx, idx, n * sizeof(long long));
@@ -164,7 +176,7 @@ int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
     a.coin_out = coin_out ? sc.coins.get() + n : nullptr;
     a.amount_in = sc.amt.get();
     a.amount_out = sc.out.get();
-    const hipError_t e = launch_for(c, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
+    const hipError_t e = launch_for(c, dir, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote launch failed: %s", hipGetErrorString(e));
     HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -174,23 +186,24 @@ int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
         sc.ns = (int64_t)((double)ms * 1e6);
         sc.dev_timed = false;
     }
-    std::memcpy(amount_out, h_out, n * sizeof(double));
+    std::memcpy(answer, h_out, n * sizeof(double));
     return CFMM_OK;
 }
 
-int cfmm_quote_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
-                   const int32_t* d_coin_out, const double* d_amount_in, double* d_amount_out)
+int quote_dev(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+              const int32_t* d_coin_out, const double* d_given, double* d_answer)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    CFMM_SINGLE_ONLY(c, "cfmm_quote_dev");
-    int rc = check_seg(c, "cfmm_quote_dev", seg, count, (int64_t)c->segs.size());
+    if (is_parent(c))   // (CFMM_SINGLE_ONLY's text, with the entry's name from the Dir)
+        return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context (host-pointer calls only)", dir.dev);
+    int rc = check_seg(c, dir.dev, seg, count, (int64_t)c->segs.size());
     if (rc != CFMM_OK) return rc;
     if (count == 0) return CFMM_OK;
     const Segment& s = c->segs[(size_t)seg];
-    if (!d_coin_in || !d_amount_in || !d_amount_out) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: null query array");
+    if (!d_coin_in || !d_given || !d_answer) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null query array", dir.dev);
     if (!d_coin_out && ragged_kind(s.kind))
-        return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: coin_out is required on a %s segment", kind_info(s.kind).name);
-    if (s.m <= 0) return fail(c, CFMM_ERR_INVALID_ARG, "cfmm_quote_dev: the segment has no pools");
+        return fail(c, CFMM_ERR_INVALID_ARG, "%s: coin_out is required on a %s segment", dir.dev, kind_info(s.kind).name);
+    if (s.m <= 0) return fail(c, CFMM_ERR_INVALID_ARG, "%s: the segment has no pools", dir.dev);
     HIP_TRY(c, hipSetDevice(c->device));
     const bool timed = c->opt_time_kernels != 0;
     QuoteScratch& sc = c->quote;
@@ -201,17 +214,43 @@ int cfmm_quote_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d_idx
     a.idx = reinterpret_cast<const long long*>(d_idx);
     a.coin_in = d_coin_in;
     a.coin_out = d_coin_out;
-    a.amount_in = d_amount_in;
-    a.amount_out = d_amount_out;
-    const hipError_t e = launch_for(c, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
+    a.amount_in = d_given;
+    a.amount_out = d_answer;
+    const hipError_t e = launch_for(c, dir, s, a, timed ? sc.ev[0].get() : nullptr, timed ? sc.ev[1].get() : nullptr);
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote launch failed: %s", hipGetErrorString(e));
     sc.dev_timed = timed;   // the span is read when "quote_ns" is asked for (the call itself does not wait)
     return CFMM_OK;
 }
 
+} // namespace
+
+int cfmm_quote(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+               const double* amount_in, double* amount_out)
+{
+    return quote_host(c, kForward, seg, count, idx, coin_in, coin_out, amount_in, amount_out);
+}
+
+int cfmm_quote_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+                   const int32_t* d_coin_out, const double* d_amount_in, double* d_amount_out)
+{
+    return quote_dev(c, kForward, seg, count, d_idx, d_coin_in, d_coin_out, d_amount_in, d_amount_out);
+}
+
+int cfmm_quote_out(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+                   const double* amount_out, double* amount_in)
+{
+    return quote_host(c, kInverse, seg, count, idx, coin_in, coin_out, amount_out, amount_in);
+}
+
+int cfmm_quote_out_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+                       const int32_t* d_coin_out, const double* d_amount_out, double* d_amount_in)
+{
+    return quote_dev(c, kInverse, seg, count, d_idx, d_coin_in, d_coin_out, d_amount_out, d_amount_in);
+}
+
 namespace cfmm {
 
-// read-only option "quote_ns": the span of the latest call's kernel timed under "time_kernels"
+// read-only option "quote_ns": the span of the latest call's kernel (of either direction) timed under "time_kernels"
 int quote_ns(cfmm_ctx* c, int64_t* value)
 {
     QuoteScratch& sc = c->quote;

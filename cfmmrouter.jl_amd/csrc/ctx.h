@@ -14,7 +14,8 @@
 //                     reserves / prices read-back
 //   abi_update.cpp    sparse pool-state updates (cfmm_pools_set_reserves / _set_curve / _set_prices / _set_ticks)
 //   ladder_store.h    LadderStore: a UniV3 segment's tick ladders on the host, one pool's replaceable (no HIP)
-//   abi_quote.cpp     exact-input swap quotes (cfmm_quote / cfmm_quote_dev; forward_trade generalised)
+//   abi_quote.cpp     exact-input swap quotes (cfmm_quote / cfmm_quote_dev; forward_trade generalised) and their inverses, the
+//                     exact-output quotes (cfmm_quote_out / cfmm_quote_out_dev)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -217,9 +218,9 @@ struct SelectScratch {
                                        // latest timed call's kernel spans (emit: 0 when the call only counted)
 };
 
-// cfmm_quote (abi_quote.cpp, quote_kernels.h): the device copies of one call's queries and answers and their pinned staging,
+// cfmm_quote and cfmm_quote_out (abi_quote.cpp, quote_kernels.h; one scratch for both directions): the device copies of one call's queries and answers and their pinned staging,
 // grown on demand and kept for the next call -- proportional to the queries of the largest call, never to the pools.
-// cfmm_quote_dev uses the two events only.
+// cfmm_quote_dev and cfmm_quote_out_dev use the two events only.
 struct QuoteScratch {
     DevBuf<long long> idx;             // [count]
     DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out

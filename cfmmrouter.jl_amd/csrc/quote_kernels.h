@@ -88,4 +88,69 @@ __global__ __launch_bounds__(kQuoteBlock) void quote_kernel(QuoteArgs a, UniV3Po
     }
 }
 
+// cfmm_quote_out / cfmm_quote_out_dev: the exact-output quotes (quote_pool.h quote_out_*), the same gather with the roles of
+// the two amounts exchanged -- QuoteArgs::amount_in carries the amount GIVEN (here the wanted output), ::amount_out the
+// answer (here the input to tender).  Same block, same clamp-then-poison rule, same dense / sparse behaviour; kernels of
+// their own, so that quote_kernel's code is what it was.
+template <int KIND>
+__device__ __forceinline__ double quote_out_one(const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, int64_t row, int ci,
+                                                int co, double amt)
+{
+    if constexpr (KIND == CFMM_KIND_PRODUCT || KIND == CFMM_KIND_SOLIDLY || KIND == CFMM_KIND_GEOMEAN) {
+        const double2 R = a.R[row];
+        const double g = a.gamma[row];
+        const double Ri = ci == 0 ? R.x : R.y, Ro = co == 0 ? R.x : R.y;
+        if constexpr (KIND == CFMM_KIND_GEOMEAN) {
+            const double2 w = a.w[row];
+            return quote_out_weighted(Ri, Ro, ci == 0 ? w.x : w.y, co == 0 ? w.x : w.y, g, amt);
+        } else if constexpr (KIND == CFMM_KIND_SOLIDLY) {
+            return quote_out_solidly(Ri, Ro, g, amt);
+        } else {
+            return quote_out_product(Ri, Ro, g, amt);
+        }
+    } else if constexpr (KIND == CFMM_KIND_UNIV3) {
+        return quote_out_univ3(u.cur_a[row], u.cur_b[row], u.cur_c[row], u.curR[row], u.walk[row], u.ticks, u.pg[row].y, ci, amt);
+    } else {
+        const int64_t m = a.m;
+        const double Ri = n.R[(int64_t)ci * m + row], Ro = n.R[(int64_t)co * m + row];
+        const double g = n.glg[row].x;
+        if constexpr (KIND == CFMM_KIND_WEIGHTED) {
+            return quote_out_weighted(Ri, Ro, n.par[(int64_t)ci * m + row], n.par[(int64_t)co * m + row], g, amt);
+        } else {
+            const double2 ab = reinterpret_cast<const double2*>(n.par)[row];   // {α, log β}
+            double srho;
+            switch (n.n_coins) {
+            case 2: srho = quote_sum_logs<2>(n.q, m, row); break;
+            case 3: srho = quote_sum_logs<3>(n.q, m, row); break;
+            case 4: srho = quote_sum_logs<4>(n.q, m, row); break;
+            case 5: srho = quote_sum_logs<5>(n.q, m, row); break;
+            case 6: srho = quote_sum_logs<6>(n.q, m, row); break;
+            case 7: srho = quote_sum_logs<7>(n.q, m, row); break;
+            default: srho = quote_sum_logs<8>(n.q, m, row); break;
+            }
+            return quote_out_curve(Ri, Ro, srho, ab.x, ab.y, g, amt);
+        }
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kQuoteBlock) void quote_out_kernel(QuoteArgs a, UniV3Pools u, NCoinPools n)
+{
+    const int64_t step = (int64_t)gridDim.x * kQuoteBlock;
+    for (int64_t q = (int64_t)blockIdx.x * kQuoteBlock + threadIdx.x; q < a.count; q += step) {
+        long long row = a.idx ? a.idx[q] : (long long)q;
+        int ci = a.coin_in[q];
+        int co = a.coin_out ? a.coin_out[q] : 1 - ci;
+        const double amt = a.amount_in[q];   // the wanted output
+        const bool ok = row >= 0 && row < a.m && ci >= 0 && ci < a.n_coins && co >= 0 && co < a.n_coins && ci != co &&
+                        amt >= 0.0 && amt < __builtin_inf();
+        // clamp, then read: an invalid query quotes some pool of the segment and is poisoned below
+        row = row < 0 ? 0 : (row >= a.m ? a.m - 1 : row);
+        ci = ci < 0 ? 0 : (ci >= a.n_coins ? a.n_coins - 1 : ci);
+        co = co < 0 ? 0 : (co >= a.n_coins ? a.n_coins - 1 : co);
+        const double in = quote_out_one<KIND>(a, u, n, row, ci, co, ok ? amt : 0.0);
+        a.amount_out[q] = ok ? in : __builtin_nan("");   // the input to tender
+    }
+}
+
 } // namespace cfmm

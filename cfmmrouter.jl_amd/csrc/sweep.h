@@ -413,6 +413,10 @@ struct QuoteArgs {
 // set = the launch is timed by the command processor.
 hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
                         hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// cfmm_quote_out / cfmm_quote_out_dev: the inverse kernels (quote_out_kernel) on the same arguments -- `amount_in` is then the
+// wanted output and `amount_out` receives the input to tender.
+hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                            hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars

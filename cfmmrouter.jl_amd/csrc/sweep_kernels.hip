@@ -41,7 +41,7 @@
 //   fold_kernels.h    reduce_partials, reduce_gather, gather_chunks, token_fold
 //   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records, compact_walks
 //   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
-//   quote_kernels.h   quote_kernel (cfmm_quote; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised)
+//   quote_kernels.h   quote_kernel, quote_out_kernel (cfmm_quote, cfmm_quote_out; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised, and their inverses)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -299,6 +299,15 @@ hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pi
     return launch_k(reinterpret_cast<const void*>(&reduce_gather<kFoldBlock>), g, dim3(kFoldBlock), 0, s, e0, e1, args);
 }
 
+// one lane per query, at most one machine of resident threads (the lanes stride over the rest)
+static hipError_t launch_quote_k(const void* kernel, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                                 hipEvent_t e0, hipEvent_t e1)
+{
+    const int64_t blocks = std::min<int64_t>((a.count + kQuoteBlock - 1) / kQuoteBlock, kResidentThreads / kQuoteBlock);
+    void* args[] = {const_cast<QuoteArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_k(kernel, dim3((unsigned)blocks), dim3(kQuoteBlock), 0, s, e0, e1, args);
+}
+
 hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (a.count <= 0 || a.m <= 0) return hipErrorInvalidValue;
@@ -312,10 +321,24 @@ hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const
     case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_SOLIDLY>); break;
     default: return hipErrorInvalidDeviceFunction;   // no such kernel: there is no falling through to another one
     }
-    // one lane per query, at most one machine of resident threads (the lanes stride over the rest)
-    const int64_t blocks = std::min<int64_t>((a.count + kQuoteBlock - 1) / kQuoteBlock, kResidentThreads / kQuoteBlock);
-    void* args[] = {const_cast<QuoteArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
-    return launch_k(kernel, dim3((unsigned)blocks), dim3(kQuoteBlock), 0, s, e0, e1, args);
+    return launch_quote_k(kernel, a, u, n, s, e0, e1);
+}
+
+hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0,
+                            hipEvent_t e1)
+{
+    if (a.count <= 0 || a.m <= 0) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_PRODUCT>); break;
+    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_GEOMEAN>); break;
+    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_UNIV3>); break;
+    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_WEIGHTED>); break;
+    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_CURVE>); break;
+    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_SOLIDLY>); break;
+    default: return hipErrorInvalidDeviceFunction;   // no such kernel
+    }
+    return launch_quote_k(kernel, a, u, n, s, e0, e1);
 }
 
 } // namespace cfmm

@@ -705,15 +705,27 @@ def quote(r: Router, pools, coin_in, amount_in, coin_out=None):
     the other coin of a two-coin or UniV3 pool.  The pools map to (segment, row) the way update_pools_ maps its changes,
     each segment's queries go through one call, and the results come back in the caller's order.  Read-only: the router's
     trades, prices and pools stay as they are.  A host-evaluated plugin pool has no device state to quote: ArgumentError."""
+    return _quote(r, "quote", pools, coin_in, amount_in, coin_out)
+
+
+def quote_out(r: Router, pools, coin_in, amount_out, coin_out=None):
+    """Exact-output swap quotes, the inverse of `quote` (cfmm_quote_out): how much of its coin `coin_in[q]` pool `pools[q]`
+    must be tendered so that exactly `amount_out[q]` of the coin out comes from it as it stands on the device.  Arguments,
+    mapping of pool numbers to (segment, row), order of the results and the refusal of a host-evaluated pool are those of
+    `quote`.  The answer is +inf where the pool cannot give that much."""
+    return _quote(r, "quote_out", pools, coin_in, amount_out, coin_out)
+
+
+def _quote(r: Router, verb, pools, coin_in, amount, coin_out):
     L = r._layout
     pools = np.asarray(pools, dtype=np.int64).reshape(-1)
     n = pools.size
     try:
-        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (n,)))
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
         ci = np.ascontiguousarray(np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,)))
         co = None if coin_out is None else np.ascontiguousarray(np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,)))
     except ValueError:
-        raise ArgumentError("amount_in, coin_in and coin_out must be scalars or have one entry per pool") from None
+        raise ArgumentError(f"{'amount_in' if verb == 'quote' else 'amount_out'}, coin_in and coin_out must be scalars or have one entry per pool") from None
     per_batch = {}
     for q, i in enumerate(pools):
         where = L.locate(i)
@@ -729,7 +741,7 @@ def quote(r: Router, pools, coin_in, amount_in, coin_out=None):
     out = np.empty(n)
     for b in sorted(per_batch):
         qs, rows = per_batch[b]
-        out[qs] = ctx.quote(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
+        out[qs] = getattr(ctx, verb)(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
     return out
 
 

@@ -363,6 +363,27 @@ int cfmm_quote(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, co
 int cfmm_quote_dev(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
                    const int32_t* d_coin_out, const double* d_amount_in, double* d_amount_out);
 
+/* Exact-output swap quotes, the inverse of cfmm_quote: "I need exactly amount_out of coin_out from this pool as it stands on
+ * the device now; how much of coin_in must I tender?"  (The reference has no such function; the constraint is the one of
+ * src/cfmms.jl:26-31, fee on the input.)  amount_in is the smallest a >= 0 with φ(R + γ·a·e_in − amount_out·e_out) = φ(R).
+ * Closed forms, one lane per query, no iteration (UniV3: a search on the running sums ΣR_out of the walk records plus one
+ * closed form).  amount_out == 0 gives exactly +0.0.  Where no finite input yields amount_out the answer is
+ * +inf, NOT an error: amount_out >= the pool's reserve of coin_out on the reserve kinds; on UniV3 an amount beyond the
+ * direction's total liquidity, or equal to a total that is only approached (the direction's last tick reaches down to price
+ * 0).  On UniV3 an amount_out equal to the total of a direction that a finite input exhausts gives that input, so
+ * cfmm_quote_out(cfmm_quote(a)) is the input the pool actually consumed when `a` exhausts the ladder.
+ * seg, idx, coin_in, coin_out, count == 0, the checks (amount_out finite and >= 0; a failure is CFMM_ERR_INVALID_ARG, names the
+ * query with the prefix "cfmm_quote_out:" and leaves amount_in untouched), the synchronisation, the read-only guarantees, large-
+ * market mode, multi-device and sharded contexts: exactly as cfmm_quote.  "quote_ns" reports the latest call of either
+ * direction.  The direction rule on UniV3 is cfmm_quote's: coin 0 in walks the price-falling list. */
+int cfmm_quote_out(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                   const int32_t* coin_out, const double* amount_out, double* amount_in);
+/* The same on device arrays, as cfmm_quote_dev is to cfmm_quote: asynchronous on the context's stream; checks only seg and
+ * count (and that coin_out is given where it must be); an out-of-range row or coin, equal coins, or a negative or non-finite
+ * amount_out yields NaN for THAT query; indices are clamped before any read.  Single-device contexts only. */
+int cfmm_quote_out_dev(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
+                       const int32_t* d_coin_out, const double* d_amount_out, double* d_amount_in);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

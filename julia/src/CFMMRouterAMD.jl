@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, forward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, quote_swaps_out, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -462,9 +462,22 @@ end
 # return in the caller's order.  Read-only.  A host-evaluated pool type has no device state to quote: ArgumentError.
 function quote_swaps(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
                      amount_in::AbstractVector{<:Real}; coin_out=nothing)
+    return quote_queries(r, pools, coin_in, amount_in, coin_out, false)
+end
+
+# quote_swaps_out(r, pools, coin_in, amount_out; coin_out) -- the inverse (cfmm_quote_out; the Python host's `quote_out`): how
+# much of its coin coin_in[q] pool pools[q] must be tendered so that exactly amount_out[q] of the coin out comes from it as it
+# stands on the device; Inf where the pool cannot give that much.  Arguments, mapping and order as quote_swaps.
+function quote_swaps_out(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
+                         amount_out::AbstractVector{<:Real}; coin_out=nothing)
+    return quote_queries(r, pools, coin_in, amount_out, coin_out, true)
+end
+
+# both directions: `amount_in` is the GIVEN amount (the wanted output when exact_out), the result the answer
+function quote_queries(r::AMDRouter, pools, coin_in, amount_in, coin_out, exact_out::Bool)
     n = length(pools)
     (length(coin_in) == n && length(amount_in) == n && (isnothing(coin_out) || length(coin_out) == n)) ||
-        throw(ArgumentError("coin_in, amount_in and coin_out must have one entry per pool"))
+        throw(ArgumentError("coin_in, the amounts and coin_out must have one entry per pool"))
     where = segment_rows(r)
     segs = Dict{Int32,Vector{Int}}()                      # segment => query numbers
     for (q, i) in enumerate(pools)
@@ -480,9 +493,14 @@ function quote_swaps(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::Ab
         co = isnothing(coin_out) ? Int32[] : Int32[coin_out[q] - 1 for q in qs]
         amt = Float64[amount_in[q] for q in qs]
         res = Vector{Float64}(undef, length(qs))
-        GC.@preserve idx ci co amt res check(r.ctx, ccall((:cfmm_quote, LIB), Cint,
+        cop = isnothing(coin_out) ? C_NULL : pointer(co)
+        GC.@preserve idx ci co amt res check(r.ctx, exact_out ?
+            ccall((:cfmm_quote_out, LIB), Cint,
+                  (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                  r.ctx, s, length(qs), idx, ci, cop, amt, res) :
+            ccall((:cfmm_quote, LIB), Cint,
             (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
-            r.ctx, s, length(qs), idx, ci, isnothing(coin_out) ? C_NULL : pointer(co), amt, res))
+            r.ctx, s, length(qs), idx, ci, cop, amt, res))
         out[qs] .= res
     end
     return out
@@ -508,6 +526,26 @@ function forward_trade(Δ::AbstractVector{<:Real}, cfmm::DeviceQuotedPool; coin_
     nt = Int(maximum(cfmm.Ai))
     r = AMDRouter(CFMMRouter.LinearNonnegative(ones(nt)), [cfmm], nt; device=device)
     return quote_swaps(r, [1], [pos[1]], [Float64(Δ[pos[1]])]; coin_out=isnothing(coin_out) ? nothing : [coin_out])[1]
+end
+
+# backward_trade(Λ, cfmm) -- the mirror of forward_trade (the reference has none): Λ has exactly one positive entry, the amount
+# wanted at the position of its coin; returns the amount of the other coin -- of coin coin_in (1-based; required on pools of
+# more than two coins) -- that must be tendered, Inf where the pool cannot give Λ.  Λ == 0 returns 0.0.  One pool through the
+# device (a one-pool AMDRouter), as forward_trade.
+function backward_trade(Λ::AbstractVector{<:Real}, cfmm::DeviceQuotedPool; coin_in=nothing, device=0)
+    n = length(cfmm.Ai)
+    length(Λ) == n || throw(ArgumentError("Λ must have $n entries"))
+    (all(isfinite, Λ) && all(>=(0), Λ)) || throw(ArgumentError("Λ must be finite and >= 0"))
+    pos = findall(>(0), Λ)
+    length(pos) <= 1 || throw(ArgumentError("Λ must have exactly one positive entry (one coin out)"))
+    (isnothing(coin_in) && n > 2) && throw(ArgumentError("coin_in is required on a pool of $n coins"))
+    (isnothing(coin_in) || 1 <= coin_in <= n) || throw(ArgumentError("coin_in $coin_in out of range 1:$n"))
+    isempty(pos) && return 0.0
+    (!isnothing(coin_in) && coin_in == pos[1]) && throw(ArgumentError("coin_in is the wanted coin"))
+    cin = isnothing(coin_in) ? 3 - pos[1] : coin_in
+    nt = Int(maximum(cfmm.Ai))
+    r = AMDRouter(CFMMRouter.LinearNonnegative(ones(nt)), [cfmm], nt; device=device)
+    return quote_swaps_out(r, [1], [cin], [Float64(Λ[pos[1]])]; coin_out=[pos[1]])[1]
 end
 
 # Optional fast path: the whole of route! inside the library (cfmm_route: its own L-BFGS-B, the

@@ -251,4 +251,18 @@ end
     end
 end
 
+@testset "quote_swaps_out: the input for a wanted output, the inverse of quote_swaps" begin
+    pools = random_product_market(50, 8; seed=9, fee=0.997)
+    r = AMDRouter(LinearNonnegative(rand(8)), pools, 8)
+    which = collect(1:50)
+    cin = [1 + i % 2 for i in which]
+    want = [0.1 * pools[i].R[3 - cin[i]] for i in which]                 # a tenth of the other reserve
+    a = quote_swaps_out(r, which, cin, want)
+    @test all(a[i] ≈ pools[i].R[cin[i]] * want[i] / ((pools[i].R[3 - cin[i]] - want[i]) * 0.997) for i in which)
+    @test all(isapprox.(quote_swaps(r, which, cin, a), want; rtol=1e-12))
+    @test quote_swaps_out(r, [1], [1], [2 * pools[1].R[2]])[1] == Inf       # more than the pool holds: not an error
+    @test backward_trade([0.0, want[1]], pools[1]) ≈ a[1] || cin[1] != 1
+    @test backward_trade([0.0, 0.0], pools[1]) == 0.0
+end
+
 end
