@@ -21,6 +21,7 @@ ERR_INVALID_ARG = -1
 ERR_HIP = -2
 ERR_STATE = -3
 ERR_UNSUPPORTED = -4
+MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -135,6 +136,10 @@ def lib():
     L.cfmm_quote_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_out.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_quote_out_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_quote_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
+    L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
+    L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -523,6 +528,62 @@ class Context:
         self._check(self._L.cfmm_quote_out_dev(self._h, int(seg), int(count), C.c_void_p(d_idx or None), C.c_void_p(d_coin_in or None),
                                                C.c_void_p(d_coin_out or None), C.c_void_p(d_amount_out or None),
                                                C.c_void_p(d_amount_in or None)))
+
+    # -- multi-hop path quotes (cfmm_quote_path / cfmm_quote_path_out): an amount through a path of pools of any segments ----
+    def quote_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, hops=False):
+        """amount_out [count] of carrying amount_in [count] through paths of n_hops[p] hops (1 .. MAX_PATH_HOPS): hop k of
+        path p enters row hop_row[p, k] of segment hop_seg[p, k] with coin hop_coin_in[p, k] and leaves with hop_coin_out[p, k]
+        (positions in the pool's own coin order).  The hop arguments are [count, max_hops] arrays (slots at k >= n_hops[p]
+        are ignored).  Every hop is quoted against the pool as it stands: no state advances between hops.  hops=True: also
+        the [max_hops, count] amounts leaving each hop (NaN in the unused slots).  Everything is checked before anything
+        runs (ArgumentError names the path and the hop)."""
+        return self._quote_path("cfmm_quote_path", n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, hops)
+
+    def quote_path_out(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_out, hops=False):
+        """The inverse of quote_path (cfmm_quote_path_out): amount_in [count] to tender to the first hop so that exactly
+        amount_out [count] leaves the last, walked from the last hop backwards; +inf from the hop on (towards the first)
+        where a pool cannot give that much.  hops=True: also the [max_hops, count] amounts to tender to each hop."""
+        return self._quote_path("cfmm_quote_path_out", n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_out, hops)
+
+    def _quote_path(self, entry, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, given, hops):
+        amt = f64(given).reshape(-1)
+        n = amt.size
+        nh = np.ascontiguousarray(n_hops, dtype=np.int32).reshape(-1)
+        if nh.size != n:
+            raise ArgumentError("n_hops must have one entry per amount")
+        cols = []
+        for name, a, dt in (("hop_seg", hop_seg, np.int32), ("hop_row", hop_row, np.int64), ("hop_coin_in", hop_coin_in, np.int32),
+                            ("hop_coin_out", hop_coin_out, np.int32)):
+            a = np.asarray(a, dtype=dt)
+            if a.ndim == 1:                                                   # one hop per path
+                a = a.reshape(-1, 1)
+            if a.ndim != 2 or a.shape[0] != n or (cols and a.shape != cols[0].shape):
+                raise ArgumentError(f"{name} must be a [count, max_hops] array, like the other hop arguments")
+            cols.append(a)
+        if n == 0:
+            return (np.empty(0), np.empty((max(1, cols[0].shape[1]), 0))) if hops else np.empty(0)
+        max_hops = int(cols[0].shape[1])
+        seg, row, ci, co = (np.ascontiguousarray(a.T) for a in cols)          # the ABI's layout: hop-major, [max_hops][count]
+        out = np.empty(n)
+        hv = np.empty((max_hops, n)) if hops else None
+        self._check(getattr(self._L, entry)(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(out),
+                                            ptr(hv)))
+        return (out, hv) if hops else out
+
+    def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
+                       d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):
+        """cfmm_quote_path_dev on device addresses (int32 n_hops / segments / coins, int64 rows, float64 amounts; the hop
+        arrays in the ABI's own hop-major [max_hops][count] layout; d_hop_out 0 = NULL): asynchronous on the context's
+        stream, unchecked -- a bad path or hop gets NaN from there on, nothing is read out of bounds."""
+        self._check(self._L.cfmm_quote_path_dev(self._h, int(count), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out, d_amount_in, d_amount_out, d_hop_out))))
+
+    def quote_path_out_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
+                           d_hop_coin_out: int, d_amount_out: int, d_amount_in: int, d_hop_in: int = 0):
+        """cfmm_quote_path_out_dev on device addresses, as quote_path_dev: d_amount_out [count] is read (the wanted outputs),
+        d_amount_in [count] and d_hop_in (0 = NULL) are written."""
+        self._check(self._L.cfmm_quote_path_out_dev(self._h, int(count), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out, d_amount_out, d_amount_in, d_hop_in))))
 
     def set_peers(self, peer_ptrs, world: int, rank: int, seq: int):
         """Sharded operation: every host-pointer sweep of this context ends with the one-shot peer

@@ -16,6 +16,8 @@
 //   ladder_store.h    LadderStore: a UniV3 segment's tick ladders on the host, one pool's replaceable (no HIP)
 //   abi_quote.cpp     exact-input swap quotes (cfmm_quote / cfmm_quote_dev; forward_trade generalised) and their inverses, the
 //                     exact-output quotes (cfmm_quote_out / cfmm_quote_out_dev)
+//   abi_quote_path.cpp  multi-hop path quotes across segments (cfmm_quote_path / _out and their _dev forms; path_checks.h: the
+//                     HIP-free checks)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -231,6 +233,22 @@ struct QuoteScratch {
     bool dev_timed = false;            // the latest timed call was cfmm_quote_dev: its span is read when asked for
 };
 
+// cfmm_quote_path and cfmm_quote_path_out (abi_quote_path.cpp, quote_path_kernels.h; one scratch for both directions): the
+// device copies of one call's paths, amounts, answers and optional hop amounts, the segment table (sweep.h PathSeg) and ONE
+// pinned staging buffer for all of them -- proportional to count x max_hops (and the number of segments), never to the pools.
+// The table is rebuilt and uploaded on every call; `done`, recorded behind each call's kernel, guards the staging and the
+// table against the call before (the _dev entries do not wait).  The kernel's span goes to QuoteScratch's events and "quote_ns".
+struct PathScratch {
+    DevBuf<PathSeg> table;             // [segments]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> hop_row;         // [max_hops][count]
+    DevBuf<double> given, answer;      // [count]
+    DevBuf<double> hops;               // [max_hops][count]
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
+    Event done;                        // behind the latest call's kernel
+    bool in_flight = false;
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -352,6 +370,7 @@ struct cfmm_ctx {
     int64_t pool_update_regrows = 0;   // read-only option "pool_update_regrows": compactions + regrows of UniV3 tick arrays
     cfmm::SelectScratch sel;
     cfmm::QuoteScratch quote;
+    cfmm::PathScratch path;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own

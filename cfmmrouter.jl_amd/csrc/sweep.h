@@ -418,6 +418,52 @@ hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const
 hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
                             hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_quote_path / cfmm_quote_path_out (quote_path_kernels.h, abi_quote_path.cpp): an amount carried through a PATH of up
+// to CFMM_MAX_PATH_HOPS pools of any segments in one launch, one lane per path.  The first kernels that read several segments
+// of different kinds at once: the segments reach them as a TABLE in device memory (a market may have more segments than fit
+// in kernel arguments), one PathSeg each -- the kind, the sizes and exactly the pointers quote_one<KIND> reads.  The table is
+// rebuilt from the segments' `.get()` addresses and uploaded on EVERY call (abi_quote_path.cpp): it is never a cache.
+struct PathSeg {
+    int32_t kind;                // CFMM_KIND_*, or -1: a segment without pools (no hop can be valid on it; nothing is read)
+    int32_t n_coins;             // 2, or the ragged segment's coin count
+    int64_t m;                   // pools of the segment
+    // two-coin kinds (QuoteArgs::R / w / gamma)
+    const double2* R;
+    const double2* w;
+    const double* gamma;
+    // UniV3: the seven members of UniV3Pools the quotes read
+    const double2* pg;
+    const double2* cur_a;
+    const double2* cur_b;
+    const double* cur_c;
+    const double2* curR;
+    const int4* walk;
+    const TickRec* ticks;
+    // weighted / Curve: the four members of NCoinPools the quotes read
+    const double* nR;
+    const double* nq;
+    const double2* nglg;
+    const double* npar;
+};
+struct PathArgs {
+    int64_t count;               // paths
+    int32_t max_hops;            // rows of the hop arrays, 1 .. CFMM_MAX_PATH_HOPS
+    int32_t nseg;                // records of `segs`
+    const PathSeg* segs;         // [nseg] device
+    const int32_t* n_hops;       // [count]; outside 1 .. max_hops: the whole path is NaN and no hop is evaluated
+    // hop-major: hop k of path p at k*count + p (neighbouring lanes read neighbouring words); slots at k >= n_hops[p] unread
+    const int32_t* hop_seg;
+    const long long* hop_row;
+    const int32_t* hop_coin_in;
+    const int32_t* hop_coin_out;
+    const double* given;         // [count] amount_in (quote_path_kernel) / the wanted amount_out (quote_path_out_kernel)
+    double* answer;              // [count]
+    double* hops;                // [max_hops][count] or null: the amount leaving hop k / the amount to tender to hop k; NaN in
+                                 // the unused slots
+};
+// exact_out picks quote_path_out_kernel.  e0, e1: both set = the launch is timed by the command processor.
+hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

@@ -42,6 +42,7 @@
 //   update_kernels.h  update_two_coin, expand_trades, update_ncoin, scatter_records, compact_walks
 //   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
 //   quote_kernels.h   quote_kernel, quote_out_kernel (cfmm_quote, cfmm_quote_out; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised, and their inverses)
+//   quote_path_kernels.h  quote_path_kernel, quote_path_out_kernel (cfmm_quote_path, cfmm_quote_path_out: the same bodies, hop after hop)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -56,6 +57,7 @@
 #include "update_kernels.h"
 #include "select_kernels.h"
 #include "quote_kernels.h"
+#include "quote_path_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -300,12 +302,17 @@ hipError_t launch_reduce_gather(const double* partials, int rows, int n1, int pi
 }
 
 // one lane per query, at most one machine of resident threads (the lanes stride over the rest)
+static hipError_t launch_quote_grid(const void* kernel, int64_t count, void** args, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    const int64_t blocks = std::min<int64_t>((count + kQuoteBlock - 1) / kQuoteBlock, kResidentThreads / kQuoteBlock);
+    return launch_k(kernel, dim3((unsigned)blocks), dim3(kQuoteBlock), 0, s, e0, e1, args);
+}
+
 static hipError_t launch_quote_k(const void* kernel, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
                                  hipEvent_t e0, hipEvent_t e1)
 {
-    const int64_t blocks = std::min<int64_t>((a.count + kQuoteBlock - 1) / kQuoteBlock, kResidentThreads / kQuoteBlock);
     void* args[] = {const_cast<QuoteArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
-    return launch_k(kernel, dim3((unsigned)blocks), dim3(kQuoteBlock), 0, s, e0, e1, args);
+    return launch_quote_grid(kernel, a.count, args, s, e0, e1);
 }
 
 hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
@@ -339,6 +346,15 @@ hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, c
     default: return hipErrorInvalidDeviceFunction;   // no such kernel
     }
     return launch_quote_k(kernel, a, u, n, s, e0, e1);
+}
+
+// one lane per path, the same grid rule
+hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.count <= 0 || a.nseg <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS) return hipErrorInvalidValue;
+    void* args[] = {const_cast<PathArgs*>(&a)};
+    const void* kernel = exact_out ? reinterpret_cast<const void*>(&quote_path_out_kernel<kQuoteBlock>) : reinterpret_cast<const void*>(&quote_path_kernel<kQuoteBlock>);
+    return launch_quote_grid(kernel, a.count, args, s, e0, e1);
 }
 
 } // namespace cfmm

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from ._lib import MAX_PATH_HOPS, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
 from .layout import PoolLayout
 from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
@@ -743,6 +743,75 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out):
         qs, rows = per_batch[b]
         out[qs] = getattr(ctx, verb)(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
     return out
+
+
+def quote_path(r: Router, pools, tokens, amount_in, hops=False):
+    """Exact-input quotes of swap PATHS on the pools as they stand on the device (cfmm_quote_path): `amount_in[p]` of token
+    `tokens[p][0]` goes into pool `pools[p][0]`, what comes out goes into `pools[p][1]`, ... and the result is what leaves
+    the path's last pool, in one launch for all paths whatever kinds the pools are.
+
+    `pools[p]` is a sequence of 1 .. 8 positions in `r.cfmms`; `tokens[p]` the token ids along the path (1-based as in
+    `Ai`), one more than the pools: hop k trades `tokens[p][k]` for `tokens[p][k+1]`.  Paths may differ in length.
+    EVERY HOP IS QUOTED AGAINST THE POOL AS IT STANDS -- no state advances between hops -- which is why a pool may appear
+    only once in a path.  ArgumentError (naming path and hop) for a token that is not one of the pool's coins or is the same
+    on both sides, a repeated pool, a host-evaluated pool, or more than 8 pools.  hops=True: also the [max_hops, count]
+    amounts leaving each hop (NaN where a path has no such hop).  Read-only, like `quote`."""
+    return _quote_path(r, "quote_path", pools, tokens, amount_in, hops)
+
+
+def quote_path_out(r: Router, pools, tokens, amount_out, hops=False):
+    """Exact-output quotes of swap paths, the inverse of `quote_path` (cfmm_quote_path_out): how much of `tokens[p][0]`
+    must be tendered to `pools[p][0]` so that exactly `amount_out[p]` of `tokens[p][-1]` leaves the path's last pool, walked
+    from the last hop backwards.  +inf where a pool on the way cannot give that much.  Arguments and refusals are those of
+    `quote_path`; hops=True: also the [max_hops, count] amounts to tender to each hop."""
+    return _quote_path(r, "quote_path_out", pools, tokens, amount_out, hops)
+
+
+def _quote_path(r: Router, verb, pools, tokens, amount, hops):
+    L = r._layout
+    pools, tokens = list(pools), list(tokens)
+    n = len(pools)
+    if len(tokens) != n:
+        raise ArgumentError("tokens must have one sequence per path")
+    try:
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
+    except ValueError:
+        raise ArgumentError(f"{'amount_in' if verb == 'quote_path' else 'amount_out'} must be a scalar or have one entry per path") from None
+    paths = [(np.asarray(pl, dtype=np.int64).reshape(-1), np.asarray(tk, dtype=np.int64).reshape(-1)) for pl, tk in zip(pools, tokens)]
+    for p, (pl, tk) in enumerate(paths):
+        if not 1 <= pl.size <= MAX_PATH_HOPS:
+            raise ArgumentError(f"path {p}: {pl.size} pools (a path has 1 to {MAX_PATH_HOPS})")
+        if tk.size != pl.size + 1:
+            raise ArgumentError(f"path {p}: {tk.size} tokens for {pl.size} pools (one more than the pools)")
+    H = max((pl.size for pl, _ in paths), default=1)
+    n_hops = np.array([pl.size for pl, _ in paths], dtype=np.int32)
+    seg, ci, co = (np.zeros((n, H), dtype=np.int32) for _ in range(3))
+    row = np.zeros((n, H), dtype=np.int64)
+    for p, (pl, tk) in enumerate(paths):
+        seen = set()
+        for k, i in enumerate(pl.tolist()):
+            where = L.locate(i)
+            if where[0] == "host":
+                raise ArgumentError(f"path {p}, hop {k}: pool {i}: {type(r._host.pools[where[1]]).__name__} is evaluated on the "
+                                    f"host by its own find_arb_ and has no device state to quote")
+            if i in seen:
+                raise ArgumentError(f"path {p}, hop {k}: pool {i} appears twice (every hop is quoted against the pool as it "
+                                    f"stands, so a second visit would ignore the first)")
+            seen.add(i)
+            Ai = L.batches[where[1]].Ai[where[2]]
+            pos = []
+            for t in (int(tk[k]), int(tk[k + 1])):
+                at = np.flatnonzero(Ai == t)
+                if at.size == 0:
+                    raise ArgumentError(f"path {p}, hop {k}: token {t} is not a coin of pool {i} (its coins: {Ai.tolist()})")
+                pos.append(int(at[0]))
+            if pos[0] == pos[1]:
+                raise ArgumentError(f"path {p}, hop {k}: token {int(tk[k])} on both sides of pool {i}")
+            seg[p, k], row[p, k], ci[p, k], co[p, k] = L.seg_of[where[1]], where[2], pos[0], pos[1]
+    ctx = getattr(r._backend, "ctx", None)
+    if ctx is None:
+        raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
+    return getattr(ctx, verb)(n_hops, seg, row, ci, co, amt, hops)
 
 
 def _update_reserves_host(r: Router):

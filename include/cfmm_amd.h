@@ -384,6 +384,52 @@ int cfmm_quote_out(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx
 int cfmm_quote_out_dev(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* d_idx, const int32_t* d_coin_in,
                        const int32_t* d_coin_out, const double* d_amount_out, double* d_amount_in);
 
+/* Multi-hop path quotes: an amount carried through a PATH of pools that may lie in different segments (and therefore be of
+ * different kinds), one launch for all paths.  (The reference has no such function; each hop is the constraint of
+ * src/cfmms.jl:26-31 as in cfmm_quote / cfmm_quote_out.)  A path has 1 .. CFMM_MAX_PATH_HOPS hops; a hop is
+ * (segment, row, coin_in, coin_out), coins being positions in the pool's own coin order.
+ *   cfmm_quote_path      exact input:  x_0 = amount_in[p], x_{k+1} = quote(hop k, x_k); amount_out[p] = x_H.
+ *   cfmm_quote_path_out  exact output: y_H = amount_out[p], y_k = quote_out(hop k, y_{k+1}), walked from the last hop to the
+ *                        first; amount_in[p] = y_0.  Once a hop answers +inf (that pool cannot give that much) every earlier
+ *                        hop and the answer are +inf and no further form is evaluated: an answer, not an error.  NaN likewise.
+ * The per-hop arithmetic is cfmm_quote's / cfmm_quote_out's own: the result and every intermediate amount equal, bit for bit,
+ * what chaining those calls hop by hop gives (UniV3: an exhausted ladder returns the direction's whole output, same direction rule).
+ * EVERY HOP IS QUOTED AGAINST THE POOL AS IT STANDS: no state advances between hops.  A path that visits a pool twice has its
+ * second visit quoted as if the first had not happened; the call does not refuse such a path.  Amounts pass from hop to hop
+ * whatever the tokens are: token continuity is the caller's business.
+ *   n_hops        [count], each 1 .. max_hops.       max_hops  1 .. CFMM_MAX_PATH_HOPS: the rows of the hop arrays.
+ *   hop_seg, hop_row, hop_coin_in, hop_coin_out   [max_hops][count], HOP-MAJOR: hop k of path p at k*count + p.  Slots at
+ *                 k >= n_hops[p] are ignored.  hop_coin_out is always required (there is no "other coin" default here).
+ *   hop_out       NULL, or [max_hops][count]: hop_out[k*count+p] = the amount leaving hop k (so the entry of a path's last hop
+ *                 equals amount_out[p]).   hop_in: hop_in[k*count+p] = the amount to tender to hop k (hop_in[p] == amount_in[p]).
+ *                 Unused slots are written as NaN.
+ * The host-pointer entries check everything before anything is enqueued: count >= 0, max_hops, every n_hops, every used
+ * hop's segment, row and coins in range for that segment, coins distinct, the given amount finite and >= 0.  A failure is
+ * CFMM_ERR_INVALID_ARG, names the path and the hop ("cfmm_quote_path: path 12, hop 3: row ...") and leaves the outputs
+ * untouched.  Synchronous on the context's stream; read-only exactly as cfmm_quote; count == 0 is a no-op; large-market mode
+ * needs nothing special; on a context sharded with cfmm_set_peers or RCCL the call is local to the rank.  On a multi-device
+ * context a path's hops may sit on different shards: the paths are walked hop level by hop level through cfmm_quote /
+ * cfmm_quote_out (one call per level and segment with an active path), the +inf / NaN rule applied on the host -- the same bits.
+ * "quote_ns" reports the latest call of any quote entry (a multi-device context: the longest span among the calls this entry made). */
+#define CFMM_MAX_PATH_HOPS 8
+int cfmm_quote_path(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                    const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
+                    double* amount_out, double* hop_out);
+int cfmm_quote_path_out(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                        const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_out,
+                        double* amount_in, double* hop_in);
+/* The same on device arrays: asynchronous on the context's stream; checks only the scalars and null pointers (d_hop_out /
+ * d_hop_in may be NULL).  The library cannot validate device memory: an n_hops outside 1 .. max_hops makes that path NaN with
+ * no hop evaluated; a hop with an out-of-range segment, row or coin, equal coins, or a negative or non-finite amount is clamped
+ * before any read and yields NaN, which then passes through the path's remaining hops.  Nothing is read out of bounds and
+ * neighbouring paths are unaffected.  Single-device contexts only. */
+int cfmm_quote_path_dev(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* d_n_hops, const int32_t* d_hop_seg,
+                        const int64_t* d_hop_row, const int32_t* d_hop_coin_in, const int32_t* d_hop_coin_out,
+                        const double* d_amount_in, double* d_amount_out, double* d_hop_out);
+int cfmm_quote_path_out_dev(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* d_n_hops, const int32_t* d_hop_seg,
+                            const int64_t* d_hop_row, const int32_t* d_hop_coin_in, const int32_t* d_hop_coin_out,
+                            const double* d_amount_out, double* d_amount_in, double* d_hop_in);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

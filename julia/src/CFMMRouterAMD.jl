@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, quote_swaps_out, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -504,6 +504,64 @@ function quote_queries(r::AMDRouter, pools, coin_in, amount_in, coin_out, exact_
         out[qs] .= res
     end
     return out
+end
+
+# quote_paths(r, pools, tokens, amount_in; hops=false) -- the Python host's router-level `quote_path` (cfmm_quote_path): amount_in[p]
+# of token tokens[p][1] carried through the pools pools[p] (1 .. 8 positions in r.cfmms) in one launch, whatever kinds they
+# are: hop k trades tokens[p][k] for tokens[p][k+1] (token ids as in Ai, one more than the pools).  EVERY HOP IS QUOTED
+# AGAINST THE POOL AS IT STANDS -- no state advances between hops -- so a pool may appear only once in a path.  The coin
+# positions are found in the pool's Ai and converted to the library's 0-based ones here.  ArgumentError, naming path and
+# hop, for a token that is not a coin of the pool or is the same on both sides, a repeated pool, a host-evaluated pool,
+# more than 8 pools.  hops=true: also the [count, max_hops] amounts leaving each hop (NaN where a path has no such hop).
+function quote_paths(r::AMDRouter, pools::AbstractVector, tokens::AbstractVector, amount_in::AbstractVector{<:Real}; hops::Bool=false)
+    return quote_path_queries(r, pools, tokens, amount_in, hops, false)
+end
+
+# quote_paths_out(r, pools, tokens, amount_out; hops=false) -- the inverse (cfmm_quote_path_out): what to tender to the first pool
+# so that exactly amount_out[p] leaves the last, walked from the last hop backwards; Inf where a pool on the way cannot give
+# that much.  hops=true: also the amounts to tender to each hop.
+function quote_paths_out(r::AMDRouter, pools::AbstractVector, tokens::AbstractVector, amount_out::AbstractVector{<:Real}; hops::Bool=false)
+    return quote_path_queries(r, pools, tokens, amount_out, hops, true)
+end
+
+const MAX_PATH_HOPS = 8   # CFMM_MAX_PATH_HOPS
+
+function quote_path_queries(r::AMDRouter, pools, tokens, given, hops::Bool, exact_out::Bool)
+    n = length(pools)
+    (length(tokens) == n && length(given) == n) || throw(ArgumentError("tokens and the amounts must have one entry per path"))
+    where = segment_rows(r)
+    H = max(1, maximum(length, pools; init=1))
+    n_hops = Int32[length(p) for p in pools]
+    seg = zeros(Int32, n, H); ci = zeros(Int32, n, H); co = zeros(Int32, n, H)     # column-major [count, max_hops] IS the
+    row = zeros(Int64, n, H)                                                       # library's hop-major layout
+    for p in 1:n
+        1 <= length(pools[p]) <= MAX_PATH_HOPS || throw(ArgumentError("path $p: $(length(pools[p])) pools (a path has 1 to $MAX_PATH_HOPS)"))
+        length(tokens[p]) == length(pools[p]) + 1 || throw(ArgumentError("path $p: $(length(tokens[p])) tokens for $(length(pools[p])) pools"))
+        for (k, i) in enumerate(pools[p])
+            i in r.host && throw(ArgumentError("path $p, hop $k: pool $i: $(typeof(r.cfmms[i])) is evaluated on the host by its own find_arb! and has no device state to quote"))
+            haskey(where, i) || throw(ArgumentError("path $p, hop $k: pool $i out of range"))
+            i in pools[p][1:k-1] && throw(ArgumentError("path $p, hop $k: pool $i appears twice (every hop is quoted against the pool as it stands)"))
+            a = findfirst(==(tokens[p][k]), r.cfmms[i].Ai)
+            b = findfirst(==(tokens[p][k+1]), r.cfmms[i].Ai)
+            (isnothing(a) || isnothing(b)) && throw(ArgumentError("path $p, hop $k: token $(isnothing(a) ? tokens[p][k] : tokens[p][k+1]) is not a coin of pool $i"))
+            a == b && throw(ArgumentError("path $p, hop $k: token $(tokens[p][k]) on both sides of pool $i"))
+            seg[p, k], row[p, k] = where[i]
+            ci[p, k] = a - 1; co[p, k] = b - 1                                      # 0-based for the library
+        end
+    end
+    amt = Float64[given[p] for p in 1:n]
+    out = Vector{Float64}(undef, n)
+    hv = fill(NaN, n, H)
+    n == 0 && return hops ? (out, hv) : out
+    hp = hops ? pointer(hv) : Ptr{Float64}(C_NULL)
+    GC.@preserve n_hops seg row ci co amt out hv check(r.ctx, exact_out ?
+        ccall((:cfmm_quote_path_out, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              r.ctx, n, H, n_hops, seg, row, ci, co, amt, out, hp) :
+        ccall((:cfmm_quote_path, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+              r.ctx, n, H, n_hops, seg, row, ci, co, amt, out, hp))
+    return hops ? (out, hv) : out
 end
 
 # forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449: methods of CFMMRouter's own function (imported above) for the pool kinds it

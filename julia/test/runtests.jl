@@ -265,4 +265,21 @@ end
     @test backward_trade([0.0, 0.0], pools[1]) == 0.0
 end
 
+
+@testset "quote_paths / quote_paths_out: an amount through a path of pools, hop by hop on the pools as they stand" begin
+    pools = random_product_market(50, 8; seed=10, fee=0.997)
+    r = AMDRouter(LinearNonnegative(rand(8)), pools, 8)
+    # two-hop paths through pools that share a token
+    pairs = [(i, j) for i in 1:50 for j in 1:50 if i != j && pools[i].Ai[2] == pools[j].Ai[1]][1:min(end, 20)]
+    paths = [[i, j] for (i, j) in pairs]
+    toks = [[pools[i].Ai[1], pools[i].Ai[2], pools[j].Ai[2]] for (i, j) in pairs]
+    a = [0.05 * pools[i].R[1] for (i, _) in pairs]
+    out, hv = quote_paths(r, paths, toks, a; hops=true)
+    mid = quote_swaps(r, [i for (i, _) in pairs], fill(1, length(pairs)), a)
+    @test hv[:, 1] == mid                                                     # the bits of chaining the single-pool quote
+    @test out == quote_swaps(r, [j for (_, j) in pairs], fill(1, length(pairs)), mid) && hv[:, 2] == out
+    back = quote_paths_out(r, paths, toks, 0.5 .* out)
+    @test all(back .< a)
+    @test_throws ArgumentError quote_paths(r, [[1, 1]], [[pools[1].Ai[1], pools[1].Ai[2], pools[1].Ai[1]]], [1.0])
+end
 end
