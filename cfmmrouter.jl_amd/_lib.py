@@ -136,6 +136,7 @@ def lib():
     L.cfmm_quote_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_out.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_quote_out_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_swap.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_quote_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -495,6 +496,13 @@ class Context:
         """The inverse of quote (cfmm_quote_out): amount_in [count] of coin_in to tender so that exactly amount_out [count]
         of coin_out comes out; same arguments and checks.  +inf where the pool cannot give that much (not an error)."""
         return self._quote("cfmm_quote_out", seg, amount_out, coin_in, coin_out, idx)
+
+    def swap(self, seg: int, amount_in, coin_in, coin_out=None, idx=None):
+        """quote's arguments, but the swaps are APPLIED (cfmm_swap), in query order: amount_out[q] is what quote answers on the
+        pool as swaps 0 .. q-1 left it, and the pool then moves to R + γΔ − Λ (UniV3: to the price the swap rests at).  A row
+        named k times is swapped k times.  A swap that would leave an invalid pool is not applied and answers NaN
+        (get_option("swap_refused") counts them).  A state change: earlier trades and outputs are invalidated."""
+        return self._quote("cfmm_swap", seg, amount_in, coin_in, coin_out, idx)
 
     def _quote(self, entry, seg, given, coin_in, coin_out, idx):
         amt = f64(given).reshape(-1)

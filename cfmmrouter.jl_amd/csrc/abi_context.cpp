@@ -331,6 +331,10 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     // reports the longest span among the shards its latest call touched (abi_quote.cpp multi_quote).  After cfmm_quote_dev
     // the span is not known until the kernel has run: the read waits for it and stores it, the one thing a getter changes
     if (key && !std::strcmp(key, "quote_ns")) return quote_ns(const_cast<cfmm_ctx*>(c), value);
+    // read-only, cfmm_swap: the sum of the kernel spans of the latest call's waves timed under "time_kernels" (a parent: the
+    // longest among the shards that call touched), and the number of that call's swaps that were not applied (NaN answers)
+    if (key && !std::strcmp(key, "swap_ns")) { *value = c->swap.ns; return CFMM_OK; }
+    if (key && !std::strcmp(key, "swap_refused")) { *value = c->swap.refused; return CFMM_OK; }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
     // option "time_kernels" (a parent reports its first shard's)
     if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }

@@ -54,34 +54,13 @@ hipError_t launch_for(const cfmm_ctx* c, const Dir& dir, const Segment& s, const
     return (dir.exact_out ? launch_quote_out : launch_quote)(s.kind, a, u, n, c->stream, e0, e1);
 }
 
-int check_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t nseg)
-{
-    if (seg < 0 || seg >= nseg) return fail(c, CFMM_ERR_INVALID_ARG, "%s: segment out of range", who);
-    if (count < 0) return fail(c, CFMM_ERR_INVALID_ARG, "%s: count must be >= 0", who);
-    return CFMM_OK;
-}
+int check_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t nseg) { return check_quote_seg(c, who, seg, count, nseg); }
 
 // every query of a host-pointer call, before anything is enqueued
 int check_queries(cfmm_ctx* c, const Dir& dir, int kind, int64_t m, int nc, int64_t count, const int64_t* idx, const int32_t* coin_in,
                   const int32_t* coin_out, const double* given, const double* answer)
 {
-    const char* who = dir.host;
-    if (count > 0 && (!coin_in || !given || !answer)) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null query array", who);
-    if (count > 0 && !coin_out && ragged_kind(kind))
-        return fail(c, CFMM_ERR_INVALID_ARG, "%s: coin_out is required on a %s segment (query 0)", who, kind_info(kind).name);
-    for (int64_t q = 0; q < count; ++q) {
-        const int64_t row = idx ? idx[q] : q;
-        if (row < 0 || row >= m)
-            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: row %lld out of range (segment has %lld pools)", who,
-                        (long long)q, (long long)row, (long long)m);
-        const int ci = coin_in[q], co = coin_out ? coin_out[q] : 1 - ci;
-        if (ci < 0 || ci >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in %d out of range (pool has %d coins)", who, (long long)q, ci, nc);
-        if (co < 0 || co >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_out %d out of range (pool has %d coins)", who, (long long)q, co, nc);
-        if (ci == co) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in and coin_out are both %d", who, (long long)q, ci);
-        if (!(given[q] >= 0.0) || !std::isfinite(given[q]))
-            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: %s must be finite and >= 0", who, (long long)q, dir.given);
-    }
-    return CFMM_OK;
+    return check_quote_queries(c, dir.host, dir.given, kind, m, nc, count, idx, coin_in, coin_out, given, answer);
 }
 
 int quote_host(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
@@ -249,6 +228,35 @@ int cfmm_quote_out_dev(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* d
 }
 
 namespace cfmm {
+
+int check_quote_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t nseg)
+{
+    if (seg < 0 || seg >= nseg) return fail(c, CFMM_ERR_INVALID_ARG, "%s: segment out of range", who);
+    if (count < 0) return fail(c, CFMM_ERR_INVALID_ARG, "%s: count must be >= 0", who);
+    return CFMM_OK;
+}
+
+// every query of a host-pointer call, before anything is enqueued (cfmm_swap runs the same checks under its own name)
+int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, int kind, int64_t m, int nc, int64_t count,
+                        const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out, const double* given, const double* answer)
+{
+    if (count > 0 && (!coin_in || !given || !answer)) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null query array", who);
+    if (count > 0 && !coin_out && ragged_kind(kind))
+        return fail(c, CFMM_ERR_INVALID_ARG, "%s: coin_out is required on a %s segment (query 0)", who, kind_info(kind).name);
+    for (int64_t q = 0; q < count; ++q) {
+        const int64_t row = idx ? idx[q] : q;
+        if (row < 0 || row >= m)
+            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: row %lld out of range (segment has %lld pools)", who,
+                        (long long)q, (long long)row, (long long)m);
+        const int ci = coin_in[q], co = coin_out ? coin_out[q] : 1 - ci;
+        if (ci < 0 || ci >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in %d out of range (pool has %d coins)", who, (long long)q, ci, nc);
+        if (co < 0 || co >= nc) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_out %d out of range (pool has %d coins)", who, (long long)q, co, nc);
+        if (ci == co) return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: coin_in and coin_out are both %d", who, (long long)q, ci);
+        if (!(given[q] >= 0.0) || !std::isfinite(given[q]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: %s must be finite and >= 0", who, (long long)q, given_name);
+    }
+    return CFMM_OK;
+}
 
 // read-only option "quote_ns": the span of the latest call's kernel (of either direction) timed under "time_kernels"
 int quote_ns(cfmm_ctx* c, int64_t* value)

@@ -1,0 +1,235 @@
+// abi_swap.cpp -- cfmm_swap: exact-input swaps of one segment's pools that MOVE the pools (include/cfmm_amd.h has the
+// contract).  Each swap answers what cfmm_quote answers on the pool as it stands (swap_kernels.h runs quote_one itself) and
+// then leaves the pool at R + γΔ − Λ (src/cfmms.jl:26-31; swap_pool.h: the per-kind forms).  The swaps of a batch are applied
+// in query order: the host cuts the batch into waves of distinct rows (swap_waves.h) and launches them in stream order.
+// The reserve kinds synchronise once, at the end; UniV3 -- whose state is its price, with records prepared on the host --
+// reads the wave's landing prices back and moves the pools through cfmm_pools_set_prices' own apply path (abi_update.cpp
+// univ3_move_prices) before the next wave.  The only memory of the feature is SwapScratch (ctx.h), proportional to the
+// swaps of a call and never to the pools.
+#include "ctx.h"
+#include "swap_waves.h"
+#include "univ3_pool.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+using namespace cfmm;
+
+namespace {
+
+constexpr const char* kWho = "cfmm_swap";
+
+// the kernel's view of segment `s`; the wave's query arrays are filled in by the caller
+hipError_t launch_wave(const cfmm_ctx* c, const Segment& s, const SwapArgs& w, hipEvent_t e0, hipEvent_t e1)
+{
+    SwapArgs a = w;
+    a.q.m = s.m;
+    a.q.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
+    a.q.R = s.R.get();
+    a.q.w = s.w.get();
+    a.q.gamma = s.gamma.get();
+    a.R = s.R.get();
+    a.Q = s.lR.get();
+    a.eta = s.eta.get();
+    a.ncR = s.nc.R.get();
+    a.ncq = s.nc.q.get();
+    UniV3Pools u;
+    NCoinPools n;
+    std::memset(&u, 0, sizeof u);
+    std::memset(&n, 0, sizeof n);
+    if (s.kind == CFMM_KIND_UNIV3) {   // (fresh addresses per wave: a moved pool may have regrown the record arrays)
+        const UniV3State& st = s.u;
+        u.pg = st.pg.get();
+        u.cur_a = st.cur_a.get();
+        u.cur_b = st.cur_b.get();
+        u.cur_c = st.cur_c.get();
+        u.curR = st.curR.get();
+        u.walk = st.walk.get();
+        u.ticks = st.ticks.get();
+    } else if (ragged_kind(s.kind)) {
+        n.R = s.nc.R.get();
+        n.q = s.nc.q.get();
+        n.glg = s.nc.glg.get();
+        n.par = s.nc.par.get();
+        n.n_coins = s.n_coins;
+    }
+    return launch_swap(s.kind, a, u, n, c->stream, e0, e1);
+}
+
+// the trades and outputs on the device describe the market before the swaps: as cfmm_pools_set_* (abi_update.cpp apply)
+void invalidate(cfmm_ctx* c)
+{
+    c->have_trades = false;
+    c->have_out = false;
+    c->x_valid = false;
+    c->trade_v.clear();
+}
+
+// One checked call on a single-device context
+int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+                const double* amount_in, double* amount_out)
+{
+    Segment& s = c->segs[(size_t)seg];
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SwapPlan plan = swap_plan(count, idx);
+    const int64_t waves = (int64_t)plan.wave_off.size() - 1;
+    const bool univ3 = s.kind == CFMM_KIND_UNIV3;
+    const bool flagged = !univ3 && kind_info(s.kind).has_fast;
+    const bool timed = c->opt_time_kernels != 0;
+    SwapScratch& sc = c->swap;
+    const size_t n = (size_t)count;
+    int rc;
+    if ((rc = sc.stage.grow(c, 5 * n + 1, false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
+        (idx && (rc = sc.idx.grow(c, n))) || (univ3 && (rc = sc.price.grow(c, n))) || (flagged && (rc = sc.left.grow(c, 1))))
+        return rc;
+    if (timed) {
+        if (sc.ev.size() < 2 * (size_t)waves) sc.ev.resize(2 * (size_t)waves);
+        for (size_t k = 0; k < 2 * (size_t)waves; ++k)
+            if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
+    }
+    // pinned staging, the swaps in launch order
+    unsigned long long* st = sc.stage.host();
+    double* h_amt = reinterpret_cast<double*>(st);
+    int32_t* h_coins = reinterpret_cast<int32_t*>(st + n);   // [count] coin_in, then [count] coin_out
+    double* h_out = reinterpret_cast<double*>(st + 2 * n);
+    double* h_price = reinterpret_cast<double*>(st + 3 * n);
+    long long* h_idx = reinterpret_cast<long long*>(st + 4 * n);
+    int* h_left = reinterpret_cast<int*>(st + 5 * n);
+    for (size_t j = 0; j < n; ++j) {
+        const size_t q = (size_t)plan.perm[j];
+        h_amt[j] = amount_in[q];
+        h_coins[j] = coin_in[q];
+        if (coin_out) h_coins[n + j] = coin_out[q];
+        if (idx) h_idx[j] = idx[q];
+    }
+    *h_left = 0;
+    armed_cancel(c);
+    HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.coins.get(), h_coins, (coin_out ? 2 : 1) * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (idx) HIP_TRY(c, hipMemcpyAsync(sc.idx.get(), h_idx, n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    if (flagged) HIP_TRY(c, hipMemsetAsync(sc.left.get(), 0, sizeof(int), c->stream));
+    invalidate(c);   // from the first launch on the pools count as moved
+    std::vector<char> refused_at(univ3 ? n : 0, 0);   // UniV3: the landing price was no state a pool can take
+    std::vector<int64_t> rows;
+    std::vector<double> prices;
+    for (int64_t w = 0; w < waves; ++w) {
+        const size_t off = (size_t)plan.wave_off[(size_t)w], nw = (size_t)plan.wave_off[(size_t)w + 1] - off;
+        SwapArgs a{};
+        a.q.count = (int64_t)nw;
+        a.q.idx = idx ? sc.idx.get() + off : nullptr;
+        a.q.coin_in = sc.coins.get() + off;
+        a.q.coin_out = coin_out ? sc.coins.get() + n + off : nullptr;
+        a.q.amount_in = sc.amt.get() + off;
+        a.q.amount_out = sc.out.get() + off;
+        a.price = univ3 ? sc.price.get() + off : nullptr;
+        a.left_window = flagged ? sc.left.get() : nullptr;
+        const hipError_t e = launch_wave(c, s, a, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
+        if (!univ3) continue;
+        // the wave's landing prices, 8 bytes per swap; then the pools move as cfmm_pools_set_prices moves them
+        HIP_TRY(c, hipMemcpyAsync(h_price + off, sc.price.get() + off, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        rows.clear();
+        prices.clear();
+        for (size_t j = off; j < off + nw; ++j) {
+            const int64_t row = idx ? idx[plan.perm[j]] : plan.perm[j];
+            double P = h_price[j];
+            if (!finite_pos(P)) {   // check_univ3_price would refuse it: the pool stays
+                refused_at[j] = 1;
+                continue;
+            }
+            const double top = s.lad.lower_ticks(row)[0];   // out of liquidity on that side: the first tick's upper price
+            P = P > top ? top : P;
+            if (std::memcmp(&P, &s.h_cp[(size_t)row], sizeof P) == 0) continue;   // (a == 0, no liquidity: where it was)
+            rows.push_back(row);
+            prices.push_back(P);
+        }
+        if ((rc = univ3_move_prices(c, s, rows, prices.data())) != CFMM_OK) return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (flagged) HIP_TRY(c, hipMemcpyAsync(h_left, sc.left.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (flagged && *h_left) s.fast_ok = 0;   // (never sent back: as cfmm_update_reserves)
+    if (timed) {
+        double ms_sum = 0.0;
+        for (int64_t w = 0; w < waves; ++w) {
+            float ms = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[2 * (size_t)w].get(), sc.ev[2 * (size_t)w + 1].get()));
+            ms_sum += (double)ms;
+        }
+        sc.ns = (int64_t)(ms_sum * 1e6);
+    }
+    int64_t refused = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const double o = univ3 && refused_at[j] ? std::nan("") : h_out[j];
+        refused += o != o;
+        amount_out[plan.perm[j]] = o;
+    }
+    sc.refused = refused;
+    return CFMM_OK;
+}
+
+// A parent: the swaps go to the shards that hold their rows (shard_range: contiguous blocks in device order), each shard's in
+// the caller's order -- a row lives on one shard, so per-row order is kept -- and the answers return in query order, as
+// multi_quote.  The caller has run every check there is, for every shard, before any shard changes.
+int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+               const double* amount_in, double* amount_out)
+{
+    const int64_t m = c->psegs[(size_t)seg].m;
+    const int nd = (int)c->shards.size();
+    std::vector<int64_t> first((size_t)nd), end((size_t)nd);
+    for (int d = 0; d < nd; ++d) shard_range(m, d, nd, first[(size_t)d], end[(size_t)d]);
+    struct Bucket {
+        std::vector<int64_t> where, rows;
+        std::vector<int32_t> ci, co;
+        std::vector<double> amt;
+    };
+    std::vector<Bucket> buckets((size_t)nd);
+    for (int64_t q = 0; q < count; ++q) {
+        const int64_t row = idx ? idx[q] : q;
+        const size_t d = (size_t)(std::upper_bound(end.begin(), end.end(), row) - end.begin());   // first shard whose end > row
+        Bucket& bk = buckets[d];
+        bk.where.push_back(q);
+        bk.rows.push_back(row - first[d]);
+        bk.ci.push_back(coin_in[q]);
+        if (coin_out) bk.co.push_back(coin_out[q]);
+        bk.amt.push_back(amount_in[q]);
+    }
+    c->have_trades = c->have_out = false;
+    std::vector<double> out;
+    int64_t ns = 0, refused = 0;
+    for (int d = 0; d < nd; ++d) {
+        const Bucket& bk = buckets[(size_t)d];
+        if (bk.where.empty()) continue;
+        out.resize(bk.where.size());
+        cfmm_ctx* child = c->shards[(size_t)d];
+        const int rc = swap_single(child, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
+                                   coin_out ? bk.co.data() : nullptr, bk.amt.data(), out.data());
+        if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s (some shards may have moved)", d, child->err.c_str());
+        for (size_t j = 0; j < bk.where.size(); ++j) amount_out[bk.where[j]] = out[j];
+        if (child->opt_time_kernels != 0) ns = std::max(ns, child->swap.ns);
+        refused += child->swap.refused;
+    }
+    c->swap.ns = ns;   // "swap_ns" of a parent: the longest among the shards THIS call touched
+    c->swap.refused = refused;
+    return CFMM_OK;
+}
+
+} // namespace
+
+extern "C" int cfmm_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+                         const double* amount_in, double* amount_out)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    const bool parent = !c->shards.empty();
+    int rc = check_quote_seg(c, kWho, seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
+    if (rc != CFMM_OK) return rc;
+    const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
+    const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
+    const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
+    if ((rc = check_quote_queries(c, kWho, "amount_in", kind, m, nc, count, idx, coin_in, coin_out, amount_in, amount_out)) != CFMM_OK) return rc;
+    if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
+    return parent ? multi_swap(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out)
+                  : swap_single(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out);
+}

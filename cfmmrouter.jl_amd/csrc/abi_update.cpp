@@ -441,6 +441,16 @@ int update(cfmm_ctx* c, const Update& u)
 
 } // namespace
 
+int cfmm::univ3_move_prices(cfmm_ctx* c, Segment& s, const std::vector<int64_t>& rows, const double* price)
+{
+    if (rows.empty()) return CFMM_OK;
+    Rows r;
+    r.idx = rows;
+    r.src.resize(rows.size());
+    for (size_t k = 0; k < rows.size(); ++k) r.src[k] = (int64_t)k;
+    return apply_univ3(c, s, Update{kSetPrices, 0, (int64_t)rows.size(), rows.data(), nullptr, nullptr, nullptr, price, nullptr, nullptr, nullptr}, r);
+}
+
 // The staging buffer with room for `words` 8-byte words, free for the host to fill: the previous scatter has read it
 int cfmm::UpdateStaging::reserve(cfmm_ctx* c, size_t words)
 {

@@ -18,6 +18,8 @@
 //                     exact-output quotes (cfmm_quote_out / cfmm_quote_out_dev)
 //   abi_quote_path.cpp  multi-hop path quotes across segments (cfmm_quote_path / _out and their _dev forms; path_checks.h: the
 //                     HIP-free checks)
+//   abi_swap.cpp      exact-input swaps that move the pools (cfmm_swap: the quote, then R + γΔ − Λ; swap_waves.h: the HIP-free
+//                     wave numbering of repeated rows)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -249,6 +251,20 @@ struct PathScratch {
     bool in_flight = false;
 };
 
+// cfmm_swap (abi_swap.cpp, swap_kernels.h): the device copies of one call's swaps -- in WAVE order (swap_waves.h) -- their
+// answers, the UniV3 landing prices and the pinned staging of all of them, grown on demand and kept for the next call --
+// proportional to the swaps of the largest call, never to the pools.
+struct SwapScratch {
+    DevBuf<long long> idx;             // [count]
+    DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out
+    DevBuf<double> amt, out, price;    // [count]; price: UniV3 segments only
+    DevBuf<int> left;                  // [1] a new reserve left the window of the fast arithmetic (update_two_coin's flag)
+    PinnedBuf<unsigned long long> stage;   // [5][count] + 1 8-byte words: amounts, coins, answers, prices, idx, the flag
+    std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
+    int64_t ns = 0;                    // read-only option "swap_ns": the sum of that call's kernel spans
+    int64_t refused = 0;               // read-only option "swap_refused": swaps of the latest call that were not applied
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -371,6 +387,7 @@ struct cfmm_ctx {
     cfmm::SelectScratch sel;
     cfmm::QuoteScratch quote;
     cfmm::PathScratch path;
+    cfmm::SwapScratch swap;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
@@ -435,6 +452,17 @@ int multi_select_trades(cfmm_ctx* c, int32_t seg, const double* v, double min_va
 
 // abi_quote.cpp
 int quote_ns(cfmm_ctx* c, int64_t* value);
+// cfmm_quote's checks of one call under the name `who` (`given`: how the messages spell the amount), before anything is
+// enqueued: the segment and count, then every query.  n_segs, kind, m, nc: the segment as the context (single or parent) sees it.
+int check_quote_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t n_segs);
+int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, int kind, int64_t m, int nc, int64_t count,
+                        const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out, const double* given, const double* answer);
+
+// abi_update.cpp
+// cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not
+// above the row's first tick): apply_univ3 for the records prepared on the host, univ3_make_room, one scatter; h_cp follows.
+// Enqueued on the context's stream; invalidates nothing by itself (the caller does).
+int univ3_move_prices(cfmm_ctx* c, Segment& s, const std::vector<int64_t>& rows, const double* price);
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

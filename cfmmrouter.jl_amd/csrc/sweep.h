@@ -418,6 +418,22 @@ hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const
 hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
                             hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_swap (swap_kernels.h, abi_swap.cpp): exact-input swaps that move the pools, one lane per swap of ONE WAVE -- queries whose
+// rows are distinct (the host numbers the waves).  `q` is the wave's view as quote_kernel takes it; the members below are the
+// segment's own arrays again, writable.  The n_coins kinds write through ncR / ncq (NCoinPools::R / ::q of the same launch).
+struct SwapArgs {
+    QuoteArgs q;
+    double2* R;                  // two-coin kinds: [m] reserves
+    double2* Q;                  // GeometricMean: [m] {Q1, Q2}
+    const double* eta;           // GeometricMean: [m] η
+    double* ncR;                 // weighted / Curve: [n_coins][m]
+    double* ncq;
+    double* price;               // UniV3: [count] the price each swap comes to rest at (the kernel changes no UniV3 state)
+    int* left_window;            // <- 1 when a new reserve lies outside [2^-kFastExp, 2^kFastExp] (kinds with a fast arithmetic), or null
+};
+hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0 = nullptr,
+                       hipEvent_t e1 = nullptr);
+
 // cfmm_quote_path / cfmm_quote_path_out (quote_path_kernels.h, abi_quote_path.cpp): an amount carried through a PATH of up
 // to CFMM_MAX_PATH_HOPS pools of any segments in one launch, one lane per path.  The first kernels that read several segments
 // of different kinds at once: the segments reach them as a TABLE in device memory (a market may have more segments than fit

@@ -43,6 +43,7 @@
 //   select_kernels.h  select_flag, select_scan, select_emit (cfmm_select_trades)
 //   quote_kernels.h   quote_kernel, quote_out_kernel (cfmm_quote, cfmm_quote_out; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised, and their inverses)
 //   quote_path_kernels.h  quote_path_kernel, quote_path_out_kernel (cfmm_quote_path, cfmm_quote_path_out: the same bodies, hop after hop)
+//   swap_kernels.h    swap_kernel (cfmm_swap: quote_one's answer, then the pool's new state; swap_pool.h: the per-kind new-state forms)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -58,6 +59,7 @@
 #include "select_kernels.h"
 #include "quote_kernels.h"
 #include "quote_path_kernels.h"
+#include "swap_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -355,6 +357,24 @@ hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, h
     void* args[] = {const_cast<PathArgs*>(&a)};
     const void* kernel = exact_out ? reinterpret_cast<const void*>(&quote_path_out_kernel<kQuoteBlock>) : reinterpret_cast<const void*>(&quote_path_kernel<kQuoteBlock>);
     return launch_quote_grid(kernel, a.count, args, s, e0, e1);
+}
+
+// one lane per swap of the wave, the same grid rule
+hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.q.count <= 0 || a.q.m <= 0) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_PRODUCT>); break;
+    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_GEOMEAN>); break;
+    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_UNIV3>); break;
+    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_WEIGHTED>); break;
+    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_CURVE>); break;
+    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_SOLIDLY>); break;
+    default: return hipErrorInvalidDeviceFunction;   // no such kernel
+    }
+    void* args[] = {const_cast<SwapArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_quote_grid(kernel, a.q.count, args, s, e0, e1);
 }
 
 } // namespace cfmm

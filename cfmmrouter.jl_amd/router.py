@@ -716,7 +716,24 @@ def quote_out(r: Router, pools, coin_in, amount_out, coin_out=None):
     return _quote(r, "quote_out", pools, coin_in, amount_out, coin_out)
 
 
-def _quote(r: Router, verb, pools, coin_in, amount, coin_out):
+def swap_(r: Router, pools, coin_in, amount_in, coin_out=None, sync_host=True):
+    """Exact-input swaps APPLIED to the pools on the device (cfmm_swap): `quote`'s arguments and mapping of pool numbers to
+    (segment, row), but every swap moves its pool to R + γΔ − Λ (UniV3: to the price it rests at) and the next swap of the
+    same pool starts from there -- "apply this pending swap, then route_ for the back-run".
+
+    Each segment's swaps go through one call, in the caller's order within the segment, so a pool named k times is swapped
+    k times in the order given; the amounts that came out return in the caller's order.  A swap that would leave an invalid
+    pool (a reserve driven to 0, say) is not applied and answers NaN.  A host-evaluated plugin pool has no device state:
+    ArgumentError, before anything moves.  sync_host=True (default) also refreshes the host mirror of the touched segments
+    (`r.cfmms[i].R`, `current_price`).  The router's trades are those of the old market: they are zeroed, as by
+    update_pools_."""
+    try:
+        return _quote(r, "swap", pools, coin_in, amount_in, coin_out, sync_host=sync_host)
+    finally:
+        r._reset_trades()
+
+
+def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False):
     L = r._layout
     pools = np.asarray(pools, dtype=np.int64).reshape(-1)
     n = pools.size
@@ -725,7 +742,7 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out):
         ci = np.ascontiguousarray(np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,)))
         co = None if coin_out is None else np.ascontiguousarray(np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,)))
     except ValueError:
-        raise ArgumentError(f"{'amount_in' if verb == 'quote' else 'amount_out'}, coin_in and coin_out must be scalars or have one entry per pool") from None
+        raise ArgumentError(f"{'amount_out' if verb == 'quote_out' else 'amount_in'}, coin_in and coin_out must be scalars or have one entry per pool") from None
     per_batch = {}
     for q, i in enumerate(pools):
         where = L.locate(i)
@@ -742,6 +759,9 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out):
     for b in sorted(per_batch):
         qs, rows = per_batch[b]
         out[qs] = getattr(ctx, verb)(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
+        if sync_host:   # (swap_: the host mirror of the segment follows the device)
+            _download_state(ctx, L.seg_of[b], L.batches[b])
+            L.sync_pools(r.cfmms, b, sorted(set(rows)))
     return out
 
 

@@ -430,6 +430,50 @@ int cfmm_quote_path_out_dev(cfmm_ctx* ctx, int64_t count, int32_t max_hops, cons
                             const int64_t* d_hop_row, const int32_t* d_hop_coin_in, const int32_t* d_hop_coin_out,
                             const double* d_amount_out, double* d_amount_in, double* d_hop_in);
 
+/* Exact-input swaps that MOVE the pools: "tender amount_in of coin_in to this pool, take what comes out, and carry on from
+ * the market that leaves behind" -- the other half of cfmm_quote.  (The reference has no such function; the move is the update
+ * of src/cfmms.jl:26-31 that cfmm_update_reserves applies to the router's own trades.)  The argument list is cfmm_quote's:
+ * seg, idx (NULL: rows 0 .. count-1), coin_in, coin_out (NULL allowed on two-coin and UniV3 segments, refused on weighted /
+ * Curve), amount_in finite and >= 0.  All of cfmm_quote's checks run before anything is enqueued: a failure is
+ * CFMM_ERR_INVALID_ARG, names the query in cfmm_last_error with the prefix "cfmm_swap:", and leaves amount_out AND the
+ * pools untouched.
+ * The swaps are applied IN QUERY ORDER.  For q = 0, 1, ...: amount_out[q] is exactly, bit for bit, what cfmm_quote answers
+ * for that query on the pool as it stands after swaps 0 .. q-1; the pool then moves to R + γΔ − Λ with Δ = amount_in·e_in,
+ * Λ = amount_out·e_out.  A row named k times is swapped k times, each from the state the previous one left.
+ *   Reserve kinds (Product, GeometricMean, Solidly, weighted, Curve): R_in <- R_in + γ·a, R_out <- R_out − out, each operation
+ *     rounded on its own; the other coins are untouched.  The prepared constants are refreshed on the device with
+ *     cfmm_update_reserves' expressions: GeometricMean {Q1, Q2}; weighted q = log(R/w) and Curve q = log R for the two coins
+ *     that moved (Curve's α and β stay).  amount_in == 0 leaves every bit of the pool.  A reserve leaving the window of the
+ *     fast arithmetic sends the segment to full-range arithmetic for good, as cfmm_update_reserves does.
+ *   UniV3: the state is the price.  The new price is computed on the device from the record the swap lands in -- inside the
+ *     current tick when it holds liquidity and γa < its δmax, else record e of the direction's walk list with
+ *     d_t = γa − Σδmax_e clamped to [0, δmax_e]; with s' = s_in + d_t, P = k/(s'·s') for coin 0 in (price falling) and
+ *     P = (s'·s')/k for coin 1 in (price rising).  A swap that exhausts the direction answers cfmm_quote's whole output and
+ *     rests at the far edge of the direction's last non-empty tick (that tick at d_t = δmax).  amount_in == 0, or a direction
+ *     without any liquidity, leaves the price where it is.  The host reads the new prices back (8 bytes per swap), clamps
+ *     each to the pool's first tick's upper price as cfmm_update_reserves does, and moves the pools through
+ *     cfmm_pools_set_prices' own apply path: afterwards the context equals, bit for bit on every output, a context freshly
+ *     uploaded at cfmm_get_prices' values.
+ * A swap that would leave a pool cfmm_pools_set_* refuses -- a new reserve that is not finite and > 0 (a huge amount_in on a
+ * Product pool, where x/(R_in + x) rounds to 1), a Solidly reserve outside [2^-150, 2^150], a Curve log(P0/R_k) outside the
+ * solve's range, a UniV3 price that is not finite and > 0 -- is NOT APPLIED: that pool stays exactly as it was, its amount_out
+ * is NaN, later swaps of the same row proceed from the unchanged state, and the call still returns CFMM_OK.  The read-only
+ * option "swap_refused" is the number of such swaps in the latest call.
+ * cfmm_swap is a state change, not a query: it invalidates the trades and outputs of earlier sweeps exactly as
+ * cfmm_pools_set_reserves does (cfmm_get_trades* then fail with "no materialised trades", a pre-armed cfmm_route is
+ * cancelled).  Synchronous on the context's stream, behind earlier sweeps and updates.  count == 0 is a no-op that
+ * invalidates nothing.  Needs no sweep to have run; large-market mode needs nothing special; on a context sharded with
+ * cfmm_set_peers or RCCL the call is local to the rank.  On a multi-device context the swaps go to the shards that hold
+ * their rows (a row lives on one shard, so per-row order is kept), the answers return in query order, and every check runs
+ * before any shard changes.  Device memory of the call is proportional to count, never to the pools.
+ * Repeated rows are ordered on the host: swap q runs in launch number (earlier queries on the same row), each launch holds
+ * distinct rows only.  A batch of distinct rows is one launch; UniV3 re-prepares the moved pools on the host after each launch.
+ * There is NO cfmm_swap_dev: the order of repeated rows is decided on the host, and an unchecked device array cannot promise it.
+ * Read-only option under "time_kernels": "swap_ns", the sum of the kernel spans of the latest call (a multi-device context:
+ * the longest among the shards that call touched). */
+int cfmm_swap(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+              const int32_t* coin_out, const double* amount_in, double* amount_out);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -366,42 +366,46 @@ function update_reserves!(r::AMDRouter; sync::Bool=true)
         CFMMRouter.update_reserves!(r.cfmms[i], r.Δs[i], r.Λs[i], r.v[r.cfmms[i].Ai])
     end
     check(r.ctx, ccall((:cfmm_update_reserves, LIB), Cint, (Ptr{Cvoid},), r.ctx))
-    if sync
-        seg, pos = Int32(0), 0
-        for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3, SolidlyStableTwoCoin)
-            idx = [i for i in r.order[pos+1:end] if r.cfmms[i] isa T]   # r.order is grouped by family
-            isempty(idx) && continue
-            if T === UniV3
-                p = Vector{Float64}(undef, length(idx))
-                GC.@preserve p check(r.ctx, ccall((:cfmm_get_prices, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, p))
-                for (k, i) in enumerate(idx)
-                    c = r.cfmms[i]
-                    r.cfmms[i] = UniV3(p[k], c.lower_ticks, c.liquidity, c.γ, c.Ai)   # re-derives current_tick (:235)
-                end
-            else
-                R = Matrix{Float64}(undef, 2, length(idx))
-                GC.@preserve R check(r.ctx, ccall((:cfmm_get_reserves, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, R))
-                for (k, i) in enumerate(idx)
-                    r.cfmms[i].R .= @view R[:, k]
-                end
+    sync && download_state!(r)
+    foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
+    return nothing
+end
+
+# the host-side pool objects <- the device: reserves of every reserve kind, current prices of the UniV3 pools
+function download_state!(r::AMDRouter)
+    seg, pos = Int32(0), 0
+    for T in (ProductTwoCoin, GeometricMeanTwoCoin, UniV3, SolidlyStableTwoCoin)
+        idx = [i for i in r.order[pos+1:end] if r.cfmms[i] isa T]   # r.order is grouped by family
+        isempty(idx) && continue
+        if T === UniV3
+            p = Vector{Float64}(undef, length(idx))
+            GC.@preserve p check(r.ctx, ccall((:cfmm_get_prices, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, p))
+            for (k, i) in enumerate(idx)
+                c = r.cfmms[i]
+                r.cfmms[i] = UniV3(p[k], c.lower_ticks, c.liquidity, c.γ, c.Ai)   # re-derives current_tick (:235)
             end
-            seg += Int32(1); pos += length(idx)
-        end
-        # weighted segments follow, one per coin count, then Curve segments (build_router); Curve's α, β stay
-        for curve in (false, true), n in 2:8
-            idx = [i for i in r.order[pos+1:end] if (curve ? r.cfmms[i] isa Curve :
-                                                     (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product)) &&
-                                                    length(r.cfmms[i].Ai) == n]
-            isempty(idx) && continue
-            R = Matrix{Float64}(undef, n, length(idx))
+        else
+            R = Matrix{Float64}(undef, 2, length(idx))
             GC.@preserve R check(r.ctx, ccall((:cfmm_get_reserves, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, R))
             for (k, i) in enumerate(idx)
                 r.cfmms[i].R .= @view R[:, k]
             end
-            seg += Int32(1); pos += length(idx)
         end
+        seg += Int32(1); pos += length(idx)
     end
-    foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
+    # weighted segments follow, one per coin count, then Curve segments (build_router); Curve's α, β stay
+    for curve in (false, true), n in 2:8
+        idx = [i for i in r.order[pos+1:end] if (curve ? r.cfmms[i] isa Curve :
+                                                 (r.cfmms[i] isa GeometricMean || r.cfmms[i] isa Product)) &&
+                                                length(r.cfmms[i].Ai) == n]
+        isempty(idx) && continue
+        R = Matrix{Float64}(undef, n, length(idx))
+        GC.@preserve R check(r.ctx, ccall((:cfmm_get_reserves, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), r.ctx, seg, R))
+        for (k, i) in enumerate(idx)
+            r.cfmms[i].R .= @view R[:, k]
+        end
+        seg += Int32(1); pos += length(idx)
+    end
     return nothing
 end
 
@@ -471,6 +475,47 @@ end
 function quote_swaps_out(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
                          amount_out::AbstractVector{<:Real}; coin_out=nothing)
     return quote_queries(r, pools, coin_in, amount_out, coin_out, true)
+end
+
+# swap!(r, pools, coin_in, amount_in; coin_out) -- the Python host's `swap_` (cfmm_swap): quote_swaps' arguments, but every swap
+# is APPLIED.  The swaps of a segment go through one call in the caller's order, so a pool named k times is swapped k times,
+# each from the state the previous one left; amount_out[q] is what quote_swaps answers on the pool as the earlier swaps left
+# it, and the pool then moves to R + γΔ − Λ (UniV3: to the price the swap rests at).  A swap that would leave an invalid pool
+# is not applied and answers NaN.  sync = true refreshes the host-side pool objects; the router's trades are those of the old
+# market and are zeroed, as by update_pools!.
+function swap!(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
+               amount_in::AbstractVector{<:Real}; coin_out=nothing, sync::Bool=true)
+    n = length(pools)
+    (length(coin_in) == n && length(amount_in) == n && (isnothing(coin_out) || length(coin_out) == n)) ||
+        throw(ArgumentError("coin_in, the amounts and coin_out must have one entry per pool"))
+    where = segment_rows(r)
+    segs = Dict{Int32,Vector{Int}}()                      # segment => query numbers, in the caller's order
+    for (q, i) in enumerate(pools)
+        i in r.host && throw(ArgumentError("pool $i: $(typeof(r.cfmms[i])) is evaluated on the host by its own find_arb! and has no device state to quote"))
+        haskey(where, i) || throw(ArgumentError("pool $i out of range"))
+        push!(get!(segs, where[i][1], Int[]), q)
+    end
+    out = Vector{Float64}(undef, n)
+    try
+        for s in sort(collect(keys(segs)))
+            qs = segs[s]
+            idx = Int64[where[pools[q]][2] for q in qs]
+            ci = Int32[coin_in[q] - 1 for q in qs]
+            co = isnothing(coin_out) ? Int32[] : Int32[coin_out[q] - 1 for q in qs]
+            amt = Float64[amount_in[q] for q in qs]
+            res = Vector{Float64}(undef, length(qs))
+            cop = isnothing(coin_out) ? C_NULL : pointer(co)
+            GC.@preserve idx ci co amt res check(r.ctx,
+                ccall((:cfmm_swap, LIB), Cint,
+                      (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                      r.ctx, s, length(qs), idx, ci, cop, amt, res))
+            out[qs] .= res
+        end
+        sync && download_state!(r)
+    finally
+        foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
+    end
+    return out
 end
 
 # both directions: `amount_in` is the GIVEN amount (the wanted output when exact_out), the result the answer

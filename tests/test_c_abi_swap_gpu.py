@@ -1,0 +1,29 @@
+"""cfmm_swap used from plain C (no Python, no torch in the process): tests/c/abi_swap.c."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build(tmp_path):
+    exe = str(tmp_path / "abi_swap")
+    libdir = os.path.join(ROOT, "cfmmrouter.jl_amd")
+    subprocess.run(["gcc", "-O1", "-std=gnu11", "-Wall", "-Werror", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
+                    os.path.join(ROOT, "tests", "c", "abi_swap.c"), "-o", exe, "-L", libdir, "-lcfmm_amd", "-Wl,-rpath," + libdir,
+                    "-Wl,-rpath,/opt/rocm/lib", "-lm"], check=True)
+    return exe
+
+
+def test_plain_c_swap_client_compiles(tmp_path):
+    """CPU: the declaration is valid C11 and the client links against the library"""
+    build(tmp_path)
+
+
+@pytest.mark.gpu
+def test_plain_c_swap_client(tmp_path):
+    r = subprocess.run([build(tmp_path)], capture_output=True, text=True, timeout=120)
+    print(r.stdout, r.stderr[-2000:])
+    assert r.returncode == 0 and "abi_swap: ok" in r.stdout
+    assert "cfmm_swap: query 2" in r.stdout and "swap_refused 1" in r.stdout and "refused swap: nan" in r.stdout.lower()
