@@ -22,6 +22,7 @@ ERR_HIP = -2
 ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
+PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = 0, 1, 2   # CFMM_PATH_*: Context.swap_path's status
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -137,6 +138,7 @@ def lib():
     L.cfmm_quote_out.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_quote_out_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_swap.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
+    L.cfmm_swap_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]
     L.cfmm_quote_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -556,6 +558,42 @@ class Context:
     def _quote_path(self, entry, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, given, hops):
         amt = f64(given).reshape(-1)
         n = amt.size
+        nh, seg, row, ci, co = self._path_columns(n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        if n == 0:
+            return (np.empty(0), np.empty((max(1, seg.shape[0]), 0))) if hops else np.empty(0)
+        max_hops = int(seg.shape[0])
+        out = np.empty(n)
+        hv = np.empty((max_hops, n)) if hops else None
+        self._check(getattr(self._L, entry)(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(out),
+                                            ptr(hv)))
+        return (out, hv) if hops else out
+
+    # -- multi-hop path execution (cfmm_swap_path): quote_path's arguments, the paths applied in order, each all or nothing ----
+    def swap_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, min_out=None, hops=False):
+        """quote_path's arguments, but the paths are APPLIED (cfmm_swap_path), in query order, each all or nothing: returns
+        (amount_out, status[, hop_out]).  status[p] is PATH_APPLIED (amount_out[p] is what quote_path answers on the market
+        the applied paths before p left, and every hop's pool has moved as `swap` moves it), PATH_BELOW_LIMIT (amount_out[p]
+        < min_out[p]: the quote it would have given, nothing moved) or PATH_REFUSED (a hop would leave an invalid pool:
+        NaN, nothing moved).  min_out: None, a scalar or one limit per path.  A pool may appear only once in a path.  A
+        state change: earlier trades and outputs are invalidated; get_option("swap_refused") counts the paths not applied."""
+        amt = f64(amount_in).reshape(-1)
+        n = amt.size
+        nh, seg, row, ci, co = self._path_columns(n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        lim = None
+        if min_out is not None:
+            try:
+                lim = np.ascontiguousarray(np.broadcast_to(np.asarray(min_out, dtype=np.float64), (n,)))
+            except ValueError:
+                raise ArgumentError("min_out must be a scalar or have one entry per amount") from None
+        max_hops = max(1, int(seg.shape[0]))
+        out, st = np.empty(n), np.empty(n, dtype=np.int32)
+        hv = np.empty((max_hops, n)) if hops else None
+        self._check(self._L.cfmm_swap_path(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(lim),
+                                           ptr(out), ptr(hv), ptr(st)))
+        return (out, st, hv) if hops else (out, st)
+
+    def _path_columns(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n):
+        """n_hops and the four [count, max_hops] hop arguments, checked and in the ABI's layout: hop-major, [max_hops][count]"""
         nh = np.ascontiguousarray(n_hops, dtype=np.int32).reshape(-1)
         if nh.size != n:
             raise ArgumentError("n_hops must have one entry per amount")
@@ -568,15 +606,7 @@ class Context:
             if a.ndim != 2 or a.shape[0] != n or (cols and a.shape != cols[0].shape):
                 raise ArgumentError(f"{name} must be a [count, max_hops] array, like the other hop arguments")
             cols.append(a)
-        if n == 0:
-            return (np.empty(0), np.empty((max(1, cols[0].shape[1]), 0))) if hops else np.empty(0)
-        max_hops = int(cols[0].shape[1])
-        seg, row, ci, co = (np.ascontiguousarray(a.T) for a in cols)          # the ABI's layout: hop-major, [max_hops][count]
-        out = np.empty(n)
-        hv = np.empty((max_hops, n)) if hops else None
-        self._check(getattr(self._L, entry)(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(out),
-                                            ptr(hv)))
-        return (out, hv) if hops else out
+        return (nh, *(np.ascontiguousarray(a.T) for a in cols))
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
                        d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):

@@ -335,6 +335,7 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     // longest among the shards that call touched), and the number of that call's swaps that were not applied (NaN answers)
     if (key && !std::strcmp(key, "swap_ns")) { *value = c->swap.ns; return CFMM_OK; }
     if (key && !std::strcmp(key, "swap_refused")) { *value = c->swap.refused; return CFMM_OK; }
+    if (key && !std::strcmp(key, "swap_launches")) { *value = c->swap.launches; return CFMM_OK; }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
     // option "time_kernels" (a parent reports its first shard's)
     if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }

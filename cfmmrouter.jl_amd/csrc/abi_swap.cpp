@@ -57,15 +57,6 @@ hipError_t launch_wave(const cfmm_ctx* c, const Segment& s, const SwapArgs& w, h
     return launch_swap(s.kind, a, u, n, c->stream, e0, e1);
 }
 
-// the trades and outputs on the device describe the market before the swaps: as cfmm_pools_set_* (abi_update.cpp apply)
-void invalidate(cfmm_ctx* c)
-{
-    c->have_trades = false;
-    c->have_out = false;
-    c->x_valid = false;
-    c->trade_v.clear();
-}
-
 // One checked call on a single-device context
 int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
                 const double* amount_in, double* amount_out)
@@ -109,7 +100,7 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
     HIP_TRY(c, hipMemcpyAsync(sc.coins.get(), h_coins, (coin_out ? 2 : 1) * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     if (idx) HIP_TRY(c, hipMemcpyAsync(sc.idx.get(), h_idx, n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
     if (flagged) HIP_TRY(c, hipMemsetAsync(sc.left.get(), 0, sizeof(int), c->stream));
-    invalidate(c);   // from the first launch on the pools count as moved
+    swap_invalidate(c);   // from the first launch on the pools count as moved
     std::vector<char> refused_at(univ3 ? n : 0, 0);   // UniV3: the landing price was no state a pool can take
     std::vector<int64_t> rows;
     std::vector<double> prices;
@@ -167,6 +158,7 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
         amount_out[plan.perm[j]] = o;
     }
     sc.refused = refused;
+    sc.launches = waves;
     return CFMM_OK;
 }
 
@@ -213,10 +205,21 @@ int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
     }
     c->swap.ns = ns;   // "swap_ns" of a parent: the longest among the shards THIS call touched
     c->swap.refused = refused;
+    c->swap.launches = 0;
+    for (const cfmm_ctx* child : c->shards) c->swap.launches += child->swap.launches;   // (of the shards' latest calls)
     return CFMM_OK;
 }
 
 } // namespace
+
+// the trades and outputs on the device describe the market before the swaps: as cfmm_pools_set_* (abi_update.cpp apply)
+void cfmm::swap_invalidate(cfmm_ctx* c)
+{
+    c->have_trades = false;
+    c->have_out = false;
+    c->x_valid = false;
+    c->trade_v.clear();
+}
 
 extern "C" int cfmm_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
                          const double* amount_in, double* amount_out)

@@ -1,0 +1,243 @@
+// abi_swap_path.cpp -- cfmm_swap_path: exact-input swap paths that MOVE their pools, in query order, each path all or
+// nothing (include/cfmm_amd.h has the contract).  A path answers what cfmm_quote_path answers on the market as the applied
+// paths before it left it, and each of its hops leaves its pool where cfmm_swap of (that hop, the amount entering it) leaves
+// it (swap_path_kernels.h: pass 1 quotes and tests, pass 2 applies).  The host cuts the batch into waves of pool-disjoint
+// paths (swap_path_waves.h), uploads the hop arrays ONCE in wave order and launches one kernel per wave over its span of
+// them.  It waits between waves only behind a wave with a UniV3 hop -- UniV3's state is its price, with records prepared on
+// the host: the wave's statuses and landing prices are read back and the pools of the applied paths move through
+// cfmm_pools_set_prices' own apply path (abi_update.cpp univ3_move_prices), after which the segment table is rebuilt (a moved
+// pool may have regrown the record arrays).  Otherwise it synchronises once, at the end.
+// The only memory of the feature is SwapPathScratch (ctx.h): proportional to count x max_hops, never to the pools.
+#include "ctx.h"
+#include "path_checks.h"
+#include "swap_path_checks.h"
+#include "swap_path_waves.h"
+#include "univ3_pool.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <utility>
+
+using namespace cfmm;
+
+namespace {
+
+constexpr const char* kWho = "cfmm_swap_path";
+
+constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
+
+// one record per segment from the addresses the segment holds NOW (abi_quote_path.cpp build_table, plus the writable side);
+// at least one record, so that the kernel's clamp of a segment number always lands on one
+void build_table(const cfmm_ctx* c, SwapPathSeg* t, size_t nrec, int* d_left)
+{
+    std::memset(t, 0, nrec * sizeof(SwapPathSeg));
+    t[0].s.kind = -1;
+    t[0].s.n_coins = 2;
+    for (size_t i = 0; i < c->segs.size(); ++i) {
+        const Segment& s = c->segs[i];
+        SwapPathSeg& r = t[i];
+        r.s.kind = s.m > 0 ? s.kind : -1;
+        r.s.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
+        r.s.m = s.m;
+        if (s.kind == CFMM_KIND_UNIV3) {
+            r.s.pg = s.u.pg.get();
+            r.s.cur_a = s.u.cur_a.get();
+            r.s.cur_b = s.u.cur_b.get();
+            r.s.cur_c = s.u.cur_c.get();
+            r.s.curR = s.u.curR.get();
+            r.s.walk = s.u.walk.get();
+            r.s.ticks = s.u.ticks.get();
+        } else if (ragged_kind(s.kind)) {
+            r.s.nR = r.nR = s.nc.R.get();
+            r.s.nq = r.nq = s.nc.q.get();
+            r.s.nglg = s.nc.glg.get();
+            r.s.npar = s.nc.par.get();
+        } else {
+            r.s.R = r.R = s.R.get();
+            r.s.w = s.w.get();
+            r.s.gamma = s.gamma.get();
+            r.Q = s.lR.get();
+            r.eta = s.eta.get();
+            if (kind_info(s.kind).has_fast) r.left_window = d_left + i;   // (cfmm_swap's `flagged`)
+        }
+    }
+}
+
+int upload_table(cfmm_ctx* c, size_t nrec)
+{
+    SwapPathScratch& sc = c->swap_path;
+    build_table(c, reinterpret_cast<SwapPathSeg*>(sc.stage.host()), nrec, sc.left.get());
+    HIP_TRY(c, hipMemcpyAsync(sc.table.get(), sc.stage.host(), nrec * sizeof(SwapPathSeg), hipMemcpyHostToDevice, c->stream));
+    return CFMM_OK;
+}
+
+} // namespace
+
+extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                              const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
+                              const double* min_amount_out, double* amount_out, double* hop_out, int32_t* status)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (is_parent(c))   // a path's hops may sit on different shards: all-or-nothing across devices is a change of its own
+        return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context (a path's hops may sit on different shards)", kWho);
+    char msg[256] = "";
+    std::vector<PathSegInfo> info;
+    for (const Segment& s : c->segs) info.push_back({s.kind, s.m, ragged_kind(s.kind) ? s.n_coins : 2});
+    int rc = check_paths(kWho, false, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
+                         amount_in, msg, sizeof msg);
+    if (rc == CFMM_OK) rc = check_swap_paths(kWho, count, n_hops, hop_seg, hop_row, min_amount_out, msg, sizeof msg);
+    if (rc != CFMM_OK) return fail(c, rc, "%s", msg);
+    if (count > 0 && !amount_out) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", kWho);
+    if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    const SwapPathPlan plan = swap_path_plan(count, n_hops, hop_seg, hop_row, &c->swap_path.pools);
+    const int64_t waves = (int64_t)plan.wave_off.size() - 1;
+    const bool timed = c->opt_time_kernels != 0;
+    SwapPathScratch& sc = c->swap_path;
+    const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H, nseg = c->segs.size(), nrec = std::max<size_t>(1, nseg);
+    // pinned staging, 8-byte words: the table; n_hops + the three int32 hop columns; the rows; amount_in and the limits;
+    // then what comes back: answers, hop amounts, landing prices, statuses, the window flags
+    const size_t w_table = words_of(nrec * sizeof(SwapPathSeg)), w_i32 = words_of((n + 3 * nh) * sizeof(int32_t));
+    const size_t w_status = words_of(n * sizeof(int32_t)), w_left = words_of(nrec * sizeof(int));
+    if ((rc = sc.stage.grow(c, w_table + w_i32 + nh + 2 * n + n + 2 * nh + w_status + w_left, false)) || (rc = sc.table.grow(c, nrec)) ||
+        (rc = sc.hop_i32.grow(c, n + 3 * nh)) || (rc = sc.hop_row.grow(c, nh)) || (rc = sc.amt.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
+        (rc = sc.hops.grow(c, nh)) || (rc = sc.price.grow(c, nh)) || (rc = sc.status.grow(c, n)) || (rc = sc.left.grow(c, nrec)))
+        return rc;
+    if (timed) {
+        if (sc.ev.size() < 2 * (size_t)waves) sc.ev.resize(2 * (size_t)waves);
+        for (size_t k = 0; k < 2 * (size_t)waves; ++k)
+            if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
+    }
+    unsigned long long* st = sc.stage.host() + w_table;
+    int32_t* h_i32 = reinterpret_cast<int32_t*>(st);
+    int32_t *h_seg = h_i32 + n, *h_ci = h_i32 + n + nh, *h_co = h_i32 + n + 2 * nh;
+    long long* h_row = reinterpret_cast<long long*>(st + w_i32);
+    double* h_amt = reinterpret_cast<double*>(st + w_i32 + nh);   // [count] amount_in, then [count] the limits
+    double* h_out = h_amt + 2 * n;
+    double* h_hops = h_out + n;
+    double* h_price = h_hops + nh;
+    int32_t* h_status = reinterpret_cast<int32_t*>(h_price + nh);
+    int* h_left = reinterpret_cast<int*>(reinterpret_cast<unsigned long long*>(h_status) + w_status);
+    // the paths in launch order; the slots a path does not use are zeroed (never read by the kernel)
+    std::memset(h_seg, 0, 3 * nh * sizeof(int32_t));
+    std::memset(h_row, 0, nh * sizeof(long long));
+    for (size_t j = 0; j < n; ++j) {
+        const size_t q = (size_t)plan.perm[j];
+        h_i32[j] = n_hops[q];
+        h_amt[j] = amount_in[q];
+        if (min_amount_out) h_amt[n + j] = min_amount_out[q];
+        for (size_t k = 0; k < (size_t)n_hops[q]; ++k) {
+            h_seg[k * n + j] = hop_seg[k * n + q];
+            h_row[k * n + j] = hop_row[k * n + q];
+            h_ci[k * n + j] = hop_coin_in[k * n + q];
+            h_co[k * n + j] = hop_coin_out[k * n + q];
+        }
+    }
+    armed_cancel(c);
+    if ((rc = upload_table(c, nrec)) != CFMM_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(sc.hop_i32.get(), h_i32, (n + 3 * nh) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.hop_row.get(), h_row, nh * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, (min_amount_out ? 2 : 1) * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(sc.left.get(), 0, nrec * sizeof(int), c->stream));
+    swap_invalidate(c);   // from the first launch on the pools count as moved
+    bool any_univ3 = false;
+    for (const Segment& s : c->segs) any_univ3 = any_univ3 || (s.kind == CFMM_KIND_UNIV3 && s.m > 0);
+    std::vector<std::vector<std::pair<int64_t, double>>> moved(any_univ3 ? nseg : 0);   // per UniV3 segment: {row, landing price}
+    std::vector<int64_t> rows;
+    std::vector<double> prices;
+    for (int64_t w = 0; w < waves; ++w) {
+        const size_t off = (size_t)plan.wave_off[(size_t)w], nw = (size_t)plan.wave_off[(size_t)w + 1] - off;
+        SwapPathArgs a{};
+        a.count = (int64_t)nw;
+        a.stride = count;
+        a.max_hops = max_hops;
+        a.nseg = (int32_t)nrec;
+        a.segs = sc.table.get();
+        a.n_hops = sc.hop_i32.get() + off;
+        a.hop_seg = sc.hop_i32.get() + n + off;
+        a.hop_coin_in = sc.hop_i32.get() + n + nh + off;
+        a.hop_coin_out = sc.hop_i32.get() + n + 2 * nh + off;
+        a.hop_row = sc.hop_row.get() + off;
+        a.amount_in = sc.amt.get() + off;
+        a.min_out = min_amount_out ? sc.amt.get() + n + off : nullptr;
+        a.amount_out = sc.out.get() + off;
+        a.hops = sc.hops.get() + off;
+        a.price = sc.price.get() + off;
+        a.status = sc.status.get() + off;
+        const hipError_t e = launch_swap_path(a, c->stream, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap path launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
+        if (!any_univ3) continue;
+        // which hop levels of the wave hold a UniV3 hop
+        bool level[CFMM_MAX_PATH_HOPS] = {};
+        bool some = false;
+        for (size_t j = off; j < off + nw; ++j)
+            for (size_t k = 0; k < (size_t)h_i32[j]; ++k)
+                if (c->segs[(size_t)h_seg[k * n + j]].kind == CFMM_KIND_UNIV3) level[k] = some = true;
+        if (!some) continue;
+        // the wave's statuses and landing prices; then the pools of its applied paths move as cfmm_pools_set_prices moves them
+        HIP_TRY(c, hipMemcpyAsync(h_status + off, sc.status.get() + off, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        for (size_t k = 0; k < H; ++k)
+            if (level[k]) HIP_TRY(c, hipMemcpyAsync(h_price + k * n + off, sc.price.get() + k * n + off, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (size_t j = off; j < off + nw; ++j) {
+            if (h_status[j] != CFMM_PATH_APPLIED) continue;
+            for (size_t k = 0; k < (size_t)h_i32[j]; ++k) {
+                const size_t seg = (size_t)h_seg[k * n + j];
+                const Segment& s = c->segs[seg];
+                if (s.kind != CFMM_KIND_UNIV3) continue;
+                const int64_t row = h_row[k * n + j];
+                double P = h_price[k * n + j];   // finite and > 0: the kernel has refused the path otherwise
+                const double top = s.lad.lower_ticks(row)[0];   // out of liquidity on that side: the first tick's upper price
+                P = P > top ? top : P;
+                if (std::memcmp(&P, &s.h_cp[(size_t)row], sizeof P) == 0) continue;   // (amount 0, no liquidity: where it was)
+                moved[seg].push_back({row, P});
+            }
+        }
+        bool replaced = false;
+        for (size_t seg = 0; seg < nseg; ++seg) {
+            if (moved[seg].empty()) continue;
+            std::sort(moved[seg].begin(), moved[seg].end());   // univ3_move_prices takes its rows ascending (distinct: one wave)
+            rows.clear();
+            prices.clear();
+            for (const auto& rp : moved[seg]) {
+                rows.push_back(rp.first);
+                prices.push_back(rp.second);
+            }
+            moved[seg].clear();
+            if ((rc = univ3_move_prices(c, c->segs[seg], rows, prices.data())) != CFMM_OK) return rc;
+            replaced = true;
+        }
+        // (the stream is idle up to the moves just enqueued, which do not read the staging's table: it may be rewritten)
+        if (replaced && w + 1 < waves && (rc = upload_table(c, nrec)) != CFMM_OK) return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_status, sc.status.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (hop_out) HIP_TRY(c, hipMemcpyAsync(h_hops, sc.hops.get(), nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_left, sc.left.get(), nrec * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < nseg; ++i)
+        if (h_left[i]) c->segs[i].fast_ok = 0;   // (never sent back: as cfmm_update_reserves)
+    if (timed) {
+        double ms_sum = 0.0;
+        for (int64_t w = 0; w < waves; ++w) {
+            float ms = 0.f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[2 * (size_t)w].get(), sc.ev[2 * (size_t)w + 1].get()));
+            ms_sum += (double)ms;
+        }
+        c->swap.ns = (int64_t)(ms_sum * 1e6);
+    }
+    int64_t refused = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const size_t q = (size_t)plan.perm[j];
+        amount_out[q] = h_out[j];
+        if (status) status[q] = h_status[j];
+        refused += h_status[j] != CFMM_PATH_APPLIED;
+        if (hop_out)
+            for (size_t k = 0; k < H; ++k) hop_out[k * n + q] = h_hops[k * n + j];
+    }
+    c->swap.refused = refused;
+    c->swap.launches = waves;
+    return CFMM_OK;
+}

@@ -20,6 +20,8 @@
 //                     HIP-free checks)
 //   abi_swap.cpp      exact-input swaps that move the pools (cfmm_swap: the quote, then R + γΔ − Λ; swap_waves.h: the HIP-free
 //                     wave numbering of repeated rows)
+//   abi_swap_path.cpp exact-input swap PATHS that move their pools, all or nothing (cfmm_swap_path; swap_path_waves.h: the HIP-free
+//                     wave numbering of paths that share pools, swap_path_checks.h: the HIP-free checks beyond path_checks.h)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -31,6 +33,7 @@
 #include "hostres.h"
 #include "ladder_store.h"
 #include "launch_plan.h"
+#include "swap_path_waves.h"
 #include "sweep.h"
 
 #include <atomic>
@@ -263,6 +266,26 @@ struct SwapScratch {
     std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
     int64_t ns = 0;                    // read-only option "swap_ns": the sum of that call's kernel spans
     int64_t refused = 0;               // read-only option "swap_refused": swaps of the latest call that were not applied
+    int64_t launches = 0;              // read-only option "swap_launches": kernel launches (waves) of the latest call
+};
+
+// cfmm_swap_path (abi_swap_path.cpp, swap_path_kernels.h): the device copies of one call's paths -- in WAVE order
+// (swap_path_waves.h) -- the limits, answers, hop amounts, UniV3 landing prices and statuses, the segment table (sweep.h
+// SwapPathSeg, rebuilt per call), one window flag per segment and ONE pinned staging buffer for all of them -- proportional
+// to count x max_hops (and the number of segments), never to the pools.  The call ends synchronised, so nothing here is
+// guarded against the call before.  The spans and the refusals go to SwapScratch's "swap_ns" / "swap_refused".
+struct SwapPathScratch {
+    DevBuf<SwapPathSeg> table;         // [segments]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> hop_row;         // [max_hops][count]
+    DevBuf<double> amt;                // [2][count] amount_in, min_amount_out
+    DevBuf<double> out;                // [count]
+    DevBuf<double> hops, price;        // [max_hops][count]
+    DevBuf<int32_t> status;            // [count]
+    DevBuf<int> left;                  // [segments] a new reserve of the segment left the window of the fast arithmetic
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
+    std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
+    PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
 };
 
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
@@ -388,6 +411,7 @@ struct cfmm_ctx {
     cfmm::QuoteScratch quote;
     cfmm::PathScratch path;
     cfmm::SwapScratch swap;
+    cfmm::SwapPathScratch swap_path;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
@@ -463,6 +487,10 @@ int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, in
 // above the row's first tick): apply_univ3 for the records prepared on the host, univ3_make_room, one scatter; h_cp follows.
 // Enqueued on the context's stream; invalidates nothing by itself (the caller does).
 int univ3_move_prices(cfmm_ctx* c, Segment& s, const std::vector<int64_t>& rows, const double* price);
+
+// abi_swap.cpp
+// the trades and outputs on the device describe the market before the swaps: what cfmm_pools_set_* invalidates
+void swap_invalidate(cfmm_ctx* c);
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

@@ -480,6 +480,45 @@ struct PathArgs {
 // exact_out picks quote_path_out_kernel.  e0, e1: both set = the launch is timed by the command processor.
 hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_swap_path (swap_path_kernels.h, abi_swap_path.cpp): exact-input paths that MOVE their pools, all or nothing, one lane per
+// path of ONE WAVE -- paths that share no pool (the host numbers the waves: swap_path_waves.h).  The kernel reads a table of
+// its own: what PathSeg holds (the quotes' view, unchanged), the segment's arrays again as writable pointers, what
+// swap_kernel takes besides them (GeometricMean's {Q1, Q2} and η) and the segment's window flag.  Rebuilt and uploaded per
+// call, and again after a wave that moved UniV3 pools (their arrays may have been replaced), like the path table.
+struct SwapPathSeg {
+    PathSeg s;
+    double2* R;                  // two-coin kinds: [m] reserves
+    double2* Q;                  // GeometricMean: [m] {Q1, Q2}
+    const double* eta;           // GeometricMean: [m] η
+    double* nR;                  // weighted / Curve: [n_coins][m]
+    double* nq;
+    int* left_window;            // <- 1 when a new reserve of THIS segment lies outside [2^-kFastExp, 2^kFastExp] (kinds with a
+                                 //    fast arithmetic), or null
+    int64_t pad[2];
+};
+static_assert(sizeof(PathSeg) == 128 && sizeof(SwapPathSeg) == 192, "PathSeg stays one line; the swap table adds half of one");
+constexpr int32_t kPathApplied = 0, kPathBelowLimit = 1, kPathRefused = 2;   // CFMM_PATH_* (include/cfmm_amd.h)
+struct SwapPathArgs {
+    int64_t count;               // paths of this wave
+    int64_t stride;              // paths of the call: hop k of the wave's path p at k*stride + p of the arrays below, which
+                                 // already point at the wave's first path
+    int32_t max_hops;            // 1 .. CFMM_MAX_PATH_HOPS
+    int32_t nseg;                // records of `segs`
+    const SwapPathSeg* segs;     // [nseg] device
+    const int32_t* n_hops;       // [count]
+    const int32_t* hop_seg;      // hop-major, as PathArgs
+    const long long* hop_row;
+    const int32_t* hop_coin_in;
+    const int32_t* hop_coin_out;
+    const double* amount_in;     // [count]
+    const double* min_out;       // [count], or null: no limit
+    double* amount_out;          // [count]
+    double* hops;                // [max_hops][stride], never null: the amount leaving hop k (pass 2 reads it back)
+    double* price;               // [max_hops][stride]: the price a UniV3 hop comes to rest at (the kernel changes no UniV3 state)
+    int32_t* status;             // [count] kPathApplied / kPathBelowLimit / kPathRefused
+};
+hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

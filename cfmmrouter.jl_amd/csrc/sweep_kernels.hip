@@ -44,6 +44,7 @@
 //   quote_kernels.h   quote_kernel, quote_out_kernel (cfmm_quote, cfmm_quote_out; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised, and their inverses)
 //   quote_path_kernels.h  quote_path_kernel, quote_path_out_kernel (cfmm_quote_path, cfmm_quote_path_out: the same bodies, hop after hop)
 //   swap_kernels.h    swap_kernel (cfmm_swap: quote_one's answer, then the pool's new state; swap_pool.h: the per-kind new-state forms)
+//   swap_path_kernels.h  swap_path_kernel (cfmm_swap_path: quote_path_kernel's walk, then every hop's new state, all or nothing)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -60,6 +61,7 @@
 #include "quote_kernels.h"
 #include "quote_path_kernels.h"
 #include "swap_kernels.h"
+#include "swap_path_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -375,6 +377,15 @@ hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const N
     }
     void* args[] = {const_cast<SwapArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
     return launch_quote_grid(kernel, a.q.count, args, s, e0, e1);
+}
+
+// one lane per path of the wave, the same grid rule
+hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.count <= 0 || a.stride < a.count || a.nseg <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS || !a.hops || !a.price || !a.status)
+        return hipErrorInvalidValue;
+    void* args[] = {const_cast<SwapPathArgs*>(&a)};
+    return launch_quote_grid(reinterpret_cast<const void*>(&swap_path_kernel<kQuoteBlock>), a.count, args, s, e0, e1);
 }
 
 } // namespace cfmm

@@ -787,7 +787,52 @@ def quote_path_out(r: Router, pools, tokens, amount_out, hops=False):
     return _quote_path(r, "quote_path_out", pools, tokens, amount_out, hops)
 
 
+def swap_path_(r: Router, pools, tokens, amount_in, min_out=None, hops=False, sync_host=True):
+    """Swap PATHS APPLIED to the pools on the device (cfmm_swap_path): `quote_path`'s arguments, mapping and refusals, but the
+    paths are executed in the order given, each ALL OR NOTHING -- "make this cycle, but only if at least this much comes out".
+    Path p sees the market as the applied paths before it left it; an applied path's amounts are what `quote_path` answers on
+    that market, and each of its pools moves as `swap_` moves it.
+
+    Returns (amount_out, status[, hop_out]): status[p] is PATH_APPLIED, PATH_BELOW_LIMIT (amount_out[p] < min_out[p]: the
+    quote it would have given; nothing moved) or PATH_REFUSED (a hop would leave an invalid pool: NaN; nothing moved).
+    min_out: None (no limit), a scalar or one limit per path.  Unlike a chain of `swap_` calls, paths that share pools need no
+    ordering by hand and a path refused at its third hop has nothing to unwind.  sync_host=True (default) also refreshes the
+    host mirror of the touched segments (`r.cfmms[i].R`, `current_price`).  The router's trades are those of the old market:
+    they are zeroed, as by swap_."""
+    n_hops, seg, row, ci, co, amt, touched = _path_hops(r, "swap_path", pools, tokens, amount_in)
+    if min_out is not None:
+        try:
+            min_out = np.ascontiguousarray(np.broadcast_to(np.asarray(min_out, dtype=np.float64), amt.shape))
+        except ValueError:
+            raise ArgumentError("min_out must be a scalar or have one entry per path") from None
+    ctx = _path_context(r)
+    L = r._layout
+    try:
+        res = ctx.swap_path(n_hops, seg, row, ci, co, amt, min_out, hops)
+        if sync_host:
+            for b in sorted(touched):
+                _download_state(ctx, L.seg_of[b], L.batches[b])
+                L.sync_pools(r.cfmms, b, sorted(touched[b]))
+        return res
+    finally:
+        r._reset_trades()
+
+
 def _quote_path(r: Router, verb, pools, tokens, amount, hops):
+    n_hops, seg, row, ci, co, amt, _ = _path_hops(r, verb, pools, tokens, amount)
+    return getattr(_path_context(r), verb)(n_hops, seg, row, ci, co, amt, hops)
+
+
+def _path_context(r: Router):
+    ctx = getattr(r._backend, "ctx", None)
+    if ctx is None:
+        raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
+    return ctx
+
+
+def _path_hops(r: Router, verb, pools, tokens, amount):
+    """(pools, tokens) of the path calls as the context's hop arrays, with every refusal the router makes; also the rows the
+    paths touch, per batch"""
     L = r._layout
     pools, tokens = list(pools), list(tokens)
     n = len(pools)
@@ -796,7 +841,7 @@ def _quote_path(r: Router, verb, pools, tokens, amount, hops):
     try:
         amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
     except ValueError:
-        raise ArgumentError(f"{'amount_in' if verb == 'quote_path' else 'amount_out'} must be a scalar or have one entry per path") from None
+        raise ArgumentError(f"{'amount_out' if verb == 'quote_path_out' else 'amount_in'} must be a scalar or have one entry per path") from None
     paths = [(np.asarray(pl, dtype=np.int64).reshape(-1), np.asarray(tk, dtype=np.int64).reshape(-1)) for pl, tk in zip(pools, tokens)]
     for p, (pl, tk) in enumerate(paths):
         if not 1 <= pl.size <= MAX_PATH_HOPS:
@@ -807,6 +852,7 @@ def _quote_path(r: Router, verb, pools, tokens, amount, hops):
     n_hops = np.array([pl.size for pl, _ in paths], dtype=np.int32)
     seg, ci, co = (np.zeros((n, H), dtype=np.int32) for _ in range(3))
     row = np.zeros((n, H), dtype=np.int64)
+    touched = {}
     for p, (pl, tk) in enumerate(paths):
         seen = set()
         for k, i in enumerate(pl.tolist()):
@@ -828,10 +874,8 @@ def _quote_path(r: Router, verb, pools, tokens, amount, hops):
             if pos[0] == pos[1]:
                 raise ArgumentError(f"path {p}, hop {k}: token {int(tk[k])} on both sides of pool {i}")
             seg[p, k], row[p, k], ci[p, k], co[p, k] = L.seg_of[where[1]], where[2], pos[0], pos[1]
-    ctx = getattr(r._backend, "ctx", None)
-    if ctx is None:
-        raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
-    return getattr(ctx, verb)(n_hops, seg, row, ci, co, amt, hops)
+            touched.setdefault(where[1], set()).add(where[2])
+    return n_hops, seg, row, ci, co, amt, touched
 
 
 def _update_reserves_host(r: Router):

@@ -474,6 +474,51 @@ int cfmm_quote_path_out_dev(cfmm_ctx* ctx, int64_t count, int32_t max_hops, cons
 int cfmm_swap(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
               const int32_t* coin_out, const double* amount_in, double* amount_out);
 
+/* Exact-input swap PATHS that MOVE their pools, each path all or nothing: what a transaction does on a chain -- it runs in
+ * order, reverts whole, and carries a slippage limit.  The path arguments are exactly cfmm_quote_path's (hop-major
+ * [max_hops][count], 1 .. CFMM_MAX_PATH_HOPS hops, slots at k >= n_hops[p] ignored); min_amount_out is NULL (no limit) or
+ * [count], each finite and >= 0; hop_out and status may be NULL.
+ * The paths are applied IN QUERY ORDER: path p sees the market as the APPLIED paths among 0 .. p-1 left it.  For an applied
+ * path, amount_out[p] and every hop_out[k*count+p] are, bit for bit, what cfmm_quote_path answers for that path on that
+ * market, and each hop's pool is then left exactly where cfmm_swap of (that hop, the amount entering it) leaves it: the
+ * reserve kinds at R_in + γ·a, R_out − out with the prepared constants refreshed and the fast-arithmetic window flag kept per
+ * segment; UniV3 at the price the hop comes to rest at, clamped on the host and moved through cfmm_pools_set_prices' own
+ * apply path.  A hop entered with amount 0 leaves every bit of its pool.  The call therefore equals chaining cfmm_swap hop by
+ * hop, path by path, in answers and in final state.
+ * A POOL MAY APPEAR ONLY ONCE IN A PATH: a path that names one (segment, row) twice is refused.  With distinct pools the hops
+ * of one path do not see each other's moves, so the whole path is quoted against the market as it stands and applied
+ * afterwards -- which is what makes all-or-nothing possible without unwinding anything.  (cfmm_quote_path, which moves
+ * nothing, does not refuse such a path.)
+ * ALL OR NOTHING.  A path is applied only if (a) no hop would leave a pool that cfmm_pools_set_* refuses -- cfmm_swap's
+ * refusal conditions, unchanged -- and (b) amount_out[p] >= min_amount_out[p] where a limit is given.  Otherwise none of its
+ * pools changes a bit and later paths proceed from the unchanged market.  status[p]:
+ *   CFMM_PATH_APPLIED      applied              amount_out[p] the answer, hop_out the hop amounts
+ *   CFMM_PATH_BELOW_LIMIT  below the limit      amount_out[p] the quote it would have given, hop_out the hop amounts
+ *   CFMM_PATH_REFUSED      a hop was refused    amount_out[p] NaN, hop_out the amounts before the refusing hop, NaN from it on
+ * The call returns CFMM_OK in all three cases; afterwards "swap_refused" is the number of paths whose status is not
+ * CFMM_PATH_APPLIED.  Unused hop_out slots are written as NaN.
+ * Everything is checked before anything is enqueued: cfmm_quote_path's checks, the repeated pool ("cfmm_swap_path: path 3,
+ * hops 0 and 2: ...") and the limits.  A failure is CFMM_ERR_INVALID_ARG, names the path and the hop(s), and leaves the
+ * outputs AND the pools untouched.
+ * A state change with cfmm_swap's protocol: the trades and outputs of earlier sweeps are invalidated, a pre-armed cfmm_route
+ * is cancelled; synchronous on the context's stream; count == 0 is a no-op that invalidates nothing; on a context sharded
+ * with cfmm_set_peers or RCCL the call is local to the rank.  Device memory of the call is proportional to count x max_hops,
+ * never to the pools.  A MULTI-DEVICE CONTEXT answers CFMM_ERR_UNSUPPORTED before anything moves: a path's hops may sit on
+ * different shards, and all-or-nothing across devices is a change of its own.
+ * Paths that share pools are ordered on the host: a path runs in the first launch in which all its pools are free, a pool
+ * being taken, for that launch, by every earlier path that names it -- applied or not, the host cannot know in advance.  Each
+ * launch holds pool-disjoint paths only; a batch of pool-disjoint paths is one launch; the host waits between launches only
+ * behind one with a UniV3 hop, whose pools it re-prepares.  There is NO cfmm_swap_path_dev, for cfmm_swap's reason: the
+ * order is decided on the host.  There is no exact-output form.
+ * Read-only options: "swap_launches", the number of launches (waves) of the latest cfmm_swap or cfmm_swap_path call; under
+ * "time_kernels", "swap_ns", the sum of their kernel spans. */
+#define CFMM_PATH_APPLIED 0
+#define CFMM_PATH_BELOW_LIMIT 1
+#define CFMM_PATH_REFUSED 2
+int cfmm_swap_path(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                   const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
+                   const double* min_amount_out, double* amount_out, double* hop_out, int32_t* status);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

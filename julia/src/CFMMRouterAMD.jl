@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -571,7 +571,8 @@ end
 
 const MAX_PATH_HOPS = 8   # CFMM_MAX_PATH_HOPS
 
-function quote_path_queries(r::AMDRouter, pools, tokens, given, hops::Bool, exact_out::Bool)
+# (pools, tokens) of the path calls as the library's hop arrays, with every refusal made here
+function path_hop_arrays(r::AMDRouter, pools, tokens, given)
     n = length(pools)
     (length(tokens) == n && length(given) == n) || throw(ArgumentError("tokens and the amounts must have one entry per path"))
     where = segment_rows(r)
@@ -594,7 +595,11 @@ function quote_path_queries(r::AMDRouter, pools, tokens, given, hops::Bool, exac
             ci[p, k] = a - 1; co[p, k] = b - 1                                      # 0-based for the library
         end
     end
-    amt = Float64[given[p] for p in 1:n]
+    return n, H, n_hops, seg, row, ci, co, Float64[given[p] for p in 1:n]
+end
+
+function quote_path_queries(r::AMDRouter, pools, tokens, given, hops::Bool, exact_out::Bool)
+    n, H, n_hops, seg, row, ci, co, amt = path_hop_arrays(r, pools, tokens, given)
     out = Vector{Float64}(undef, n)
     hv = fill(NaN, n, H)
     n == 0 && return hops ? (out, hv) : out
@@ -607,6 +612,36 @@ function quote_path_queries(r::AMDRouter, pools, tokens, given, hops::Bool, exac
               (Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
               r.ctx, n, H, n_hops, seg, row, ci, co, amt, out, hp))
     return hops ? (out, hv) : out
+end
+
+# swap_paths!(r, pools, tokens, amount_in; min_out=nothing, hops=false, sync=true) -- the Python host's `swap_path_`
+# (cfmm_swap_path): quote_paths' arguments, mapping and refusals, but the paths are EXECUTED in the order given, each all or
+# nothing.  Path p sees the market as the applied paths before it left it; an applied path's amounts are what quote_paths
+# answers on that market and each of its pools moves as swap! moves it.  Returns (amount_out, status[, hop_out]): status[p]
+# is 0 (applied), 1 (amount_out[p] < min_out[p]: the quote it would have given, nothing moved) or 2 (a hop would leave an
+# invalid pool: NaN, nothing moved).  sync = true refreshes the host-side pool objects; the router's trades are zeroed.
+const PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = Int32(0), Int32(1), Int32(2)   # CFMM_PATH_*
+function swap_paths!(r::AMDRouter, pools::AbstractVector, tokens::AbstractVector, amount_in::AbstractVector{<:Real};
+                     min_out=nothing, hops::Bool=false, sync::Bool=true)
+    n, H, n_hops, seg, row, ci, co, amt = path_hop_arrays(r, pools, tokens, amount_in)
+    (isnothing(min_out) || length(min_out) == n) || throw(ArgumentError("min_out must have one entry per path"))
+    lim = isnothing(min_out) ? Float64[] : Float64[min_out[p] for p in 1:n]
+    out = Vector{Float64}(undef, n)
+    status = Vector{Int32}(undef, n)
+    hv = fill(NaN, n, H)
+    n == 0 && return hops ? (out, status, hv) : (out, status)
+    hp = hops ? pointer(hv) : Ptr{Float64}(C_NULL)
+    lp = isnothing(min_out) ? Ptr{Float64}(C_NULL) : pointer(lim)
+    try
+        GC.@preserve n_hops seg row ci co amt lim out hv status check(r.ctx,
+            ccall((:cfmm_swap_path, LIB), Cint,
+                  (Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                  r.ctx, n, H, n_hops, seg, row, ci, co, amt, lp, out, hp, status))
+        sync && download_state!(r)
+    finally
+        foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
+    end
+    return hops ? (out, status, hv) : (out, status)
 end
 
 # forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449: methods of CFMMRouter's own function (imported above) for the pool kinds it
