@@ -11,7 +11,7 @@ from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwo
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
 from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_,
-                     swap_, swap_path_, update_pools_, update_reserves_)
+                     swap_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
 
 
 def find_arb_(*args, **kw):
@@ -29,5 +29,5 @@ __all__ = [
     "lower_limit", "upper_limit", "Router", "route_", "netflows_", "netflows", "ArgumentError",
     "CFMMDeviceError", "Context", "DeviceBackend", "build", "lib", "zerotrade", "ϕ", "ϕ_grad_", "phi", "grad_phi_",
     "polish_", "dual_jacobian", "active_trades", "forward_trade", "quote", "backward_trade", "quote_out",
-    "quote_path", "quote_path_out", "swap_", "swap_path_",
+    "quote_path", "quote_path_out", "swap_", "swap_path_", "swap_out_", "swap_path_out_",
 ]

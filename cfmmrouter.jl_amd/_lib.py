@@ -23,6 +23,7 @@ ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
 PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = 0, 1, 2   # CFMM_PATH_*: Context.swap_path's status
+SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = 0, 1, 2, 3   # CFMM_SWAP_*: Context.swap_out's / swap_path_out's status
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -139,6 +140,8 @@ def lib():
     L.cfmm_quote_out_dev.argtypes = [_ctx, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_swap.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p]
     L.cfmm_swap_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_swap_out.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_swap_path_out.argtypes = L.cfmm_swap_path.argtypes
     L.cfmm_quote_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -506,7 +509,25 @@ class Context:
         (get_option("swap_refused") counts them).  A state change: earlier trades and outputs are invalidated."""
         return self._quote("cfmm_swap", seg, amount_in, coin_in, coin_out, idx)
 
-    def _quote(self, entry, seg, given, coin_in, coin_out, idx):
+    def swap_out(self, seg: int, amount_out, coin_in, coin_out=None, idx=None, max_in=None, status=False):
+        """quote_out's arguments, but the swaps are APPLIED (cfmm_swap_out), in query order: amount_in[q] is what quote_out
+        answers on the pool as swaps 0 .. q-1 left it, and the pool then gives exactly amount_out[q]: it moves to
+        R_in + γ·amount_in, R_out − amount_out (UniV3: to the price `swap` of amount_in rests at).  max_in: None, a scalar or
+        one limit per swap.  A swap is not applied when the pool cannot give that much (+inf, SWAP_UNOBTAINABLE), when it
+        would leave an invalid pool (NaN, SWAP_REFUSED) or when it costs more than max_in (the would-be quote,
+        SWAP_OVER_LIMIT); get_option("swap_refused") counts them.  status=True: returns (amount_in, status).  A state
+        change: earlier trades and outputs are invalidated."""
+        lim = None
+        if max_in is not None:
+            try:
+                lim = np.ascontiguousarray(np.broadcast_to(np.asarray(max_in, dtype=np.float64), (f64(amount_out).size,)))
+            except ValueError:
+                raise ArgumentError("max_in must be a scalar or have one entry per amount") from None
+        st = np.empty(f64(amount_out).size, dtype=np.int32)
+        out = self._quote("cfmm_swap_out", seg, amount_out, coin_in, coin_out, idx, lim, st)
+        return (out, st) if status else out
+
+    def _quote(self, entry, seg, given, coin_in, coin_out, idx, *swap_out_args):
         amt = f64(given).reshape(-1)
         n = amt.size
         bcast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32).reshape(-1) if np.ndim(a) else
@@ -520,7 +541,11 @@ class Context:
         if ix is not None and ix.size != n:
             raise ArgumentError("idx must have one entry per amount")
         out = np.empty(n)
-        self._check(getattr(self._L, entry)(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out)))
+        if swap_out_args:   # cfmm_swap_out: the limits go in front of the answers, the statuses behind them
+            lim, st = swap_out_args
+            self._check(getattr(self._L, entry)(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(lim), ptr(out), ptr(st)))
+        else:
+            self._check(getattr(self._L, entry)(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out)))
         return out
 
     def quote_dev(self, seg: int, count: int, d_amount_in: int, d_coin_in: int, d_amount_out: int, d_coin_out: int = 0,
@@ -568,7 +593,7 @@ class Context:
                                             ptr(hv)))
         return (out, hv) if hops else out
 
-    # -- multi-hop path execution (cfmm_swap_path): quote_path's arguments, the paths applied in order, each all or nothing ----
+    # -- multi-hop path execution (cfmm_swap_path / cfmm_swap_path_out): the paths applied in order, each all or nothing ----
     def swap_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, min_out=None, hops=False):
         """quote_path's arguments, but the paths are APPLIED (cfmm_swap_path), in query order, each all or nothing: returns
         (amount_out, status[, hop_out]).  status[p] is PATH_APPLIED (amount_out[p] is what quote_path answers on the market
@@ -576,20 +601,32 @@ class Context:
         < min_out[p]: the quote it would have given, nothing moved) or PATH_REFUSED (a hop would leave an invalid pool:
         NaN, nothing moved).  min_out: None, a scalar or one limit per path.  A pool may appear only once in a path.  A
         state change: earlier trades and outputs are invalidated; get_option("swap_refused") counts the paths not applied."""
-        amt = f64(amount_in).reshape(-1)
+        return self._swap_path("cfmm_swap_path", "min_out", n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, min_out, hops)
+
+    def swap_path_out(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_out, max_in=None, hops=False):
+        """quote_path_out's arguments, but the paths are APPLIED (cfmm_swap_path_out), in query order, each all or nothing:
+        returns (amount_in, status[, hop_in]).  amount_in[p] and hop_in are what quote_path_out answers on the market the
+        applied paths before p left; status[p] is SWAP_APPLIED (every hop's pool has moved as `swap_out` moves it),
+        SWAP_UNOBTAINABLE (a pool on the way cannot give that much: +inf), SWAP_REFUSED (a hop would leave an invalid pool:
+        NaN) or SWAP_OVER_LIMIT (amount_in[p] > max_in[p]: the quote it would have cost); in the last three nothing moved.
+        max_in: None, a scalar or one limit per path.  A pool may appear only once in a path.  A state change, as swap_path."""
+        return self._swap_path("cfmm_swap_path_out", "max_in", n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_out, max_in, hops)
+
+    def _swap_path(self, entry, limit_name, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, given, limit, hops):
+        amt = f64(given).reshape(-1)
         n = amt.size
         nh, seg, row, ci, co = self._path_columns(n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
         lim = None
-        if min_out is not None:
+        if limit is not None:
             try:
-                lim = np.ascontiguousarray(np.broadcast_to(np.asarray(min_out, dtype=np.float64), (n,)))
+                lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limit, dtype=np.float64), (n,)))
             except ValueError:
-                raise ArgumentError("min_out must be a scalar or have one entry per amount") from None
+                raise ArgumentError(f"{limit_name} must be a scalar or have one entry per amount") from None
         max_hops = max(1, int(seg.shape[0]))
         out, st = np.empty(n), np.empty(n, dtype=np.int32)
         hv = np.empty((max_hops, n)) if hops else None
-        self._check(self._L.cfmm_swap_path(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(lim),
-                                           ptr(out), ptr(hv), ptr(st)))
+        self._check(getattr(self._L, entry)(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt), ptr(lim),
+                                            ptr(out), ptr(hv), ptr(st)))
         return (out, st, hv) if hops else (out, st)
 
     def _path_columns(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n):

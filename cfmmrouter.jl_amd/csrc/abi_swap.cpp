@@ -1,11 +1,15 @@
-// abi_swap.cpp -- cfmm_swap: exact-input swaps of one segment's pools that MOVE the pools (include/cfmm_amd.h has the
-// contract).  Each swap answers what cfmm_quote answers on the pool as it stands (swap_kernels.h runs quote_one itself) and
-// then leaves the pool at R + γΔ − Λ (src/cfmms.jl:26-31; swap_pool.h: the per-kind forms).  The swaps of a batch are applied
-// in query order: the host cuts the batch into waves of distinct rows (swap_waves.h) and launches them in stream order.
-// The reserve kinds synchronise once, at the end; UniV3 -- whose state is its price, with records prepared on the host --
-// reads the wave's landing prices back and moves the pools through cfmm_pools_set_prices' own apply path (abi_update.cpp
-// univ3_move_prices) before the next wave.  The only memory of the feature is SwapScratch (ctx.h), proportional to the
-// swaps of a call and never to the pools.
+// abi_swap.cpp -- cfmm_swap and cfmm_swap_out: swaps of one segment's pools that MOVE the pools (include/cfmm_amd.h has the
+// contracts).  The two directions share every line here, as abi_quote.cpp's do: a Dir names the entry and its given amount
+// in the messages and picks the launcher; `given` / `answer` below are amount_in / amount_out of cfmm_swap and amount_out /
+// amount_in of cfmm_swap_out, which adds a limit on the answer and a status per swap.
+// Each exact-input swap answers what cfmm_quote answers on the pool as it stands (swap_kernels.h runs quote_one itself) and
+// then leaves the pool at R + γΔ − Λ (src/cfmms.jl:26-31; swap_pool.h: the per-kind forms); each exact-output swap answers
+// cfmm_quote_out's bits (swap_out_kernels.h runs quote_out_one) and leaves the pool at R_in + γ·in, R_out − want.  The swaps
+// of a batch are applied in query order: the host cuts the batch into waves of distinct rows (swap_waves.h) and launches them
+// in stream order.  The reserve kinds synchronise once, at the end; UniV3 -- whose state is its price, with records prepared
+// on the host -- reads the wave's landing prices back and moves the pools through cfmm_pools_set_prices' own apply path
+// (abi_update.cpp univ3_move_prices) before the next wave.  The only memory of the feature is SwapScratch (ctx.h),
+// proportional to the swaps of a call and never to the pools.
 #include "ctx.h"
 #include "swap_waves.h"
 #include "univ3_pool.h"
@@ -18,12 +22,20 @@ using namespace cfmm;
 
 namespace {
 
-constexpr const char* kWho = "cfmm_swap";
+struct Dir {
+    bool exact_out;
+    const char *who, *given;   // the entry's name and the given amount's, as the messages spell them
+};
+constexpr Dir kForward{false, "cfmm_swap", "amount_in"};
+constexpr Dir kInverse{true, "cfmm_swap_out", "amount_out"};
+
+constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
 
 // the kernel's view of segment `s`; the wave's query arrays are filled in by the caller
-hipError_t launch_wave(const cfmm_ctx* c, const Segment& s, const SwapArgs& w, hipEvent_t e0, hipEvent_t e1)
+hipError_t launch_wave(const cfmm_ctx* c, const Dir& dir, const Segment& s, const SwapOutArgs& w, hipEvent_t e0, hipEvent_t e1)
 {
-    SwapArgs a = w;
+    SwapOutArgs so = w;
+    SwapArgs& a = so.s;
     a.q.m = s.m;
     a.q.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
     a.q.R = s.R.get();
@@ -54,12 +66,12 @@ hipError_t launch_wave(const cfmm_ctx* c, const Segment& s, const SwapArgs& w, h
         n.par = s.nc.par.get();
         n.n_coins = s.n_coins;
     }
-    return launch_swap(s.kind, a, u, n, c->stream, e0, e1);
+    return dir.exact_out ? launch_swap_out(s.kind, so, u, n, c->stream, e0, e1) : launch_swap(s.kind, a, u, n, c->stream, e0, e1);
 }
 
-// One checked call on a single-device context
-int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
-                const double* amount_in, double* amount_out)
+// One checked call on a single-device context.  limit, status: cfmm_swap_out's (either may be null); cfmm_swap passes neither.
+int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                const int32_t* coin_out, const double* given, const double* limit, double* answer, int32_t* status)
 {
     Segment& s = c->segs[(size_t)seg];
     HIP_TRY(c, hipSetDevice(c->device));
@@ -68,11 +80,13 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
     const bool univ3 = s.kind == CFMM_KIND_UNIV3;
     const bool flagged = !univ3 && kind_info(s.kind).has_fast;
     const bool timed = c->opt_time_kernels != 0;
+    const bool out = dir.exact_out;
     SwapScratch& sc = c->swap;
-    const size_t n = (size_t)count;
+    const size_t n = (size_t)count, w_status = words_of(n * sizeof(int32_t));
     int rc;
-    if ((rc = sc.stage.grow(c, 5 * n + 1, false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
-        (idx && (rc = sc.idx.grow(c, n))) || (univ3 && (rc = sc.price.grow(c, n))) || (flagged && (rc = sc.left.grow(c, 1))))
+    if ((rc = sc.stage.grow(c, 6 * n + w_status + 1, false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
+        (idx && (rc = sc.idx.grow(c, n))) || (univ3 && (rc = sc.price.grow(c, n))) || (flagged && (rc = sc.left.grow(c, 1))) ||
+        (limit && (rc = sc.limit.grow(c, n))) || (out && (rc = sc.status.grow(c, n))))
         return rc;
     if (timed) {
         if (sc.ev.size() < 2 * (size_t)waves) sc.ev.resize(2 * (size_t)waves);
@@ -86,27 +100,32 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
     double* h_out = reinterpret_cast<double*>(st + 2 * n);
     double* h_price = reinterpret_cast<double*>(st + 3 * n);
     long long* h_idx = reinterpret_cast<long long*>(st + 4 * n);
-    int* h_left = reinterpret_cast<int*>(st + 5 * n);
+    double* h_limit = reinterpret_cast<double*>(st + 5 * n);
+    int32_t* h_status = reinterpret_cast<int32_t*>(st + 6 * n);
+    int* h_left = reinterpret_cast<int*>(st + 6 * n + w_status);
     for (size_t j = 0; j < n; ++j) {
         const size_t q = (size_t)plan.perm[j];
-        h_amt[j] = amount_in[q];
+        h_amt[j] = given[q];
         h_coins[j] = coin_in[q];
         if (coin_out) h_coins[n + j] = coin_out[q];
         if (idx) h_idx[j] = idx[q];
+        if (limit) h_limit[j] = limit[q];
     }
     *h_left = 0;
     armed_cancel(c);
     HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sc.coins.get(), h_coins, (coin_out ? 2 : 1) * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     if (idx) HIP_TRY(c, hipMemcpyAsync(sc.idx.get(), h_idx, n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    if (limit) HIP_TRY(c, hipMemcpyAsync(sc.limit.get(), h_limit, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (flagged) HIP_TRY(c, hipMemsetAsync(sc.left.get(), 0, sizeof(int), c->stream));
     swap_invalidate(c);   // from the first launch on the pools count as moved
-    std::vector<char> refused_at(univ3 ? n : 0, 0);   // UniV3: the landing price was no state a pool can take
+    std::vector<char> refused_at(univ3 && !out ? n : 0, 0);   // UniV3, exact input: the landing price was no state a pool can take
     std::vector<int64_t> rows;
     std::vector<double> prices;
     for (int64_t w = 0; w < waves; ++w) {
         const size_t off = (size_t)plan.wave_off[(size_t)w], nw = (size_t)plan.wave_off[(size_t)w + 1] - off;
-        SwapArgs a{};
+        SwapOutArgs so{};
+        SwapArgs& a = so.s;
         a.q.count = (int64_t)nw;
         a.q.idx = idx ? sc.idx.get() + off : nullptr;
         a.q.coin_in = sc.coins.get() + off;
@@ -115,18 +134,24 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
         a.q.amount_out = sc.out.get() + off;
         a.price = univ3 ? sc.price.get() + off : nullptr;
         a.left_window = flagged ? sc.left.get() : nullptr;
-        const hipError_t e = launch_wave(c, s, a, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        so.max_in = limit ? sc.limit.get() + off : nullptr;
+        so.status = out ? sc.status.get() + off : nullptr;
+        const hipError_t e = launch_wave(c, dir, s, so, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
         if (!univ3) continue;
-        // the wave's landing prices, 8 bytes per swap; then the pools move as cfmm_pools_set_prices moves them
+        // the wave's landing prices, 8 bytes per swap (exact output: and its statuses -- only an applied swap moves its pool);
+        // then the pools move as cfmm_pools_set_prices moves them
         HIP_TRY(c, hipMemcpyAsync(h_price + off, sc.price.get() + off, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (out) HIP_TRY(c, hipMemcpyAsync(h_status + off, sc.status.get() + off, nw * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         rows.clear();
         prices.clear();
         for (size_t j = off; j < off + nw; ++j) {
             const int64_t row = idx ? idx[plan.perm[j]] : plan.perm[j];
             double P = h_price[j];
-            if (!finite_pos(P)) {   // check_univ3_price would refuse it: the pool stays
+            if (out) {
+                if (h_status[j] != CFMM_SWAP_APPLIED) continue;   // (the kernel has tested the price of an applied swap)
+            } else if (!finite_pos(P)) {   // check_univ3_price would refuse it: the pool stays
                 refused_at[j] = 1;
                 continue;
             }
@@ -139,6 +164,7 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
         if ((rc = univ3_move_prices(c, s, rows, prices.data())) != CFMM_OK) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (out) HIP_TRY(c, hipMemcpyAsync(h_status, sc.status.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (flagged) HIP_TRY(c, hipMemcpyAsync(h_left, sc.left.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (flagged && *h_left) s.fast_ok = 0;   // (never sent back: as cfmm_update_reserves)
@@ -153,9 +179,10 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
     }
     int64_t refused = 0;
     for (size_t j = 0; j < n; ++j) {
-        const double o = univ3 && refused_at[j] ? std::nan("") : h_out[j];
-        refused += o != o;
-        amount_out[plan.perm[j]] = o;
+        const double o = univ3 && !out && refused_at[j] ? std::nan("") : h_out[j];
+        refused += out ? h_status[j] != CFMM_SWAP_APPLIED : o != o;
+        answer[plan.perm[j]] = o;
+        if (out && status) status[plan.perm[j]] = h_status[j];
     }
     sc.refused = refused;
     sc.launches = waves;
@@ -165,8 +192,8 @@ int swap_single(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, con
 // A parent: the swaps go to the shards that hold their rows (shard_range: contiguous blocks in device order), each shard's in
 // the caller's order -- a row lives on one shard, so per-row order is kept -- and the answers return in query order, as
 // multi_quote.  The caller has run every check there is, for every shard, before any shard changes.
-int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
-               const double* amount_in, double* amount_out)
+int multi_swap(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+               const int32_t* coin_out, const double* given, const double* limit, double* answer, int32_t* status)
 {
     const int64_t m = c->psegs[(size_t)seg].m;
     const int nd = (int)c->shards.size();
@@ -175,7 +202,7 @@ int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
     struct Bucket {
         std::vector<int64_t> where, rows;
         std::vector<int32_t> ci, co;
-        std::vector<double> amt;
+        std::vector<double> amt, lim;
     };
     std::vector<Bucket> buckets((size_t)nd);
     for (int64_t q = 0; q < count; ++q) {
@@ -186,20 +213,27 @@ int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
         bk.rows.push_back(row - first[d]);
         bk.ci.push_back(coin_in[q]);
         if (coin_out) bk.co.push_back(coin_out[q]);
-        bk.amt.push_back(amount_in[q]);
+        bk.amt.push_back(given[q]);
+        if (limit) bk.lim.push_back(limit[q]);
     }
     c->have_trades = c->have_out = false;
     std::vector<double> out;
+    std::vector<int32_t> st;
     int64_t ns = 0, refused = 0;
     for (int d = 0; d < nd; ++d) {
         const Bucket& bk = buckets[(size_t)d];
         if (bk.where.empty()) continue;
         out.resize(bk.where.size());
+        st.resize(bk.where.size());
         cfmm_ctx* child = c->shards[(size_t)d];
-        const int rc = swap_single(child, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
-                                   coin_out ? bk.co.data() : nullptr, bk.amt.data(), out.data());
+        const int rc = swap_single(child, dir, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
+                                   coin_out ? bk.co.data() : nullptr, bk.amt.data(), limit ? bk.lim.data() : nullptr, out.data(),
+                                   status ? st.data() : nullptr);
         if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s (some shards may have moved)", d, child->err.c_str());
-        for (size_t j = 0; j < bk.where.size(); ++j) amount_out[bk.where[j]] = out[j];
+        for (size_t j = 0; j < bk.where.size(); ++j) {
+            answer[bk.where[j]] = out[j];
+            if (status) status[bk.where[j]] = st[j];
+        }
         if (child->opt_time_kernels != 0) ns = std::max(ns, child->swap.ns);
         refused += child->swap.refused;
     }
@@ -208,6 +242,26 @@ int multi_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, cons
     c->swap.launches = 0;
     for (const cfmm_ctx* child : c->shards) c->swap.launches += child->swap.launches;   // (of the shards' latest calls)
     return CFMM_OK;
+}
+
+// every check of either entry, before anything is enqueued; then the call
+int swap_host(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+              const int32_t* coin_out, const double* given, const double* limit, double* answer, int32_t* status)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    const bool parent = !c->shards.empty();
+    int rc = check_quote_seg(c, dir.who, seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
+    if (rc != CFMM_OK) return rc;
+    const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
+    const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
+    const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
+    if ((rc = check_quote_queries(c, dir.who, dir.given, kind, m, nc, count, idx, coin_in, coin_out, given, answer)) != CFMM_OK) return rc;
+    for (int64_t q = 0; limit && q < count; ++q)
+        if (!(limit[q] >= 0.0) || !std::isfinite(limit[q]))
+            return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: max_amount_in must be finite and >= 0", dir.who, (long long)q);
+    if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
+    return parent ? multi_swap(c, dir, seg, count, idx, coin_in, coin_out, given, limit, answer, status)
+                  : swap_single(c, dir, seg, count, idx, coin_in, coin_out, given, limit, answer, status);
 }
 
 } // namespace
@@ -224,15 +278,11 @@ void cfmm::swap_invalidate(cfmm_ctx* c)
 extern "C" int cfmm_swap(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
                          const double* amount_in, double* amount_out)
 {
-    if (!c) return CFMM_ERR_INVALID_ARG;
-    const bool parent = !c->shards.empty();
-    int rc = check_quote_seg(c, kWho, seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
-    if (rc != CFMM_OK) return rc;
-    const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
-    const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
-    const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
-    if ((rc = check_quote_queries(c, kWho, "amount_in", kind, m, nc, count, idx, coin_in, coin_out, amount_in, amount_out)) != CFMM_OK) return rc;
-    if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
-    return parent ? multi_swap(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out)
-                  : swap_single(c, seg, count, idx, coin_in, coin_out, amount_in, amount_out);
+    return swap_host(c, kForward, seg, count, idx, coin_in, coin_out, amount_in, nullptr, amount_out, nullptr);
+}
+
+extern "C" int cfmm_swap_out(cfmm_ctx* c, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out,
+                             const double* amount_out, const double* max_amount_in, double* amount_in, int32_t* status)
+{
+    return swap_host(c, kInverse, seg, count, idx, coin_in, coin_out, amount_out, max_amount_in, amount_in, status);
 }

@@ -1,14 +1,18 @@
-// abi_swap_path.cpp -- cfmm_swap_path: exact-input swap paths that MOVE their pools, in query order, each path all or
-// nothing (include/cfmm_amd.h has the contract).  A path answers what cfmm_quote_path answers on the market as the applied
-// paths before it left it, and each of its hops leaves its pool where cfmm_swap of (that hop, the amount entering it) leaves
-// it (swap_path_kernels.h: pass 1 quotes and tests, pass 2 applies).  The host cuts the batch into waves of pool-disjoint
-// paths (swap_path_waves.h), uploads the hop arrays ONCE in wave order and launches one kernel per wave over its span of
-// them.  It waits between waves only behind a wave with a UniV3 hop -- UniV3's state is its price, with records prepared on
-// the host: the wave's statuses and landing prices are read back and the pools of the applied paths move through
-// cfmm_pools_set_prices' own apply path (abi_update.cpp univ3_move_prices), after which the segment table is rebuilt (a moved
-// pool may have regrown the record arrays).  Otherwise it synchronises once, at the end.
+// abi_swap_path.cpp -- cfmm_swap_path and, by a direction (Dir), cfmm_swap_path_out: swap paths that MOVE their pools, in
+// query order, each path all or nothing (include/cfmm_amd.h and cfmm_amd_path_out.h have the contracts).  The exact-output
+// form differs in the kernel it launches (swap_path_out_kernel: the walk from the last hop backwards), the roles of the
+// amounts and the names in the messages; every line below serves both, described for the exact-input form.
+// A path answers what cfmm_quote_path answers on the market as the applied paths before it left it, and each of its hops
+// leaves its pool where cfmm_swap of (that hop, the amount entering it) leaves it (swap_path_kernels.h: pass 1 quotes and
+// tests, pass 2 applies).  The host cuts the batch into waves of pool-disjoint paths (swap_path_waves.h), uploads the hop
+// arrays ONCE in wave order and launches one kernel per wave over its span of them.  It waits between waves only behind a
+// wave with a UniV3 hop -- UniV3's state is its price, with records prepared on the host: the wave's statuses and landing
+// prices are read back and the pools of the applied paths move through cfmm_pools_set_prices' own apply path (abi_update.cpp
+// univ3_move_prices), after which the segment table is rebuilt (a moved pool may have regrown the record arrays).  Otherwise
+// it synchronises once, at the end.
 // The only memory of the feature is SwapPathScratch (ctx.h): proportional to count x max_hops, never to the pools.
 #include "ctx.h"
+#include "../../include/cfmm_amd_path_out.h"
 #include "path_checks.h"
 #include "swap_path_checks.h"
 #include "swap_path_waves.h"
@@ -23,7 +27,12 @@ using namespace cfmm;
 
 namespace {
 
-constexpr const char* kWho = "cfmm_swap_path";
+struct Dir {
+    bool exact_out;
+    const char* who;
+};
+constexpr Dir kForward{false, "cfmm_swap_path"};
+constexpr Dir kInverse{true, "cfmm_swap_path_out"};
 
 constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
 
@@ -72,23 +81,24 @@ int upload_table(cfmm_ctx* c, size_t nrec)
     return CFMM_OK;
 }
 
-} // namespace
-
-extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
-                              const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
-                              const double* min_amount_out, double* amount_out, double* hop_out, int32_t* status)
+// One call of either direction.  given / limit / answer / hop_ans: amount_in, min_amount_out, amount_out, hop_out of
+// cfmm_swap_path; amount_out, max_amount_in, amount_in, hop_in of cfmm_swap_path_out.
+int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                   const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* given,
+                   const double* limit, double* answer, double* hop_ans, int32_t* status)
 {
+    const char* who = dir.who;
     if (!c) return CFMM_ERR_INVALID_ARG;
     if (is_parent(c))   // a path's hops may sit on different shards: all-or-nothing across devices is a change of its own
-        return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context (a path's hops may sit on different shards)", kWho);
+        return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context (a path's hops may sit on different shards)", who);
     char msg[256] = "";
     std::vector<PathSegInfo> info;
     for (const Segment& s : c->segs) info.push_back({s.kind, s.m, ragged_kind(s.kind) ? s.n_coins : 2});
-    int rc = check_paths(kWho, false, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
-                         amount_in, msg, sizeof msg);
-    if (rc == CFMM_OK) rc = check_swap_paths(kWho, count, n_hops, hop_seg, hop_row, min_amount_out, msg, sizeof msg);
+    int rc = check_paths(who, dir.exact_out, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
+                         given, msg, sizeof msg);
+    if (rc == CFMM_OK) rc = check_swap_paths(who, count, n_hops, hop_seg, hop_row, limit, msg, sizeof msg, dir.exact_out);
     if (rc != CFMM_OK) return fail(c, rc, "%s", msg);
-    if (count > 0 && !amount_out) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", kWho);
+    if (count > 0 && !answer) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", who);
     if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
 
     HIP_TRY(c, hipSetDevice(c->device));
@@ -97,7 +107,7 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     const bool timed = c->opt_time_kernels != 0;
     SwapPathScratch& sc = c->swap_path;
     const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H, nseg = c->segs.size(), nrec = std::max<size_t>(1, nseg);
-    // pinned staging, 8-byte words: the table; n_hops + the three int32 hop columns; the rows; amount_in and the limits;
+    // pinned staging, 8-byte words: the table; n_hops + the three int32 hop columns; the rows; the given amounts and the limits;
     // then what comes back: answers, hop amounts, landing prices, statuses, the window flags
     const size_t w_table = words_of(nrec * sizeof(SwapPathSeg)), w_i32 = words_of((n + 3 * nh) * sizeof(int32_t));
     const size_t w_status = words_of(n * sizeof(int32_t)), w_left = words_of(nrec * sizeof(int));
@@ -114,7 +124,7 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     int32_t* h_i32 = reinterpret_cast<int32_t*>(st);
     int32_t *h_seg = h_i32 + n, *h_ci = h_i32 + n + nh, *h_co = h_i32 + n + 2 * nh;
     long long* h_row = reinterpret_cast<long long*>(st + w_i32);
-    double* h_amt = reinterpret_cast<double*>(st + w_i32 + nh);   // [count] amount_in, then [count] the limits
+    double* h_amt = reinterpret_cast<double*>(st + w_i32 + nh);   // [count] the given amounts, then [count] the limits
     double* h_out = h_amt + 2 * n;
     double* h_hops = h_out + n;
     double* h_price = h_hops + nh;
@@ -126,8 +136,8 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     for (size_t j = 0; j < n; ++j) {
         const size_t q = (size_t)plan.perm[j];
         h_i32[j] = n_hops[q];
-        h_amt[j] = amount_in[q];
-        if (min_amount_out) h_amt[n + j] = min_amount_out[q];
+        h_amt[j] = given[q];
+        if (limit) h_amt[n + j] = limit[q];
         for (size_t k = 0; k < (size_t)n_hops[q]; ++k) {
             h_seg[k * n + j] = hop_seg[k * n + q];
             h_row[k * n + j] = hop_row[k * n + q];
@@ -139,7 +149,7 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     if ((rc = upload_table(c, nrec)) != CFMM_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(sc.hop_i32.get(), h_i32, (n + 3 * nh) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sc.hop_row.get(), h_row, nh * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, (min_amount_out ? 2 : 1) * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, (limit ? 2 : 1) * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(sc.left.get(), 0, nrec * sizeof(int), c->stream));
     swap_invalidate(c);   // from the first launch on the pools count as moved
     bool any_univ3 = false;
@@ -161,12 +171,12 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
         a.hop_coin_out = sc.hop_i32.get() + n + 2 * nh + off;
         a.hop_row = sc.hop_row.get() + off;
         a.amount_in = sc.amt.get() + off;
-        a.min_out = min_amount_out ? sc.amt.get() + n + off : nullptr;
+        a.min_out = limit ? sc.amt.get() + n + off : nullptr;
         a.amount_out = sc.out.get() + off;
         a.hops = sc.hops.get() + off;
         a.price = sc.price.get() + off;
         a.status = sc.status.get() + off;
-        const hipError_t e = launch_swap_path(a, c->stream, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        const hipError_t e = (dir.exact_out ? launch_swap_path_out : launch_swap_path)(a, c->stream, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap path launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
         if (!any_univ3) continue;
         // which hop levels of the wave hold a UniV3 hop
@@ -214,7 +224,7 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     }
     HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_status, sc.status.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    if (hop_out) HIP_TRY(c, hipMemcpyAsync(h_hops, sc.hops.get(), nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (hop_ans) HIP_TRY(c, hipMemcpyAsync(h_hops, sc.hops.get(), nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_left, sc.left.get(), nrec * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < nseg; ++i)
@@ -231,13 +241,31 @@ extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, cons
     int64_t refused = 0;
     for (size_t j = 0; j < n; ++j) {
         const size_t q = (size_t)plan.perm[j];
-        amount_out[q] = h_out[j];
+        answer[q] = h_out[j];
         if (status) status[q] = h_status[j];
         refused += h_status[j] != CFMM_PATH_APPLIED;
-        if (hop_out)
-            for (size_t k = 0; k < H; ++k) hop_out[k * n + q] = h_hops[k * n + j];
+        if (hop_ans)
+            for (size_t k = 0; k < H; ++k) hop_ans[k * n + q] = h_hops[k * n + j];
     }
     c->swap.refused = refused;
     c->swap.launches = waves;
     return CFMM_OK;
+}
+
+} // namespace
+
+extern "C" int cfmm_swap_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                              const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
+                              const double* min_amount_out, double* amount_out, double* hop_out, int32_t* status)
+{
+    return swap_path_host(c, kForward, count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, min_amount_out,
+                          amount_out, hop_out, status);
+}
+
+extern "C" int cfmm_swap_path_out(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
+                                  const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_out,
+                                  const double* max_amount_in, double* amount_in, double* hop_in, int32_t* status)
+{
+    return swap_path_host(c, kInverse, count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_out, max_amount_in,
+                          amount_in, hop_in, status);
 }

@@ -18,10 +18,11 @@
 //                     exact-output quotes (cfmm_quote_out / cfmm_quote_out_dev)
 //   abi_quote_path.cpp  multi-hop path quotes across segments (cfmm_quote_path / _out and their _dev forms; path_checks.h: the
 //                     HIP-free checks)
-//   abi_swap.cpp      exact-input swaps that move the pools (cfmm_swap: the quote, then R + γΔ − Λ; swap_waves.h: the HIP-free
-//                     wave numbering of repeated rows)
-//   abi_swap_path.cpp exact-input swap PATHS that move their pools, all or nothing (cfmm_swap_path; swap_path_waves.h: the HIP-free
-//                     wave numbering of paths that share pools, swap_path_checks.h: the HIP-free checks beyond path_checks.h)
+//   abi_swap.cpp      exact-input swaps that move the pools, and by a direction their exact-output form cfmm_swap_out
+//                     (cfmm_swap: the quote, then R + γΔ − Λ; swap_waves.h: the HIP-free wave numbering of repeated rows)
+//   abi_swap_path.cpp swap PATHS that move their pools, all or nothing, in both directions (cfmm_swap_path,
+//                     cfmm_swap_path_out; swap_path_waves.h: the HIP-free wave numbering of paths that share pools,
+//                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -254,15 +255,19 @@ struct PathScratch {
     bool in_flight = false;
 };
 
-// cfmm_swap (abi_swap.cpp, swap_kernels.h): the device copies of one call's swaps -- in WAVE order (swap_waves.h) -- their
-// answers, the UniV3 landing prices and the pinned staging of all of them, grown on demand and kept for the next call --
-// proportional to the swaps of the largest call, never to the pools.
+// cfmm_swap and cfmm_swap_out (abi_swap.cpp, swap_kernels.h, swap_out_kernels.h; one scratch for both directions): the
+// device copies of one call's swaps -- in WAVE order (swap_waves.h) -- their answers, the UniV3 landing prices and the pinned
+// staging of all of them, grown on demand and kept for the next call -- proportional to the swaps of the largest call, never
+// to the pools.
 struct SwapScratch {
     DevBuf<long long> idx;             // [count]
     DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out
     DevBuf<double> amt, out, price;    // [count]; price: UniV3 segments only
+    DevBuf<double> limit;              // [count] cfmm_swap_out: max_amount_in, where given
+    DevBuf<int32_t> status;            // [count] cfmm_swap_out: CFMM_SWAP_*
     DevBuf<int> left;                  // [1] a new reserve left the window of the fast arithmetic (update_two_coin's flag)
-    PinnedBuf<unsigned long long> stage;   // [5][count] + 1 8-byte words: amounts, coins, answers, prices, idx, the flag
+    PinnedBuf<unsigned long long> stage;   // [6.5][count] + 1 8-byte words: amounts, coins, answers, prices, idx, limits,
+                                           // statuses, the flag
     std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
     int64_t ns = 0;                    // read-only option "swap_ns": the sum of that call's kernel spans
     int64_t refused = 0;               // read-only option "swap_refused": swaps of the latest call that were not applied
@@ -278,7 +283,7 @@ struct SwapPathScratch {
     DevBuf<SwapPathSeg> table;         // [segments]
     DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
     DevBuf<long long> hop_row;         // [max_hops][count]
-    DevBuf<double> amt;                // [2][count] amount_in, min_amount_out
+    DevBuf<double> amt;                // [2][count] the given amounts, the limits
     DevBuf<double> out;                // [count]
     DevBuf<double> hops, price;        // [max_hops][count]
     DevBuf<int32_t> status;            // [count]

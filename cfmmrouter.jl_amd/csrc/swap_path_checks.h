@@ -1,4 +1,5 @@
-// swap_path_checks.h -- internal, host only, HIP-free: what cfmm_swap_path (abi_swap_path.cpp) checks beyond check_paths
+// swap_path_checks.h -- internal, host only, HIP-free: what cfmm_swap_path and cfmm_swap_path_out (abi_swap_path.cpp; exact_out:
+// the limit is max_amount_in, on the first hop's input) check beyond check_paths
 // (path_checks.h), before anything is enqueued.  A path may name a pool (segment, row) only once -- the rule that lets a lane
 // quote the whole path against the market as it stands and apply it afterwards -- and a limit, where one is given, is
 // finite and >= 0.  Same conventions as path_checks.h: the refusal's text goes to a caller's buffer and names the path and
@@ -16,7 +17,7 @@
 namespace cfmm {
 
 inline int check_swap_paths(const char* who, int64_t count, const int32_t* n_hops, const int32_t* hop_seg, const int64_t* hop_row,
-                            const double* min_amount_out, char* msg, size_t len)
+                            const double* limit, char* msg, size_t len, bool exact_out = false)
 {
     for (int64_t p = 0; p < count; ++p) {
         const int nh = n_hops[p];
@@ -29,8 +30,9 @@ inline int check_swap_paths(const char* who, int64_t count, const int32_t* n_hop
                     return CFMM_ERR_INVALID_ARG;
                 }
             }
-        if (min_amount_out && (!(min_amount_out[p] >= 0.0) || !std::isfinite(min_amount_out[p]))) {
-            std::snprintf(msg, len, "%s: path %lld, hop %d: min_amount_out must be finite and >= 0", who, (long long)p, nh - 1);
+        if (limit && (!(limit[p] >= 0.0) || !std::isfinite(limit[p]))) {   // (named at the hop the limited amount belongs to)
+            std::snprintf(msg, len, "%s: path %lld, hop %d: %s must be finite and >= 0", who, (long long)p, exact_out ? 0 : nh - 1,
+                          exact_out ? "max_amount_in" : "min_amount_out");
             return CFMM_ERR_INVALID_ARG;
         }
     }

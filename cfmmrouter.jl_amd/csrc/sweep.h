@@ -434,6 +434,18 @@ struct SwapArgs {
 hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0 = nullptr,
                        hipEvent_t e1 = nullptr);
 
+// cfmm_swap_out (swap_out_kernels.h, abi_swap.cpp): exact-output swaps that move the pools, one lane per swap of one wave.
+// `s` is swap_kernel's view with the roles of the two amounts exchanged as in quote_out_kernel: s.q.amount_in carries the
+// wanted output, s.q.amount_out receives the input tendered.
+constexpr int32_t kSwapApplied = 0, kSwapOverLimit = 1, kSwapRefused = 2, kSwapUnobtainable = 3;   // CFMM_SWAP_* (include/cfmm_amd.h)
+struct SwapOutArgs {
+    SwapArgs s;
+    const double* max_in;        // [count], or null: no limit
+    int32_t* status;             // [count], never null: kSwap*
+};
+hipError_t launch_swap_out(int kind, const SwapOutArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                           hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // cfmm_quote_path / cfmm_quote_path_out (quote_path_kernels.h, abi_quote_path.cpp): an amount carried through a PATH of up
 // to CFMM_MAX_PATH_HOPS pools of any segments in one launch, one lane per path.  The first kernels that read several segments
 // of different kinds at once: the segments reach them as a TABLE in device memory (a market may have more segments than fit
@@ -518,6 +530,10 @@ struct SwapPathArgs {
     int32_t* status;             // [count] kPathApplied / kPathBelowLimit / kPathRefused
 };
 hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// cfmm_swap_path_out (swap_path_out_kernel): the same arguments with the roles of the amounts exchanged, as PathArgs serves
+// both quote directions -- amount_in carries the wanted output of the LAST hop, min_out the limit on the input (max_amount_in),
+// amount_out receives the input to tender to the first hop, hops the amount TO TENDER to hop k, and status is one of kSwap*.
+hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars

@@ -44,7 +44,9 @@
 //   quote_kernels.h   quote_kernel, quote_out_kernel (cfmm_quote, cfmm_quote_out; quote_pool.h: the per-kind forms, src/cfmms.jl:398-449 generalised, and their inverses)
 //   quote_path_kernels.h  quote_path_kernel, quote_path_out_kernel (cfmm_quote_path, cfmm_quote_path_out: the same bodies, hop after hop)
 //   swap_kernels.h    swap_kernel (cfmm_swap: quote_one's answer, then the pool's new state; swap_pool.h: the per-kind new-state forms)
-//   swap_path_kernels.h  swap_path_kernel (cfmm_swap_path: quote_path_kernel's walk, then every hop's new state, all or nothing)
+//   swap_path_kernels.h  swap_path_kernel (cfmm_swap_path: quote_path_kernel's walk, then every hop's new state, all or nothing),
+//                        swap_path_out_kernel (cfmm_swap_path_out: quote_path_out_kernel's walk, then the same)
+//   swap_out_kernels.h   swap_out_kernel (cfmm_swap_out: quote_out_one's answer, then the pool's new state, with a status per swap)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -62,6 +64,7 @@
 #include "quote_path_kernels.h"
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
+#include "swap_out_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -386,6 +389,33 @@ hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0,
         return hipErrorInvalidValue;
     void* args[] = {const_cast<SwapPathArgs*>(&a)};
     return launch_quote_grid(reinterpret_cast<const void*>(&swap_path_kernel<kQuoteBlock>), a.count, args, s, e0, e1);
+}
+
+// cfmm_swap_out: one lane per swap of the wave, the same grid rule
+hipError_t launch_swap_out(int kind, const SwapOutArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.s.q.count <= 0 || a.s.q.m <= 0 || !a.status) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_PRODUCT>); break;
+    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_GEOMEAN>); break;
+    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_UNIV3>); break;
+    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_WEIGHTED>); break;
+    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_CURVE>); break;
+    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_SOLIDLY>); break;
+    default: return hipErrorInvalidDeviceFunction;   // no such kernel
+    }
+    void* args[] = {const_cast<SwapOutArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_quote_grid(kernel, a.s.q.count, args, s, e0, e1);
+}
+
+// cfmm_swap_path_out: launch_swap_path's rule
+hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.count <= 0 || a.stride < a.count || a.nseg <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS || !a.hops || !a.price || !a.status)
+        return hipErrorInvalidValue;
+    void* args[] = {const_cast<SwapPathArgs*>(&a)};
+    return launch_quote_grid(reinterpret_cast<const void*>(&swap_path_out_kernel<kQuoteBlock>), a.count, args, s, e0, e1);
 }
 
 } // namespace cfmm

@@ -733,7 +733,30 @@ def swap_(r: Router, pools, coin_in, amount_in, coin_out=None, sync_host=True):
         r._reset_trades()
 
 
-def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False):
+def swap_out_(r: Router, pools, coin_in, amount_out, coin_out=None, max_in=None, sync_host=True):
+    """Exact-output swaps APPLIED to the pools on the device (cfmm_swap_out): `quote_out`'s arguments and mapping, but every
+    swap moves its pool -- "I must receive exactly this much; take what it costs, unless it costs more than max_in".  The
+    pool gives exactly `amount_out[q]` and takes what `quote_out` answers on the pool as the earlier swaps left it.
+
+    Returns (amount_in, status) in the caller's order: status[q] is SWAP_APPLIED, SWAP_UNOBTAINABLE (the pool cannot give
+    that much: +inf), SWAP_REFUSED (the swap would leave an invalid pool: NaN) or SWAP_OVER_LIMIT (amount_in[q] >
+    max_in[q]: the quote it would have cost); in the last three the pool stays as it was.  max_in: None (no limit), a scalar
+    or one limit per swap.  Order within a segment, the refusal of a host-evaluated pool, sync_host and the zeroing of the
+    router's trades are `swap_`'s."""
+    n = np.asarray(pools).size
+    if max_in is not None:
+        try:
+            max_in = np.ascontiguousarray(np.broadcast_to(np.asarray(max_in, dtype=np.float64), (n,)))
+        except ValueError:
+            raise ArgumentError("max_in must be a scalar or have one entry per pool") from None
+    status = np.empty(n, dtype=np.int32)
+    try:
+        return _quote(r, "swap_out", pools, coin_in, amount_out, coin_out, sync_host=sync_host, max_in=max_in, status=status), status
+    finally:
+        r._reset_trades()
+
+
+def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False, max_in=None, status=None):
     L = r._layout
     pools = np.asarray(pools, dtype=np.int64).reshape(-1)
     n = pools.size
@@ -742,7 +765,7 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False):
         ci = np.ascontiguousarray(np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,)))
         co = None if coin_out is None else np.ascontiguousarray(np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,)))
     except ValueError:
-        raise ArgumentError(f"{'amount_out' if verb == 'quote_out' else 'amount_in'}, coin_in and coin_out must be scalars or have one entry per pool") from None
+        raise ArgumentError(f"{'amount_out' if verb in ('quote_out', 'swap_out') else 'amount_in'}, coin_in and coin_out must be scalars or have one entry per pool") from None
     per_batch = {}
     for q, i in enumerate(pools):
         where = L.locate(i)
@@ -758,7 +781,11 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False):
     out = np.empty(n)
     for b in sorted(per_batch):
         qs, rows = per_batch[b]
-        out[qs] = getattr(ctx, verb)(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
+        if status is not None:   # swap_out_
+            out[qs], status[qs] = ctx.swap_out(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows,
+                                               None if max_in is None else max_in[qs], True)
+        else:
+            out[qs] = getattr(ctx, verb)(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows)
         if sync_host:   # (swap_: the host mirror of the segment follows the device)
             _download_state(ctx, L.seg_of[b], L.batches[b])
             L.sync_pools(r.cfmms, b, sorted(set(rows)))
@@ -799,16 +826,33 @@ def swap_path_(r: Router, pools, tokens, amount_in, min_out=None, hops=False, sy
     ordering by hand and a path refused at its third hop has nothing to unwind.  sync_host=True (default) also refreshes the
     host mirror of the touched segments (`r.cfmms[i].R`, `current_price`).  The router's trades are those of the old market:
     they are zeroed, as by swap_."""
-    n_hops, seg, row, ci, co, amt, touched = _path_hops(r, "swap_path", pools, tokens, amount_in)
-    if min_out is not None:
+    return _swap_path(r, "swap_path", "min_out", pools, tokens, amount_in, min_out, hops, sync_host)
+
+
+def swap_path_out_(r: Router, pools, tokens, amount_out, max_in=None, hops=False, sync_host=True):
+    """Exact-output swap PATHS APPLIED to the pools on the device (cfmm_swap_path_out): `quote_path_out`'s arguments, mapping
+    and refusals, but the paths are executed in the order given, each ALL OR NOTHING -- "buy exactly this much through
+    A -> B -> C, but only if it costs at most max_in".  Path p sees the market as the applied paths before it left it; its
+    amounts are what `quote_path_out` answers on that market, and each pool of an applied path moves as `swap_out_` moves it.
+
+    Returns (amount_in, status[, hop_in]): status[p] is SWAP_APPLIED, SWAP_UNOBTAINABLE (a pool on the way cannot give that
+    much: +inf), SWAP_REFUSED (a hop would leave an invalid pool: NaN) or SWAP_OVER_LIMIT (amount_in[p] > max_in[p]: the
+    quote it would have cost); in the last three nothing moved.  max_in: None (no limit), a scalar or one limit per path.
+    sync_host and the zeroing of the router's trades are `swap_path_`'s."""
+    return _swap_path(r, "swap_path_out", "max_in", pools, tokens, amount_out, max_in, hops, sync_host)
+
+
+def _swap_path(r: Router, verb, limit_name, pools, tokens, amount, limit, hops, sync_host):
+    n_hops, seg, row, ci, co, amt, touched = _path_hops(r, verb, pools, tokens, amount)
+    if limit is not None:
         try:
-            min_out = np.ascontiguousarray(np.broadcast_to(np.asarray(min_out, dtype=np.float64), amt.shape))
+            limit = np.ascontiguousarray(np.broadcast_to(np.asarray(limit, dtype=np.float64), amt.shape))
         except ValueError:
-            raise ArgumentError("min_out must be a scalar or have one entry per path") from None
+            raise ArgumentError(f"{limit_name} must be a scalar or have one entry per path") from None
     ctx = _path_context(r)
     L = r._layout
     try:
-        res = ctx.swap_path(n_hops, seg, row, ci, co, amt, min_out, hops)
+        res = getattr(ctx, verb)(n_hops, seg, row, ci, co, amt, limit, hops)
         if sync_host:
             for b in sorted(touched):
                 _download_state(ctx, L.seg_of[b], L.batches[b])
@@ -841,7 +885,7 @@ def _path_hops(r: Router, verb, pools, tokens, amount):
     try:
         amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
     except ValueError:
-        raise ArgumentError(f"{'amount_out' if verb == 'quote_path_out' else 'amount_in'} must be a scalar or have one entry per path") from None
+        raise ArgumentError(f"{'amount_out' if verb.endswith('_out') else 'amount_in'} must be a scalar or have one entry per path") from None
     paths = [(np.asarray(pl, dtype=np.int64).reshape(-1), np.asarray(tk, dtype=np.int64).reshape(-1)) for pl, tk in zip(pools, tokens)]
     for p, (pl, tk) in enumerate(paths):
         if not 1 <= pl.size <= MAX_PATH_HOPS:

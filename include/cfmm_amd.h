@@ -474,6 +474,45 @@ int cfmm_quote_path_out_dev(cfmm_ctx* ctx, int64_t count, int32_t max_hops, cons
 int cfmm_swap(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
               const int32_t* coin_out, const double* amount_in, double* amount_out);
 
+/* Exact-output swaps that MOVE the pools: "I must receive exactly amount_out of coin_out from this pool; take what that
+ * costs, unless it costs more than max_amount_in" -- the other half of cfmm_quote_out, and cfmm_swap's mirror image.  The
+ * arguments are cfmm_quote_out's plus max_amount_in, NULL (no limit) or [count], each finite and >= 0, and status, NULL or
+ * [count].  All of cfmm_quote_out's checks and the limit check run before anything is enqueued: a failure is
+ * CFMM_ERR_INVALID_ARG, names the query in cfmm_last_error with the prefix "cfmm_swap_out:", and leaves the outputs AND the
+ * pools untouched.
+ * The swaps are applied IN QUERY ORDER.  For q = 0, 1, ...: amount_in[q] is exactly, bit for bit, what cfmm_quote_out answers
+ * for that query on the pool as swaps 0 .. q-1 left it (the kernel runs cfmm_quote_out's own function).  The swap then
+ * delivers exactly the amount asked for -- not cfmm_quote(amount_in), which differs from it by rounding:
+ *   Reserve kinds: R_in <- R_in + γ·amount_in, R_out <- R_out − amount_out, each operation rounded on its own; prepared
+ *     constants and the fast-arithmetic window flag exactly as in cfmm_swap.
+ *   UniV3: the state is the price, and the price is determined by the input: the pool rests at the price cfmm_swap of
+ *     amount_in comes to rest at (the same function on the device, the same clamp and re-preparation on the host), so a
+ *     UniV3 pool is left, bit for bit, where cfmm_swap of amount_in leaves it.  cfmm_quote_out finds its record on the running
+ *     sums of the ticks' outputs and the landing price finds its own on the running sums of their inputs; when amount_out
+ *     equals a running output sum at a tick boundary the two may name neighbouring records, which is harmless: the price is
+ *     continuous across the boundary.
+ * amount_out == 0 answers +0.0 and leaves every bit of the pool (status CFMM_SWAP_APPLIED).
+ * A swap is NOT APPLIED in three cases, tested in this order; in each the pool keeps every bit, later swaps of that row
+ * proceed from the unchanged state, and the call still returns CFMM_OK.  status[q]:
+ *   CFMM_SWAP_APPLIED       applied                  amount_in[q] the answer
+ *   CFMM_SWAP_UNOBTAINABLE  cfmm_quote_out answers +inf (the pool cannot give that much)   amount_in[q] +inf
+ *   CFMM_SWAP_REFUSED       the new state is one cfmm_pools_set_* refuses -- cfmm_swap's conditions, unchanged; on UniV3 a
+ *                           landing price that is not finite and > 0                       amount_in[q] NaN
+ *   CFMM_SWAP_OVER_LIMIT    !(amount_in[q] <= max_amount_in[q])                            amount_in[q] the quote it would have cost
+ * "swap_refused" is the number of swaps of the latest call whose status is not CFMM_SWAP_APPLIED.
+ * Everything else is cfmm_swap's: the invalidation of earlier trades and outputs, count == 0 as a no-op, synchronous on the
+ * context's stream, repeated rows ordered on the host in launches of distinct rows (one launch per wave, UniV3 pools moved
+ * on the host between them), no _dev form, "swap_ns" and "swap_launches", device memory proportional to count; on a
+ * multi-device context the swaps go to the shards that hold their rows, every check runs before any shard changes, and
+ * amount_in and status return in query order. */
+#define CFMM_SWAP_APPLIED 0      /* == CFMM_PATH_APPLIED */
+#define CFMM_SWAP_OVER_LIMIT 1   /* == CFMM_PATH_BELOW_LIMIT's value: "the limit was not met" */
+#define CFMM_SWAP_REFUSED 2      /* == CFMM_PATH_REFUSED */
+#define CFMM_SWAP_UNOBTAINABLE 3 /* the pool cannot give that much: cfmm_quote_out answers +inf */
+int cfmm_swap_out(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
+                  const int32_t* coin_out, const double* amount_out, const double* max_amount_in, double* amount_in,
+                  int32_t* status);
+
 /* Exact-input swap PATHS that MOVE their pools, each path all or nothing: what a transaction does on a chain -- it runs in
  * order, reverts whole, and carries a slippage limit.  The path arguments are exactly cfmm_quote_path's (hop-major
  * [max_hops][count], 1 .. CFMM_MAX_PATH_HOPS hops, slots at k >= n_hops[p] ignored); min_amount_out is NULL (no limit) or
@@ -509,8 +548,9 @@ int cfmm_swap(cfmm_ctx* ctx, int32_t seg, int64_t count, const int64_t* idx, con
  * being taken, for that launch, by every earlier path that names it -- applied or not, the host cannot know in advance.  Each
  * launch holds pool-disjoint paths only; a batch of pool-disjoint paths is one launch; the host waits between launches only
  * behind one with a UniV3 hop, whose pools it re-prepares.  There is NO cfmm_swap_path_dev, for cfmm_swap's reason: the
- * order is decided on the host.  There is no exact-output form.
- * Read-only options: "swap_launches", the number of launches (waves) of the latest cfmm_swap or cfmm_swap_path call; under
+ * order is decided on the host.  The exact-output form, cfmm_swap_path_out, is declared in
+ * cfmm_amd_path_out.h.
+ * Read-only options: "swap_launches", the number of launches (waves) of the latest cfmm_swap* call; under
  * "time_kernels", "swap_ns", the sum of their kernel spans. */
 #define CFMM_PATH_APPLIED 0
 #define CFMM_PATH_BELOW_LIMIT 1

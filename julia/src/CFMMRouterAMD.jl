@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, swap_out!, swap_paths_out!, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -518,6 +518,54 @@ function swap!(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::Abstract
     return out
 end
 
+# swap_out!(r, pools, coin_in, amount_out; coin_out, max_in=nothing, sync=true) -- the Python host's `swap_out_` (cfmm_swap_out):
+# quote_swaps_out's arguments, but every swap is APPLIED: the pool gives exactly amount_out[q] and takes what quote_swaps_out
+# answers on the pool as the earlier swaps of the call left it (R_in + γ·amount_in, R_out − amount_out; UniV3: the price swap!
+# of amount_in rests at).  Returns (amount_in, status): status[q] is 0 (applied), 3 (the pool cannot give that much: Inf),
+# 2 (the swap would leave an invalid pool: NaN) or 1 (amount_in[q] > max_in[q]: the quote it would have cost); in the last
+# three the pool stays as it was.  Order within a segment, sync and the zeroing of the router's trades are swap!'s.
+const SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = Int32(0), Int32(1), Int32(2), Int32(3)   # CFMM_SWAP_*
+function swap_out!(r::AMDRouter, pools::AbstractVector{<:Integer}, coin_in::AbstractVector{<:Integer},
+                   amount_out::AbstractVector{<:Real}; coin_out=nothing, max_in=nothing, sync::Bool=true)
+    n = length(pools)
+    (length(coin_in) == n && length(amount_out) == n && (isnothing(coin_out) || length(coin_out) == n) &&
+     (isnothing(max_in) || length(max_in) == n)) ||
+        throw(ArgumentError("coin_in, the amounts, coin_out and max_in must have one entry per pool"))
+    where = segment_rows(r)
+    segs = Dict{Int32,Vector{Int}}()                      # segment => query numbers, in the caller's order
+    for (q, i) in enumerate(pools)
+        i in r.host && throw(ArgumentError("pool $i: $(typeof(r.cfmms[i])) is evaluated on the host by its own find_arb! and has no device state to quote"))
+        haskey(where, i) || throw(ArgumentError("pool $i out of range"))
+        push!(get!(segs, where[i][1], Int[]), q)
+    end
+    out = Vector{Float64}(undef, n)
+    status = Vector{Int32}(undef, n)
+    try
+        for s in sort(collect(keys(segs)))
+            qs = segs[s]
+            idx = Int64[where[pools[q]][2] for q in qs]
+            ci = Int32[coin_in[q] - 1 for q in qs]
+            co = isnothing(coin_out) ? Int32[] : Int32[coin_out[q] - 1 for q in qs]
+            amt = Float64[amount_out[q] for q in qs]
+            lim = isnothing(max_in) ? Float64[] : Float64[max_in[q] for q in qs]
+            res = Vector{Float64}(undef, length(qs))
+            st = Vector{Int32}(undef, length(qs))
+            cop = isnothing(coin_out) ? C_NULL : pointer(co)
+            lp = isnothing(max_in) ? Ptr{Float64}(C_NULL) : pointer(lim)
+            GC.@preserve idx ci co amt lim res st check(r.ctx,
+                ccall((:cfmm_swap_out, LIB), Cint,
+                      (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                      r.ctx, s, length(qs), idx, ci, cop, amt, lp, res, st))
+            out[qs] .= res
+            status[qs] .= st
+        end
+        sync && download_state!(r)
+    finally
+        foreach(d -> fill!(d, 0), r.Δs); foreach(l -> fill!(l, 0), r.Λs)
+    end
+    return out, status
+end
+
 # both directions: `amount_in` is the GIVEN amount (the wanted output when exact_out), the result the answer
 function quote_queries(r::AMDRouter, pools, coin_in, amount_in, coin_out, exact_out::Bool)
     n = length(pools)
@@ -643,6 +691,9 @@ function swap_paths!(r::AMDRouter, pools::AbstractVector, tokens::AbstractVector
     end
     return hops ? (out, status, hv) : (out, status)
 end
+
+
+include("swap_paths_out.jl")   # swap_paths_out! (cfmm_swap_path_out, declared in include/cfmm_amd_path_out.h)
 
 # forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449: methods of CFMMRouter's own function (imported above) for the pool kinds it
 # has none for, one pool through the device (a one-pool AMDRouter).  Δ has exactly one positive entry; on pools of more than
