@@ -24,6 +24,7 @@ ERR_UNSUPPORTED = -4
 MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
 PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = 0, 1, 2   # CFMM_PATH_*: Context.swap_path's status
 SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = 0, 1, 2, 3   # CFMM_SWAP_*: Context.swap_out's / swap_path_out's status
+FOUND, FOUND_NONE, FOUND_REPEATS = 0, 1, 2   # CFMM_FOUND*: Context.find_path's status
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -146,6 +147,7 @@ def lib():
     L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -644,6 +646,32 @@ class Context:
                 raise ArgumentError(f"{name} must be a [count, max_hops] array, like the other hop arguments")
             cols.append(a)
         return (nh, *(np.ascontiguousarray(a.T) for a in cols))
+
+    # -- path search (cfmm_find_path): the best walk of at most max_hops hops between two tokens, found on the device ----------
+    def find_path(self, token_in, token_out, amount_in, max_hops=3):
+        """The best swap walk from token_in[q] to token_out[q] (0-based token ids) for amount_in[q], of at most max_hops
+        (1 .. MAX_PATH_HOPS) hops, on the pools as they stand on the device (cfmm_find_path): returns (amount_out, n_hops, seg,
+        row, ci, co, status) -- amount_out, n_hops, status [count]; seg, row, ci, co [count, max_hops] hop arrays, exactly what
+        quote_path / swap_path take (-1 in the slots at k >= n_hops[q]).  The contract is the layered search: layer h holds, per
+        token, the largest quote over every pool and ordered coin pair from layer h-1; the answer is the largest layer entry of
+        token_out, with the fewest hops, walked back through the smallest (segment, row, coin_in, coin_out) that attains each
+        layer bit for bit -- so quote_path on the result answers amount_out bit for bit.  Every hop is quoted against the pool
+        as it stands; the result is a WALK and may visit a pool twice: status[q] is FOUND, FOUND_NONE (not reached, or amount 0:
+        amount_out 0.0, n_hops 0) or FOUND_REPEATS (swap_path would refuse it as one path).  Scalars broadcast.  Read-only.
+        Everything is checked before anything runs (ArgumentError names the query)."""
+        try:
+            tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int32).reshape(-1), np.asarray(token_out, dtype=np.int32).reshape(-1),
+                                                 f64(amount_in).reshape(-1))
+        except ValueError:
+            raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+        tin, tout, amt = (np.ascontiguousarray(a) for a in (tin, tout, amt))
+        n, H = amt.size, int(max_hops)
+        out, nh, st = np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        seg, ci, co = (np.empty((max(H, 0), n), dtype=np.int32) for _ in range(3))
+        row = np.empty((max(H, 0), n), dtype=np.int64)
+        self._check(self._L.cfmm_find_path(self._h, n, H, ptr(tin), ptr(tout), ptr(amt), ptr(out), ptr(nh), ptr(seg), ptr(row), ptr(ci),
+                                           ptr(co), ptr(st)))
+        return out, nh, seg.T.copy(), row.T.copy(), ci.T.copy(), co.T.copy(), st
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
                        d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):

@@ -276,6 +276,7 @@ static int64_t* option_slot(cfmm_ctx* c, const char* key)
         {"cost_geomean", &c->geo.cost_geomean}, {"cost_univ3", &c->geo.cost_univ3}, {"host_flag", &c->opt_host_flag},
         {"stop_in_noise", &c->opt_stop_in_noise}, {"multi_threads", &c->opt_multi_threads},
         {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->geo.direct_small}, {"stream_stores", &c->opt_stream_stores},
+        {"find_lds", &c->opt_find_lds},
 #ifdef CFMM_TEST_HOOKS
         {"debug_stall_ms", &c->opt_debug_stall_ms},
 #endif
@@ -336,6 +337,19 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (key && !std::strcmp(key, "swap_ns")) { *value = c->swap.ns; return CFMM_OK; }
     if (key && !std::strcmp(key, "swap_refused")) { *value = c->swap.refused; return CFMM_OK; }
     if (key && !std::strcmp(key, "swap_launches")) { *value = c->swap.launches; return CFMM_OK; }
+    // read-only, cfmm_find_path: the latest call's kernel launches, and under "time_kernels" the sums of the spans of its layer
+    // launches (find_relax) and of its walk-back launches (find_claim + find_advance)
+    if (key && !std::strcmp(key, "find_launches")) { *value = c->find.launches; return CFMM_OK; }
+    if (key && !std::strcmp(key, "find_relax_ns")) { *value = c->find.relax_ns; return CFMM_OK; }
+    if (key && !std::strcmp(key, "find_walk_ns")) { *value = c->find.walk_ns; return CFMM_OK; }
+    for (int k = 0; k < 3 && key; ++k) {   // ... and layer by layer: "find_relax_ns_3" is layer 3's find_relax
+        static const char* const names[3] = {"find_relax_ns_", "find_claim_ns_", "find_advance_ns_"};
+        const size_t len = std::strlen(names[k]);
+        if (!std::strncmp(key, names[k], len) && key[len] >= '1' && key[len] <= '0' + CFMM_MAX_PATH_HOPS && !key[len + 1]) {
+            *value = c->find.layer_ns[k][key[len] - '1'];
+            return CFMM_OK;
+        }
+    }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
     // option "time_kernels" (a parent reports its first shard's)
     if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }

@@ -1,0 +1,229 @@
+// abi_find_path.cpp -- cfmm_find_path: the best swap walk of at most max_hops hops between two tokens, found on the device by
+// layers (the kernels and the contract: find_path_kernels.h; the checks and the chunking rule: find_checks.h).
+// Read-only.  Like the path quotes the kernels see the segments through a table in device memory (sweep.h FindSeg) that
+// build_table below REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES AND UPLOADS ON EVERY CALL: it is never a cache.
+// The queries are processed in chunks whose layers fit kFindScratchBudget; a chunk is a sequence of launches on the context's
+// stream -- clear, find_init, find_relax per layer, find_select, then find_claim + find_advance per layer from the last, and
+// find_finish, which writes the chunk's part of the call's outputs -- and no chunk reads what another wrote, so the results do
+// not depend on the chunking.  One synchronisation, at the end.
+#include "ctx.h"
+#include "find_checks.h"
+
+#include <algorithm>
+#include <cstring>
+
+using namespace cfmm;
+
+namespace {
+
+constexpr const char* kWho = "cfmm_find_path";
+constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
+
+// one record per segment from the addresses the segment holds NOW (every stored segment has pools); returns the blocks that
+// cover them
+int64_t build_table(const cfmm_ctx* c, FindSeg* t)
+{
+    std::memset(t, 0, c->segs.size() * sizeof(FindSeg));
+    int64_t tiles = 0, pools = 0;
+    for (size_t i = 0; i < c->segs.size(); ++i) {
+        const Segment& s = c->segs[i];
+        FindSeg& f = t[i];
+        PathSeg& r = f.s;
+        r.kind = s.m > 0 ? s.kind : -1;
+        r.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
+        r.m = s.m;
+        if (s.kind == CFMM_KIND_UNIV3) {
+            r.pg = s.u.pg.get();
+            r.cur_a = s.u.cur_a.get();
+            r.cur_b = s.u.cur_b.get();
+            r.cur_c = s.u.cur_c.get();
+            r.curR = s.u.curR.get();
+            r.walk = s.u.walk.get();
+            r.ticks = s.u.ticks.get();
+        } else if (ragged_kind(s.kind)) {
+            r.nR = s.nc.R.get();
+            r.nq = s.nc.q.get();
+            r.nglg = s.nc.glg.get();
+            r.npar = s.nc.par.get();
+        } else {
+            r.R = s.R.get();
+            r.w = s.w.get();
+            r.gamma = s.gamma.get();
+        }
+        if (ragged_kind(s.kind)) {
+            f.tok = s.nc.tok.get();
+        } else {
+            f.pk = s.pk.get();
+            f.Ai = s.Ai.get();
+        }
+        f.first_tile = tiles;
+        f.first_pool = pools;
+        tiles += (s.m + kFindBlock - 1) / kFindBlock;
+        pools += s.m;
+    }
+    return tiles;
+}
+
+struct Timing {
+    cfmm_ctx* c;
+    bool on;
+    size_t used = 0;
+    std::vector<int> what, layer;   // FindKernel and layer of every timed launch, in order
+    int pair(hipEvent_t& e0, hipEvent_t& e1, FindKernel k, int h)
+    {
+        e0 = e1 = nullptr;
+        if (!on) return CFMM_OK;
+        std::vector<Event>& ev = c->find.ev;
+        if (ev.size() < used + 2) ev.resize(used + 2);
+        int rc;
+        if ((rc = ev[used].create(c, hipEventDefault)) || (rc = ev[used + 1].create(c, hipEventDefault))) return rc;
+        e0 = ev[used].get();
+        e1 = ev[used + 1].get();
+        used += 2;
+        what.push_back(k);
+        layer.push_back(h);
+        return CFMM_OK;
+    }
+};
+
+int launch(cfmm_ctx* c, Timing& t, FindKernel k, const FindArgs& a)
+{
+    hipEvent_t e0, e1;
+    const int rc = t.pair(e0, e1, k, a.layer);
+    if (rc != CFMM_OK) return rc;
+    const hipError_t e = launch_find(k, a, c->stream, e0, e1);
+    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "find path launch failed: %s", hipGetErrorString(e));
+    ++c->find.launches;
+    return CFMM_OK;
+}
+
+} // namespace
+
+int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+                   const double* amount_in, double* amount_out, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
+                   int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status)
+{
+    if (!c) return CFMM_ERR_INVALID_ARG;
+    if (is_parent(c))
+        return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context: the layers of the search live on one "
+                                             "device (find on a single-device context of the same pools)", kWho);
+    char msg[256] = "";
+    int rc = check_find(kWho, c->n, count, max_hops, token_in, token_out, amount_in, amount_out, n_hops, hop_seg, hop_row, hop_coin_in,
+                        hop_coin_out, status, msg, sizeof msg);
+    if (rc != CFMM_OK) return fail(c, rc, "%s", msg);
+    if (count == 0) return CFMM_OK;
+    FindScratch& fs = c->find;
+    fs.launches = fs.relax_ns = fs.walk_ns = 0;
+    std::memset(fs.layer_ns, 0, sizeof fs.layer_ns);
+    const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H;
+    if (c->segs.empty()) {   // a market without pools reaches nothing
+        for (size_t q = 0; q < n; ++q) {
+            amount_out[q] = 0.0;
+            n_hops[q] = 0;
+            status[q] = CFMM_FOUND_NONE;
+        }
+        for (size_t at = 0; at < nh; ++at) {
+            hop_seg[at] = hop_coin_in[at] = hop_coin_out[at] = -1;
+            hop_row[at] = -1;
+        }
+        return CFMM_OK;
+    }
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t nseg = c->segs.size(), nt = (size_t)c->n;
+    const size_t chunk = (size_t)std::min<int64_t>(count, find_chunk_queries(c->n, max_hops));
+    // staging, 8-byte words: the table | token_in, token_out | amount_in || amount_out | n_hops, status | the three int32 hop
+    // columns | the rows
+    const size_t w_table = words_of(nseg * sizeof(FindSeg)), w_tok = words_of(2 * n * sizeof(int32_t));
+    const size_t w_ns = words_of(2 * n * sizeof(int32_t)), w_hop32 = words_of(3 * nh * sizeof(int32_t));
+    const size_t w_in = w_table + w_tok + n, w_out = n + w_ns + w_hop32 + nh;
+    if ((rc = fs.stage.grow(c, w_in + w_out, false)) || (rc = fs.table.grow(c, nseg)) || (rc = fs.best.grow(c, (H + 1) * chunk * nt)) ||
+        (rc = fs.edge.grow(c, H * chunk)) || (rc = fs.i32.grow(c, 4 * n + 3 * nh + 2 * chunk)) || (rc = fs.hop_row.grow(c, nh)) ||
+        (rc = fs.amt.grow(c, 2 * n)))
+        return rc;
+    unsigned long long* st = fs.stage.host();
+    const int64_t tiles = build_table(c, reinterpret_cast<FindSeg*>(st));
+    int32_t* h_tok = reinterpret_cast<int32_t*>(st + w_table);
+    double* h_amt = reinterpret_cast<double*>(st + w_table + w_tok);
+    double* h_out = reinterpret_cast<double*>(st + w_in);
+    int32_t* h_ns = reinterpret_cast<int32_t*>(st + w_in + n);
+    int32_t* h_hop32 = reinterpret_cast<int32_t*>(st + w_in + n + w_ns);
+    long long* h_row = reinterpret_cast<long long*>(st + w_in + n + w_ns + w_hop32);
+    std::memcpy(h_tok, token_in, n * sizeof(int32_t));
+    std::memcpy(h_tok + n, token_out, n * sizeof(int32_t));
+    std::memcpy(h_amt, amount_in, n * sizeof(double));
+    int32_t* d_i32 = fs.i32.get();
+    HIP_TRY(c, hipMemcpyAsync(fs.table.get(), st, nseg * sizeof(FindSeg), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_i32, h_tok, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(fs.amt.get(), h_amt, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+
+    Timing timing{c, c->opt_time_kernels != 0};
+    for (size_t q0 = 0; q0 < n; q0 += chunk) {
+        const size_t cq = std::min(chunk, n - q0);
+        FindArgs a{};
+        a.count = (int64_t)cq;
+        a.stride = count;
+        a.max_hops = max_hops;
+        a.nseg = (int32_t)nseg;
+        a.n_tokens = c->n;
+        a.tiles = tiles;
+        a.segs = fs.table.get();
+        a.token_in = d_i32 + q0;
+        a.token_out = d_i32 + n + q0;
+        a.n_hops = d_i32 + 2 * n + q0;
+        a.status = d_i32 + 3 * n + q0;
+        a.hop_seg = d_i32 + 4 * n + q0;
+        a.hop_coin_in = d_i32 + 4 * n + nh + q0;
+        a.hop_coin_out = d_i32 + 4 * n + 2 * nh + q0;
+        a.h_star = d_i32 + 4 * n + 3 * nh;
+        a.target = d_i32 + 4 * n + 3 * nh + chunk;
+        a.hop_row = fs.hop_row.get() + q0;
+        a.amount_in = fs.amt.get() + q0;
+        a.amount_out = fs.amt.get() + n + q0;
+        a.best = fs.best.get();
+        a.edge = fs.edge.get();
+        HIP_TRY(c, hipMemsetAsync(a.best, 0, (H + 1) * cq * nt * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(a.edge, 0xff, H * cq * sizeof(unsigned long long), c->stream));
+        if ((rc = launch(c, timing, kFindInit, a)) != CFMM_OK) return rc;
+        // the layers: with the block's LDS copy where a group of queries' rows fit it (option "find_lds", default on), a block
+        // folding enough tiles that about four blocks per CU remain
+        a.group = c->opt_find_lds != 0 ? find_lds_group(c->n) : 0;
+        if (a.group > 0) {
+            a.group = (int32_t)std::min<int64_t>(a.group, (int64_t)cq);
+            const int64_t rows = ((int64_t)cq + a.group - 1) / a.group;
+            a.tiles_per_block = (int32_t)std::clamp<int64_t>(tiles * rows / 1024, 1, 64);
+            if (rows > 65535) a.group = 0;
+        }
+        for (a.layer = 1; a.layer <= max_hops; ++a.layer)
+            if ((rc = launch(c, timing, kFindRelax, a)) != CFMM_OK) return rc;
+        a.group = 0;
+        if ((rc = launch(c, timing, kFindSelect, a)) != CFMM_OK) return rc;
+        for (a.layer = max_hops; a.layer >= 1; --a.layer)
+            if ((rc = launch(c, timing, kFindClaim, a)) || (rc = launch(c, timing, kFindAdvance, a))) return rc;
+        a.layer = 0;
+        if ((rc = launch(c, timing, kFindFinish, a)) != CFMM_OK) return rc;
+    }
+    HIP_TRY(c, hipMemcpyAsync(h_out, fs.amt.get() + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_ns, d_i32 + 2 * n, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_hop32, d_i32 + 4 * n, 3 * nh * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_row, fs.hop_row.get(), nh * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < timing.what.size(); ++k) {
+        float ms = 0.f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, fs.ev[2 * k].get(), fs.ev[2 * k + 1].get()));
+        const int64_t ns = (int64_t)((double)ms * 1e6);
+        const int w = timing.what[k], h = timing.layer[k];
+        if (w == kFindRelax) fs.relax_ns += ns;
+        if (w == kFindClaim || w == kFindAdvance) fs.walk_ns += ns;
+        if ((w == kFindRelax || w == kFindClaim || w == kFindAdvance) && h >= 1 && h <= CFMM_MAX_PATH_HOPS)
+            fs.layer_ns[w == kFindRelax ? 0 : (w == kFindClaim ? 1 : 2)][h - 1] += ns;
+    }
+    std::memcpy(amount_out, h_out, n * sizeof(double));
+    std::memcpy(n_hops, h_ns, n * sizeof(int32_t));
+    std::memcpy(status, h_ns + n, n * sizeof(int32_t));
+    std::memcpy(hop_seg, h_hop32, nh * sizeof(int32_t));
+    std::memcpy(hop_coin_in, h_hop32 + nh, nh * sizeof(int32_t));
+    std::memcpy(hop_coin_out, h_hop32 + 2 * nh, nh * sizeof(int32_t));
+    std::memcpy(hop_row, h_row, nh * sizeof(long long));
+    return CFMM_OK;
+}

@@ -23,6 +23,8 @@
 //   abi_swap_path.cpp swap PATHS that move their pools, all or nothing, in both directions (cfmm_swap_path,
 //                     cfmm_swap_path_out; swap_path_waves.h: the HIP-free wave numbering of paths that share pools,
 //                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
+//   abi_find_path.cpp the best swap walk between two tokens, found on the device (cfmm_find_path; find_checks.h: the HIP-free
+//                     checks and the chunking rule)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -293,6 +295,29 @@ struct SwapPathScratch {
     PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
 };
 
+// cfmm_find_path (abi_find_path.cpp, find_path_kernels.h): the layers of the search -- the one array of the path features that
+// is proportional to n_tokens: (max_hops + 1) x queries of a chunk x n_tokens words, bounded by kFindScratchBudget
+// (find_checks.h) -- the claimed edges, the device copies of one call's queries and answers, the segment table (sweep.h
+// FindSeg, rebuilt per call) and ONE pinned staging buffer, all grown on demand and kept for the next call.  The call ends
+// synchronised, so nothing here is guarded against the call before.
+struct FindScratch {
+    DevBuf<FindSeg> table;             // [segments]
+    DevBuf<unsigned long long> best;   // [max_hops + 1][chunk][n_tokens]
+    DevBuf<unsigned long long> edge;   // [max_hops][chunk]
+    DevBuf<int32_t> i32;               // [4][count] token_in, token_out, n_hops, status; [3][max_hops][count] hop_seg, hop_coin_in,
+                                       // hop_coin_out; [2][chunk] the hops of the answer, the walk's target token
+    DevBuf<long long> hop_row;         // [max_hops][count]
+    DevBuf<double> amt;                // [2][count] amount_in, amount_out
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
+    std::vector<Event> ev;             // option "time_kernels": {start, stop} per launch of the latest call
+    int64_t relax_ns = 0, walk_ns = 0; // read-only options "find_relax_ns" / "find_walk_ns": the sums of that call's find_relax spans
+                                       // and of its find_claim + find_advance spans
+    int64_t launches = 0;              // read-only option "find_launches": kernel launches of the latest call
+    // the same spans layer by layer, summed over the call's chunks: read-only options "find_relax_ns_<h>", "find_claim_ns_<h>",
+    // "find_advance_ns_<h>", h = 1 .. CFMM_MAX_PATH_HOPS (0 for a layer the call did not have)
+    int64_t layer_ns[3][CFMM_MAX_PATH_HOPS] = {};
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -401,6 +426,9 @@ struct cfmm_ctx {
     int64_t opt_stream_stores = 0; // trade-record stores: 0 = auto (non-temporal when one sweep touches more than the 256 MiB Infinity Cache,
                                    //    i.e. the pool state cannot stay cache-resident between sweeps; write-through otherwise), 1 = always
                                    //    write-through, 2 = always non-temporal (a caller that rotates over many markets says so)
+    int64_t opt_find_lds = 1;      // 1: cfmm_find_path's layer launches fold their candidates into a per-block LDS copy of the layer rows
+                                   //    first, where n_tokens lets one fit (find_path_kernels.h find_relax<., true>); 0: every candidate
+                                   //    goes to global memory (the A/B of scripts/find_path_times.py; the same bits either way)
     int64_t opt_univ3_heads = 1;   // 1: multi-tick UniV3 walks decide their first four list ticks from the per-pool float threshold heads
     int64_t opt_dev_prices_in_window = 0; // 1 = the CALLER vouches that the prices of device-pointer sweeps lie in [2^-kFastExp, 2^kFastExp]
                                      //    (what the host checks itself for host-pointer calls): cfmm_sweep_dev launches the fast kernels
@@ -417,6 +445,7 @@ struct cfmm_ctx {
     cfmm::PathScratch path;
     cfmm::SwapScratch swap;
     cfmm::SwapPathScratch swap_path;
+    cfmm::FindScratch find;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own

@@ -1,0 +1,68 @@
+// find_checks.h -- internal, host only, HIP-free: the checks of a batch of cfmm_find_path queries before anything is enqueued,
+// and the rule that cuts a call into chunks of queries (abi_find_path.cpp).  Like path_checks.h they take plain arrays and
+// write the refusal's text into a caller's buffer, so a host program without a device or a context can exercise them
+// (tests/native/find_checks_host.cpp).  A refusal names the QUERY.
+#pragma once
+
+#include "../../include/cfmm_amd.h"
+
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+
+namespace cfmm {
+
+// The layers of one chunk, (max_hops + 1) x queries x n_tokens words of 8 bytes, stay within this budget: a design choice --
+// the size of the Infinity Cache, so that a layer that is being relaxed and the one it is relaxed from can stay on chip.
+// Results do not depend on it.
+constexpr int64_t kFindScratchBudget = 256ll << 20;
+// queries of one chunk beyond which no budget asks to go: gridDim.y of the per-pool launches is 65535 rows of 64 queries
+constexpr int64_t kFindMaxChunk = 1 << 20;
+
+// queries per chunk for a market of n_tokens: as many as the budget holds, at least one (a single query of a market whose
+// layers exceed the budget still runs, over the budget)
+inline int64_t find_chunk_queries(int64_t n_tokens, int32_t max_hops, int64_t budget = kFindScratchBudget)
+{
+    const int64_t per_query = (int64_t)(max_hops + 1) * (n_tokens < 1 ? 1 : n_tokens) * 8;
+    const int64_t fit = budget / per_query;
+    return fit < 1 ? 1 : (fit > kFindMaxChunk ? kFindMaxChunk : fit);
+}
+
+inline int check_find(const char* who, int64_t n_tokens, int64_t count, int32_t max_hops, const int32_t* token_in,
+                      const int32_t* token_out, const double* amount_in, const void* amount_out, const void* n_hops, const void* hop_seg,
+                      const void* hop_row, const void* hop_coin_in, const void* hop_coin_out, const void* status, char* msg, size_t len)
+{
+    if (count < 0) {
+        std::snprintf(msg, len, "%s: count must be >= 0", who);
+        return CFMM_ERR_INVALID_ARG;
+    }
+    if (max_hops < 1 || max_hops > CFMM_MAX_PATH_HOPS) {
+        std::snprintf(msg, len, "%s: max_hops must be 1 .. %d (got %d)", who, CFMM_MAX_PATH_HOPS, (int)max_hops);
+        return CFMM_ERR_INVALID_ARG;
+    }
+    if (count == 0) return CFMM_OK;
+    if (!token_in || !token_out || !amount_in || !amount_out || !n_hops || !hop_seg || !hop_row || !hop_coin_in || !hop_coin_out || !status) {
+        std::snprintf(msg, len, "%s: null query array", who);
+        return CFMM_ERR_INVALID_ARG;
+    }
+    for (int64_t q = 0; q < count; ++q) {
+        if (token_in[q] < 0 || token_in[q] >= n_tokens) {
+            std::snprintf(msg, len, "%s: query %lld: token_in %d out of range (the market has %lld tokens)", who, (long long)q,
+                          (int)token_in[q], (long long)n_tokens);
+            return CFMM_ERR_INVALID_ARG;
+        }
+        if (token_out[q] < 0 || token_out[q] >= n_tokens) {
+            std::snprintf(msg, len, "%s: query %lld: token_out %d out of range (the market has %lld tokens)", who, (long long)q,
+                          (int)token_out[q], (long long)n_tokens);
+            return CFMM_ERR_INVALID_ARG;
+        }
+        if (!(amount_in[q] >= 0.0) || !std::isfinite(amount_in[q])) {
+            std::snprintf(msg, len, "%s: query %lld: amount_in must be finite and >= 0", who, (long long)q);
+            return CFMM_ERR_INVALID_ARG;
+        }
+    }
+    return CFMM_OK;
+}
+
+} // namespace cfmm

@@ -535,6 +535,58 @@ hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 
 // amount_out receives the input to tender to the first hop, hops the amount TO TENDER to hop k, and status is one of kSwap*.
 hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_find_path (find_path_kernels.h, abi_find_path.cpp): the best walk of at most max_hops hops between two tokens, by
+// layers -- one launch per layer with ONE LANE PER POOL of every segment.  The kernels read a table of their own: what
+// PathSeg holds (the quotes' view, unchanged), the segment's token arrays (two-coin kinds and UniV3: the packed records, or
+// the plain pairs in large-market mode, as SelectArgs; ragged kinds: the coin-major column) and where the segment starts in
+// the two numberings the kernels use -- blocks of the per-pool launches, and pools of the whole market (the order of the
+// tie-break).  Rebuilt and uploaded per call, like the path table.
+constexpr int kFindBlock = 256;          // pools per block of the per-pool launches (a segment starts a new block)
+constexpr int kFindLaneQueries = 64;     // queries one lane serves (one bit each of its reached mask); gridDim.y covers the rest
+struct FindSeg {
+    PathSeg s;
+    const PackedFeeTok* pk;      // two-coin kinds, UniV3: {i1 | i2 << 16, .}, or null (large-market mode)
+    const int2* Ai;              //   ... then the plain pairs
+    const int32_t* tok;          // ragged kinds: [n_coins][m]; null otherwise
+    int64_t first_tile;          // blocks of the segments before this one
+    int64_t first_pool;          // pools of the segments before this one
+    int64_t pad[3];
+};
+static_assert(sizeof(FindSeg) == 192, "the find table: a PathSeg and half a line");
+struct FindArgs {
+    int64_t count;               // queries of this chunk
+    int64_t stride;              // queries of the call: hop k of the chunk's query q at k*stride + q of the hop arrays below
+    int32_t max_hops;            // 1 .. CFMM_MAX_PATH_HOPS
+    int32_t nseg;                // records of `segs`
+    int32_t n_tokens;
+    int32_t layer;               // find_relax / find_claim / find_advance: 1 .. max_hops
+    int64_t tiles;               // blocks of kFindBlock pools that cover every segment's pools
+    int32_t group;               // find_relax with the LDS copy: queries per grid row (1 .. kFindLaneQueries), 0: no LDS copy
+    int32_t tiles_per_block;     //   ... and tiles one block folds into its copy before it touches global memory
+    const FindSeg* segs;         // [nseg] device
+    // all per-query arrays already point at the chunk's first query
+    const int32_t* token_in;     // [count] 0-based
+    const int32_t* token_out;
+    const double* amount_in;
+    unsigned long long* best;    // [max_hops + 1][count][n_tokens] the layers: a positive finite double's bits, 0 = unreached
+    unsigned long long* edge;    // [max_hops][count] the claimed hop that ENDS layer k + 1, packed; all ones: none
+    int32_t* h_star;             // [count] hops of the answer, 0: none
+    int32_t* target;             // [count] the token the walk back stands at
+    double* amount_out;          // [count]
+    int32_t* n_hops;
+    int32_t* status;             // CFMM_FOUND*
+    int32_t* hop_seg;            // [max_hops][stride], -1 in the unused slots
+    long long* hop_row;
+    int32_t* hop_coin_in;
+    int32_t* hop_coin_out;
+};
+// the LDS copy of find_relax: group x n_tokens words within this many bytes (four blocks of it fit a CU beside their registers)
+constexpr int kFindLdsBytes = 32768;
+inline int find_lds_group(int n_tokens) { const int g = kFindLdsBytes / 8 / (n_tokens < 1 ? 1 : n_tokens); return g > kFindLaneQueries ? kFindLaneQueries : g; }
+enum FindKernel { kFindInit, kFindRelax, kFindSelect, kFindClaim, kFindAdvance, kFindFinish };
+// e0, e1: both set = the launch is timed by the command processor
+hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

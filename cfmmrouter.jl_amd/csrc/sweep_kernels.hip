@@ -47,6 +47,7 @@
 //   swap_path_kernels.h  swap_path_kernel (cfmm_swap_path: quote_path_kernel's walk, then every hop's new state, all or nothing),
 //                        swap_path_out_kernel (cfmm_swap_path_out: quote_path_out_kernel's walk, then the same)
 //   swap_out_kernels.h   swap_out_kernel (cfmm_swap_out: quote_out_one's answer, then the pool's new state, with a status per swap)
+//   find_path_kernels.h  find_relax and the walk back (cfmm_find_path: the best walk between two tokens, a layer per launch, one lane per pool)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -65,6 +66,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
+#include "find_path_kernels.h"
 
 #include <hip/hip_ext.h>
 
@@ -416,6 +418,41 @@ hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t
         return hipErrorInvalidValue;
     void* args[] = {const_cast<SwapPathArgs*>(&a)};
     return launch_quote_grid(reinterpret_cast<const void*>(&swap_path_out_kernel<kQuoteBlock>), a.count, args, s, e0, e1);
+}
+
+// cfmm_find_path: the per-query kernels take launch_quote_grid's rule without the stride (one lane per query of the chunk);
+// the per-pool kernels one block per tile of the table and one grid row per kFindLaneQueries queries
+hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.count <= 0 || a.stride < a.count || a.nseg <= 0 || a.n_tokens <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS)
+        return hipErrorInvalidValue;
+    const int64_t qblocks = (a.count + kFindBlock - 1) / kFindBlock, qrows = (a.count + kFindLaneQueries - 1) / kFindLaneQueries;
+    const bool per_pool = which == kFindRelax || which == kFindClaim;
+    if (which != kFindInit && which != kFindSelect && which != kFindFinish && (a.layer < 1 || a.layer > a.max_hops)) return hipErrorInvalidValue;
+    if (per_pool && (a.tiles <= 0 || a.tiles > 0x7fffffffll || qrows > 65535)) return hipErrorInvalidValue;
+    if (qblocks > 0x7fffffffll) return hipErrorInvalidValue;
+    const bool lds = which == kFindRelax && a.group > 0;
+    if (lds && (a.group > kFindLaneQueries || a.group > find_lds_group(a.n_tokens) || a.tiles_per_block < 1)) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (which) {
+    case kFindInit: kernel = reinterpret_cast<const void*>(&find_init<kFindBlock>); break;
+    case kFindRelax: kernel = lds ? reinterpret_cast<const void*>(&find_relax<kFindBlock, true>) : reinterpret_cast<const void*>(&find_relax<kFindBlock, false>); break;
+    case kFindSelect: kernel = reinterpret_cast<const void*>(&find_select<kFindBlock>); break;
+    case kFindClaim: kernel = reinterpret_cast<const void*>(&find_claim<kFindBlock>); break;
+    case kFindAdvance: kernel = reinterpret_cast<const void*>(&find_advance<kFindBlock>); break;
+    case kFindFinish: kernel = reinterpret_cast<const void*>(&find_finish<kFindBlock>); break;
+    default: return hipErrorInvalidDeviceFunction;   // no such kernel
+    }
+    void* args[] = {const_cast<FindArgs*>(&a)};
+    dim3 grid = per_pool ? dim3((unsigned)a.tiles, (unsigned)qrows) : dim3((unsigned)qblocks);
+    size_t lds_bytes = 0;
+    if (lds) {
+        const int64_t rows = (a.count + a.group - 1) / a.group;
+        if (rows > 65535) return hipErrorInvalidValue;
+        grid = dim3((unsigned)((a.tiles + a.tiles_per_block - 1) / a.tiles_per_block), (unsigned)rows);
+        lds_bytes = (size_t)a.group * (size_t)a.n_tokens * sizeof(unsigned long long);
+    }
+    return launch_k(kernel, grid, dim3(kFindBlock), lds_bytes, s, e0, e1, args);
 }
 
 } // namespace cfmm

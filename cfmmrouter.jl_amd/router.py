@@ -842,6 +842,43 @@ def swap_path_out_(r: Router, pools, tokens, amount_out, max_in=None, hops=False
     return _swap_path(r, "swap_path_out", "max_in", pools, tokens, amount_out, max_in, hops, sync_host)
 
 
+def find_path(r: Router, token_in, token_out, amount_in, max_hops=3):
+    """The best swap path from `token_in[q]` to `token_out[q]` (token ids 1-based as in `Ai`) for `amount_in[q]`, of at most
+    `max_hops` (1 .. 8) pools, FOUND on the device among the pools as they stand there (cfmm_find_path) -- "I have 1000 of A and
+    want C: through which pools, and how much do I get?".  Scalars broadcast.
+
+    Returns (amount_out, pools, tokens, status): `pools[q]` / `tokens[q]` are in the form `quote_path` / `swap_path_` accept
+    (positions in `r.cfmms`; the token ids along the path, one more than the pools), empty where nothing was found.
+    The contract is the layered search: layer h holds per token the largest quote over every pool and ordered coin pair from
+    layer h-1, every hop quoted AGAINST THE POOL AS IT STANDS; the answer is the largest layer entry of token_out with the
+    fewest hops, ties broken towards the smallest (segment, row, coin_in, coin_out) -- `quote_path(r, pools, tokens, amount_in)`
+    answers `amount_out` bit for bit.  What is found is a walk: status[q] is FOUND, FOUND_NONE (token_out not reached within
+    max_hops, or amount 0: amount_out 0.0) or FOUND_REPEATS (the walk visits a pool twice; `quote_path` and `swap_path_` refuse
+    it as one path).  Host-evaluated plugin pools have no device state and are NOT searched.  Read-only, like `quote`."""
+    L = r._layout
+    try:
+        tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int64).reshape(-1), np.asarray(token_out, dtype=np.int64).reshape(-1),
+                                             np.asarray(amount_in, dtype=np.float64).reshape(-1))
+    except ValueError:
+        raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+    for name, t in (("token_in", tin), ("token_out", tout)):
+        bad = np.flatnonzero((t < 1) | (t > r.n_tokens))
+        if bad.size:
+            raise ArgumentError(f"query {int(bad[0])}: {name} {int(t[bad[0]])} out of range 1:{r.n_tokens}")
+    out, n_hops, seg, row, ci, co, status = _path_context(r).find_path(tin - 1, tout - 1, amt, max_hops)
+    batch_of = {s: b for b, s in L.seg_of.items()}
+    pools, tokens = [], []
+    for q in range(len(out)):
+        pl, tk = [], [int(tin[q])] if n_hops[q] else []
+        for k in range(int(n_hops[q])):
+            b = batch_of[int(seg[q, k])]
+            pl.append(int(L.place[int(L.offsets[b]) + int(row[q, k])]))
+            tk.append(int(L.batches[b].Ai[int(row[q, k]), int(co[q, k])]))
+        pools.append(pl)
+        tokens.append(tk)
+    return out, pools, tokens, status
+
+
 def _swap_path(r: Router, verb, limit_name, pools, tokens, amount, limit, hops, sync_host):
     n_hops, seg, row, ci, co, amt, touched = _path_hops(r, verb, pools, tokens, amount)
     if limit is not None:

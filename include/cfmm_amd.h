@@ -559,6 +559,54 @@ int cfmm_swap_path(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t
                    const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, const double* amount_in,
                    const double* min_amount_out, double* amount_out, double* hop_out, int32_t* status);
 
+/* The best swap path between two tokens, FOUND on the device: "I have amount_in of token_in and want token_out -- through
+ * which pools, and how much do I get?"  (The reference has no such function: route! with a Swap objective, src/objectives.jl:133-150,
+ * answers with the optimal SPLIT over the whole market as per-pool trades; this entry answers with ONE executable path, the
+ * thing cfmm_quote_path prices and cfmm_swap_path executes.)  Per query q: token_in[q], token_out[q] (0-based, < n_tokens),
+ * amount_in[q] finite and >= 0, and at most max_hops (1 .. CFMM_MAX_PATH_HOPS) hops.
+ * THE CONTRACT IS THE LAYERED SEARCH, on the market as it stands on the device:
+ *   best[0][token_in] = amount_in; everything else is unreached.
+ *   best[h][t], h = 1 .. max_hops: the maximum of quote(pool, ci -> co, best[h-1][tok(ci)]) over every pool of every segment
+ *   and every ordered pair of its coins (ci, co) with tok(co) == t whose source best[h-1][tok(ci)] is reached.  A quote that is
+ *   NaN, not finite or <= 0 enters nothing.
+ *   amount_out = the maximum over h >= 1 of best[h][token_out]; the path has the FEWEST hops h* that attain it bit for bit, and
+ *   is walked back from (h*, token_out): at each layer the hop is the SMALLEST (segment, row, coin_in, coin_out), in
+ *   lexicographic order, among the edges that attain best[h][t] bit for bit.
+ * So the answer is a pure function of the market and the query -- not of launch geometry, the order atomics arrive in or how
+ * queries are batched.  The quotes are cfmm_quote's own, and EVERY HOP IS QUOTED AGAINST THE POOL AS IT STANDS, cfmm_quote_path's
+ * rule: cfmm_quote_path on the returned arrays answers amount_out bit for bit, and every intermediate amount with it.
+ * What is found is a WALK, not a simple path: it may pass a token twice and may visit a pool twice (quoted twice from the same
+ * reserves); a search constrained to simple paths is not offered.  Where every pool's quote is non-decreasing in its input --
+ * it is mathematically; rounding can break it by ulps -- the layered maximum is the maximum over all walks of at most
+ * max_hops hops; the contract is the layered one, not "the global maximum".  token_in == token_out is allowed: the best
+ * cycle through that token.
+ *   amount_out, n_hops, status   [count]
+ *   hop_seg, hop_row, hop_coin_in, hop_coin_out   [max_hops][count], hop-major: exactly what cfmm_quote_path and cfmm_swap_path
+ *                 take (with n_hops and max_hops); -1 in the slots at k >= n_hops[q]
+ *   status[q]:
+ *     CFMM_FOUND          a walk was found; every pool on it is visited once
+ *     CFMM_FOUND_NONE     token_out is not reached within max_hops, or amount_in is 0: amount_out 0.0, n_hops 0, hop slots -1
+ *     CFMM_FOUND_REPEATS  a walk was found and its amounts are cfmm_quote_path's, but it visits some pool more than once:
+ *                         cfmm_swap_path would refuse it as one path
+ * Everything is checked before anything is enqueued: count >= 0, max_hops, no null array, every token in 0 .. n_tokens-1, every
+ * amount finite and >= 0.  A failure is CFMM_ERR_INVALID_ARG, names the query ("cfmm_find_path: query 12: ...") and leaves the
+ * outputs untouched.  Read-only exactly as cfmm_quote: no state moves, no earlier trades or outputs are invalidated.
+ * Synchronous on the context's stream; count == 0 is a no-op; a context without pools answers CFMM_FOUND_NONE everywhere;
+ * large-market mode needs nothing special.  A MULTI-DEVICE CONTEXT answers CFMM_ERR_UNSUPPORTED.  One launch per layer with one
+ * lane per pool, then one sparse launch per layer walking back; the scratch, (max_hops + 1) x queries x n_tokens x 8 bytes, is
+ * kept by the context and bounded by 256 MiB: a larger call is processed in chunks of queries, with the same results.
+ * Read-only options under "time_kernels": "find_relax_ns" and "find_walk_ns", the sums of the latest call's layer launches
+ * and walk-back launches ("find_relax_ns_<h>", "find_claim_ns_<h>", "find_advance_ns_<h>", h = 1 .. 8: the same layer by
+ * layer); "find_launches", all kernel launches of the latest call.  Option "find_lds" (default 1): the layer launches fold
+ * their candidates through a per-block LDS copy of the layer rows where n_tokens lets one fit; 0 sends every candidate to
+ * global memory -- the same bits, a measurement switch. */
+#define CFMM_FOUND 0
+#define CFMM_FOUND_NONE 1
+#define CFMM_FOUND_REPEATS 2
+int cfmm_find_path(cfmm_ctx* ctx, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+                   const double* amount_in, double* amount_out, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
+                   int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status);
+
 /* netflows!(psi, r) -- src/router.jl:111-119, for the most recent sweep. */
 int cfmm_netflows(cfmm_ctx* ctx, double* psi);
 /* the `acc` of fn (src/router.jl:79-83) for the most recent sweep. */

@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, swap_out!, swap_paths_out!, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, swap_out!, swap_paths_out!, find_paths, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -692,6 +692,48 @@ function swap_paths!(r::AMDRouter, pools::AbstractVector, tokens::AbstractVector
     return hops ? (out, status, hv) : (out, status)
 end
 
+
+# find_paths(r, token_in, token_out, amount_in; max_hops=3) -- the Python host's router-level `find_path` (cfmm_find_path): the
+# best swap path of at most max_hops (1 .. 8) pools from token_in[q] to token_out[q] (token ids as in Ai) for amount_in[q],
+# FOUND on the device among the pools as they stand there.  Returns (amount_out, pools, tokens, status): pools[q] / tokens[q]
+# in the form quote_paths / swap_paths! take (positions in r.cfmms; the tokens along the path, one more than the pools), empty
+# where nothing was found.  The contract is the layered search: layer h holds per token the largest quote over every pool and
+# ordered coin pair from layer h-1, every hop quoted against the pool as it stands; the answer is the largest layer entry of
+# token_out with the fewest hops, ties to the smallest (segment, row, coin_in, coin_out) -- quote_paths on the result answers
+# amount_out bit for bit.  What is found is a walk: status[q] is 0 (found), 1 (token_out not reached within max_hops, or
+# amount 0: amount_out 0.0) or 2 (found, but the walk visits a pool twice: quote_paths and swap_paths! refuse it as one
+# path).  Host-evaluated pools have no device state and are not searched.  Read-only.
+const FOUND, FOUND_NONE, FOUND_REPEATS = Int32(0), Int32(1), Int32(2)   # CFMM_FOUND*
+function find_paths(r::AMDRouter, token_in::AbstractVector{<:Integer}, token_out::AbstractVector{<:Integer},
+                    amount_in::AbstractVector{<:Real}; max_hops::Integer=3)
+    n = length(token_in)
+    (length(token_out) == n && length(amount_in) == n) || throw(ArgumentError("token_in, token_out and amount_in must have one entry per query"))
+    nt = length(r.v)
+    for q in 1:n
+        1 <= token_in[q] <= nt || throw(ArgumentError("query $q: token_in $(token_in[q]) out of range 1:$nt"))
+        1 <= token_out[q] <= nt || throw(ArgumentError("query $q: token_out $(token_out[q]) out of range 1:$nt"))
+    end
+    1 <= max_hops <= MAX_PATH_HOPS || throw(ArgumentError("max_hops must be 1 to $MAX_PATH_HOPS"))
+    H = Int(max_hops)
+    tin = Int32[token_in[q] - 1 for q in 1:n]; tout = Int32[token_out[q] - 1 for q in 1:n]       # 0-based for the library
+    amt = Float64[amount_in[q] for q in 1:n]
+    out = Vector{Float64}(undef, n)
+    n_hops = Vector{Int32}(undef, n); status = Vector{Int32}(undef, n)
+    seg = fill(Int32(-1), n, H); ci = fill(Int32(-1), n, H); co = fill(Int32(-1), n, H)          # column-major [count, max_hops] IS the
+    row = fill(Int64(-1), n, H)                                                                  # library's hop-major layout
+    n == 0 && return out, Vector{Int}[], Vector{Int}[], status
+    GC.@preserve tin tout amt out n_hops seg row ci co status check(r.ctx,
+        ccall((:cfmm_find_path, LIB), Cint,
+              (Ptr{Cvoid}, Int64, Int32, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int64}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+              r.ctx, n, H, tin, tout, amt, out, n_hops, seg, row, ci, co, status))
+    pool_at = Dict{Tuple{Int32,Int64},Int}(sr => i for (i, sr) in segment_rows(r))
+    pools = Vector{Vector{Int}}(undef, n); tokens = Vector{Vector{Int}}(undef, n)
+    for q in 1:n
+        pools[q] = Int[pool_at[(seg[q, k], row[q, k])] for k in 1:n_hops[q]]
+        tokens[q] = n_hops[q] == 0 ? Int[] : vcat(Int(token_in[q]), Int[r.cfmms[pools[q][k]].Ai[co[q, k] + 1] for k in 1:n_hops[q]])
+    end
+    return out, pools, tokens, status
+end
 
 include("swap_paths_out.jl")   # swap_paths_out! (cfmm_swap_path_out, declared in include/cfmm_amd_path_out.h)
 

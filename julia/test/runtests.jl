@@ -282,4 +282,22 @@ end
     @test all(back .< a)
     @test_throws ArgumentError quote_paths(r, [[1, 1]], [[pools[1].Ai[1], pools[1].Ai[2], pools[1].Ai[1]]], [1.0])
 end
+
+@testset "find_paths: the best path between two tokens, found on the device, then quoted and executed" begin
+    pools = random_product_market(50, 8; seed=11, fee=0.997)
+    r = AMDRouter(LinearNonnegative(rand(8)), pools, 8)
+    tin = [1 + q % 8 for q in 0:15]; tout = [1 + (q + 3) % 8 for q in 0:15]
+    a = fill(0.01 * pools[1].R[1], 16)
+    out, paths, toks, status = find_paths(r, tin, tout, a; max_hops=3)
+    found = findall(==(0), status)
+    @test !isempty(found)
+    @test all(toks[q][1] == tin[q] && toks[q][end] == tout[q] && length(toks[q]) == length(paths[q]) + 1 for q in found)
+    @test quote_paths(r, paths[found], toks[found], a[found]) == out[found]      # the bits of quoting the found path
+    q = found[1]
+    got, st = swap_paths!(r, [paths[q]], [toks[q]], [a[q]]; min_out=[out[q]])
+    @test st == [0] && got[1] == out[q]
+    @test find_paths(r, [tin[q]], [tout[q]], [a[q]]; max_hops=3)[1][1] < out[q]   # the same query afterwards: a worse price
+    @test find_paths(r, [1], [2], [0.0])[4] == [1]                                # nothing to carry: not found
+    @test_throws ArgumentError find_paths(r, [9], [1], [1.0])
+end
 end
