@@ -276,7 +276,7 @@ static int64_t* option_slot(cfmm_ctx* c, const char* key)
         {"cost_geomean", &c->geo.cost_geomean}, {"cost_univ3", &c->geo.cost_univ3}, {"host_flag", &c->opt_host_flag},
         {"stop_in_noise", &c->opt_stop_in_noise}, {"multi_threads", &c->opt_multi_threads},
         {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->geo.direct_small}, {"stream_stores", &c->opt_stream_stores},
-        {"find_lds", &c->opt_find_lds},
+        {"find_lds", &c->opt_find_lds}, {"lean_kernels", &c->opt_lean_kernels},
 #ifdef CFMM_TEST_HOOKS
         {"debug_stall_ms", &c->opt_debug_stall_ms},
 #endif
@@ -322,6 +322,11 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (key && !std::strcmp(key, "pool_update_regrows")) {   // read-only: compactions + regrows of UniV3 tick arrays (cfmm_pools_set_prices)
         *value = c->pool_update_regrows;
         for (const cfmm_ctx* child : c->shards) *value += child->pool_update_regrows;
+        return CFMM_OK;
+    }
+    if (key && !std::strcmp(key, "lean_launches")) {   // read-only: sweep launches that took a lean kernel (sweep_core.h sweep_body<..., LEAN>)
+        *value = c->lean_launches;
+        for (const cfmm_ctx* child : c->shards) *value += child->lean_launches;
         return CFMM_OK;
     }
     if (key && !std::strcmp(key, "compact_walks_ns")) {   // read-only: the span of the latest compact_walks launch timed under "time_kernels"

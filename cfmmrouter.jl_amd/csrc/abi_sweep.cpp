@@ -315,7 +315,11 @@ int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
                              : sweep_lds_bytes(c->n_pad, d.copies, g.block, d.need_logv, d.gtab_n, d.v_shift == 4 ? 1 : 0);
     hipEvent_t ea = nullptr, eb = nullptr;
     if (ev.timed) c->timer.take_events(ea, eb);   // start/stop written by the command processor around this launch (hipExtLaunchKernel)
-    const LaunchCfg cfg{g.block, g.grid, lds, arith_of(c, ev, g, d), ea, eb};
+    const int arith = arith_of(c, ev, g, d);
+    int kinds[kMaxMulti] = {0};
+    for (int k = 0; k < d.nseg; ++k) kinds[k] = c->segs[(size_t)g.first + k].kind;
+    const bool lean = c->opt_lean_kernels != 0 && lean_launch(d, g, kinds, arith);
+    const LaunchCfg cfg{g.block, g.grid, lds, arith, lean, ea, eb};
     const Segment& s0 = c->segs[(size_t)g.first];
     hipError_t e;
     if (g.multi) {
@@ -330,6 +334,7 @@ int launch_group(cfmm_ctx* c, const Eval& ev, const Group& g, size_t gi)
     }
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "sweep launch failed: %s", hipGetErrorString(e));
     if (ea && eb) c->timer.pending.push_back({ea, eb, 0});
+    if (lean) ++c->lean_launches;
     return CFMM_OK;
 }
 

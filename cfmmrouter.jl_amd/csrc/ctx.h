@@ -430,6 +430,9 @@ struct cfmm_ctx {
                                    //    first, where n_tokens lets one fit (find_path_kernels.h find_relax<., true>); 0: every candidate
                                    //    goes to global memory (the A/B of scripts/find_path_times.py; the same bits either way)
     int64_t opt_univ3_heads = 1;   // 1: multi-tick UniV3 walks decide their first four list ticks from the per-pool float threshold heads
+    int64_t opt_lean_kernels = 1;  // 1: a launch in the default configuration takes the lean form of its kernel (launch_plan.h lean_launch:
+                                   //    the same bits with fewer instructions per tile); 0: always the general kernels (A/B, tests)
+    int64_t lean_launches = 0;     // read-only option "lean_launches": sweep launches of this context that took a lean kernel
     int64_t opt_dev_prices_in_window = 0; // 1 = the CALLER vouches that the prices of device-pointer sweeps lie in [2^-kFastExp, 2^kFastExp]
                                      //    (what the host checks itself for host-pointer calls): cfmm_sweep_dev launches the fast kernels
                                      //    instead of the ones that carry both arithmetics; every block still checks what it stages and

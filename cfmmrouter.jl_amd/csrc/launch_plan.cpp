@@ -243,6 +243,31 @@ std::vector<unsigned char> build_sweep_desc(const std::vector<Group>& groups, co
     return bytes;
 }
 
+bool lean_launch(const SweepDesc& d, const Group& g, const int* kinds, int arith)
+{
+    if (arith != 1 && arith != 2) return false;                  // (LaunchCfg::arith: fast, auto)
+    if (d.nseg < 1 || d.nseg != g.nseg) return false;            // (0: an N-coin launch, which takes no descriptor)
+    if (d.compact != 1 || d.nt_stores != 0 || d.v_shift != 4 || d.direct != 0 || d.copies != g.block / 64) return false;
+    if (g.block != (g.multi ? kMidBlock : kBigBlock)) return false;
+    for (int k = 0; k < d.nseg; ++k) {
+        const SegRec& s = d.seg[k];
+        if (s.m > kLeanMaxPools) return false;
+        switch (kinds[k]) {
+        case CFMM_KIND_PRODUCT:
+            if (s.pools.p.gbase < 0) return false;
+            break;
+        case CFMM_KIND_GEOMEAN:
+            if (s.pools.g.gbase < 0 || s.pools.g.reference_order != 0 || d.need_logv != 1) return false;
+            break;
+        case CFMM_KIND_UNIV3:
+            if (s.pools.u.gbase < 0 || (!g.multi && !s.pools.u.head)) return false;
+            break;
+        default: return false;                                   // Solidly and the N-coin kinds
+        }
+    }
+    return true;
+}
+
 bool stage_pairs(int n_tokens, int block)
 {
     return !global_bins(n_tokens) && sweep_lds_bytes(n_pad_of(n_tokens), 1, block, 1, kMaxFeeTable, 1) <= 160 * 1024;

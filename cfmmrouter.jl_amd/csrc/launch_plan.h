@@ -86,6 +86,17 @@ std::vector<unsigned char> build_sweep_desc(const std::vector<Group>& groups, co
                                             const std::vector<int>& seg_kinds, std::vector<size_t>& offsets);
 BlockRec plan_block_rec(const Group& g, int b, const SweepDesc& head, const int* kinds);
 
+// Does a launch take the LEAN form of its kernel (sweep_core.h sweep_body<..., LEAN>)?  Pure: the head of the launch's
+// descriptor with its segments filled in, the group, the segments' kinds and the arithmetic the launch runs on (LaunchCfg::arith).
+// Lean iff the launch is what every default launch is -- compact trade records, write-through trade stores, prices staged as
+// pairs (which excludes large-market mode), one bin copy per wavefront, not direct, the log-price row there when a segment reads
+// it -- and every segment has its fees in the launch's table (gbase >= 0), at most kLeanMaxPools pools (32-bit byte offsets
+// into every pool stream) and a kind with a lean kernel at this block size: a fused launch of 512-thread blocks, or
+// ProductTwoCoin, log-space GeometricMean or UniV3 with threshold heads alone at 1024; on the fast or the auto arithmetic.
+// True means the kernel table HAS the kernel.
+constexpr int64_t kLeanMaxPools = (int64_t)1 << 26;   // x 32 bytes per pool (UniV3's threshold heads) = 2 GiB
+bool lean_launch(const SweepDesc& head, const Group& g, const int* kinds, int arith);
+
 // Prices are staged in LDS as {v, rcp_refined(v)} pairs unless the market is too wide for them (sweep.h SweepArgs::v_shift)
 bool stage_pairs(int n_tokens, int block);
 // private bin copies per block (SweepArgs::copies)

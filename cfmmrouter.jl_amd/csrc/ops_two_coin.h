@@ -5,6 +5,8 @@
 
 #include "fast_arith.h"
 
+#include <type_traits>
+
 namespace cfmm {
 
 struct Trade {
@@ -32,6 +34,30 @@ __device__ __forceinline__ void expand_dir(int dir, double d, double l, Trade& t
     t.l2 = dir == kDir1 ? l : 0.0;
 }
 
+// Element i of a pool stream.  LEAN (the lean kernels, sweep_core.h; i is then 32 bits wide and the host has checked that
+// every stream of the launch is shorter than 2 GiB): the stream's base -- a launch constant, in SGPRs -- plus a 32-bit
+// per-lane BYTE offset, the `global_load v, v_off, s[base]` form: the index of the next tile is one 32-bit add and one
+// shift per record width instead of a 64-bit vector add per stream.
+// The record is loaded as ONE register value of its width (8 or 16 bytes) and copied into T from there: copied as a struct
+// from the computed address, the compiler turned the tile loop's `cur = nxt` into a choice between two ADDRESSES and loaded
+// the record's fields where they are used -- in the next tile, behind its solve, with the first tile parked in scratch.
+typedef unsigned int stream_u2 __attribute__((ext_vector_type(2), may_alias));
+typedef unsigned int stream_u4 __attribute__((ext_vector_type(4), may_alias));
+template <bool LEAN, class T, class I>
+__device__ __forceinline__ T stream_at(const T* base, I i)
+{
+    if constexpr (LEAN) {
+        static_assert(sizeof(T) == 8 || sizeof(T) == 16, "pool streams are 8- or 16-byte records");
+        using Bits = typename std::conditional<sizeof(T) == 8, stream_u2, stream_u4>::type;
+        const Bits bits = *reinterpret_cast<const Bits*>(reinterpret_cast<const char*>(base) + (size_t)((uint32_t)i * (uint32_t)sizeof(T)));
+        T out;
+        __builtin_memcpy(&out, &bits, sizeof(T));
+        return out;
+    } else {
+        return base[i];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // The packed {tokens, fee index} record (sweep.h PackedFeeTok) of ProductTwoCoin, GeometricMeanTwoCoin and UniV3 segments
 // ---------------------------------------------------------------------------------------------
@@ -45,19 +71,21 @@ __device__ __forceinline__ void expand_dir(int dir, double d, double l, Trade& t
 // plus the fee itself (*fee: the pool's entry of the gamma array) when the launch has no fee table (gbase < 0: too many
 // fee tiers); with a table the fee is 0.0 until resolve_packed() reads it.  Two calls, so that a family can keep the
 // order in which it issues its loads (UniV3 requests its price between the two: any other order changes its schedule).
-__device__ __forceinline__ int2 load_packed(const PackedFeeTok* pk, int64_t i)
+template <bool LEAN = false, class I>
+__device__ __forceinline__ int2 load_packed(const PackedFeeTok* pk, I i)
 {
-    const PackedFeeTok k = pk[i];
+    const PackedFeeTok k = stream_at<LEAN>(pk, i);
     return make_int2((int)k.tok, (int)k.gidx);
 }
 __device__ __forceinline__ double load_packed_fee(int gbase, const double* fee) { return gbase < 0 ? *fee : 0.0; }
 // after stage_prices(): take the packed record apart; the fee from the LDS table {γ, rcp_refined(γ)}, or -- no table --
 // its reciprocal refined here (FAST only)
-template <bool FAST>
+// LEAN: the launch has a fee table (launch_plan.h lean_launch), so there is nothing to decide
+template <bool FAST, bool LEAN = false>
 __device__ __forceinline__ void resolve_packed(int gbase, const double2* gtab_lds, int2& ai, double& g, double& yg)
 {
     const unsigned tok = (unsigned)ai.x;
-    if (gbase >= 0) {
+    if (LEAN || gbase >= 0) {
         const double2 gy = gtab_lds[gbase + ai.y];
         g = gy.x;
         yg = pinned(gy.y);
@@ -81,25 +109,25 @@ struct ProductOps {
     };
     ProductPools p;
     // GBINS (n_tokens > 8192): the plain gamma / Ai arrays; otherwise the packed record (load_packed)
-    template <bool GBINS>
-    __device__ __forceinline__ Raw load(int64_t i) const
+    template <bool GBINS, bool LEAN = false, class I>
+    __device__ __forceinline__ Raw load(I i) const
     {
         Raw r;
-        r.R = p.R[i];
+        r.R = stream_at<LEAN>(p.R, i);
         r.yg = 0.0;
         if constexpr (GBINS) {
             r.g = p.gamma[i];
             r.ai = p.Ai[i];
         } else {
-            r.ai = load_packed(p.pk, i);
-            r.g = load_packed_fee(p.gbase, p.gamma + i);
+            r.ai = load_packed<LEAN>(p.pk, i);
+            r.g = LEAN ? 0.0 : load_packed_fee(p.gbase, p.gamma + i);
         }
         return r;
     }
-    template <bool GBINS, bool FAST>
+    template <bool GBINS, bool FAST, bool LEAN = false>
     __device__ __forceinline__ void resolve(Raw& r, const double2* gtab_lds) const
     {
-        if constexpr (!GBINS) resolve_packed<FAST>(p.gbase, gtab_lds, r.ai, r.g, r.yg);
+        if constexpr (!GBINS) resolve_packed<FAST, LEAN>(p.gbase, gtab_lds, r.ai, r.g, r.yg);
     }
     __device__ __forceinline__ int2 tokens(const Raw& r) const { return r.ai; }
     // All four closed forms exactly as written in the reference (:134-138).
@@ -181,9 +209,9 @@ struct GeoMeanOps {
         double yg;    // unused (interface of process_pool)
     };
     GeoMeanPools p;
-    template <bool GBINS>
-    __device__ __forceinline__ Raw load(int64_t i) const { return Raw{p.R[i], p.w[i], p.gamma[i], p.Ai[i], 0.0}; }
-    template <bool GBINS, bool FAST>
+    template <bool GBINS, bool LEAN = false, class I>
+    __device__ __forceinline__ Raw load(I i) const { return Raw{p.R[i], p.w[i], p.gamma[i], p.Ai[i], 0.0}; }
+    template <bool GBINS, bool FAST, bool LEAN = false>
     __device__ __forceinline__ void resolve(Raw&, const double2*) const {}
     __device__ __forceinline__ int2 tokens(const Raw& r) const { return r.ai; }
     // Same idea as ProductOps::solve: Δ₁,Λ₂ > 0 ⇔ γ·m₁₂·η·R₂ > R₁ and Δ₂,Λ₁ > 0 ⇔ γ·m₂₁·R₁/η > R₂
@@ -249,27 +277,27 @@ struct GeoMeanLogOps {
         double yg;
     };
     GeoMeanPools p;
-    template <bool GBINS>
-    __device__ __forceinline__ Raw load(int64_t i) const
+    template <bool GBINS, bool LEAN = false, class I>
+    __device__ __forceinline__ Raw load(I i) const
     {
         Raw r;
-        r.R = p.R[i];
-        r.Q = p.Q[i];
-        r.eta = p.eta[i];
+        r.R = stream_at<LEAN>(p.R, i);
+        r.Q = stream_at<LEAN>(p.Q, i);
+        r.eta = stream_at<LEAN>(p.eta, i);
         r.yg = 0.0;
         if constexpr (GBINS) {
             r.g = p.gamma[i];
             r.ai = p.Ai[i];
         } else {
-            r.ai = load_packed(p.pk, i);
-            r.g = load_packed_fee(p.gbase, p.gamma + i);
+            r.ai = load_packed<LEAN>(p.pk, i);
+            r.g = LEAN ? 0.0 : load_packed_fee(p.gbase, p.gamma + i);
         }
         return r;
     }
-    template <bool GBINS, bool FAST>
+    template <bool GBINS, bool FAST, bool LEAN = false>
     __device__ __forceinline__ void resolve(Raw& r, const double2* gtab_lds) const
     {
-        if constexpr (!GBINS) resolve_packed<FAST>(p.gbase, gtab_lds, r.ai, r.g, r.yg);
+        if constexpr (!GBINS) resolve_packed<FAST, LEAN>(p.gbase, gtab_lds, r.ai, r.g, r.yg);
     }
     __device__ __forceinline__ int2 tokens(const Raw& r) const { return r.ai; }
     // one direction of the log-space forms: {d, l} for direction 1 (dir1) or 2

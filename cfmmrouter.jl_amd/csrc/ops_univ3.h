@@ -38,19 +38,19 @@ struct UniV3OpsT {
         double yg;
     };
     UniV3Pools p;
-    template <bool GBINS>
-    __device__ __forceinline__ Raw load(int64_t i) const
+    template <bool GBINS, bool LEAN = false, class I>
+    __device__ __forceinline__ Raw load(I i) const
     {
         Raw r;
-        r.ca = p.cur_a[i];
-        r.cb = p.cur_b[i];
-        r.cc = p.cur_c[i];
-        r.walk = p.has_walk ? p.walk[i] : make_int4(0, 0, 0, 0);
+        r.ca = stream_at<LEAN>(p.cur_a, i);
+        r.cb = stream_at<LEAN>(p.cur_b, i);
+        r.cc = stream_at<LEAN>(p.cur_c, i);
+        r.walk = p.has_walk ? stream_at<LEAN>(p.walk, i) : make_int4(0, 0, 0, 0);
         r.hu = r.hd = make_uint4(0u, 0u, 0u, 0u);
         if constexpr (HEADS) {
             if (p.head) {                                 // (kernel argument: uniform) 32 contiguous bytes per lane
-                r.hu = p.head[2 * i];
-                r.hd = p.head[2 * i + 1];
+                r.hu = stream_at<LEAN>(p.head, 2 * i);
+                r.hd = stream_at<LEAN>(p.head, 2 * i + 1);
             }
         }
         r.i = i;
@@ -59,15 +59,15 @@ struct UniV3OpsT {
             r.pg = p.pg[i];
             r.ai = p.Ai[i];
         } else {   // packed record: price alone + {tokens, fee-table index} (+ the fee itself without a table)
-            r.ai = load_packed(p.pk, i);
-            r.pg = make_double2(p.cp[i], load_packed_fee(p.gbase, &p.pg[i].y));
+            r.ai = load_packed<LEAN>(p.pk, i);
+            r.pg = make_double2(stream_at<LEAN>(p.cp, i), LEAN ? 0.0 : load_packed_fee(p.gbase, &p.pg[i].y));
         }
         return r;
     }
-    template <bool GBINS, bool FAST>
+    template <bool GBINS, bool FAST, bool LEAN = false>
     __device__ __forceinline__ void resolve(Raw& r, const double2* gtab_lds) const
     {
-        if constexpr (!GBINS) resolve_packed<FAST>(p.gbase, gtab_lds, r.ai, r.pg.y, r.yg);
+        if constexpr (!GBINS) resolve_packed<FAST, LEAN>(p.gbase, gtab_lds, r.ai, r.pg.y, r.yg);
     }
     __device__ __forceinline__ int2 tokens(const Raw& r) const { return r.ai; }
 

@@ -260,6 +260,8 @@ struct LaunchCfg {
                                  // 1 = fast (every pool constant of the launch and -- the host KNOWS -- every price inside the
                                  // kFastExp window), 2 = auto (pool constants inside the window, prices unknown to the host:
                                  // device-pointer sweeps; every block picks the loop from the prices it stages)
+    bool lean = false;           // the lean form of the kernel (launch_plan.h lean_launch said so); a family, block or arithmetic
+                                 // without one: hipErrorInvalidDeviceFunction, like every other missing kernel
     hipEvent_t ev_start = nullptr; // both set: the launch is timed by the command processor
     hipEvent_t ev_stop = nullptr;  // (hipExtLaunchKernel), i.e. the kernel's own execution span
 };

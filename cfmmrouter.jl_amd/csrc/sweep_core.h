@@ -6,6 +6,8 @@
 #include "ops_two_coin.h"
 #include "ops_univ3.h"
 
+#include <type_traits>
+
 namespace cfmm {
 
 // ---------------------------------------------------------------------------------------------
@@ -29,6 +31,16 @@ __device__ __forceinline__ void store_pair(double2* dst, double x, double y, int
     d2v val = {x, y};
     if (nt) asm volatile("global_store_dwordx4 %0, %1, off nt\n\ts_nop 1" : : "v"(dst), "v"(val) : "memory");
     else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(dst), "v"(val) : "memory");
+}
+// The lean kernels' form of the same write-through store: record i of the segment's trade rows as the rows' base (a launch
+// constant, in SGPRs) plus a 32-bit per-lane byte offset -- the offset the lane's reserve load already uses, so a tile's
+// store costs no address arithmetic.  The leading s_nop: the compiler may have parked the base in a VGPR lane, and a VMEM
+// instruction must not read an SGPR in the 5 wait states after a v_readlane wrote it (it pads its own instructions, not
+// the inside of an asm statement).
+__device__ __forceinline__ void store_pair_at(double2* base, uint32_t i, double x, double y)
+{
+    d2v val = {x, y};
+    asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" : : "v"(i * 16u), "v"(val), "s"(base) : "memory");
 }
 
 // Partial rows are written through as well: no dirty line is left for the end-of-kernel release in front of the fold
@@ -186,12 +198,19 @@ __device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& 
 }
 
 // One pool: prices from LDS, closed form, trade record, dual scalar, netflow bins.
-template <class Ops, bool MAT, bool GBINS, bool FAST>
+// LEAN (sweep_body): a.compact, a.nt_stores, a.v_shift, a.need_logv and a.copies are compile-time constants here, the fee
+// comes from the LDS table and the trade record leaves through store_pair_at; the code is this one.
+template <class Ops, bool MAT, bool GBINS, bool FAST, bool LEAN, class Idx>
 __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a, const SweepLds& L,
-                                             const typename Ops::Raw& raw_in, int64_t i, double& acc)
+                                             const typename Ops::Raw& raw_in, Idx i, double& acc)
 {
+    // a compact trade record {x, y} of pool i
+    const auto put_record = [&](double x, double y) {
+        if constexpr (LEAN) store_pair_at(a.Delta, i, x, y);
+        else store_pair(a.Delta + i, x, y, a.nt_stores);
+    };
     typename Ops::Raw raw = raw_in;
-    ops.template resolve<GBINS, FAST>(raw, L.gtab);   // packed records: {tokens, fee-table index} -> tokens, fee
+    ops.template resolve<GBINS, FAST, LEAN>(raw, L.gtab);   // packed records: {tokens, fee-table index} -> tokens, fee
     const int2 tok = ops.tokens(raw);
     Px px;                                            // v[r.cfmms[i].Ai]
     px.yg = raw.yg;
@@ -230,7 +249,7 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
         const bool d1 = dir == kDir1;
         if (MAT) {
             if (a.compact) {
-                store_pair(a.Delta + i, d1 ? d : -d, l, a.nt_stores);   // {+Δ₁, Λ₂} or {−Δ₂, Λ₁}: the sign bit carries the direction
+                put_record(d1 ? d : -d, l);   // {+Δ₁, Λ₂} or {−Δ₂, Λ₁}: the sign bit carries the direction
             } else {
                 store_pair(a.Delta + i, d1 ? d : 0.0, d1 ? 0.0 : d, a.nt_stores);
                 store_pair(a.Lambda + i, d1 ? 0.0 : l, d1 ? l : 0.0, a.nt_stores);
@@ -249,7 +268,7 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
     if (dir == kDirNone) {
         if (MAT) {
             if (a.compact) {
-                store_pair(a.Delta + i, 0.0, 0.0, a.nt_stores);
+                put_record(0.0, 0.0);
             } else {
                 store_pair(a.Delta + i, 0.0, 0.0, a.nt_stores);
                 store_pair(a.Lambda + i, 0.0, 0.0, a.nt_stores);
@@ -282,7 +301,7 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
                     rb = -1.0;
                 }
             }
-            store_pair(a.Delta + i, ra, rb, a.nt_stores);
+            put_record(ra, rb);
         } else {
             store_pair(a.Delta + i, t.d1, t.d2, a.nt_stores);
             store_pair(a.Lambda + i, t.l1, t.l2, a.nt_stores);
@@ -311,9 +330,9 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
 // Requesting tile k+1 before tile k is solved (Ops::kPrefetch, single-family launches): +-0.1 us cache-warm, -4..-6 %
 // HBM-resident on the two-coin families at +6..8 VGPRs (round 3 measured the same and dropped it for the registers; since round 4's per-kernel
 // arithmetic they are free: profiles/r04_ab_prefetch_stores.txt); +4 % on the multi-tick UniV3 walk, which keeps the plain loop.
-template <class Ops, bool MAT, int BLOCK, bool GBINS, bool FAST, bool PREFETCH>
+template <class Ops, bool MAT, int BLOCK, bool GBINS, bool FAST, bool PREFETCH, bool LEAN, class Idx>
 __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, const SweepLds& L, typename Ops::Raw cur,
-                                          int64_t i, int64_t step, int64_t left, double& acc)
+                                          Idx i, Idx step, Idx left, double& acc)
 {
     if constexpr (PREFETCH) {
         // tile k+1's pool state is requested before tile k is solved: two tiles' loads in flight per lane
@@ -321,8 +340,8 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
         while (ok) {
             const bool more = left > 1;
             typename Ops::Raw nxt = cur;
-            if (more) nxt = ops.template load<GBINS>(i + step);
-            process_pool<Ops, MAT, GBINS, FAST>(ops, a, L, cur, i, acc);
+            if (more) nxt = ops.template load<GBINS, LEAN>((Idx)(i + step));
+            process_pool<Ops, MAT, GBINS, FAST, LEAN>(ops, a, L, cur, i, acc);
             i += step;
             --left;
             ok = more;
@@ -331,10 +350,10 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
     } else {
         bool ok = left > 0;
         while (ok) {
-            process_pool<Ops, MAT, GBINS, FAST>(ops, a, L, cur, i, acc);
+            process_pool<Ops, MAT, GBINS, FAST, LEAN>(ops, a, L, cur, i, acc);
             i += step;
             ok = --left > 0;
-            if (ok) cur = ops.template load<GBINS>(i);
+            if (ok) cur = ops.template load<GBINS, LEAN>(i);
         }
     }
 }
@@ -356,9 +375,9 @@ __device__ __forceinline__ void tile_loop(const Ops& ops, const SweepArgs& a, co
 //               (ADVICE r4, medium).  Costs the registers of rounds 1-3 again, which the default geometry (4 wavefronts per
 //               SIMD) never needed.
 constexpr int kArithFull = 0, kArithFast = 1, kArithAuto = 2;
-template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI, bool LEAN, class Idx>
 __device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a, const SweepLds& L, const typename Ops::Raw& cur,
-                                              int64_t i, int64_t step, int64_t left, bool& poison, bool& live, const PricePre& pre)
+                                              Idx i, Idx step, Idx left, bool& poison, bool& live, const PricePre& pre)
 {
     static_assert(!(GBINS && FASTK != kArithFull), "large-market mode runs on the compiler's sequences");
     double acc = 0.0;
@@ -375,10 +394,10 @@ __device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a
     // fused multi-family launch keeps the plain loop (same-box A/B on config3: -2 % HBM-resident but +1.5 % on the warm step)
     constexpr bool kPre = Ops::kPrefetch && !MULTI;
     if constexpr (FASTK == kArithAuto) {
-        if (staged & kStageFast) tile_loop<Ops, MAT, BLOCK, GBINS, true, kPre>(ops, a, L, cur, i, step, left, acc);
-        else tile_loop<Ops, MAT, BLOCK, GBINS, false, kPre>(ops, a, L, cur, i, step, left, acc);
+        if (staged & kStageFast) tile_loop<Ops, MAT, BLOCK, GBINS, true, kPre, LEAN>(ops, a, L, cur, i, step, left, acc);
+        else tile_loop<Ops, MAT, BLOCK, GBINS, false, kPre, LEAN>(ops, a, L, cur, i, step, left, acc);
     } else {
-        tile_loop<Ops, MAT, BLOCK, GBINS, FASTK == kArithFast, kPre>(ops, a, L, cur, i, step, left, acc);
+        tile_loop<Ops, MAT, BLOCK, GBINS, FASTK == kArithFast, kPre, LEAN>(ops, a, L, cur, i, step, left, acc);
     }
     return acc;
 }
@@ -541,10 +560,18 @@ __device__ __forceinline__ UniV3Pools pools_of(const CFMM_CONST_AS AnyPools& u, 
 // the launch's direction ALONE -- lane t takes pools first + t + k·stride, k < full + (t < tail): the host did the division
 // -- and only then is everything else read (block_args: the LDS geometry, the trade and row buffers, the fee table), while
 // those loads are in flight.
-template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI>
+// LEAN: the same body for the one configuration every default launch has (launch_plan.h lean_launch, checked on the host:
+// compact write-through trade records, prices staged as pairs, a fee table, one bin copy per wavefront, not direct, every
+// pool stream shorter than 2 GiB).  What the general kernel asks per pool of every tile is a constant here, the pool index is
+// 32 bits wide (stream_at, store_pair_at), and in a fused launch only the blocks of a family that reads log v stage it (the
+// LDS layout is the launch's: carve_lds comes first).  Same grid, same tiles per lane in the same order, same operations
+// on the same operands: every output bit is the general kernel's.
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool MULTI, bool LEAN>
 __device__ __forceinline__ void sweep_body(const LaunchHead& h, const CFMM_CONST_AS SweepDesc& d, const CFMM_CONST_AS SegRec& sg,
                                            const BlockRec& br, const PricePre& pre)
 {
+    static_assert(!(LEAN && (GBINS || FASTK == kArithFull)), "the lean kernels: LDS bins, prices staged as pairs");
+    using Idx = typename std::conditional<LEAN, uint32_t, int64_t>::type;   // (LEAN: steps and indices wrap modulo 2^32, counts < 2^31)
     const Ops ops{pools_of(sg.pools, (const decltype(Ops::p)*)nullptr)};
     const int64_t stride = br.stride;
     const int64_t i0 = br.first + threadIdx.x;
@@ -553,16 +580,24 @@ __device__ __forceinline__ void sweep_body(const LaunchHead& h, const CFMM_CONST
     const int64_t step = reverse ? -stride : stride;
     const int64_t i = reverse ? i0 + (left - 1) * stride : i0;
     typename Ops::Raw cur = {};
-    if (left > 0) cur = ops.template load<GBINS>(i);
-    const SweepArgs a = block_args(h, launch_args(), d, sg);
+    if (left > 0) cur = ops.template load<GBINS, LEAN>((Idx)i);
+    SweepArgs a = block_args(h, launch_args(), d, sg);
+    if constexpr (LEAN) {
+        a.compact = 1;
+        a.nt_stores = 0;
+        a.v_shift = 4;
+        a.copies = BLOCK / 64;
+        a.direct = 0;
+    }
     const SweepLds L = carve_lds<BLOCK, GBINS>(a);
+    if constexpr (LEAN) a.need_logv = Ops::kNeedsLogPrices ? 1 : 0;   // (a launch with such a family has the row: lean_launch)
     bool poison, live;
-    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI>(ops, a, L, cur, i, step, left, poison, live, pre);
+    const double acc = sweep_tiles<Ops, MAT, BLOCK, GBINS, FASTK, MULTI, LEAN>(ops, a, L, cur, (Idx)i, (Idx)step, (Idx)left, poison, live, pre);
     finish_row<BLOCK, GBINS>(a, L, acc, br.row, poison, live);
 }
 
 // One segment's own launch: segment 0 of the descriptor, whose pool streams are requested together with the block's record
-template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK>
+template <class Ops, bool MAT, int BLOCK, bool GBINS, int FASTK, bool LEAN = false>
 __global__ __launch_bounds__(BLOCK) void sweep_kernel(const SweepDesc* desc, const double* v, int reverse, int n, SweepTail)
 {
     const LaunchHead h{desc, v, reverse, n};
@@ -570,7 +605,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(const SweepDesc* desc, con
     if constexpr (!GBINS) pre = request_prices<BLOCK>(v, n);
     const BlockRec br = block_rec(desc);
     const CFMM_CONST_AS SweepDesc& d = *const_as(desc);
-    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false>(h, d, d.seg[0], br, pre);
+    sweep_body<Ops, MAT, BLOCK, GBINS, FASTK, false, LEAN>(h, d, d.seg[0], br, pre);
 }
 
 // Several segments (pool families) in ONE launch, so HBM-bound ProductTwoCoin blocks and ALU-bound GeometricMean /
@@ -584,7 +619,7 @@ __global__ __launch_bounds__(BLOCK) void sweep_kernel(const SweepDesc* desc, con
 // pattern is rotated by one every 32 deals (one pass over an XCD's 32 CUs), so every XCD -- and, as the dispatcher fills
 // CUs in order, every CU -- hosts all families.  Placement is only a performance assumption: any placement computes the
 // same result.  Small grids: block b -> segment b % nseg.
-template <bool MAT, int BLOCK, bool GBINS, int FASTK>
+template <bool MAT, int BLOCK, bool GBINS, int FASTK, bool LEAN = false>
 __global__ __launch_bounds__(BLOCK) void sweep_multi(const SweepDesc* desc, const double* v, int reverse, int n, SweepTail)
 {
     const LaunchHead h{desc, v, reverse, n};
@@ -594,11 +629,11 @@ __global__ __launch_bounds__(BLOCK) void sweep_multi(const SweepDesc* desc, cons
     const CFMM_CONST_AS SweepDesc& d = *const_as(desc);
     const CFMM_CONST_AS SegRec& sg = d.seg[br.seg];
     switch (br.kind) {
-    case 0: sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre); break;
+    case 0: sweep_body<ProductOps, MAT, BLOCK, GBINS, FASTK, true, LEAN>(h, d, sg, br, pre); break;
     case 1: // log-space forms only; geomean_exact routers are swept by per-segment launches
-        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre);
+        sweep_body<GeoMeanLogOps, MAT, BLOCK, GBINS, FASTK, true, LEAN>(h, d, sg, br, pre);
         break;
-    default: sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true>(h, d, sg, br, pre); break;
+    default: sweep_body<UniV3Ops, MAT, BLOCK, GBINS, FASTK, true, LEAN>(h, d, sg, br, pre); break;
     }
 }
 #undef CFMM_CONST_AS

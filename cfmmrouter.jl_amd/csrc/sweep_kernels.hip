@@ -99,48 +99,64 @@ static hipError_t launch_k(const void* kernel, dim3 g, dim3 b, size_t lds, hipSt
     return hipLaunchKernel(kernel, g, b, args, lds, s);
 }
 
-// The sweep kernels (round 5: 82 two-coin instantiations, + 4 N-coin), written down ONCE: this table is what the launchers
+// The sweep kernels (82 two-coin instantiations + their 16 lean forms, + 4 N-coin), written down ONCE: this table is what the launchers
 // look a kernel up in AND what prepare_kernels walks, so a kernel that can be launched cannot miss its LDS attribute.
 // Which (family, arithmetic) pairs exist is the constructor below: per family {full-range, fast, auto} x {materialising,
 // fused} x {512, 1024 threads}; the reference-order GeometricMean forms, Solidly and the N-coin families run full-range
 // only (the N-coin ones at 512 threads), and so does the large-market mode (GBINS) of every family, at 512 threads.
+// The last dimension is the lean form (sweep_core.h sweep_body<..., LEAN>; chosen by launch_plan.h lean_launch): the fused
+// launch at 512 threads and ProductTwoCoin, log-space GeometricMean and UniV3 (with heads) at 1024, fast and auto arithmetic.
 enum KernelFamily { kFamProduct, kFamGeoMean, kFamGeoMeanLog, kFamSolidly, kFamUniV3, kFamUniV3Lean, kFamMulti, kFamWeighted, kFamCurve, kFamilies };
 struct SweepKernelTable {
     static constexpr int kGbinsSlot = 3;   // large-market mode sits behind the three arithmetics
-    // [family][arithmetic, or kGbinsSlot][block == kBigBlock][materialising]; null: no such kernel
-    const void* fn[kFamilies][4][2][2] = {};
+    // [family][arithmetic, or kGbinsSlot][block == kBigBlock][materialising][lean]; null: no such kernel
+    const void* fn[kFamilies][4][2][2][2] = {};
 
     template <class K> static const void* ptr(K* kernel) { return reinterpret_cast<const void*>(kernel); }
     template <class Ops, int ARITH> void sweep(int f)
     {
-        fn[f][ARITH][0][1] = ptr(&sweep_kernel<Ops, true, kMidBlock, false, ARITH>);
-        fn[f][ARITH][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, false, ARITH>);
-        fn[f][ARITH][1][1] = ptr(&sweep_kernel<Ops, true, kBigBlock, false, ARITH>);
-        fn[f][ARITH][1][0] = ptr(&sweep_kernel<Ops, false, kBigBlock, false, ARITH>);
+        fn[f][ARITH][0][1][0] = ptr(&sweep_kernel<Ops, true, kMidBlock, false, ARITH>);
+        fn[f][ARITH][0][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, false, ARITH>);
+        fn[f][ARITH][1][1][0] = ptr(&sweep_kernel<Ops, true, kBigBlock, false, ARITH>);
+        fn[f][ARITH][1][0][0] = ptr(&sweep_kernel<Ops, false, kBigBlock, false, ARITH>);
+    }
+    template <class Ops, int ARITH> void sweep_lean(int f)
+    {
+        fn[f][ARITH][1][1][1] = ptr(&sweep_kernel<Ops, true, kBigBlock, false, ARITH, true>);
+        fn[f][ARITH][1][0][1] = ptr(&sweep_kernel<Ops, false, kBigBlock, false, ARITH, true>);
+    }
+    template <int ARITH> void lean()
+    {
+        fn[kFamMulti][ARITH][0][1][1] = ptr(&sweep_multi<true, kMidBlock, false, ARITH, true>);
+        fn[kFamMulti][ARITH][0][0][1] = ptr(&sweep_multi<false, kMidBlock, false, ARITH, true>);
+        sweep_lean<ProductOps, ARITH>(kFamProduct);
+        sweep_lean<GeoMeanLogOps, ARITH>(kFamGeoMeanLog);
+        sweep_lean<UniV3Ops, ARITH>(kFamUniV3);
     }
     template <class Ops> void sweep_all(int f) { sweep<Ops, kArithFull>(f); sweep<Ops, kArithFast>(f); sweep<Ops, kArithAuto>(f); }
     template <class Ops> void sweep_gbins(int f)
     {
-        fn[f][kGbinsSlot][0][1] = ptr(&sweep_kernel<Ops, true, kMidBlock, true, kArithFull>);
-        fn[f][kGbinsSlot][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, true, kArithFull>);
+        fn[f][kGbinsSlot][0][1][0] = ptr(&sweep_kernel<Ops, true, kMidBlock, true, kArithFull>);
+        fn[f][kGbinsSlot][0][0][0] = ptr(&sweep_kernel<Ops, false, kMidBlock, true, kArithFull>);
     }
     template <int ARITH> void multi()
     {
-        fn[kFamMulti][ARITH][1][1] = ptr(&sweep_multi<true, kBigBlock, false, ARITH>);
-        fn[kFamMulti][ARITH][1][0] = ptr(&sweep_multi<false, kBigBlock, false, ARITH>);
-        fn[kFamMulti][ARITH][0][1] = ptr(&sweep_multi<true, kMidBlock, false, ARITH>);
-        fn[kFamMulti][ARITH][0][0] = ptr(&sweep_multi<false, kMidBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][1][1][0] = ptr(&sweep_multi<true, kBigBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][1][0][0] = ptr(&sweep_multi<false, kBigBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][0][1][0] = ptr(&sweep_multi<true, kMidBlock, false, ARITH>);
+        fn[kFamMulti][ARITH][0][0][0] = ptr(&sweep_multi<false, kMidBlock, false, ARITH>);
     }
     template <class F> void ncoin(int f)
     {
-        fn[f][kArithFull][0][1] = ptr(&sweep_ncoin<F, true>);
-        fn[f][kArithFull][0][0] = ptr(&sweep_ncoin<F, false>);
+        fn[f][kArithFull][0][1][0] = ptr(&sweep_ncoin<F, true>);
+        fn[f][kArithFull][0][0][0] = ptr(&sweep_ncoin<F, false>);
     }
     SweepKernelTable()
     {
-        fn[kFamMulti][kGbinsSlot][0][1] = ptr(&sweep_multi<true, kMidBlock, true, kArithFull>);
-        fn[kFamMulti][kGbinsSlot][0][0] = ptr(&sweep_multi<false, kMidBlock, true, kArithFull>);
+        fn[kFamMulti][kGbinsSlot][0][1][0] = ptr(&sweep_multi<true, kMidBlock, true, kArithFull>);
+        fn[kFamMulti][kGbinsSlot][0][0][0] = ptr(&sweep_multi<false, kMidBlock, true, kArithFull>);
         multi<kArithFull>(); multi<kArithFast>(); multi<kArithAuto>();
+        lean<kArithFast>(); lean<kArithAuto>();
         ncoin<WeightedFamily>(kFamWeighted);
         ncoin<CurveFamily>(kFamCurve);
         sweep_all<ProductOps>(kFamProduct);
@@ -157,11 +173,11 @@ struct SweepKernelTable {
         sweep_gbins<UniV3OpsLean>(kFamUniV3Lean);
     }
     // null: no such kernel -- there is no falling through to another one
-    const void* find(int f, bool mat, int block, bool gbins, int arith) const
+    const void* find(int f, bool mat, int block, bool gbins, int arith, bool lean) const
     {
-        if ((block != kMidBlock && block != kBigBlock) || arith < kArithFull || arith > kArithAuto || (gbins && arith != kArithFull))
+        if ((block != kMidBlock && block != kBigBlock) || arith < kArithFull || arith > kArithAuto || (gbins && (arith != kArithFull || lean)))
             return nullptr;
-        return fn[f][gbins ? kGbinsSlot : arith][block == kBigBlock][mat];
+        return fn[f][gbins ? kGbinsSlot : arith][block == kBigBlock][mat][lean];
     }
 };
 static const SweepKernelTable kSweepKernels;
@@ -169,7 +185,7 @@ static const SweepKernelTable kSweepKernels;
 // every kernel of the table may use the whole LDS of a CU
 hipError_t prepare_kernels(size_t max_lds_bytes)
 {
-    const void* const* kernels = &kSweepKernels.fn[0][0][0][0];
+    const void* const* kernels = &kSweepKernels.fn[0][0][0][0][0];
     for (size_t k = 0; k < sizeof(SweepKernelTable::fn) / sizeof(void*); ++k) {
         if (!kernels[k]) continue;
         hipError_t e = hipFuncSetAttribute(kernels[k], hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds_bytes);
@@ -181,7 +197,7 @@ hipError_t prepare_kernels(size_t max_lds_bytes)
 // every sweep launch: the kernel comes from the table or the launch fails
 static hipError_t launch_family(int family, bool gbins, const LaunchCfg& c, bool mat, hipStream_t s, void** args)
 {
-    const void* kernel = kSweepKernels.find(family, mat, c.block, gbins, c.arith);
+    const void* kernel = kSweepKernels.find(family, mat, c.block, gbins, c.arith, c.lean);
     if (!kernel) return hipErrorInvalidDeviceFunction;
     return launch_k(kernel, dim3(c.grid), dim3(c.block), c.lds_bytes, s, c.ev_start, c.ev_stop, args);
 }

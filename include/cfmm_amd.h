@@ -106,7 +106,11 @@ int cfmm_reset_stream(cfmm_ctx* ctx);
  *                     "univ3_heads" (default 1: multi-tick UniV3 walks decide their first four list ticks from a per-pool
  *                     head of rounded-down binary32 thresholds read with the pool's coalesced streams, and consult the
  *                     exact threshold array only for deeper walks or a price within 2^-23 of a threshold: same decisions,
- *                     same bits, 11 % fewer bytes; 0: always the exact array)
+ *                     same bits, 11 % fewer bytes; 0: always the exact array),
+ *                     "lean_kernels" (default 1: a launch in the default configuration -- compact write-through trade
+ *                     records, a fee table, prices staged as pairs, one bin copy per wavefront -- takes the form of its
+ *                     kernel in which those are compile-time facts: same bits, fewer instructions per tile; 0: always the
+ *                     general kernels; read-only "lean_launches": the sweep launches that took such a kernel)
  *   arithmetic        "fast_math" (default 1: where every operand lies in [2^-150, 2^150] -- pool constants checked at
  *                     upload, prices by the host (host-pointer calls, cfmm_route) and again by every block as it stages
  *                     them; the library then launches kernels in which divisions and square roots run the compiler's
