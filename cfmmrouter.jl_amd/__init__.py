@@ -10,7 +10,7 @@ from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwo
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
-from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_path, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_,
+from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_,
                      swap_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
 
 
@@ -30,5 +30,5 @@ __all__ = [
     "CFMMDeviceError", "Context", "DeviceBackend", "build", "lib", "zerotrade", "ϕ", "ϕ_grad_", "phi", "grad_phi_",
     "polish_", "dual_jacobian", "active_trades", "forward_trade", "quote", "backward_trade", "quote_out",
     "quote_path", "quote_path_out", "swap_", "swap_path_", "swap_out_", "swap_path_out_",
-    "find_path", "FOUND", "FOUND_NONE", "FOUND_REPEATS",
+    "find_path", "find_path_out", "FOUND", "FOUND_NONE", "FOUND_REPEATS",
 ]

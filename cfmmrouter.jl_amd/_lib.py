@@ -67,7 +67,7 @@ class CFMMDeviceError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile libcfmm_amd.so for gfx950 with hipcc (csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    srcs.append(os.path.join(os.path.dirname(_HERE), "include", "cfmm_amd.h"))
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h")]
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -148,6 +148,7 @@ def lib():
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
+    L.cfmm_find_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -647,7 +648,7 @@ class Context:
             cols.append(a)
         return (nh, *(np.ascontiguousarray(a.T) for a in cols))
 
-    # -- path search (cfmm_find_path): the best walk of at most max_hops hops between two tokens, found on the device ----------
+    # -- path search (cfmm_find_path / cfmm_find_path_out): the best walk of at most max_hops hops between two tokens, found on the device ----------
     def find_path(self, token_in, token_out, amount_in, max_hops=3):
         """The best swap walk from token_in[q] to token_out[q] (0-based token ids) for amount_in[q], of at most max_hops
         (1 .. MAX_PATH_HOPS) hops, on the pools as they stand on the device (cfmm_find_path): returns (amount_out, n_hops, seg,
@@ -659,18 +660,35 @@ class Context:
         as it stands; the result is a WALK and may visit a pool twice: status[q] is FOUND, FOUND_NONE (not reached, or amount 0:
         amount_out 0.0, n_hops 0) or FOUND_REPEATS (swap_path would refuse it as one path).  Scalars broadcast.  Read-only.
         Everything is checked before anything runs (ArgumentError names the query)."""
+        return self._find_path("cfmm_find_path", "amount_in", token_in, token_out, amount_in, max_hops)
+
+    def find_path_out(self, token_in, token_out, amount_out, max_hops=3):
+        """The CHEAPEST swap walk that buys exactly amount_out[q] of token_out[q], paid in token_in[q] (0-based token ids), of at
+        most max_hops (1 .. MAX_PATH_HOPS) hops, on the pools as they stand on the device (cfmm_find_path_out): returns
+        (amount_in, n_hops, seg, row, ci, co, status) -- amount_in, n_hops, status [count]; seg, row, ci, co [count, max_hops] hop
+        arrays in path order, exactly what quote_path_out / swap_path_out take (-1 in the slots at k >= n_hops[q]).  The
+        contract is find_path's layered search run backwards from the wanted output: layer h holds, per token, the SMALLEST
+        quote_out over every pool and ordered coin pair into layer h-1; the answer is the smallest layer entry of token_in, with
+        the fewest hops, walked forward through the smallest (segment, row, coin_in, coin_out) that attains each layer bit for
+        bit -- so quote_path_out on the result answers amount_in bit for bit.  status[q] is FOUND, FOUND_REPEATS (a walk that
+        visits a pool twice: swap_path_out would refuse it as one path) or FOUND_NONE with n_hops 0 and amount_in +inf (token_in
+        not reached within max_hops: no pool can give that much) or +0.0 (amount_out 0: nothing to buy).  Scalars broadcast.
+        Read-only.  Everything is checked before anything runs (ArgumentError names the query)."""
+        return self._find_path("cfmm_find_path_out", "amount_out", token_in, token_out, amount_out, max_hops)
+
+    def _find_path(self, entry, amount_name, token_in, token_out, amount, max_hops):
         try:
             tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int32).reshape(-1), np.asarray(token_out, dtype=np.int32).reshape(-1),
-                                                 f64(amount_in).reshape(-1))
+                                                 f64(amount).reshape(-1))
         except ValueError:
-            raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+            raise ArgumentError(f"token_in, token_out and {amount_name} must be scalars or have one entry per query") from None
         tin, tout, amt = (np.ascontiguousarray(a) for a in (tin, tout, amt))
         n, H = amt.size, int(max_hops)
         out, nh, st = np.empty(n), np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
         seg, ci, co = (np.empty((max(H, 0), n), dtype=np.int32) for _ in range(3))
         row = np.empty((max(H, 0), n), dtype=np.int64)
-        self._check(self._L.cfmm_find_path(self._h, n, H, ptr(tin), ptr(tout), ptr(amt), ptr(out), ptr(nh), ptr(seg), ptr(row), ptr(ci),
-                                           ptr(co), ptr(st)))
+        self._check(getattr(self._L, entry)(self._h, n, H, ptr(tin), ptr(tout), ptr(amt), ptr(out), ptr(nh), ptr(seg), ptr(row), ptr(ci),
+                                            ptr(co), ptr(st)))
         return out, nh, seg.T.copy(), row.T.copy(), ci.T.copy(), co.T.copy(), st
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,

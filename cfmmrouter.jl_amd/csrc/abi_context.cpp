@@ -342,8 +342,9 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (key && !std::strcmp(key, "swap_ns")) { *value = c->swap.ns; return CFMM_OK; }
     if (key && !std::strcmp(key, "swap_refused")) { *value = c->swap.refused; return CFMM_OK; }
     if (key && !std::strcmp(key, "swap_launches")) { *value = c->swap.launches; return CFMM_OK; }
-    // read-only, cfmm_find_path: the latest call's kernel launches, and under "time_kernels" the sums of the spans of its layer
-    // launches (find_relax) and of its walk-back launches (find_claim + find_advance)
+    // read-only, cfmm_find_path / cfmm_find_path_out (whichever was called last): the latest call's kernel launches, and under
+    // "time_kernels" the sums of the spans of its layer launches (find_relax / find_out_relax) and of its walk launches (claim +
+    // advance)
     if (key && !std::strcmp(key, "find_launches")) { *value = c->find.launches; return CFMM_OK; }
     if (key && !std::strcmp(key, "find_relax_ns")) { *value = c->find.relax_ns; return CFMM_OK; }
     if (key && !std::strcmp(key, "find_walk_ns")) { *value = c->find.walk_ns; return CFMM_OK; }

@@ -6,8 +6,12 @@
 // stream -- clear, find_init, find_relax per layer, find_select, then find_claim + find_advance per layer from the last, and
 // find_finish, which writes the chunk's part of the call's outputs -- and no chunk reads what another wrote, so the results do
 // not depend on the chunking.  One synchronisation, at the end.
+// cfmm_find_path_out (include/cfmm_amd_find_out.h) is the same call in the other direction, as abi_swap_path.cpp serves both path
+// executions: the same table, staging, chunks and timing, the kFindOut* kernels, the layers cleared to all ones (the unreached
+// word of a min-search) and the two amounts exchanged -- FindArgs::amount_in carries the wanted amount_out.
 #include "ctx.h"
 #include "find_checks.h"
+#include "../../include/cfmm_amd_find_out.h"
 
 #include <algorithm>
 #include <cstring>
@@ -16,7 +20,16 @@ using namespace cfmm;
 
 namespace {
 
-constexpr const char* kWho = "cfmm_find_path";
+// the two directions: the entry's name, the given amount's name in a refusal, what a query without a path answers
+struct Direction {
+    bool out;
+    const char* who;
+    const char* amount;
+    FindKernel kernel(FindKernel k) const { return out ? (FindKernel)(k + kFindOutFirst) : k; }
+    // exact input: 0.0.  exact output: +inf, cfmm_quote_out's "cannot give that much" -- but buying nothing costs nothing
+    double none(double given) const { return !out || given == 0.0 ? 0.0 : __builtin_inf(); }
+};
+constexpr Direction kExactIn{false, "cfmm_find_path", "amount_in"}, kExactOut{true, "cfmm_find_path_out", "amount_out"};
 constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
 
 // one record per segment from the addresses the segment holds NOW (every stored segment has pools); returns the blocks that
@@ -97,19 +110,19 @@ int launch(cfmm_ctx* c, Timing& t, FindKernel k, const FindArgs& a)
     return CFMM_OK;
 }
 
-} // namespace
-
-int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
-                   const double* amount_in, double* amount_out, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
-                   int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status)
+// both entries; amount_in is the GIVEN amount and amount_out the ANSWER, whichever side of the path each stands on
+int find_paths(const Direction& d, cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+               const double* amount_in, double* amount_out, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
+               int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
+    const char* const kWho = d.who;
     if (is_parent(c))
         return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context: the layers of the search live on one "
                                              "device (find on a single-device context of the same pools)", kWho);
     char msg[256] = "";
     int rc = check_find(kWho, c->n, count, max_hops, token_in, token_out, amount_in, amount_out, n_hops, hop_seg, hop_row, hop_coin_in,
-                        hop_coin_out, status, msg, sizeof msg);
+                        hop_coin_out, status, msg, sizeof msg, d.amount);
     if (rc != CFMM_OK) return fail(c, rc, "%s", msg);
     if (count == 0) return CFMM_OK;
     FindScratch& fs = c->find;
@@ -118,7 +131,7 @@ int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
     const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H;
     if (c->segs.empty()) {   // a market without pools reaches nothing
         for (size_t q = 0; q < n; ++q) {
-            amount_out[q] = 0.0;
+            amount_out[q] = d.none(amount_in[q]);
             n_hops[q] = 0;
             status[q] = CFMM_FOUND_NONE;
         }
@@ -182,9 +195,9 @@ int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
         a.amount_out = fs.amt.get() + n + q0;
         a.best = fs.best.get();
         a.edge = fs.edge.get();
-        HIP_TRY(c, hipMemsetAsync(a.best, 0, (H + 1) * cq * nt * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(a.best, d.out ? 0xff : 0, (H + 1) * cq * nt * sizeof(unsigned long long), c->stream));
         HIP_TRY(c, hipMemsetAsync(a.edge, 0xff, H * cq * sizeof(unsigned long long), c->stream));
-        if ((rc = launch(c, timing, kFindInit, a)) != CFMM_OK) return rc;
+        if ((rc = launch(c, timing, d.kernel(kFindInit), a)) != CFMM_OK) return rc;
         // the layers: with the block's LDS copy where a group of queries' rows fit it (option "find_lds", default on), a block
         // folding enough tiles that about four blocks per CU remain
         a.group = c->opt_find_lds != 0 ? find_lds_group(c->n) : 0;
@@ -195,13 +208,13 @@ int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
             if (rows > 65535) a.group = 0;
         }
         for (a.layer = 1; a.layer <= max_hops; ++a.layer)
-            if ((rc = launch(c, timing, kFindRelax, a)) != CFMM_OK) return rc;
+            if ((rc = launch(c, timing, d.kernel(kFindRelax), a)) != CFMM_OK) return rc;
         a.group = 0;
-        if ((rc = launch(c, timing, kFindSelect, a)) != CFMM_OK) return rc;
+        if ((rc = launch(c, timing, d.kernel(kFindSelect), a)) != CFMM_OK) return rc;
         for (a.layer = max_hops; a.layer >= 1; --a.layer)
-            if ((rc = launch(c, timing, kFindClaim, a)) || (rc = launch(c, timing, kFindAdvance, a))) return rc;
+            if ((rc = launch(c, timing, d.kernel(kFindClaim), a)) || (rc = launch(c, timing, d.kernel(kFindAdvance), a))) return rc;
         a.layer = 0;
-        if ((rc = launch(c, timing, kFindFinish, a)) != CFMM_OK) return rc;
+        if ((rc = launch(c, timing, d.kernel(kFindFinish), a)) != CFMM_OK) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(h_out, fs.amt.get() + n, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_ns, d_i32 + 2 * n, 2 * n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -212,7 +225,7 @@ int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
         float ms = 0.f;
         HIP_TRY(c, hipEventElapsedTime(&ms, fs.ev[2 * k].get(), fs.ev[2 * k + 1].get()));
         const int64_t ns = (int64_t)((double)ms * 1e6);
-        const int w = timing.what[k], h = timing.layer[k];
+        const int w = timing.what[k] >= kFindOutFirst ? timing.what[k] - kFindOutFirst : timing.what[k], h = timing.layer[k];
         if (w == kFindRelax) fs.relax_ns += ns;
         if (w == kFindClaim || w == kFindAdvance) fs.walk_ns += ns;
         if ((w == kFindRelax || w == kFindClaim || w == kFindAdvance) && h >= 1 && h <= CFMM_MAX_PATH_HOPS)
@@ -226,4 +239,22 @@ int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
     std::memcpy(hop_coin_out, h_hop32 + 2 * nh, nh * sizeof(int32_t));
     std::memcpy(hop_row, h_row, nh * sizeof(long long));
     return CFMM_OK;
+}
+
+} // namespace
+
+int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+                   const double* amount_in, double* amount_out, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
+                   int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status)
+{
+    return find_paths(kExactIn, c, count, max_hops, token_in, token_out, amount_in, amount_out, n_hops, hop_seg, hop_row, hop_coin_in,
+                      hop_coin_out, status);
+}
+
+int cfmm_find_path_out(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+                       const double* amount_out, double* amount_in, int32_t* n_hops, int32_t* hop_seg, int64_t* hop_row,
+                       int32_t* hop_coin_in, int32_t* hop_coin_out, int32_t* status)
+{
+    return find_paths(kExactOut, c, count, max_hops, token_in, token_out, amount_out, amount_in, n_hops, hop_seg, hop_row, hop_coin_in,
+                      hop_coin_out, status);
 }

@@ -299,7 +299,9 @@ struct SwapPathScratch {
 // is proportional to n_tokens: (max_hops + 1) x queries of a chunk x n_tokens words, bounded by kFindScratchBudget
 // (find_checks.h) -- the claimed edges, the device copies of one call's queries and answers, the segment table (sweep.h
 // FindSeg, rebuilt per call) and ONE pinned staging buffer, all grown on demand and kept for the next call.  The call ends
-// synchronised, so nothing here is guarded against the call before.
+// synchronised, so nothing here is guarded against the call before.  cfmm_find_path_out uses the same scratch with the roles of
+// the amounts exchanged (best: the layers of its min-search, all ones = unreached; edge[k]: hop k in path order); the read-only
+// options describe the latest call of either entry.
 struct FindScratch {
     DevBuf<FindSeg> table;             // [segments]
     DevBuf<unsigned long long> best;   // [max_hops + 1][chunk][n_tokens]

@@ -1,7 +1,8 @@
 // find_checks.h -- internal, host only, HIP-free: the checks of a batch of cfmm_find_path queries before anything is enqueued,
 // and the rule that cuts a call into chunks of queries (abi_find_path.cpp).  Like path_checks.h they take plain arrays and
 // write the refusal's text into a caller's buffer, so a host program without a device or a context can exercise them
-// (tests/native/find_checks_host.cpp).  A refusal names the QUERY.
+// (tests/native/find_checks_host.cpp).  A refusal names the QUERY.  cfmm_find_path_out takes the same checks: its given amount
+// arrives as `amount_in` and is called by the name passed as `amount` ("amount_out") in the refusal.
 #pragma once
 
 #include "../../include/cfmm_amd.h"
@@ -31,7 +32,8 @@ inline int64_t find_chunk_queries(int64_t n_tokens, int32_t max_hops, int64_t bu
 
 inline int check_find(const char* who, int64_t n_tokens, int64_t count, int32_t max_hops, const int32_t* token_in,
                       const int32_t* token_out, const double* amount_in, const void* amount_out, const void* n_hops, const void* hop_seg,
-                      const void* hop_row, const void* hop_coin_in, const void* hop_coin_out, const void* status, char* msg, size_t len)
+                      const void* hop_row, const void* hop_coin_in, const void* hop_coin_out, const void* status, char* msg, size_t len,
+                      const char* amount = "amount_in")
 {
     if (count < 0) {
         std::snprintf(msg, len, "%s: count must be >= 0", who);
@@ -58,7 +60,7 @@ inline int check_find(const char* who, int64_t n_tokens, int64_t count, int32_t 
             return CFMM_ERR_INVALID_ARG;
         }
         if (!(amount_in[q] >= 0.0) || !std::isfinite(amount_in[q])) {
-            std::snprintf(msg, len, "%s: query %lld: amount_in must be finite and >= 0", who, (long long)q);
+            std::snprintf(msg, len, "%s: query %lld: %s must be finite and >= 0", who, (long long)q, amount);
             return CFMM_ERR_INVALID_ARG;
         }
     }

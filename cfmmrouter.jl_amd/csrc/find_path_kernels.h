@@ -302,4 +302,244 @@ __global__ __launch_bounds__(BLOCK) void find_finish(FindArgs a)
     a.status[q] = !h ? CFMM_FOUND_NONE : (repeats ? CFMM_FOUND_REPEATS : CFMM_FOUND);
 }
 
+// ---- cfmm_find_path_out: the cheapest walk that BUYS an exact amount, the same search run backwards from the wanted output ----
+// need[0][token_out] = amount_out, and need[h][t] is the SMALLEST quote_out_one<KIND>(pool, ci -> co, need[h-1][tok(co)]) over
+// every pool of every segment and every ordered coin pair whose tok(ci) is t and whose destination is reached.  FindArgs serves
+// with the amounts' roles exchanged, as PathArgs serves both quote directions: a.amount_in carries the wanted amount_out,
+// a.amount_out receives the amount to tender, a.best holds need -- a positive finite double's bits, ALL ONES = unreached (the
+// scratch is set by a memset of 0xff), so that the fold is a 64-BIT UNSIGNED INTEGER atomic min: still no float atomic.
+//   find_out_init     one lane per query: need[0][q][token_out] <- amount_out
+//   find_out_relax    THE HOT PATH: find_relax's grid, tiles and ballot early-out (a wavefront none of whose pools holds a reached
+//                     DESTINATION leaves before any pool state is read).  For every reached (query, co) and every ci != co it
+//                     evaluates path_hop<KIND, true> (quote_out_one<KIND>'s body, so the bits are cfmm_quote_out's) and folds the
+//                     answer into need[h][q][tok(ci)]; +inf ("that pool cannot give that much") enters nothing.  The LDS copy
+//                     (ds_min_u64) starts at all ones, under find_relax's group and tiles_per_block rule.
+//   find_out_select   one lane per query: amount_in = min over h >= 1 of need[h][q][token_in], the FEWEST hops that attain it
+//   find_out_claim    walking FORWARD from (h*, token_in), one launch per layer from h* down: one lane per pool, but only a lane
+//                     whose pool holds the CURRENT token of some query evaluates anything -- the quotes OUT OF that token, compared
+//                     bit for bit with need[h][current]; the smallest (segment, row, coin_in, coin_out) wins by an integer atomic
+//                     min on the packed edge, which lands in the hop's slot in PATH ORDER (hop k = h* - layer)
+//   find_out_advance  one lane per query: the claimed edge's coin_out token becomes the current token of the layer below
+//   find_out_finish   one lane per query: as find_finish; no path: amount_in +0.0 where amount_out is 0 (nothing to buy), else +inf
+constexpr unsigned long long kFindUnreached = ~0ull;
+
+__device__ __forceinline__ double find_quote_out(const PathSeg& s, int kind, long long m, long long row, int ci, int co, double amt)
+{
+    switch (kind) {
+    case CFMM_KIND_PRODUCT: return path_hop<CFMM_KIND_PRODUCT, true>(s, m, row, ci, co, amt);
+    case CFMM_KIND_GEOMEAN: return path_hop<CFMM_KIND_GEOMEAN, true>(s, m, row, ci, co, amt);
+    case CFMM_KIND_UNIV3: return path_hop<CFMM_KIND_UNIV3, true>(s, m, row, ci, co, amt);
+    case CFMM_KIND_WEIGHTED: return path_hop<CFMM_KIND_WEIGHTED, true>(s, m, row, ci, co, amt);
+    case CFMM_KIND_CURVE: return path_hop<CFMM_KIND_CURVE, true>(s, m, row, ci, co, amt);
+    case CFMM_KIND_SOLIDLY: return path_hop<CFMM_KIND_SOLIDLY, true>(s, m, row, ci, co, amt);
+    default: return __builtin_inf();
+    }
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void find_out_init(FindArgs a)
+{
+    const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= a.count) return;
+    const double y = a.amount_in[q];   // (the wanted amount_out)
+    const int t = a.token_out[q];
+    if (find_enters(y) && t >= 0 && t < a.n_tokens) a.best[q * a.n_tokens + t] = (unsigned long long)__double_as_longlong(y);
+}
+
+// find_fold's mirror: the words only shrink, so a value that does not undercut what is already there cannot change it
+template <bool LDS>
+__device__ __forceinline__ void find_fold_min(unsigned long long* word, unsigned long long bits)
+{
+    if (LDS) atomicMin(word, bits);
+    else if (bits < __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(word, bits);
+}
+
+// layer a.layer (1 .. max_hops) from the layer before; the two grids are find_relax's
+template <int BLOCK, bool LDS>
+__global__ __launch_bounds__(BLOCK) void find_out_relax(FindArgs a)
+{
+    extern __shared__ unsigned long long find_rows[];   // [group][n_tokens], LDS only
+    const int group = LDS ? a.group : kFindLaneQueries;
+    const long long q0 = (long long)blockIdx.y * group;
+    const int nq = (int)(a.count - q0 < group ? a.count - q0 : group);
+    const long long layer_words = a.count * (long long)a.n_tokens;
+    const unsigned long long* prev = a.best + (long long)(a.layer - 1) * layer_words + q0 * a.n_tokens;
+    unsigned long long* cur = a.best + (long long)a.layer * layer_words + q0 * a.n_tokens;
+    unsigned long long* into = LDS ? find_rows : cur;
+    const int words = nq * a.n_tokens;
+    if (LDS) {
+        for (int i = threadIdx.x; i < words; i += BLOCK) find_rows[i] = kFindUnreached;
+        __syncthreads();
+    }
+    const long long per_block = LDS ? a.tiles_per_block : 1;
+    const long long tile0 = (long long)blockIdx.x * per_block;
+    const long long tile1 = tile0 + per_block < a.tiles ? tile0 + per_block : a.tiles;
+    for (long long tile = tile0; tile < tile1; ++tile) {
+        const int sg = find_segment<true>(a.segs, a.nseg, tile);
+        const FindSeg& f = a.segs[sg];
+        const int kind = f.s.kind;
+        const int nc = f.s.n_coins < 2 ? 2 : (f.s.n_coins > kMaxCoins ? kMaxCoins : f.s.n_coins);
+        const long long m = f.s.m;
+        const long long row = (tile - f.first_tile) * BLOCK + threadIdx.x;
+        int tok[kMaxCoins];
+        unsigned long long reached = 0;   // bit j: some coin of this pool is a reached destination in query q0 + j
+        const bool live = kind >= 0 && row >= 0 && row < m;
+        if (live) {
+            find_tokens(f, nc, m, row, a.n_tokens, tok);
+            for (int j = 0; j < nq; ++j) {
+                unsigned long long all = kFindUnreached;
+                for (int k = 0; k < nc; ++k) all &= prev[(long long)j * a.n_tokens + tok[k]];
+                reached |= (unsigned long long)(all != kFindUnreached) << j;
+            }
+        }
+        if (__ballot(reached != 0) == 0) continue;   // the whole wavefront: no pool state was touched
+        while (reached) {
+            const int j = __builtin_ctzll(reached);
+            reached &= reached - 1;
+            const unsigned long long* pj = prev + (long long)j * a.n_tokens;
+            unsigned long long* cj = into + (long long)j * a.n_tokens;
+            for (int co = 0; co < nc; ++co) {
+                const unsigned long long bits = pj[tok[co]];
+                if (bits == kFindUnreached) continue;
+                const double amt = __longlong_as_double((long long)bits);
+                if (!find_enters(amt)) continue;   // (only such words are ever written; the scratch is not trusted to say so)
+                for (int ci = 0; ci < nc; ++ci) {
+                    if (ci == co) continue;
+                    const double r = find_quote_out(f.s, kind, m, row, ci, co, amt);
+                    if (find_enters(r)) find_fold_min<LDS>(cj + tok[ci], (unsigned long long)__double_as_longlong(r));
+                }
+            }
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < words; i += BLOCK) {
+            const unsigned long long bits = find_rows[i];
+            if (bits != kFindUnreached) find_fold_min<false>(cur + i, bits);
+        }
+    }
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void find_out_select(FindArgs a)
+{
+    const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= a.count) return;
+    const int t = a.token_in[q];
+    const long long layer_words = a.count * (long long)a.n_tokens;
+    unsigned long long low = kFindUnreached;
+    int h_star = 0;
+    if (t >= 0 && t < a.n_tokens)
+        for (int h = 1; h <= a.max_hops; ++h) {
+            const unsigned long long b = a.best[(long long)h * layer_words + q * a.n_tokens + t];
+            if (b < low) {   // strictly: the fewest hops among those that attain the minimum
+                low = b;
+                h_star = h;
+            }
+        }
+    a.h_star[q] = h_star;
+    a.target[q] = h_star ? t : -1;
+}
+
+// the hop that LEAVES layer a.layer: grid as find_out_relax without the LDS copy.  Only a lane whose pool holds a query's
+// current token evaluates anything.
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void find_out_claim(FindArgs a)
+{
+    const int sg = find_segment<true>(a.segs, a.nseg, blockIdx.x);
+    const FindSeg& f = a.segs[sg];
+    const int kind = f.s.kind;
+    const int nc = f.s.n_coins < 2 ? 2 : (f.s.n_coins > kMaxCoins ? kMaxCoins : f.s.n_coins);
+    const long long m = f.s.m;
+    const long long row = ((long long)blockIdx.x - f.first_tile) * BLOCK + threadIdx.x;
+    if (kind < 0 || row < 0 || row >= m) return;
+    const long long q0 = (long long)blockIdx.y * kFindLaneQueries;
+    const int nq = (int)(a.count - q0 < kFindLaneQueries ? a.count - q0 : kFindLaneQueries);
+    const long long layer_words = a.count * (long long)a.n_tokens;
+    int tok[kMaxCoins];
+    find_tokens(f, nc, m, row, a.n_tokens, tok);
+    for (int j = 0; j < nq; ++j) {
+        const long long q = q0 + j;
+        const int hs = a.h_star[q];
+        if (hs < a.layer || hs > a.max_hops) continue;
+        const int t = a.target[q];
+        if (t < 0 || t >= a.n_tokens) continue;
+        const unsigned long long* pj = a.best + (long long)(a.layer - 1) * layer_words + q * a.n_tokens;
+        unsigned long long want = 0;
+        bool have = false;
+        for (int ci = 0; ci < nc; ++ci) {
+            if (tok[ci] != t) continue;
+            if (!have) {
+                want = a.best[(long long)a.layer * layer_words + q * a.n_tokens + t];
+                have = true;
+            }
+            for (int co = 0; co < nc; ++co) {
+                if (co == ci) continue;
+                const unsigned long long bits = pj[tok[co]];
+                if (bits == kFindUnreached) continue;
+                const double amt = __longlong_as_double((long long)bits);
+                if (!find_enters(amt)) continue;
+                const double r = find_quote_out(f.s, kind, m, row, ci, co, amt);
+                if (find_enters(r) && (unsigned long long)__double_as_longlong(r) == want)
+                    atomicMin(a.edge + (long long)(hs - a.layer) * a.count + q,
+                              ((unsigned long long)(f.first_pool + row) << 6) | ((unsigned long long)ci << 3) | (unsigned long long)co);
+            }
+        }
+    }
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void find_out_advance(FindArgs a)
+{
+    const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= a.count) return;
+    const int hs = a.h_star[q];
+    if (hs < a.layer || hs > a.max_hops) return;
+    int sg, ci, co;
+    long long row;
+    int t = -1;
+    if (find_decode(a, a.edge[(long long)(hs - a.layer) * a.count + q], sg, row, ci, co)) {
+        const FindSeg& f = a.segs[sg];
+        int tok[kMaxCoins];
+        find_tokens(f, f.s.n_coins, f.s.m, row, a.n_tokens, tok);
+        t = tok[co];
+    }
+    a.target[q] = t;   // -1: nothing claims from here on, and find_out_finish answers that no path was found
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void find_out_finish(FindArgs a)
+{
+    const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= a.count) return;
+    int h = a.h_star[q];
+    h = h < 0 ? 0 : (h > a.max_hops ? a.max_hops : h);
+    int sg[CFMM_MAX_PATH_HOPS], ci[CFMM_MAX_PATH_HOPS], co[CFMM_MAX_PATH_HOPS];
+    long long row[CFMM_MAX_PATH_HOPS];
+    bool whole = h > 0;
+    for (int k = 0; k < CFMM_MAX_PATH_HOPS; ++k) {
+        sg[k] = ci[k] = co[k] = -1;
+        row[k] = -1;
+        if (k < h && whole) whole = find_decode(a, a.edge[(long long)k * a.count + q], sg[k], row[k], ci[k], co[k]);
+    }
+    if (!whole) h = 0;
+    bool repeats = false;
+    for (int k = 1; k < CFMM_MAX_PATH_HOPS; ++k)
+        for (int i = 0; i < k; ++i) repeats = repeats || (k < h && sg[i] == sg[k] && row[i] == row[k]);
+    for (int k = 0; k < a.max_hops; ++k) {
+        const long long at = (long long)k * a.stride + q;
+        const bool used = k < h;
+        a.hop_seg[at] = used ? sg[k] : -1;
+        a.hop_row[at] = used ? row[k] : -1;
+        a.hop_coin_in[at] = used ? ci[k] : -1;
+        a.hop_coin_out[at] = used ? co[k] : -1;
+    }
+    const long long layer_words = a.count * (long long)a.n_tokens;
+    const int t = find_clamp_token(a.token_in[q], a.n_tokens);
+    a.n_hops[q] = h;
+    a.amount_out[q] = h ? __longlong_as_double((long long)a.best[(long long)h * layer_words + q * a.n_tokens + t])
+                        : (a.amount_in[q] == 0.0 ? 0.0 : __builtin_inf());   // (the amount to tender)
+    a.status[q] = !h ? CFMM_FOUND_NONE : (repeats ? CFMM_FOUND_REPEATS : CFMM_FOUND);
+}
+
 } // namespace cfmm

@@ -585,7 +585,13 @@ struct FindArgs {
 // the LDS copy of find_relax: group x n_tokens words within this many bytes (four blocks of it fit a CU beside their registers)
 constexpr int kFindLdsBytes = 32768;
 inline int find_lds_group(int n_tokens) { const int g = kFindLdsBytes / 8 / (n_tokens < 1 ? 1 : n_tokens); return g > kFindLaneQueries ? kFindLaneQueries : g; }
-enum FindKernel { kFindInit, kFindRelax, kFindSelect, kFindClaim, kFindAdvance, kFindFinish };
+// kFindOut*: cfmm_find_path_out, the same search run backwards from the wanted output (find_path_kernels.h).  FindArgs serves
+// it with the roles of the amounts exchanged, as PathArgs serves both quote directions: amount_in carries the wanted
+// amount_out, amount_out receives the amount to tender, best holds the layers of a MIN-search (all ones = unreached), edge[k]
+// is hop k in path order and target is the token the forward walk stands at.
+enum FindKernel { kFindInit, kFindRelax, kFindSelect, kFindClaim, kFindAdvance, kFindFinish,
+                  kFindOutInit, kFindOutRelax, kFindOutSelect, kFindOutClaim, kFindOutAdvance, kFindOutFinish };
+constexpr int kFindOutFirst = kFindOutInit;   // a kFindOut* value minus this is the exact-input kernel of the same role
 // e0, e1: both set = the launch is timed by the command processor
 hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 

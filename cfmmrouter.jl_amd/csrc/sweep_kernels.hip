@@ -443,11 +443,12 @@ hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEv
     if (a.count <= 0 || a.stride < a.count || a.nseg <= 0 || a.n_tokens <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS)
         return hipErrorInvalidValue;
     const int64_t qblocks = (a.count + kFindBlock - 1) / kFindBlock, qrows = (a.count + kFindLaneQueries - 1) / kFindLaneQueries;
-    const bool per_pool = which == kFindRelax || which == kFindClaim;
-    if (which != kFindInit && which != kFindSelect && which != kFindFinish && (a.layer < 1 || a.layer > a.max_hops)) return hipErrorInvalidValue;
+    const int role = which >= kFindOutFirst ? which - kFindOutFirst : which;   // (cfmm_find_path_out's kernels take the same grids)
+    const bool per_pool = role == kFindRelax || role == kFindClaim;
+    if (role != kFindInit && role != kFindSelect && role != kFindFinish && (a.layer < 1 || a.layer > a.max_hops)) return hipErrorInvalidValue;
     if (per_pool && (a.tiles <= 0 || a.tiles > 0x7fffffffll || qrows > 65535)) return hipErrorInvalidValue;
     if (qblocks > 0x7fffffffll) return hipErrorInvalidValue;
-    const bool lds = which == kFindRelax && a.group > 0;
+    const bool lds = role == kFindRelax && a.group > 0;
     if (lds && (a.group > kFindLaneQueries || a.group > find_lds_group(a.n_tokens) || a.tiles_per_block < 1)) return hipErrorInvalidValue;
     const void* kernel;
     switch (which) {
@@ -457,6 +458,12 @@ hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEv
     case kFindClaim: kernel = reinterpret_cast<const void*>(&find_claim<kFindBlock>); break;
     case kFindAdvance: kernel = reinterpret_cast<const void*>(&find_advance<kFindBlock>); break;
     case kFindFinish: kernel = reinterpret_cast<const void*>(&find_finish<kFindBlock>); break;
+    case kFindOutInit: kernel = reinterpret_cast<const void*>(&find_out_init<kFindBlock>); break;
+    case kFindOutRelax: kernel = lds ? reinterpret_cast<const void*>(&find_out_relax<kFindBlock, true>) : reinterpret_cast<const void*>(&find_out_relax<kFindBlock, false>); break;
+    case kFindOutSelect: kernel = reinterpret_cast<const void*>(&find_out_select<kFindBlock>); break;
+    case kFindOutClaim: kernel = reinterpret_cast<const void*>(&find_out_claim<kFindBlock>); break;
+    case kFindOutAdvance: kernel = reinterpret_cast<const void*>(&find_out_advance<kFindBlock>); break;
+    case kFindOutFinish: kernel = reinterpret_cast<const void*>(&find_out_finish<kFindBlock>); break;
     default: return hipErrorInvalidDeviceFunction;   // no such kernel
     }
     void* args[] = {const_cast<FindArgs*>(&a)};

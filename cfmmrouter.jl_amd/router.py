@@ -855,17 +855,40 @@ def find_path(r: Router, token_in, token_out, amount_in, max_hops=3):
     answers `amount_out` bit for bit.  What is found is a walk: status[q] is FOUND, FOUND_NONE (token_out not reached within
     max_hops, or amount 0: amount_out 0.0) or FOUND_REPEATS (the walk visits a pool twice; `quote_path` and `swap_path_` refuse
     it as one path).  Host-evaluated plugin pools have no device state and are NOT searched.  Read-only, like `quote`."""
+    return _find_path(r, "find_path", "amount_in", token_in, token_out, amount_in, max_hops)
+
+
+def find_path_out(r: Router, token_in, token_out, amount_out, max_hops=3):
+    """The CHEAPEST swap path that buys exactly `amount_out[q]` of `token_out[q]`, paid in `token_in[q]` (token ids 1-based as in
+    `Ai`), of at most `max_hops` (1 .. 8) pools, FOUND on the device among the pools as they stand there (cfmm_find_path_out) --
+    "buy exactly 1000 of C, pay in A: through which pools, and what does it cost?".  Scalars broadcast.  The best path for an
+    input amount is not the cheapest path for an output amount; this is `find_path`'s search run backwards from the output.
+
+    Returns (amount_in, pools, tokens, status): `pools[q]` / `tokens[q]` are in the form `quote_path_out` / `swap_path_out_`
+    accept (positions in `r.cfmms`; the token ids along the path from token_in to token_out, one more than the pools), empty
+    where nothing was found.  The contract is the layered search: layer h holds per token the smallest `quote_out` over every
+    pool and ordered coin pair into layer h-1, every hop quoted AGAINST THE POOL AS IT STANDS; the answer is the smallest layer
+    entry of token_in with the fewest hops, ties broken towards the smallest (segment, row, coin_in, coin_out) walking forward
+    -- `quote_path_out(r, pools, tokens, amount_out)` answers `amount_in` bit for bit, and `swap_path_out_` with
+    `max_in=amount_in` executes it.  status[q] is FOUND, FOUND_REPEATS (the walk visits a pool twice; `quote_path_out` and
+    `swap_path_out_` refuse it as one path) or FOUND_NONE, with amount_in +inf (token_in not reached within max_hops: no pool
+    can give that much) or 0.0 (amount_out 0: nothing to buy).  Host-evaluated plugin pools have no device state: they are
+    NOT searched.  Read-only, like `quote_out`."""
+    return _find_path(r, "find_path_out", "amount_out", token_in, token_out, amount_out, max_hops)
+
+
+def _find_path(r: Router, verb, amount_name, token_in, token_out, amount, max_hops):
     L = r._layout
     try:
         tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int64).reshape(-1), np.asarray(token_out, dtype=np.int64).reshape(-1),
-                                             np.asarray(amount_in, dtype=np.float64).reshape(-1))
+                                             np.asarray(amount, dtype=np.float64).reshape(-1))
     except ValueError:
-        raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+        raise ArgumentError(f"token_in, token_out and {amount_name} must be scalars or have one entry per query") from None
     for name, t in (("token_in", tin), ("token_out", tout)):
         bad = np.flatnonzero((t < 1) | (t > r.n_tokens))
         if bad.size:
             raise ArgumentError(f"query {int(bad[0])}: {name} {int(t[bad[0]])} out of range 1:{r.n_tokens}")
-    out, n_hops, seg, row, ci, co, status = _path_context(r).find_path(tin - 1, tout - 1, amt, max_hops)
+    out, n_hops, seg, row, ci, co, status = getattr(_path_context(r), verb)(tin - 1, tout - 1, amt, max_hops)
     batch_of = {s: b for b, s in L.seg_of.items()}
     pools, tokens = [], []
     for q in range(len(out)):

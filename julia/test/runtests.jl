@@ -300,4 +300,23 @@ end
     @test find_paths(r, [1], [2], [0.0])[4] == [1]                                # nothing to carry: not found
     @test_throws ArgumentError find_paths(r, [9], [1], [1.0])
 end
+
+@testset "find_paths_out: the cheapest path that buys an exact amount, found on the device, then quoted and executed" begin
+    pools = random_product_market(50, 8; seed=12, fee=0.997)
+    r = AMDRouter(LinearNonnegative(rand(8)), pools, 8)
+    tin = [1 + q % 8 for q in 0:15]; tout = [1 + (q + 3) % 8 for q in 0:15]
+    want = fill(1e-3 * minimum(minimum(p.R) for p in pools), 16)
+    cost, paths, toks, status = find_paths_out(r, tin, tout, want; max_hops=3)
+    found = findall(==(0), status)
+    @test !isempty(found)
+    @test all(toks[q][1] == tin[q] && toks[q][end] == tout[q] && length(toks[q]) == length(paths[q]) + 1 for q in found)
+    @test quote_paths_out(r, paths[found], toks[found], want[found]) == cost[found]   # the bits of quoting the found path
+    q = found[1]
+    paid, st = swap_paths_out!(r, [paths[q]], [toks[q]], [want[q]]; max_in=[cost[q]])
+    @test st == [0] && paid[1] == cost[q]
+    @test find_paths_out(r, [tin[q]], [tout[q]], [want[q]]; max_hops=3)[1][1] > cost[q]   # the same order afterwards: dearer
+    none = find_paths_out(r, [1, 1], [2, 2], [0.0, 1e300])
+    @test none[4] == [1, 1] && none[1] == [0.0, Inf]                           # nothing to buy; more than any pool holds
+    @test_throws ArgumentError find_paths_out(r, [9], [1], [1.0])
+end
 end
