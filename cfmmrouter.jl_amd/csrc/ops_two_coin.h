@@ -1,6 +1,7 @@
 // ops_two_coin.h -- the two-coin closed forms of the sweep: what process_pool (sweep_core.h) asks of a pool family (Raw,
-// load, resolve, tokens, solve_dir), the packed {tokens, fee index} record's two helpers, and the Ops structs of
-// ProductTwoCoin, GeometricMeanTwoCoin (reference order and log space) and the Solidly-style stable pair.
+// load, resolve, tokens, solve_dir; lean_solve for the families of process_pool_lean), the packed {tokens, fee index}
+// record's two helpers, and the Ops structs of ProductTwoCoin, GeometricMeanTwoCoin (reference order and log space) and
+// the Solidly-style stable pair.
 #pragma once
 
 #include "fast_arith.h"
@@ -183,6 +184,38 @@ struct ProductOps {
         }
         return kDirNone;
     }
+    // The lean kernels' solve (sweep_core.h process_pool_lean): the same predicates and the same forms on the same operands,
+    // returned as what the epilogue of a pool uses instead of a code it has to decode -- the two amounts (+0.0 for a pool that
+    // does not trade), the direction and two lane predicates.  rare: the overlap of the two predicates or a NaN among the
+    // inputs; a wavefront with such a lane goes through solve_dir and the general epilogue, whatever d and l say here.
+    // dir1 is true for a pool that does not trade, so that its record is {+0.0, +0.0} and never {-(+0.0), +0.0}.
+    template <bool FAST>
+    __device__ __forceinline__ void lean_solve(const Raw& r, const Px& px, double& d, double& l, bool& dir1, bool& trades, bool& rare) const
+    {
+        const double R1 = r.R.x, R2 = r.R.y, g = r.g, v1 = px.v1, v2 = px.v2;
+        constexpr double kMargin = 1.0 + 1e-12;
+        const double a = v1 * R1, b = v2 * R2;
+        const bool p1 = (g * b) * kMargin >= a;
+        const bool p2 = (g * a) * kMargin >= b;
+        trades = p1 != p2;
+        dir1 = !p2;
+        rare = (p1 == p2) & (p1 | (a != a) | (b != b));
+        d = l = 0.0;
+        if (trades) {
+            const double k = R1 * R2;                          // :132
+            const double r_in = p1 ? R1 : R2, r_out = p1 ? R2 : R1;
+            const double v_in = p1 ? v1 : v2, v_out = p1 ? v2 : v1;
+            if constexpr (FAST) {
+                const double gm = g * div_by(v_out, v_in, p1 ? px.y1 : px.y2);
+                d = div_by(__builtin_fmax(fast_sqrt(gm * k) - r_in, 0.0), g, px.yg);   // :125
+                l = __builtin_fmax(r_out - fast_sqrt(fast_div(k, gm)), 0.0);           // :126
+            } else {
+                const double gm = g * (v_out / v_in);          // γ*m, m = v_out / v_in
+                d = max0(sqrt(gm * k) - r_in) / g;             // :125
+                l = max0(r_out - sqrt(k / gm));                // :126
+            }
+        }
+    }
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -339,6 +372,40 @@ struct GeoMeanLogOps {
         t.l2 = l;
         one_direction<FAST>(r, px, false, n2, d2, t.d2, t.l1);
         return kDirBoth;
+    }
+    // The lean kernels' solve (see ProductOps::lean_solve).  rare: a NaN price, or both directions live (needs γ > 1);
+    // a wavefront with such a lane goes through solve_dir and the general epilogue.  The live direction's operands are
+    // SELECTED: both exponents' numerators are formed (an add, and a multiply and a subtract) and one is taken, instead of
+    // a region per side.  The arithmetic is one_direction's.
+    template <bool FAST>
+    __device__ __forceinline__ void lean_solve(const Raw& r, const Px& px, double& d, double& l, bool& dir1, bool& trades, bool& rare) const
+    {
+        const double v1 = px.v1, v2 = px.v2;
+        const double R1 = r.R.x, R2 = r.R.y, g = r.g, eta = r.eta;
+        const double n1 = ((g * v2) * eta) * R2, d1 = v1;
+        const double n2 = (g * v1) * R1, d2 = v2 * eta;
+        const bool p1 = n1 > R1 * d1, p2 = n2 > R2 * d2;
+        trades = p1 | p2;                                    // (a NaN price: both false)
+        dir1 = !p2;
+        rare = (p1 & p2) | (v1 != v1) | (v2 != v2);
+        d = l = 0.0;
+        if (trades) {
+            const double A1 = r.Q.x + px.dlv, A2 = r.Q.y - eta * px.dlv;
+            const double A = p1 ? A1 : A2;
+            const double ra = p1 ? R2 : R1, rb = p1 ? R1 : R2;
+            const double n = p1 ? n1 : n2, dd = p1 ? d1 : d2;
+            double X, Y;
+            if constexpr (FAST) {
+                X = fast_exp(fast_div(A, eta + 1.0));
+                Y = fast_div((X * ra) * dd, n);
+                d = div_by(max0(X - rb), g, px.yg);
+            } else {
+                X = exp(A / (eta + 1.0));
+                Y = ((X * ra) * dd) / n;
+                d = max0(X - rb) / g;
+            }
+            l = max0(ra - Y);
+        }
     }
 };
 

@@ -1,5 +1,5 @@
-// sweep_core.h -- the fused two-coin sweep: trade and row stores, the LDS layout, price staging, one pool's epilogue
-// (process_pool), the tile loops, the block epilogue and the kernels sweep_kernel (one segment) / sweep_multi (several).
+// sweep_core.h -- the fused two-coin sweep: trade and row stores, the LDS layout, price staging, one pool's solve and
+// epilogue (process_pool: finish_pool, and process_pool_lean for the lean two-coin kernels), the tile loops, the block epilogue and the kernels sweep_kernel (one segment) / sweep_multi (several).
 #pragma once
 
 #include "granule.h"
@@ -142,7 +142,7 @@ __device__ __forceinline__ PricePre request_prices(const double* v, int n)
     }
     return r;
 }
-template <int BLOCK, bool GBINS, bool PRE = false>
+template <int BLOCK, bool GBINS, bool PRE = false, bool LEAN = false>
 __device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& L, const PricePre& pre = PricePre{})
 {
     if constexpr (GBINS) {
@@ -192,48 +192,37 @@ __device__ __forceinline__ int stage_prices(const SweepArgs& a, const SweepLds& 
     if ((tid & 63) == 0) L.flags[tid >> 6] = wave_in ? 1.0 : 0.0;
     __syncthreads();
     bool all_in = true;
+    if constexpr (LEAN) {
+        // the lean kernels: the flags as 16-byte reads (carve_lds: 16-byte aligned there), one wait, and an AND of their high
+        // words (1.0 / +0.0) instead of a short-circuit chain of one branch per wavefront
+        static_assert((BLOCK / 64) % 2 == 0, "flags are read in pairs");
+        const double2* pairs = reinterpret_cast<const double2*>(L.flags);
+        int bits = -1;
 #pragma unroll
-    for (int w = 0; w < BLOCK / 64; ++w) all_in = all_in && L.flags[w] != 0.0;
+        for (int w = 0; w < BLOCK / 128; ++w) {
+            const double2 f = pairs[w];
+            bits &= __double2hiint(f.x) & __double2hiint(f.y);
+        }
+        all_in = bits != 0;
+    } else {
+#pragma unroll
+        for (int w = 0; w < BLOCK / 64; ++w) all_in = all_in && L.flags[w] != 0.0;
+    }
     return (live ? kStageLive : 0) | (all_in ? kStageFast : 0) | (gave_up ? kStageGaveUp : 0);
 }
 
-// One pool: prices from LDS, closed form, trade record, dual scalar, netflow bins.
+// One pool behind its prices: closed form, trade record, dual scalar, netflow bins.
 // LEAN (sweep_body): a.compact, a.nt_stores, a.v_shift, a.need_logv and a.copies are compile-time constants here, the fee
 // comes from the LDS table and the trade record leaves through store_pair_at; the code is this one.
 template <class Ops, bool MAT, bool GBINS, bool FAST, bool LEAN, class Idx>
-__device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a, const SweepLds& L,
-                                             const typename Ops::Raw& raw_in, Idx i, double& acc)
+__device__ __forceinline__ void finish_pool(const Ops& ops, const SweepArgs& a, const SweepLds& L, const typename Ops::Raw& raw,
+                                            const Px& px, int2 tok, Idx i, double& acc)
 {
     // a compact trade record {x, y} of pool i
     const auto put_record = [&](double x, double y) {
         if constexpr (LEAN) store_pair_at(a.Delta, i, x, y);
         else store_pair(a.Delta + i, x, y, a.nt_stores);
     };
-    typename Ops::Raw raw = raw_in;
-    ops.template resolve<GBINS, FAST, LEAN>(raw, L.gtab);   // packed records: {tokens, fee-table index} -> tokens, fee
-    const int2 tok = ops.tokens(raw);
-    Px px;                                            // v[r.cfmms[i].Ai]
-    px.yg = raw.yg;
-    if constexpr (GBINS) {
-        px.v1 = a.v[tok.x];
-        px.v2 = a.v[tok.y];
-        px.y1 = px.y2 = 0.0;
-        px.dlv = Ops::kNeedsLogPrices ? log(px.v2 / px.v1) : 0.0;   // large markets: v is not staged, one logarithm per pool
-    } else {
-        if constexpr (FAST) {   // {v, rcp_refined(v)} pairs (FAST implies a.stage_y)
-            const double2 a1 = L.vy[tok.x], a2 = L.vy[tok.y];
-            px.v1 = a1.x; px.y1 = a1.y;
-            px.v2 = a2.x; px.y2 = a2.y;
-        } else {                // pairs, or -- markets too wide for them -- the prices alone (a.v_shift = 4 / 3)
-            const char* base = reinterpret_cast<const char*>(L.vy);
-            px.v1 = *reinterpret_cast<const double*>(base + ((size_t)tok.x << a.v_shift));
-            px.v2 = *reinterpret_cast<const double*>(base + ((size_t)tok.y << a.v_shift));
-            px.y1 = px.y2 = 0.0;
-        }
-        px.dlv = 0.0;
-        if constexpr (Ops::kNeedsLogPrices)   // log v staged per token, or -- markets too wide for that row -- one logarithm per pool
-            px.dlv = a.need_logv ? L.lv[tok.y] - L.lv[tok.x] : log(px.v2 / px.v1);
-    }
     Trade t;
     double d, l;
     int dir;
@@ -319,6 +308,101 @@ __device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a,
     }
 }
 
+// The families whose lean kernels run process_pool_lean (Ops::lean_solve): the two of the fused default launch
+template <class Ops> struct HasLeanSolve : std::false_type {};
+template <> struct HasLeanSolve<ProductOps> : std::true_type {};
+template <> struct HasLeanSolve<GeoMeanLogOps> : std::true_type {};
+
+// One pool of a lean kernel, ProductTwoCoin or log-space GeometricMean: a straight line for the pool every tile of a real
+// market is made of -- one direction or none, finite prices, amounts with a clear sign bit.
+//  * Every LDS read of the tile -- the fee pair, both {v, rcp v} pairs, both log v -- is issued from the packed record at
+//    once and waited for ONCE: the asm statement below names all of them, so none can be deferred into a region behind a
+//    wait of its own (what pinned() did for the fee alone, with a wait in front of the price reads).
+//  * lean_solve hands back {d, l}, the direction and the lane predicates trades / rare; the common epilogue is the general
+//    one's `plain` branch without its decoding: the record {dir1 ? d : -d, l} (a pool that does not trade: dir1, so
+//    {+0.0, +0.0}), acc += l·v_out − d·v_in under `trades`, the two LDS adds under their != 0 tests.
+//  * Rare lanes -- both directions live, a NaN price, ProductTwoCoin's predicate overlap, a set sign bit in a compact
+//    record's amounts -- are found by ONE wave-uniform test, and a wavefront that has one takes finish_pool, the general
+//    kernel's own solve and epilogue, with ALL its lanes and from the prices already read.  All of them, not the rare ones
+//    alone: a wavefront's lanes share one bin copy, two lanes' adds to the same bin round differently in a different order,
+//    and the order in which the general kernel issues the adds of its common and its rare lanes is the one its compiled
+//    epilogue has.  (Rare lanes alone behind the branch, the others on the straight line: Ψ of an 8-token market differed
+//    from the general kernel's in the last bit.)  A wavefront without a rare lane issues its two adds in the general order.
+// Same operations on the same operands in the same order as process_pool: same bits (tests/test_gpu_lean_common_path.py).
+template <class Ops, bool MAT, bool FAST, class Idx>
+__device__ __forceinline__ void process_pool_lean(const Ops& ops, const SweepArgs& a, const SweepLds& L,
+                                                  const typename Ops::Raw& raw_in, Idx i, double& acc)
+{
+    typename Ops::Raw raw = raw_in;
+    const unsigned packed = (unsigned)raw.ai.x;
+    const int2 tok = make_int2((int)(packed & 0xffffu), (int)(packed >> 16));
+    const double2 gy = L.gtab[ops.p.gbase + raw.ai.y];
+    const double2 a1 = L.vy[tok.x], a2 = L.vy[tok.y];
+    double g = gy.x, yg = gy.y, v1 = a1.x, y1 = a1.y, v2 = a2.x, y2 = a2.y, lv1 = 0.0, lv2 = 0.0;
+    if constexpr (Ops::kNeedsLogPrices) {
+        lv1 = L.lv[tok.x];
+        lv2 = L.lv[tok.y];
+        asm volatile("" : "+v"(g), "+v"(yg), "+v"(v1), "+v"(y1), "+v"(v2), "+v"(y2), "+v"(lv1), "+v"(lv2));
+    } else {
+        asm volatile("" : "+v"(g), "+v"(yg), "+v"(v1), "+v"(y1), "+v"(v2), "+v"(y2));
+    }
+    raw.ai = tok;
+    raw.g = g;
+    raw.yg = yg;
+    const Px px{v1, v2, y1, y2, yg, lv2 - lv1};
+    double d, l;
+    bool dir1, trades, rare;
+    ops.template lean_solve<FAST>(raw, px, d, l, dir1, trades, rare);
+    if (MAT) rare = rare | ((__double2hiint(d) | __double2hiint(l)) < 0);   // a compact record carries two clear sign bits
+    if (__builtin_expect(__any(rare ? 1 : 0) != 0, 0)) {
+        finish_pool<Ops, MAT, false, FAST, true>(ops, a, L, raw, px, tok, i, acc);
+        return;
+    }
+    if (MAT) store_pair_at(a.Delta, i, dir1 ? d : -d, l);   // {+Δ₁, Λ₂} or {−Δ₂, Λ₁}: the sign bit carries the direction
+    const double worth = l * (dir1 ? v2 : v1) - d * (dir1 ? v1 : v2);
+    acc = trades ? acc + worth : acc;
+    const double f_in = 0.0 - d;                            // Λ − Δ of the tendered token
+    if (f_in != 0.0) atomicAdd(&L.my_bins[dir1 ? tok.x : tok.y], f_in);   // ds_add_f64
+    if (l != 0.0) atomicAdd(&L.my_bins[dir1 ? tok.y : tok.x], l);
+}
+
+// One pool: prices from LDS, then finish_pool.
+template <class Ops, bool MAT, bool GBINS, bool FAST, bool LEAN, class Idx>
+__device__ __forceinline__ void process_pool(const Ops& ops, const SweepArgs& a, const SweepLds& L,
+                                             const typename Ops::Raw& raw_in, Idx i, double& acc)
+{
+    if constexpr (LEAN && HasLeanSolve<Ops>::value) {
+        process_pool_lean<Ops, MAT, FAST>(ops, a, L, raw_in, i, acc);
+        return;
+    }
+    typename Ops::Raw raw = raw_in;
+    ops.template resolve<GBINS, FAST, LEAN>(raw, L.gtab);   // packed records: {tokens, fee-table index} -> tokens, fee
+    const int2 tok = ops.tokens(raw);
+    Px px;                                            // v[r.cfmms[i].Ai]
+    px.yg = raw.yg;
+    if constexpr (GBINS) {
+        px.v1 = a.v[tok.x];
+        px.v2 = a.v[tok.y];
+        px.y1 = px.y2 = 0.0;
+        px.dlv = Ops::kNeedsLogPrices ? log(px.v2 / px.v1) : 0.0;   // large markets: v is not staged, one logarithm per pool
+    } else {
+        if constexpr (FAST) {   // {v, rcp_refined(v)} pairs (FAST implies a.stage_y)
+            const double2 a1 = L.vy[tok.x], a2 = L.vy[tok.y];
+            px.v1 = a1.x; px.y1 = a1.y;
+            px.v2 = a2.x; px.y2 = a2.y;
+        } else {                // pairs, or -- markets too wide for them -- the prices alone (a.v_shift = 4 / 3)
+            const char* base = reinterpret_cast<const char*>(L.vy);
+            px.v1 = *reinterpret_cast<const double*>(base + ((size_t)tok.x << a.v_shift));
+            px.v2 = *reinterpret_cast<const double*>(base + ((size_t)tok.y << a.v_shift));
+            px.y1 = px.y2 = 0.0;
+        }
+        px.dlv = 0.0;
+        if constexpr (Ops::kNeedsLogPrices)   // log v staged per token, or -- markets too wide for that row -- one logarithm per pool
+            px.dlv = a.need_logv ? L.lv[tok.y] - L.lv[tok.x] : log(px.v2 / px.v1);
+    }
+    finish_pool<Ops, MAT, GBINS, FAST, LEAN>(ops, a, L, raw, px, tok, i, acc);
+}
+
 // The tile loop of one pool family over a block's share of a segment: lane tid takes pools
 // i + k·step, k = 0, 1, ... left - 1.  Returns this lane's dual-scalar part.
 // The first tile's pool state is requested BEFORE v and the bins are staged in LDS, so that HBM round trip is not
@@ -381,7 +465,7 @@ __device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a
 {
     static_assert(!(GBINS && FASTK != kArithFull), "large-market mode runs on the compiler's sequences");
     double acc = 0.0;
-    const int staged = stage_prices<BLOCK, GBINS, !GBINS>(a, L, pre);
+    const int staged = stage_prices<BLOCK, GBINS, !GBINS, LEAN>(a, L, pre);
     poison = (staged & kStageLive) == 0;              // a pre-armed launch that is not needed (or gave up)
     live = !poison || (staged & kStageGaveUp) != 0;   // false: CANCELLED by the host (a launch that gave up waiting still reports NaN)
     if (staged & kStageGaveUp) report(a, kFlagGaveUp);
@@ -391,7 +475,9 @@ __device__ __forceinline__ double sweep_tiles(const Ops& ops, const SweepArgs& a
     }
     if (poison) left = 0;
     // next-tile prefetch: single-family launches of the two-coin families (HBM-resident -4..-6 %, cache-warm +-0.1 us); the
-    // fused multi-family launch keeps the plain loop (same-box A/B on config3: -2 % HBM-resident but +1.5 % on the warm step)
+    // fused multi-family launch keeps the plain loop (same-box A/B on config3: -2 % HBM-resident but +1.5 % on the warm step;
+    // again in the lean fused kernel, which has the registers for it: 11.92-12.38 us per step with it against 11.93-12.09
+    // without, 8 rounds -- no gain, profiles/lean_common_path.txt)
     constexpr bool kPre = Ops::kPrefetch && !MULTI;
     if constexpr (FASTK == kArithAuto) {
         if (staged & kStageFast) tile_loop<Ops, MAT, BLOCK, GBINS, true, kPre, LEAN>(ops, a, L, cur, i, step, left, acc);
