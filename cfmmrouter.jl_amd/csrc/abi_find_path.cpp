@@ -1,7 +1,7 @@
 // abi_find_path.cpp -- cfmm_find_path: the best swap walk of at most max_hops hops between two tokens, found on the device by
 // layers (the kernels and the contract: find_path_kernels.h; the checks and the chunking rule: find_checks.h).
 // Read-only.  Like the path quotes the kernels see the segments through a table in device memory (sweep.h FindSeg) that
-// build_table below REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES AND UPLOADS ON EVERY CALL: it is never a cache.
+// build_find_table below REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES (seg_view.h) AND UPLOADS ON EVERY CALL: it is never a cache.
 // The queries are processed in chunks whose layers fit kFindScratchBudget; a chunk is a sequence of launches on the context's
 // stream -- clear, find_init, find_relax per layer, find_select, then find_claim + find_advance per layer from the last, and
 // find_finish, which writes the chunk's part of the call's outputs -- and no chunk reads what another wrote, so the results do
@@ -9,8 +9,9 @@
 // cfmm_find_path_out (include/cfmm_amd_find_out.h) is the same call in the other direction, as abi_swap_path.cpp serves both path
 // executions: the same table, staging, chunks and timing, the kFindOut* kernels, the layers cleared to all ones (the unreached
 // word of a min-search) and the two amounts exchanged -- FindArgs::amount_in carries the wanted amount_out.
-#include "ctx.h"
 #include "find_checks.h"
+#include "seg_view.h"
+#include "stage_layout.h"
 #include "../../include/cfmm_amd_find_out.h"
 
 #include <algorithm>
@@ -30,81 +31,37 @@ struct Direction {
     double none(double given) const { return !out || given == 0.0 ? 0.0 : __builtin_inf(); }
 };
 constexpr Direction kExactIn{false, "cfmm_find_path", "amount_in"}, kExactOut{true, "cfmm_find_path_out", "amount_out"};
-constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
 
-// one record per segment from the addresses the segment holds NOW (every stored segment has pools); returns the blocks that
-// cover them
-int64_t build_table(const cfmm_ctx* c, FindSeg* t)
+// one record per segment (seg_view.h: from the addresses the segment holds NOW; every stored segment has pools); returns the
+// blocks that cover them
+int64_t build_find_table(const cfmm_ctx* c, FindSeg* t)
 {
-    std::memset(t, 0, c->segs.size() * sizeof(FindSeg));
     int64_t tiles = 0, pools = 0;
-    for (size_t i = 0; i < c->segs.size(); ++i) {
-        const Segment& s = c->segs[i];
-        FindSeg& f = t[i];
-        PathSeg& r = f.s;
-        r.kind = s.m > 0 ? s.kind : -1;
-        r.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
-        r.m = s.m;
-        if (s.kind == CFMM_KIND_UNIV3) {
-            r.pg = s.u.pg.get();
-            r.cur_a = s.u.cur_a.get();
-            r.cur_b = s.u.cur_b.get();
-            r.cur_c = s.u.cur_c.get();
-            r.curR = s.u.curR.get();
-            r.walk = s.u.walk.get();
-            r.ticks = s.u.ticks.get();
-        } else if (ragged_kind(s.kind)) {
-            r.nR = s.nc.R.get();
-            r.nq = s.nc.q.get();
-            r.nglg = s.nc.glg.get();
-            r.npar = s.nc.par.get();
-        } else {
-            r.R = s.R.get();
-            r.w = s.w.get();
-            r.gamma = s.gamma.get();
-        }
-        if (ragged_kind(s.kind)) {
-            f.tok = s.nc.tok.get();
-        } else {
-            f.pk = s.pk.get();
-            f.Ai = s.Ai.get();
-        }
-        f.first_tile = tiles;
-        f.first_pool = pools;
+    build_table(c, t, [&](const Segment& s, size_t) {
+        const FindSeg f = find_seg(s, tiles, pools);
         tiles += (s.m + kFindBlock - 1) / kFindBlock;
         pools += s.m;
-    }
+        return f;
+    });
     return tiles;
 }
 
 struct Timing {
-    cfmm_ctx* c;
     bool on;
-    size_t used = 0;
-    std::vector<int> what, layer;   // FindKernel and layer of every timed launch, in order
-    int pair(hipEvent_t& e0, hipEvent_t& e1, FindKernel k, int h)
-    {
-        e0 = e1 = nullptr;
-        if (!on) return CFMM_OK;
-        std::vector<Event>& ev = c->find.ev;
-        if (ev.size() < used + 2) ev.resize(used + 2);
-        int rc;
-        if ((rc = ev[used].create(c, hipEventDefault)) || (rc = ev[used + 1].create(c, hipEventDefault))) return rc;
-        e0 = ev[used].get();
-        e1 = ev[used + 1].get();
-        used += 2;
-        what.push_back(k);
-        layer.push_back(h);
-        return CFMM_OK;
-    }
+    std::vector<int> what, layer;   // FindKernel and layer of every timed launch, in order: launch k has pair k of FindScratch::ev
 };
 
 int launch(cfmm_ctx* c, Timing& t, FindKernel k, const FindArgs& a)
 {
-    hipEvent_t e0, e1;
-    const int rc = t.pair(e0, e1, k, a.layer);
-    if (rc != CFMM_OK) return rc;
-    const hipError_t e = launch_find(k, a, c->stream, e0, e1);
+    EventPairs& ev = c->find.ev;
+    const size_t j = t.what.size();
+    if (t.on) {
+        const int rc = ev.ensure(c, j + 1, j);
+        if (rc != CFMM_OK) return rc;
+        t.what.push_back(k);
+        t.layer.push_back(a.layer);
+    }
+    const hipError_t e = launch_find(k, a, c->stream, ev.start(j, t.on), ev.stop(j, t.on));
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "find path launch failed: %s", hipGetErrorString(e));
     ++c->find.launches;
     return CFMM_OK;
@@ -145,32 +102,26 @@ int find_paths(const Direction& d, cfmm_ctx* c, int64_t count, int32_t max_hops,
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nseg = c->segs.size(), nt = (size_t)c->n;
     const size_t chunk = (size_t)std::min<int64_t>(count, find_chunk_queries(c->n, max_hops));
-    // staging, 8-byte words: the table | token_in, token_out | amount_in || amount_out | n_hops, status | the three int32 hop
-    // columns | the rows
-    const size_t w_table = words_of(nseg * sizeof(FindSeg)), w_tok = words_of(2 * n * sizeof(int32_t));
-    const size_t w_ns = words_of(2 * n * sizeof(int32_t)), w_hop32 = words_of(3 * nh * sizeof(int32_t));
-    const size_t w_in = w_table + w_tok + n, w_out = n + w_ns + w_hop32 + nh;
-    if ((rc = fs.stage.grow(c, w_in + w_out, false)) || (rc = fs.table.grow(c, nseg)) || (rc = fs.best.grow(c, (H + 1) * chunk * nt)) ||
+    const FindStage lay(nseg * sizeof(FindSeg), n, nh);   // the pinned staging (stage_layout.h)
+    if ((rc = fs.stage.grow(c, lay.l.words(), false)) || (rc = fs.table.grow(c, nseg)) || (rc = fs.best.grow(c, (H + 1) * chunk * nt)) ||
         (rc = fs.edge.grow(c, H * chunk)) || (rc = fs.i32.grow(c, 4 * n + 3 * nh + 2 * chunk)) || (rc = fs.hop_row.grow(c, nh)) ||
         (rc = fs.amt.grow(c, 2 * n)))
         return rc;
     unsigned long long* st = fs.stage.host();
-    const int64_t tiles = build_table(c, reinterpret_cast<FindSeg*>(st));
-    int32_t* h_tok = reinterpret_cast<int32_t*>(st + w_table);
-    double* h_amt = reinterpret_cast<double*>(st + w_table + w_tok);
-    double* h_out = reinterpret_cast<double*>(st + w_in);
-    int32_t* h_ns = reinterpret_cast<int32_t*>(st + w_in + n);
-    int32_t* h_hop32 = reinterpret_cast<int32_t*>(st + w_in + n + w_ns);
-    long long* h_row = reinterpret_cast<long long*>(st + w_in + n + w_ns + w_hop32);
+    FindSeg* h_table = reinterpret_cast<FindSeg*>(lay.table.in(st));
+    const int64_t tiles = build_find_table(c, h_table);
+    int32_t *h_tok = lay.tok.in(st), *h_ns = lay.ns.in(st), *h_hop32 = lay.hop32.in(st);
+    double *h_amt = lay.amt.in(st), *h_out = lay.out.in(st);
+    long long* h_row = lay.row.in(st);
     std::memcpy(h_tok, token_in, n * sizeof(int32_t));
     std::memcpy(h_tok + n, token_out, n * sizeof(int32_t));
     std::memcpy(h_amt, amount_in, n * sizeof(double));
     int32_t* d_i32 = fs.i32.get();
-    HIP_TRY(c, hipMemcpyAsync(fs.table.get(), st, nseg * sizeof(FindSeg), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(fs.table.get(), h_table, nseg * sizeof(FindSeg), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(d_i32, h_tok, 2 * n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(fs.amt.get(), h_amt, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
 
-    Timing timing{c, c->opt_time_kernels != 0};
+    Timing timing{c->opt_time_kernels != 0, {}, {}};
     for (size_t q0 = 0; q0 < n; q0 += chunk) {
         const size_t cq = std::min(chunk, n - q0);
         FindArgs a{};
@@ -222,9 +173,8 @@ int find_paths(const Direction& d, cfmm_ctx* c, int64_t count, int32_t max_hops,
     HIP_TRY(c, hipMemcpyAsync(h_row, fs.hop_row.get(), nh * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < timing.what.size(); ++k) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, fs.ev[2 * k].get(), fs.ev[2 * k + 1].get()));
-        const int64_t ns = (int64_t)((double)ms * 1e6);
+        int64_t ns = 0;
+        if ((rc = fs.ev.elapsed_ns(c, k, 1, ns)) != CFMM_OK) return rc;
         const int w = timing.what[k] >= kFindOutFirst ? timing.what[k] - kFindOutFirst : timing.what[k], h = timing.layer[k];
         if (w == kFindRelax) fs.relax_ns += ns;
         if (w == kFindClaim || w == kFindAdvance) fs.walk_ns += ns;

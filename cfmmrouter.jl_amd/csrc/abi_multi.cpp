@@ -50,13 +50,6 @@ void pop_last_segment(cfmm_ctx* child)
 
 namespace cfmm {
 
-void shard_range(int64_t m, int d, int nd, int64_t& lo, int64_t& hi)
-{
-    const int64_t base = m / nd, rem = m % nd;
-    lo = d * base + std::min<int64_t>(d, rem);
-    hi = lo + base + (d < rem ? 1 : 0);
-}
-
 int multi_host_sweep(cfmm_ctx* c, const double* v, bool materialize)
 {
     const int nd = (int)c->shards.size();

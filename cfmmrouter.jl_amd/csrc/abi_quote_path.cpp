@@ -3,12 +3,12 @@
 // the per-hop forms are cfmm_quote's own, quote_pool.h; the checks: path_checks.h).  As in abi_quote.cpp the two directions
 // share every line: `given` / `answer` are amount_in / amount_out of the forward entries and amount_out / amount_in of the
 // inverse ones, `hops` is hop_out / hop_in.
-// Read-only.  The kernels see the segments through a table of PathSeg records in device memory, which build_table below
-// REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES AND UPLOADS ON EVERY CALL: cfmm_update_reserves, cfmm_pools_set_ticks and tick
-// compaction swap UniV3 arrays, and a table kept across calls would hold a freed address.  It is a line per segment.
+// Read-only.  The kernels see the segments through a table of PathSeg records in device memory, which upload_table below
+// REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES (seg_view.h) AND UPLOADS ON EVERY CALL: cfmm_update_reserves, cfmm_pools_set_ticks
+// and tick compaction swap UniV3 arrays, and a table kept across calls would hold a freed address.  It is a line per segment.
 // The only memory of the feature is PathScratch (ctx.h): proportional to count x max_hops, never to the pools.
-#include "ctx.h"
-#include "path_checks.h"
+#include "seg_view.h"
+#include "stage_layout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -19,61 +19,10 @@ using namespace cfmm;
 
 namespace {
 
-struct Dir {
-    bool exact_out;
-    const char *host, *dev;
-};
-constexpr Dir kForward{false, "cfmm_quote_path", "cfmm_quote_path_dev"};
-constexpr Dir kInverse{true, "cfmm_quote_path_out", "cfmm_quote_path_out_dev"};
+constexpr Dir kForward{false, "cfmm_quote_path", "cfmm_quote_path_dev", nullptr};
+constexpr Dir kInverse{true, "cfmm_quote_path_out", "cfmm_quote_path_out_dev", nullptr};
 
 int refuse(cfmm_ctx* c, int rc, const char* msg) { return rc == CFMM_OK ? rc : fail(c, rc, "%s", msg); }
-
-// the segments as the checks see them (a parent: its own list)
-std::vector<PathSegInfo> seg_infos(const cfmm_ctx* c)
-{
-    std::vector<PathSegInfo> v;
-    if (!c->shards.empty())
-        for (const cfmm_ctx::ParentSeg& s : c->psegs) v.push_back({s.kind, s.m, ragged_kind(s.kind) ? s.n_coins : 2});
-    else
-        for (const Segment& s : c->segs) v.push_back({s.kind, s.m, ragged_kind(s.kind) ? s.n_coins : 2});
-    return v;
-}
-
-// one record per segment from the addresses the segment holds NOW; at least one record, so that the kernel's clamp of a
-// segment number always lands on one (a context without pools: a record of kind -1, which no hop is valid on)
-void build_table(const cfmm_ctx* c, PathSeg* t, size_t nrec)
-{
-    std::memset(t, 0, nrec * sizeof(PathSeg));
-    t[0].kind = -1;
-    t[0].n_coins = 2;
-    for (size_t i = 0; i < c->segs.size(); ++i) {
-        const Segment& s = c->segs[i];
-        PathSeg& r = t[i];
-        r.kind = s.m > 0 ? s.kind : -1;
-        r.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
-        r.m = s.m;
-        if (s.kind == CFMM_KIND_UNIV3) {
-            r.pg = s.u.pg.get();
-            r.cur_a = s.u.cur_a.get();
-            r.cur_b = s.u.cur_b.get();
-            r.cur_c = s.u.cur_c.get();
-            r.curR = s.u.curR.get();
-            r.walk = s.u.walk.get();
-            r.ticks = s.u.ticks.get();
-        } else if (ragged_kind(s.kind)) {
-            r.nR = s.nc.R.get();
-            r.nq = s.nc.q.get();
-            r.nglg = s.nc.glg.get();
-            r.npar = s.nc.par.get();
-        } else {
-            r.R = s.R.get();
-            r.w = s.w.get();
-            r.gamma = s.gamma.get();
-        }
-    }
-}
-
-constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
 
 // The staging is free again, the table may be rewritten: the call before has left the device (`done` sits behind its kernel)
 int wait_previous(cfmm_ctx* c)
@@ -84,18 +33,21 @@ int wait_previous(cfmm_ctx* c)
     return CFMM_OK;
 }
 
-// table -> staging -> device, in stream order; `stage_words` is what the caller needs of the staging behind the table
-int upload_table(cfmm_ctx* c, size_t stage_words, size_t& table_words, int32_t& nrec_out)
+// the staging of a call of n paths (stage_layout.h PathStage)
+PathStage stage_of(const cfmm_ctx* c, size_t n, size_t nh, bool want_hops) { return PathStage(table_records(c) * sizeof(PathSeg), n, nh, want_hops); }
+
+// table (seg_view.h: rebuilt from the segments' current addresses) -> staging -> device, in stream order
+int upload_table(cfmm_ctx* c, const PathStage& lay, int32_t& nrec_out)
 {
     PathScratch& ps = c->path;
-    const size_t nrec = std::max<size_t>(1, c->segs.size());
-    table_words = words_of(nrec * sizeof(PathSeg));
+    const size_t nrec = table_records(c);
     int rc;
-    if ((rc = wait_previous(c)) || (rc = ps.stage.grow(c, table_words + stage_words, false)) || (rc = ps.table.grow(c, nrec)) ||
+    if ((rc = wait_previous(c)) || (rc = ps.stage.grow(c, lay.l.words(), false)) || (rc = ps.table.grow(c, nrec)) ||
         (rc = ps.done.create(c, hipEventDisableTiming)))
         return rc;
-    build_table(c, reinterpret_cast<PathSeg*>(ps.stage.host()), nrec);
-    HIP_TRY(c, hipMemcpyAsync(ps.table.get(), ps.stage.host(), nrec * sizeof(PathSeg), hipMemcpyHostToDevice, c->stream));
+    PathSeg* t = reinterpret_cast<PathSeg*>(lay.table.in(ps.stage.host()));
+    build_table(c, t, [](const Segment& s, size_t) { return path_seg(s); });
+    HIP_TRY(c, hipMemcpyAsync(ps.table.get(), t, nrec * sizeof(PathSeg), hipMemcpyHostToDevice, c->stream));
     nrec_out = (int32_t)nrec;
     return CFMM_OK;
 }
@@ -106,9 +58,8 @@ int launch(cfmm_ctx* c, const Dir& dir, const PathArgs& a)
     PathScratch& ps = c->path;
     const bool timed = c->opt_time_kernels != 0;
     int rc;
-    for (int k = 0; k < 2 && timed; ++k)
-        if ((rc = q.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
-    const hipError_t e = launch_quote_path(dir.exact_out, a, c->stream, timed ? q.ev[0].get() : nullptr, timed ? q.ev[1].get() : nullptr);
+    if (timed && (rc = q.ev.ensure(c, 1)) != CFMM_OK) return rc;
+    const hipError_t e = launch_quote_path(dir.exact_out, a, c->stream, q.ev.start(0, timed), q.ev.stop(0, timed));
     if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote path launch failed: %s", hipGetErrorString(e));
     HIP_TRY(c, hipEventRecord(ps.done.get(), c->stream));
     ps.in_flight = true;
@@ -166,38 +117,33 @@ int multi_path(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, con
     return CFMM_OK;
 }
 
-// Pinned staging behind the table, 8-byte words: n_hops + the three int32 hop columns ([1 + 3*max_hops][count] int32), the
-// rows, the given amounts, then the answers and the hop amounts -- copied to / from the scratch's device arrays in stream
-// order; one synchronisation.
+// Pinned staging behind the table (stage_layout.h PathStage), copied to / from the scratch's device arrays in stream order; one
+// synchronisation.
 int path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
               const int64_t* hop_row, const int32_t* ci, const int32_t* co, const double* given, double* answer, double* hops)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
     char msg[256] = "";
     const std::vector<PathSegInfo> info = seg_infos(c);
-    int rc = check_paths(dir.host, dir.exact_out, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, ci, co,
+    int rc = check_paths(dir.who, dir.exact_out, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, ci, co,
                          given, msg, sizeof msg);
     if (rc != CFMM_OK) return refuse(c, rc, msg);
-    if (count > 0 && !answer) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", dir.host);
+    if (count > 0 && !answer) return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", dir.who);
     if (count == 0) return CFMM_OK;
     if (!c->shards.empty()) return multi_path(c, dir, count, max_hops, n_hops, hop_seg, hop_row, ci, co, given, answer, hops);
 
     HIP_TRY(c, hipSetDevice(c->device));
     PathScratch& ps = c->path;
     const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H;
-    const size_t w_i32 = words_of((n + 3 * nh) * sizeof(int32_t));
-    const size_t w_in = w_i32 + nh + n, w_out = n + (hops ? nh : 0);
-    size_t tw = 0;
+    const PathStage lay = stage_of(c, n, nh, hops != nullptr);
     PathArgs a{};
-    if ((rc = upload_table(c, w_in + w_out, tw, a.nseg)) || (rc = ps.hop_i32.grow(c, n + 3 * nh)) || (rc = ps.hop_row.grow(c, nh)) ||
+    if ((rc = upload_table(c, lay, a.nseg)) || (rc = ps.hop_i32.grow(c, n + 3 * nh)) || (rc = ps.hop_row.grow(c, nh)) ||
         (rc = ps.given.grow(c, n)) || (rc = ps.answer.grow(c, n)) || (hops && (rc = ps.hops.grow(c, nh))))
         return rc;
-    unsigned long long* st = ps.stage.host() + tw;
-    int32_t* h_i32 = reinterpret_cast<int32_t*>(st);
-    long long* h_row = reinterpret_cast<long long*>(st + w_i32);
-    double* h_given = reinterpret_cast<double*>(st + w_i32 + nh);
-    double* h_answer = reinterpret_cast<double*>(st + w_in);
-    double* h_hops = h_answer + n;
+    unsigned long long* st = ps.stage.host();
+    int32_t* h_i32 = lay.i32.in(st);
+    long long* h_row = lay.row.in(st);
+    double *h_given = lay.given.in(st), *h_answer = lay.answer.in(st), *h_hops = lay.hops.in(st);
     std::memcpy(h_i32, n_hops, n * sizeof(int32_t));
     std::memcpy(h_i32 + n, hop_seg, nh * sizeof(int32_t));
     std::memcpy(h_i32 + n + nh, ci, nh * sizeof(int32_t));
@@ -224,9 +170,7 @@ int path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, cons
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     ps.in_flight = false;
     if (c->opt_time_kernels != 0) {
-        float ms = 0.f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->quote.ev[0].get(), c->quote.ev[1].get()));
-        c->quote.ns = (int64_t)((double)ms * 1e6);
+        if ((rc = c->quote.ev.elapsed_ns(c, 0, 1, c->quote.ns)) != CFMM_OK) return rc;
         c->quote.dev_timed = false;
     }
     std::memcpy(answer, h_answer, n * sizeof(double));
@@ -247,9 +191,8 @@ int path_dev(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, const
     if (!d_n_hops || !d_hop_seg || !d_hop_row || !d_ci || !d_co || !d_given || !d_answer)
         return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", dir.dev);
     HIP_TRY(c, hipSetDevice(c->device));
-    size_t tw = 0;
     PathArgs a{};
-    if ((rc = upload_table(c, 0, tw, a.nseg)) != CFMM_OK) return rc;
+    if ((rc = upload_table(c, stage_of(c, 0, 0, false), a.nseg)) != CFMM_OK) return rc;
     a.count = count;
     a.max_hops = max_hops;
     a.segs = c->path.table.get();

@@ -10,7 +10,8 @@
 // on the host -- reads the wave's landing prices back and moves the pools through cfmm_pools_set_prices' own apply path
 // (abi_update.cpp univ3_move_prices) before the next wave.  The only memory of the feature is SwapScratch (ctx.h),
 // proportional to the swaps of a call and never to the pools.
-#include "ctx.h"
+#include "seg_view.h"
+#include "stage_layout.h"
 #include "swap_waves.h"
 #include "univ3_pool.h"
 
@@ -22,51 +23,19 @@ using namespace cfmm;
 
 namespace {
 
-struct Dir {
-    bool exact_out;
-    const char *who, *given;   // the entry's name and the given amount's, as the messages spell them
-};
-constexpr Dir kForward{false, "cfmm_swap", "amount_in"};
-constexpr Dir kInverse{true, "cfmm_swap_out", "amount_out"};
+constexpr Dir kForward{false, "cfmm_swap", nullptr, "amount_in"};
+constexpr Dir kInverse{true, "cfmm_swap_out", nullptr, "amount_out"};
 
-constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
-
-// the kernel's view of segment `s`; the wave's query arrays are filled in by the caller
-hipError_t launch_wave(const cfmm_ctx* c, const Dir& dir, const Segment& s, const SwapOutArgs& w, hipEvent_t e0, hipEvent_t e1)
+// the kernel's view of segment `s` (seg_view.h), taken afresh per wave: a moved UniV3 pool may have regrown the record
+// arrays.  The wave's query arrays are filled in by the caller; `left`: the call's window flag.
+hipError_t launch_wave(const cfmm_ctx* c, const Dir& dir, const Segment& s, const SwapOutArgs& w, int* left, hipEvent_t e0, hipEvent_t e1)
 {
+    const SwapPathSeg p = swap_path_seg(s, left);
     SwapOutArgs so = w;
-    SwapArgs& a = so.s;
-    a.q.m = s.m;
-    a.q.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
-    a.q.R = s.R.get();
-    a.q.w = s.w.get();
-    a.q.gamma = s.gamma.get();
-    a.R = s.R.get();
-    a.Q = s.lR.get();
-    a.eta = s.eta.get();
-    a.ncR = s.nc.R.get();
-    a.ncq = s.nc.q.get();
-    UniV3Pools u;
-    NCoinPools n;
-    std::memset(&u, 0, sizeof u);
-    std::memset(&n, 0, sizeof n);
-    if (s.kind == CFMM_KIND_UNIV3) {   // (fresh addresses per wave: a moved pool may have regrown the record arrays)
-        const UniV3State& st = s.u;
-        u.pg = st.pg.get();
-        u.cur_a = st.cur_a.get();
-        u.cur_b = st.cur_b.get();
-        u.cur_c = st.cur_c.get();
-        u.curR = st.curR.get();
-        u.walk = st.walk.get();
-        u.ticks = st.ticks.get();
-    } else if (ragged_kind(s.kind)) {
-        n.R = s.nc.R.get();
-        n.q = s.nc.q.get();
-        n.glg = s.nc.glg.get();
-        n.par = s.nc.par.get();
-        n.n_coins = s.n_coins;
-    }
-    return dir.exact_out ? launch_swap_out(s.kind, so, u, n, c->stream, e0, e1) : launch_swap(s.kind, a, u, n, c->stream, e0, e1);
+    swap_view(p, so.s);
+    const UniV3Pools u = univ3_view(p.s);
+    const NCoinPools n = ncoin_view(p.s);
+    return dir.exact_out ? launch_swap_out(s.kind, so, u, n, c->stream, e0, e1) : launch_swap(s.kind, so.s, u, n, c->stream, e0, e1);
 }
 
 // One checked call on a single-device context.  limit, status: cfmm_swap_out's (either may be null); cfmm_swap passes neither.
@@ -82,27 +51,19 @@ int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const i
     const bool timed = c->opt_time_kernels != 0;
     const bool out = dir.exact_out;
     SwapScratch& sc = c->swap;
-    const size_t n = (size_t)count, w_status = words_of(n * sizeof(int32_t));
+    const size_t n = (size_t)count;
+    const SwapStage lay(n, idx != nullptr, univ3, limit != nullptr, out);
     int rc;
-    if ((rc = sc.stage.grow(c, 6 * n + w_status + 1, false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
+    if ((rc = sc.stage.grow(c, lay.l.words(), false)) || (rc = sc.amt.grow(c, n)) || (rc = sc.coins.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
         (idx && (rc = sc.idx.grow(c, n))) || (univ3 && (rc = sc.price.grow(c, n))) || (flagged && (rc = sc.left.grow(c, 1))) ||
-        (limit && (rc = sc.limit.grow(c, n))) || (out && (rc = sc.status.grow(c, n))))
+        (limit && (rc = sc.limit.grow(c, n))) || (out && (rc = sc.status.grow(c, n))) || (timed && (rc = sc.ev.ensure(c, (size_t)waves))))
         return rc;
-    if (timed) {
-        if (sc.ev.size() < 2 * (size_t)waves) sc.ev.resize(2 * (size_t)waves);
-        for (size_t k = 0; k < 2 * (size_t)waves; ++k)
-            if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
-    }
     // pinned staging, the swaps in launch order
     unsigned long long* st = sc.stage.host();
-    double* h_amt = reinterpret_cast<double*>(st);
-    int32_t* h_coins = reinterpret_cast<int32_t*>(st + n);   // [count] coin_in, then [count] coin_out
-    double* h_out = reinterpret_cast<double*>(st + 2 * n);
-    double* h_price = reinterpret_cast<double*>(st + 3 * n);
-    long long* h_idx = reinterpret_cast<long long*>(st + 4 * n);
-    double* h_limit = reinterpret_cast<double*>(st + 5 * n);
-    int32_t* h_status = reinterpret_cast<int32_t*>(st + 6 * n);
-    int* h_left = reinterpret_cast<int*>(st + 6 * n + w_status);
+    double *h_amt = lay.amt.in(st), *h_out = lay.out.in(st), *h_price = lay.price.in(st), *h_limit = lay.limit.in(st);
+    int32_t *h_coins = lay.coins.in(st), *h_status = lay.status.in(st);   // coins: [count] coin_in, then [count] coin_out
+    long long* h_idx = lay.idx.in(st);
+    int* h_left = lay.left.in(st);
     for (size_t j = 0; j < n; ++j) {
         const size_t q = (size_t)plan.perm[j];
         h_amt[j] = given[q];
@@ -133,10 +94,9 @@ int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const i
         a.q.amount_in = sc.amt.get() + off;
         a.q.amount_out = sc.out.get() + off;
         a.price = univ3 ? sc.price.get() + off : nullptr;
-        a.left_window = flagged ? sc.left.get() : nullptr;
         so.max_in = limit ? sc.limit.get() + off : nullptr;
         so.status = out ? sc.status.get() + off : nullptr;
-        const hipError_t e = launch_wave(c, dir, s, so, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        const hipError_t e = launch_wave(c, dir, s, so, sc.left.get(), sc.ev.start((size_t)w, timed), sc.ev.stop((size_t)w, timed));
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
         if (!univ3) continue;
         // the wave's landing prices, 8 bytes per swap (exact output: and its statuses -- only an applied swap moves its pool);
@@ -168,15 +128,7 @@ int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const i
     if (flagged) HIP_TRY(c, hipMemcpyAsync(h_left, sc.left.get(), sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (flagged && *h_left) s.fast_ok = 0;   // (never sent back: as cfmm_update_reserves)
-    if (timed) {
-        double ms_sum = 0.0;
-        for (int64_t w = 0; w < waves; ++w) {
-            float ms = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[2 * (size_t)w].get(), sc.ev[2 * (size_t)w + 1].get()));
-            ms_sum += (double)ms;
-        }
-        sc.ns = (int64_t)(ms_sum * 1e6);
-    }
+    if (timed && (rc = sc.ev.elapsed_ns(c, 0, (size_t)waves, sc.ns)) != CFMM_OK) return rc;
     int64_t refused = 0;
     for (size_t j = 0; j < n; ++j) {
         const double o = univ3 && !out && refused_at[j] ? std::nan("") : h_out[j];
@@ -195,45 +147,26 @@ int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const i
 int multi_swap(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int64_t* idx, const int32_t* coin_in,
                const int32_t* coin_out, const double* given, const double* limit, double* answer, int32_t* status)
 {
-    const int64_t m = c->psegs[(size_t)seg].m;
     const int nd = (int)c->shards.size();
-    std::vector<int64_t> first((size_t)nd), end((size_t)nd);
-    for (int d = 0; d < nd; ++d) shard_range(m, d, nd, first[(size_t)d], end[(size_t)d]);
-    struct Bucket {
-        std::vector<int64_t> where, rows;
-        std::vector<int32_t> ci, co;
-        std::vector<double> amt, lim;
-    };
-    std::vector<Bucket> buckets((size_t)nd);
-    for (int64_t q = 0; q < count; ++q) {
-        const int64_t row = idx ? idx[q] : q;
-        const size_t d = (size_t)(std::upper_bound(end.begin(), end.end(), row) - end.begin());   // first shard whose end > row
-        Bucket& bk = buckets[d];
-        bk.where.push_back(q);
-        bk.rows.push_back(row - first[d]);
-        bk.ci.push_back(coin_in[q]);
-        if (coin_out) bk.co.push_back(coin_out[q]);
-        bk.amt.push_back(given[q]);
-        if (limit) bk.lim.push_back(limit[q]);
-    }
+    const std::vector<ShardBucket> buckets = split_by_shard(c->psegs[(size_t)seg].m, nd, count, idx);
     c->have_trades = c->have_out = false;
     std::vector<double> out;
     std::vector<int32_t> st;
     int64_t ns = 0, refused = 0;
     for (int d = 0; d < nd; ++d) {
-        const Bucket& bk = buckets[(size_t)d];
+        const ShardBucket& bk = buckets[(size_t)d];
         if (bk.where.empty()) continue;
         out.resize(bk.where.size());
         st.resize(bk.where.size());
+        const std::vector<int32_t> ci = gather(bk.where, coin_in), co = gather(bk.where, coin_out);
+        const std::vector<double> amt = gather(bk.where, given), lim = gather(bk.where, limit);
         cfmm_ctx* child = c->shards[(size_t)d];
-        const int rc = swap_single(child, dir, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), bk.ci.data(),
-                                   coin_out ? bk.co.data() : nullptr, bk.amt.data(), limit ? bk.lim.data() : nullptr, out.data(),
+        const int rc = swap_single(child, dir, child_segment(c, seg, d), (int64_t)bk.where.size(), bk.rows.data(), ci.data(),
+                                   coin_out ? co.data() : nullptr, amt.data(), limit ? lim.data() : nullptr, out.data(),
                                    status ? st.data() : nullptr);
         if (rc != CFMM_OK) return fail(c, rc, "shard %d: %s (some shards may have moved)", d, child->err.c_str());
-        for (size_t j = 0; j < bk.where.size(); ++j) {
-            answer[bk.where[j]] = out[j];
-            if (status) status[bk.where[j]] = st[j];
-        }
+        scatter(bk.where, out.data(), answer);
+        if (status) scatter(bk.where, st.data(), status);
         if (child->opt_time_kernels != 0) ns = std::max(ns, child->swap.ns);
         refused += child->swap.refused;
     }
@@ -249,18 +182,15 @@ int swap_host(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const int
               const int32_t* coin_out, const double* given, const double* limit, double* answer, int32_t* status)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    const bool parent = !c->shards.empty();
-    int rc = check_quote_seg(c, dir.who, seg, count, parent ? (int64_t)c->psegs.size() : (int64_t)c->segs.size());
+    int rc = check_quote_seg(c, dir.who, seg, count, seg_count(c));
     if (rc != CFMM_OK) return rc;
-    const int kind = parent ? c->psegs[(size_t)seg].kind : c->segs[(size_t)seg].kind;
-    const int64_t m = parent ? c->psegs[(size_t)seg].m : c->segs[(size_t)seg].m;
-    const int nc = !ragged_kind(kind) ? 2 : (parent ? c->psegs[(size_t)seg].n_coins : c->segs[(size_t)seg].n_coins);
-    if ((rc = check_quote_queries(c, dir.who, dir.given, kind, m, nc, count, idx, coin_in, coin_out, given, answer)) != CFMM_OK) return rc;
+    const PathSegInfo si = seg_info(c, seg);
+    if ((rc = check_quote_queries(c, dir.who, dir.given, si.kind, si.m, si.n_coins, count, idx, coin_in, coin_out, given, answer)) != CFMM_OK) return rc;
     for (int64_t q = 0; limit && q < count; ++q)
         if (!(limit[q] >= 0.0) || !std::isfinite(limit[q]))
             return fail(c, CFMM_ERR_INVALID_ARG, "%s: query %lld: max_amount_in must be finite and >= 0", dir.who, (long long)q);
     if (count == 0) return CFMM_OK;   // a no-op that invalidates nothing
-    return parent ? multi_swap(c, dir, seg, count, idx, coin_in, coin_out, given, limit, answer, status)
+    return !c->shards.empty() ? multi_swap(c, dir, seg, count, idx, coin_in, coin_out, given, limit, answer, status)
                   : swap_single(c, dir, seg, count, idx, coin_in, coin_out, given, limit, answer, status);
 }
 

@@ -11,9 +11,9 @@
 // univ3_move_prices), after which the segment table is rebuilt (a moved pool may have regrown the record arrays).  Otherwise
 // it synchronises once, at the end.
 // The only memory of the feature is SwapPathScratch (ctx.h): proportional to count x max_hops, never to the pools.
-#include "ctx.h"
+#include "seg_view.h"
+#include "stage_layout.h"
 #include "../../include/cfmm_amd_path_out.h"
-#include "path_checks.h"
 #include "swap_path_checks.h"
 #include "swap_path_waves.h"
 #include "univ3_pool.h"
@@ -27,57 +27,15 @@ using namespace cfmm;
 
 namespace {
 
-struct Dir {
-    bool exact_out;
-    const char* who;
-};
-constexpr Dir kForward{false, "cfmm_swap_path"};
-constexpr Dir kInverse{true, "cfmm_swap_path_out"};
+constexpr Dir kForward{false, "cfmm_swap_path", nullptr, nullptr};
+constexpr Dir kInverse{true, "cfmm_swap_path_out", nullptr, nullptr};
 
-constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
-
-// one record per segment from the addresses the segment holds NOW (abi_quote_path.cpp build_table, plus the writable side);
-// at least one record, so that the kernel's clamp of a segment number always lands on one
-void build_table(const cfmm_ctx* c, SwapPathSeg* t, size_t nrec, int* d_left)
-{
-    std::memset(t, 0, nrec * sizeof(SwapPathSeg));
-    t[0].s.kind = -1;
-    t[0].s.n_coins = 2;
-    for (size_t i = 0; i < c->segs.size(); ++i) {
-        const Segment& s = c->segs[i];
-        SwapPathSeg& r = t[i];
-        r.s.kind = s.m > 0 ? s.kind : -1;
-        r.s.n_coins = ragged_kind(s.kind) ? s.n_coins : 2;
-        r.s.m = s.m;
-        if (s.kind == CFMM_KIND_UNIV3) {
-            r.s.pg = s.u.pg.get();
-            r.s.cur_a = s.u.cur_a.get();
-            r.s.cur_b = s.u.cur_b.get();
-            r.s.cur_c = s.u.cur_c.get();
-            r.s.curR = s.u.curR.get();
-            r.s.walk = s.u.walk.get();
-            r.s.ticks = s.u.ticks.get();
-        } else if (ragged_kind(s.kind)) {
-            r.s.nR = r.nR = s.nc.R.get();
-            r.s.nq = r.nq = s.nc.q.get();
-            r.s.nglg = s.nc.glg.get();
-            r.s.npar = s.nc.par.get();
-        } else {
-            r.s.R = r.R = s.R.get();
-            r.s.w = s.w.get();
-            r.s.gamma = s.gamma.get();
-            r.Q = s.lR.get();
-            r.eta = s.eta.get();
-            if (kind_info(s.kind).has_fast) r.left_window = d_left + i;   // (cfmm_swap's `flagged`)
-        }
-    }
-}
-
-int upload_table(cfmm_ctx* c, size_t nrec)
+// table (seg_view.h: rebuilt from the segments' current addresses, one window flag per segment) -> staging -> device
+int upload_table(cfmm_ctx* c, SwapPathSeg* t)
 {
     SwapPathScratch& sc = c->swap_path;
-    build_table(c, reinterpret_cast<SwapPathSeg*>(sc.stage.host()), nrec, sc.left.get());
-    HIP_TRY(c, hipMemcpyAsync(sc.table.get(), sc.stage.host(), nrec * sizeof(SwapPathSeg), hipMemcpyHostToDevice, c->stream));
+    build_table(c, t, [&](const Segment& s, size_t i) { return swap_path_seg(s, sc.left.get() + i); });
+    HIP_TRY(c, hipMemcpyAsync(sc.table.get(), t, table_records(c) * sizeof(SwapPathSeg), hipMemcpyHostToDevice, c->stream));
     return CFMM_OK;
 }
 
@@ -92,8 +50,7 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
     if (is_parent(c))   // a path's hops may sit on different shards: all-or-nothing across devices is a change of its own
         return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context (a path's hops may sit on different shards)", who);
     char msg[256] = "";
-    std::vector<PathSegInfo> info;
-    for (const Segment& s : c->segs) info.push_back({s.kind, s.m, ragged_kind(s.kind) ? s.n_coins : 2});
+    const std::vector<PathSegInfo> info = seg_infos(c);
     int rc = check_paths(who, dir.exact_out, info.data(), (int64_t)info.size(), count, max_hops, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
                          given, msg, sizeof msg);
     if (rc == CFMM_OK) rc = check_swap_paths(who, count, n_hops, hop_seg, hop_row, limit, msg, sizeof msg, dir.exact_out);
@@ -106,30 +63,20 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
     const int64_t waves = (int64_t)plan.wave_off.size() - 1;
     const bool timed = c->opt_time_kernels != 0;
     SwapPathScratch& sc = c->swap_path;
-    const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H, nseg = c->segs.size(), nrec = std::max<size_t>(1, nseg);
-    // pinned staging, 8-byte words: the table; n_hops + the three int32 hop columns; the rows; the given amounts and the limits;
-    // then what comes back: answers, hop amounts, landing prices, statuses, the window flags
-    const size_t w_table = words_of(nrec * sizeof(SwapPathSeg)), w_i32 = words_of((n + 3 * nh) * sizeof(int32_t));
-    const size_t w_status = words_of(n * sizeof(int32_t)), w_left = words_of(nrec * sizeof(int));
-    if ((rc = sc.stage.grow(c, w_table + w_i32 + nh + 2 * n + n + 2 * nh + w_status + w_left, false)) || (rc = sc.table.grow(c, nrec)) ||
+    const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H, nseg = c->segs.size(), nrec = table_records(c);
+    const SwapPathStage lay(nrec * sizeof(SwapPathSeg), nrec, n, nh);   // the pinned staging (stage_layout.h)
+    if ((rc = sc.stage.grow(c, lay.l.words(), false)) || (rc = sc.table.grow(c, nrec)) ||
         (rc = sc.hop_i32.grow(c, n + 3 * nh)) || (rc = sc.hop_row.grow(c, nh)) || (rc = sc.amt.grow(c, 2 * n)) || (rc = sc.out.grow(c, n)) ||
-        (rc = sc.hops.grow(c, nh)) || (rc = sc.price.grow(c, nh)) || (rc = sc.status.grow(c, n)) || (rc = sc.left.grow(c, nrec)))
+        (rc = sc.hops.grow(c, nh)) || (rc = sc.price.grow(c, nh)) || (rc = sc.status.grow(c, n)) || (rc = sc.left.grow(c, nrec)) ||
+        (timed && (rc = sc.ev.ensure(c, (size_t)waves))))
         return rc;
-    if (timed) {
-        if (sc.ev.size() < 2 * (size_t)waves) sc.ev.resize(2 * (size_t)waves);
-        for (size_t k = 0; k < 2 * (size_t)waves; ++k)
-            if ((rc = sc.ev[k].create(c, hipEventDefault)) != CFMM_OK) return rc;
-    }
-    unsigned long long* st = sc.stage.host() + w_table;
-    int32_t* h_i32 = reinterpret_cast<int32_t*>(st);
-    int32_t *h_seg = h_i32 + n, *h_ci = h_i32 + n + nh, *h_co = h_i32 + n + 2 * nh;
-    long long* h_row = reinterpret_cast<long long*>(st + w_i32);
-    double* h_amt = reinterpret_cast<double*>(st + w_i32 + nh);   // [count] the given amounts, then [count] the limits
-    double* h_out = h_amt + 2 * n;
-    double* h_hops = h_out + n;
-    double* h_price = h_hops + nh;
-    int32_t* h_status = reinterpret_cast<int32_t*>(h_price + nh);
-    int* h_left = reinterpret_cast<int*>(reinterpret_cast<unsigned long long*>(h_status) + w_status);
+    unsigned long long* st = sc.stage.host();
+    SwapPathSeg* h_table = reinterpret_cast<SwapPathSeg*>(lay.table.in(st));
+    int32_t *h_i32 = lay.i32.in(st), *h_seg = h_i32 + n, *h_ci = h_i32 + n + nh, *h_co = h_i32 + n + 2 * nh, *h_status = lay.status.in(st);
+    long long* h_row = lay.row.in(st);
+    double* h_amt = lay.amt.in(st);   // [count] the given amounts, then [count] the limits
+    double *h_out = lay.out.in(st), *h_hops = lay.hops.in(st), *h_price = lay.price.in(st);
+    int* h_left = lay.left.in(st);
     // the paths in launch order; the slots a path does not use are zeroed (never read by the kernel)
     std::memset(h_seg, 0, 3 * nh * sizeof(int32_t));
     std::memset(h_row, 0, nh * sizeof(long long));
@@ -146,7 +93,7 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
         }
     }
     armed_cancel(c);
-    if ((rc = upload_table(c, nrec)) != CFMM_OK) return rc;
+    if ((rc = upload_table(c, h_table)) != CFMM_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(sc.hop_i32.get(), h_i32, (n + 3 * nh) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sc.hop_row.get(), h_row, nh * sizeof(long long), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(sc.amt.get(), h_amt, (limit ? 2 : 1) * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -176,7 +123,7 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
         a.hops = sc.hops.get() + off;
         a.price = sc.price.get() + off;
         a.status = sc.status.get() + off;
-        const hipError_t e = (dir.exact_out ? launch_swap_path_out : launch_swap_path)(a, c->stream, timed ? sc.ev[2 * (size_t)w].get() : nullptr, timed ? sc.ev[2 * (size_t)w + 1].get() : nullptr);
+        const hipError_t e = (dir.exact_out ? launch_swap_path_out : launch_swap_path)(a, c->stream, sc.ev.start((size_t)w, timed), sc.ev.stop((size_t)w, timed));
         if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "swap path launch failed: %s (earlier waves of the call have moved their pools)", hipGetErrorString(e));
         if (!any_univ3) continue;
         // which hop levels of the wave hold a UniV3 hop
@@ -220,7 +167,7 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
             replaced = true;
         }
         // (the stream is idle up to the moves just enqueued, which do not read the staging's table: it may be rewritten)
-        if (replaced && w + 1 < waves && (rc = upload_table(c, nrec)) != CFMM_OK) return rc;
+        if (replaced && w + 1 < waves && (rc = upload_table(c, h_table)) != CFMM_OK) return rc;
     }
     HIP_TRY(c, hipMemcpyAsync(h_out, sc.out.get(), n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(h_status, sc.status.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -229,15 +176,7 @@ int swap_path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops,
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t i = 0; i < nseg; ++i)
         if (h_left[i]) c->segs[i].fast_ok = 0;   // (never sent back: as cfmm_update_reserves)
-    if (timed) {
-        double ms_sum = 0.0;
-        for (int64_t w = 0; w < waves; ++w) {
-            float ms = 0.f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, sc.ev[2 * (size_t)w].get(), sc.ev[2 * (size_t)w + 1].get()));
-            ms_sum += (double)ms;
-        }
-        c->swap.ns = (int64_t)(ms_sum * 1e6);
-    }
+    if (timed && (rc = sc.ev.elapsed_ns(c, 0, (size_t)waves, c->swap.ns)) != CFMM_OK) return rc;
     int64_t refused = 0;
     for (size_t j = 0; j < n; ++j) {
         const size_t q = (size_t)plan.perm[j];

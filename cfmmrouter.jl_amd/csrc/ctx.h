@@ -25,6 +25,9 @@
 //                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
 //   abi_find_path.cpp the best swap walk between two tokens, found on the device (cfmm_find_path; find_checks.h: the HIP-free
 //                     checks and the chunking rule)
+//   seg_view.h        what those five share, on top of this header: a segment as their kernels and their checks see it
+//   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
+//   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
 //   abi_multi.cpp     single-process multi-device parents
 //   abi_peers.cpp     one process per GPU: peer buffers, cfmm_set_peers
@@ -36,6 +39,7 @@
 #include "hostres.h"
 #include "ladder_store.h"
 #include "launch_plan.h"
+#include "shard_split.h"
 #include "swap_path_waves.h"
 #include "sweep.h"
 
@@ -235,8 +239,8 @@ struct QuoteScratch {
     DevBuf<long long> idx;             // [count]
     DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out
     DevBuf<double> amt, out;           // [count]
-    PinnedBuf<unsigned long long> stage;   // [4][count] 8-byte words: amounts, coins, answers, idx
-    Event ev[2];                       // option "time_kernels": {start, stop} of the latest call's kernel
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h QuoteStage
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
     int64_t ns = 0;                    // read-only option "quote_ns": that kernel's span
     bool dev_timed = false;            // the latest timed call was cfmm_quote_dev: its span is read when asked for
 };
@@ -252,7 +256,7 @@ struct PathScratch {
     DevBuf<long long> hop_row;         // [max_hops][count]
     DevBuf<double> given, answer;      // [count]
     DevBuf<double> hops;               // [max_hops][count]
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h PathStage
     Event done;                        // behind the latest call's kernel
     bool in_flight = false;
 };
@@ -268,9 +272,8 @@ struct SwapScratch {
     DevBuf<double> limit;              // [count] cfmm_swap_out: max_amount_in, where given
     DevBuf<int32_t> status;            // [count] cfmm_swap_out: CFMM_SWAP_*
     DevBuf<int> left;                  // [1] a new reserve left the window of the fast arithmetic (update_two_coin's flag)
-    PinnedBuf<unsigned long long> stage;   // [6.5][count] + 1 8-byte words: amounts, coins, answers, prices, idx, limits,
-                                           // statuses, the flag
-    std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapStage
+    EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
     int64_t ns = 0;                    // read-only option "swap_ns": the sum of that call's kernel spans
     int64_t refused = 0;               // read-only option "swap_refused": swaps of the latest call that were not applied
     int64_t launches = 0;              // read-only option "swap_launches": kernel launches (waves) of the latest call
@@ -290,8 +293,8 @@ struct SwapPathScratch {
     DevBuf<double> hops, price;        // [max_hops][count]
     DevBuf<int32_t> status;            // [count]
     DevBuf<int> left;                  // [segments] a new reserve of the segment left the window of the fast arithmetic
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
-    std::vector<Event> ev;             // option "time_kernels": {start, stop} per wave of the latest call
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapPathStage
+    EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
     PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
 };
 
@@ -310,8 +313,8 @@ struct FindScratch {
                                        // hop_coin_out; [2][chunk] the hops of the answer, the walk's target token
     DevBuf<long long> hop_row;         // [max_hops][count]
     DevBuf<double> amt;                // [2][count] amount_in, amount_out
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: the table, then the columns above
-    std::vector<Event> ev;             // option "time_kernels": {start, stop} per launch of the latest call
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h FindStage
+    EventPairs ev;                     // option "time_kernels": {start, stop} per launch of the latest call
     int64_t relax_ns = 0, walk_ns = 0; // read-only options "find_relax_ns" / "find_walk_ns": the sums of that call's find_relax spans
                                        // and of its find_claim + find_advance spans
     int64_t launches = 0;              // read-only option "find_launches": kernel launches of the latest call
@@ -504,8 +507,7 @@ bool can_arm(cfmm_ctx* c);
 void armed_cancel(cfmm_ctx* c);
 int armed_eval(cfmm_ctx* c, const double* v, bool* lost_out);      // single device or parent
 
-// abi_multi.cpp
-void shard_range(int64_t m, int d, int nd, int64_t& lo, int64_t& hi);
+// abi_multi.cpp (shard_range: shard_split.h)
 int multi_host_sweep(cfmm_ctx* c, const double* v, bool materialize);
 int multi_add(cfmm_ctx* c, int kind, int64_t m, const std::function<int(cfmm_ctx*, int64_t, int64_t)>& add, int n_coins = 2);
 int child_segment(const cfmm_ctx* c, int pseg, int d);

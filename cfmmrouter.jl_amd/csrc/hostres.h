@@ -1,5 +1,5 @@
 // hostres.h -- internal: the owners of what is not a device array -- PinnedBuf<T> (pinned host memory, mapped or plain),
-// Event, Stream -- and TradeStaging, which is built from them.  Host-side only.
+// Event, Stream -- and EventPairs and TradeStaging, which are built from them.  Host-side only.
 // The rule is devbuf.h's: an owner ALWAYS owns what it holds -- it releases in its destructor, a move hands the resource
 // over, nothing copies it -- and whoever takes `.host()` / `.dev()` / `.get()` never does.  Every create and destroy goes
 // through the functions below (abi_context.cpp, beside dev_alloc / dev_free), the only callers of hipHostMalloc /
@@ -8,6 +8,8 @@
 #pragma once
 
 #include "devbuf.h"
+
+#include <vector>
 
 namespace cfmm {
 
@@ -105,6 +107,35 @@ public:
     {
         const hipError_t e = create(flags);
         return e == hipSuccess ? CFMM_OK : fail(c, CFMM_ERR_HIP, "hipEventCreateWithFlags failed: %s", hipGetErrorString(e));
+    }
+};
+
+// The {start, stop} pairs that time the query entries' launches under option "time_kernels", created on demand and kept
+struct EventPairs {
+    std::vector<Event> ev;   // pair j: ev[2j], ev[2j + 1]
+    // pairs first .. k - 1 exist afterwards
+    int ensure(const cfmm_ctx* c, size_t k, size_t first = 0)
+    {
+        if (ev.size() < 2 * k) ev.resize(2 * k);
+        for (size_t i = 2 * first; i < 2 * k; ++i)
+            if (const int rc = ev[i].create(c, hipEventDefault)) return rc;
+        return CFMM_OK;
+    }
+    // what a launch takes: pair j, or nulls (an untimed launch) when timing is off
+    hipEvent_t start(size_t j, bool on = true) const { return on ? ev[2 * j].get() : nullptr; }
+    hipEvent_t stop(size_t j, bool on = true) const { return on ? ev[2 * j + 1].get() : nullptr; }
+    // the spans of pairs first .. first + k - 1, whose events have all been reached, summed, in nanoseconds
+    int elapsed_ns(const cfmm_ctx* c, size_t first, size_t k, int64_t& ns) const
+    {
+        double ms_sum = 0.0;
+        for (size_t j = first; j < first + k; ++j) {
+            float ms = 0.f;
+            const hipError_t e = hipEventElapsedTime(&ms, start(j), stop(j));
+            if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "reading a kernel's span from its events failed: %s", hipGetErrorString(e));
+            ms_sum += (double)ms;
+        }
+        ns = (int64_t)(ms_sum * 1e6);
+        return CFMM_OK;
     }
 };
 

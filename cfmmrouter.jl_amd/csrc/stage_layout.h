@@ -1,0 +1,95 @@
+// stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp,
+// abi_find_path.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
+// A layout is declared once, column by column; each column starts on a word and takes ceil(bytes / 8) words.  The entry grows
+// its buffer by words() and takes every host pointer from the column's handle, so the size and the addresses cannot disagree.
+// What crosses to the device in ONE copy is ONE column (the [2][count] coins, n_hops with the three int32 hop columns, ...).
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace cfmm {
+
+constexpr size_t words_of(size_t bytes) { return (bytes + 7) / 8; }
+
+template <class T>
+struct StageCol {
+    size_t off = 0, n = 0;   // first word, elements
+    T* in(unsigned long long* stage) const { return reinterpret_cast<T*>(stage + off); }
+};
+
+class StageLayout {
+    size_t words_ = 0;
+
+public:
+    template <class T>
+    StageCol<T> add(size_t n)
+    {
+        const StageCol<T> col{words_, n};
+        words_ += words_of(n * sizeof(T));
+        return col;
+    }
+    size_t words() const { return words_; }
+};
+
+// The entries' layouts for n queries / paths of at most H hops (nh = n * H).  Members are initialised in the order they are
+// declared, which is the order of the columns.  `table_bytes`: the entry's segment table (seg_view.h), first.
+struct QuoteStage {   // cfmm_quote / cfmm_quote_out
+    StageLayout l;
+    StageCol<double> amt;
+    StageCol<int32_t> coins;    // [2][n] coin_in, coin_out
+    StageCol<double> out;
+    StageCol<long long> idx;    // only where the call has one
+    QuoteStage(size_t n, bool has_idx) : amt(l.add<double>(n)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(n)), idx(l.add<long long>(has_idx ? n : 0)) {}
+};
+struct SwapStage {   // cfmm_swap / cfmm_swap_out, the swaps in wave order; price: UniV3 segments, limit / status: cfmm_swap_out
+    StageLayout l;
+    StageCol<double> amt;
+    StageCol<int32_t> coins;    // [2][n]
+    StageCol<double> out, price;
+    StageCol<long long> idx;
+    StageCol<double> limit;
+    StageCol<int32_t> status;
+    StageCol<int> left;         // [1] the window flag
+    SwapStage(size_t n, bool has_idx, bool univ3, bool has_limit, bool exact_out)
+        : amt(l.add<double>(n)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(n)), price(l.add<double>(univ3 ? n : 0)),
+          idx(l.add<long long>(has_idx ? n : 0)), limit(l.add<double>(has_limit ? n : 0)), status(l.add<int32_t>(exact_out ? n : 0)),
+          left(l.add<int>(1)) {}
+};
+struct PathStage {   // cfmm_quote_path / cfmm_quote_path_out (the _dev entries: the table alone, n = 0)
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> i32;      // [1 + 3*H][n] n_hops, hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [H][n]
+    StageCol<double> given, answer, hops;   // hops: [H][n], only where the call wants them
+    PathStage(size_t table_bytes, size_t n, size_t nh, bool want_hops)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), given(l.add<double>(n)),
+          answer(l.add<double>(n)), hops(l.add<double>(want_hops ? nh : 0)) {}
+};
+struct SwapPathStage {   // cfmm_swap_path / cfmm_swap_path_out, the paths in wave order; nrec: the table's records, one window flag each
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> i32;      // [1 + 3*H][n]
+    StageCol<long long> row;    // [H][n]
+    StageCol<double> amt;       // [2][n] the given amounts, the limits
+    StageCol<double> out, hops, price;
+    StageCol<int32_t> status;
+    StageCol<int> left;         // [nrec]
+    SwapPathStage(size_t table_bytes, size_t nrec, size_t n, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), amt(l.add<double>(2 * n)),
+          out(l.add<double>(n)), hops(l.add<double>(nh)), price(l.add<double>(nh)), status(l.add<int32_t>(n)), left(l.add<int>(nrec)) {}
+};
+struct FindStage {   // cfmm_find_path / cfmm_find_path_out
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> tok;      // [2][n] token_in, token_out
+    StageCol<double> amt, out;
+    StageCol<int32_t> ns;       // [2][n] n_hops, status
+    StageCol<int32_t> hop32;    // [3][H][n] hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [H][n]
+    FindStage(size_t table_bytes, size_t n, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), tok(l.add<int32_t>(2 * n)), amt(l.add<double>(n)), out(l.add<double>(n)),
+          ns(l.add<int32_t>(2 * n)), hop32(l.add<int32_t>(3 * nh)), row(l.add<long long>(nh)) {}
+};
+
+} // namespace cfmm
