@@ -25,6 +25,8 @@ MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
 PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = 0, 1, 2   # CFMM_PATH_*: Context.swap_path's status
 SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = 0, 1, 2, 3   # CFMM_SWAP_*: Context.swap_out's / swap_path_out's status
 FOUND, FOUND_NONE, FOUND_REPEATS = 0, 1, 2   # CFMM_FOUND*: Context.find_path's status
+SIZED, SIZED_NONE, SIZED_AT_LIMIT, SIZED_NAN = 0, 1, 2, 3   # CFMM_SIZED*: Context.size_path's status
+MAX_SIZE_ROUNDS = 16       # CFMM_MAX_SIZE_ROUNDS
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -67,7 +69,7 @@ class CFMMDeviceError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile libcfmm_amd.so for gfx950 with hipcc (csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h", "cfmm_amd_size_path.h")]
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -149,6 +151,9 @@ def lib():
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
+    L.cfmm_size_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
+                                 _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_size_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 4
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -690,6 +695,43 @@ class Context:
         self._check(getattr(self._L, entry)(self._h, n, H, ptr(tin), ptr(tout), ptr(amt), ptr(out), ptr(nh), ptr(seg), ptr(row), ptr(ci),
                                             ptr(co), ptr(st)))
         return out, nh, seg.T.copy(), row.T.copy(), ci.T.copy(), co.T.copy(), st
+
+    # -- path sizing (cfmm_size_path): the input of a path, at most max_in, that maximises its gain ----------
+    def size_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, max_in, value_in=None, value_out=None, rounds=5):
+        """How much to put into each path (cfmm_size_path): quote_path's path arguments, and per path the largest input
+        max_in[p] to consider.  Returns (amount_in, amount_out, gain, status), each [count]: the input that maximises
+        gain(x) = value_out[p] * quote_path(p, x) - value_in[p] * x (None = 1.0: "out minus in", the profit of a cycle), what
+        quote_path answers for it bit for bit, and that gain.  The contract is the bracketing search: `rounds` (1 ..
+        MAX_SIZE_ROUNDS) rounds of 64 trial sizes spread evenly over the bracket, which starts as [0, max_in] and becomes the
+        two neighbours of the best trial size (the smallest among equals; NaN loses).  For a concave gain -- every pool
+        family's quote is concave -- the bracket shrinks by 2/63 per round around the maximiser; 5 rounds reach the closed-form
+        optimum of two-pool cycles to about 1e-12 of its gain.  status[p] is SIZED, SIZED_AT_LIMIT (gain > 0 at amount_in == max_in
+        bit for bit: the limit binds), SIZED_NONE (no trial size gains: three 0.0) or SIZED_NAN.  Every hop is quoted against the
+        pool as it stands.  Scalars broadcast.  Read-only.  Everything is checked before anything runs (ArgumentError names
+        the path and the hop)."""
+        nh0 = np.ascontiguousarray(n_hops, dtype=np.int32).reshape(-1)
+        n = nh0.size
+        try:
+            lim = np.ascontiguousarray(np.broadcast_to(f64(max_in).reshape(-1), (n,)))
+            vi, vo = (None if v is None else np.ascontiguousarray(np.broadcast_to(f64(v).reshape(-1), (n,))) for v in (value_in, value_out))
+        except ValueError:
+            raise ArgumentError("max_in, value_in and value_out must be scalars or have one entry per path") from None
+        nh, seg, row, ci, co = self._path_columns(nh0, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        max_hops = max(1, int(seg.shape[0]))
+        x, y, g, st = np.empty(n), np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+        self._check(self._L.cfmm_size_path(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(lim), ptr(vi), ptr(vo),
+                                           int(rounds), ptr(x), ptr(y), ptr(g), ptr(st)))
+        return x, y, g, st
+
+    def size_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
+                      d_hop_coin_out: int, d_max_in: int, d_value_in: int, d_value_out: int, rounds: int, d_amount_in: int,
+                      d_amount_out: int, d_gain: int, d_status: int):
+        """cfmm_size_path_dev on device addresses (as quote_path_dev: the hop arrays hop-major [max_hops][count]; d_value_in /
+        d_value_out 0 = NULL = 1.0; float64 amounts and gains, int32 status): asynchronous on the context's stream, unchecked
+        -- a bad path, hop, limit or value gives that path SIZED_NAN and NaN outputs, nothing is read out of bounds."""
+        self._check(self._L.cfmm_size_path_dev(self._h, int(count), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out, d_max_in, d_value_in, d_value_out)), int(rounds),
+            *(C.c_void_p(p or None) for p in (d_amount_in, d_amount_out, d_gain, d_status))))
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
                        d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):

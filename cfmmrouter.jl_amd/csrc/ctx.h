@@ -25,7 +25,9 @@
 //                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
 //   abi_find_path.cpp the best swap walk between two tokens, found on the device (cfmm_find_path; find_checks.h: the HIP-free
 //                     checks and the chunking rule)
-//   seg_view.h        what those five share, on top of this header: a segment as their kernels and their checks see it
+//   abi_size_path.cpp the input of a path that maximises its gain (cfmm_size_path; size_checks.h: the HIP-free checks, size_grid.h:
+//                     the search's arithmetic, shared with the kernel)
+//   seg_view.h        what those six share, on top of this header: a segment as their kernels and their checks see it
 //   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
 //   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
@@ -323,6 +325,28 @@ struct FindScratch {
     int64_t layer_ns[3][CFMM_MAX_PATH_HOPS] = {};
 };
 
+// cfmm_size_path (abi_size_path.cpp, size_path_kernels.h): the device copies of one call's paths, limits, values and answers,
+// the segment table (sweep.h PathSeg, rebuilt and uploaded on every call, for abi_quote_path.cpp's reason) and ONE pinned
+// staging buffer for all of them -- proportional to count x max_hops (and the number of segments), never to the pools.
+// `done`, recorded behind each call's kernel, guards the staging and the table against the call before (cfmm_size_path_dev does
+// not wait).  A multi-device parent uses none of the device arrays: its search runs on the host (size_grid.h) over cfmm_quote_path.
+struct SizeScratch {
+    DevBuf<PathSeg> table;             // [segments]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> hop_row;         // [max_hops][count]
+    DevBuf<double> in;                 // [3][count] max_amount_in, value_in, value_out
+    DevBuf<double> out;                // [3][count] amount_in, amount_out, gain
+    DevBuf<int32_t> status;            // [count]
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SizeStage
+    Event done;                        // behind the latest call's kernel
+    bool in_flight = false;
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // read-only option "size_ns": that kernel's span (a parent: the sum of its rounds' "quote_ns")
+    bool dev_timed = false;            // the latest timed call was cfmm_size_path_dev: its span is read when asked for
+    int64_t launches = 0;              // read-only option "size_launches": kernel launches of the latest call (a parent: its
+                                       // cfmm_quote_path calls)
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -434,6 +458,8 @@ struct cfmm_ctx {
     int64_t opt_find_lds = 1;      // 1: cfmm_find_path's layer launches fold their candidates into a per-block LDS copy of the layer rows
                                    //    first, where n_tokens lets one fit (find_path_kernels.h find_relax<., true>); 0: every candidate
                                    //    goes to global memory (the A/B of scripts/find_path_times.py; the same bits either way)
+    int64_t opt_size_max_blocks = cfmm::kSizeMaxBlocks; // cfmm_size_path: the most blocks of its launch (>= 1; its wavefronts stride over the
+                                   //    paths, the same bits at any value: a measurement and test switch)
     int64_t opt_univ3_heads = 1;   // 1: multi-tick UniV3 walks decide their first four list ticks from the per-pool float threshold heads
     int64_t opt_lean_kernels = 1;  // 1: a launch in the default configuration takes the lean form of its kernel (launch_plan.h lean_launch:
                                    //    the same bits with fewer instructions per tile); 0: always the general kernels (A/B, tests)
@@ -454,6 +480,7 @@ struct cfmm_ctx {
     cfmm::SwapScratch swap;
     cfmm::SwapPathScratch swap_path;
     cfmm::FindScratch find;
+    cfmm::SizeScratch size;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
@@ -522,6 +549,9 @@ int quote_ns(cfmm_ctx* c, int64_t* value);
 int check_quote_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t n_segs);
 int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, int kind, int64_t m, int nc, int64_t count,
                         const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out, const double* given, const double* answer);
+
+// abi_size_path.cpp
+int size_ns(cfmm_ctx* c, int64_t* value);
 
 // abi_update.cpp
 // cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not

@@ -543,3 +543,7 @@ __global__ __launch_bounds__(BLOCK) void find_out_finish(FindArgs a)
 }
 
 } // namespace cfmm
+
+// The header that comes LAST in sweep_kernels.hip stays this one (tests/test_find_path_cpu.py pins that, so that new templates are
+// emitted behind every kernel the translation unit had); what came after it is included from here, behind everything above.
+#include "size_path_kernels.h"

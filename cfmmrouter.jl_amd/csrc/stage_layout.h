@@ -1,5 +1,5 @@
 // stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp,
-// abi_find_path.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
+// abi_find_path.cpp, abi_size_path.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
 // A layout is declared once, column by column; each column starts on a word and takes ceil(bytes / 8) words.  The entry grows
 // its buffer by words() and takes every host pointer from the column's handle, so the size and the addresses cannot disagree.
 // What crosses to the device in ONE copy is ONE column (the [2][count] coins, n_hops with the three int32 hop columns, ...).
@@ -65,6 +65,18 @@ struct PathStage {   // cfmm_quote_path / cfmm_quote_path_out (the _dev entries:
     PathStage(size_t table_bytes, size_t n, size_t nh, bool want_hops)
         : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), given(l.add<double>(n)),
           answer(l.add<double>(n)), hops(l.add<double>(want_hops ? nh : 0)) {}
+};
+struct SizeStage {   // cfmm_size_path (cfmm_size_path_dev: the table alone, n = 0)
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> i32;      // [1 + 3*H][n] n_hops, hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [H][n]
+    StageCol<double> in;        // [3][n] max_amount_in, value_in, value_out (a value the call does not give: unused)
+    StageCol<double> out;       // [3][n] amount_in, amount_out, gain
+    StageCol<int32_t> status;   // [n]
+    SizeStage(size_t table_bytes, size_t n, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), in(l.add<double>(3 * n)),
+          out(l.add<double>(3 * n)), status(l.add<int32_t>(n)) {}
 };
 struct SwapPathStage {   // cfmm_swap_path / cfmm_swap_path_out, the paths in wave order; nrec: the table's records, one window flag each
     StageLayout l;

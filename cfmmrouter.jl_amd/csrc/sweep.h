@@ -494,6 +494,23 @@ struct PathArgs {
 // exact_out picks quote_path_out_kernel.  e0, e1: both set = the launch is timed by the command processor.
 hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_size_path (size_path_kernels.h, abi_size_path.cpp): the input of a path that maximises its gain, one WAVEFRONT per
+// path and one lane per trial size.  The paths are a PathArgs as cfmm_quote_path's kernel takes it -- p.given is
+// max_amount_in, p.answer receives amount_in, p.hops is unused (null) -- plus the arrays of the search.
+struct SizeArgs {
+    PathArgs p;
+    const double* value_in;      // [count], or null: 1.0
+    const double* value_out;     // [count], or null: 1.0
+    int32_t rounds;              // 1 .. CFMM_MAX_SIZE_ROUNDS
+    double* amount_out;          // [count]
+    double* gain;                // [count]
+    int32_t* status;             // [count] CFMM_SIZED*
+};
+constexpr int kSizeBlock = 256;                                  // four wavefronts = four paths per block
+constexpr int kSizeMaxBlocks = kResidentThreads / kSizeBlock;    // default of option "size_max_blocks": one machine of resident wavefronts
+// max_blocks >= 1 caps the grid (the wavefronts stride over the paths).  e0, e1: both set = the launch is timed.
+hipError_t launch_size_path(const SizeArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // cfmm_swap_path (swap_path_kernels.h, abi_swap_path.cpp): exact-input paths that MOVE their pools, all or nothing, one lane per
 // path of ONE WAVE -- paths that share no pool (the host numbers the waves: swap_path_waves.h).  The kernel reads a table of
 // its own: what PathSeg holds (the quotes' view, unchanged), the segment's arrays again as writable pointers, what

@@ -48,6 +48,7 @@
 //                        swap_path_out_kernel (cfmm_swap_path_out: quote_path_out_kernel's walk, then the same)
 //   swap_out_kernels.h   swap_out_kernel (cfmm_swap_out: quote_out_one's answer, then the pool's new state, with a status per swap)
 //   find_path_kernels.h  find_relax and the walk back (cfmm_find_path: the best walk between two tokens, a layer per launch, one lane per pool)
+//   size_path_kernels.h  size_path_kernel (cfmm_size_path: the input that maximises a path's gain, one wavefront per path, one lane per trial size)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -66,7 +67,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -476,6 +477,19 @@ hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEv
         lds_bytes = (size_t)a.group * (size_t)a.n_tokens * sizeof(unsigned long long);
     }
     return launch_k(kernel, grid, dim3(kFindBlock), lds_bytes, s, e0, e1, args);
+}
+
+// cfmm_size_path: one wavefront per path, kSizeBlock / 64 paths per block, at most max_blocks blocks.  (Behind every other
+// launcher: the kernel is instantiated last, so every kernel before it keeps its function number and labels.)
+hipError_t launch_size_path(const SizeArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.p.count <= 0 || a.p.nseg <= 0 || a.p.max_hops < 1 || a.p.max_hops > CFMM_MAX_PATH_HOPS || a.rounds < 1 ||
+        a.rounds > CFMM_MAX_SIZE_ROUNDS || max_blocks < 1 || !a.p.answer || !a.amount_out || !a.gain || !a.status)
+        return hipErrorInvalidValue;
+    constexpr int64_t per_block = kSizeBlock / CFMM_SIZE_POINTS;
+    const int64_t blocks = std::min<int64_t>({(a.p.count + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
+    void* args[] = {const_cast<SizeArgs*>(&a)};
+    return launch_k(reinterpret_cast<const void*>(&size_path_kernel<kSizeBlock>), dim3((unsigned)blocks), dim3(kSizeBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm

@@ -319,4 +319,25 @@ end
     @test none[4] == [1, 1] && none[1] == [0.0, Inf]                           # nothing to buy; more than any pool holds
     @test_throws ArgumentError find_paths_out(r, [9], [1], [1.0])
 end
+
+@testset "size_paths: the input of a cycle that maximises its gain, then executed" begin
+    pools = [ProductTwoCoin([1.00e5, 2.00e5], 0.997, [1, 2]), ProductTwoCoin([2.00e5, 1.04e5], 0.997, [2, 3]),
+             ProductTwoCoin([1.0e5, 1.0e5], 0.9995, [3, 1])]
+    r = AMDRouter(LinearNonnegative(ones(3)), pools, 3)
+    cycle, toks = [1, 2, 3], [1, 2, 3, 1]
+    x, y, g, st = size_paths(r, [cycle, cycle], [toks, toks], [5000.0, 10.0])
+    @test st == [0, 2] && x[2] == 10.0 && 0 < x[1] < 5000.0                  # sized inside the limit; the small limit binds
+    @test quote_paths(r, [cycle, cycle], [toks, toks], x) == y               # the bits of quoting the answer
+    @test g == y .- x && all(g .> 0)
+    sizes = 50.0 .* 1.25 .^ (0:19)
+    ladder = quote_paths(r, fill(cycle, 20), fill(toks, 20), sizes) .- sizes
+    @test g[1] >= maximum(ladder)                                            # at least the best of a hand-made ladder
+    got, applied = swap_paths!(r, [cycle], [toks], [x[1]]; min_out=[x[1]])
+    @test applied == [0] && got[1] == y[1]
+    again = size_paths(r, [cycle], [toks], [5000.0])
+    @test again[4][1] == 1 || again[3][1] < 1e-3 * g[1]                      # the market it left: nothing, or next to nothing
+    @test size_paths(r, [cycle], [toks], [100.0]; value_in=[2.0])[4] == [1]  # the input valued at twice the output: no size gains
+    @test_throws ArgumentError size_paths(r, [cycle], [toks], [100.0]; rounds=17)
+    @test_throws ArgumentError size_paths(r, [[1, 1]], [[1, 2, 1]], [100.0])
+end
 end
