@@ -2,16 +2,17 @@
 // PATH, grid-stride over the paths.  Per hop the lane reads its 20 bytes of hop (segment, row, two coins; hop-major arrays,
 // so a wavefront reads each as one stream), the PathSeg of that segment from the table in device memory (sweep.h), and
 // evaluates the hop with the body of the single-pool kernels -- quote_one<KIND> / quote_out_one<KIND> of quote_kernels.h,
-// picked by a switch on the segment's kind -- so a path's amounts carry the bits of chaining cfmm_quote / cfmm_quote_out hop
+// picked by with_kind (kind_switch.h) on the segment's kind -- so a path's amounts carry the bits of chaining cfmm_quote / cfmm_quote_out hop
 // by hop.  Every hop is quoted against the pool AS IT STANDS: no state advances between hops, a pool visited twice is quoted
 // twice from the same reserves.  No LDS, no atomics, no state; lanes whose hops land in different kinds serialise.
 // Nothing is trusted (cfmm_quote_path_dev takes unchecked device arrays): an n_hops outside 1 .. max_hops makes the whole
 // path NaN with no hop evaluated; a hop whose segment, row or coins are out of range, or whose amount is negative or not
-// finite, is clamped BEFORE any read and poisoned after (quote_kernel's rule), and the NaN then travels through the
+// finite, is clamped BEFORE any read and poisoned after (query_read.h read_hop), and the NaN then travels through the
 // remaining hops by that same rule.  The kernels never read out of bounds.
 #pragma once
 
 #include "../../include/cfmm_amd.h"
+#include "kind_switch.h"
 #include "quote_kernels.h"
 
 namespace cfmm {
@@ -51,36 +52,15 @@ __device__ __forceinline__ double path_hop(const PathSeg& s, int64_t m, int64_t 
 }
 
 // One hop: hop `at` (= k*count + p) of the arrays, the amount `amt` entering it (exact input) or wanted from it (exact
-// output).  Clamp, read, evaluate, poison.
+// output).  Read by the rule of query_read.h, evaluated by the kind's body, poisoned.
 template <bool OUT>
 __device__ __forceinline__ double path_step(const PathArgs& a, int64_t at, double amt)
 {
-    int seg = a.hop_seg[at];
-    long long row = a.hop_row[at];
-    int ci = a.hop_coin_in[at];
-    int co = a.hop_coin_out[at];
-    bool ok = seg >= 0 && seg < a.nseg;
-    seg = seg < 0 ? 0 : (seg >= a.nseg ? a.nseg - 1 : seg);
-    const PathSeg& s = a.segs[seg];
-    const int kind = s.kind;
-    const int nc = s.n_coins;
-    const int64_t m = s.m;
-    ok = ok && row >= 0 && row < m && ci >= 0 && ci < nc && co >= 0 && co < nc && ci != co && amt >= 0.0 && amt < __builtin_inf();
-    // (a segment without pools has kind -1: no body below runs, so the row clamped to -1 is never used)
-    row = row < 0 ? 0 : (row >= m ? m - 1 : row);
-    ci = ci < 0 ? 0 : (ci >= nc ? nc - 1 : ci);
-    co = co < 0 ? 0 : (co >= nc ? nc - 1 : co);
-    const double x = ok ? amt : 0.0;
+    const auto h = read_hop(a, at, amt);
+    const PathSeg& s = h.seg;
+    bool ok = h.ok;
     double r;
-    switch (kind) {
-    case CFMM_KIND_PRODUCT: r = path_hop<CFMM_KIND_PRODUCT, OUT>(s, m, row, ci, co, x); break;
-    case CFMM_KIND_GEOMEAN: r = path_hop<CFMM_KIND_GEOMEAN, OUT>(s, m, row, ci, co, x); break;
-    case CFMM_KIND_UNIV3: r = path_hop<CFMM_KIND_UNIV3, OUT>(s, m, row, ci, co, x); break;
-    case CFMM_KIND_WEIGHTED: r = path_hop<CFMM_KIND_WEIGHTED, OUT>(s, m, row, ci, co, x); break;
-    case CFMM_KIND_CURVE: r = path_hop<CFMM_KIND_CURVE, OUT>(s, m, row, ci, co, x); break;
-    case CFMM_KIND_SOLIDLY: r = path_hop<CFMM_KIND_SOLIDLY, OUT>(s, m, row, ci, co, x); break;
-    default: r = 0.0; ok = false; break;
-    }
+    with_kind(h.kind, [&](auto K) { r = path_hop<decltype(K)::value, OUT>(s, h.m, h.row, h.ci, h.co, h.amt); }, [&] { r = 0.0; ok = false; });
     return ok ? r : __builtin_nan("");
 }
 

@@ -17,8 +17,8 @@
 // boundary, in·γ may round to either side of the matching Σδmax and the two then name neighbouring records.  That is
 // harmless: the price is continuous across the boundary -- the far edge of record e (d_t = δmax_e) and the near edge of
 // record e+1 (d_t = 0) are the same tick price up to the rounding of their prepared constants.
-// The host has checked every query; the clamp-then-poison rule of quote_kernel stays, so that nothing is ever read or
-// written out of bounds.
+// The host has checked every query; the query is still read by the rule of query_read.h (read_query), so that nothing is
+// ever read or written out of bounds.  The new state is swap_pool.h's: swap_move computes and tests it, swap_store writes it.
 #pragma once
 
 #include "quote_kernels.h"
@@ -31,28 +31,22 @@ __global__ __launch_bounds__(kQuoteBlock) void swap_out_kernel(SwapOutArgs so, U
 {
     const SwapArgs& s = so.s;
     const QuoteArgs& a = s.q;
+    const SwapView v = swap_view(s, n);
     const double nan = __builtin_nan("");
     const int64_t step = (int64_t)gridDim.x * kQuoteBlock;
     for (int64_t q = (int64_t)blockIdx.x * kQuoteBlock + threadIdx.x; q < a.count; q += step) {
-        long long row = a.idx ? a.idx[q] : (long long)q;
-        int ci = a.coin_in[q];
-        int co = a.coin_out ? a.coin_out[q] : 1 - ci;
-        const double want = a.amount_in[q];   // the wanted output
-        const bool ok = row >= 0 && row < a.m && ci >= 0 && ci < a.n_coins && co >= 0 && co < a.n_coins && ci != co &&
-                        want >= 0.0 && want < __builtin_inf();
-        row = row < 0 ? 0 : (row >= a.m ? a.m - 1 : row);
-        ci = ci < 0 ? 0 : (ci >= a.n_coins ? a.n_coins - 1 : ci);
-        co = co < 0 ? 0 : (co >= a.n_coins ? a.n_coins - 1 : co);
-        const double in = quote_out_one<KIND>(a, u, n, row, ci, co, ok ? want : 0.0);   // the input to tender
+        const Query r = read_query(a, q);
+        const double want = r.amt;   // the wanted output
+        const double in = quote_out_one<KIND>(a, u, n, r.row, r.ci, r.co, r.ok ? want : 0.0);   // the input to tender
         const bool within = !so.max_in || in <= so.max_in[q];
-        if (!ok || in == __builtin_inf()) {
-            a.amount_out[q] = ok ? in : nan;
-            so.status[q] = ok ? kSwapUnobtainable : kSwapRefused;
+        if (!r.ok || in == __builtin_inf()) {
+            a.amount_out[q] = r.ok ? in : nan;
+            so.status[q] = r.ok ? kSwapUnobtainable : kSwapRefused;
             continue;
         }
         if constexpr (KIND == CFMM_KIND_UNIV3) {
-            const double P = swap_univ3_price(u.pg[row].x, u.cur_a[row], u.cur_b[row], u.cur_c[row], u.walk[row], u.ticks, u.pg[row].y,
-                                              ci, in);
+            const double P = swap_univ3_price(u.pg[r.row].x, u.cur_a[r.row], u.cur_b[r.row], u.cur_c[r.row], u.walk[r.row], u.ticks,
+                                              u.pg[r.row].y, r.ci, in);
             const bool valid = swap_finite_pos(P);
             const int32_t st = !valid ? kSwapRefused : (within ? kSwapApplied : kSwapOverLimit);
             s.price[q] = st == kSwapApplied ? P : nan;
@@ -64,50 +58,15 @@ __global__ __launch_bounds__(kQuoteBlock) void swap_out_kernel(SwapOutArgs so, U
                 so.status[q] = kSwapApplied;
                 continue;
             }
-            if constexpr (KIND == CFMM_KIND_PRODUCT || KIND == CFMM_KIND_SOLIDLY || KIND == CFMM_KIND_GEOMEAN) {
-                const double2 R = a.R[row];
-                const double g = a.gamma[row];
-                const double2 rn = swap_reserves(ci == 0 ? R.x : R.y, co == 0 ? R.x : R.y, g, in, want);
-                if (!swap_reserves_valid(rn, KIND == CFMM_KIND_SOLIDLY)) {
-                    a.amount_out[q] = nan;
-                    so.status[q] = kSwapRefused;
-                    continue;
-                }
-                a.amount_out[q] = in;
-                so.status[q] = within ? kSwapApplied : kSwapOverLimit;
-                if (!within) continue;
-                const double2 Rn = ci == 0 ? rn : make_double2(rn.y, rn.x);
-                s.R[row] = Rn;
-                if (s.left_window && !(swap_in_window(Rn.x) && swap_in_window(Rn.y))) *s.left_window = 1;
-                if constexpr (KIND == CFMM_KIND_GEOMEAN) s.Q[row] = swap_geomean_q(g, s.eta[row], Rn.x, Rn.y);
-            } else {
-                const int64_t m = a.m;
-                const int64_t ji = (int64_t)ci * m + row, jo = (int64_t)co * m + row;
-                const double2 rn = swap_reserves(n.R[ji], n.R[jo], n.glg[row].x, in, want);
-                bool valid = swap_reserves_valid(rn, false);
-                double qi, qo;
-                if constexpr (KIND == CFMM_KIND_WEIGHTED) {
-                    qi = swap_weighted_q(rn.x, n.par[ji]);
-                    qo = swap_weighted_q(rn.y, n.par[jo]);
-                } else {
-                    qi = swap_curve_q(rn.x);
-                    qo = swap_curve_q(rn.y);
-                    const double2 ab = reinterpret_cast<const double2*>(n.par)[row];   // {α, log β}
-                    if (valid && ab.x > 0.0) valid = swap_curve_in_range(ab.y, n.q + row, m, n.n_coins, ci, qi, co, qo);
-                }
-                if (!valid) {
-                    a.amount_out[q] = nan;
-                    so.status[q] = kSwapRefused;
-                    continue;
-                }
-                a.amount_out[q] = in;
-                so.status[q] = within ? kSwapApplied : kSwapOverLimit;
-                if (!within) continue;
-                s.ncR[ji] = rn.x;
-                s.ncR[jo] = rn.y;
-                s.ncq[ji] = qi;
-                s.ncq[jo] = qo;
+            const SwapMove mv = swap_move<KIND>(v, a.m, r.row, r.ci, r.co, in, want);
+            if (!mv.valid) {
+                a.amount_out[q] = nan;
+                so.status[q] = kSwapRefused;
+                continue;
             }
+            a.amount_out[q] = in;
+            so.status[q] = within ? kSwapApplied : kSwapOverLimit;
+            if (within) swap_store<KIND>(v, a.m, r.row, r.ci, r.co, mv);
         }
     }
 }

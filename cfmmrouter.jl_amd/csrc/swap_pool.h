@@ -1,5 +1,6 @@
-// swap_pool.h -- the state an exact-input swap leaves behind, one function per pool kind.  Host + device code: swap_kernel
-// (swap_kernels.h) runs them one lane per swap; tests/native/swap_host.cpp builds them for the CPU.
+// swap_pool.h -- the state a swap leaves behind: one function per piece and pool kind, and at the end swap_move / swap_store,
+// which put the pieces together for every moving kernel (swap_kernel, swap_out_kernel, both swap-path kernels).  Host + device
+// code: the kernels run them one lane per swap; tests/native/swap_host.cpp builds the pieces for the CPU.
 //
 // The amount that comes out is quote_pool.h's, unchanged: cfmm_swap's answer IS cfmm_quote's answer on the pool as it stands,
 // by construction.  What is added here is the move R <- R + γΔ − Λ with Δ = a·e_in, Λ = out·e_out (src/cfmms.jl:26-31, the
@@ -16,6 +17,7 @@
 //   UniV3           below
 #pragma once
 
+#include "../../include/cfmm_amd.h"
 #include "quote_pool.h"
 
 namespace cfmm {
@@ -124,6 +126,93 @@ __host__ __device__ inline double swap_univ3_price(double cp, double2 cur_a, dou
     }
     const double sp = ss + dt;
     return in == 0 ? kk / (sp * sp) : (sp * sp) / kk;
+}
+
+// ---- the state after a swap, tested and stored: the one place where the pieces above are put together ----
+// What swap_move reads and swap_store writes of a reserve-kind segment: the arrays the new state is computed from, as the quotes see
+// them, and the same arrays again, writable.  Filled from a launch's own arguments (swap_kernel, swap_out_kernel) or from a
+// record of the swap-path table.
+struct SwapView {
+    const double2* R;            // two-coin kinds: reserves, fees
+    const double* gamma;
+    const double* nR;            // weighted / Curve: the four columns of NCoinPools the quotes read, and the coin count
+    const double* nq;
+    const double2* nglg;
+    const double* npar;
+    int n_coins;
+    double2* R_new;              // two-coin kinds: [m] reserves
+    double2* Q_new;              // GeometricMean: [m] {Q1, Q2}, and η
+    const double* eta;
+    double* nR_new;              // weighted / Curve: [n_coins][m]
+    double* nq_new;
+    int* left_window;            // <- 1 when a new reserve lies outside [2^-kFastExp, 2^kFastExp], or null
+};
+__host__ __device__ __forceinline__ SwapView swap_view(const SwapArgs& s, const NCoinPools& n)
+{
+    return SwapView{s.q.R, s.q.gamma, n.R, n.q, n.glg, n.par, n.n_coins, s.R, s.Q, s.eta, s.ncR, s.ncq, s.left_window};
+}
+__host__ __device__ __forceinline__ SwapView swap_view(const SwapPathSeg& t)
+{
+    return SwapView{t.s.R, t.s.gamma, t.s.nR, t.s.nq, t.s.nglg, t.s.npar, t.s.n_coins, t.R, t.Q, t.eta, t.nR, t.nq, t.left_window};
+}
+
+// The state pool `row` of a reserve-kind segment of m pools is left in by a swap of amt > 0 of coin ci for out of coin co:
+// swap_move computes it and, with TEST, says whether cfmm_pools_set_* accepts it (the refusal conditions of every moving
+// entry); swap_store writes one that was accepted.  TEST false is for a caller that only stores (pass 2 of the path kernels,
+// whose pass 1 saw the test pass on the same values): no test is evaluated, Curve's range test with its loads included, and
+// `valid` is true.
+struct SwapMove {
+    double2 rn;                  // {R_in', R_out'}
+    double g;                    // the fee it was computed with
+    double qi, qo;               // weighted / Curve: the two coins' refreshed constants
+    bool valid;
+};
+template <int KIND, bool TEST = true>
+__host__ __device__ __forceinline__ SwapMove swap_move(const SwapView& t, int64_t m, int64_t row, int ci, int co, double amt, double out)
+{
+    SwapMove mv;
+    mv.valid = true;
+    if constexpr (KIND == CFMM_KIND_PRODUCT || KIND == CFMM_KIND_SOLIDLY || KIND == CFMM_KIND_GEOMEAN) {
+        const double2 R = t.R[row];
+        mv.g = t.gamma[row];
+        mv.rn = swap_reserves(ci == 0 ? R.x : R.y, co == 0 ? R.x : R.y, mv.g, amt, out);
+        mv.qi = mv.qo = 0.0;
+        if constexpr (TEST) mv.valid = swap_reserves_valid(mv.rn, KIND == CFMM_KIND_SOLIDLY);
+    } else {
+        static_assert(KIND == CFMM_KIND_WEIGHTED || KIND == CFMM_KIND_CURVE, "UniV3 has no state the kernel writes");
+        const int64_t ji = (int64_t)ci * m + row, jo = (int64_t)co * m + row;
+        mv.g = t.nglg[row].x;
+        mv.rn = swap_reserves(t.nR[ji], t.nR[jo], mv.g, amt, out);
+        if constexpr (TEST) mv.valid = swap_reserves_valid(mv.rn, false);
+        if constexpr (KIND == CFMM_KIND_WEIGHTED) {
+            mv.qi = swap_weighted_q(mv.rn.x, t.npar[ji]);
+            mv.qo = swap_weighted_q(mv.rn.y, t.npar[jo]);
+        } else {
+            mv.qi = swap_curve_q(mv.rn.x);
+            mv.qo = swap_curve_q(mv.rn.y);
+            if constexpr (TEST) {
+                const double2 ab = reinterpret_cast<const double2*>(t.npar)[row];   // {α, log β}
+                if (mv.valid && ab.x > 0.0) mv.valid = swap_curve_in_range(ab.y, t.nq + row, m, t.n_coins, ci, mv.qi, co, mv.qo);
+            }
+        }
+    }
+    return mv;
+}
+template <int KIND>
+__host__ __device__ __forceinline__ void swap_store(const SwapView& t, int64_t m, int64_t row, int ci, int co, const SwapMove& mv)
+{
+    if constexpr (KIND == CFMM_KIND_PRODUCT || KIND == CFMM_KIND_SOLIDLY || KIND == CFMM_KIND_GEOMEAN) {
+        const double2 Rn = ci == 0 ? mv.rn : make_double2(mv.rn.y, mv.rn.x);
+        t.R_new[row] = Rn;
+        if (t.left_window && !(swap_in_window(Rn.x) && swap_in_window(Rn.y))) *t.left_window = 1;
+        if constexpr (KIND == CFMM_KIND_GEOMEAN) t.Q_new[row] = swap_geomean_q(mv.g, t.eta[row], Rn.x, Rn.y);
+    } else {
+        const int64_t ji = (int64_t)ci * m + row, jo = (int64_t)co * m + row;
+        t.nR_new[ji] = mv.rn.x;
+        t.nR_new[jo] = mv.rn.y;
+        t.nq_new[ji] = mv.qi;
+        t.nq_new[jo] = mv.qo;
+    }
 }
 
 } // namespace cfmm

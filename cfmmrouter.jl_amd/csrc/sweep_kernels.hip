@@ -344,16 +344,9 @@ static hipError_t launch_quote_k(const void* kernel, const QuoteArgs& a, const U
 hipError_t launch_quote(int kind, const QuoteArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (a.count <= 0 || a.m <= 0) return hipErrorInvalidValue;
-    const void* kernel;
-    switch (kind) {
-    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_PRODUCT>); break;
-    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_GEOMEAN>); break;
-    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_UNIV3>); break;
-    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_WEIGHTED>); break;
-    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_CURVE>); break;
-    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&quote_kernel<CFMM_KIND_SOLIDLY>); break;
-    default: return hipErrorInvalidDeviceFunction;   // no such kernel: there is no falling through to another one
-    }
+    const void* kernel = nullptr;   // no such kernel: there is no falling through to another one
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&quote_kernel<decltype(K)::value>); }, [] {});
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     return launch_quote_k(kernel, a, u, n, s, e0, e1);
 }
 
@@ -361,16 +354,9 @@ hipError_t launch_quote_out(int kind, const QuoteArgs& a, const UniV3Pools& u, c
                             hipEvent_t e1)
 {
     if (a.count <= 0 || a.m <= 0) return hipErrorInvalidValue;
-    const void* kernel;
-    switch (kind) {
-    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_PRODUCT>); break;
-    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_GEOMEAN>); break;
-    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_UNIV3>); break;
-    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_WEIGHTED>); break;
-    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_CURVE>); break;
-    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&quote_out_kernel<CFMM_KIND_SOLIDLY>); break;
-    default: return hipErrorInvalidDeviceFunction;   // no such kernel
-    }
+    const void* kernel = nullptr;   // no such kernel: there is no falling through to another one
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&quote_out_kernel<decltype(K)::value>); }, [] {});
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     return launch_quote_k(kernel, a, u, n, s, e0, e1);
 }
 
@@ -387,16 +373,9 @@ hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, h
 hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (a.q.count <= 0 || a.q.m <= 0) return hipErrorInvalidValue;
-    const void* kernel;
-    switch (kind) {
-    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_PRODUCT>); break;
-    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_GEOMEAN>); break;
-    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_UNIV3>); break;
-    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_WEIGHTED>); break;
-    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_CURVE>); break;
-    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&swap_kernel<CFMM_KIND_SOLIDLY>); break;
-    default: return hipErrorInvalidDeviceFunction;   // no such kernel
-    }
+    const void* kernel = nullptr;   // no such kernel: there is no falling through to another one
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&swap_kernel<decltype(K)::value>); }, [] {});
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     void* args[] = {const_cast<SwapArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
     return launch_quote_grid(kernel, a.q.count, args, s, e0, e1);
 }
@@ -414,16 +393,9 @@ hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0,
 hipError_t launch_swap_out(int kind, const SwapOutArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (a.s.q.count <= 0 || a.s.q.m <= 0 || !a.status) return hipErrorInvalidValue;
-    const void* kernel;
-    switch (kind) {
-    case CFMM_KIND_PRODUCT: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_PRODUCT>); break;
-    case CFMM_KIND_GEOMEAN: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_GEOMEAN>); break;
-    case CFMM_KIND_UNIV3: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_UNIV3>); break;
-    case CFMM_KIND_WEIGHTED: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_WEIGHTED>); break;
-    case CFMM_KIND_CURVE: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_CURVE>); break;
-    case CFMM_KIND_SOLIDLY: kernel = reinterpret_cast<const void*>(&swap_out_kernel<CFMM_KIND_SOLIDLY>); break;
-    default: return hipErrorInvalidDeviceFunction;   // no such kernel
-    }
+    const void* kernel = nullptr;   // no such kernel: there is no falling through to another one
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&swap_out_kernel<decltype(K)::value>); }, [] {});
+    if (!kernel) return hipErrorInvalidDeviceFunction;
     void* args[] = {const_cast<SwapOutArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
     return launch_quote_grid(kernel, a.s.q.count, args, s, e0, e1);
 }

@@ -2,6 +2,7 @@
 // tests/test_query_host_cpu.py: a stand-alone program, built with the address and undefined-behaviour sanitizers.  Not linked
 // against the HIP runtime: the raw create / destroy calls of the owners are defined HERE over malloc / free (a freed "device
 // array" is never handed out again, so a regrown DevBuf always shows a new address).  Nothing touches a GPU.
+#include "kind_switch.h"
 #include "seg_view.h"
 #include "shard_split.h"
 #include "stage_layout.h"
@@ -288,9 +289,28 @@ int test_event_pairs()
     return 0;
 }
 
+// ---- the kind dispatch ----------------------------------------------------------------------------------------------------
+
+// every kind reaches f exactly once, with its own constant; a number that names no kind reaches `none`
+int test_with_kind()
+{
+    const int kinds[] = {CFMM_KIND_PRODUCT, CFMM_KIND_GEOMEAN, CFMM_KIND_UNIV3, CFMM_KIND_WEIGHTED, CFMM_KIND_CURVE, CFMM_KIND_SOLIDLY};
+    for (int kind : kinds) {
+        int calls = 0, seen = -99, nones = 0;
+        with_kind(kind, [&](auto K) { ++calls; seen = decltype(K)::value; }, [&] { ++nones; });
+        CHECK(calls == 1 && seen == kind && nones == 0);
+    }
+    for (int kind : {-1, 6}) {
+        int calls = 0, nones = 0;
+        with_kind(kind, [&](auto) { ++calls; }, [&] { ++nones; });
+        CHECK(calls == 0 && nones == 1);
+    }
+    return 0;
+}
+
 int main()
 {
-    if (test_layouts() || test_split() || test_views() || test_event_pairs()) return 1;
+    if (test_layouts() || test_split() || test_views() || test_event_pairs() || test_with_kind()) return 1;
     for (void* p : g_freed) std::free(p);
     std::printf("QUERY_HOST_OK\n");
     return 0;

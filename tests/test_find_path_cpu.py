@@ -62,7 +62,15 @@ def test_device_header_is_included_behind_every_other_one():
     includes = re.findall(r'#include "([^"]+)"', hip)
     assert includes[-1] == "find_path_kernels.h"                            # new templates are emitted behind the existing kernels
     src = open(os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc", "find_path_kernels.h")).read()
+    assert '#include "find_dir_kernels.h"' in src                           # the kernels' text, part of the search header
+    src += open(os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc", "find_dir_kernels.h")).read()
     assert "atomicMax" in src and "atomicMin" in src and "__ballot" in src and "atomicAdd" not in src
+    # the one dispatch on a kind lives in kind_switch.h: no query header spells the cases out again
+    csrc = os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc")
+    for header in ("query_read.h", "quote_kernels.h", "quote_path_kernels.h", "swap_kernels.h", "swap_out_kernels.h", "swap_path_kernels.h",
+                   "find_path_kernels.h", "find_dir_kernels.h", "size_path_kernels.h"):
+        assert "case CFMM_KIND_" not in open(os.path.join(csrc, header)).read(), header
+    assert open(os.path.join(csrc, "kind_switch.h")).read().count("case CFMM_KIND_") == 6
     assert "kFindScratchBudget = 256ll << 20" in open(os.path.join(ROOT, "cfmmrouter.jl_amd", "csrc", "find_checks.h")).read()
 
 

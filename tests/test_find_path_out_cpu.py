@@ -72,15 +72,31 @@ def test_device_code_sits_below_the_existing_kernels_and_has_no_float_atomic():
     hip = read("cfmmrouter.jl_amd", "csrc", "sweep_kernels.hip")
     assert re.findall(r'#include "([^"]+)"', hip)[-1] == "find_path_kernels.h"
     src = read("cfmmrouter.jl_amd", "csrc", "find_path_kernels.h")
-    new = src[src.index("cfmm_find_path_out"):]
-    assert src.index("void find_finish(") < src.index("void find_out_init(")      # below the existing kernels
-    for name in ("find_out_init", "find_out_relax", "find_out_select", "find_out_claim", "find_out_advance", "find_out_finish"):
-        assert f"void {name}(FindArgs a)" in new, name
-        assert name in hip                                                 # launched through launch_find
-    for reused in ("find_segment<true>", "find_tokens(", "find_decode(", "find_clamp_token(", "path_hop<CFMM_KIND_CURVE, true>", "__ballot"):
-        assert reused in new, reused
-    assert "atomicMin" in new and "atomicMax" not in new and "atomicAdd" not in src
-    assert "template <bool TILE>" in src and "template <int BLOCK, bool LDS>\n__global__ __launch_bounds__(BLOCK) void find_relax(FindArgs a)" in src
+    launch = hip[hip.index("hipError_t launch_find("):hip.index("hipError_t launch_size_path(")]
+    # both directions are ONE search: every entry keeps its name and template arguments, is defined in the header and is
+    # what launch_find launches
+    kernels = read("cfmmrouter.jl_amd", "csrc", "find_dir_kernels.h")     # the six kernels' one text, included once per direction
+    assert src.count('#include "find_dir_kernels.h"') == 2
+    for prefix, out in (("find_", "false"), ("find_out_", "true")):
+        assert f'#define CFMM_FIND_OUT {out}\n#define CFMM_FIND(role) {prefix}##role\n#include "find_dir_kernels.h"' in src
+    for role in ("init", "relax", "select", "claim", "advance", "finish"):
+        args = "template <int BLOCK, bool LDS>" if role == "relax" else "template <int BLOCK>"
+        assert kernels.count(f"{args}\n__global__ __launch_bounds__(BLOCK) void CFMM_FIND({role})(FindArgs a)") == 1, role
+        for prefix in ("find_", "find_out_"):
+            assert f"&{prefix}{role}<kFindBlock" in launch, prefix + role
+    assert kernels.count("\n__global__ ") == 6
+    src += kernels
+    # the search reuses the quotes and the one kind dispatch, and copies neither: no kind is named here
+    for reused in ("find_segment<true>", "find_tokens(", "find_decode(", "find_clamp_token(", "with_kind(", "path_hop<decltype(K)::value, OUT>"):
+        assert reused in src, reused
+    assert "CFMM_KIND_" not in src and "switch (" not in src
+    assert src.count("__ballot(") == 1                                     # one relax text, one early-out
+    # both integer folds, and no float atomic in any query header
+    assert "atomicMax(word, bits)" in src and "atomicMin(word, bits)" in src
+    for header in ("kind_switch.h", "query_read.h", "quote_kernels.h", "quote_path_kernels.h", "swap_kernels.h", "swap_out_kernels.h",
+                   "swap_path_kernels.h", "find_path_kernels.h", "find_dir_kernels.h", "size_path_kernels.h", "swap_pool.h"):
+        assert "atomicAdd" not in read("cfmmrouter.jl_amd", "csrc", header), header
+    assert "template <bool TILE>" in src
 
 
 # ---- the router-level call on a recording context ---------------------------------------------------------------------------
