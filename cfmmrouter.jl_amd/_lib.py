@@ -27,6 +27,9 @@ SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = 0, 1, 2, 3   # 
 FOUND, FOUND_NONE, FOUND_REPEATS = 0, 1, 2   # CFMM_FOUND*: Context.find_path's status
 SIZED, SIZED_NONE, SIZED_AT_LIMIT, SIZED_NAN = 0, 1, 2, 3   # CFMM_SIZED*: Context.size_path's status
 MAX_SIZE_ROUNDS = 16       # CFMM_MAX_SIZE_ROUNDS
+SPLIT_OK, SPLIT_NONE, SPLIT_NAN, SPLIT_SATURATED = 0, 1, 2, 3   # CFMM_SPLIT_*: Context.split_paths' status
+MAX_SPLIT_PATHS = 8        # CFMM_MAX_SPLIT_PATHS
+MAX_SPLIT_ROUNDS = 16      # CFMM_MAX_SPLIT_ROUNDS
 
 KIND_PRODUCT, KIND_GEOMEAN, KIND_UNIV3, KIND_WEIGHTED, KIND_CURVE, KIND_SOLIDLY = 0, 1, 2, 3, 4, 5
 
@@ -69,7 +72,7 @@ class CFMMDeviceError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile libcfmm_amd.so for gfx950 with hipcc (csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h", "cfmm_amd_size_path.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h", "cfmm_amd_size_path.h", "cfmm_amd_split.h")]
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -154,6 +157,9 @@ def lib():
     L.cfmm_size_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                  _f64p, _f64p, _f64p, _i32p]
     L.cfmm_size_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 4
+    L.cfmm_split_paths.argtypes = [_ctx, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, C.c_int32,
+                                   _f64p, _f64p, _f64p, _i32p]
+    L.cfmm_split_paths_dev.argtypes = [_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -732,6 +738,47 @@ class Context:
         self._check(self._L.cfmm_size_path_dev(self._h, int(count), int(max_hops), *(C.c_void_p(p or None) for p in (
             d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out, d_max_in, d_value_in, d_value_out)), int(rounds),
             *(C.c_void_p(p or None) for p in (d_amount_in, d_amount_out, d_gain, d_status))))
+
+    # -- order splitting (cfmm_split_paths): an order's amount spread over its 1 .. 8 paths ----------
+    def split_paths(self, order_first, amount_in, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, rounds=5):
+        """How much of each order goes down each of its paths (cfmm_split_paths): quote_path's path arguments for all the
+        paths, `order_first` [orders + 1] (order g owns the paths order_first[g] .. order_first[g+1] - 1, 1 .. MAX_SPLIT_PATHS of
+        them) and the amount of each order.  Returns (path_amount_in [n_paths], path_amount_out [n_paths], total_out [orders],
+        status [orders]).  The contract is the greedy search of include/cfmm_amd_split.h: `rounds` (1 .. MAX_SPLIT_ROUNDS) rounds
+        of 64 grid points per path; each round hands out 63 slices of what is left, one by one, to the path whose next slice
+        buys the most (the smallest path among equals; NaN loses), then steps every share back one slice and refines.  The
+        shares sum to the amount (to its rounding); with one path the share is the amount bit for bit; quote_path at
+        path_amount_in answers path_amount_out bit for bit.  On 4000 random orders of product chains the default 5 rounds
+        were within 8e-12 of the closed-form optimum for 99 % of the orders and within 1.6e-7 for all (the worst orders have 8
+        paths, one of which carries most of the amount: one step back is then not enough).  status[g] is SPLIT_OK,
+        SPLIT_SATURATED (part of the amount buys nothing: the paths cannot absorb it), SPLIT_NONE (amount 0 or nothing
+        comes out: zeros) or SPLIT_NAN.  No pool may occur twice among an order's paths.  Every hop is quoted against the
+        pool as it stands.  Read-only.  Everything is checked before anything runs (ArgumentError names the order)."""
+        first = np.ascontiguousarray(order_first, dtype=np.int64).reshape(-1)
+        amt = np.ascontiguousarray(f64(amount_in).reshape(-1))
+        if first.size != amt.size + 1:
+            raise ArgumentError("order_first must have one entry more than amount_in")
+        nh0 = np.ascontiguousarray(n_hops, dtype=np.int32).reshape(-1)
+        n = nh0.size
+        nh, seg, row, ci, co = self._path_columns(nh0, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        max_hops = max(1, int(seg.shape[0]))
+        g = amt.size
+        x, y, tot, st = np.empty(n), np.empty(n), np.empty(g), np.empty(g, dtype=np.int32)
+        self._check(self._L.cfmm_split_paths(self._h, g, ptr(first), ptr(amt), n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co),
+                                             int(rounds), ptr(x), ptr(y), ptr(tot), ptr(st)))
+        return x, y, tot, st
+
+    def split_paths_dev(self, count: int, d_order_first: int, d_amount_in: int, n_paths: int, max_hops: int, d_n_hops: int,
+                        d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int, d_hop_coin_out: int, rounds: int, d_path_amount_in: int,
+                        d_path_amount_out: int, d_total_out: int, d_status: int):
+        """cfmm_split_paths_dev on device addresses (int64 order_first [count + 1], float64 amounts; the hop arrays hop-major
+        [max_hops][n_paths] as quote_path_dev's; int32 status): asynchronous on the context's stream, unchecked -- a bad
+        order, path, hop or amount gives that order SPLIT_NAN and NaN outputs, nothing is read out of bounds.  Pools shared
+        between an order's paths are NOT looked for here."""
+        self._check(self._L.cfmm_split_paths_dev(self._h, int(count), C.c_void_p(d_order_first or None), C.c_void_p(d_amount_in or None),
+                                                 int(n_paths), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out)), int(rounds),
+            *(C.c_void_p(p or None) for p in (d_path_amount_in, d_path_amount_out, d_total_out, d_status))))
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
                        d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):

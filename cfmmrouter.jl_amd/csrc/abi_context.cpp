@@ -277,6 +277,7 @@ static int64_t* option_slot(cfmm_ctx* c, const char* key)
         {"stop_in_noise", &c->opt_stop_in_noise}, {"multi_threads", &c->opt_multi_threads},
         {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->geo.direct_small}, {"stream_stores", &c->opt_stream_stores},
         {"find_lds", &c->opt_find_lds}, {"lean_kernels", &c->opt_lean_kernels}, {"size_max_blocks", &c->opt_size_max_blocks},
+        {"split_max_blocks", &c->opt_split_max_blocks},
 #ifdef CFMM_TEST_HOOKS
         {"debug_stall_ms", &c->opt_debug_stall_ms},
 #endif
@@ -299,6 +300,7 @@ int cfmm_set_option(cfmm_ctx* c, const char* key, int64_t value)
     if (slot == &c->opt_stream_stores && !(value == 0 || value == 1 || value == 2))
         return fail(c, CFMM_ERR_INVALID_ARG, "stream_stores must be 0 (auto), 1 (write-through) or 2 (non-temporal)");
     if (slot == &c->opt_size_max_blocks && value < 1) return fail(c, CFMM_ERR_INVALID_ARG, "size_max_blocks must be >= 1");
+    if (slot == &c->opt_split_max_blocks && value < 1) return fail(c, CFMM_ERR_INVALID_ARG, "split_max_blocks must be >= 1");
     *slot = value;
     c->desc_dirty = true;   // pack, compact_trades, block, max_grid, fuse_segments, bin_copies, stream_stores, univ3_heads, geomean_exact, cost_*: all copied
     if (slot != &c->opt_multi_threads)
@@ -347,6 +349,9 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     // "time_kernels" its kernel's span (a parent: the sum of its rounds' "quote_ns"); after cfmm_size_path_dev the read waits, as "quote_ns"
     if (key && !std::strcmp(key, "size_launches")) { *value = c->size.launches; return CFMM_OK; }
     if (key && !std::strcmp(key, "size_ns")) return size_ns(const_cast<cfmm_ctx*>(c), value);
+    // read-only, cfmm_split_paths / cfmm_split_paths_dev: the same two of the latest split
+    if (key && !std::strcmp(key, "split_launches")) { *value = c->split.launches; return CFMM_OK; }
+    if (key && !std::strcmp(key, "split_ns")) return split_ns(const_cast<cfmm_ctx*>(c), value);
     // read-only, cfmm_find_path / cfmm_find_path_out (whichever was called last): the latest call's kernel launches, and under
     // "time_kernels" the sums of the spans of its layer launches (find_relax / find_out_relax) and of its walk launches (claim +
     // advance)

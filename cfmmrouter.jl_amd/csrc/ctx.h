@@ -27,7 +27,9 @@
 //                     checks and the chunking rule)
 //   abi_size_path.cpp the input of a path that maximises its gain (cfmm_size_path; size_checks.h: the HIP-free checks, size_grid.h:
 //                     the search's arithmetic, shared with the kernel)
-//   seg_view.h        what those six share, on top of this header: a segment as their kernels and their checks see it
+//   abi_split_paths.cpp an order's amount spread over several paths (cfmm_split_paths; split_checks.h: the HIP-free checks,
+//                     split_grid.h: the search's arithmetic, shared with the kernel)
+//   seg_view.h        what those seven share, on top of this header: a segment as their kernels and their checks see it
 //   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
 //   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
@@ -347,6 +349,27 @@ struct SizeScratch {
                                        // cfmm_quote_path calls)
 };
 
+// cfmm_split_paths (abi_split_paths.cpp, split_paths_kernels.h): SizeScratch's arrangement for the splits -- the device copies of
+// one call's orders, paths and answers, the segment table (rebuilt and uploaded on every call) and ONE pinned staging buffer,
+// proportional to the orders and to n_paths x max_hops, never to the pools; `done` guards staging and table against the call
+// before.  A multi-device parent uses none of the device arrays: its search runs on the host (split_grid.h) over cfmm_quote_path.
+struct SplitScratch {
+    DevBuf<PathSeg> table;             // [segments]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][n_paths]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> i64;             // [max_hops][n_paths] hop_row, then [count + 1] order_first
+    DevBuf<double> amount;             // [count]
+    DevBuf<double> out;                // [2][n_paths] path_amount_in, path_amount_out, then [count] total_out
+    DevBuf<int32_t> status;            // [count]
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SplitStage
+    Event done;                        // behind the latest call's kernel
+    bool in_flight = false;
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // read-only option "split_ns": that kernel's span (a parent: the sum of its rounds' "quote_ns")
+    bool dev_timed = false;            // the latest timed call was cfmm_split_paths_dev: its span is read when asked for
+    int64_t launches = 0;              // read-only option "split_launches": kernel launches of the latest call (1; a parent: its
+                                       // cfmm_quote_path calls)
+};
+
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
 // one after the other BEHIND the launches' fee tables in cfmm_ctx::d_gtab (ensure_geometry sizes that array for both: what
 // a launch reads and no evaluation changes is one device array): rebuilt by ensure_desc (abi_sweep.cpp) when
@@ -460,6 +483,7 @@ struct cfmm_ctx {
                                    //    goes to global memory (the A/B of scripts/find_path_times.py; the same bits either way)
     int64_t opt_size_max_blocks = cfmm::kSizeMaxBlocks; // cfmm_size_path: the most blocks of its launch (>= 1; its wavefronts stride over the
                                    //    paths, the same bits at any value: a measurement and test switch)
+    int64_t opt_split_max_blocks = cfmm::kSplitMaxBlocks; // cfmm_split_paths: the same switch of its launch (its wavefronts stride over the orders)
     int64_t opt_univ3_heads = 1;   // 1: multi-tick UniV3 walks decide their first four list ticks from the per-pool float threshold heads
     int64_t opt_lean_kernels = 1;  // 1: a launch in the default configuration takes the lean form of its kernel (launch_plan.h lean_launch:
                                    //    the same bits with fewer instructions per tile); 0: always the general kernels (A/B, tests)
@@ -481,6 +505,7 @@ struct cfmm_ctx {
     cfmm::SwapPathScratch swap_path;
     cfmm::FindScratch find;
     cfmm::SizeScratch size;
+    cfmm::SplitScratch split;
     cfmm::KernelTimer timer;
 
     // single-process multi-device parent (cfmm_ctx_create_multi): shards non-empty, no device state of its own
@@ -552,6 +577,8 @@ int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, in
 
 // abi_size_path.cpp
 int size_ns(cfmm_ctx* c, int64_t* value);
+// abi_split_paths.cpp
+int split_ns(cfmm_ctx* c, int64_t* value);
 
 // abi_update.cpp
 // cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not

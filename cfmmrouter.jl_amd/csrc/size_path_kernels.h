@@ -77,3 +77,6 @@ __global__ __launch_bounds__(BLOCK) void size_path_kernel(SizeArgs a)
 }
 
 } // namespace cfmm
+
+// (what came after this header is included from here, behind everything above: find_path_kernels.h's rule)
+#include "split_paths_kernels.h"

@@ -1,5 +1,5 @@
 // stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp,
-// abi_find_path.cpp, abi_size_path.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
+// abi_find_path.cpp, abi_size_path.cpp, abi_split_paths.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
 // A layout is declared once, column by column; each column starts on a word and takes ceil(bytes / 8) words.  The entry grows
 // its buffer by words() and takes every host pointer from the column's handle, so the size and the addresses cannot disagree.
 // What crosses to the device in ONE copy is ONE column (the [2][count] coins, n_hops with the three int32 hop columns, ...).
@@ -77,6 +77,18 @@ struct SizeStage {   // cfmm_size_path (cfmm_size_path_dev: the table alone, n =
     SizeStage(size_t table_bytes, size_t n, size_t nh)
         : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), in(l.add<double>(3 * n)),
           out(l.add<double>(3 * n)), status(l.add<int32_t>(n)) {}
+};
+struct SplitStage {   // cfmm_split_paths: g orders over n paths (cfmm_split_paths_dev: the table alone, g = n = 0)
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> i32;      // [1 + 3*H][n] n_hops, hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [H][n] hop_row, then [g + 1] order_first
+    StageCol<double> amount;    // [g]
+    StageCol<double> out;       // [2][n] path_amount_in, path_amount_out, then [g] total_out
+    StageCol<int32_t> status;   // [g]
+    SplitStage(size_t table_bytes, size_t g, size_t n, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh + (g ? g + 1 : 0))),
+          amount(l.add<double>(g)), out(l.add<double>(2 * n + g)), status(l.add<int32_t>(g)) {}
 };
 struct SwapPathStage {   // cfmm_swap_path / cfmm_swap_path_out, the paths in wave order; nrec: the table's records, one window flag each
     StageLayout l;

@@ -511,6 +511,24 @@ constexpr int kSizeMaxBlocks = kResidentThreads / kSizeBlock;    // default of o
 // max_blocks >= 1 caps the grid (the wavefronts stride over the paths).  e0, e1: both set = the launch is timed.
 hipError_t launch_size_path(const SizeArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_split_paths (split_paths_kernels.h, abi_split_paths.cpp): an order's amount spread over its 1 .. 8 paths, one WAVEFRONT
+// per order and one lane per grid point.  The paths are a PathArgs as cfmm_quote_path's kernel takes it -- p.count is n_paths,
+// p.given is unused (null), p.answer receives path_amount_in, p.hops is unused (null) -- plus the orders.
+struct SplitArgs {
+    PathArgs p;
+    int64_t orders;              // orders
+    const long long* order_first; // [orders + 1]: order g owns the paths order_first[g] .. order_first[g+1] - 1
+    const double* amount;        // [orders] the amount to spread
+    int32_t rounds;              // 1 .. CFMM_MAX_SPLIT_ROUNDS
+    double* path_out;            // [p.count] path_amount_out
+    double* total;               // [orders]
+    int32_t* status;             // [orders] CFMM_SPLIT_*
+};
+constexpr int kSplitBlock = 256;                                  // four wavefronts = four orders per block
+constexpr int kSplitMaxBlocks = kResidentThreads / kSplitBlock;   // default of option "split_max_blocks": one machine of resident wavefronts
+// max_blocks >= 1 caps the grid (the wavefronts stride over the orders).  e0, e1: both set = the launch is timed.
+hipError_t launch_split_paths(const SplitArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // cfmm_swap_path (swap_path_kernels.h, abi_swap_path.cpp): exact-input paths that MOVE their pools, all or nothing, one lane per
 // path of ONE WAVE -- paths that share no pool (the host numbers the waves: swap_path_waves.h).  The kernel reads a table of
 // its own: what PathSeg holds (the quotes' view, unchanged), the segment's arrays again as writable pointers, what

@@ -49,6 +49,7 @@
 //   swap_out_kernels.h   swap_out_kernel (cfmm_swap_out: quote_out_one's answer, then the pool's new state, with a status per swap)
 //   find_path_kernels.h  find_relax and the walk back (cfmm_find_path: the best walk between two tokens, a layer per launch, one lane per pool)
 //   size_path_kernels.h  size_path_kernel (cfmm_size_path: the input that maximises a path's gain, one wavefront per path, one lane per trial size)
+//   split_paths_kernels.h  split_paths_kernel (cfmm_split_paths: an order's amount spread over its paths, one wavefront per order, one lane per grid point)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -67,7 +68,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, and from that one's split_paths_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -462,6 +463,19 @@ hipError_t launch_size_path(const SizeArgs& a, int64_t max_blocks, hipStream_t s
     const int64_t blocks = std::min<int64_t>({(a.p.count + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
     void* args[] = {const_cast<SizeArgs*>(&a)};
     return launch_k(reinterpret_cast<const void*>(&size_path_kernel<kSizeBlock>), dim3((unsigned)blocks), dim3(kSizeBlock), 0, s, e0, e1, args);
+}
+
+// cfmm_split_paths: one wavefront per order, kSplitBlock / 64 orders per block, at most max_blocks blocks.  (Behind every other
+// launcher, for launch_size_path's reason.)
+hipError_t launch_split_paths(const SplitArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.orders <= 0 || a.p.count <= 0 || a.p.nseg <= 0 || a.p.max_hops < 1 || a.p.max_hops > CFMM_MAX_PATH_HOPS || a.rounds < 1 ||
+        a.rounds > CFMM_MAX_SPLIT_ROUNDS || max_blocks < 1 || !a.order_first || !a.amount || !a.p.answer || !a.path_out || !a.total || !a.status)
+        return hipErrorInvalidValue;
+    constexpr int64_t per_block = kSplitBlock / CFMM_SPLIT_POINTS;
+    const int64_t blocks = std::min<int64_t>({(a.orders + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
+    void* args[] = {const_cast<SplitArgs*>(&a)};
+    return launch_k(reinterpret_cast<const void*>(&split_paths_kernel<kSplitBlock>), dim3((unsigned)blocks), dim3(kSplitBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import MAX_PATH_HOPS, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from ._lib import MAX_PATH_HOPS, MAX_SPLIT_PATHS, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
 from .layout import PoolLayout
 from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
@@ -889,10 +889,59 @@ def size_path(r: Router, pools, tokens, max_in, value_in=None, value_out=None, r
     as [0, max_in] and becomes the two neighbours of the best trial size.  A path's gain is concave, so the bracket shrinks by
     2/63 per round around the maximiser; the default 5 rounds reach the closed-form optimum of two-pool cycles to about 1e-12 of
     its gain.  status[p] is SIZED, SIZED_AT_LIMIT (gain > 0 at amount_in == max_in: the limit binds), SIZED_NONE (no size gains:
-    three 0.0) or SIZED_NAN.  It sizes ONE path on the STANDING market: it does not split an amount over several paths.
+    three 0.0) or SIZED_NAN.  It sizes ONE path on the STANDING market: it does not split an amount over several paths
+    (`split_paths` does).
     `swap_path_(r, pools, tokens, amount_in, min_out=...)` executes the answer.  Read-only, like `quote`."""
     n_hops, seg, row, ci, co, lim, _ = _path_hops(r, "size_path", pools, tokens, max_in, "max_in")
     return _path_context(r).size_path(n_hops, seg, row, ci, co, lim, value_in, value_out, rounds)
+
+
+def split_paths(r: Router, pools, tokens, amount_in, rounds=5):
+    """HOW MUCH OF AN ORDER GOES DOWN EACH PATH, on the pools as they stand on the device (cfmm_split_paths) -- "I have A of X and
+    these K routes to Y; how much goes down each?".  `pools[g]` is a list of 1 .. 8 paths, each a list of positions in `r.cfmms`;
+    `tokens[g][k]` the token ids along path k (1-based as in `Ai`, one more than the pools); `amount_in[g]` the amount of
+    order g (a scalar broadcasts).  The mapping and the refusals are `quote_path`'s (a token break, a repeated pool, a
+    host-evaluated pool, named by the path's number in the whole call), and two more: every path of an order must start at
+    the same token and end at the same token, and no pool may occur twice in an order -- the paths are quoted independently
+    against the standing market, so a shared pool would be counted twice.
+
+    Returns (path_amount_in, path_amount_out, total_out, status): the first two are lists shaped like `pools` (one array per
+    order), the last two arrays with one entry per order.  The contract is the greedy search with scaling: `rounds` (1 .. 16)
+    rounds of 64 grid points per path; a round hands out 63 slices of what is left, each to the path whose next slice buys the
+    most, then steps every share back one slice and refines.  The shares sum to the amount; `quote_path` at a share answers
+    its output bit for bit.  On 4000 random orders of product chains the default 5 rounds were within 8e-12 of the
+    closed-form optimum for 99 % of the orders and within 1.6e-7 for all.  status[g] is SPLIT_OK, SPLIT_SATURATED (part of the
+    amount buys nothing: the paths cannot absorb it), SPLIT_NONE (amount 0, or nothing comes out: zeros) or SPLIT_NAN.
+    `swap_path_(r, pools[g], tokens[g], path_amount_in[g])` executes order g's split.  Read-only, like `quote`."""
+    pools, tokens = [list(o) for o in pools], [list(o) for o in tokens]
+    if len(tokens) != len(pools):
+        raise ArgumentError("tokens must have one list of paths per order")
+    try:
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (len(pools),)))
+    except ValueError:
+        raise ArgumentError("amount_in must be a scalar or have one entry per order") from None
+    for g, (pl, tk) in enumerate(zip(pools, tokens)):
+        if not 1 <= len(pl) <= MAX_SPLIT_PATHS:
+            raise ArgumentError(f"order {g}: {len(pl)} paths (an order has 1 to {MAX_SPLIT_PATHS})")
+        if len(tk) != len(pl):
+            raise ArgumentError(f"order {g}: {len(tk)} token sequences for {len(pl)} paths")
+    first = np.concatenate(([0], np.cumsum([len(pl) for pl in pools]))).astype(np.int64)
+    flat_pools, flat_tokens = [p for pl in pools for p in pl], [t for tk in tokens for t in tk]
+    n_hops, seg, row, ci, co, _, _ = _path_hops(r, "split_paths", flat_pools, flat_tokens, 0.0)
+    for g, (pl, tk) in enumerate(zip(pools, tokens)):
+        ends = {(int(np.asarray(t).reshape(-1)[0]), int(np.asarray(t).reshape(-1)[-1])) for t in tk}
+        if len(ends) != 1:
+            raise ArgumentError(f"order {g}: its paths must all start at the same token and end at the same token (got {sorted(ends)})")
+        seen = {}
+        for k, path in enumerate(pl):
+            for i in np.asarray(path, dtype=np.int64).reshape(-1).tolist():
+                if i in seen:
+                    raise ArgumentError(f"order {g}: paths {seen[i]} and {k} share pool {i} (the paths are quoted independently "
+                                        f"against the standing market, so a shared pool would be counted twice)")
+                seen[i] = k
+    x, y, total, status = _path_context(r).split_paths(first, amt, n_hops, seg, row, ci, co, rounds)
+    cut = lambda v: [v[first[g]:first[g + 1]] for g in range(len(pools))]
+    return cut(x), cut(y), total, status
 
 
 def _find_path(r: Router, verb, amount_name, token_in, token_out, amount, max_hops):

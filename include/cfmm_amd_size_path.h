@@ -49,8 +49,8 @@ extern "C" {
  * closed-form optimum; the gain within 6e-10 (relative) of the closed-form gain at 4 rounds, within 1.2e-12 at 5 rounds, and no
  * improvement beyond 6 rounds (4e-13: the rounding of the gain itself).
  * The Python default is therefore rounds = 5.  THE CONTRACT IS THE SEARCH, not "the global maximum".
- * It sizes ONE path on the STANDING market: it does not split an amount over several paths, and no state advances between
- * hops.
+ * It sizes ONE path on the STANDING market: it does not split an amount over several paths (cfmm_split_paths of
+ * cfmm_amd_split.h does), and no state advances between hops.
  *   amount_in, amount_out, gain, status   [count]
  * Everything is checked before anything is enqueued: cfmm_quote_path's checks of the paths, max_amount_in[p] finite and
  * >= 0, rounds in 1 .. CFMM_MAX_SIZE_ROUNDS, the values, no null output array.  A failure is CFMM_ERR_INVALID_ARG, names the
