@@ -10,7 +10,7 @@ from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwo
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
-from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_, size_path, split_paths,
+from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_disjoint_paths, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_, route_order, size_path, split_paths,
                      swap_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
 
 
@@ -32,5 +32,6 @@ __all__ = [
     "quote_path", "quote_path_out", "swap_", "swap_path_", "swap_out_", "swap_path_out_",
     "find_path", "find_path_out", "FOUND", "FOUND_NONE", "FOUND_REPEATS",
     "size_path", "SIZED", "SIZED_NONE", "SIZED_AT_LIMIT", "SIZED_NAN",
+    "find_disjoint_paths", "route_order",
     "split_paths", "SPLIT_OK", "SPLIT_NONE", "SPLIT_NAN", "SPLIT_SATURATED",
 ]

@@ -154,6 +154,7 @@ def lib():
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
+    L.cfmm_find_disjoint_paths.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
     L.cfmm_size_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                  _f64p, _f64p, _f64p, _i32p]
     L.cfmm_size_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 4
@@ -701,6 +702,35 @@ class Context:
         self._check(getattr(self._L, entry)(self._h, n, H, ptr(tin), ptr(tout), ptr(amt), ptr(out), ptr(nh), ptr(seg), ptr(row), ptr(ci),
                                             ptr(co), ptr(st)))
         return out, nh, seg.T.copy(), row.T.copy(), ci.T.copy(), co.T.copy(), st
+
+    # -- several paths per order (cfmm_find_disjoint_paths): find_path's search run max_paths times, the found pools absent afterwards ----------
+    def find_disjoint_paths(self, token_in, token_out, amount_in, max_paths=4, max_hops=3):
+        """Up to max_paths (1 .. MAX_SPLIT_PATHS) swap paths from token_in[q] to token_out[q] (0-based token ids) that share NO
+        POOL, on the pools as they stand on the device (cfmm_find_disjoint_paths): returns (n_paths [count], amount_out
+        [count, K], n_hops [count, K], seg, row, ci, co [count, K, max_hops], status [count, K]) with K = max_paths.  The
+        contract is successive search: path r of a query is find_path's answer for (token_in, token_out, amount_in, max_hops) on
+        the market without every pool of the query's paths 0 .. r-1 -- greedy successive-best, not "the K best overall".  So
+        slot 0 is find_path's answer, the amounts do not increase with r, quote_path on path r at amount_in[q] answers
+        amount_out[q, r] bit for bit, and the found paths fill the slots 0 .. n_paths[q]-1; the others carry FOUND_NONE, 0 hops,
+        0.0 and -1.  A walk that visits a pool twice keeps its slot as FOUND_REPEATS.  The same amount_in probes every round: to
+        split A over K paths, probing with A / K may serve better.  Scalars broadcast.  Read-only.  Everything is checked before
+        anything runs (ArgumentError names the query)."""
+        try:
+            tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int32).reshape(-1), np.asarray(token_out, dtype=np.int32).reshape(-1),
+                                                 f64(amount_in).reshape(-1))
+        except ValueError:
+            raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+        tin, tout, amt = (np.ascontiguousarray(a) for a in (tin, tout, amt))
+        n, H, K = amt.size, int(max_hops), int(max_paths)
+        kk, hh = max(K, 0), max(H, 0)
+        npaths, out = np.empty(n, dtype=np.int32), np.empty((kk, n))
+        nh, st = (np.empty((kk, n), dtype=np.int32) for _ in range(2))
+        seg, ci, co = (np.empty((kk, hh, n), dtype=np.int32) for _ in range(3))
+        row = np.empty((kk, hh, n), dtype=np.int64)
+        self._check(self._L.cfmm_find_disjoint_paths(self._h, n, K, H, ptr(tin), ptr(tout), ptr(amt), ptr(npaths), ptr(out), ptr(nh), ptr(st),
+                                                     ptr(seg), ptr(row), ptr(ci), ptr(co)))
+        hops = lambda a: np.ascontiguousarray(a.transpose(2, 0, 1))
+        return npaths, out.T.copy(), nh.T.copy(), hops(seg), hops(row), hops(ci), hops(co), st.T.copy()
 
     # -- path sizing (cfmm_size_path): the input of a path, at most max_in, that maximises its gain ----------
     def size_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, max_in, value_in=None, value_out=None, rounds=5):

@@ -366,6 +366,14 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
             return CFMM_OK;
         }
     }
+    for (int k = 0; k < 2 && key; ++k) {   // ... and round by round: "find_round_relax_ns_2" is the second round of cfmm_find_disjoint_paths
+        static const char* const names[2] = {"find_round_relax_ns_", "find_round_walk_ns_"};
+        const size_t len = std::strlen(names[k]);
+        if (!std::strncmp(key, names[k], len) && key[len] >= '1' && key[len] <= '0' + CFMM_MAX_SPLIT_PATHS && !key[len + 1]) {
+            *value = c->find.round_ns[k][key[len] - '1'];
+            return CFMM_OK;
+        }
+    }
     // read-only, cfmm_select_trades: its two geometry constants, and the three kernel spans of the latest call timed under
     // option "time_kernels" (a parent reports its first shard's)
     if (key && !std::strcmp(key, "select_block_pools")) { *value = kSelBlock; return CFMM_OK; }

@@ -39,6 +39,7 @@
 #pragma once
 
 #include "../../include/cfmm_amd.h"
+#include "../../include/cfmm_amd_split.h"
 #include "devbuf.h"
 #include "hostres.h"
 #include "ladder_store.h"
@@ -308,7 +309,8 @@ struct SwapPathScratch {
 // FindSeg, rebuilt per call) and ONE pinned staging buffer, all grown on demand and kept for the next call.  The call ends
 // synchronised, so nothing here is guarded against the call before.  cfmm_find_path_out uses the same scratch with the roles of
 // the amounts exchanged (best: the layers of its min-search, all ones = unreached; edge[k]: hop k in path order); the read-only
-// options describe the latest call of either entry.
+// options describe the latest call of either entry.  cfmm_find_disjoint_paths (include/cfmm_amd_find_disjoint.h) uses it too, its
+// outputs max_paths times as large (the layout: abi_find_path.cpp find_disjoint), plus the ban rows.
 struct FindScratch {
     DevBuf<FindSeg> table;             // [segments]
     DevBuf<unsigned long long> best;   // [max_hops + 1][chunk][n_tokens]
@@ -317,7 +319,8 @@ struct FindScratch {
                                        // hop_coin_out; [2][chunk] the hops of the answer, the walk's target token
     DevBuf<long long> hop_row;         // [max_hops][count]
     DevBuf<double> amt;                // [2][count] amount_in, amount_out
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h FindStage
+    DevBuf<unsigned long long> ban;    // cfmm_find_disjoint_paths: [chunk][ceil(pools / 64)] the pools absent for each query, cleared per chunk
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h FindStage / FindDisjointStage
     EventPairs ev;                     // option "time_kernels": {start, stop} per launch of the latest call
     int64_t relax_ns = 0, walk_ns = 0; // read-only options "find_relax_ns" / "find_walk_ns": the sums of that call's find_relax spans
                                        // and of its find_claim + find_advance spans
@@ -325,6 +328,9 @@ struct FindScratch {
     // the same spans layer by layer, summed over the call's chunks: read-only options "find_relax_ns_<h>", "find_claim_ns_<h>",
     // "find_advance_ns_<h>", h = 1 .. CFMM_MAX_PATH_HOPS (0 for a layer the call did not have)
     int64_t layer_ns[3][CFMM_MAX_PATH_HOPS] = {};
+    // ... and round by round (cfmm_find_disjoint_paths; the other entries have one round): read-only options
+    // "find_round_relax_ns_<r>" / "find_round_walk_ns_<r>", r = 1 .. CFMM_MAX_SPLIT_PATHS
+    int64_t round_ns[2][CFMM_MAX_SPLIT_PATHS] = {};
 };
 
 // cfmm_size_path (abi_size_path.cpp, size_path_kernels.h): the device copies of one call's paths, limits, values and answers,

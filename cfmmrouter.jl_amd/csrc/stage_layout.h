@@ -1,5 +1,5 @@
 // stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp,
-// abi_find_path.cpp, abi_size_path.cpp, abi_split_paths.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
+// abi_find_path.cpp (both find entries and cfmm_find_disjoint_paths), abi_size_path.cpp, abi_split_paths.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
 // A layout is declared once, column by column; each column starts on a word and takes ceil(bytes / 8) words.  The entry grows
 // its buffer by words() and takes every host pointer from the column's handle, so the size and the addresses cannot disagree.
 // What crosses to the device in ONE copy is ONE column (the [2][count] coins, n_hops with the three int32 hop columns, ...).
@@ -114,6 +114,19 @@ struct FindStage {   // cfmm_find_path / cfmm_find_path_out
     FindStage(size_t table_bytes, size_t n, size_t nh)
         : table(l.add<unsigned char>(table_bytes)), tok(l.add<int32_t>(2 * n)), amt(l.add<double>(n)), out(l.add<double>(n)),
           ns(l.add<int32_t>(2 * n)), hop32(l.add<int32_t>(3 * nh)), row(l.add<long long>(nh)) {}
+};
+struct FindDisjointStage {   // cfmm_find_disjoint_paths: n queries, K paths each, nh = n * H
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> tok;      // [2][n] token_in, token_out
+    StageCol<double> amt;       // [n]
+    StageCol<double> out;       // [K][n]
+    StageCol<int32_t> ns;       // [n] n_paths, then [2][K][n] n_hops, status
+    StageCol<int32_t> hop32;    // [3][K][H][n] hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [K][H][n]
+    FindDisjointStage(size_t table_bytes, size_t n, size_t K, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), tok(l.add<int32_t>(2 * n)), amt(l.add<double>(n)), out(l.add<double>(K * n)),
+          ns(l.add<int32_t>(n + 2 * K * n)), hop32(l.add<int32_t>(3 * K * nh)), row(l.add<long long>(K * nh)) {}
 };
 
 } // namespace cfmm

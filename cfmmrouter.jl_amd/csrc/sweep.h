@@ -630,6 +630,19 @@ constexpr int kFindOutFirst = kFindOutInit;   // a kFindOut* value minus this is
 // e0, e1: both set = the launch is timed by the command processor
 hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_find_disjoint_paths (find_disjoint_kernels.h, abi_find_disjoint.cpp): round `round` of the successive search -- the four
+// exact-input kernels that know the ban (kFindInit, kFindRelax, kFindClaim, kFindFinish; select and advance are launch_find's)
+// take FindArgs UNCHANGED, its output pointers standing at the round's slot, and beside it what the ban needs.
+struct FindBanArgs {
+    unsigned long long* ban;     // [count][ban_words] of the chunk: bit p & 63 of word p >> 6 = pool first_pool + row is absent
+    int64_t ban_words;           // ceil(pools of the table / 64)
+    int32_t* ended;              // [count] of the chunk: 1 once a round found nothing (written by every round's finish)
+    int32_t* n_paths;            // [count], at the chunk's first query: written by round 0's finish, incremented by the others
+    int32_t round;               // 0 .. max_paths - 1
+    int32_t pad;
+};
+hipError_t launch_find_ban(FindKernel which, const FindArgs& a, const FindBanArgs& b, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 // dynamic LDS of a sweep launch: prices (pairs when stage_y), the log-price row, the bin copies, the fee table {γ, 1/γ},
 // two doubles per wavefront and the block's two scalars
 inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, int gtab_n, int stage_y)

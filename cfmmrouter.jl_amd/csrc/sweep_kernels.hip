@@ -50,6 +50,7 @@
 //   find_path_kernels.h  find_relax and the walk back (cfmm_find_path: the best walk between two tokens, a layer per launch, one lane per pool)
 //   size_path_kernels.h  size_path_kernel (cfmm_size_path: the input that maximises a path's gain, one wavefront per path, one lane per trial size)
 //   split_paths_kernels.h  split_paths_kernel (cfmm_split_paths: an order's amount spread over its paths, one wavefront per order, one lane per grid point)
+//   find_disjoint_kernels.h  find_ban_relax and the walk back (cfmm_find_disjoint_paths: find_path's search with a per-query bitmap of absent pools)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -68,7 +69,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, and from that one's split_paths_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, and from that one's find_disjoint_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -412,18 +413,36 @@ hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t
 
 // cfmm_find_path: the per-query kernels take launch_quote_grid's rule without the stride (one lane per query of the chunk);
 // the per-pool kernels one block per tile of the table and one grid row per kFindLaneQueries queries
-hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+// (the grid and LDS of a launch of `role`, an exact-input FindKernel: launch_find and launch_find_ban)
+static hipError_t find_launch_shape(int role, const FindArgs& a, dim3& grid, size_t& lds_bytes)
 {
     if (a.count <= 0 || a.stride < a.count || a.nseg <= 0 || a.n_tokens <= 0 || a.max_hops < 1 || a.max_hops > CFMM_MAX_PATH_HOPS)
         return hipErrorInvalidValue;
     const int64_t qblocks = (a.count + kFindBlock - 1) / kFindBlock, qrows = (a.count + kFindLaneQueries - 1) / kFindLaneQueries;
-    const int role = which >= kFindOutFirst ? which - kFindOutFirst : which;   // (cfmm_find_path_out's kernels take the same grids)
     const bool per_pool = role == kFindRelax || role == kFindClaim;
     if (role != kFindInit && role != kFindSelect && role != kFindFinish && (a.layer < 1 || a.layer > a.max_hops)) return hipErrorInvalidValue;
     if (per_pool && (a.tiles <= 0 || a.tiles > 0x7fffffffll || qrows > 65535)) return hipErrorInvalidValue;
     if (qblocks > 0x7fffffffll) return hipErrorInvalidValue;
     const bool lds = role == kFindRelax && a.group > 0;
     if (lds && (a.group > kFindLaneQueries || a.group > find_lds_group(a.n_tokens) || a.tiles_per_block < 1)) return hipErrorInvalidValue;
+    grid = per_pool ? dim3((unsigned)a.tiles, (unsigned)qrows) : dim3((unsigned)qblocks);
+    lds_bytes = 0;
+    if (lds) {
+        const int64_t rows = (a.count + a.group - 1) / a.group;
+        if (rows > 65535) return hipErrorInvalidValue;
+        grid = dim3((unsigned)((a.tiles + a.tiles_per_block - 1) / a.tiles_per_block), (unsigned)rows);
+        lds_bytes = (size_t)a.group * (size_t)a.n_tokens * sizeof(unsigned long long);
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    dim3 grid;
+    size_t lds_bytes;
+    const hipError_t shape = find_launch_shape(which >= kFindOutFirst ? which - kFindOutFirst : which, a, grid, lds_bytes);   // (cfmm_find_path_out's kernels take the same grids)
+    if (shape != hipSuccess) return shape;
+    const bool lds = lds_bytes > 0;
     const void* kernel;
     switch (which) {
     case kFindInit: kernel = reinterpret_cast<const void*>(&find_init<kFindBlock>); break;
@@ -441,14 +460,6 @@ hipError_t launch_find(FindKernel which, const FindArgs& a, hipStream_t s, hipEv
     default: return hipErrorInvalidDeviceFunction;   // no such kernel
     }
     void* args[] = {const_cast<FindArgs*>(&a)};
-    dim3 grid = per_pool ? dim3((unsigned)a.tiles, (unsigned)qrows) : dim3((unsigned)qblocks);
-    size_t lds_bytes = 0;
-    if (lds) {
-        const int64_t rows = (a.count + a.group - 1) / a.group;
-        if (rows > 65535) return hipErrorInvalidValue;
-        grid = dim3((unsigned)((a.tiles + a.tiles_per_block - 1) / a.tiles_per_block), (unsigned)rows);
-        lds_bytes = (size_t)a.group * (size_t)a.n_tokens * sizeof(unsigned long long);
-    }
     return launch_k(kernel, grid, dim3(kFindBlock), lds_bytes, s, e0, e1, args);
 }
 
@@ -476,6 +487,27 @@ hipError_t launch_split_paths(const SplitArgs& a, int64_t max_blocks, hipStream_
     const int64_t blocks = std::min<int64_t>({(a.orders + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
     void* args[] = {const_cast<SplitArgs*>(&a)};
     return launch_k(reinterpret_cast<const void*>(&split_paths_kernel<kSplitBlock>), dim3((unsigned)blocks), dim3(kSplitBlock), 0, s, e0, e1, args);
+}
+
+// cfmm_find_disjoint_paths: launch_find's grids for the four kernels that know the ban.  (Behind every other launcher, for
+// launch_size_path's reason.)
+hipError_t launch_find_ban(FindKernel which, const FindArgs& a, const FindBanArgs& b, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    dim3 grid;
+    size_t lds_bytes;
+    const hipError_t shape = find_launch_shape(which, a, grid, lds_bytes);
+    if (shape != hipSuccess) return shape;
+    if (!b.ban || b.ban_words < 1 || !b.ended || !b.n_paths || b.round < 0 || b.round >= CFMM_MAX_SPLIT_PATHS) return hipErrorInvalidValue;
+    const void* kernel;
+    switch (which) {
+    case kFindInit: kernel = reinterpret_cast<const void*>(&find_ban_init<kFindBlock>); break;
+    case kFindRelax: kernel = lds_bytes > 0 ? reinterpret_cast<const void*>(&find_ban_relax<kFindBlock, true>) : reinterpret_cast<const void*>(&find_ban_relax<kFindBlock, false>); break;
+    case kFindClaim: kernel = reinterpret_cast<const void*>(&find_ban_claim<kFindBlock>); break;
+    case kFindFinish: kernel = reinterpret_cast<const void*>(&find_ban_finish<kFindBlock>); break;
+    default: return hipErrorInvalidDeviceFunction;   // select and advance know no ban: launch_find
+    }
+    void* args[] = {const_cast<FindArgs*>(&a), const_cast<FindBanArgs*>(&b)};
+    return launch_k(kernel, grid, dim3(kFindBlock), lds_bytes, s, e0, e1, args);
 }
 
 } // namespace cfmm

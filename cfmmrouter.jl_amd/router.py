@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import MAX_PATH_HOPS, MAX_SPLIT_PATHS, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from ._lib import FOUND_REPEATS, MAX_PATH_HOPS, MAX_SPLIT_PATHS, SPLIT_NONE, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
 from .layout import PoolLayout
 from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
@@ -959,14 +959,83 @@ def _find_path(r: Router, verb, amount_name, token_in, token_out, amount, max_ho
     batch_of = {s: b for b, s in L.seg_of.items()}
     pools, tokens = [], []
     for q in range(len(out)):
-        pl, tk = [], [int(tin[q])] if n_hops[q] else []
-        for k in range(int(n_hops[q])):
-            b = batch_of[int(seg[q, k])]
-            pl.append(int(L.place[int(L.offsets[b]) + int(row[q, k])]))
-            tk.append(int(L.batches[b].Ai[int(row[q, k]), int(co[q, k])]))
+        pl, tk = _found_path(L, batch_of, int(tin[q]), int(n_hops[q]), seg[q], row[q], co[q])
         pools.append(pl)
         tokens.append(tk)
     return out, pools, tokens, status
+
+
+def _found_path(L, batch_of, token_in, n_hops, seg, row, co):
+    """a found path's hops (segment, row, coin_out) as positions in r.cfmms and the 1-based token ids along it; two empty lists
+    where nothing was found"""
+    pl, tk = [], [token_in] if n_hops else []
+    for k in range(n_hops):
+        b = batch_of[int(seg[k])]
+        pl.append(int(L.place[int(L.offsets[b]) + int(row[k])]))
+        tk.append(int(L.batches[b].Ai[int(row[k]), int(co[k])]))
+    return pl, tk
+
+
+def find_disjoint_paths(r: Router, token_in, token_out, amount_in, max_paths=4, max_hops=3, usable_only=True):
+    """SEVERAL swap paths per order that share no pool, FOUND on the device (cfmm_find_disjoint_paths) -- "I have A of X and want
+    Y: which routes are there?", the link between `find_path` (one path) and `split_paths` (an order spread over the paths it is
+    given).  For every query up to `max_paths` (1 .. 8) paths from `token_in[q]` to `token_out[q]` (1-based as in `Ai`) of at most
+    `max_hops` pools.  Scalars broadcast.
+
+    Returns (amount_out, pools, tokens, status): `pools[q]` / `tokens[q]` are LISTS OF PATHS, exactly the `pools[g]` / `tokens[g]`
+    that `split_paths` takes (and each path what `quote_path` / `swap_path_` take); `amount_out[q]` and `status[q]` are arrays with
+    one entry per listed path.  The contract is successive search: path r is `find_path`'s answer for `amount_in[q]` on the market
+    without every pool of the query's paths before it -- the best path, the best one that avoids it, and so on; greedy, not "the K
+    best overall".  The first path is `find_path`'s, the amounts do not increase along the list, and `quote_path` at `amount_in[q]`
+    answers each bit for bit.  The same amount probes every round: to split A over K paths, A / K may be the better probe.
+    usable_only=True (the default) leaves out paths whose status is FOUND_REPEATS (a walk that visits a pool twice: `split_paths`
+    would refuse it; its pools stay banned for the paths after it); with False they are listed with their status.  A query for
+    which nothing is found has empty lists.  Host-evaluated plugin pools are NOT searched.  Read-only, like `quote`."""
+    L = r._layout
+    try:
+        tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int64).reshape(-1), np.asarray(token_out, dtype=np.int64).reshape(-1),
+                                             np.asarray(amount_in, dtype=np.float64).reshape(-1))
+    except ValueError:
+        raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+    for name, t in (("token_in", tin), ("token_out", tout)):
+        bad = np.flatnonzero((t < 1) | (t > r.n_tokens))
+        if bad.size:
+            raise ArgumentError(f"query {int(bad[0])}: {name} {int(t[bad[0]])} out of range 1:{r.n_tokens}")
+    n_paths, out, n_hops, seg, row, ci, co, status = _path_context(r).find_disjoint_paths(tin - 1, tout - 1, amt, max_paths, max_hops)
+    batch_of = {s: b for b, s in L.seg_of.items()}
+    amounts, pools, tokens, statuses = [], [], [], []
+    for q in range(len(n_paths)):
+        keep = [k for k in range(int(n_paths[q])) if not (usable_only and status[q, k] == FOUND_REPEATS)]
+        found = [_found_path(L, batch_of, int(tin[q]), int(n_hops[q, k]), seg[q, k], row[q, k], co[q, k]) for k in keep]
+        pools.append([pl for pl, _ in found])
+        tokens.append([tk for _, tk in found])
+        amounts.append(out[q, keep])
+        statuses.append(status[q, keep])
+    return amounts, pools, tokens, statuses
+
+
+def route_order(r: Router, token_in, token_out, amount_in, max_paths=4, max_hops=3, rounds=5, probe=None):
+    """find -> split in one call: `find_disjoint_paths` (probed with `probe`, by default the order's amount) and `split_paths` on
+    what it found.  Returns (pools, tokens, path_amount_in, path_amount_out, total_out, status): per order the list of paths and
+    the share and output of each, then the total and the SPLIT_* status, as `split_paths` answers them.  An order for which
+    nothing is found has empty lists, total 0.0 and SPLIT_NONE, and is not sent to `split_paths`.  Nothing is executed:
+    `swap_path_(r, pools[g], tokens[g], path_amount_in[g])` executes order g.  Scalars broadcast."""
+    try:
+        tin, tout, amt = np.broadcast_arrays(np.asarray(token_in).reshape(-1), np.asarray(token_out).reshape(-1),
+                                             np.asarray(amount_in, dtype=np.float64).reshape(-1))
+        look = amt if probe is None else np.broadcast_to(np.asarray(probe, dtype=np.float64).reshape(-1), amt.shape)
+    except ValueError:
+        raise ArgumentError("token_in, token_out, amount_in and probe must be scalars or have one entry per order") from None
+    _, pools, tokens, _ = find_disjoint_paths(r, tin, tout, look, max_paths, max_hops, usable_only=True)
+    n = len(pools)
+    have = [g for g in range(n) if pools[g]]
+    x, y = [np.empty(0) for _ in range(n)], [np.empty(0) for _ in range(n)]
+    total, status = np.zeros(n), np.full(n, SPLIT_NONE, dtype=np.int32)
+    if have:
+        xs, ys, total[have], status[have] = split_paths(r, [pools[g] for g in have], [tokens[g] for g in have], amt[have], rounds)
+        for g, xg, yg in zip(have, xs, ys):
+            x[g], y[g] = xg, yg
+    return pools, tokens, x, y, total, status
 
 
 def _swap_path(r: Router, verb, limit_name, pools, tokens, amount, limit, hops, sync_host):
