@@ -28,6 +28,7 @@ FOUND, FOUND_NONE, FOUND_REPEATS = 0, 1, 2   # CFMM_FOUND*: Context.find_path's 
 SIZED, SIZED_NONE, SIZED_AT_LIMIT, SIZED_NAN = 0, 1, 2, 3   # CFMM_SIZED*: Context.size_path's status
 MAX_SIZE_ROUNDS = 16       # CFMM_MAX_SIZE_ROUNDS
 SPLIT_OK, SPLIT_NONE, SPLIT_NAN, SPLIT_SATURATED = 0, 1, 2, 3   # CFMM_SPLIT_*: Context.split_paths' status
+SPLIT_UNOBTAINABLE = 4     # CFMM_SPLIT_UNOBTAINABLE: Context.split_paths_out's "no path can give another slice"
 MAX_SPLIT_PATHS = 8        # CFMM_MAX_SPLIT_PATHS
 MAX_SPLIT_ROUNDS = 16      # CFMM_MAX_SPLIT_ROUNDS
 
@@ -72,7 +73,7 @@ class CFMMDeviceError(RuntimeError):
 def build(force: bool = False) -> str:
     """Compile libcfmm_amd.so for gfx950 with hipcc (csrc/Makefile)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp", ".h"))]
-    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h", "cfmm_amd_size_path.h", "cfmm_amd_split.h")]
+    srcs += [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("cfmm_amd.h", "cfmm_amd_path_out.h", "cfmm_amd_find_out.h", "cfmm_amd_size_path.h", "cfmm_amd_split.h", "cfmm_amd_split_out.h", "cfmm_amd_find_disjoint.h", "cfmm_amd_find_disjoint_out.h")]
     stale = not os.path.exists(LIB_PATH) or any(
         os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
@@ -155,12 +156,15 @@ def lib():
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_disjoint_paths.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
+    L.cfmm_find_disjoint_paths_out.argtypes = L.cfmm_find_disjoint_paths.argtypes
     L.cfmm_size_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, C.c_int32,
                                  _f64p, _f64p, _f64p, _i32p]
     L.cfmm_size_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 4
     L.cfmm_split_paths.argtypes = [_ctx, C.c_int64, _i64p, _f64p, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, C.c_int32,
                                    _f64p, _f64p, _f64p, _i32p]
     L.cfmm_split_paths_dev.argtypes = [_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
+    L.cfmm_split_paths_out.argtypes = L.cfmm_split_paths.argtypes
+    L.cfmm_split_paths_out_dev.argtypes = L.cfmm_split_paths_dev.argtypes
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     L.cfmm_kernel_times.argtypes = [_ctx, _i64p, _f64p, _i64p, _f64p]
@@ -715,11 +719,25 @@ class Context:
         0.0 and -1.  A walk that visits a pool twice keeps its slot as FOUND_REPEATS.  The same amount_in probes every round: to
         split A over K paths, probing with A / K may serve better.  Scalars broadcast.  Read-only.  Everything is checked before
         anything runs (ArgumentError names the query)."""
+        return self._find_disjoint("cfmm_find_disjoint_paths", "amount_in", token_in, token_out, amount_in, max_paths, max_hops)
+
+    def find_disjoint_paths_out(self, token_in, token_out, amount_out, max_paths=4, max_hops=3):
+        """find_disjoint_paths for a wanted output (cfmm_find_disjoint_paths_out): up to max_paths paths from token_in[q] to
+        token_out[q] that share NO POOL, path r being find_path_out's answer for (token_in, token_out, amount_out, max_hops) on
+        the market without every pool of the query's paths 0 .. r-1.  Returns (n_paths [count], amount_in [count, K], n_hops
+        [count, K], seg, row, ci, co [count, K, max_hops], status [count, K]).  Slot 0 is find_path_out's answer, the amounts do
+        not decrease with r, quote_path_out on path r at amount_out[q] answers amount_in[q, r] bit for bit; empty slots carry
+        FOUND_NONE, 0 hops, -1 and find_path_out's none value (+inf, or 0.0 where amount_out is 0).  The same amount_out probes
+        every round, and a path that cannot give it alone is never found: to buy B through K paths probe with about B / K.
+        Scalars broadcast.  Read-only.  Everything is checked before anything runs (ArgumentError names the query)."""
+        return self._find_disjoint("cfmm_find_disjoint_paths_out", "amount_out", token_in, token_out, amount_out, max_paths, max_hops)
+
+    def _find_disjoint(self, entry, amount_name, token_in, token_out, amount_in, max_paths, max_hops):
         try:
             tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int32).reshape(-1), np.asarray(token_out, dtype=np.int32).reshape(-1),
                                                  f64(amount_in).reshape(-1))
         except ValueError:
-            raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+            raise ArgumentError(f"token_in, token_out and {amount_name} must be scalars or have one entry per query") from None
         tin, tout, amt = (np.ascontiguousarray(a) for a in (tin, tout, amt))
         n, H, K = amt.size, int(max_hops), int(max_paths)
         kk, hh = max(K, 0), max(H, 0)
@@ -727,8 +745,8 @@ class Context:
         nh, st = (np.empty((kk, n), dtype=np.int32) for _ in range(2))
         seg, ci, co = (np.empty((kk, hh, n), dtype=np.int32) for _ in range(3))
         row = np.empty((kk, hh, n), dtype=np.int64)
-        self._check(self._L.cfmm_find_disjoint_paths(self._h, n, K, H, ptr(tin), ptr(tout), ptr(amt), ptr(npaths), ptr(out), ptr(nh), ptr(st),
-                                                     ptr(seg), ptr(row), ptr(ci), ptr(co)))
+        self._check(getattr(self._L, entry)(self._h, n, K, H, ptr(tin), ptr(tout), ptr(amt), ptr(npaths), ptr(out), ptr(nh), ptr(st),
+                                            ptr(seg), ptr(row), ptr(ci), ptr(co)))
         hops = lambda a: np.ascontiguousarray(a.transpose(2, 0, 1))
         return npaths, out.T.copy(), nh.T.copy(), hops(seg), hops(row), hops(ci), hops(co), st.T.copy()
 
@@ -809,6 +827,44 @@ class Context:
                                                  int(n_paths), int(max_hops), *(C.c_void_p(p or None) for p in (
             d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out)), int(rounds),
             *(C.c_void_p(p or None) for p in (d_path_amount_in, d_path_amount_out, d_total_out, d_status))))
+
+    # -- buying through several paths (cfmm_split_paths_out): a wanted amount spread over an order's 1 .. 8 paths ----------
+    def split_paths_out(self, order_first, amount_out, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, rounds=5):
+        """How much of each order's wanted amount is bought through each of its paths (cfmm_split_paths_out): split_paths'
+        arguments with amount_out[g], the amount of the paths' common last token to buy.  Returns (path_amount_out [n_paths],
+        path_amount_in [n_paths], total_in [orders], status [orders]).  The contract is the greedy search of
+        include/cfmm_amd_split_out.h: split_paths' grid laid over the output; each round hands out 63 slices of what is left,
+        one by one, to the path whose next slice COSTS the least (the smallest path among equals; +inf is a number, NaN
+        loses), then steps every share back one slice and refines.  On a SPLIT_OK order the shares sum to the amount (to its
+        rounding), with one path the share is the amount bit for bit, and quote_path_out at path_amount_out answers
+        path_amount_in bit for bit.  status[g] is SPLIT_OK; SPLIT_UNOBTAINABLE (the first step that was not finite took +inf:
+        no path can give another slice -- costs and total +inf, shares 0.0; the search's verdict on its grid: paths that
+        jointly give less than amount * (1 + K/63) may be refused though a finer split exists); SPLIT_NONE (amount 0: zeros)
+        or SPLIT_NAN.  No pool may occur twice among an order's paths.  Every hop is quoted against the pool as it stands.
+        Read-only.  Everything is checked before anything runs (ArgumentError names the order)."""
+        first = np.ascontiguousarray(order_first, dtype=np.int64).reshape(-1)
+        amt = np.ascontiguousarray(f64(amount_out).reshape(-1))
+        if first.size != amt.size + 1:
+            raise ArgumentError("order_first must have one entry more than amount_out")
+        nh0 = np.ascontiguousarray(n_hops, dtype=np.int32).reshape(-1)
+        n = nh0.size
+        nh, seg, row, ci, co = self._path_columns(nh0, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        max_hops = max(1, int(seg.shape[0]))
+        g = amt.size
+        x, y, tot, st = np.empty(n), np.empty(n), np.empty(g), np.empty(g, dtype=np.int32)
+        self._check(self._L.cfmm_split_paths_out(self._h, g, ptr(first), ptr(amt), n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co),
+                                                 int(rounds), ptr(x), ptr(y), ptr(tot), ptr(st)))
+        return x, y, tot, st
+
+    def split_paths_out_dev(self, count: int, d_order_first: int, d_amount_out: int, n_paths: int, max_hops: int, d_n_hops: int,
+                            d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int, d_hop_coin_out: int, rounds: int, d_path_amount_out: int,
+                            d_path_amount_in: int, d_total_in: int, d_status: int):
+        """cfmm_split_paths_out_dev on device addresses, as split_paths_dev: d_amount_out [count] is read (the wanted amounts),
+        d_path_amount_out (the shares), d_path_amount_in (their costs), d_total_in and d_status are written."""
+        self._check(self._L.cfmm_split_paths_out_dev(self._h, int(count), C.c_void_p(d_order_first or None), C.c_void_p(d_amount_out or None),
+                                                     int(n_paths), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out)), int(rounds),
+            *(C.c_void_p(p or None) for p in (d_path_amount_out, d_path_amount_in, d_total_in, d_status))))
 
     def quote_path_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
                        d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_hop_out: int = 0):

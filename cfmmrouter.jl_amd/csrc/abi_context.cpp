@@ -349,7 +349,7 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     // "time_kernels" its kernel's span (a parent: the sum of its rounds' "quote_ns"); after cfmm_size_path_dev the read waits, as "quote_ns"
     if (key && !std::strcmp(key, "size_launches")) { *value = c->size.launches; return CFMM_OK; }
     if (key && !std::strcmp(key, "size_ns")) return size_ns(const_cast<cfmm_ctx*>(c), value);
-    // read-only, cfmm_split_paths / cfmm_split_paths_dev: the same two of the latest split
+    // read-only, cfmm_split_paths / cfmm_split_paths_out and their _dev forms: the same two of the latest call of either split entry
     if (key && !std::strcmp(key, "split_launches")) { *value = c->split.launches; return CFMM_OK; }
     if (key && !std::strcmp(key, "split_ns")) return split_ns(const_cast<cfmm_ctx*>(c), value);
     // read-only, cfmm_find_path / cfmm_find_path_out (whichever was called last): the latest call's kernel launches, and under

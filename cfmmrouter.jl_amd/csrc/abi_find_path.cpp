@@ -11,11 +11,14 @@
 // word of a min-search) and the two amounts exchanged -- FindArgs::amount_in carries the wanted amount_out.
 // cfmm_find_disjoint_paths (include/cfmm_amd_find_disjoint.h) is the exact-input search run max_paths times per chunk with the
 // kernels that know the ban (find_disjoint_kernels.h): the same table, staging, chunks (find_disjoint_chunk_queries: the ban row
-// counts) and timing, the outputs one dimension larger, round r's finish writing slot r.
+// counts) and timing, the outputs one dimension larger, round r's finish writing slot r.  cfmm_find_disjoint_paths_out
+// (include/cfmm_amd_find_disjoint_out.h) is that call in the other direction, by the Direction find_paths takes: the backwards
+// kernels of each role, the layers cleared to all ones, the none value of cfmm_find_path_out.
 #include "find_checks.h"
 #include "seg_view.h"
 #include "stage_layout.h"
 #include "../../include/cfmm_amd_find_disjoint.h"
+#include "../../include/cfmm_amd_find_disjoint_out.h"
 #include "../../include/cfmm_amd_find_out.h"
 
 #include <algorithm>
@@ -35,6 +38,7 @@ struct Direction {
     double none(double given) const { return !out || given == 0.0 ? 0.0 : __builtin_inf(); }
 };
 constexpr Direction kExactIn{false, "cfmm_find_path", "amount_in"}, kExactOut{true, "cfmm_find_path_out", "amount_out"};
+constexpr Direction kDisjointIn{false, "cfmm_find_disjoint_paths", "amount_in"}, kDisjointOut{true, "cfmm_find_disjoint_paths_out", "amount_out"};
 
 // one record per segment (seg_view.h: from the addresses the segment holds NOW; every stored segment has pools); returns the
 // blocks that cover them (and, where asked, the pools: the numbers an edge and a ban bit carry run below it)
@@ -221,20 +225,21 @@ int find_paths(const Direction& d, cfmm_ctx* c, int64_t count, int32_t max_hops,
     return CFMM_OK;
 }
 
-// cfmm_find_disjoint_paths: find_paths' table, staging, chunks and timing; per chunk the ban rows are cleared once and max_paths
-// rounds follow, each the launches of one exact-input search with the kernels that know the ban, its finish writing slot r
-int find_disjoint(cfmm_ctx* c, int64_t count, int32_t max_paths, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
+// cfmm_find_disjoint_paths / cfmm_find_disjoint_paths_out: find_paths' table, staging, chunks and timing; per chunk the ban rows
+// are cleared once and max_paths rounds follow, each the launches of one search of the direction with the kernels that know
+// the ban, its finish writing slot r.  As in find_paths amount_in is the GIVEN amount and amount_out the ANSWER.
+int find_disjoint(const Direction& d, cfmm_ctx* c, int64_t count, int32_t max_paths, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,
                   const double* amount_in, int32_t* n_paths, double* amount_out, int32_t* n_hops, int32_t* status, int32_t* hop_seg,
                   int64_t* hop_row, int32_t* hop_coin_in, int32_t* hop_coin_out)
 {
     if (!c) return CFMM_ERR_INVALID_ARG;
-    const char* const kWho = "cfmm_find_disjoint_paths";
+    const char* const kWho = d.who;
     if (is_parent(c))
         return fail(c, CFMM_ERR_UNSUPPORTED, "%s is not available on a multi-device context: the layers of the search live on one "
                                              "device (find on a single-device context of the same pools)", kWho);
     char msg[256] = "";
     int rc = check_find_disjoint(kWho, c->n, count, max_paths, max_hops, token_in, token_out, amount_in, n_paths, amount_out, n_hops, status,
-                                 hop_seg, hop_row, hop_coin_in, hop_coin_out, msg, sizeof msg);
+                                 hop_seg, hop_row, hop_coin_in, hop_coin_out, msg, sizeof msg, d.amount);
     if (rc != CFMM_OK) return fail(c, rc, "%s", msg);
     if (count == 0) return CFMM_OK;
     FindScratch& fs = c->find;
@@ -242,7 +247,8 @@ int find_disjoint(cfmm_ctx* c, int64_t count, int32_t max_paths, int32_t max_hop
     const size_t n = (size_t)count, H = (size_t)max_hops, K = (size_t)max_paths, nh = n * H;
     if (c->segs.empty()) {   // a market without pools reaches nothing
         std::fill(n_paths, n_paths + n, 0);
-        std::fill(amount_out, amount_out + K * n, 0.0);
+        for (size_t r = 0; r < K; ++r)
+            for (size_t q = 0; q < n; ++q) amount_out[r * n + q] = d.none(amount_in[q]);
         std::fill(n_hops, n_hops + K * n, 0);
         std::fill(status, status + K * n, CFMM_FOUND_NONE);
         std::fill(hop_seg, hop_seg + K * nh, -1);
@@ -314,18 +320,19 @@ int find_disjoint(cfmm_ctx* c, int64_t count, int32_t max_paths, int32_t max_hop
             a.hop_row = fs.hop_row.get() + r * nh + q0;
             a.layer = 0;
             a.group = 0;
-            HIP_TRY(c, hipMemsetAsync(a.best, 0, (H + 1) * cq * nt * sizeof(unsigned long long), c->stream));
+            HIP_TRY(c, hipMemsetAsync(a.best, d.out ? 0xff : 0, (H + 1) * cq * nt * sizeof(unsigned long long), c->stream));
             HIP_TRY(c, hipMemsetAsync(a.edge, 0xff, H * cq * sizeof(unsigned long long), c->stream));
-            if ((rc = launch(c, timing, kFindInit, a, &b, round)) != CFMM_OK) return rc;
+            if ((rc = launch(c, timing, d.kernel(kFindInit), a, &b, round)) != CFMM_OK) return rc;
             set_lds_group(c, a, cq, tiles);
             for (a.layer = 1; a.layer <= max_hops; ++a.layer)
-                if ((rc = launch(c, timing, kFindRelax, a, &b, round)) != CFMM_OK) return rc;
+                if ((rc = launch(c, timing, d.kernel(kFindRelax), a, &b, round)) != CFMM_OK) return rc;
             a.group = 0;
-            if ((rc = launch(c, timing, kFindSelect, a, nullptr, round)) != CFMM_OK) return rc;
+            if ((rc = launch(c, timing, d.kernel(kFindSelect), a, nullptr, round)) != CFMM_OK) return rc;
             for (a.layer = max_hops; a.layer >= 1; --a.layer)
-                if ((rc = launch(c, timing, kFindClaim, a, &b, round)) || (rc = launch(c, timing, kFindAdvance, a, nullptr, round))) return rc;
+                if ((rc = launch(c, timing, d.kernel(kFindClaim), a, &b, round)) || (rc = launch(c, timing, d.kernel(kFindAdvance), a, nullptr, round)))
+                    return rc;
             a.layer = 0;
-            if ((rc = launch(c, timing, kFindFinish, a, &b, round)) != CFMM_OK) return rc;
+            if ((rc = launch(c, timing, d.kernel(kFindFinish), a, &b, round)) != CFMM_OK) return rc;
         }
     }
     HIP_TRY(c, hipMemcpyAsync(h_out, fs.amt.get() + n, K * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -352,8 +359,17 @@ int cfmm_find_disjoint_paths(cfmm_ctx* c, int64_t count, int32_t max_paths, int3
                              int32_t* n_hops, int32_t* status, int32_t* hop_seg, int64_t* hop_row, int32_t* hop_coin_in,
                              int32_t* hop_coin_out)
 {
-    return find_disjoint(c, count, max_paths, max_hops, token_in, token_out, amount_in, n_paths, amount_out, n_hops, status, hop_seg, hop_row,
-                         hop_coin_in, hop_coin_out);
+    return find_disjoint(kDisjointIn, c, count, max_paths, max_hops, token_in, token_out, amount_in, n_paths, amount_out, n_hops, status, hop_seg,
+                         hop_row, hop_coin_in, hop_coin_out);
+}
+
+int cfmm_find_disjoint_paths_out(cfmm_ctx* c, int64_t count, int32_t max_paths, int32_t max_hops, const int32_t* token_in,
+                                 const int32_t* token_out, const double* amount_out, int32_t* n_paths, double* amount_in,
+                                 int32_t* n_hops, int32_t* status, int32_t* hop_seg, int64_t* hop_row, int32_t* hop_coin_in,
+                                 int32_t* hop_coin_out)
+{
+    return find_disjoint(kDisjointOut, c, count, max_paths, max_hops, token_in, token_out, amount_out, n_paths, amount_in, n_hops, status,
+                         hop_seg, hop_row, hop_coin_in, hop_coin_out);
 }
 
 int cfmm_find_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* token_in, const int32_t* token_out,

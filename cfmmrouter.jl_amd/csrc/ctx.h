@@ -29,6 +29,8 @@
 //                     the search's arithmetic, shared with the kernel)
 //   abi_split_paths.cpp an order's amount spread over several paths (cfmm_split_paths; split_checks.h: the HIP-free checks,
 //                     split_grid.h: the search's arithmetic, shared with the kernel)
+//                     and bought through several paths (cfmm_split_paths_out: the same file, checks and scratch;
+//                     split_out_grid.h: what its search has of its own)
 //   seg_view.h        what those seven share, on top of this header: a segment as their kernels and their checks see it
 //   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
 //   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
@@ -40,6 +42,7 @@
 
 #include "../../include/cfmm_amd.h"
 #include "../../include/cfmm_amd_split.h"
+#include "../../include/cfmm_amd_split_out.h"
 #include "devbuf.h"
 #include "hostres.h"
 #include "ladder_store.h"

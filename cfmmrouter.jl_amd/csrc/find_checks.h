@@ -85,14 +85,14 @@ inline int64_t find_disjoint_chunk_queries(int64_t n_tokens, int32_t max_hops, i
 inline int check_find_disjoint(const char* who, int64_t n_tokens, int64_t count, int32_t max_paths, int32_t max_hops,
                                const int32_t* token_in, const int32_t* token_out, const double* amount_in, const void* n_paths,
                                const void* amount_out, const void* n_hops, const void* status, const void* hop_seg, const void* hop_row,
-                               const void* hop_coin_in, const void* hop_coin_out, char* msg, size_t len)
+                               const void* hop_coin_in, const void* hop_coin_out, char* msg, size_t len, const char* amount = "amount_in")
 {
     if (count >= 0 && (max_paths < 1 || max_paths > CFMM_MAX_SPLIT_PATHS)) {
         std::snprintf(msg, len, "%s: max_paths must be 1 .. %d (got %d)", who, CFMM_MAX_SPLIT_PATHS, (int)max_paths);
         return CFMM_ERR_INVALID_ARG;
     }
     return check_find(who, n_tokens, count, max_hops, token_in, token_out, amount_in, amount_out, n_hops, hop_seg, hop_row, hop_coin_in,
-                      hop_coin_out, count > 0 && !n_paths ? nullptr : status, msg, len);
+                      hop_coin_out, count > 0 && !n_paths ? nullptr : status, msg, len, amount);
 }
 
 } // namespace cfmm

@@ -1,5 +1,5 @@
 // find_disjoint_kernels.h -- cfmm_find_disjoint_paths: up to 8 paths per query that share no pool, by SUCCESSIVE runs of
-// cfmm_find_path's layered search (find_path_kernels.h, forwards only) in which every pool of the query's earlier paths is
+// cfmm_find_path's layered search (find_path_kernels.h; cfmm_find_disjoint_paths_out: of cfmm_find_path_out's) in which every pool of the query's earlier paths is
 // ABSENT.  The ban is a bitmap in device memory: one row of ban_words 64-bit words per query of the chunk, bit p & 63 of word
 // p >> 6 for pool number p = first_pool + row -- the number find_pack packs into an edge.  Round r is
 //   find_ban_init     find_init, but a query that has ENDED (an earlier round found nothing for it) puts nothing into layer 0:
@@ -17,9 +17,17 @@
 //                     slot), and: the path's pools are ORed into the query's ban row, the query is marked ended when nothing
 //                     was found, n_paths is written (round 0) or incremented.  ONE LANE OWNS ITS QUERY'S ROW, so plain loads
 //                     and vector stores do: no atomics.
-// The text stands in the __global__ functions themselves (find_dir_kernels.h says why).  The existing fourteen search kernels
+// cfmm_find_disjoint_paths_out is the same with the direction turned (find_out_ban_init .. find_out_ban_finish; select and advance
+// are find_out_select and find_out_advance, unchanged): the text of the four kernels stands ONCE, in the second half of THIS
+// file, which includes itself once per direction as find_path_kernels.h includes find_dir_kernels.h: with CFMM_FIND_BAN
+// defined an inclusion yields the kernels' text alone, CFMM_FIND_OUT the direction and CFMM_FIND_BAN(role) the kernel's name
+// (find_ban_init .. find_ban_finish, find_out_ban_init .. find_out_ban_finish).  Everything that differs between the directions
+// is FindDir<OUT> (find_path_kernels.h), used exactly as find_dir_kernels.h uses it.  With OUT false every line is the forward
+// kernel's as it was: the four forward kernels compile to the instructions they had.  The existing fourteen search kernels
 // are not touched: FindArgs is theirs, what the ban needs travels in FindBanArgs.
-#pragma once
+#if !defined(CFMM_FIND_BAN)   /* ---- the header proper, once ---- */
+#ifndef CFMM_FIND_DISJOINT_KERNELS_H
+#define CFMM_FIND_DISJOINT_KERNELS_H
 
 #include "find_path_kernels.h"
 
@@ -30,22 +38,44 @@ __device__ __forceinline__ bool find_banned(const FindBanArgs& b, long long q, l
     return (b.ban[q * b.ban_words + (pool >> 6)] >> (pool & 63)) & 1ull;
 }
 
+#define CFMM_FIND_OUT false
+#define CFMM_FIND_BAN(role) find_ban_##role
+#include "find_disjoint_kernels.h"
+#undef CFMM_FIND_OUT
+#undef CFMM_FIND_BAN
+#define CFMM_FIND_OUT true
+#define CFMM_FIND_BAN(role) find_out_ban_##role
+#include "find_disjoint_kernels.h"
+#undef CFMM_FIND_OUT
+#undef CFMM_FIND_BAN
+
+} // namespace cfmm
+
+// (what came after this header is included from here, behind everything above: find_path_kernels.h's rule)
+#include "split_paths_out_kernels.h"
+
+#endif
+#else   /* ---- the four kernels' text, once per direction (inside namespace cfmm) ---- */
+
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void find_ban_init(FindArgs a, FindBanArgs b)
+__global__ __launch_bounds__(BLOCK) void CFMM_FIND_BAN(init)(FindArgs a, FindBanArgs b)
 {
+    constexpr bool OUT = CFMM_FIND_OUT;
+    using D = FindDir<OUT>;
     const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= a.count) return;
     if (b.round > 0 && b.ended[q]) return;
-    const double x = a.amount_in[q];
-    const int t = a.token_in[q];
+    const double x = a.amount_in[q];   // (backwards: the wanted amount_out)
+    const int t = D::start_token(a)[q];
     if (find_enters(x) && t >= 0 && t < a.n_tokens) a.best[q * a.n_tokens + t] = (unsigned long long)__double_as_longlong(x);
 }
 
 // find_relax's grids and LDS copy (find_dir_kernels.h); a pool's number is < the table's pools, so its word is < ban_words
 template <int BLOCK, bool LDS>
-__global__ __launch_bounds__(BLOCK) void find_ban_relax(FindArgs a, FindBanArgs b)
+__global__ __launch_bounds__(BLOCK) void CFMM_FIND_BAN(relax)(FindArgs a, FindBanArgs b)
 {
-    using D = FindDir<false>;
+    constexpr bool OUT = CFMM_FIND_OUT;
+    using D = FindDir<OUT>;
     extern __shared__ unsigned long long find_rows[];   // [group][n_tokens], LDS only
     const int group = LDS ? a.group : kFindLaneQueries;
     const long long q0 = (long long)blockIdx.y * group;
@@ -93,7 +123,7 @@ __global__ __launch_bounds__(BLOCK) void find_ban_relax(FindArgs a, FindBanArgs 
                 const double amt = __longlong_as_double((long long)bits);
                 for (int far = 0; far < nc; ++far) {
                     if (far == near) continue;
-                    const double r = find_quote<false>(f.s, kind, m, row, near, far, amt);
+                    const double r = find_quote<OUT>(f.s, kind, m, row, near, far, amt);
                     if (find_enters(r)) D::template fold<LDS>(cj + tok[far], (unsigned long long)__double_as_longlong(r));
                 }
             }
@@ -109,9 +139,10 @@ __global__ __launch_bounds__(BLOCK) void find_ban_relax(FindArgs a, FindBanArgs 
 }
 
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void find_ban_claim(FindArgs a, FindBanArgs b)
+__global__ __launch_bounds__(BLOCK) void CFMM_FIND_BAN(claim)(FindArgs a, FindBanArgs b)
 {
-    using D = FindDir<false>;
+    constexpr bool OUT = CFMM_FIND_OUT;
+    using D = FindDir<OUT>;
     const int sg = find_segment<true>(a.segs, a.nseg, blockIdx.x);
     const FindSeg& f = a.segs[sg];
     const int kind = f.s.kind;
@@ -127,7 +158,7 @@ __global__ __launch_bounds__(BLOCK) void find_ban_claim(FindArgs a, FindBanArgs 
     for (int j = 0; j < nq; ++j) {
         const long long q = q0 + j;
         const int hs = a.h_star[q];
-        if (hs < a.layer) continue;
+        if (hs < a.layer || (OUT && hs > a.max_hops)) continue;
         const int t = a.target[q];
         if (t < 0 || t >= a.n_tokens) continue;
         const unsigned long long* pj = a.best + (long long)(a.layer - 1) * layer_words + q * a.n_tokens;
@@ -144,9 +175,9 @@ __global__ __launch_bounds__(BLOCK) void find_ban_claim(FindArgs a, FindBanArgs 
                 if (near == far) continue;
                 const unsigned long long bits = pj[tok[near]];
                 if (!D::reached(bits)) continue;
-                const double r = find_quote<false>(f.s, kind, m, row, near, far, __longlong_as_double((long long)bits));
+                const double r = find_quote<OUT>(f.s, kind, m, row, near, far, __longlong_as_double((long long)bits));
                 if (find_enters(r) && (unsigned long long)__double_as_longlong(r) == want)
-                    atomicMin(a.edge + (long long)D::slot(a.layer, hs) * a.count + q, find_pack(f.first_pool + row, near, far, false));
+                    atomicMin(a.edge + (long long)D::slot(a.layer, hs) * a.count + q, find_pack(f.first_pool + row, near, far, OUT));
             }
         }
     }
@@ -155,8 +186,10 @@ __global__ __launch_bounds__(BLOCK) void find_ban_claim(FindArgs a, FindBanArgs 
 // find_finish (the outputs of query q at q and k*stride + q of pointers that stand at slot r and the chunk's first query), then
 // the ban row, the ended mark and n_paths
 template <int BLOCK>
-__global__ __launch_bounds__(BLOCK) void find_ban_finish(FindArgs a, FindBanArgs b)
+__global__ __launch_bounds__(BLOCK) void CFMM_FIND_BAN(finish)(FindArgs a, FindBanArgs b)
 {
+    constexpr bool OUT = CFMM_FIND_OUT;
+    using D = FindDir<OUT>;
     const long long q = (long long)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= a.count) return;
     int h = a.h_star[q];
@@ -182,9 +215,9 @@ __global__ __launch_bounds__(BLOCK) void find_ban_finish(FindArgs a, FindBanArgs
         a.hop_coin_out[at] = used ? co[k] : -1;
     }
     const long long layer_words = a.count * (long long)a.n_tokens;
-    const int t = find_clamp_token(a.token_out[q], a.n_tokens);
+    const int t = find_clamp_token(D::end_token(a)[q], a.n_tokens);
     a.n_hops[q] = h;
-    a.amount_out[q] = h ? __longlong_as_double((long long)a.best[(long long)h * layer_words + q * a.n_tokens + t]) : 0.0;
+    a.amount_out[q] = h ? __longlong_as_double((long long)a.best[(long long)h * layer_words + q * a.n_tokens + t]) : D::none(a.amount_in[q]);
     a.status[q] = !h ? CFMM_FOUND_NONE : (repeats ? CFMM_FOUND_REPEATS : CFMM_FOUND);
     // the path's pools leave the market of this query's later rounds (find_decode accepted each: the number is a pool's)
     for (int k = 0; k < CFMM_MAX_PATH_HOPS; ++k)
@@ -196,4 +229,4 @@ __global__ __launch_bounds__(BLOCK) void find_ban_finish(FindArgs a, FindBanArgs
     b.n_paths[q] = (b.round > 0 ? b.n_paths[q] : 0) + (h != 0);
 }
 
-} // namespace cfmm
+#endif

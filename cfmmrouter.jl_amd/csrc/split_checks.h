@@ -1,4 +1,5 @@
-// split_checks.h -- internal, host only, HIP-free: the checks of cfmm_split_paths / cfmm_split_paths_dev (abi_split_paths.cpp)
+// split_checks.h -- internal, host only, HIP-free: the checks of cfmm_split_paths / cfmm_split_paths_dev and of their
+// exact-output twins cfmm_split_paths_out / cfmm_split_paths_out_dev, the same checks under the other name (abi_split_paths.cpp)
 // beyond those of the paths themselves, which stay path_checks.h's check_paths: the scalars, the orders' path ranges and
 // amounts, and the rule that no pool occurs twice among the hops of one order's paths.  As there, a refusal's text goes into a
 // caller's buffer, so a host program without a device or a context can exercise them (tests/native/split_checks_host.cpp).
@@ -50,8 +51,9 @@ inline int check_split_arrays(const char* who, int64_t count, const void* order_
 }
 
 // every order's path range and amount of a host-pointer call (the arrays are known not to be null)
+// (`amount_name`: what the entry calls the amount -- cfmm_split_paths_out's is amount_out)
 inline int check_split_orders(const char* who, int64_t count, const int64_t* order_first, const double* amount_in, int64_t n_paths,
-                              char* msg, size_t len)
+                              char* msg, size_t len, const char* amount_name = "amount_in")
 {
     if (count == 0) {
         if (n_paths != 0) {
@@ -81,7 +83,7 @@ inline int check_split_orders(const char* who, int64_t count, const int64_t* ord
             return CFMM_ERR_INVALID_ARG;
         }
         if (!split_amount_ok(amount_in[g])) {
-            std::snprintf(msg, len, "%s: order %lld: amount_in must be finite and >= 0", who, (long long)g);
+            std::snprintf(msg, len, "%s: order %lld: %s must be finite and >= 0", who, (long long)g, amount_name);
             return CFMM_ERR_INVALID_ARG;
         }
     }
@@ -142,13 +144,13 @@ inline int check_split(const char* who, const PathSegInfo* segs, int64_t nseg, i
                        const double* amount_in, int64_t n_paths, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg,
                        const int64_t* hop_row, const int32_t* hop_coin_in, const int32_t* hop_coin_out, int32_t rounds,
                        const void* path_amount_in, const void* path_amount_out, const void* total_out, const void* status, char* msg,
-                       size_t len)
+                       size_t len, const char* amount_name = "amount_in")
 {
     int rc;
     if ((rc = check_split_scalars(who, count, n_paths, max_hops, rounds, msg, len)) ||
         (rc = check_split_arrays(who, count, order_first, amount_in, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, path_amount_in,
                                  path_amount_out, total_out, status, msg, len)) ||
-        (rc = check_split_orders(who, count, order_first, amount_in, n_paths, msg, len)))
+        (rc = check_split_orders(who, count, order_first, amount_in, n_paths, msg, len, amount_name)))
         return rc;
     if (count == 0) return CFMM_OK;
     // (check_paths wants an amount per path: the paths have none of their own, so it is given zeros)

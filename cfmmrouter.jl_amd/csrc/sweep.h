@@ -528,6 +528,10 @@ constexpr int kSplitBlock = 256;                                  // four wavefr
 constexpr int kSplitMaxBlocks = kResidentThreads / kSplitBlock;   // default of option "split_max_blocks": one machine of resident wavefronts
 // max_blocks >= 1 caps the grid (the wavefronts stride over the orders).  e0, e1: both set = the launch is timed.
 hipError_t launch_split_paths(const SplitArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// cfmm_split_paths_out (split_paths_out_kernels.h): the same arguments with the roles of the amounts exchanged, as PathArgs
+// serves both quote directions -- amount carries the wanted output B, p.answer receives path_amount_out (the shares of B),
+// path_out receives path_amount_in (what each share costs), total is total_in.  The same block, the same grid rule.
+hipError_t launch_split_paths_out(const SplitArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
 // cfmm_swap_path (swap_path_kernels.h, abi_swap_path.cpp): exact-input paths that MOVE their pools, all or nothing, one lane per
 // path of ONE WAVE -- paths that share no pool (the host numbers the waves: swap_path_waves.h).  The kernel reads a table of

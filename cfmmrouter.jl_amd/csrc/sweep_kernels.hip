@@ -50,7 +50,9 @@
 //   find_path_kernels.h  find_relax and the walk back (cfmm_find_path: the best walk between two tokens, a layer per launch, one lane per pool)
 //   size_path_kernels.h  size_path_kernel (cfmm_size_path: the input that maximises a path's gain, one wavefront per path, one lane per trial size)
 //   split_paths_kernels.h  split_paths_kernel (cfmm_split_paths: an order's amount spread over its paths, one wavefront per order, one lane per grid point)
-//   find_disjoint_kernels.h  find_ban_relax and the walk back (cfmm_find_disjoint_paths: find_path's search with a per-query bitmap of absent pools)
+//   find_disjoint_kernels.h  find_ban_relax and the walk back (cfmm_find_disjoint_paths: find_path's search with a per-query bitmap of absent pools;
+//                            find_out_ban_relax and its walk: cfmm_find_disjoint_paths_out, the same text in the other direction: the header includes its second half once per direction)
+//   split_paths_out_kernels.h  split_paths_out_kernel (cfmm_split_paths_out: a wanted amount bought through an order's paths, split_paths_kernel's shape, the hops walked backwards)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -69,7 +71,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, and from that one's find_disjoint_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -489,13 +491,13 @@ hipError_t launch_split_paths(const SplitArgs& a, int64_t max_blocks, hipStream_
     return launch_k(reinterpret_cast<const void*>(&split_paths_kernel<kSplitBlock>), dim3((unsigned)blocks), dim3(kSplitBlock), 0, s, e0, e1, args);
 }
 
-// cfmm_find_disjoint_paths: launch_find's grids for the four kernels that know the ban.  (Behind every other launcher, for
+// cfmm_find_disjoint_paths / cfmm_find_disjoint_paths_out: launch_find's grids for the four kernels per direction that know the ban.  (Behind every other launcher, for
 // launch_size_path's reason.)
 hipError_t launch_find_ban(FindKernel which, const FindArgs& a, const FindBanArgs& b, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     dim3 grid;
     size_t lds_bytes;
-    const hipError_t shape = find_launch_shape(which, a, grid, lds_bytes);
+    const hipError_t shape = find_launch_shape(which >= kFindOutFirst ? which - kFindOutFirst : which, a, grid, lds_bytes);   // (the backwards kernels take the same grids)
     if (shape != hipSuccess) return shape;
     if (!b.ban || b.ban_words < 1 || !b.ended || !b.n_paths || b.round < 0 || b.round >= CFMM_MAX_SPLIT_PATHS) return hipErrorInvalidValue;
     const void* kernel;
@@ -504,10 +506,27 @@ hipError_t launch_find_ban(FindKernel which, const FindArgs& a, const FindBanArg
     case kFindRelax: kernel = lds_bytes > 0 ? reinterpret_cast<const void*>(&find_ban_relax<kFindBlock, true>) : reinterpret_cast<const void*>(&find_ban_relax<kFindBlock, false>); break;
     case kFindClaim: kernel = reinterpret_cast<const void*>(&find_ban_claim<kFindBlock>); break;
     case kFindFinish: kernel = reinterpret_cast<const void*>(&find_ban_finish<kFindBlock>); break;
+    // cfmm_find_disjoint_paths_out (behind the four above: templates are emitted in the order they are named)
+    case kFindOutInit: kernel = reinterpret_cast<const void*>(&find_out_ban_init<kFindBlock>); break;
+    case kFindOutRelax: kernel = lds_bytes > 0 ? reinterpret_cast<const void*>(&find_out_ban_relax<kFindBlock, true>) : reinterpret_cast<const void*>(&find_out_ban_relax<kFindBlock, false>); break;
+    case kFindOutClaim: kernel = reinterpret_cast<const void*>(&find_out_ban_claim<kFindBlock>); break;
+    case kFindOutFinish: kernel = reinterpret_cast<const void*>(&find_out_ban_finish<kFindBlock>); break;
     default: return hipErrorInvalidDeviceFunction;   // select and advance know no ban: launch_find
     }
     void* args[] = {const_cast<FindArgs*>(&a), const_cast<FindBanArgs*>(&b)};
     return launch_k(kernel, grid, dim3(kFindBlock), lds_bytes, s, e0, e1, args);
+}
+
+// cfmm_split_paths_out: launch_split_paths' checks and grid.  (Behind every other launcher, for launch_size_path's reason.)
+hipError_t launch_split_paths_out(const SplitArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.orders <= 0 || a.p.count <= 0 || a.p.nseg <= 0 || a.p.max_hops < 1 || a.p.max_hops > CFMM_MAX_PATH_HOPS || a.rounds < 1 ||
+        a.rounds > CFMM_MAX_SPLIT_ROUNDS || max_blocks < 1 || !a.order_first || !a.amount || !a.p.answer || !a.path_out || !a.total || !a.status)
+        return hipErrorInvalidValue;
+    constexpr int64_t per_block = kSplitBlock / CFMM_SPLIT_POINTS;
+    const int64_t blocks = std::min<int64_t>({(a.orders + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
+    void* args[] = {const_cast<SplitArgs*>(&a)};
+    return launch_k(reinterpret_cast<const void*>(&split_paths_out_kernel<kSplitBlock>), dim3((unsigned)blocks), dim3(kSplitBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm

@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import FOUND_REPEATS, MAX_PATH_HOPS, MAX_SPLIT_PATHS, SPLIT_NONE, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from ._lib import FOUND_REPEATS, MAX_PATH_HOPS, MAX_SPLIT_PATHS, SPLIT_NONE, SPLIT_UNOBTAINABLE, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
 from .layout import PoolLayout
 from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
@@ -913,13 +913,36 @@ def split_paths(r: Router, pools, tokens, amount_in, rounds=5):
     closed-form optimum for 99 % of the orders and within 1.6e-7 for all.  status[g] is SPLIT_OK, SPLIT_SATURATED (part of the
     amount buys nothing: the paths cannot absorb it), SPLIT_NONE (amount 0, or nothing comes out: zeros) or SPLIT_NAN.
     `swap_path_(r, pools[g], tokens[g], path_amount_in[g])` executes order g's split.  Read-only, like `quote`."""
+    return _split_paths(r, "split_paths", "amount_in", pools, tokens, amount_in, rounds)
+
+
+def split_paths_out(r: Router, pools, tokens, amount_out, rounds=5):
+    """HOW MUCH OF A WANTED AMOUNT COMES OUT OF EACH PATH, on the pools as they stand on the device (cfmm_split_paths_out) -- "I
+    want B of Y and have these K routes from X; how much do I buy through each?".  `pools`, `tokens`, the mapping and every
+    refusal are `split_paths`'; `amount_out[g]` is the amount of the paths' common last token that order g buys (a scalar
+    broadcasts).
+
+    Returns (path_amount_out, path_amount_in, total_in, status): the first two are lists shaped like `pools` (the share of
+    `amount_out[g]` bought through each path, and what `quote_path_out` answers for it bit for bit), the last two arrays with
+    one entry per order.  The contract is `split_paths`' greedy search laid over the output: a round hands out 63 slices of what
+    is left, each to the path whose next slice COSTS the least (+inf where a path cannot give that much), then steps every share
+    back one slice and refines.  status[g] is SPLIT_OK; SPLIT_UNOBTAINABLE (a step found no path that can give another slice:
+    costs and total +inf, shares 0.0 -- the search's verdict on its grid: paths that jointly give less than
+    amount_out * (1 + K/63) may be refused though a finer split exists); SPLIT_NONE (amount 0: zeros) or SPLIT_NAN.  Three paths
+    that can each give half of B fill an order that `quote_path_out` answers +inf for on every one of them.
+    `swap_path_out_(r, pools[g], tokens[g], path_amount_out[g], max_in=path_amount_in[g])` executes order g's split.  Read-only,
+    like `quote`."""
+    return _split_paths(r, "split_paths_out", "amount_out", pools, tokens, amount_out, rounds)
+
+
+def _split_paths(r: Router, verb, amount_name, pools, tokens, amount_in, rounds):
     pools, tokens = [list(o) for o in pools], [list(o) for o in tokens]
     if len(tokens) != len(pools):
         raise ArgumentError("tokens must have one list of paths per order")
     try:
         amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (len(pools),)))
     except ValueError:
-        raise ArgumentError("amount_in must be a scalar or have one entry per order") from None
+        raise ArgumentError(f"{amount_name} must be a scalar or have one entry per order") from None
     for g, (pl, tk) in enumerate(zip(pools, tokens)):
         if not 1 <= len(pl) <= MAX_SPLIT_PATHS:
             raise ArgumentError(f"order {g}: {len(pl)} paths (an order has 1 to {MAX_SPLIT_PATHS})")
@@ -927,7 +950,7 @@ def split_paths(r: Router, pools, tokens, amount_in, rounds=5):
             raise ArgumentError(f"order {g}: {len(tk)} token sequences for {len(pl)} paths")
     first = np.concatenate(([0], np.cumsum([len(pl) for pl in pools]))).astype(np.int64)
     flat_pools, flat_tokens = [p for pl in pools for p in pl], [t for tk in tokens for t in tk]
-    n_hops, seg, row, ci, co, _, _ = _path_hops(r, "split_paths", flat_pools, flat_tokens, 0.0)
+    n_hops, seg, row, ci, co, _, _ = _path_hops(r, verb, flat_pools, flat_tokens, 0.0)
     for g, (pl, tk) in enumerate(zip(pools, tokens)):
         ends = {(int(np.asarray(t).reshape(-1)[0]), int(np.asarray(t).reshape(-1)[-1])) for t in tk}
         if len(ends) != 1:
@@ -939,7 +962,7 @@ def split_paths(r: Router, pools, tokens, amount_in, rounds=5):
                     raise ArgumentError(f"order {g}: paths {seen[i]} and {k} share pool {i} (the paths are quoted independently "
                                         f"against the standing market, so a shared pool would be counted twice)")
                 seen[i] = k
-    x, y, total, status = _path_context(r).split_paths(first, amt, n_hops, seg, row, ci, co, rounds)
+    x, y, total, status = getattr(_path_context(r), verb)(first, amt, n_hops, seg, row, ci, co, rounds)
     cut = lambda v: [v[first[g]:first[g + 1]] for g in range(len(pools))]
     return cut(x), cut(y), total, status
 
@@ -991,17 +1014,33 @@ def find_disjoint_paths(r: Router, token_in, token_out, amount_in, max_paths=4, 
     usable_only=True (the default) leaves out paths whose status is FOUND_REPEATS (a walk that visits a pool twice: `split_paths`
     would refuse it; its pools stay banned for the paths after it); with False they are listed with their status.  A query for
     which nothing is found has empty lists.  Host-evaluated plugin pools are NOT searched.  Read-only, like `quote`."""
+    return _find_disjoint(r, "find_disjoint_paths", "amount_in", token_in, token_out, amount_in, max_paths, max_hops, usable_only)
+
+
+def find_disjoint_paths_out(r: Router, token_in, token_out, amount_out, max_paths=4, max_hops=3, usable_only=True):
+    """SEVERAL swap paths per order that share no pool, FOUND on the device FOR A WANTED OUTPUT (cfmm_find_disjoint_paths_out) -- "I
+    want B of Y and pay in X: which routes are there?", the link between `find_path_out` (one path) and `split_paths_out`.
+    `find_disjoint_paths`' arguments and answer with the direction turned: returns (amount_in, pools, tokens, status), `pools[q]` /
+    `tokens[q]` lists of paths as `split_paths_out` takes them, `amount_in[q]` what each listed path asks for `amount_out[q]`.
+    Path r is `find_path_out`'s answer on the market without every pool of the query's paths before it: the first path is
+    `find_path_out`'s, the amounts do not decrease along the list, and `quote_path_out` at `amount_out[q]` answers each bit for
+    bit.  The same amount probes every round, and A PATH THAT CANNOT GIVE IT ALONE IS NEVER FOUND: to buy B through K paths probe
+    with about B / K (`route_order_out` does).  usable_only as in `find_disjoint_paths`.  Read-only, like `quote`."""
+    return _find_disjoint(r, "find_disjoint_paths_out", "amount_out", token_in, token_out, amount_out, max_paths, max_hops, usable_only)
+
+
+def _find_disjoint(r: Router, verb, amount_name, token_in, token_out, amount_in, max_paths, max_hops, usable_only):
     L = r._layout
     try:
         tin, tout, amt = np.broadcast_arrays(np.asarray(token_in, dtype=np.int64).reshape(-1), np.asarray(token_out, dtype=np.int64).reshape(-1),
                                              np.asarray(amount_in, dtype=np.float64).reshape(-1))
     except ValueError:
-        raise ArgumentError("token_in, token_out and amount_in must be scalars or have one entry per query") from None
+        raise ArgumentError(f"token_in, token_out and {amount_name} must be scalars or have one entry per query") from None
     for name, t in (("token_in", tin), ("token_out", tout)):
         bad = np.flatnonzero((t < 1) | (t > r.n_tokens))
         if bad.size:
             raise ArgumentError(f"query {int(bad[0])}: {name} {int(t[bad[0]])} out of range 1:{r.n_tokens}")
-    n_paths, out, n_hops, seg, row, ci, co, status = _path_context(r).find_disjoint_paths(tin - 1, tout - 1, amt, max_paths, max_hops)
+    n_paths, out, n_hops, seg, row, ci, co, status = getattr(_path_context(r), verb)(tin - 1, tout - 1, amt, max_paths, max_hops)
     batch_of = {s: b for b, s in L.seg_of.items()}
     amounts, pools, tokens, statuses = [], [], [], []
     for q in range(len(n_paths)):
@@ -1033,6 +1072,40 @@ def route_order(r: Router, token_in, token_out, amount_in, max_paths=4, max_hops
     total, status = np.zeros(n), np.full(n, SPLIT_NONE, dtype=np.int32)
     if have:
         xs, ys, total[have], status[have] = split_paths(r, [pools[g] for g in have], [tokens[g] for g in have], amt[have], rounds)
+        for g, xg, yg in zip(have, xs, ys):
+            x[g], y[g] = xg, yg
+    return pools, tokens, x, y, total, status
+
+
+def route_order_out(r: Router, token_in, token_out, amount_out, max_paths=4, max_hops=3, rounds=5, probe=None):
+    """find -> split in one call for an order that BUYS an exact amount: `find_disjoint_paths_out` (probed with `probe`) and
+    `split_paths_out` on what it found.  Returns (pools, tokens, path_amount_out, path_amount_in, total_in, status): per order
+    the list of paths, the share of `amount_out[g]` bought through each and what it costs, then the total cost and the SPLIT_*
+    status, as `split_paths_out` answers them.
+
+    THE DEFAULT PROBE IS `amount_out / max_paths`, NOT THE AMOUNT.  The search finds only paths that can give the probe alone
+    (a path that cannot answers +inf and is no path).  Probed with the whole amount, an order that is large against the pools
+    -- one that no single path can fill, the very order that needs splitting -- would find nothing; probed with the size a
+    share will have, it finds the paths that can each carry one.  Pass `probe=amount_out` for the paths that are best for the
+    whole amount (`route_order`'s default), or any other size.
+
+    An order for which nothing is found has empty lists, total +inf and SPLIT_UNOBTAINABLE (with `amount_out` 0: 0.0 and
+    SPLIT_NONE), and is not sent to `split_paths_out`.  Nothing is executed:
+    `swap_path_out_(r, pools[g], tokens[g], path_amount_out[g], max_in=path_amount_in[g])` executes order g.  Scalars broadcast."""
+    try:
+        tin, tout, amt = np.broadcast_arrays(np.asarray(token_in).reshape(-1), np.asarray(token_out).reshape(-1),
+                                             np.asarray(amount_out, dtype=np.float64).reshape(-1))
+        look = amt / float(max_paths) if probe is None else np.broadcast_to(np.asarray(probe, dtype=np.float64).reshape(-1), amt.shape)
+    except ValueError:
+        raise ArgumentError("token_in, token_out, amount_out and probe must be scalars or have one entry per order") from None
+    _, pools, tokens, _ = find_disjoint_paths_out(r, tin, tout, look, max_paths, max_hops, usable_only=True)
+    n = len(pools)
+    have = [g for g in range(n) if pools[g]]
+    x, y = [np.empty(0) for _ in range(n)], [np.empty(0) for _ in range(n)]
+    total = np.where(amt == 0.0, 0.0, np.inf)
+    status = np.where(amt == 0.0, SPLIT_NONE, SPLIT_UNOBTAINABLE).astype(np.int32)
+    if have:
+        xs, ys, total[have], status[have] = split_paths_out(r, [pools[g] for g in have], [tokens[g] for g in have], amt[have], rounds)
         for g, xg, yg in zip(have, xs, ys):
             x[g], y[g] = xg, yg
     return pools, tokens, x, y, total, status

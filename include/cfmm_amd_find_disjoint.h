@@ -55,7 +55,7 @@ extern "C" {
  * (larger calls run in chunks of queries, at least one query each, with the same results).  The read-only options
  * "find_launches", "find_relax_ns", "find_walk_ns" and the per-layer ones describe the latest call of any find entry, summed
  * over the rounds; "find_round_relax_ns_<r>" and "find_round_walk_ns_<r>" (r = 1 .. 8) are this entry's spans round by round.
- * OUT OF SCOPE: the exact-output direction; a device-pointer variant; executing inside the call (cfmm_split_paths sizes the
+ * OUT OF SCOPE: a device-pointer variant; executing inside the call (cfmm_split_paths sizes the
  * shares, cfmm_swap_path executes them). */
 int cfmm_find_disjoint_paths(cfmm_ctx* ctx, int64_t count, int32_t max_paths, int32_t max_hops, const int32_t* token_in,
                              const int32_t* token_out, const double* amount_in, int32_t* n_paths, double* amount_out,
