@@ -4,14 +4,14 @@ Exports the reference's names (src/CFMMRouter.jl, src/cfmms.jl:1-3, src/objectiv
 src/router.jl:1-2).  Julia's `f!` is spelled `f_` here.  All pool arithmetic runs on the GPU
 through libcfmm_amd.so (include/cfmm_amd.h); there is no CPU fallback in this package.
 """
-from ._lib import FOUND, FOUND_NONE, FOUND_REPEATS, SIZED, SIZED_AT_LIMIT, SIZED_NAN, SIZED_NONE, SPLIT_NAN, SPLIT_NONE, SPLIT_OK, SPLIT_SATURATED, SPLIT_UNOBTAINABLE, ArgumentError, CFMMDeviceError, Context, build, lib
+from ._lib import FOUND, FOUND_NONE, FOUND_REPEATS, ORDER_APPLIED, ORDER_LIMIT, ORDER_PATH_HELD, ORDER_REFUSED, ORDER_UNOBTAINABLE, SIZED, SIZED_AT_LIMIT, SIZED_NAN, SIZED_NONE, SPLIT_NAN, SPLIT_NONE, SPLIT_OK, SPLIT_SATURATED, SPLIT_UNOBTAINABLE, ArgumentError, CFMMDeviceError, Context, build, lib
 from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwoCoin, PoolBatch, Product, ProductTwoCoin,
                     SolidlyStableTwoCoin, UniV3, backward_trade, find_arb_ as _find_arb_pool, forward_trade,
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
-from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_disjoint_paths, find_disjoint_paths_out, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_, route_order, route_order_out, size_path, split_paths, split_paths_out,
-                     swap_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
+from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_disjoint_paths, find_disjoint_paths_out, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_, route_order, route_order_, route_order_out, route_order_out_, size_path, split_paths, split_paths_out,
+                     swap_, swap_order_, swap_order_out_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
 
 
 def find_arb_(*args, **kw):
@@ -35,4 +35,6 @@ __all__ = [
     "find_disjoint_paths", "route_order",
     "split_paths", "SPLIT_OK", "SPLIT_NONE", "SPLIT_NAN", "SPLIT_SATURATED",
     "split_paths_out", "find_disjoint_paths_out", "route_order_out", "SPLIT_UNOBTAINABLE",
+    "swap_order_", "swap_order_out_", "route_order_", "route_order_out_",
+    "ORDER_APPLIED", "ORDER_LIMIT", "ORDER_REFUSED", "ORDER_UNOBTAINABLE", "ORDER_PATH_HELD",
 ]

@@ -29,6 +29,8 @@ SIZED, SIZED_NONE, SIZED_AT_LIMIT, SIZED_NAN = 0, 1, 2, 3   # CFMM_SIZED*: Conte
 MAX_SIZE_ROUNDS = 16       # CFMM_MAX_SIZE_ROUNDS
 SPLIT_OK, SPLIT_NONE, SPLIT_NAN, SPLIT_SATURATED = 0, 1, 2, 3   # CFMM_SPLIT_*: Context.split_paths' status
 SPLIT_UNOBTAINABLE = 4     # CFMM_SPLIT_UNOBTAINABLE: Context.split_paths_out's "no path can give another slice"
+ORDER_APPLIED, ORDER_LIMIT, ORDER_REFUSED, ORDER_UNOBTAINABLE = 0, 1, 2, 3   # CFMM_ORDER_*: Context.swap_order's / swap_order_out's status
+ORDER_PATH_HELD = 4        # CFMM_ORDER_PATH_HELD: their path_status of a path that passes in an order that was not applied
 MAX_SPLIT_PATHS = 8        # CFMM_MAX_SPLIT_PATHS
 MAX_SPLIT_ROUNDS = 16      # CFMM_MAX_SPLIT_ROUNDS
 
@@ -164,6 +166,8 @@ def lib():
                                    _f64p, _f64p, _f64p, _i32p]
     L.cfmm_split_paths_dev.argtypes = [_ctx, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
     L.cfmm_split_paths_out.argtypes = L.cfmm_split_paths.argtypes
+    L.cfmm_swap_order.argtypes = [_ctx, C.c_int64, _i64p, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p, _i32p, _i32p]
+    L.cfmm_swap_order_out.argtypes = L.cfmm_swap_order.argtypes
     L.cfmm_split_paths_out_dev.argtypes = L.cfmm_split_paths_dev.argtypes
     L.cfmm_sweep_dev.argtypes = [_ctx, C.c_void_p, C.c_void_p, C.c_int]
     L.cfmm_trades_dev.argtypes = [_ctx, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
@@ -827,6 +831,51 @@ class Context:
                                                  int(n_paths), int(max_hops), *(C.c_void_p(p or None) for p in (
             d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out)), int(rounds),
             *(C.c_void_p(p or None) for p in (d_path_amount_in, d_path_amount_out, d_total_out, d_status))))
+
+    # -- order execution (cfmm_swap_order / cfmm_swap_order_out): orders applied in order, each all or nothing ACROSS its paths ----
+    def swap_order(self, order_first, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, path_amount_in, min_total_out=None, hops=False):
+        """split_paths' path arguments and `order_first`, with an amount per path, but the orders are APPLIED (cfmm_swap_order),
+        in the caller's order, each all or nothing across its 1 .. MAX_SPLIT_PATHS paths: returns (path_amount_out [n_paths],
+        total_out [orders], status [orders], path_status [n_paths][, hop_out]).  Every path is walked as swap_path walks it,
+        on the market the applied orders before left; total_out[g] is the paths' outputs added in increasing path order
+        (split_paths' total_out bit for bit on an unmoved market).  status[g] is ORDER_APPLIED (every path's pools moved as
+        swap_path moves them), ORDER_LIMIT (total_out[g] < min_total_out[g]: the sum it would have given, nothing moved) or
+        ORDER_REFUSED (some path has a refusing hop: NaN, nothing moved); path_status[p] is PATH_APPLIED, PATH_REFUSED or
+        ORDER_PATH_HELD (the path passes, its order was not applied).  min_total_out: None, a scalar or one limit per order.
+        No pool may occur twice among an order's paths.  A state change as swap_path; get_option("swap_refused") counts the
+        orders not applied."""
+        return self._swap_order("cfmm_swap_order", "min_total_out", order_first, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
+                                path_amount_in, min_total_out, hops)
+
+    def swap_order_out(self, order_first, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, path_amount_out, max_total_in=None, hops=False):
+        """The exact-output twin (cfmm_swap_order_out): path_amount_out[p] is wanted from path p, every path is walked as
+        swap_path_out walks it; returns (path_amount_in, total_in, status, path_status[, hop_in]).  status[g] may also be
+        ORDER_UNOBTAINABLE (some path cannot give its amount: total_in +inf, nothing moved; that path's path_status is
+        SWAP_UNOBTAINABLE); ORDER_LIMIT is total_in[g] > max_total_in[g]."""
+        return self._swap_order("cfmm_swap_order_out", "max_total_in", order_first, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out,
+                                path_amount_out, max_total_in, hops)
+
+    def _swap_order(self, entry, limit_name, order_first, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, given, limit, hops):
+        first = np.ascontiguousarray(order_first, dtype=np.int64).reshape(-1)
+        amt = np.ascontiguousarray(f64(given).reshape(-1))
+        n = amt.size
+        nh, seg, row, ci, co = self._path_columns(n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        g = max(0, first.size - 1)
+        if first.size == 0 and n:
+            raise ArgumentError("order_first must have one entry more than there are orders")
+        lim = None
+        if limit is not None:
+            try:
+                lim = np.ascontiguousarray(np.broadcast_to(np.asarray(limit, dtype=np.float64), (g,)))
+            except ValueError:
+                raise ArgumentError(f"{limit_name} must be a scalar or have one entry per order") from None
+        max_hops = max(1, int(seg.shape[0]))
+        out, pst = np.empty(n), np.empty(n, dtype=np.int32)
+        tot, st = np.empty(g), np.empty(g, dtype=np.int32)
+        hv = np.empty((max_hops, n)) if hops else None
+        self._check(getattr(self._L, entry)(self._h, g, ptr(first), n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt),
+                                            ptr(lim), ptr(out), ptr(hv), ptr(tot), ptr(pst), ptr(st)))
+        return (out, tot, st, pst, hv) if hops else (out, tot, st, pst)
 
     # -- buying through several paths (cfmm_split_paths_out): a wanted amount spread over an order's 1 .. 8 paths ----------
     def split_paths_out(self, order_first, amount_out, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, rounds=5):

@@ -277,7 +277,7 @@ static int64_t* option_slot(cfmm_ctx* c, const char* key)
         {"stop_in_noise", &c->opt_stop_in_noise}, {"multi_threads", &c->opt_multi_threads},
         {"dev_prices_in_window", &c->opt_dev_prices_in_window}, {"univ3_heads", &c->opt_univ3_heads}, {"direct_small", &c->geo.direct_small}, {"stream_stores", &c->opt_stream_stores},
         {"find_lds", &c->opt_find_lds}, {"lean_kernels", &c->opt_lean_kernels}, {"size_max_blocks", &c->opt_size_max_blocks},
-        {"split_max_blocks", &c->opt_split_max_blocks},
+        {"split_max_blocks", &c->opt_split_max_blocks}, {"order_max_blocks", &c->opt_order_max_blocks},
 #ifdef CFMM_TEST_HOOKS
         {"debug_stall_ms", &c->opt_debug_stall_ms},
 #endif
@@ -301,6 +301,7 @@ int cfmm_set_option(cfmm_ctx* c, const char* key, int64_t value)
         return fail(c, CFMM_ERR_INVALID_ARG, "stream_stores must be 0 (auto), 1 (write-through) or 2 (non-temporal)");
     if (slot == &c->opt_size_max_blocks && value < 1) return fail(c, CFMM_ERR_INVALID_ARG, "size_max_blocks must be >= 1");
     if (slot == &c->opt_split_max_blocks && value < 1) return fail(c, CFMM_ERR_INVALID_ARG, "split_max_blocks must be >= 1");
+    if (slot == &c->opt_order_max_blocks && value < 1) return fail(c, CFMM_ERR_INVALID_ARG, "order_max_blocks must be >= 1");
     *slot = value;
     c->desc_dirty = true;   // pack, compact_trades, block, max_grid, fuse_segments, bin_copies, stream_stores, univ3_heads, geomean_exact, cost_*: all copied
     if (slot != &c->opt_multi_threads)

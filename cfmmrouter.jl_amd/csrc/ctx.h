@@ -23,6 +23,9 @@
 //   abi_swap_path.cpp swap PATHS that move their pools, all or nothing, in both directions (cfmm_swap_path,
 //                     cfmm_swap_path_out; swap_path_waves.h: the HIP-free wave numbering of paths that share pools,
 //                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
+//   abi_swap_order.cpp ORDERS executed all or nothing across their 1 .. 8 paths, in both directions (cfmm_swap_order,
+//                     cfmm_swap_order_out; swap_order_waves.h: the HIP-free wave numbering of orders that share pools,
+//                     order_checks.h: the HIP-free checks)
 //   abi_find_path.cpp the best swap walk between two tokens, found on the device (cfmm_find_path; find_checks.h: the HIP-free
 //                     checks and the chunking rule)
 //   abi_size_path.cpp the input of a path that maximises its gain (cfmm_size_path; size_checks.h: the HIP-free checks, size_grid.h:
@@ -31,7 +34,7 @@
 //                     split_grid.h: the search's arithmetic, shared with the kernel)
 //                     and bought through several paths (cfmm_split_paths_out: the same file, checks and scratch;
 //                     split_out_grid.h: what its search has of its own)
-//   seg_view.h        what those seven share, on top of this header: a segment as their kernels and their checks see it
+//   seg_view.h        what those eight share, on top of this header: a segment as their kernels and their checks see it
 //   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
 //   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
 //   abi_route.cpp     route! in one call (L-BFGS-B + objectives), the bare solver
@@ -306,6 +309,25 @@ struct SwapPathScratch {
     PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
 };
 
+// cfmm_swap_order / cfmm_swap_order_out (abi_swap_order.cpp, swap_order_kernels.h): SwapPathScratch's arrangement for orders --
+// the device copies of one call's paths and orders, both in WAVE order (swap_order_waves.h), the limits, answers, hop amounts,
+// UniV3 landing prices and statuses, the segment table (rebuilt per call), one window flag per segment and ONE pinned staging
+// buffer -- proportional to the orders and to n_paths x max_hops (and the number of segments), never to the pools.  The call
+// ends synchronised.  The spans and the orders not applied go to SwapScratch's "swap_ns" / "swap_refused" / "swap_launches".
+struct SwapOrderScratch {
+    DevBuf<SwapPathSeg> table;         // [segments]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][n_paths]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> i64;             // [max_hops][n_paths] hop_row, then [count + 1] order_first
+    DevBuf<double> amt;                // [n_paths] the given amounts, then [count] the limits
+    DevBuf<double> out;                // [n_paths] the paths' answers, then [count] the totals
+    DevBuf<double> hops, price;        // [max_hops][n_paths]
+    DevBuf<int32_t> status;            // [n_paths] path_status, then [count] status
+    DevBuf<int> left;                  // [segments] a new reserve of the segment left the window of the fast arithmetic
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapOrderStage
+    EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
+    PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
+};
+
 // cfmm_find_path (abi_find_path.cpp, find_path_kernels.h): the layers of the search -- the one array of the path features that
 // is proportional to n_tokens: (max_hops + 1) x queries of a chunk x n_tokens words, bounded by kFindScratchBudget
 // (find_checks.h) -- the claimed edges, the device copies of one call's queries and answers, the segment table (sweep.h
@@ -523,6 +545,12 @@ struct cfmm_ctx {
     std::vector<ParentSeg> psegs;          // one per cfmm_pools_add_* call with m > 0
     std::unique_ptr<cfmm::Workers> workers;
     bool shards_distinct = true;           // no two shards share a device (pre-armed evaluations need that)
+
+    // cfmm_swap_order / cfmm_swap_order_out.  (Behind everything above, so that every member the sweep's host path reads stands
+    // where it stood before these two came.)
+    int64_t opt_order_max_blocks = cfmm::kOrderMaxBlocks; // the most blocks of their launches (>= 1; the wavefronts stride over a wave's
+                                   //    orders, the same bits at any value: a measurement and test switch, as "split_max_blocks")
+    cfmm::SwapOrderScratch swap_order;
 
     mutable std::string err = "";
 };

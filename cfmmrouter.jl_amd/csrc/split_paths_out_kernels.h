@@ -101,3 +101,6 @@ __global__ __launch_bounds__(BLOCK) void split_paths_out_kernel(SplitArgs a)
 }
 
 } // namespace cfmm
+
+// (what came after this header is included from here, behind everything above: find_path_kernels.h's rule)
+#include "swap_order_kernels.h"

@@ -576,6 +576,27 @@ hipError_t launch_swap_path(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 
 // amount_out receives the input to tender to the first hop, hops the amount TO TENDER to hop k, and status is one of kSwap*.
 hipError_t launch_swap_path_out(const SwapPathArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_swap_order / cfmm_swap_order_out (swap_order_kernels.h, abi_swap_order.cpp): orders that MOVE their pools, each all or
+// nothing across its 1 .. 8 paths, EIGHT LANES PER ORDER of ONE WAVE -- orders that share no pool (swap_order_waves.h).  The
+// paths are a SwapPathArgs as swap_path_kernel takes it, for ALL paths of the call: p.count == p.stride == n_paths, the
+// arrays point at the call's first path (order_first names paths by their position in them), p.min_out is unused (null),
+// p.status receives path_status.  The orders' arrays point at the wave's first order.
+constexpr int32_t kOrderApplied = 0, kOrderLimit = 1, kOrderRefused = 2, kOrderUnobtainable = 3;   // CFMM_ORDER_* (include/cfmm_amd_order.h)
+constexpr int32_t kOrderPathHeld = 4;                                                              // CFMM_ORDER_PATH_HELD
+struct SwapOrderArgs {
+    SwapPathArgs p;
+    int64_t orders;               // orders of this wave
+    const long long* order_first; // [orders + 1]: order g owns the paths order_first[g] .. order_first[g+1] - 1
+    const double* limit;          // [orders] min_total_out / max_total_in, or null: no limit
+    double* total;                // [orders]
+    int32_t* status;              // [orders] kOrder*
+};
+constexpr int kOrderBlock = 256;                                  // four wavefronts = 32 orders per block
+constexpr int kOrderMaxBlocks = kResidentThreads / kOrderBlock;   // default of option "order_max_blocks": one machine of resident wavefronts
+// max_blocks >= 1 caps the grid (the wavefronts stride over the wave's orders).  e0, e1: both set = the launch is timed.
+hipError_t launch_swap_order(bool exact_out, const SwapOrderArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0 = nullptr,
+                             hipEvent_t e1 = nullptr);
+
 // cfmm_find_path (find_path_kernels.h, abi_find_path.cpp): the best walk of at most max_hops hops between two tokens, by
 // layers -- one launch per layer with ONE LANE PER POOL of every segment.  The kernels read a table of their own: what
 // PathSeg holds (the quotes' view, unchanged), the segment's token arrays (two-coin kinds and UniV3: the packed records, or

@@ -53,6 +53,7 @@
 //   find_disjoint_kernels.h  find_ban_relax and the walk back (cfmm_find_disjoint_paths: find_path's search with a per-query bitmap of absent pools;
 //                            find_out_ban_relax and its walk: cfmm_find_disjoint_paths_out, the same text in the other direction: the header includes its second half once per direction)
 //   split_paths_out_kernels.h  split_paths_out_kernel (cfmm_split_paths_out: a wanted amount bought through an order's paths, split_paths_kernel's shape, the hops walked backwards)
+//   swap_order_kernels.h  swap_order_kernel, swap_order_out_kernel (cfmm_swap_order, cfmm_swap_order_out: orders executed all or nothing across their paths, eight lanes per order)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -71,7 +72,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h, and from that one's swap_order_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -527,6 +528,20 @@ hipError_t launch_split_paths_out(const SplitArgs& a, int64_t max_blocks, hipStr
     const int64_t blocks = std::min<int64_t>({(a.orders + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
     void* args[] = {const_cast<SplitArgs*>(&a)};
     return launch_k(reinterpret_cast<const void*>(&split_paths_out_kernel<kSplitBlock>), dim3((unsigned)blocks), dim3(kSplitBlock), 0, s, e0, e1, args);
+}
+
+// cfmm_swap_order / cfmm_swap_order_out: eight lanes per order of the wave, kOrderBlock / 8 orders per block, at most max_blocks
+// blocks.  (Behind every other launcher, for launch_size_path's reason.)
+hipError_t launch_swap_order(bool exact_out, const SwapOrderArgs& a, int64_t max_blocks, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.orders <= 0 || a.p.count <= 0 || a.p.stride != a.p.count || a.p.nseg <= 0 || a.p.max_hops < 1 || a.p.max_hops > CFMM_MAX_PATH_HOPS ||
+        max_blocks < 1 || !a.order_first || !a.p.amount_out || !a.p.hops || !a.p.price || !a.p.status || !a.total || !a.status)
+        return hipErrorInvalidValue;
+    constexpr int64_t per_block = kOrderBlock / kOrderLanes;
+    const int64_t blocks = std::min<int64_t>({(a.orders + per_block - 1) / per_block, max_blocks, (int64_t)0x7fffffff});
+    void* args[] = {const_cast<SwapOrderArgs*>(&a)};
+    const void* kernel = exact_out ? reinterpret_cast<const void*>(&swap_order_out_kernel<kOrderBlock>) : reinterpret_cast<const void*>(&swap_order_kernel<kOrderBlock>);
+    return launch_k(kernel, dim3((unsigned)blocks), dim3(kOrderBlock), 0, s, e0, e1, args);
 }
 
 } // namespace cfmm

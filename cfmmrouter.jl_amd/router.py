@@ -22,7 +22,7 @@ import math
 import numpy as np
 
 from . import objectives as _obj
-from ._lib import FOUND_REPEATS, MAX_PATH_HOPS, MAX_SPLIT_PATHS, SPLIT_NONE, SPLIT_UNOBTAINABLE, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
+from ._lib import FOUND_REPEATS, MAX_PATH_HOPS, MAX_SPLIT_PATHS, ORDER_REFUSED, SPLIT_NONE, SPLIT_OK, SPLIT_SATURATED, SPLIT_UNOBTAINABLE, OBJ_BASKET_LIQUIDATION, OBJ_LINEAR_NONNEGATIVE, ArgumentError, CFMMDeviceError, Context
 from .layout import PoolLayout
 from .cfmms import CFMM, KINDS, MAX_COINS, PoolBatch, _download_state, _has_ladder, _set_pool_state, _upload
 
@@ -943,6 +943,15 @@ def _split_paths(r: Router, verb, amount_name, pools, tokens, amount_in, rounds)
         amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (len(pools),)))
     except ValueError:
         raise ArgumentError(f"{amount_name} must be a scalar or have one entry per order") from None
+    first, (n_hops, seg, row, ci, co, _, _) = _order_hops(r, verb, pools, tokens, 0.0)
+    x, y, total, status = getattr(_path_context(r), verb)(first, amt, n_hops, seg, row, ci, co, rounds)
+    cut = lambda v: [v[first[g]:first[g + 1]] for g in range(len(pools))]
+    return cut(x), cut(y), total, status
+
+
+def _order_hops(r: Router, verb, pools, tokens, path_amount):
+    """(pools, tokens) of the order calls -- per order a list of paths -- as `order_first` and `_path_hops`' answer for the flat
+    paths, with every refusal the router makes of an order; path_amount: a scalar or one entry per path of the whole call"""
     for g, (pl, tk) in enumerate(zip(pools, tokens)):
         if not 1 <= len(pl) <= MAX_SPLIT_PATHS:
             raise ArgumentError(f"order {g}: {len(pl)} paths (an order has 1 to {MAX_SPLIT_PATHS})")
@@ -950,7 +959,7 @@ def _split_paths(r: Router, verb, amount_name, pools, tokens, amount_in, rounds)
             raise ArgumentError(f"order {g}: {len(tk)} token sequences for {len(pl)} paths")
     first = np.concatenate(([0], np.cumsum([len(pl) for pl in pools]))).astype(np.int64)
     flat_pools, flat_tokens = [p for pl in pools for p in pl], [t for tk in tokens for t in tk]
-    n_hops, seg, row, ci, co, _, _ = _path_hops(r, verb, flat_pools, flat_tokens, 0.0)
+    hops = _path_hops(r, verb, flat_pools, flat_tokens, path_amount)
     for g, (pl, tk) in enumerate(zip(pools, tokens)):
         ends = {(int(np.asarray(t).reshape(-1)[0]), int(np.asarray(t).reshape(-1)[-1])) for t in tk}
         if len(ends) != 1:
@@ -962,9 +971,101 @@ def _split_paths(r: Router, verb, amount_name, pools, tokens, amount_in, rounds)
                     raise ArgumentError(f"order {g}: paths {seen[i]} and {k} share pool {i} (the paths are quoted independently "
                                         f"against the standing market, so a shared pool would be counted twice)")
                 seen[i] = k
-    x, y, total, status = getattr(_path_context(r), verb)(first, amt, n_hops, seg, row, ci, co, rounds)
+    return first, hops
+
+
+def swap_order_(r: Router, pools, tokens, path_amount_in, min_total_out=None, hops=False, sync_host=True):
+    """ORDERS APPLIED to the pools on the device, each ALL OR NOTHING ACROSS ITS PATHS (cfmm_swap_order) -- "send this order down
+    these K routes, but only if at least this much comes out in total".  `pools[g]` and `tokens[g]` are lists of paths exactly as
+    `split_paths` takes (and answers) them, with its refusals and `swap_path_`'s; `path_amount_in[g]` the amount going down each
+    path of order g, as `split_paths` returns it.  The orders are executed in the order given; order g sees the market as the
+    applied orders before it left it, every path is walked as `swap_path_` walks it, and only when no path refuses and the
+    total clears the limit does anything move -- then every pool moves as `swap_path_` moves it.
+
+    Returns (path_amount_out, total_out, status, path_status[, hop_out]): the first and `path_status` are lists shaped like
+    `pools`.  total_out[g] is the paths' outputs added in path order (on an unmoved market `split_paths`' total_out bit for
+    bit).  status[g] is ORDER_APPLIED, ORDER_LIMIT (total_out[g] < min_total_out[g]: nothing moved) or ORDER_REFUSED (some path
+    has a refusing hop: NaN, nothing moved); path_status is PATH_APPLIED, PATH_REFUSED or ORDER_PATH_HELD (the path passes, its
+    order was not applied).  min_total_out: None (no limit), a scalar or one limit per order.  Unlike `swap_path_` on the
+    order's paths, a later order that an earlier one has moved out of its limit leaves NO path executed.  sync_host and the
+    zeroing of the router's trades are `swap_path_`'s."""
+    return _swap_order(r, "swap_order", "min_total_out", pools, tokens, path_amount_in, min_total_out, hops, sync_host)
+
+
+def swap_order_out_(r: Router, pools, tokens, path_amount_out, max_total_in=None, hops=False, sync_host=True):
+    """The exact-output twin of `swap_order_` (cfmm_swap_order_out): `path_amount_out[g]` is what each path of order g is to
+    give, as `split_paths_out` returns it; every path is walked as `swap_path_out_` walks it.  Returns (path_amount_in, total_in,
+    status, path_status[, hop_in]); status[g] may also be ORDER_UNOBTAINABLE (some path cannot give its amount: total_in +inf,
+    that path's path_status SWAP_UNOBTAINABLE; nothing moved), and ORDER_LIMIT is total_in[g] > max_total_in[g]."""
+    return _swap_order(r, "swap_order_out", "max_total_in", pools, tokens, path_amount_out, max_total_in, hops, sync_host)
+
+
+def _swap_order(r: Router, verb, limit_name, pools, tokens, path_amount, limit, hops, sync_host):
+    pools, tokens = [list(o) for o in pools], [list(o) for o in tokens]
+    if len(tokens) != len(pools):
+        raise ArgumentError("tokens must have one list of paths per order")
+    amount_name = "path_amount_out" if verb.endswith("_out") else "path_amount_in"
+    if np.isscalar(path_amount) or isinstance(path_amount, np.ndarray) and path_amount.ndim == 0:
+        flat = float(path_amount)
+    else:
+        per_order = list(path_amount)
+        if len(per_order) != len(pools) or any(np.size(a) != len(pl) for a, pl in zip(per_order, pools)):
+            raise ArgumentError(f"{amount_name} must be a scalar or have one entry per path, shaped like pools")
+        flat = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1) for a in per_order]) if per_order else np.empty(0)
+    first, (n_hops, seg, row, ci, co, amt, touched) = _order_hops(r, verb, pools, tokens, flat)
+    if limit is not None:
+        try:
+            limit = np.ascontiguousarray(np.broadcast_to(np.asarray(limit, dtype=np.float64), (len(pools),)))
+        except ValueError:
+            raise ArgumentError(f"{limit_name} must be a scalar or have one entry per order") from None
+    ctx = _path_context(r)
+    L = r._layout
     cut = lambda v: [v[first[g]:first[g + 1]] for g in range(len(pools))]
-    return cut(x), cut(y), total, status
+    try:
+        res = getattr(ctx, verb)(first, n_hops, seg, row, ci, co, amt, limit, hops)
+        if sync_host:
+            for b in sorted(touched):
+                _download_state(ctx, L.seg_of[b], L.batches[b])
+                L.sync_pools(r.cfmms, b, sorted(touched[b]))
+        return (cut(res[0]), res[1], res[2], cut(res[3])) + tuple(res[4:])
+    finally:
+        r._reset_trades()
+
+
+def route_order_(r: Router, token_in, token_out, amount_in, max_slippage=0.0, max_paths=4, max_hops=3, rounds=5, probe=None, sync_host=True):
+    """find -> split -> EXECUTE in one call: `route_order`, then `swap_order_` on what it answered with
+    min_total_out = total_out * (1 - max_slippage).  Orders for which nothing was found (or whose split is not SPLIT_OK /
+    SPLIT_SATURATED) are not sent to the device: their executed total is 0.0, their status ORDER_REFUSED and their lists empty.
+    Returns `route_order`'s six answers, then (path_amount_out, total_out, status, path_status) as executed."""
+    if not 0.0 <= float(max_slippage) < 1.0:
+        raise ArgumentError("max_slippage must be in [0, 1)")
+    pools, tokens, x, y, total, split_status = route_order(r, token_in, token_out, amount_in, max_paths, max_hops, rounds, probe)
+    limit = total * (1.0 - float(max_slippage))
+    return (pools, tokens, x, y, total, split_status) + _execute_routed(r, swap_order_, pools, tokens, x, limit, split_status, sync_host)
+
+
+def route_order_out_(r: Router, token_in, token_out, amount_out, max_slippage=0.0, max_paths=4, max_hops=3, rounds=5, probe=None, sync_host=True):
+    """The exact-output twin of `route_order_`: `route_order_out`, then `swap_order_out_` with
+    max_total_in = total_in * (1 + max_slippage).  Returns `route_order_out`'s six answers, then (path_amount_in, total_in,
+    status, path_status) as executed."""
+    if not float(max_slippage) >= 0.0:
+        raise ArgumentError("max_slippage must be >= 0")
+    pools, tokens, x, y, total, split_status = route_order_out(r, token_in, token_out, amount_out, max_paths, max_hops, rounds, probe)
+    limit = total * (1.0 + float(max_slippage))
+    return (pools, tokens, x, y, total, split_status) + _execute_routed(r, swap_order_out_, pools, tokens, x, limit, split_status, sync_host)
+
+
+def _execute_routed(r: Router, execute, pools, tokens, shares, limit, split_status, sync_host):
+    n = len(pools)
+    send = [g for g in range(n) if pools[g] and split_status[g] in (SPLIT_OK, SPLIT_SATURATED)]
+    out, pst = [np.empty(0) for _ in range(n)], [np.empty(0, dtype=np.int32) for _ in range(n)]
+    total, status = np.zeros(n), np.full(n, ORDER_REFUSED, dtype=np.int32)
+    if send:
+        o, total[send], status[send], ps = execute(r, [pools[g] for g in send], [tokens[g] for g in send], [shares[g] for g in send],
+                                                   limit[send], sync_host=sync_host)
+        for g, og, pg in zip(send, o, ps):
+            out[g], pst[g] = og, pg
+    return out, total, status, pst
 
 
 def _find_path(r: Router, verb, amount_name, token_in, token_out, amount, max_hops):

@@ -86,8 +86,9 @@ extern "C" {
  * "quote_ns"); "split_launches" its kernel launches (1; a parent: its cfmm_quote_path calls).  Option "split_max_blocks" (any
  * value >= 1) caps the grid: the same bits either way, a measurement and test switch.
  * OUT OF SCOPE: finding the K candidate paths (cfmm_find_path answers with one; a pool-exclusion mask for it is its own
- * addition); paths that share pools; executing inside the same call (cfmm_swap_path on the order's
- * paths at path_amount_in executes the split -- the paths share no pool, so their order cannot matter). */
+ * addition); paths that share pools.  EXECUTING the answer: cfmm_swap_order (include/cfmm_amd_order.h) takes order_first, the
+ * path arrays and path_amount_in unchanged and executes every order all or nothing across its paths, with one limit on its
+ * total; cfmm_swap_path on the order's paths at path_amount_in executes the paths one by one, each all or nothing on its own. */
 int cfmm_split_paths(cfmm_ctx* ctx, int64_t count, const int64_t* order_first, const double* amount_in, int64_t n_paths,
                      int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg, const int64_t* hop_row,
                      const int32_t* hop_coin_in, const int32_t* hop_coin_out, int32_t rounds, double* path_amount_in,

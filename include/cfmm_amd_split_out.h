@@ -89,9 +89,10 @@ extern "C" {
  * 64 * n_paths paths per round, with the grid and greedy arithmetic of the kernel: the same bits.
  * Options: "split_max_blocks" caps this entry's grid too (the same bits either way); "split_ns" and "split_launches" describe
  * the latest call of EITHER split entry.
- * Executing: cfmm_swap_path_out on the order's paths at path_amount_out, with path_amount_in as the limits, buys the split --
- * the paths share no pool, so their order cannot matter.
- * OUT OF SCOPE: paths that share pools; executing inside the same call. */
+ * Executing: cfmm_swap_order_out (include/cfmm_amd_order.h) takes order_first, the path arrays and path_amount_out unchanged and
+ * buys every order all or nothing across its paths, with one limit on its total cost; cfmm_swap_path_out on the order's paths at
+ * path_amount_out, with path_amount_in as the limits, buys the paths one by one, each all or nothing on its own.
+ * OUT OF SCOPE: paths that share pools. */
 int cfmm_split_paths_out(cfmm_ctx* ctx, int64_t count, const int64_t* order_first, const double* amount_out, int64_t n_paths,
                          int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg, const int64_t* hop_row,
                          const int32_t* hop_coin_in, const int32_t* hop_coin_out, int32_t rounds, double* path_amount_out,
