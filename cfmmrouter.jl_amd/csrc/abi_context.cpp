@@ -1,5 +1,5 @@
 // abi_context.cpp -- context life cycle, options, streams, introspection (include/cfmm_amd.h).
-#include "ctx.h"
+#include "path_rig.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -349,10 +349,11 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     // read-only, cfmm_size_path / cfmm_size_path_dev: the latest call's kernel launches (a parent: its cfmm_quote_path calls), and under
     // "time_kernels" its kernel's span (a parent: the sum of its rounds' "quote_ns"); after cfmm_size_path_dev the read waits, as "quote_ns"
     if (key && !std::strcmp(key, "size_launches")) { *value = c->size.launches; return CFMM_OK; }
-    if (key && !std::strcmp(key, "size_ns")) return size_ns(const_cast<cfmm_ctx*>(c), value);
+    cfmm_ctx* const m = const_cast<cfmm_ctx*>(c);   // (a getter that waits for a timed _dev call's span stores it)
+    if (key && !std::strcmp(key, "size_ns")) return m->size.read_ns(m, value);
     // read-only, cfmm_split_paths / cfmm_split_paths_out and their _dev forms: the same two of the latest call of either split entry
     if (key && !std::strcmp(key, "split_launches")) { *value = c->split.launches; return CFMM_OK; }
-    if (key && !std::strcmp(key, "split_ns")) return split_ns(const_cast<cfmm_ctx*>(c), value);
+    if (key && !std::strcmp(key, "split_ns")) return m->split.read_ns(m, value);
     // read-only, cfmm_find_path / cfmm_find_path_out (whichever was called last): the latest call's kernel launches, and under
     // "time_kernels" the sums of the spans of its layer launches (find_relax / find_out_relax) and of its walk launches (claim +
     // advance)

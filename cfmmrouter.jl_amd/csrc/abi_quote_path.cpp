@@ -3,11 +3,10 @@
 // the per-hop forms are cfmm_quote's own, quote_pool.h; the checks: path_checks.h).  As in abi_quote.cpp the two directions
 // share every line: `given` / `answer` are amount_in / amount_out of the forward entries and amount_out / amount_in of the
 // inverse ones, `hops` is hop_out / hop_in.
-// Read-only.  The kernels see the segments through a table of PathSeg records in device memory, which upload_table below
-// REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES (seg_view.h) AND UPLOADS ON EVERY CALL: cfmm_update_reserves, cfmm_pools_set_ticks
-// and tick compaction swap UniV3 arrays, and a table kept across calls would hold a freed address.  It is a line per segment.
+// Read-only.  The kernels see the segments through a table of PathSeg records in device memory, rebuilt and uploaded on every
+// call by the rig these entries share with cfmm_size_path and cfmm_split_paths (ctx.h PathRig, path_rig.h).
 // The only memory of the feature is PathScratch (ctx.h): proportional to count x max_hops, never to the pools.
-#include "seg_view.h"
+#include "path_rig.h"
 #include "stage_layout.h"
 
 #include <algorithm>
@@ -22,48 +21,14 @@ namespace {
 constexpr Dir kForward{false, "cfmm_quote_path", "cfmm_quote_path_dev", nullptr};
 constexpr Dir kInverse{true, "cfmm_quote_path_out", "cfmm_quote_path_out_dev", nullptr};
 
-int refuse(cfmm_ctx* c, int rc, const char* msg) { return rc == CFMM_OK ? rc : fail(c, rc, "%s", msg); }
-
-// The staging is free again, the table may be rewritten: the call before has left the device (`done` sits behind its kernel)
-int wait_previous(cfmm_ctx* c)
-{
-    PathScratch& ps = c->path;
-    if (ps.in_flight) HIP_TRY(c, hipEventSynchronize(ps.done.get()));
-    ps.in_flight = false;
-    return CFMM_OK;
-}
-
 // the staging of a call of n paths (stage_layout.h PathStage)
 PathStage stage_of(const cfmm_ctx* c, size_t n, size_t nh, bool want_hops) { return PathStage(table_records(c) * sizeof(PathSeg), n, nh, want_hops); }
 
-// table (seg_view.h: rebuilt from the segments' current addresses) -> staging -> device, in stream order
-int upload_table(cfmm_ctx* c, const PathStage& lay, int32_t& nrec_out)
-{
-    PathScratch& ps = c->path;
-    const size_t nrec = table_records(c);
-    int rc;
-    if ((rc = wait_previous(c)) || (rc = ps.stage.grow(c, lay.l.words(), false)) || (rc = ps.table.grow(c, nrec)) ||
-        (rc = ps.done.create(c, hipEventDisableTiming)))
-        return rc;
-    PathSeg* t = reinterpret_cast<PathSeg*>(lay.table.in(ps.stage.host()));
-    build_table(c, t, [](const Segment& s, size_t) { return path_seg(s); });
-    HIP_TRY(c, hipMemcpyAsync(ps.table.get(), t, nrec * sizeof(PathSeg), hipMemcpyHostToDevice, c->stream));
-    nrec_out = (int32_t)nrec;
-    return CFMM_OK;
-}
-
+// (the span goes to QuoteScratch's events: "quote_ns")
 int launch(cfmm_ctx* c, const Dir& dir, const PathArgs& a)
 {
-    QuoteScratch& q = c->quote;
-    PathScratch& ps = c->path;
-    const bool timed = c->opt_time_kernels != 0;
-    int rc;
-    if (timed && (rc = q.ev.ensure(c, 1)) != CFMM_OK) return rc;
-    const hipError_t e = launch_quote_path(dir.exact_out, a, c->stream, q.ev.start(0, timed), q.ev.stop(0, timed));
-    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "quote path launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(c, hipEventRecord(ps.done.get(), c->stream));
-    ps.in_flight = true;
-    return CFMM_OK;
+    return c->path.launch(c, c->quote.ev, "quote path",
+                          [&](hipEvent_t e0, hipEvent_t e1) { return launch_quote_path(dir.exact_out, a, c->stream, e0, e1); });
 }
 
 // A parent: the paths are walked hop level by hop level through the per-segment parent path (cfmm_quote / cfmm_quote_out ->
@@ -137,7 +102,7 @@ int path_host(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, cons
     const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H;
     const PathStage lay = stage_of(c, n, nh, hops != nullptr);
     PathArgs a{};
-    if ((rc = upload_table(c, lay, a.nseg)) || (rc = ps.hop_i32.grow(c, n + 3 * nh)) || (rc = ps.hop_row.grow(c, nh)) ||
+    if ((rc = ps.upload_table(c, lay, a.nseg)) || (rc = ps.hop_i32.grow(c, n + 3 * nh)) || (rc = ps.hop_row.grow(c, nh)) ||
         (rc = ps.given.grow(c, n)) || (rc = ps.answer.grow(c, n)) || (hops && (rc = ps.hops.grow(c, nh))))
         return rc;
     unsigned long long* st = ps.stage.host();
@@ -192,7 +157,7 @@ int path_dev(cfmm_ctx* c, const Dir& dir, int64_t count, int32_t max_hops, const
         return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", dir.dev);
     HIP_TRY(c, hipSetDevice(c->device));
     PathArgs a{};
-    if ((rc = upload_table(c, stage_of(c, 0, 0, false), a.nseg)) != CFMM_OK) return rc;
+    if ((rc = c->path.upload_table(c, stage_of(c, 0, 0, false), a.nseg)) != CFMM_OK) return rc;
     a.count = count;
     a.max_hops = max_hops;
     a.segs = c->path.table.get();

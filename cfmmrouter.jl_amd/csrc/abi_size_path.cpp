@@ -1,15 +1,15 @@
 // abi_size_path.cpp -- cfmm_size_path / cfmm_size_path_dev (include/cfmm_amd_size_path.h): the input of a path that maximises its
 // gain, by a bracketing search of rounds x 64 trial sizes in ONE launch, one wavefront per path (the kernel:
 // size_path_kernels.h; the search's arithmetic: size_grid.h, shared with it; the checks: size_checks.h and path_checks.h).
-// Read-only.  As in abi_quote_path.cpp the kernel sees the segments through a table of PathSeg records in device memory, which
-// upload_table below REBUILDS FROM THE SEGMENTS' CURRENT ADDRESSES (seg_view.h) AND UPLOADS ON EVERY CALL: cfmm_update_reserves,
-// cfmm_pools_set_ticks and tick compaction swap UniV3 arrays, and a table kept across calls would hold a freed address.
+// Read-only.  As in abi_quote_path.cpp the kernel sees the segments through a table of PathSeg records in device memory,
+// rebuilt and uploaded on every call by the rig of the read-only path entries (ctx.h TimedPathRig, path_rig.h).
 // The only memory of the feature is SizeScratch (ctx.h): proportional to count x max_hops, never to the pools.
 // A multi-device parent runs the search on the host (multi_size): per round one cfmm_quote_path call of 64 x count paths
 // through the parent path, the trial sizes, gains and selection by size_grid.h -- the text the kernel compiles -- so the
 // answers are the same bits.
-#include "seg_view.h"
+#include "path_rig.h"
 #include "size_checks.h"
+#include "split_search.h"
 #include "stage_layout.h"
 
 #include <cstring>
@@ -22,69 +22,27 @@ namespace {
 constexpr const char* kWho = "cfmm_size_path";
 constexpr const char* kWhoDev = "cfmm_size_path_dev";
 
-int refuse(cfmm_ctx* c, int rc, const char* msg) { return rc == CFMM_OK ? rc : fail(c, rc, "%s", msg); }
-
-// The staging is free again, the table may be rewritten: the call before has left the device (`done` sits behind its kernel)
-int wait_previous(cfmm_ctx* c)
-{
-    SizeScratch& sc = c->size;
-    if (sc.in_flight) HIP_TRY(c, hipEventSynchronize(sc.done.get()));
-    sc.in_flight = false;
-    return CFMM_OK;
-}
-
 SizeStage stage_of(const cfmm_ctx* c, size_t n, size_t nh) { return SizeStage(table_records(c) * sizeof(PathSeg), n, nh); }
-
-// table (seg_view.h: rebuilt from the segments' current addresses) -> staging -> device, in stream order
-int upload_table(cfmm_ctx* c, const SizeStage& lay, int32_t& nrec_out)
-{
-    SizeScratch& sc = c->size;
-    const size_t nrec = table_records(c);
-    int rc;
-    if ((rc = wait_previous(c)) || (rc = sc.stage.grow(c, lay.l.words(), false)) || (rc = sc.table.grow(c, nrec)) ||
-        (rc = sc.done.create(c, hipEventDisableTiming)))
-        return rc;
-    PathSeg* t = reinterpret_cast<PathSeg*>(lay.table.in(sc.stage.host()));
-    build_table(c, t, [](const Segment& s, size_t) { return path_seg(s); });
-    HIP_TRY(c, hipMemcpyAsync(sc.table.get(), t, nrec * sizeof(PathSeg), hipMemcpyHostToDevice, c->stream));
-    nrec_out = (int32_t)nrec;
-    return CFMM_OK;
-}
 
 int launch(cfmm_ctx* c, const SizeArgs& a)
 {
     SizeScratch& sc = c->size;
-    const bool timed = c->opt_time_kernels != 0;
-    int rc;
-    if (timed && (rc = sc.ev.ensure(c, 1)) != CFMM_OK) return rc;
-    const hipError_t e = launch_size_path(a, c->opt_size_max_blocks, c->stream, sc.ev.start(0, timed), sc.ev.stop(0, timed));
-    if (e != hipSuccess) return fail(c, CFMM_ERR_HIP, "size path launch failed: %s", hipGetErrorString(e));
-    HIP_TRY(c, hipEventRecord(sc.done.get(), c->stream));
-    sc.in_flight = true;
-    sc.launches = 1;
-    return CFMM_OK;
+    const int rc = sc.launch(c, sc.ev, "size path",
+                             [&](hipEvent_t e0, hipEvent_t e1) { return launch_size_path(a, c->opt_size_max_blocks, c->stream, e0, e1); });
+    if (rc == CFMM_OK) sc.launches = 1;
+    return rc;
 }
 
-// A parent.  Per round the 64 trial sizes of every path (trial j of path p is path j*count + p of the inner call, whose hop
-// arrays repeat the call's 64 times) go through cfmm_quote_path's parent path; the rest is size_grid.h.  Everything was
-// checked by the caller; the answers are written only when every call has succeeded.
+// A parent.  Per round the 64 trial sizes of every path (trial j of path p is path j*count + p of the inner call: split_search.h
+// GridPaths) go through cfmm_quote_path's parent path; the rest is size_grid.h.  Everything was checked by the caller; the
+// answers are written only when every call has succeeded.
 int multi_size(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg, const int64_t* hop_row,
                const int32_t* ci, const int32_t* co, const double* max_in, const double* value_in, const double* value_out,
                int32_t rounds, double* amount_in, double* amount_out, double* gain, int32_t* status)
 {
     constexpr size_t J = CFMM_SIZE_POINTS;
-    const size_t n = (size_t)count, H = (size_t)max_hops, N = J * n;
-    std::vector<int32_t> nh(N), seg(H * N), cin(H * N), cot(H * N);
-    std::vector<int64_t> row(H * N);
-    for (size_t j = 0; j < J; ++j) {
-        std::memcpy(&nh[j * n], n_hops, n * sizeof(int32_t));
-        for (size_t k = 0; k < H; ++k) {
-            std::memcpy(&seg[k * N + j * n], hop_seg + k * n, n * sizeof(int32_t));
-            std::memcpy(&row[k * N + j * n], hop_row + k * n, n * sizeof(int64_t));
-            std::memcpy(&cin[k * N + j * n], ci + k * n, n * sizeof(int32_t));
-            std::memcpy(&cot[k * N + j * n], co + k * n, n * sizeof(int32_t));
-        }
-    }
+    const size_t n = (size_t)count, N = J * n;
+    const GridPaths gp(count, max_hops, n_hops, hop_seg, hop_row, ci, co);
     std::vector<double> lo(n, 0.0), hi(max_in, max_in + n), x(N), y(N), bx(n, 0.0), by(n, 0.0), bg(n, 0.0);
     std::vector<char> any_nan(n, 0);
     SizeScratch& sc = c->size;
@@ -92,8 +50,8 @@ int multi_size(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_ho
     for (int r = 0; r < rounds; ++r) {
         for (size_t j = 0; j < J; ++j)
             for (size_t p = 0; p < n; ++p) x[j * n + p] = size_trial(lo[p], hi[p], (int)j);
-        const int rc = cfmm_quote_path(c, (int64_t)N, max_hops, nh.data(), seg.data(), row.data(), cin.data(), cot.data(), x.data(),
-                                       y.data(), nullptr);
+        const int rc = cfmm_quote_path(c, (int64_t)N, max_hops, gp.nh.data(), gp.seg.data(), gp.row.data(), gp.cin.data(), gp.cot.data(),
+                                       x.data(), y.data(), nullptr);
         if (rc != CFMM_OK) return rc;   // (the message is the inner call's)
         if (c->opt_time_kernels != 0) ns += c->quote.ns;
         for (size_t p = 0; p < n; ++p) {
@@ -138,23 +96,6 @@ void fill_args(SizeArgs& a, int64_t count, int32_t max_hops, int32_t rounds)
 
 } // namespace
 
-namespace cfmm {
-
-int size_ns(cfmm_ctx* c, int64_t* value)
-{
-    SizeScratch& sc = c->size;
-    if (sc.dev_timed) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        HIP_TRY(c, hipEventSynchronize(sc.ev.stop(0)));
-        if (const int rc = sc.ev.elapsed_ns(c, 0, 1, sc.ns)) return rc;
-        sc.dev_timed = false;
-    }
-    *value = sc.ns;
-    return CFMM_OK;
-}
-
-} // namespace cfmm
-
 // Pinned staging behind the table (stage_layout.h SizeStage), copied to / from the scratch's device arrays in stream order; one
 // synchronisation.
 int cfmm_size_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* n_hops, const int32_t* hop_seg, const int64_t* hop_row,
@@ -182,7 +123,7 @@ int cfmm_size_path(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32_t* 
     const size_t n = (size_t)count, H = (size_t)max_hops, nh = n * H;
     const SizeStage lay = stage_of(c, n, nh);
     SizeArgs a{};
-    if ((rc = upload_table(c, lay, a.p.nseg)) || (rc = sc.hop_i32.grow(c, n + 3 * nh)) || (rc = sc.hop_row.grow(c, nh)) ||
+    if ((rc = sc.upload_table(c, lay, a.p.nseg)) || (rc = sc.hop_i32.grow(c, n + 3 * nh)) || (rc = sc.hop_row.grow(c, nh)) ||
         (rc = sc.in.grow(c, 3 * n)) || (rc = sc.out.grow(c, 3 * n)) || (rc = sc.status.grow(c, n)))
         return rc;
     unsigned long long* st = sc.stage.host();
@@ -250,7 +191,7 @@ int cfmm_size_path_dev(cfmm_ctx* c, int64_t count, int32_t max_hops, const int32
         return fail(c, CFMM_ERR_INVALID_ARG, "%s: null path array", kWhoDev);
     HIP_TRY(c, hipSetDevice(c->device));
     SizeArgs a{};
-    if ((rc = upload_table(c, stage_of(c, 0, 0), a.p.nseg)) != CFMM_OK) return rc;
+    if ((rc = c->size.upload_table(c, stage_of(c, 0, 0), a.p.nseg)) != CFMM_OK) return rc;
     fill_args(a, count, max_hops, rounds);
     a.p.segs = c->size.table.get();
     a.p.n_hops = d_n_hops;

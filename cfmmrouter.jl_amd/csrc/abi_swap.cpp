@@ -108,16 +108,14 @@ int swap_single(cfmm_ctx* c, const Dir& dir, int32_t seg, int64_t count, const i
         prices.clear();
         for (size_t j = off; j < off + nw; ++j) {
             const int64_t row = idx ? idx[plan.perm[j]] : plan.perm[j];
-            double P = h_price[j];
+            double P;
             if (out) {
                 if (h_status[j] != CFMM_SWAP_APPLIED) continue;   // (the kernel has tested the price of an applied swap)
-            } else if (!finite_pos(P)) {   // check_univ3_price would refuse it: the pool stays
+            } else if (!finite_pos(h_price[j])) {   // check_univ3_price would refuse it: the pool stays
                 refused_at[j] = 1;
                 continue;
             }
-            const double top = s.lad.lower_ticks(row)[0];   // out of liquidity on that side: the first tick's upper price
-            P = P > top ? top : P;
-            if (std::memcmp(&P, &s.h_cp[(size_t)row], sizeof P) == 0) continue;   // (a == 0, no liquidity: where it was)
+            if (!univ3_landing(h_price[j], s.lad.lower_ticks(row)[0], s.h_cp[(size_t)row], P)) continue;   // (a == 0, no liquidity: where it was)
             rows.push_back(row);
             prices.push_back(P);
         }

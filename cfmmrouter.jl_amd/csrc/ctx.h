@@ -21,11 +21,11 @@
 //   abi_swap.cpp      exact-input swaps that move the pools, and by a direction their exact-output form cfmm_swap_out
 //                     (cfmm_swap: the quote, then R + γΔ − Λ; swap_waves.h: the HIP-free wave numbering of repeated rows)
 //   abi_swap_path.cpp swap PATHS that move their pools, all or nothing, in both directions (cfmm_swap_path,
-//                     cfmm_swap_path_out; swap_path_waves.h: the HIP-free wave numbering of paths that share pools,
-//                     swap_path_checks.h: the HIP-free checks beyond path_checks.h)
+//                     cfmm_swap_path_out; swap_path_checks.h: the HIP-free checks beyond path_checks.h), and swap_paths_run, the
+//                     driver of every executing path entry (swap_path_waves.h: the HIP-free wave planner and its
+//                     pool table; swap_fill.h: the HIP-free fill in launch order, its inverse and the UniV3 landing rule)
 //   abi_swap_order.cpp ORDERS executed all or nothing across their 1 .. 8 paths, in both directions (cfmm_swap_order,
-//                     cfmm_swap_order_out; swap_order_waves.h: the HIP-free wave numbering of orders that share pools,
-//                     order_checks.h: the HIP-free checks)
+//                     cfmm_swap_order_out: the checks, order_checks.h, HIP-free; the call is swap_paths_run)
 //   abi_find_path.cpp the best swap walk between two tokens, found on the device (cfmm_find_path; find_checks.h: the HIP-free
 //                     checks and the chunking rule)
 //   abi_size_path.cpp the input of a path that maximises its gain (cfmm_size_path; size_checks.h: the HIP-free checks, size_grid.h:
@@ -34,6 +34,8 @@
 //                     split_grid.h: the search's arithmetic, shared with the kernel)
 //                     and bought through several paths (cfmm_split_paths_out: the same file, checks and scratch;
 //                     split_out_grid.h: what its search has of its own)
+//   path_rig.h        the rig of the read-only path entries (PathRig below: quote_path, size_path, split_paths)
+//   split_search.h    the search a multi-device parent runs on the host for the last two (no HIP)
 //   seg_view.h        what those eight share, on top of this header: a segment as their kernels and their checks see it
 //   stage_layout.h    ... and how each carves its pinned staging buffer into columns (no HIP)
 //   shard_split.h     shard_range, and a parent's queries bucketed by shard (no HIP)
@@ -51,7 +53,7 @@
 #include "ladder_store.h"
 #include "launch_plan.h"
 #include "shard_split.h"
-#include "swap_path_waves.h"
+#include "swap_fill.h"
 #include "sweep.h"
 
 #include <atomic>
@@ -256,20 +258,38 @@ struct QuoteScratch {
     bool dev_timed = false;            // the latest timed call was cfmm_quote_dev: its span is read when asked for
 };
 
-// cfmm_quote_path and cfmm_quote_path_out (abi_quote_path.cpp, quote_path_kernels.h; one scratch for both directions): the
-// device copies of one call's paths, amounts, answers and optional hop amounts, the segment table (sweep.h PathSeg) and ONE
-// pinned staging buffer for all of them -- proportional to count x max_hops (and the number of segments), never to the pools.
-// The table is rebuilt and uploaded on every call; `done`, recorded behind each call's kernel, guards the staging and the
-// table against the call before (the _dev entries do not wait).  The kernel's span goes to QuoteScratch's events and "quote_ns".
-struct PathScratch {
+// The rig of the READ-ONLY path entries (cfmm_quote_path(_out), cfmm_size_path, cfmm_split_paths(_out) and their _dev forms;
+// the functions: path_rig.h): the segment table (sweep.h PathSeg) on the device and the entry's ONE pinned staging buffer, whose
+// first column is the table's host copy.  The table is rebuilt and uploaded on every call; `done`, recorded behind each
+// call's kernel, guards the staging and the table against the call before (the _dev entries do not wait).
+struct PathRig {
     DevBuf<PathSeg> table;             // [segments]
+    PinnedBuf<unsigned long long> stage;   // 8-byte words: the entry's layout of stage_layout.h
+    Event done;                        // behind the latest call's kernel
+    bool in_flight = false;
+    int wait_previous(cfmm_ctx* c);
+    template <class Layout>
+    int upload_table(cfmm_ctx* c, const Layout& lay, int32_t& nrec_out);   // Layout: the entry's of stage_layout.h
+    template <class Launch>
+    int launch(cfmm_ctx* c, EventPairs& ev, const char* what, const Launch& go);
+};
+// ... of an entry with a span of its own ("size_ns", "split_ns") and a launch count
+struct TimedPathRig : PathRig {
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // that kernel's span (a parent: the sum of its rounds' "quote_ns")
+    bool dev_timed = false;            // the latest timed call was the _dev entry: its span is read when asked for
+    int64_t launches = 0;              // kernel launches of the latest call (1; a parent: its cfmm_quote_path calls)
+    int read_ns(cfmm_ctx* c, int64_t* value);
+};
+
+// cfmm_quote_path and cfmm_quote_path_out (abi_quote_path.cpp, quote_path_kernels.h; one scratch for both directions): the rig
+// and the device copies of one call's paths, amounts, answers and optional hop amounts -- proportional to count x max_hops
+// (and the number of segments), never to the pools.  The kernel's span goes to QuoteScratch's events and "quote_ns".
+struct PathScratch : PathRig {         // (stage: stage_layout.h PathStage)
     DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
     DevBuf<long long> hop_row;         // [max_hops][count]
     DevBuf<double> given, answer;      // [count]
     DevBuf<double> hops;               // [max_hops][count]
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h PathStage
-    Event done;                        // behind the latest call's kernel
-    bool in_flight = false;
 };
 
 // cfmm_swap and cfmm_swap_out (abi_swap.cpp, swap_kernels.h, swap_out_kernels.h; one scratch for both directions): the
@@ -290,40 +310,23 @@ struct SwapScratch {
     int64_t launches = 0;              // read-only option "swap_launches": kernel launches (waves) of the latest call
 };
 
-// cfmm_swap_path (abi_swap_path.cpp, swap_path_kernels.h): the device copies of one call's paths -- in WAVE order
-// (swap_path_waves.h) -- the limits, answers, hop amounts, UniV3 landing prices and statuses, the segment table (sweep.h
-// SwapPathSeg, rebuilt per call), one window flag per segment and ONE pinned staging buffer for all of them -- proportional
-// to count x max_hops (and the number of segments), never to the pools.  The call ends synchronised, so nothing here is
-// guarded against the call before.  The spans and the refusals go to SwapScratch's "swap_ns" / "swap_refused".
+// cfmm_swap_path(_out) and cfmm_swap_order(_out) (abi_swap_path.cpp swap_paths_run; swap_path_kernels.h, swap_order_kernels.h;
+// ONE scratch for the four: each call ends synchronised, so nothing here is guarded against the call before): the device
+// copies of one call's paths and orders, both in WAVE order (swap_path_waves.h), the limits, answers, hop amounts, UniV3
+// landing prices and statuses, the segment table (sweep.h SwapPathSeg, rebuilt per call), one window flag per segment and ONE
+// pinned staging buffer for all of them -- proportional to the orders and to n_paths x max_hops (and the number of
+// segments), never to the pools.  The path entries have no orders: the tails marked "orders" are empty and the limits are the
+// paths'.  The spans, the refusals and the waves go to SwapScratch's "swap_ns" / "swap_refused" / "swap_launches".
 struct SwapPathScratch {
     DevBuf<SwapPathSeg> table;         // [segments]
-    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
-    DevBuf<long long> hop_row;         // [max_hops][count]
-    DevBuf<double> amt;                // [2][count] the given amounts, the limits
-    DevBuf<double> out;                // [count]
-    DevBuf<double> hops, price;        // [max_hops][count]
-    DevBuf<int32_t> status;            // [count]
+    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][n_paths]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
+    DevBuf<long long> i64;             // [max_hops][n_paths] hop_row, then (orders) [count + 1] order_first
+    DevBuf<double> amt;                // [n_paths] the given amounts, then the limits ([count] of the orders, else [n_paths])
+    DevBuf<double> out;                // [n_paths] the paths' answers, then (orders) [count] the totals
+    DevBuf<double> hops, price;        // [max_hops][n_paths]
+    DevBuf<int32_t> status;            // [n_paths] the paths' statuses, then (orders) [count] status
     DevBuf<int> left;                  // [segments] a new reserve of the segment left the window of the fast arithmetic
     PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapPathStage
-    EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
-    PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
-};
-
-// cfmm_swap_order / cfmm_swap_order_out (abi_swap_order.cpp, swap_order_kernels.h): SwapPathScratch's arrangement for orders --
-// the device copies of one call's paths and orders, both in WAVE order (swap_order_waves.h), the limits, answers, hop amounts,
-// UniV3 landing prices and statuses, the segment table (rebuilt per call), one window flag per segment and ONE pinned staging
-// buffer -- proportional to the orders and to n_paths x max_hops (and the number of segments), never to the pools.  The call
-// ends synchronised.  The spans and the orders not applied go to SwapScratch's "swap_ns" / "swap_refused" / "swap_launches".
-struct SwapOrderScratch {
-    DevBuf<SwapPathSeg> table;         // [segments]
-    DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][n_paths]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
-    DevBuf<long long> i64;             // [max_hops][n_paths] hop_row, then [count + 1] order_first
-    DevBuf<double> amt;                // [n_paths] the given amounts, then [count] the limits
-    DevBuf<double> out;                // [n_paths] the paths' answers, then [count] the totals
-    DevBuf<double> hops, price;        // [max_hops][n_paths]
-    DevBuf<int32_t> status;            // [n_paths] path_status, then [count] status
-    DevBuf<int> left;                  // [segments] a new reserve of the segment left the window of the fast arithmetic
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapOrderStage
     EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
     PathPoolTable pools;               // the wave planner's table (swap_path_waves.h), host memory kept between calls
 };
@@ -358,47 +361,28 @@ struct FindScratch {
     int64_t round_ns[2][CFMM_MAX_SPLIT_PATHS] = {};
 };
 
-// cfmm_size_path (abi_size_path.cpp, size_path_kernels.h): the device copies of one call's paths, limits, values and answers,
-// the segment table (sweep.h PathSeg, rebuilt and uploaded on every call, for abi_quote_path.cpp's reason) and ONE pinned
-// staging buffer for all of them -- proportional to count x max_hops (and the number of segments), never to the pools.
-// `done`, recorded behind each call's kernel, guards the staging and the table against the call before (cfmm_size_path_dev does
-// not wait).  A multi-device parent uses none of the device arrays: its search runs on the host (size_grid.h) over cfmm_quote_path.
-struct SizeScratch {
-    DevBuf<PathSeg> table;             // [segments]
+// cfmm_size_path (abi_size_path.cpp, size_path_kernels.h): the rig (read-only options "size_ns" / "size_launches") and the
+// device copies of one call's paths, limits, values and answers -- proportional to count x max_hops (and the number of
+// segments), never to the pools.  A multi-device parent uses none of the device arrays: its search runs on the host
+// (size_grid.h) over cfmm_quote_path.
+struct SizeScratch : TimedPathRig {    // (stage: stage_layout.h SizeStage)
     DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][count]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
     DevBuf<long long> hop_row;         // [max_hops][count]
     DevBuf<double> in;                 // [3][count] max_amount_in, value_in, value_out
     DevBuf<double> out;                // [3][count] amount_in, amount_out, gain
     DevBuf<int32_t> status;            // [count]
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SizeStage
-    Event done;                        // behind the latest call's kernel
-    bool in_flight = false;
-    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
-    int64_t ns = 0;                    // read-only option "size_ns": that kernel's span (a parent: the sum of its rounds' "quote_ns")
-    bool dev_timed = false;            // the latest timed call was cfmm_size_path_dev: its span is read when asked for
-    int64_t launches = 0;              // read-only option "size_launches": kernel launches of the latest call (a parent: its
-                                       // cfmm_quote_path calls)
 };
 
-// cfmm_split_paths (abi_split_paths.cpp, split_paths_kernels.h): SizeScratch's arrangement for the splits -- the device copies of
-// one call's orders, paths and answers, the segment table (rebuilt and uploaded on every call) and ONE pinned staging buffer,
-// proportional to the orders and to n_paths x max_hops, never to the pools; `done` guards staging and table against the call
-// before.  A multi-device parent uses none of the device arrays: its search runs on the host (split_grid.h) over cfmm_quote_path.
-struct SplitScratch {
-    DevBuf<PathSeg> table;             // [segments]
+// cfmm_split_paths and cfmm_split_paths_out (abi_split_paths.cpp, split_paths_kernels.h, split_paths_out_kernels.h): the rig
+// (read-only options "split_ns" / "split_launches") and the device copies of one call's orders, paths and answers, proportional
+// to the orders and to n_paths x max_hops, never to the pools.  A multi-device parent uses none of the device arrays: its
+// search runs on the host (split_search.h) over cfmm_quote_path / cfmm_quote_path_out.
+struct SplitScratch : TimedPathRig {   // (stage: stage_layout.h SplitStage)
     DevBuf<int32_t> hop_i32;           // [1 + 3*max_hops][n_paths]: n_hops, then hop_seg, hop_coin_in, hop_coin_out
     DevBuf<long long> i64;             // [max_hops][n_paths] hop_row, then [count + 1] order_first
     DevBuf<double> amount;             // [count]
     DevBuf<double> out;                // [2][n_paths] path_amount_in, path_amount_out, then [count] total_out
     DevBuf<int32_t> status;            // [count]
-    PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SplitStage
-    Event done;                        // behind the latest call's kernel
-    bool in_flight = false;
-    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
-    int64_t ns = 0;                    // read-only option "split_ns": that kernel's span (a parent: the sum of its rounds' "quote_ns")
-    bool dev_timed = false;            // the latest timed call was cfmm_split_paths_dev: its span is read when asked for
-    int64_t launches = 0;              // read-only option "split_launches": kernel launches of the latest call (1; a parent: its
-                                       // cfmm_quote_path calls)
 };
 
 // The launch-invariant descriptors of the sweep launches (sweep.h SweepDesc; launch_plan.h build_sweep_desc) on the device,
@@ -550,7 +534,6 @@ struct cfmm_ctx {
     // where it stood before these two came.)
     int64_t opt_order_max_blocks = cfmm::kOrderMaxBlocks; // the most blocks of their launches (>= 1; the wavefronts stride over a wave's
                                    //    orders, the same bits at any value: a measurement and test switch, as "split_max_blocks")
-    cfmm::SwapOrderScratch swap_order;
 
     mutable std::string err = "";
 };
@@ -612,11 +595,6 @@ int check_quote_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, in
 int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, int kind, int64_t m, int nc, int64_t count,
                         const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out, const double* given, const double* answer);
 
-// abi_size_path.cpp
-int size_ns(cfmm_ctx* c, int64_t* value);
-// abi_split_paths.cpp
-int split_ns(cfmm_ctx* c, int64_t* value);
-
 // abi_update.cpp
 // cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not
 // above the row's first tick): apply_univ3 for the records prepared on the host, univ3_make_room, one scatter; h_cp follows.
@@ -626,6 +604,27 @@ int univ3_move_prices(cfmm_ctx* c, Segment& s, const std::vector<int64_t>& rows,
 // abi_swap.cpp
 // the trades and outputs on the device describe the market before the swaps: what cfmm_pools_set_* invalidates
 void swap_invalidate(cfmm_ctx* c);
+
+// abi_swap_path.cpp
+// One checked call of cfmm_swap_path(_out) or cfmm_swap_order(_out) on a single-device context, count > 0: the plan, the
+// staging, one launch per wave, the UniV3 moves between waves, the answers back in the caller's order.
+struct SwapPathCall {
+    const char* what;              // "swap path" / "swap order": the launch error's text
+    int64_t orders;                // 0: the path entries -- every path is applied on its own, `limit` has one entry per path
+    const int64_t* order_first;    // [orders + 1], null without orders
+    int64_t n_paths;
+    int32_t max_hops;
+    HopCols hop;
+    const double *given, *limit;   // limit: null = none
+    double *answer, *hop_ans;      // [n_paths]; [max_hops][n_paths] or null
+    int32_t* path_status;          // [n_paths] or null
+    double* total;                 // [orders]
+    int32_t* status;               // [orders]
+};
+// `launch`: one wave.  a.p is a SwapPathArgs for the wave's paths (the path entries; a.orders == 0) or for all paths of the call
+// with the wave's orders beside it (sweep.h SwapOrderArgs).
+using SwapWaveLaunch = hipError_t (*)(const cfmm_ctx* c, bool exact_out, const SwapOrderArgs& a, hipEvent_t e0, hipEvent_t e1);
+int swap_paths_run(cfmm_ctx* c, bool exact_out, const SwapPathCall& q, SwapWaveLaunch launch);
 
 // abi_rccl.cpp
 int rccl_all_reduce_out(cfmm_ctx* c, double* d_out);

@@ -1,6 +1,6 @@
-// stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp,
-// abi_swap_order.cpp,
-// abi_find_path.cpp (both find entries and cfmm_find_disjoint_paths), abi_size_path.cpp, abi_split_paths.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
+// stage_layout.h -- internal: how the query entries (abi_quote.cpp, abi_swap.cpp, abi_quote_path.cpp, abi_swap_path.cpp for
+// itself and abi_swap_order.cpp, abi_find_path.cpp (both find entries and cfmm_find_disjoint_paths), abi_size_path.cpp,
+// abi_split_paths.cpp) carve their ONE pinned staging buffer of 8-byte words into typed columns.  No HIP, no context.
 // A layout is declared once, column by column; each column starts on a word and takes ceil(bytes / 8) words.  The entry grows
 // its buffer by words() and takes every host pointer from the column's handle, so the size and the addresses cannot disagree.
 // What crosses to the device in ONE copy is ONE column (the [2][count] coins, n_hops with the three int32 hop columns, ...).
@@ -91,32 +91,21 @@ struct SplitStage {   // cfmm_split_paths: g orders over n paths (cfmm_split_pat
         : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh + (g ? g + 1 : 0))),
           amount(l.add<double>(g)), out(l.add<double>(2 * n + g)), status(l.add<int32_t>(g)) {}
 };
-struct SwapPathStage {   // cfmm_swap_path / cfmm_swap_path_out, the paths in wave order; nrec: the table's records, one window flag each
-    StageLayout l;
-    StageCol<unsigned char> table;
-    StageCol<int32_t> i32;      // [1 + 3*H][n]
-    StageCol<long long> row;    // [H][n]
-    StageCol<double> amt;       // [2][n] the given amounts, the limits
-    StageCol<double> out, hops, price;
-    StageCol<int32_t> status;
-    StageCol<int> left;         // [nrec]
-    SwapPathStage(size_t table_bytes, size_t nrec, size_t n, size_t nh)
-        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), amt(l.add<double>(2 * n)),
-          out(l.add<double>(n)), hops(l.add<double>(nh)), price(l.add<double>(nh)), status(l.add<int32_t>(n)), left(l.add<int>(nrec)) {}
-};
-struct SwapOrderStage {   // cfmm_swap_order / cfmm_swap_order_out: g orders over n paths, both in wave order; nrec as SwapPathStage
+struct SwapPathStage {   // cfmm_swap_path(_out) and cfmm_swap_order(_out): g orders (the path entries: 0) over n paths, in wave
+                         // order; nrec: the table's records, one window flag each
     StageLayout l;
     StageCol<unsigned char> table;
     StageCol<int32_t> i32;      // [1 + 3*H][n]
     StageCol<long long> row;    // [H][n] hop_row, then [g + 1] order_first
-    StageCol<double> amt;       // [n] the given amounts, then [g] the limits
+    StageCol<double> amt;       // [n] the given amounts, then the limits: [g], the path entries [n]
     StageCol<double> out;       // [n] the paths' answers, then [g] the totals
     StageCol<double> hops, price;
-    StageCol<int32_t> status;   // [n] path_status, then [g] status
+    StageCol<int32_t> status;   // [n] the paths' statuses, then [g] the orders'
     StageCol<int> left;         // [nrec]
-    SwapOrderStage(size_t table_bytes, size_t nrec, size_t g, size_t n, size_t nh)
-        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh + g + 1)), amt(l.add<double>(n + g)),
-          out(l.add<double>(n + g)), hops(l.add<double>(nh)), price(l.add<double>(nh)), status(l.add<int32_t>(n + g)), left(l.add<int>(nrec)) {}
+    SwapPathStage(size_t table_bytes, size_t nrec, size_t n, size_t nh, size_t g = 0)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh + (g ? g + 1 : 0))),
+          amt(l.add<double>(n + (g ? g : n))), out(l.add<double>(n + g)), hops(l.add<double>(nh)), price(l.add<double>(nh)),
+          status(l.add<int32_t>(n + g)), left(l.add<int>(nrec)) {}
 };
 struct FindStage {   // cfmm_find_path / cfmm_find_path_out
     StageLayout l;
