@@ -10,7 +10,7 @@ from .cfmms import (CFMM, BoundedProduct, Curve, GeometricMean, GeometricMeanTwo
                     grad_phi_, phi, zerotrade, ϕ, ϕ_grad_)
 from .objectives import (BasketLiquidation, LinearNonnegative, Objective, Swap, f, grad_, lower_limit,
                          upper_limit)
-from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_disjoint_paths, find_disjoint_paths_out, find_path, find_path_out, netflows, netflows_, polish_, quote, quote_out, quote_path, quote_path_out, route_, route_order, route_order_, route_order_out, route_order_out_, size_path, split_paths, split_paths_out,
+from .router import (DeviceBackend, Router, active_trades, dual_jacobian, find_arb_ as _find_arb_router, find_disjoint_paths, find_disjoint_paths_out, find_path, find_path_out, netflows, netflows_, path_price_impact, polish_, price_impact, quote, quote_out, quote_path, quote_path_out, quote_path_rate, quote_rate, route_, route_order, route_order_, route_order_out, route_order_out_, size_path, split_paths, split_paths_out, spot_price,
                      swap_, swap_order_, swap_order_out_, swap_out_, swap_path_, swap_path_out_, update_pools_, update_reserves_)
 
 
@@ -36,5 +36,6 @@ __all__ = [
     "split_paths", "SPLIT_OK", "SPLIT_NONE", "SPLIT_NAN", "SPLIT_SATURATED",
     "split_paths_out", "find_disjoint_paths_out", "route_order_out", "SPLIT_UNOBTAINABLE",
     "swap_order_", "swap_order_out_", "route_order_", "route_order_out_",
+    "quote_rate", "spot_price", "price_impact", "quote_path_rate", "path_price_impact",
     "ORDER_APPLIED", "ORDER_LIMIT", "ORDER_REFUSED", "ORDER_UNOBTAINABLE", "ORDER_PATH_HELD",
 ]

@@ -155,6 +155,10 @@ def lib():
     L.cfmm_quote_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cfmm_quote_rate.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
+    L.cfmm_quote_rate_dev.argtypes = [_ctx, C.c_int32, C.c_int64] + [C.c_void_p] * 6
+    L.cfmm_quote_path_rate.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p]
+    L.cfmm_quote_path_rate_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 10
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_path_out.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
     L.cfmm_find_disjoint_paths.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_int32, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, _i32p, _i64p, _i32p, _i32p]
@@ -586,6 +590,62 @@ class Context:
         self._check(self._L.cfmm_quote_out_dev(self._h, int(seg), int(count), C.c_void_p(d_idx or None), C.c_void_p(d_coin_in or None),
                                                C.c_void_p(d_coin_out or None), C.c_void_p(d_amount_out or None),
                                                C.c_void_p(d_amount_in or None)))
+
+    # -- marginal rates (cfmm_quote_rate / cfmm_quote_path_rate, include/cfmm_amd_rate.h): the quote and its derivative --------
+    def quote_rate(self, seg: int, amount_in, coin_in, coin_out=None, idx=None, count=None, want_out=True):
+        """(amount_out, rate) [count]: quote's answer bit for bit, and the right derivative of the quote at amount_in -- at
+        0 the pool's spot rate, fee included.  quote's arguments and checks.  amount_in=None means 0 for every query (a
+        spot-price table; `count` gives the number of queries when neither coin_in nor idx is an array, and idx=None is then
+        the dense pass over rows 0 .. count-1); want_out=False is allowed exactly then and returns (None, rate)."""
+        if amount_in is None:
+            n = int(count) if count is not None else max(np.size(coin_in), 0 if idx is None else np.size(idx))
+            amt = None
+        else:
+            amt = f64(amount_in).reshape(-1)
+            n = amt.size
+            want_out = True
+        bcast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32).reshape(-1) if np.ndim(a) else
+                                                               np.int32(a), (n,)), dtype=np.int32)
+        try:
+            ci = bcast(coin_in)
+            co = None if coin_out is None else bcast(coin_out)
+        except ValueError:
+            raise ArgumentError("coin_in and coin_out must be scalars or have one entry per query") from None
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if ix is not None and ix.size != n:
+            raise ArgumentError("idx must have one entry per query")
+        out, rate = (np.empty(n) if want_out else None), np.empty(n)
+        self._check(self._L.cfmm_quote_rate(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(out), ptr(rate)))
+        return out, rate
+
+    def quote_rate_dev(self, seg: int, count: int, d_amount_in: int, d_coin_in: int, d_amount_out: int, d_rate: int,
+                       d_coin_out: int = 0, d_idx: int = 0):
+        """cfmm_quote_rate_dev on device addresses, as quote_dev (0 = NULL; d_amount_in 0: every amount is 0, and d_amount_out
+        may be 0 exactly then): asynchronous, unchecked -- a bad query gets NaN in both outputs."""
+        self._check(self._L.cfmm_quote_rate_dev(self._h, int(seg), int(count), *(C.c_void_p(p or None) for p in (
+            d_idx, d_coin_in, d_coin_out, d_amount_in, d_amount_out, d_rate))))
+
+    def quote_path_rate(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, hops=False):
+        """(amount_out, rate[, hop_out, hop_rate]): quote_path's answers bit for bit, every hop's rate at the amount entering
+        it ([max_hops, count], NaN in the unused slots) and their left-fold product ((r_0·r_1)·r_2)..., the path's marginal
+        rate.  quote_path's arguments and checks."""
+        amt = f64(amount_in).reshape(-1)
+        n = amt.size
+        nh, seg, row, ci, co = self._path_columns(n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, n)
+        max_hops = max(1, int(seg.shape[0]))
+        out, rate = np.empty(n), np.empty(n)
+        hv, hr = (np.empty((max_hops, n)), np.empty((max_hops, n))) if hops else (None, None)
+        if n:
+            self._check(self._L.cfmm_quote_path_rate(self._h, n, max_hops, ptr(nh), ptr(seg), ptr(row), ptr(ci), ptr(co), ptr(amt),
+                                                     ptr(out), ptr(rate), ptr(hv), ptr(hr)))
+        return (out, rate, hv, hr) if hops else (out, rate)
+
+    def quote_path_rate_dev(self, count: int, max_hops: int, d_n_hops: int, d_hop_seg: int, d_hop_row: int, d_hop_coin_in: int,
+                            d_hop_coin_out: int, d_amount_in: int, d_amount_out: int, d_rate: int, d_hop_out: int = 0,
+                            d_hop_rate: int = 0):
+        """cfmm_quote_path_rate_dev on device addresses, as quote_path_dev (the hop arrays hop-major [max_hops, count])."""
+        self._check(self._L.cfmm_quote_path_rate_dev(self._h, int(count), int(max_hops), *(C.c_void_p(p or None) for p in (
+            d_n_hops, d_hop_seg, d_hop_row, d_hop_coin_in, d_hop_coin_out, d_amount_in, d_amount_out, d_rate, d_hop_out, d_hop_rate))))
 
     # -- multi-hop path quotes (cfmm_quote_path / cfmm_quote_path_out): an amount through a path of pools of any segments ----
     def quote_path(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, hops=False):

@@ -292,6 +292,18 @@ struct PathScratch : PathRig {         // (stage: stage_layout.h PathStage)
     DevBuf<double> hops;               // [max_hops][count]
 };
 
+// cfmm_quote_rate and cfmm_quote_path_rate (abi_rate.cpp, rate_kernels.h): the query columns, the staging, the table and the rig
+// are QuoteScratch's and PathScratch's (a call of either entry ends synchronised); what is kept here is the device copy of the
+// two answers per query / path and per hop, and the span of the latest call's kernel -- proportional to the queries, never
+// to the pools.
+struct RateScratch {
+    DevBuf<double> out;                // [2][count] amount_out, rate
+    DevBuf<double> hops;               // [2][max_hops][count] hop_out, hop_rate
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // read-only option "rate_ns": that kernel's span
+    bool dev_timed = false;            // the latest timed call was a _dev entry: its span is read when asked for
+};
+
 // cfmm_swap and cfmm_swap_out (abi_swap.cpp, swap_kernels.h, swap_out_kernels.h; one scratch for both directions): the
 // device copies of one call's swaps -- in WAVE order (swap_waves.h) -- their answers, the UniV3 landing prices and the pinned
 // staging of all of them, grown on demand and kept for the next call -- proportional to the swaps of the largest call, never
@@ -516,6 +528,7 @@ struct cfmm_ctx {
     cfmm::SelectScratch sel;
     cfmm::QuoteScratch quote;
     cfmm::PathScratch path;
+    cfmm::RateScratch rate;
     cfmm::SwapScratch swap;
     cfmm::SwapPathScratch swap_path;
     cfmm::FindScratch find;
@@ -594,6 +607,9 @@ int quote_ns(cfmm_ctx* c, int64_t* value);
 int check_quote_seg(cfmm_ctx* c, const char* who, int32_t seg, int64_t count, int64_t n_segs);
 int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, int kind, int64_t m, int nc, int64_t count,
                         const int64_t* idx, const int32_t* coin_in, const int32_t* coin_out, const double* given, const double* answer);
+
+// abi_rate.cpp
+int rate_ns(cfmm_ctx* c, int64_t* value);
 
 // abi_update.cpp
 // cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not

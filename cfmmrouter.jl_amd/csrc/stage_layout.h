@@ -43,6 +43,15 @@ struct QuoteStage {   // cfmm_quote / cfmm_quote_out
     StageCol<long long> idx;    // only where the call has one
     QuoteStage(size_t n, bool has_idx) : amt(l.add<double>(n)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(n)), idx(l.add<long long>(has_idx ? n : 0)) {}
 };
+struct RateStage {   // cfmm_quote_rate: QuoteStage's columns (amt: only where the call has amounts) and the rates
+    StageLayout l;
+    StageCol<double> amt;
+    StageCol<int32_t> coins;    // [2][n] coin_in, coin_out
+    StageCol<double> out;       // [2][n] amount_out, rate
+    StageCol<long long> idx;    // only where the call has one
+    RateStage(size_t n, bool has_amt, bool has_idx)
+        : amt(l.add<double>(has_amt ? n : 0)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(2 * n)), idx(l.add<long long>(has_idx ? n : 0)) {}
+};
 struct SwapStage {   // cfmm_swap / cfmm_swap_out, the swaps in wave order; price: UniV3 segments, limit / status: cfmm_swap_out
     StageLayout l;
     StageCol<double> amt;
@@ -66,6 +75,18 @@ struct PathStage {   // cfmm_quote_path / cfmm_quote_path_out (the _dev entries:
     PathStage(size_t table_bytes, size_t n, size_t nh, bool want_hops)
         : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), given(l.add<double>(n)),
           answer(l.add<double>(n)), hops(l.add<double>(want_hops ? nh : 0)) {}
+};
+struct PathRateStage {   // cfmm_quote_path_rate (cfmm_quote_path_rate_dev: the table alone, n = 0)
+    StageLayout l;
+    StageCol<unsigned char> table;
+    StageCol<int32_t> i32;      // [1 + 3*H][n] n_hops, hop_seg, hop_coin_in, hop_coin_out
+    StageCol<long long> row;    // [H][n]
+    StageCol<double> given;
+    StageCol<double> answer;    // [2][n] amount_out, rate
+    StageCol<double> hops;      // [2][H][n] hop_out, hop_rate (the half the call does not want: unused)
+    PathRateStage(size_t table_bytes, size_t n, size_t nh)
+        : table(l.add<unsigned char>(table_bytes)), i32(l.add<int32_t>(n + 3 * nh)), row(l.add<long long>(nh)), given(l.add<double>(n)),
+          answer(l.add<double>(2 * n)), hops(l.add<double>(2 * nh)) {}
 };
 struct SizeStage {   // cfmm_size_path (cfmm_size_path_dev: the table alone, n = 0)
     StageLayout l;

@@ -199,3 +199,6 @@ __global__ __launch_bounds__(BLOCK) void swap_order_out_kernel(SwapOrderArgs a)
 }
 
 } // namespace cfmm
+
+// (the next kernels of the translation unit: the include chain of sweep_kernels.hip goes on from here)
+#include "rate_kernels.h"

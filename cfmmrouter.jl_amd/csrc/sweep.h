@@ -677,4 +677,21 @@ inline size_t sweep_lds_bytes(int n_pad, int copies, int block, int need_logv, i
 }
 hipError_t prepare_kernels(size_t max_lds_bytes);
 
+// cfmm_quote_rate / cfmm_quote_rate_dev (rate_kernels.h, abi_rate.cpp): cfmm_quote's answer and its marginal rate from one read
+// of the pool, one lane per query.  `q` is quote_kernel's view, with two freedoms: q.amount_in null = every amount is 0 (the
+// spot-price table), and q.amount_out may be null exactly then.
+struct RateArgs {
+    QuoteArgs q;
+    double* rate;                // [count], never null; NaN for a query that gets NaN in amount_out
+};
+hipError_t launch_quote_rate(int kind, const RateArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                             hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// cfmm_quote_path_rate / cfmm_quote_path_rate_dev: quote_path_kernel's walk (`p`, exact input) with every hop's rate.
+struct PathRateArgs {
+    PathArgs p;
+    double* rate;                // [count], never null: ((r_0·r_1)·r_2)... over the path's hops
+    double* hop_rate;            // [max_hops][count] or null: r_k; NaN in the unused slots
+};
+hipError_t launch_quote_path_rate(const PathRateArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 } // namespace cfmm

@@ -54,6 +54,7 @@
 //                            find_out_ban_relax and its walk: cfmm_find_disjoint_paths_out, the same text in the other direction: the header includes its second half once per direction)
 //   split_paths_out_kernels.h  split_paths_out_kernel (cfmm_split_paths_out: a wanted amount bought through an order's paths, split_paths_kernel's shape, the hops walked backwards)
 //   swap_order_kernels.h  swap_order_kernel, swap_order_out_kernel (cfmm_swap_order, cfmm_swap_order_out: orders executed all or nothing across their paths, eight lanes per order)
+//   rate_kernels.h    rate_kernel, quote_path_rate_kernel (cfmm_quote_rate, cfmm_quote_path_rate: the quote and its marginal rate from one read of the pool; rate_pool.h: the per-kind derivatives)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
 #include "../../include/cfmm_amd.h"
@@ -72,7 +73,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h, and from that one's swap_order_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h, and from that one's swap_order_kernels.h, and from that one's rate_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -374,6 +375,28 @@ hipError_t launch_quote_path(bool exact_out, const PathArgs& a, hipStream_t s, h
     return launch_quote_grid(kernel, a.count, args, s, e0, e1);
 }
 
+// cfmm_quote_rate / cfmm_quote_path_rate: launch_quote's and launch_quote_path's rules and grids.  The kernels are NAMED at the
+// end of this file (rate_kernel_of, path_rate_kernel), behind every other launcher: templates are emitted in the order they are
+// named, so every kernel the translation unit had before keeps its function number, labels and bytes.
+static const void* rate_kernel_of(int kind);
+static const void* path_rate_kernel();
+
+hipError_t launch_quote_rate(int kind, const RateArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.q.count <= 0 || a.q.m <= 0 || !a.rate || (!a.q.amount_out && a.q.amount_in)) return hipErrorInvalidValue;
+    const void* kernel = rate_kernel_of(kind);   // no such kernel: there is no falling through to another one
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    void* args[] = {const_cast<RateArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_quote_grid(kernel, a.q.count, args, s, e0, e1);
+}
+
+hipError_t launch_quote_path_rate(const PathRateArgs& a, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.p.count <= 0 || a.p.nseg <= 0 || a.p.max_hops < 1 || a.p.max_hops > CFMM_MAX_PATH_HOPS || !a.p.answer || !a.rate) return hipErrorInvalidValue;
+    void* args[] = {const_cast<PathRateArgs*>(&a)};
+    return launch_quote_grid(path_rate_kernel(), a.p.count, args, s, e0, e1);
+}
+
 // one lane per swap of the wave, the same grid rule
 hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
@@ -543,5 +566,15 @@ hipError_t launch_swap_order(bool exact_out, const SwapOrderArgs& a, int64_t max
     const void* kernel = exact_out ? reinterpret_cast<const void*>(&swap_order_out_kernel<kOrderBlock>) : reinterpret_cast<const void*>(&swap_order_kernel<kOrderBlock>);
     return launch_k(kernel, dim3((unsigned)blocks), dim3(kOrderBlock), 0, s, e0, e1, args);
 }
+
+// The kernels of launch_quote_rate and launch_quote_path_rate, named here and nowhere else.  (Behind every launcher, for
+// launch_size_path's reason.)
+static const void* rate_kernel_of(int kind)
+{
+    const void* kernel = nullptr;
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&rate_kernel<decltype(K)::value>); }, [] {});
+    return kernel;
+}
+static const void* path_rate_kernel() { return reinterpret_cast<const void*>(&quote_path_rate_kernel<kQuoteBlock>); }
 
 } // namespace cfmm

@@ -716,6 +716,80 @@ def quote_out(r: Router, pools, coin_in, amount_out, coin_out=None):
     return _quote(r, "quote_out", pools, coin_in, amount_out, coin_out)
 
 
+def quote_rate(r: Router, pools, coin_in, amount_in, coin_out=None):
+    """`quote` and the MARGINAL RATE of every query (cfmm_quote_rate): returns (amount_out, rate).  amount_out is `quote`'s
+    answer bit for bit; rate[q] is the right derivative of the quote at amount_in[q] -- units of the coin out per unit of the
+    coin in for the NEXT unit tendered, fee included; at amount 0 the pool's spot rate.  On UniV3 it is the rate of the tick
+    the amount lands in (at an exact tick boundary the next tick's) and 0.0 once the ladder is exhausted.  Arguments, mapping
+    of pool numbers to (segment, row), order of the results and the refusal of a host-evaluated pool are `quote`'s."""
+    n = np.asarray(pools).size
+    res = _quote(r, "quote_rate", pools, coin_in, amount_in, coin_out, answers=2)
+    return res[:n], res[n:]
+
+
+def spot_price(r: Router, pools=None, coin_in=0, coin_out=None):
+    """The SPOT RATE of pools as they stand on the device, fee included: `quote_rate`'s rate at amount 0, without tendering
+    anything (cfmm_quote_rate with no amounts).  pools=None: every device pool of the router, in `r.cfmms` order with NaN at
+    host-evaluated pools, one dense coalesced call per segment; else positions in `r.cfmms` as `quote` takes them."""
+    if pools is not None:
+        n = np.asarray(pools).size
+        return _quote(r, "quote_rate", pools, coin_in, None, coin_out, answers=2)[n:]
+    ctx = _path_context(r)
+    L = r._layout
+    out = np.full(L.n_pools, np.nan)
+    for seg, first, batch in L.segments():   # (packed position first + row is router position place[first + row])
+        _, rate = ctx.quote_rate(seg, None, coin_in, coin_out, None, count=len(batch), want_out=False)
+        out[L.place[first:first + len(batch)]] = rate
+    return out
+
+
+def price_impact(r: Router, pools, coin_in, amount_in, coin_out=None):
+    """The PRICE IMPACT of every query: 1 − amount_out/(amount_in·spot), the share of the spot value the order loses to its own
+    size -- 0.0 where amount_in is 0, NaN where the spot rate is 0 (no liquidity in the direction), rising with the amount.
+    ONE device call of 2·count queries: the orders themselves and the same pools at amount 0.  `quote`'s arguments."""
+    pools = np.asarray(pools, dtype=np.int64).reshape(-1)
+    n = pools.size
+    try:
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (n,)))
+        ci = np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,))
+        co = None if coin_out is None else np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,))
+    except ValueError:
+        raise ArgumentError("amount_in, coin_in and coin_out must be scalars or have one entry per pool") from None
+    out, rate = quote_rate(r, np.tile(pools, 2), np.tile(ci, 2), np.concatenate([amt, np.zeros(n)]),
+                           None if co is None else np.tile(co, 2))
+    return _impact(amt, out[:n], rate[n:])
+
+
+def _impact(amt, out, spot):
+    with np.errstate(all="ignore"):
+        imp = 1.0 - out / (amt * spot)
+    imp = np.where(amt == 0.0, 0.0, imp)
+    return np.where(spot == 0.0, np.nan, imp)
+
+
+def quote_path_rate(r: Router, pools, tokens, amount_in, hops=False):
+    """`quote_path` and the MARGINAL RATE of every path (cfmm_quote_path_rate): returns (amount_out, rate[, hop_out, hop_rate]).
+    amount_out / hop_out are `quote_path`'s bit for bit; hop_rate[k, p] is `quote_rate` of hop k at the amount entering it and
+    rate[p] their product ((r_0·r_1)·r_2)... -- the chain rule: units of the last token per unit of the first for the next
+    unit tendered.  A hop through an exhausted UniV3 ladder makes the path's rate 0.0.  Arguments and refusals are
+    `quote_path`'s."""
+    n_hops, seg, row, ci, co, amt, _ = _path_hops(r, "quote_path_rate", pools, tokens, amount_in)
+    return _path_context(r).quote_path_rate(n_hops, seg, row, ci, co, amt, hops)
+
+
+def path_price_impact(r: Router, pools, tokens, amount_in):
+    """`price_impact` for paths: 1 − amount_out/(amount_in·spot) with spot the path's rate at amount 0, from ONE device call of
+    2·count paths.  `quote_path`'s arguments."""
+    pools, tokens = list(pools), list(tokens)
+    n = len(pools)
+    try:
+        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount_in, dtype=np.float64), (n,)))
+    except ValueError:
+        raise ArgumentError("amount_in must be a scalar or have one entry per path") from None
+    out, rate = quote_path_rate(r, pools + pools, tokens + tokens, np.concatenate([amt, np.zeros(n)]))
+    return _impact(amt, out[:n], rate[n:])
+
+
 def swap_(r: Router, pools, coin_in, amount_in, coin_out=None, sync_host=True):
     """Exact-input swaps APPLIED to the pools on the device (cfmm_swap): `quote`'s arguments and mapping of pool numbers to
     (segment, row), but every swap moves its pool to R + γΔ − Λ (UniV3: to the price it rests at) and the next swap of the
@@ -756,12 +830,14 @@ def swap_out_(r: Router, pools, coin_in, amount_out, coin_out=None, max_in=None,
         r._reset_trades()
 
 
-def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False, max_in=None, status=None):
+def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False, max_in=None, status=None, answers=1):
+    """answers=2 (quote_rate): the context returns (amount_out, rate) and the result is [2n], the rates behind the amounts;
+    amount=None there: no amounts (the spot rate), the first half stays NaN"""
     L = r._layout
     pools = np.asarray(pools, dtype=np.int64).reshape(-1)
     n = pools.size
     try:
-        amt = np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
+        amt = None if amount is None else np.ascontiguousarray(np.broadcast_to(np.asarray(amount, dtype=np.float64), (n,)))
         ci = np.ascontiguousarray(np.broadcast_to(np.asarray(coin_in, dtype=np.int32), (n,)))
         co = None if coin_out is None else np.ascontiguousarray(np.broadcast_to(np.asarray(coin_out, dtype=np.int32), (n,)))
     except ValueError:
@@ -778,10 +854,16 @@ def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False, m
     ctx = getattr(r._backend, "ctx", None)
     if ctx is None and per_batch:
         raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
-    out = np.empty(n)
+    out = np.empty(n) if answers == 1 else np.full(2 * n, np.nan)
     for b in sorted(per_batch):
         qs, rows = per_batch[b]
-        if status is not None:   # swap_out_
+        if answers == 2:   # quote_rate / spot_price
+            a_out, rate = ctx.quote_rate(L.seg_of[b], None if amt is None else amt[qs], ci[qs], None if co is None else co[qs], rows,
+                                         count=len(qs), want_out=amt is not None)
+            if a_out is not None:
+                out[qs] = a_out
+            out[n + np.asarray(qs, dtype=np.int64)] = rate
+        elif status is not None:   # swap_out_
             out[qs], status[qs] = ctx.swap_out(L.seg_of[b], amt[qs], ci[qs], None if co is None else co[qs], rows,
                                                None if max_in is None else max_in[qs], True)
         else:
