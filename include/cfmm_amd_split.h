@@ -69,6 +69,10 @@ extern "C" {
  * supports a slice falls below the rounding of the outputs, an increment rounds to 0.0 and the order reports
  * CFMM_SPLIT_SATURATED though the paths could absorb it: one-path orders, whose remainder shrinks 63-fold per round, reach
  * that at 6 rounds; no order of the sample did at 5.
+ * Against 80-digit water-filling optima on orders of every pool family, single-family and mixed (tests/test_optimum_precise_cpu.py,
+ * profiles/optimum_precise.txt; 56 orders): worst shortfall 6.5e-7 at 5 rounds (an 8-path order of mixed families: the stall
+ * above, four times the product chains' 1.6e-7) and 2.4e-10 at 16; median 2e-14 at 5.  A path the optimum leaves empty gets +0.0
+ * through 5 rounds; at 16 rounds it can be handed a slice of noise (measured 3.4e-13), at most A*(K/63)^5.
  * The Python default is therefore rounds = 5.
  *   path_amount_in, path_amount_out   [n_paths]
  *   total_out, status                 [count]
