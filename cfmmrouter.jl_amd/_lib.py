@@ -23,6 +23,7 @@ ERR_STATE = -3
 ERR_UNSUPPORTED = -4
 MAX_PATH_HOPS = 8          # CFMM_MAX_PATH_HOPS
 PATH_APPLIED, PATH_BELOW_LIMIT, PATH_REFUSED = 0, 1, 2   # CFMM_PATH_*: Context.swap_path's status
+LIMIT_FILLED, LIMIT_PARTIAL, LIMIT_NONE, LIMIT_REFUSED = 0, 1, 2, 3   # CFMM_LIMIT_*: Context.swap_limit's status
 SWAP_APPLIED, SWAP_OVER_LIMIT, SWAP_REFUSED, SWAP_UNOBTAINABLE = 0, 1, 2, 3   # CFMM_SWAP_*: Context.swap_out's / swap_path_out's status
 FOUND, FOUND_NONE, FOUND_REPEATS = 0, 1, 2   # CFMM_FOUND*: Context.find_path's status
 SIZED, SIZED_NONE, SIZED_AT_LIMIT, SIZED_NAN = 0, 1, 2, 3   # CFMM_SIZED*: Context.size_path's status
@@ -157,6 +158,9 @@ def lib():
     L.cfmm_quote_path_out_dev.argtypes = [_ctx, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.cfmm_quote_rate.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
     L.cfmm_quote_rate_dev.argtypes = [_ctx, C.c_int32, C.c_int64] + [C.c_void_p] * 6
+    L.cfmm_quote_to_rate.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p]
+    L.cfmm_quote_to_rate_dev.argtypes = [_ctx, C.c_int32, C.c_int64] + [C.c_void_p] * 6
+    L.cfmm_swap_limit.argtypes = [_ctx, C.c_int32, C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _i32p]
     L.cfmm_quote_path_rate.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p]
     L.cfmm_quote_path_rate_dev.argtypes = [_ctx, C.c_int64, C.c_int32] + [C.c_void_p] * 10
     L.cfmm_find_path.argtypes = [_ctx, C.c_int64, C.c_int32, _i32p, _i32p, _f64p, _f64p, _i32p, _i32p, _i64p, _i32p, _i32p, _i32p]
@@ -624,6 +628,57 @@ class Context:
         may be 0 exactly then): asynchronous, unchecked -- a bad query gets NaN in both outputs."""
         self._check(self._L.cfmm_quote_rate_dev(self._h, int(seg), int(count), *(C.c_void_p(p or None) for p in (
             d_idx, d_coin_in, d_coin_out, d_amount_in, d_amount_out, d_rate))))
+
+    # -- price limits (cfmm_quote_to_rate / cfmm_swap_limit, include/cfmm_amd_limit.h): the inverse of quote_rate -------------
+    def quote_to_rate(self, seg: int, rate_limit, coin_in, coin_out=None, idx=None, want_out=True):
+        """(amount_in, amount_out) [count]: the amount of coin_in that brings the pool's marginal rate (quote_rate's) down to
+        rate_limit -- exactly +0.0 where the spot rate is already at or below it -- and what quote answers for that amount,
+        bit for bit.  quote's arguments and checks with the limit (finite, > 0) in the place of the amount.  Read-only.
+        want_out=False returns (amount_in, None)."""
+        lim = f64(rate_limit).reshape(-1)
+        n = lim.size
+        ci, co, ix = self._query_columns(coin_in, coin_out, idx, n)
+        amt, out = np.empty(n), (np.empty(n) if want_out else None)
+        self._check(self._L.cfmm_quote_to_rate(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(lim), ptr(amt), ptr(out)))
+        return amt, out
+
+    def quote_to_rate_dev(self, seg: int, count: int, d_rate_limit: int, d_coin_in: int, d_amount_in: int, d_amount_out: int = 0,
+                          d_coin_out: int = 0, d_idx: int = 0):
+        """cfmm_quote_to_rate_dev on device addresses, as quote_rate_dev (0 = NULL; d_amount_out may be 0): asynchronous,
+        unchecked -- a query with a bad row, coin or limit gets NaN in both outputs."""
+        self._check(self._L.cfmm_quote_to_rate_dev(self._h, int(seg), int(count), *(C.c_void_p(p or None) for p in (
+            d_idx, d_coin_in, d_coin_out, d_rate_limit, d_amount_in, d_amount_out))))
+
+    def swap_limit(self, seg: int, amount_in, rate_limit, coin_in, coin_out=None, idx=None):
+        """(amount_used, amount_out, status) [count]: swap's arguments and a limit on the marginal rate per swap (a scalar or
+        one per swap; 0.0: no limit).  The swaps are APPLIED in query order; swap q tenders min(amount_in, quote_to_rate's
+        answer on the pool as swaps 0 .. q-1 left it), and the answer and the new state are swap's for that amount.
+        amount_in may be +inf where the limit is > 0.  status: LIMIT_FILLED / LIMIT_PARTIAL / LIMIT_NONE / LIMIT_REFUSED.
+        A state change: earlier trades and outputs are invalidated."""
+        amt = f64(amount_in).reshape(-1)
+        n = amt.size
+        try:
+            lim = np.ascontiguousarray(np.broadcast_to(np.asarray(rate_limit, dtype=np.float64), (n,)))
+        except ValueError:
+            raise ArgumentError("rate_limit must be a scalar or have one entry per amount") from None
+        ci, co, ix = self._query_columns(coin_in, coin_out, idx, n)
+        used, out, st = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+        self._check(self._L.cfmm_swap_limit(self._h, int(seg), n, ptr(ix), ptr(ci), ptr(co), ptr(amt), ptr(lim), ptr(used), ptr(out), ptr(st)))
+        return used, out, st
+
+    @staticmethod
+    def _query_columns(coin_in, coin_out, idx, n):
+        bcast = lambda a: np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.int32).reshape(-1) if np.ndim(a) else
+                                                               np.int32(a), (n,)), dtype=np.int32)
+        try:
+            ci = bcast(coin_in)
+            co = None if coin_out is None else bcast(coin_out)
+        except ValueError:
+            raise ArgumentError("coin_in and coin_out must be scalars or have one entry per query") from None
+        ix = None if idx is None else np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+        if ix is not None and ix.size != n:
+            raise ArgumentError("idx must have one entry per query")
+        return ci, co, ix
 
     def quote_path_rate(self, n_hops, hop_seg, hop_row, hop_coin_in, hop_coin_out, amount_in, hops=False):
         """(amount_out, rate[, hop_out, hop_rate]): quote_path's answers bit for bit, every hop's rate at the amount entering

@@ -343,6 +343,8 @@ int cfmm_get_option(const cfmm_ctx* c, const char* key, int64_t* value)
     if (key && !std::strcmp(key, "quote_ns")) return quote_ns(const_cast<cfmm_ctx*>(c), value);
     // read-only, cfmm_quote_rate / cfmm_quote_path_rate and their _dev forms: the same of the latest call of any of the four
     if (key && !std::strcmp(key, "rate_ns")) return rate_ns(const_cast<cfmm_ctx*>(c), value);
+    // read-only, cfmm_quote_to_rate / cfmm_quote_to_rate_dev: the same of the latest call of either
+    if (key && !std::strcmp(key, "limit_ns")) return limit_ns(const_cast<cfmm_ctx*>(c), value);
     // read-only, cfmm_swap: the sum of the kernel spans of the latest call's waves timed under "time_kernels" (a parent: the
     // longest among the shards that call touched), and the number of that call's swaps that were not applied (NaN answers)
     if (key && !std::strcmp(key, "swap_ns")) { *value = c->swap.ns; return CFMM_OK; }

@@ -304,6 +304,15 @@ struct RateScratch {
     bool dev_timed = false;            // the latest timed call was a _dev entry: its span is read when asked for
 };
 
+// cfmm_quote_to_rate (abi_limit.cpp, to_rate_kernels.h): the query columns and the staging are QuoteScratch's (the limits travel
+// in its amounts); kept here: the device copy of the two answers per query and the span of the latest call's kernel.
+struct ToRateScratch {
+    DevBuf<double> out;                // [2][count] amount_in, amount_out
+    EventPairs ev;                     // option "time_kernels": {start, stop} of the latest call's kernel
+    int64_t ns = 0;                    // read-only option "limit_ns": that kernel's span
+    bool dev_timed = false;            // the latest timed call was the _dev entry: its span is read when asked for
+};
+
 // cfmm_swap and cfmm_swap_out (abi_swap.cpp, swap_kernels.h, swap_out_kernels.h; one scratch for both directions): the
 // device copies of one call's swaps -- in WAVE order (swap_waves.h) -- their answers, the UniV3 landing prices and the pinned
 // staging of all of them, grown on demand and kept for the next call -- proportional to the swaps of the largest call, never
@@ -313,7 +322,8 @@ struct SwapScratch {
     DevBuf<int32_t> coins;             // [2][count] coin_in, coin_out
     DevBuf<double> amt, out, price;    // [count]; price: UniV3 segments only
     DevBuf<double> limit;              // [count] cfmm_swap_out: max_amount_in, where given
-    DevBuf<int32_t> status;            // [count] cfmm_swap_out: CFMM_SWAP_*
+    DevBuf<int32_t> status;            // [count] cfmm_swap_out: CFMM_SWAP_*; cfmm_swap_limit: CFMM_LIMIT_*
+    DevBuf<double> used;               // [count] cfmm_swap_limit: amount_used
     DevBuf<int> left;                  // [1] a new reserve left the window of the fast arithmetic (update_two_coin's flag)
     PinnedBuf<unsigned long long> stage;   // 8-byte words: stage_layout.h SwapStage
     EventPairs ev;                     // option "time_kernels": {start, stop} per wave of the latest call
@@ -529,6 +539,7 @@ struct cfmm_ctx {
     cfmm::QuoteScratch quote;
     cfmm::PathScratch path;
     cfmm::RateScratch rate;
+    cfmm::ToRateScratch to_rate;
     cfmm::SwapScratch swap;
     cfmm::SwapPathScratch swap_path;
     cfmm::FindScratch find;
@@ -610,6 +621,8 @@ int check_quote_queries(cfmm_ctx* c, const char* who, const char* given_name, in
 
 // abi_rate.cpp
 int rate_ns(cfmm_ctx* c, int64_t* value);
+// abi_limit.cpp
+int limit_ns(cfmm_ctx* c, int64_t* value);
 
 // abi_update.cpp
 // cfmm_pools_set_prices' apply path on rows that are distinct, ascending and already checked (each price finite, > 0 and not

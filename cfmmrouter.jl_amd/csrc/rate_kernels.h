@@ -160,3 +160,5 @@ __global__ __launch_bounds__(BLOCK) void quote_path_rate_kernel(PathRateArgs r)
 }
 
 } // namespace cfmm
+
+#include "swap_limit_kernels.h"

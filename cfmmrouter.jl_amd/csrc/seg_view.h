@@ -18,6 +18,7 @@ namespace cfmm {
 struct Dir {
     bool exact_out;
     const char *who, *dev, *given;
+    bool rated = false;   // cfmm_swap_limit: an exact-input swap behind a limit on the marginal rate, with the amount used beside its answer
 };
 
 // {kind, m, coins per pool} of segment `seg` as the checks see it, on a single context or a parent (its own list); the

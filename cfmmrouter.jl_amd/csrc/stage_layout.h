@@ -52,7 +52,7 @@ struct RateStage {   // cfmm_quote_rate: QuoteStage's columns (amt: only where t
     RateStage(size_t n, bool has_amt, bool has_idx)
         : amt(l.add<double>(has_amt ? n : 0)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(2 * n)), idx(l.add<long long>(has_idx ? n : 0)) {}
 };
-struct SwapStage {   // cfmm_swap / cfmm_swap_out, the swaps in wave order; price: UniV3 segments, limit / status: cfmm_swap_out
+struct SwapStage {   // cfmm_swap / cfmm_swap_out / cfmm_swap_limit, the swaps in wave order; price: UniV3 segments, limit / status: cfmm_swap_out and cfmm_swap_limit
     StageLayout l;
     StageCol<double> amt;
     StageCol<int32_t> coins;    // [2][n]
@@ -61,10 +61,11 @@ struct SwapStage {   // cfmm_swap / cfmm_swap_out, the swaps in wave order; pric
     StageCol<double> limit;
     StageCol<int32_t> status;
     StageCol<int> left;         // [1] the window flag
-    SwapStage(size_t n, bool has_idx, bool univ3, bool has_limit, bool exact_out)
+    StageCol<double> used;      // cfmm_swap_limit: amount_used
+    SwapStage(size_t n, bool has_idx, bool univ3, bool has_limit, bool has_status, bool has_used = false)
         : amt(l.add<double>(n)), coins(l.add<int32_t>(2 * n)), out(l.add<double>(n)), price(l.add<double>(univ3 ? n : 0)),
-          idx(l.add<long long>(has_idx ? n : 0)), limit(l.add<double>(has_limit ? n : 0)), status(l.add<int32_t>(exact_out ? n : 0)),
-          left(l.add<int>(1)) {}
+          idx(l.add<long long>(has_idx ? n : 0)), limit(l.add<double>(has_limit ? n : 0)), status(l.add<int32_t>(has_status ? n : 0)),
+          left(l.add<int>(1)), used(l.add<double>(has_used ? n : 0)) {}
 };
 struct PathStage {   // cfmm_quote_path / cfmm_quote_path_out (the _dev entries: the table alone, n = 0)
     StageLayout l;

@@ -694,4 +694,24 @@ struct PathRateArgs {
 };
 hipError_t launch_quote_path_rate(const PathRateArgs& a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
+// cfmm_quote_to_rate / cfmm_quote_to_rate_dev (to_rate_kernels.h, abi_limit.cpp): the amount that brings the pool's marginal rate
+// down to a limit (to_rate_pool.h) and what it buys, one lane per query.  `q` is quote_kernel's view: q.amount_in carries the
+// LIMITS (the value given, as for the exact-output quotes), q.amount_out receives cfmm_quote's answer for the amount and may
+// be null.
+struct ToRateArgs {
+    QuoteArgs q;
+    double* amount;              // [count], never null: the amount in; NaN for a bad query
+};
+hipError_t launch_quote_to_rate(int kind, const ToRateArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                                hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// cfmm_swap_limit (swap_limit_kernels.h, abi_swap.cpp): swap_kernel behind a limit on the rate.  `o` is SwapOutArgs with its
+// fields re-read: o.max_in carries the RATE limits (never null here; +0.0: no limit for that swap), o.status receives kLimit*.
+constexpr int32_t kLimitFilled = 0, kLimitPartial = 1, kLimitNone = 2, kLimitRefused = 3;   // CFMM_LIMIT_* (include/cfmm_amd_limit.h)
+struct SwapLimitArgs {
+    SwapOutArgs o;
+    double* used;                // [count], never null: min(amount_in, the amount to the limit); NaN for a refused swap
+};
+hipError_t launch_swap_limit(int kind, const SwapLimitArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s,
+                             hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+
 } // namespace cfmm

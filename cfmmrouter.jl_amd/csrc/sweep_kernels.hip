@@ -54,6 +54,7 @@
 //                            find_out_ban_relax and its walk: cfmm_find_disjoint_paths_out, the same text in the other direction: the header includes its second half once per direction)
 //   split_paths_out_kernels.h  split_paths_out_kernel (cfmm_split_paths_out: a wanted amount bought through an order's paths, split_paths_kernel's shape, the hops walked backwards)
 //   swap_order_kernels.h  swap_order_kernel, swap_order_out_kernel (cfmm_swap_order, cfmm_swap_order_out: orders executed all or nothing across their paths, eight lanes per order)
+//   to_rate_kernels.h, swap_limit_kernels.h   to_rate_kernel, swap_limit_kernel (cfmm_quote_to_rate, cfmm_swap_limit: the amount that brings a pool's marginal rate down to a limit, and the swap that stops there; to_rate_pool.h: the per-kind inverses)
 //   rate_kernels.h    rate_kernel, quote_path_rate_kernel (cfmm_quote_rate, cfmm_quote_path_rate: the quote and its marginal rate from one read of the pool; rate_pool.h: the per-kind derivatives)
 // What is left here: the kernel table (the one enumeration of the sweep kernels) and the host launchers.
 
@@ -73,7 +74,7 @@
 #include "swap_kernels.h"
 #include "swap_path_kernels.h"
 #include "swap_out_kernels.h"
-#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h, and from that one's swap_order_kernels.h, and from that one's rate_kernels.h)
+#include "find_path_kernels.h"   // (and behind it, from its last line, size_path_kernels.h, from that one's split_paths_kernels.h, from that one's find_disjoint_kernels.h, and from that one's split_paths_out_kernels.h, and from that one's swap_order_kernels.h, and from that one's rate_kernels.h, and from that one's swap_limit_kernels.h, which includes to_rate_kernels.h)
 
 #include <hip/hip_ext.h>
 
@@ -397,6 +398,29 @@ hipError_t launch_quote_path_rate(const PathRateArgs& a, hipStream_t s, hipEvent
     return launch_quote_grid(path_rate_kernel(), a.p.count, args, s, e0, e1);
 }
 
+// cfmm_quote_to_rate and cfmm_swap_limit: launch_quote_rate's and launch_swap's rules and grids.  Their kernels are named at the
+// end of this file too (to_rate_kernel_of, swap_limit_kernel_of), behind the rate kernels, for the same reason.
+static const void* to_rate_kernel_of(int kind);
+static const void* swap_limit_kernel_of(int kind);
+
+hipError_t launch_quote_to_rate(int kind, const ToRateArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.q.count <= 0 || a.q.m <= 0 || !a.amount || !a.q.amount_in) return hipErrorInvalidValue;
+    const void* kernel = to_rate_kernel_of(kind);   // no such kernel: there is no falling through to another one
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    void* args[] = {const_cast<ToRateArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_quote_grid(kernel, a.q.count, args, s, e0, e1);
+}
+
+hipError_t launch_swap_limit(int kind, const SwapLimitArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
+{
+    if (a.o.s.q.count <= 0 || a.o.s.q.m <= 0 || !a.o.max_in || !a.o.status || !a.used) return hipErrorInvalidValue;
+    const void* kernel = swap_limit_kernel_of(kind);   // no such kernel: there is no falling through to another one
+    if (!kernel) return hipErrorInvalidDeviceFunction;
+    void* args[] = {const_cast<SwapLimitArgs*>(&a), const_cast<UniV3Pools*>(&u), const_cast<NCoinPools*>(&n)};
+    return launch_quote_grid(kernel, a.o.s.q.count, args, s, e0, e1);
+}
+
 // one lane per swap of the wave, the same grid rule
 hipError_t launch_swap(int kind, const SwapArgs& a, const UniV3Pools& u, const NCoinPools& n, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
@@ -576,5 +600,19 @@ static const void* rate_kernel_of(int kind)
     return kernel;
 }
 static const void* path_rate_kernel() { return reinterpret_cast<const void*>(&quote_path_rate_kernel<kQuoteBlock>); }
+
+// The kernels of launch_quote_to_rate and launch_swap_limit, named here and nowhere else, behind the rate kernels.
+static const void* to_rate_kernel_of(int kind)
+{
+    const void* kernel = nullptr;
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&to_rate_kernel<decltype(K)::value>); }, [] {});
+    return kernel;
+}
+static const void* swap_limit_kernel_of(int kind)
+{
+    const void* kernel = nullptr;
+    with_kind(kind, [&](auto K) { kernel = reinterpret_cast<const void*>(&swap_limit_kernel<decltype(K)::value>); }, [] {});
+    return kernel;
+}
 
 } // namespace cfmm

@@ -830,6 +830,90 @@ def swap_out_(r: Router, pools, coin_in, amount_out, coin_out=None, max_in=None,
         r._reset_trades()
 
 
+def _limit_queries(r: Router, pools, token_in, token_out, *columns):
+    """the single-pool limit calls' arguments: positions in `r.cfmms` and 1-based token ids (as in `Ai`) mapped to (batch, row,
+    coin positions) with the refusals of `quote` and of the path calls; columns: (name, values) broadcast to one entry per pool.
+    -> (n, {batch: (queries, rows)}, coin_in, coin_out, the columns)"""
+    L = r._layout
+    pools = np.asarray(pools, dtype=np.int64).reshape(-1)
+    n = pools.size
+    try:
+        ti = np.broadcast_to(np.asarray(token_in, dtype=np.int64), (n,))
+        to = np.broadcast_to(np.asarray(token_out, dtype=np.int64), (n,))
+        cols = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for _, v in columns]
+    except ValueError:
+        names = ", ".join(name for name, _ in columns)
+        raise ArgumentError(f"token_in, token_out, {names} must be scalars or have one entry per pool") from None
+    ci, co = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    per_batch = {}
+    for q, i in enumerate(pools.tolist()):
+        where = L.locate(i)
+        if where[0] == "host":
+            raise ArgumentError(f"pool {i}: {type(r._host.pools[where[1]]).__name__} is evaluated on the host by its own "
+                                f"find_arb_ and has no device state to quote")
+        Ai = L.batches[where[1]].Ai[where[2]]
+        pos = []
+        for t in (int(ti[q]), int(to[q])):
+            at = np.flatnonzero(Ai == t)
+            if at.size == 0:
+                raise ArgumentError(f"query {q}: token {t} is not a coin of pool {i} (its coins: {Ai.tolist()})")
+            pos.append(int(at[0]))
+        if pos[0] == pos[1]:
+            raise ArgumentError(f"query {q}: token {int(ti[q])} on both sides of pool {i}")
+        ci[q], co[q] = pos
+        qs, rows = per_batch.setdefault(where[1], ([], []))
+        qs.append(q)
+        rows.append(where[2])
+    if getattr(r._backend, "ctx", None) is None and per_batch:
+        raise NotImplementedError(f"{type(r._backend).__name__} has no device context to quote on")
+    return n, per_batch, ci, co, cols
+
+
+def amount_to_rate(r: Router, pools, token_in, token_out, rate):
+    """The inverse of `quote_rate` (cfmm_quote_to_rate): how much of token `token_in[q]` pool `pools[q]` takes before its
+    marginal rate -- units of `token_out[q]` per unit tendered, fee included -- has fallen to `rate[q]`, on the pools as they
+    stand on the device.  Returns (amount_in, amount_out): amount_in is exactly 0.0 where the spot rate is already at or
+    below the limit; amount_out is what `quote` answers for amount_in, bit for bit.  The rate the pool would rest at is the
+    limit to rounding and may lie an ulp-scale amount below it: a strict caller passes a margin.
+
+    `pools` are positions in `r.cfmms` (any order, repeats allowed); token_in / token_out are token ids, 1-based as in `Ai`
+    (scalars serve every query); rate must be finite and > 0.  ArgumentError for a token that is not one of the pool's coins or
+    is the same on both sides, and for a host-evaluated plugin pool.  Read-only, like `quote`."""
+    n, per_batch, ci, co, (lim,) = _limit_queries(r, pools, token_in, token_out, ("rate", rate))
+    ctx, L = r._backend.ctx if per_batch else None, r._layout
+    amt, out = np.empty(n), np.empty(n)
+    for b in sorted(per_batch):
+        qs, rows = per_batch[b]
+        amt[qs], out[qs] = ctx.quote_to_rate(L.seg_of[b], lim[qs], ci[qs], co[qs], rows)
+    return amt, out
+
+
+def swap_limit_(r: Router, pools, token_in, token_out, amount_in, rate_limit, sync_host=True):
+    """Price-limited swaps APPLIED to the pools on the device (cfmm_swap_limit): "sell up to amount_in[q] of token_in[q] into
+    pool pools[q], but stop where its marginal rate reaches rate_limit[q]".  Swap q tenders min(amount_in[q], what
+    `amount_to_rate` answers on the pool as the earlier swaps left it); the amount out and the pool's new state are `swap_`'s
+    for the amount used.  rate_limit 0.0 means no limit (the swap is `swap_`'s); amount_in may be inf -- "as much as it
+    takes" -- where the limit is > 0: that moves the pool to an outside price.
+
+    Returns (amount_used, amount_out, status) in the caller's order: LIMIT_FILLED (all of amount_in), LIMIT_PARTIAL (the pool
+    rests at the limit, to rounding), LIMIT_NONE (the spot rate is already at or below the limit, or amount_in is 0: nothing
+    moved) or LIMIT_REFUSED (the swap would leave an invalid pool: NaN, nothing moved).  Pools and tokens as `amount_to_rate`
+    takes them; order within a segment, sync_host and the zeroing of the router's trades are `swap_`'s."""
+    try:
+        n, per_batch, ci, co, (amt, lim) = _limit_queries(r, pools, token_in, token_out, ("amount_in", amount_in), ("rate_limit", rate_limit))
+        ctx, L = r._backend.ctx if per_batch else None, r._layout
+        used, out, status = np.empty(n), np.empty(n), np.empty(n, dtype=np.int32)
+        for b in sorted(per_batch):
+            qs, rows = per_batch[b]
+            used[qs], out[qs], status[qs] = ctx.swap_limit(L.seg_of[b], amt[qs], lim[qs], ci[qs], co[qs], rows)
+            if sync_host:
+                _download_state(ctx, L.seg_of[b], L.batches[b])
+                L.sync_pools(r.cfmms, b, sorted(set(rows)))
+        return used, out, status
+    finally:
+        r._reset_trades()
+
+
 def _quote(r: Router, verb, pools, coin_in, amount, coin_out, sync_host=False, max_in=None, status=None, answers=1):
     """answers=2 (quote_rate): the context returns (amount_out, rate) and the result is [2n], the rates behind the amounts;
     amount=None there: no amounts (the spot rate), the first half stays NaN"""

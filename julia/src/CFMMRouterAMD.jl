@@ -20,7 +20,7 @@ using CFMMRouter: CFMM, ProductTwoCoin, GeometricMeanTwoCoin, UniV3, Objective, 
 using LBFGSB
 import CFMMRouter: route!, netflows, netflows!, find_arb!, update_reserves!, forward_trade
 
-export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, swap_out!, swap_paths_out!, find_paths, find_paths_out, size_paths, split_paths, find_disjoint_paths, split_paths_out, find_disjoint_paths_out, swap_orders!, swap_orders_out!, quote_rate, spot_price, quote_path_rate, forward_trade, backward_trade, SolidlyStableTwoCoin
+export AMDRouter, route_native!, polish!, update_pools!, swap!, select_trades, quote_swaps, quote_swaps_out, quote_paths, quote_paths_out, swap_paths!, swap_out!, swap_paths_out!, find_paths, find_paths_out, size_paths, split_paths, find_disjoint_paths, split_paths_out, find_disjoint_paths_out, swap_orders!, swap_orders_out!, quote_rate, spot_price, quote_path_rate, amount_to_rate, swap_limit!, forward_trade, backward_trade, SolidlyStableTwoCoin
 
 const LIB = get(ENV, "CFMM_AMD_LIB", "libcfmm_amd.so")
 
@@ -743,6 +743,7 @@ include("find_disjoint_paths.jl")   # find_disjoint_paths (cfmm_find_disjoint_pa
 include("split_paths_out.jl")      # split_paths_out (cfmm_split_paths_out, declared in include/cfmm_amd_split_out.h)
 include("find_disjoint_paths_out.jl")   # find_disjoint_paths_out (cfmm_find_disjoint_paths_out, declared in include/cfmm_amd_find_disjoint_out.h)
 include("quote_rate.jl")      # quote_rate, spot_price, quote_path_rate (cfmm_quote_rate, cfmm_quote_path_rate, declared in include/cfmm_amd_rate.h)
+include("quote_to_rate.jl")   # amount_to_rate, swap_limit! (cfmm_quote_to_rate, cfmm_swap_limit, declared in include/cfmm_amd_limit.h)
 include("swap_order.jl")      # swap_orders!, swap_orders_out! (cfmm_swap_order, cfmm_swap_order_out, declared in include/cfmm_amd_order.h)
 
 # forward_trade(Δ, cfmm) -- src/cfmms.jl:436-449: methods of CFMMRouter's own function (imported above) for the pool kinds it
